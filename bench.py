@@ -25,6 +25,9 @@ Rank 0 prints ONE JSON line.
                 ns/(nz*column) and labelled so; plus the reference-faithful tocsr()+dot of one tiled layer (keynet/sparse.py:603-612).
   parity        this run's own gate: logits of the timed batch's first images against the source network in plain torch f32
                 (the reference's criterion, atol 1e-3); a run that fails it raises instead of printing a number.
+
+--dump-outputs DIR writes the logits of the last timed step to DIR/logits.npy (float32): the same arguments give the same inputs on every
+run, so two builds can be compared output for output.
 """
 import argparse
 import json
@@ -75,6 +78,23 @@ def spawn_ranks(args):
     return subprocess.call(cmd, env=env)
 
 
+DUMP_LIMIT_BYTES = 64 << 20
+
+
+def dump_outputs(out, directory):
+    """--dump-outputs: the timed step's result as DIR/logits.npy (float32).  A result larger than DUMP_LIMIT_BYTES is cut to a sample of whole rows drawn
+    with a fixed seed (the same rows on every run of the same arguments), kept in their original order."""
+    import numpy as np
+    y = out.detach().float().contiguous().cpu().numpy()
+    if y.nbytes > DUMP_LIMIT_BYTES:
+        keep = max(1, DUMP_LIMIT_BYTES // max(1, y.itemsize * (y.size // y.shape[0])))
+        y = y[np.sort(np.random.RandomState(0).choice(y.shape[0], keep, replace=False))]
+    os.makedirs(directory, exist_ok=True)
+    path = os.path.join(directory, 'logits.npy')
+    np.save(path, y)
+    log('[bench] logits of the last timed step %s written to %s' % (tuple(y.shape), path))
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument('--gpus', type=int, default=1)
@@ -103,7 +123,11 @@ def main():
     ap.add_argument('--pmc-forward', default=None, metavar='FILE', help='profiling aid (run under rocprofv3 --kernel-trace --pmc <counter>): behind the calibrating forward and two warm ones, launch '
                                                                         'EXACTLY ONE forward_linear -- the timed step\'s launches, nothing else -- between two marker kernels, write FILE and exit; '
                                                                         'tools/pmc_forward.py sums the counter over the launches between the markers (`roofline.traffic`: ONE definition)')
+    ap.add_argument('--dump-outputs', default=None, metavar='DIR', help='after the timed steps, write what the last timed step returned (the logits, gathered over the ranks) to DIR/logits.npy '
+                                                                         'as float32; above %d MB a fixed, seeded sample of whole rows in their original order' % (DUMP_LIMIT_BYTES >> 20))
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error('--steps must be at least 1')
 
     world = int(os.environ.get('WORLD_SIZE', '1'))
     if args.gpus > 1 and 'WORLD_SIZE' not in os.environ:
@@ -265,6 +289,8 @@ def main():
 
     (elapsed, out) = timed(args.warmup, args.steps)
     assert out.shape[0] == batch * world and bool(torch.isfinite(out).all())
+    if args.dump_outputs and rank == 0:
+        dump_outputs(out, args.dump_outputs)
     parity = None
     if rank == 0:
         err = float((out[:n_gate].contiguous().cpu() - y_plain).abs().max())   # contiguous first: a strided D2H copy is ~1500 tiny copies

@@ -20,6 +20,8 @@ Fixtures:
   F8 mini_tiled_stochastic.npz  MiniNet (2,16,16) under the key family of test/test_keynet.py:116-129 (test_vgg16_stochastic:
                          hierarchical permutation + doubly-stochastic local keys + uniform random affine): FILLED-IN operators
                          (keynet/sparse.py:335-353 keys, SpGEMM fill-in at keynet/layer.py:35), blocks/tiles dumps, CSR, I/O
+  F9 generator_cases.npz  the reference's key generators on the randomised case sequence of diff_generators.py: stored CSR triplets,
+                         dense results, and the next np.random.rand() after each seeded call (RNG consumption)
 """
 import os
 import sys
@@ -499,14 +501,34 @@ def f6():
     return save('keygen_cases.npz', out, manifest)
 
 
+def f9():
+    """diff_generators.run on the reference's generators (keynet/sparse.py, keynet/blockpermute.py)."""
+    import types
+    import warnings
+    import keynet.blockpermute
+    import diff_generators
+    S = keynet.sparse
+    api = types.SimpleNamespace(givens_orthogonal=S.sparse_orthogonal_matrix,
+                                diagonally_dominant_doubly_stochastic=S.sparse_random_diagonally_dominant_doubly_stochastic_matrix,
+                                hierarchical_block_permute=keynet.blockpermute.hierarchical_block_permute,
+                                hierarchical_block_permutation_matrix=keynet.blockpermute.hierarchical_block_permutation_matrix,
+                                diagonal_affine_to_linear=S.diagonal_affine_to_linear, sparse_affine_to_linear=S.sparse_affine_to_linear,
+                                sparse_permutation_matrix=S.sparse_permutation_matrix, DiagonalTiledMatrix=S.DiagonalTiledMatrix)
+    with warnings.catch_warnings():
+        warnings.simplefilter('ignore')
+        out = diff_generators.run(api)
+    assert not diff_generators.mismatches(out, diff_generators.run(api)), 'the case sequence is not deterministic'
+    return save('generator_cases.npz', out, {'keys': len(out), 'functions': list(diff_generators.FUNCTIONS), 'recipe': 'diff_generators.run(reference generators)'})
+
+
 if __name__ == '__main__':
     os.chdir('/tmp')
-    which = sys.argv[1:] or ['f1', 'f2', 'f3', 'f4', 'f5', 'f6', 'f7', 'f8']
+    which = sys.argv[1:] or ['f1', 'f2', 'f3', 'f4', 'f5', 'f6', 'f7', 'f8', 'f9']
     mf = os.path.join(HERE, 'MANIFEST.json')
     manifest = json.load(open(mf)) if os.path.exists(mf) else {}
     manifest['_versions'] = {'numpy': np.__version__, 'scipy': scipy.__version__, 'torch': torch.__version__, 'python': sys.version.split()[0]}
     for w in which:
-        r = {'f1': f1, 'f2': f2, 'f3': f3, 'f4': f4, 'f5': f5, 'f6': f6, 'f7': f7, 'f8': f8}[w]()
+        r = {'f1': f1, 'f2': f2, 'f3': f3, 'f4': f4, 'f5': f5, 'f6': f6, 'f7': f7, 'f8': f8, 'f9': f9}[w]()
         manifest[w] = r
     with open(mf, 'w') as f:
         json.dump(manifest, f, indent=1, sort_keys=True)

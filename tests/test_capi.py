@@ -56,19 +56,6 @@ def test_product_never_imports_oracle():
                 assert 'kn_oracle' not in src, f
 
 
-import pytest  # noqa: E402
-
-
-@pytest.mark.skipif(not os.path.isdir('/root/reference'), reason='the reference is only mounted in the build container')
-def test_integration_md_stub_is_real_code():
-    """INTEGRATION.md's `keynet/hip.py` is extracted and run against the reference's own classes (tests/golden/check_integration_stub.py)."""
-    import subprocess
-    import sys
-    p = subprocess.run([sys.executable, os.path.join(os.path.dirname(os.path.abspath(__file__)), 'golden', 'check_integration_stub.py')],
-                       capture_output=True, text=True, timeout=600)
-    assert p.returncode == 0 and 'STUB OK' in p.stdout, (p.stdout[-1000:], p.stderr[-3000:])
-
-
 def test_no_cpp_exception_crosses_the_c_abi():
     """include/keynet_hip.h promises integer codes only.  Sizes that cannot be allocated (a host std::vector of 2^60 elements throws
     std::length_error / std::bad_alloc inside the create function) and sizes that contradict the arrays must come back as codes with a

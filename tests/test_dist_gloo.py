@@ -16,7 +16,7 @@ def test_sharded_forward_equals_single_process(n):
 
 def test_sharded_forward_on_eight_ranks_ragged():
     """BASELINE configs[4] is an 8-rank job: eight gloo processes, a ragged total of 61 rows (shards of 8 and 7), gathered logits bit-equal to the
-    single-process forward on every rank, rank-major, one all_gather_into_tensor per forward (tests/test_dist_gpu.py: the same with the real kernels)."""
+    single-process forward on every rank, rank-major, one all_gather_into_tensor per forward (tests/test_dist_gpu.py: the same on four ranks with the real kernels)."""
     n = 61
     res = dist_harness.run('standin', n, world_size=8)
     assert [r[0] for r in res] == list(range(8)) and all(r[1] for r in res)

@@ -36,40 +36,48 @@ def test_one_ranks_data_trips_the_contract_for_all():
     assert own0 and own1 and peer0 and peer1, res
 
 
+# The one-GPU rehearsals of a multi-rank job run RANKS ranks.  Every rank and this test process hold the device open at once: eight ranks made nine
+# such processes, more than the GPU machines that run this tier admit (six), and the tier was stopped there.  RANKS + 1 = 5 stays within it.  The
+# 8-rank control flow without the kernels runs on CPU: 8-way ragged shards (tests/test_dist_gloo.py), rank 0 keying for seven loaders
+# (tests/test_shared_keying_gloo.py), the 8-rank bench line (tests/test_bench_line.py).
+RANKS = 4
+
+
 @pytest.mark.parametrize('kind', ['lenet', 'tiled'])
-def test_real_keynet_sharded_over_eight_ranks_ragged(kind):
-    """BASELINE configs[4] is an 8-rank job: the first 8-GPU run must not be the first 8-rank run.  Eight processes share cuda:0 (gloo), a
-    ragged total of 250 images (shards of 32 and 31), the real key-nets: every rank's gathered block equals the single-process forward
+def test_real_keynet_sharded_over_four_ranks_ragged(kind):
+    """BASELINE configs[4] is an 8-rank job: the first 8-GPU run must not be the first multi-rank run with the real kernels.  Four processes share cuda:0 (gloo), a
+    ragged total of 250 images (shards of 63 and 62), the real key-nets: every rank's gathered block equals the single-process forward
     of the whole batch bit for bit, the shard bounds tile [0, 250) in rank order, one collective per forward."""
     n = 250
-    res = dist_harness.run(kind, n, world_size=8, timeout=600)
-    assert [r[0] for r in res] == list(range(8)) and all(r[1] for r in res), res
+    res = dist_harness.run(kind, n, world_size=RANKS, timeout=600)
+    assert [r[0] for r in res] == list(range(RANKS)) and all(r[1] for r in res), res
     bounds = [r[2] for r in res]
-    assert bounds[0][0] == 0 and bounds[-1][1] == n and all(bounds[k][1] == bounds[k + 1][0] for k in range(7))
-    assert sorted(set(hi - lo for (lo, hi) in bounds)) == [31, 32]
+    assert bounds[0][0] == 0 and bounds[-1][1] == n and all(bounds[k][1] == bounds[k + 1][0] for k in range(RANKS - 1))
+    assert sorted(set(hi - lo for (lo, hi) in bounds)) == [62, 63]
     assert all(r[3][0] == n and r[4].startswith('cuda') and r[5] == 'gloo' for r in res)
     assert all(len(r[6]) == 1 for r in res), [r[6] for r in res]          # ONE all_gather_into_tensor per sharded forward, nothing else on the data path
 
 
-def test_one_ranks_data_trips_the_contract_for_all_eight():
-    """The 'auto' contract on eight ranks: only the last rank's images (300x larger) can trip a tolerance screen; after sharded_forward ALL
-    eight run every layer under the same contract, own and peer shards are bit-equal on recompute."""
-    res = dist_harness.run_contract('device', world_size=8, timeout=600)
+def test_one_ranks_data_trips_the_contract_for_all_four():
+    """The 'auto' contract on four ranks: only the last rank's images (300x larger) can trip a tolerance screen; after sharded_forward ALL
+    four run every layer under the same contract, own and peer shards are bit-equal on recompute."""
+    res = dist_harness.run_contract('device', world_size=RANKS, timeout=600)
+    assert [r[0] for r in res] == list(range(RANKS)), res
     states = [r[1] for r in res]
     assert all(st == states[0] for st in states), states
     assert all(v in (True, False) for v in states[0].values())
     assert all(r[2] and r[3] for r in res), res
 
 
-def test_bench_eight_ranks_on_one_gpu():
-    """`python bench.py --gpus 8` as the driver's multi-GPU tier starts it (its own ranks through torch.distributed.run), on a shared GPU with
-    gloo: the control flow of cfg5 -- 8 keyings, 8 uploads, the 8-way gather, max-over-ranks timing, the 8-rank compact line -- on a real box."""
+def test_bench_four_ranks_on_one_gpu():
+    """`python bench.py --gpus 4` as the driver's multi-GPU tier starts it (its own ranks through torch.distributed.run), on a shared GPU with
+    gloo: the control flow of cfg5 -- one keying per rank, one upload per rank, the N-way gather, max-over-ranks timing, the N-rank compact line -- on a real box."""
     import time
     env = dict(os.environ, KN_BENCH_SHARE_GPU='1')
     env.pop('WORLD_SIZE', None)
     env.pop('RANK', None)
     t0 = time.time()
-    p = subprocess.run([sys.executable, os.path.join(ROOT, 'bench.py'), '--gpus', '8', '--workload', 'lenet', '--steps', '3', '--warmup', '1', '--layer-iters', '1'],
+    p = subprocess.run([sys.executable, os.path.join(ROOT, 'bench.py'), '--gpus', str(RANKS), '--workload', 'lenet', '--steps', '3', '--warmup', '1', '--layer-iters', '1'],
                        env=env, capture_output=True, text=True, timeout=900)
     wall = time.time() - t0
     assert p.returncode == 0, p.stderr[-3000:]
@@ -77,9 +85,9 @@ def test_bench_eight_ranks_on_one_gpu():
     assert len(lines) == 1 and len(lines[0]) < 4096, (len(lines), [len(l) for l in lines])
     r = json.loads(lines[0])
     c = r['collective']
-    assert r['n_gpus'] == 8 and r['config']['global_batch'] == 8 * r['config']['images_per_gpu'] and r['value'] > 0 and r['parity']['ok']
-    assert c['ranks_seen'] == 8 and sorted(x[0] for x in c['ranks']) == list(range(8))
-    assert c['every_rank_shard_bit_equal_to_its_local_forward'] is True and c['peer_shard_recomputed_on_rank0'] == {'peer_rank': 7, 'bit_equal': True}
+    assert r['n_gpus'] == RANKS and r['config']['global_batch'] == RANKS * r['config']['images_per_gpu'] and r['value'] > 0 and r['parity']['ok']
+    assert c['ranks_seen'] == RANKS and sorted(x[0] for x in c['ranks']) == list(range(RANKS))
+    assert c['every_rank_shard_bit_equal_to_its_local_forward'] is True and c['peer_shard_recomputed_on_rank0'] == {'peer_rank': RANKS - 1, 'bit_equal': True}
     assert r['scaling'] == 'weak' and 'N=1' in json.dumps(r.get('cpu_baseline'))
     assert wall < 120, wall
 
@@ -109,25 +117,25 @@ def _shm_archives():
     return sorted(n for n in os.listdir('/dev/shm') if n.startswith('keynet_bench')) if os.path.isdir('/dev/shm') else []
 
 
-def test_bench_eight_ranks_share_one_keying_of_a_tiled_vgg():
+def test_bench_four_ranks_share_one_keying_of_a_tiled_vgg():
     """cfg5's control flow with cfg5's KIND of key-net (21 keyed layers of VGG-16, tiled conv operators; reduced width so that the tier stays short -- the full-size
-    8-rank run is profiles/r06_vgg16_bench_8ranks_one_gpu.json): rank 0 keys ONCE, seven ranks load its anonymous archive (benchlegs/shared.py), every rank uploads and
+    8-rank run is profiles/r06_vgg16_bench_8ranks_one_gpu.json): rank 0 keys ONCE, the other ranks load its anonymous archive (benchlegs/shared.py), every rank uploads and
     runs its shard on the matrix cores under the calibrated contract, one all-gather per step.  The line validates itself: backend, ranks seen, bytes gathered per rank,
     the gather's own time, slowest / fastest rank, every shard bit-equal to its rank's local forward and the LAST rank's shard recomputed on rank 0 bit-equal
     (= loaded operators == keyed operators)."""
     before = _shm_archives()
-    p = _bench(['--gpus', '8', '--workload', 'vgg16-slice', '--batch', '16', '--steps', '2', '--warmup', '1', '--layer-iters', '1', '--no-cpu-baseline'])
+    p = _bench(['--gpus', str(RANKS), '--workload', 'vgg16-slice', '--batch', '16', '--steps', '2', '--warmup', '1', '--layer-iters', '1', '--no-cpu-baseline'])
     assert p.returncode == 0, p.stderr[-3000:]
     lines = [l for l in p.stdout.splitlines() if l.startswith('{')]
     assert len(lines) == 1 and len(lines[0]) < 4096
     r = json.loads(lines[0])
     c = r['collective']
-    assert r['n_gpus'] == 8 and r['config']['global_batch'] == 128 and r['value'] > 0 and r['parity']['ok'] and r['scaling'] == 'weak'
-    assert c['backend'] == 'gloo' and c['ranks_seen'] == 8 and sorted(x[0] for x in c['ranks']) == list(range(8))
+    assert r['n_gpus'] == RANKS and r['config']['global_batch'] == 16 * RANKS and r['value'] > 0 and r['parity']['ok'] and r['scaling'] == 'weak'
+    assert c['backend'] == 'gloo' and c['ranks_seen'] == RANKS and sorted(x[0] for x in c['ranks']) == list(range(RANKS))
     assert c['bytes_per_rank'] == 16 * 10 * 4 and c['gather_ms'] > 0
     assert 0 < c['rank_images_per_s']['min'] <= c['rank_images_per_s']['max']
-    assert c['every_rank_shard_bit_equal_to_its_local_forward'] is True and c['peer_shard_recomputed_on_rank0'] == {'peer_rank': 7, 'bit_equal': True}
-    assert p.stderr.count('loaded rank 0\'s keyed net') == 7 and 'keying locally' not in p.stderr      # seven loaders, nobody fell back to its own keying
+    assert c['every_rank_shard_bit_equal_to_its_local_forward'] is True and c['peer_shard_recomputed_on_rank0'] == {'peer_rank': RANKS - 1, 'bit_equal': True}
+    assert p.stderr.count('loaded rank 0\'s keyed net') == RANKS - 1 and 'keying locally' not in p.stderr      # every other rank a loader, nobody fell back to its own keying
     assert _shm_archives() == before
 
 
@@ -137,7 +145,7 @@ def test_bench_rank_dying_before_the_barrier_fails_the_job_and_leaves_no_archive
     import time
     before = _shm_archives()
     t0 = time.time()
-    p = _bench(['--gpus', '4', '--workload', 'vgg16-slice', '--batch', '8', '--steps', '1', '--warmup', '0', '--layer-iters', '1', '--no-cpu-baseline'],
+    p = _bench(['--gpus', str(RANKS), '--workload', 'vgg16-slice', '--batch', '8', '--steps', '1', '--warmup', '0', '--layer-iters', '1', '--no-cpu-baseline'],
                extra_env={'KN_BENCH_TEST_DIE_BEFORE_BARRIER': '2'}, timeout=600)
     assert p.returncode != 0
     assert not [l for l in p.stdout.splitlines() if l.startswith('{')]

@@ -85,12 +85,21 @@ def test_hierarchical_permutation_matrix_is_the_image_permutation():
         assert not np.array_equal(ref, img)
 
 
-@pytest.mark.skipif(not os.path.isdir('/root/reference'), reason='the reference is only mounted in the build container')
-def test_generators_against_reference_randomised():
-    """tests/golden/diff_generators.py: every rewritten generator against the reference itself on randomised arguments (same seed
-    -> same matrix, same stored triplets, same RNG consumption).  Runs in a subprocess: importing the reference needs stand-ins for
-    third-party packages that must not leak into this process."""
-    import subprocess
-    p = subprocess.run([sys.executable, os.path.join(os.path.dirname(os.path.abspath(__file__)), 'golden', 'diff_generators.py')],
-                       capture_output=True, text=True, timeout=900)
-    assert p.returncode == 0 and 'ALL OK' in p.stdout, (p.stdout[-1500:], p.stderr[-3000:])
+def test_generators_against_reference_randomised(golden):
+    """tests/golden/diff_generators.py: every rewritten generator on the randomised argument sequence whose results from the reference
+    itself are stored in generator_cases.npz (make_golden.py f9): same seed -> same matrix, same stored triplets, same RNG consumption."""
+    import types
+    import diff_generators
+    from keynet_amd import keys as kk
+    from keynet_amd import sparse as ks
+    api = types.SimpleNamespace(givens_orthogonal=kk.givens_orthogonal, diagonally_dominant_doubly_stochastic=kk.diagonally_dominant_doubly_stochastic,
+                                hierarchical_block_permute=kk.hierarchical_block_permute, hierarchical_block_permutation_matrix=kk.hierarchical_block_permutation_matrix,
+                                diagonal_affine_to_linear=kk.diagonal_affine_to_linear, sparse_affine_to_linear=ks.sparse_affine_to_linear,
+                                sparse_permutation_matrix=ks.sparse_permutation_matrix, DiagonalTiledMatrix=ks.DiagonalTiledMatrix)
+    with warnings.catch_warnings():
+        warnings.simplefilter('ignore')
+        own = diff_generators.run(api)
+    z = golden('generator_cases.npz')
+    assert len(z.files) == len(own) > 700
+    bad = diff_generators.mismatches({k: z[k] for k in z.files}, own)
+    assert not bad, bad[:20]

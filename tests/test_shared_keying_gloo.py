@@ -119,3 +119,17 @@ def test_a_loader_dying_before_the_barrier_leaves_nothing_behind():
         p.join(60)
     assert all(p.exitcode not in (0, None) for p in procs), [p.exitcode for p in procs]
     assert _shm_names() == before
+
+
+def test_seven_loaders_get_rank0s_keynet_on_eight_ranks():
+    """BASELINE configs[4]'s rank count: rank 0 keys once and SEVEN loaders re-open its anonymous archive; every replica holds the same operators."""
+    before = _shm_names()
+    (procs, q) = _run(8, 'normal')
+    res = sorted(q.get(timeout=600) for _ in procs)
+    for p in procs:
+        p.join(120)
+    assert [p.exitcode for p in procs] == [0] * 8
+    assert [r[0] for r in res] == list(range(8)) and [r[1] for r in res] == ['ok'] * 8
+    assert len(set(r[2] for r in res)) == 1, 'replicas do not hold the same keys'
+    assert [r[5] for r in res] == [True] + [False] * 7                                    # seven loaders: only rank 0 keeps the source network
+    assert all(r[6] == [] for r in res) and _shm_names() == before
