@@ -11,7 +11,9 @@ Random-init weights (torch.manual_seed(0)), keys from np.random.seed(0), images 
 checkpoints or datasets).  With N GPUs every rank runs its own 256-image shard (weak scaling, no collective inside the
 forward) and the step ends with ONE RCCL all-gather of the logits.
 
-Rank 0 prints ONE JSON line.
+Rank 0 prints ONE JSON line.  A plain run does only what its headline needs: it keys the workload, uploads it (the first forward), warms up, times
+the steps, writes --dump-outputs and prints `metric`, `value`, `unit`, `higher_is_better`, `dtype`, `ms_per_step` and the run's configuration.  Everything
+else it can measure or check runs with --full, which adds to the line:
   roofline      the dominant kernel of the mode that ran: convtaps_mfma_kernel against the f32-MFMA peak (tolerance mode of the
                 tiled key-nets), the order-preserving kernels against the no-FMA VALU peak (--exact, AllConvNet), the CSR kernels
                 against HBM (LeNet).  `traffic` (HBM bytes per forward of that kernel from a separate rocprofv3 --pmc pass) is
@@ -23,8 +25,10 @@ Rank 0 prints ONE JSON line.
                 host cores BEFORE the GPU is touched (the worker pool is forked from a GPU-free process): conv1_1, conv5_1, every
                 pool, fc6-8 measured directly on 1 thread and on all physical cores; the other layers extrapolated at the measured
                 ns/(nz*column) and labelled so; plus the reference-faithful tocsr()+dot of one tiled layer (keynet/sparse.py:603-612).
-  parity        this run's own gate: logits of the timed batch's first images against the source network in plain torch f32
+  parity        the run's own gate: logits of the timed batch's first images against the source network in plain torch f32
                 (the reference's criterion, atol 1e-3); a run that fails it raises instead of printing a number.
+  secondary, contract, end_to_end, collective (N > 1), oracle_parity (LeNet, AllConvNet) and the opt-in legs (--graph-leg, --experimental,
+                --exact-layers-parity): benchlegs/.
 
 --dump-outputs DIR writes the logits of the last timed step to DIR/logits.npy (float32): the same arguments give the same inputs on every
 run, so two builds can be compared output for output.
@@ -36,6 +40,7 @@ import os
 import subprocess
 import sys
 import time
+T_START = time.time()                          # (before torch is imported: the wall-time log line at the end counts from here)
 
 import torch
 import torch.distributed as dist
@@ -49,6 +54,7 @@ from keynet_amd import dist as kdist           # noqa: E402
 # what the timed path below calls; everything else lives in benchlegs/
 from benchlegs.common import log, kernel_sources_sha                                                                    # noqa: E402
 from benchlegs.shared import build_workload_shared                                                                      # noqa: E402
+from benchlegs.workloads import upload_operators                                                                        # noqa: E402
 from benchlegs.cpu import cpu_baseline                                                                                  # noqa: E402
 from benchlegs.layers import layer_table, time_layers, roofline_of, chain_roofline                                      # noqa: E402
 from benchlegs.parity import oracle_parity_csr                                                                          # noqa: E402
@@ -125,9 +131,14 @@ def main():
                                                                         'tools/pmc_forward.py sums the counter over the launches between the markers (`roofline.traffic`: ONE definition)')
     ap.add_argument('--dump-outputs', default=None, metavar='DIR', help='after the timed steps, write what the last timed step returned (the logits, gathered over the ranks) to DIR/logits.npy '
                                                                          'as float32; above %d MB a fixed, seeded sample of whole rows in their original order' % (DUMP_LIMIT_BYTES >> 20))
+    ap.add_argument('--full', action='store_true', help='everything beyond the headline: parity gate, scipy baseline, per-layer roofline, LeNet / AllConvNet children, '
+                                                        'the bit-exact leg and the other side legs, the N > 1 collective record (a plain run keys, uploads, warms up, times and prints)')
     args = ap.parse_args()
     if args.steps < 1:
         ap.error('--steps must be at least 1')
+    for (flag, on) in (('--graph-leg', args.graph_leg), ('--experimental', args.experimental), ('--exact-layers-parity', args.exact_layers_parity)):
+        if on and not args.full:
+            ap.error('%s is a leg of the full run: add --full' % flag)
 
     world = int(os.environ.get('WORLD_SIZE', '1'))
     if args.gpus > 1 and 'WORLD_SIZE' not in os.environ:
@@ -141,7 +152,7 @@ def main():
     local_rank = int(os.environ.get('LOCAL_RANK', '0'))
 
     secondary = None
-    if args.workload == 'vgg16' and world == 1 and not args.no_secondary and not args.exact and not args.dist and args.batch is None:
+    if args.full and args.workload == 'vgg16' and world == 1 and not args.no_secondary and not args.exact and not args.dist and args.batch is None:
         secondary = run_secondary(args)                   # children own the GPU one after the other; this process has not touched it yet
 
     # Test-only override (single-GPU boxes): KN_BENCH_SHARE_GPU=1 puts every rank on cuda:0 and uses gloo, so the N>1 control flow (shared keying, sharding,
@@ -175,12 +186,16 @@ def main():
         torch.cuda.set_device(local_rank)
         init_dist()
 
-    # ---- host phase: keying and the CPU baseline; at N = 1 nothing below touches the GPU until "device phase" -------------
+    # ---- host phase: keying and the CPU baseline; with the baseline, nothing below touches the GPU until "device phase" -------
     # Arithmetic contract of the headline: BASELINE configs[3] names "MFMA dense sub-tiles", so the tiled VGG-16 key-nets are built with the
     # 'auto' contract EXPLICITLY (matrix cores wherever the 1e-5 tolerance holds, screened on every forward); a permutation-only tiled key-net's
     # own default is the bit-exact contract, which the `exact` leg of the same line measures on the same key-net.
+    # One rank keys its pooling layers in processes of their own (benchlegs/workloads.py: the same key-net, sooner), and unless the scipy baseline forks its workers
+    # after the keying, the operators of the layers keyed first go to the GPU while those are still being keyed.
+    cpu_leg = args.full and world == 1 and not args.no_cpu_baseline and args.workload in ('vgg16', 'lenet', 'allconv')    # (the configs BASELINE.json quotes)
     t_key = time.time()
-    (sensor, knet, inshape, batch, desc, net) = build_workload_shared(args.workload, rank, world, exact=True if args.exact else ('auto' if args.workload.startswith('vgg16') else None))
+    (sensor, knet, inshape, batch, desc, net) = build_workload_shared(args.workload, rank, world, exact=True if args.exact else ('auto' if args.workload.startswith('vgg16') else None),
+                                                                      fanout=world == 1, prepare=upload_operators(dev) if (world == 1 and not cpu_leg) else None)
     t_key = time.time() - t_key
     mode = 'exact' if (args.exact or not args.workload.startswith('vgg16')) else 'tolerance'
     mode_desc = {'exact': 'exact: order-preserving kernels, bit-exact with the reference (the default of permutation-only key-nets)',
@@ -190,7 +205,7 @@ def main():
         desc += ' [exact mode: order-preserving kernels, bit-exact with the reference algorithm]'
     batch = args.batch if args.batch is not None else batch
     cpu = None
-    if world == 1 and not args.no_cpu_baseline and args.workload in ('vgg16', 'lenet', 'allconv'):      # (the scipy baseline is measured on the configs BASELINE.json quotes)
+    if cpu_leg:
         t0 = time.time()
         cpu = cpu_baseline(knet, args.workload, budget_s=args.cpu_budget)
         log('[bench cpu] baseline section took %.1f s' % (time.time() - t0))
@@ -209,7 +224,7 @@ def main():
     # equal the source network's on the same plain images -- evaluated on the first images of the timed batch, plain torch f32 on the host
     n_gate = min(4, batch)
     with torch.no_grad():
-        y_plain = net(x[:n_gate].cpu()).reshape(n_gate, -1) if rank == 0 else None
+        y_plain = net(x[:n_gate].cpu()).reshape(n_gate, -1) if (rank == 0 and args.full) else None
     x_plain = x if (rank == 0 and world == 1) else None
     del x
     t0 = time.time()
@@ -287,12 +302,14 @@ def main():
             rank_seconds['steps'] = n_steps
         return (elapsed, out)
 
+    t_steps = time.time()
     (elapsed, out) = timed(args.warmup, args.steps)
+    t_steps = time.time() - t_steps
     assert out.shape[0] == batch * world and bool(torch.isfinite(out).all())
     if args.dump_outputs and rank == 0:
         dump_outputs(out, args.dump_outputs)
     parity = None
-    if rank == 0:
+    if rank == 0 and args.full:
         err = float((out[:n_gate].contiguous().cpu() - y_plain).abs().max())   # contiguous first: a strided D2H copy is ~1500 tiny copies
         parity = {'check': 'keyed logits of the timed batch vs the source network (torch f32, host) on %d images' % n_gate, 'max_abs_err': err,
                   'max_abs_logit': float(y_plain.abs().max()), 'err_over_max_logit': err / max(float(y_plain.abs().max()), 1e-30), 'atol': 1e-3,
@@ -300,31 +317,20 @@ def main():
         if not parity['ok']:
             raise AssertionError('parity gate failed: %s' % json.dumps(parity))
     collective = None
-    if use_dist:
+    if use_dist and args.full:
         collective = collective_record(knet, sensor, x_cipher, out, batch, world, rank, local_rank, dev, inshape, share)
         per_rank = [batch * rank_seconds['steps'] / t for t in rank_seconds['own']]
         collective['rank_images_per_s'] = {'min': min(per_rank), 'max': max(per_rank), 'all': per_rank,
                                            'what': 'images of the rank\'s own shard / its own time over the timed steps (before the closing barrier; every step ends in the all-gather)'}
         collective['startup'] = {'keying_or_loading_s_rank0': t_key, 'what': 'rank 0 keys once and hands the net to the other ranks through an anonymous file (benchlegs/shared.py)'}
     oracle_par = None
-    if rank == 0 and not args.workload.startswith('vgg16'):
+    if rank == 0 and args.full and not args.workload.startswith('vgg16'):
         oracle_par = oracle_parity_csr(knet, x_cipher, out[:batch])
         if oracle_par.get('ok') is False:
             raise AssertionError('oracle parity failed: %s' % json.dumps(oracle_par))
     del out
 
     if rank == 0:
-        table = time_layers(x_cipher, layer_table(knet, batch), args.layer_iters)
-        nnz_img = float(sum(r['nnz'] for r in table))
-        for r in table:
-            log('[bench layer] %-8s %-9s rows=%8d nnz=%12d  %8.3f ms  %7.2f TFLOP/s  %8.1f GB/s(alg)%s' %
-                (r['name'], r['kind'], r['rows'], r['nnz'], r['ms'], r['flops'] / r['ms'] / 1e9, r['bytes'] / r['ms'] / 1e6,
-                 '' if not r.get('flops_executed') else '  (on the stored entries of the fused operator; the split application executes %.2f TFLOP/s)' % (r['flops_executed'] / r['ms'] / 1e9)))
-        roof = roofline_of(table, args.workload, batch, mode)
-        total_bytes = sum(r['bytes'] for r in table)
-        chain = knet._chain_op(dev) if hasattr(knet, '_chain_op') else None
-        if chain is not None:                # the forward of this key-net is ONE launch of the whole-net kernel: that launch is the dominant kernel
-            roof = chain_roofline(knet, chain, x_cipher, table, batch)
         ms_per_step = 1e3 * elapsed / args.steps
         res = {
             'metric': 'encrypted images/sec (whole node), keyed %s' % {'vgg16': 'VGG-16 224x224', 'vgg16-gain': 'VGG-16 224x224 (float keys: permutation + photometric gain)', 'vgg16-givens': 'VGG-16 224x224 (float keys: Givens rotations + affine photometric, the reference\'s test_vgg16_orthogonal)', 'vgg16-givens28': 'VGG-16 224x224 (float keys: Givens rotations + affine photometric, tile 28: the reference\'s test_vgg16_orthogonal_8)', 'vgg16-stochastic': 'VGG-16 224x224 (float keys: hierarchical permutation + doubly-stochastic blocks + affine photometric: the reference\'s test_vgg16_stochastic)', 'vgg16-slice': 'VGG-16 slice 32x32 width 8 (rehearsal workload)', 'lenet': 'LeNet_AvgPool 28x28', 'allconv': 'AllConvNet 32x32'}[args.workload],
@@ -334,27 +340,45 @@ def main():
                        # which arithmetic contract the headline `value` was measured under, next to the library default's name (advisor, round 4): a
                        # permutation-only tiled key-net is bit-exact BY DEFAULT; the matrix-core number needs exact='auto' / False at construction
                        'headline_contract': ("opt-in exact='auto' (matrix cores within 1e-5, re-screened)" if mode == 'tolerance' else 'library default (bit-exact)'),
-                       'default_contract_value': 'see `exact.images_per_s`' if mode == 'tolerance' else 'this value',
-                       'images_per_gpu': batch, 'global_batch': batch * world, 'nnz_per_image': nnz_img,
+                       'default_contract_value': ('see `exact.images_per_s`' if args.full else 'the `exact` leg of --full') if mode == 'tolerance' else 'this value',
+                       'images_per_gpu': batch, 'global_batch': batch * world,
                        'parallelism': 'batch shards x%d, all_gather(logits)' % world if world > 1 else 'single GPU'},
-            'achieved_hbm_gbs_algorithmic': total_bytes / (ms_per_step * 1e6), 'achieved_tflops_algorithmic': 2.0 * nnz_img * batch / (ms_per_step * 1e9),
-            'roofline': roof, 'parity': parity,
-            'cpu_baseline': cpu if (cpu is not None or world == 1) else 'measured at N=1 only (the scipy baseline runs on rank 0 of a single-GPU run; see BENCH / profiles)',
-            'collective': collective,
-            'layers_ms': {r['name']: round(r['ms'], 4) for r in table},
-            'plans': {r['name']: r['plan'] for r in table},        # kn_spmm_plan: the kernels (tile shape, loader) each layer really takes at this batch
+            'full': args.full,
         }
-        if oracle_par is not None:
-            res['oracle_parity'] = oracle_par
-        if secondary is not None:
-            res['secondary'] = secondary
+        table = None
+        if args.full:
+            table = time_layers(x_cipher, layer_table(knet, batch), args.layer_iters)
+            nnz_img = float(sum(r['nnz'] for r in table))
+            for r in table:
+                log('[bench layer] %-8s %-9s rows=%8d nnz=%12d  %8.3f ms  %7.2f TFLOP/s  %8.1f GB/s(alg)%s' %
+                    (r['name'], r['kind'], r['rows'], r['nnz'], r['ms'], r['flops'] / r['ms'] / 1e9, r['bytes'] / r['ms'] / 1e6,
+                     '' if not r.get('flops_executed') else '  (on the stored entries of the fused operator; the split application executes %.2f TFLOP/s)' % (r['flops_executed'] / r['ms'] / 1e9)))
+            roof = roofline_of(table, args.workload, batch, mode)
+            total_bytes = sum(r['bytes'] for r in table)
+            chain = knet._chain_op(dev) if hasattr(knet, '_chain_op') else None
+            if chain is not None:                # the forward of this key-net is ONE launch of the whole-net kernel: that launch is the dominant kernel
+                roof = chain_roofline(knet, chain, x_cipher, table, batch)
+            res['config']['nnz_per_image'] = nnz_img
+            res.update({
+                'achieved_hbm_gbs_algorithmic': total_bytes / (ms_per_step * 1e6), 'achieved_tflops_algorithmic': 2.0 * nnz_img * batch / (ms_per_step * 1e9),
+                'roofline': roof, 'parity': parity,
+                'cpu_baseline': cpu if (cpu is not None or world == 1) else 'measured at N=1 only (the scipy baseline runs on rank 0 of a single-GPU run; see BENCH / profiles)',
+                'collective': collective,
+                'layers_ms': {r['name']: round(r['ms'], 4) for r in table},
+                'plans': {r['name']: r['plan'] for r in table},        # kn_spmm_plan: the kernels (tile shape, loader) each layer really takes at this batch
+            })
+            if oracle_par is not None:
+                res['oracle_parity'] = oracle_par
+            if secondary is not None:
+                res['secondary'] = secondary
         # ---- the headline record is complete here.  Every leg below is reported-only: it runs inside leg(), which turns a failure into
         # an entry of res['errors'], and the line is printed from the `finally` -- a late failure (an out-of-memory in a side leg, say)
         # can no longer lose the headline.
         res['errors'] = {}
         try:
-            run_side_legs(SimpleNamespace(args=args, res=res, knet=knet, sensor=sensor, x_cipher=x_cipher, x_plain=x_plain, y_plain=y_plain, n_gate=n_gate, batch=batch, world=world,
-                                          dev=dev, table=table, timed=timed, replay=replay))
+            if args.full:
+                run_side_legs(SimpleNamespace(args=args, res=res, knet=knet, sensor=sensor, x_cipher=x_cipher, x_plain=x_plain, y_plain=y_plain, n_gate=n_gate, batch=batch,
+                                              world=world, dev=dev, table=table, timed=timed, replay=replay))
         finally:
             if not res['errors']:
                 del res['errors']
@@ -362,6 +386,7 @@ def main():
             write_detail(res, args.detail)
             log('[bench detail] ' + json.dumps(res, default=str))
             os.write(json_fd, (compact_record(res, os.path.relpath(detail, ROOT) if detail.startswith(ROOT) else detail) + '\n').encode())
+    log('[bench rank %d] %.1f s since start, %.2f s of it in the warm-up and timed steps' % (rank, time.time() - T_START, t_steps))
     if use_dist:
         dist.barrier()
         dist.destroy_process_group()

@@ -23,7 +23,7 @@ def run_secondary(args):
         t0 = time.time()
         child_detail = os.path.join(ROOT, 'bench_detail_%s.json' % wl)
         cmd = [sys.executable, os.path.join(ROOT, 'bench.py'), '--workload', wl, '--steps', str(steps), '--warmup', str(warm), '--layer-iters', '3',
-               '--no-secondary', '--cpu-budget', '8', '--detail', child_detail] + extra
+               '--no-secondary', '--cpu-budget', '8', '--detail', child_detail, '--full'] + extra
         env = dict(os.environ)
         for k in ('WORLD_SIZE', 'RANK', 'LOCAL_RANK'):
             env.pop(k, None)

@@ -65,12 +65,17 @@ def compact_record(res, detail_path=DETAIL_FILE):
     line['config'] = _pick(cfg, ('workload', 'mode', 'headline_contract', 'default_contract_value', 'images_per_gpu', 'global_batch', 'nnz_per_image', 'parallelism'))
     line['config']['workload'] = _clip(line['config'].get('workload'), 160)
     line['config']['mode'] = _clip(line['config'].get('mode'), 160)
-    line['roofline'] = _compact_roofline(res.get('roofline'))
-    line['cpu_baseline'] = _compact_cpu(res.get('cpu_baseline')) if isinstance(res.get('cpu_baseline'), dict) else _clip(res.get('cpu_baseline'), 120)
-    par = res.get('parity') or {}
-    line['parity'] = _pick(par, ('ok', 'max_abs_err', 'atol'))
-    if isinstance(res.get('oracle_parity'), dict):
-        line['parity']['oracle_bit_equal'] = res['oracle_parity'].get('bit_equal')
+    # (a plain run's record holds the headline alone: roofline, cpu_baseline and parity are sections of `bench.py --full`)
+    if 'full' in res:
+        line['full'] = res['full']
+    if 'roofline' in res:
+        line['roofline'] = _compact_roofline(res.get('roofline'))
+    if 'cpu_baseline' in res:
+        line['cpu_baseline'] = _compact_cpu(res.get('cpu_baseline')) if isinstance(res.get('cpu_baseline'), dict) else _clip(res.get('cpu_baseline'), 120)
+    if 'parity' in res:
+        line['parity'] = _pick(res.get('parity') or {}, ('ok', 'max_abs_err', 'atol'))
+        if isinstance(res.get('oracle_parity'), dict):
+            line['parity']['oracle_bit_equal'] = res['oracle_parity'].get('bit_equal')
     ex = res.get('exact')
     if isinstance(ex, dict):
         if 'error' in ex:

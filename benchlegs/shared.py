@@ -49,12 +49,12 @@ def _barrier(what):
     w.wait()
 
 
-def build_workload_shared(name, rank, world, exact=None):
+def build_workload_shared(name, rank, world, exact=None, fanout=False, prepare=None):
     """build_workload for the ranks of ONE node (bench contract: --nnodes=1, so rank 0 is the node's first rank).  Ranks other than 0 get net = None (only rank 0
-    evaluates the plain network for the parity gate).  Returns the tuple of build_workload."""
+    evaluates the plain network for the parity gate).  Returns the tuple of build_workload; `fanout` and `prepare` are passed on to it on a single rank only."""
     forced = os.environ.get('KN_BENCH_TEST_FORCE_SHARED') == '1'            # test-only: run the protocol with one rank (its collectives on the RCCL backend of a single-GPU box)
     if (world <= 1 and not forced) or not dist.is_available() or not dist.is_initialized():
-        return build_workload(name, rank, exact=exact)
+        return build_workload(name, rank, exact=exact, fanout=fanout, prepare=prepare)
     out = None
     fd = -1
     msg = None

@@ -1,17 +1,129 @@
 """The bench workloads (host only: no GPU call in this module): BASELINE.json's configs and the reference's float-key VGG-16 tests, keyed under fixed seeds."""
+import contextlib
+import multiprocessing
+import multiprocessing.connection
 import time
+import traceback
 
 import numpy as np
 import torch
 
+from keynet_amd import sparse as ksp
 from keynet_amd import system as ksys
+from keynet_amd.layer import KeyedLayer
 from keynet_amd.models import VGG16, LeNet_AvgPool, AllConvNet
 from .common import log
 
+FANOUT_TYPES = (torch.nn.AvgPool2d,)
+FANOUT_TIMEOUT_S = 900
 
-def build_workload(name, rank, exact=None):
-    """(sensor, knet, inshape, per_gpu_batch, description, source network).  Deterministic under the seeds, identical on every rank."""
+
+class _Pending(torch.nn.Module):
+    """Holds a layer's place in the key-net while a forked process keys it (_keying)."""
+
+    def __init__(self, proc, conn):
+        super(_Pending, self).__init__()
+        (self.proc, self.conn, self.t0) = (proc, conn, time.time())
+
+
+def _key_in_child(conn, make, args, kw):
+    try:
+        torch.set_num_threads(1)         # no OpenMP team in a forked child: the parent's threads are not there
+        conn.send(('ok', make(*args, **kw)))
+    except BaseException as e:
+        conn.send(('error', '%s: %s\n%s' % (type(e).__name__, e, traceback.format_exc())))
+    finally:
+        conn.close()
+
+
+@contextlib.contextmanager
+def _keying(types=()):
+    """Inside the block, every layer of a key-net under construction whose source module is one of `types` is keyed in a process forked at that moment
+    (its arguments -- the module, the shapes and the two keys, drawn already -- are inherited, not copied); the construction goes on with a _Pending in its
+    place.  The keyed VGG-16 spends most of its keying in its five pooling layers, each a pure function of those arguments, so they run side by side and
+    behind the rest of the construction.  Yields finish(knet, prepare=None): receives the keyed layers as they complete and puts them in place of the _Pending
+    modules; prepare(layer), if given, runs on every keyed layer as soon as it is there -- first on those keyed in this process, then on each forked one as it
+    arrives.  With `types` given, the process must not have initialised the GPU when the block starts (a forked child of a HIP process is not safe); prepare
+    may, every fork has happened by then."""
+    assert not (types and torch.cuda.is_initialized()), 'keying in forked processes: it must run before the GPU is touched'
+    ctx = multiprocessing.get_context('fork')
+    make = ksys.layergen
+    procs = []
+
+    def layergen(module, inshape, outshape, A, Ainv, **kw):
+        if not isinstance(module, types):
+            return make(module, inshape, outshape, A, Ainv, **kw)
+        (mine, theirs) = ctx.Pipe(duplex=False)
+        p = ctx.Process(target=_key_in_child, args=(theirs, make, (module, inshape, outshape, A, Ainv), kw), daemon=True)
+        p.start()
+        theirs.close()
+        procs.append(p)
+        return _Pending(p, mine)
+
+    def finish(knet, prepare=None):
+        pending = {m.conn: (name, m) for (name, m) in knet._keynet.named_children() if isinstance(m, _Pending)}
+        if prepare is not None:
+            for m in knet._keynet.children():
+                if isinstance(m, KeyedLayer):
+                    prepare(m)
+        deadline = time.time() + FANOUT_TIMEOUT_S
+        while pending:
+            ready = multiprocessing.connection.wait(list(pending), timeout=max(0.0, deadline - time.time()))
+            if not ready:
+                raise RuntimeError('keying of %s did not finish in %d s' % (', '.join(n for (n, _) in pending.values()), FANOUT_TIMEOUT_S))
+            for conn in ready:
+                (name, m) = pending.pop(conn)
+                try:
+                    (status, layer) = conn.recv()
+                except EOFError:
+                    (status, layer) = ('error', 'the process keying it exited with %s before sending it' % m.proc.exitcode)
+                conn.close()
+                m.proc.join()
+                if status != 'ok':
+                    raise RuntimeError('keying layer "%s" failed: %s' % (name, layer))
+                setattr(knet._keynet, name, layer)
+                log('[bench] %s keyed in a process of its own in %.1f s' % (name, time.time() - m.t0))
+                if prepare is not None:
+                    prepare(layer)
+        return knet
+
+    if types:
+        ksys.layergen = layergen
+    try:
+        yield finish
+    finally:
+        ksys.layergen = make
+        for p in procs:                                  # nothing keeps running behind a failure
+            if p.is_alive():
+                p.terminate()
+            p.join()
+
+
+def upload_operators(dev):
+    """A prepare() for build_workload: builds on `dev` the device operators the first forward of a key-net under the 'auto' contract builds for the layer
+    (KeyedLayer._calibrate: the operator, and for a keyed Linear also its split-K matrix-core form) -- the same handles, only sooner."""
+    def prepare(layer):
+        W = layer.W
+        if type(W) is ksp.SparseMatrix:
+            W._dense_device_op(dev)
+        W._device_op(dev)
+    return prepare
+
+
+def build_workload(name, rank, exact=None, fanout=False, prepare=None):
+    """(sensor, knet, inshape, per_gpu_batch, description, source network).  Deterministic under the seeds, identical on every rank.  `fanout`: key the
+    pooling layers in processes of their own (_keying: this process must not have touched the GPU yet).  prepare(layer), if given, runs on every keyed layer
+    once it is keyed -- with `fanout`, while the pooling layers are still being keyed."""
     t0 = time.time()
+    with _keying(FANOUT_TYPES if fanout else ()) as finish:
+        out = _workload(name, exact)
+        finish(out[1], prepare)
+    log('[bench rank %d] keyed %s on the host in %.1f s%s' % (rank, name, time.time() - t0, '' if prepare is None else ' (operators uploaded as the layers came)'))
+    return out
+
+
+def _workload(name, exact):
+    """build_workload's keyed nets under their seeds: (sensor, knet, inshape, per_gpu_batch, description, source network)."""
     if name == 'vgg16':
         torch.manual_seed(0)
         net = VGG16(num_classes=2622).eval()
@@ -85,5 +197,4 @@ def build_workload(name, rank, exact=None):
         (inshape, batch, desc) = ((3, 32, 32), 4096, 'PermutationKeynet AllConvNet 3x32x32 (BASELINE configs[2])')
     else:
         raise ValueError('unknown workload "%s"' % name)
-    log('[bench rank %d] keyed %s on the host in %.1f s' % (rank, name, time.time() - t0))
     return (sensor, knet, inshape, batch, desc, net)

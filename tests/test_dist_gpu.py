@@ -77,7 +77,7 @@ def test_bench_four_ranks_on_one_gpu():
     env.pop('WORLD_SIZE', None)
     env.pop('RANK', None)
     t0 = time.time()
-    p = subprocess.run([sys.executable, os.path.join(ROOT, 'bench.py'), '--gpus', str(RANKS), '--workload', 'lenet', '--steps', '3', '--warmup', '1', '--layer-iters', '1'],
+    p = subprocess.run([sys.executable, os.path.join(ROOT, 'bench.py'), '--gpus', str(RANKS), '--workload', 'lenet', '--steps', '3', '--warmup', '1', '--layer-iters', '1', '--full'],
                        env=env, capture_output=True, text=True, timeout=900)
     wall = time.time() - t0
     assert p.returncode == 0, p.stderr[-3000:]
@@ -96,7 +96,7 @@ def test_bench_starts_its_own_ranks():
     env = dict(os.environ, KN_BENCH_SHARE_GPU='1')
     env.pop('WORLD_SIZE', None)
     env.pop('RANK', None)
-    p = subprocess.run([sys.executable, os.path.join(ROOT, 'bench.py'), '--gpus', '2', '--workload', 'lenet', '--steps', '3', '--warmup', '1', '--layer-iters', '1'],
+    p = subprocess.run([sys.executable, os.path.join(ROOT, 'bench.py'), '--gpus', '2', '--workload', 'lenet', '--steps', '3', '--warmup', '1', '--layer-iters', '1', '--full'],
                        env=env, capture_output=True, text=True, timeout=900)
     assert p.returncode == 0, p.stderr[-3000:]
     lines = [l for l in p.stdout.splitlines() if l.startswith('{')]
@@ -124,7 +124,7 @@ def test_bench_four_ranks_share_one_keying_of_a_tiled_vgg():
     the gather's own time, slowest / fastest rank, every shard bit-equal to its rank's local forward and the LAST rank's shard recomputed on rank 0 bit-equal
     (= loaded operators == keyed operators)."""
     before = _shm_archives()
-    p = _bench(['--gpus', str(RANKS), '--workload', 'vgg16-slice', '--batch', '16', '--steps', '2', '--warmup', '1', '--layer-iters', '1', '--no-cpu-baseline'])
+    p = _bench(['--gpus', str(RANKS), '--workload', 'vgg16-slice', '--batch', '16', '--steps', '2', '--warmup', '1', '--layer-iters', '1', '--no-cpu-baseline', '--full'])
     assert p.returncode == 0, p.stderr[-3000:]
     lines = [l for l in p.stdout.splitlines() if l.startswith('{')]
     assert len(lines) == 1 and len(lines[0]) < 4096

@@ -33,7 +33,7 @@ def test_bench_dist_flag_runs_the_rccl_path_on_one_gpu():
     for k in ('WORLD_SIZE', 'RANK', 'LOCAL_RANK', 'KN_BENCH_SHARE_GPU'):
         env.pop(k, None)
     p = subprocess.run([sys.executable, os.path.join(ROOT, 'bench.py'), '--gpus', '1', '--dist', '--workload', 'lenet', '--steps', '3', '--warmup', '1',
-                        '--layer-iters', '1', '--no-cpu-baseline', '--no-secondary'], env=env, capture_output=True, text=True, timeout=900)
+                        '--layer-iters', '1', '--no-cpu-baseline', '--no-secondary', '--full'], env=env, capture_output=True, text=True, timeout=900)
     assert p.returncode == 0, p.stderr[-3000:]
     lines = [l for l in p.stdout.splitlines() if l.startswith('{')]
     assert len(lines) == 1, p.stdout[-2000:]
@@ -54,7 +54,7 @@ def test_keyed_net_handover_protocol_runs_on_the_rccl_backend():
     for k in ('WORLD_SIZE', 'RANK', 'LOCAL_RANK', 'KN_BENCH_SHARE_GPU'):
         env.pop(k, None)
     p = subprocess.run([sys.executable, os.path.join(ROOT, 'bench.py'), '--gpus', '1', '--dist', '--workload', 'lenet', '--steps', '3', '--warmup', '1',
-                        '--layer-iters', '1', '--no-cpu-baseline', '--no-secondary'], env=env, capture_output=True, text=True, timeout=900)
+                        '--layer-iters', '1', '--no-cpu-baseline', '--no-secondary', '--full'], env=env, capture_output=True, text=True, timeout=900)
     assert p.returncode == 0, p.stderr[-3000:]
     assert 'keyed net handed to the other 0 ranks through an anonymous file' in p.stderr, p.stderr[-2000:]
     lines = [l for l in p.stdout.splitlines() if l.startswith('{')]

@@ -10,7 +10,7 @@ mkdir -p "$REPO/$R"
 R="$REPO/$R"
 export TMPDIR=/tmp
 cd /tmp
-PMC_BENCH="--steps 1 --warmup 0 --layer-iters 1 --no-cpu-baseline --no-exact-leg $EXTRA"
+PMC_BENCH="--steps 1 --warmup 0 --full --layer-iters 1 --no-cpu-baseline --no-exact-leg $EXTRA"
 rocprofv3 --kernel-trace --pmc FETCH_SIZE --output-format csv -d "$R/pmc_fetch" -- python3 "$REPO/bench.py" $PMC_BENCH > "$R/pmc_fetch.json" 2> "$R/pmc_fetch.log"
 rocprofv3 --kernel-trace --pmc WRITE_SIZE --output-format csv -d "$R/pmc_write" -- python3 "$REPO/bench.py" $PMC_BENCH > "$R/pmc_write.json" 2> "$R/pmc_write.log"
 rocprofv3 --kernel-trace --pmc SQ_VALU_MFMA_BUSY_CYCLES SQ_BUSY_CYCLES GRBM_GUI_ACTIVE SQ_WAVES SQ_LDS_BANK_CONFLICT --output-format csv -d "$R/pmc_mfma" -- python3 "$REPO/bench.py" $PMC_BENCH > "$R/pmc_mfma.json" 2> "$R/pmc_mfma.log"

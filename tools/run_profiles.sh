@@ -9,11 +9,11 @@ REPO=$(pwd)
 mkdir -p "$REPO/$R"
 R="$REPO/$R"
 export TMPDIR=/tmp
-python3 bench.py --steps 20 --warmup 5 --detail "$R/bench_detail.json" > "$R/bench.json" 2> "$R/bench.log"
+python3 bench.py --steps 20 --warmup 5 --full --detail "$R/bench_detail.json" > "$R/bench.json" 2> "$R/bench.log"
 cd /tmp
-rocprofv3 --kernel-trace --stats --output-format csv -d "$R/stats" -- python3 "$REPO/bench.py" --steps 3 --warmup 1 --no-cpu-baseline --no-secondary > "$R/stats_bench.json" 2> "$R/stats_bench.log"
+rocprofv3 --kernel-trace --stats --output-format csv -d "$R/stats" -- python3 "$REPO/bench.py" --steps 3 --warmup 1 --full --no-cpu-baseline --no-secondary > "$R/stats_bench.json" 2> "$R/stats_bench.log"
 rocprofv3 --kernel-trace --output-format csv -d "$R/trace" -- python3 "$REPO/bench.py" --no-cpu-baseline --no-secondary --trace-layers "$R/layers.json" > /dev/null 2> "$R/trace.log"
-PMC_BENCH="--steps 1 --warmup 0 --layer-iters 1 --no-cpu-baseline --no-exact-leg --no-secondary"
+PMC_BENCH="--steps 1 --warmup 0 --full --layer-iters 1 --no-cpu-baseline --no-exact-leg --no-secondary"
 # roofline.traffic, ONE definition (round 6): the launches of exactly one forward between two marker kernels (bench.py --pmc-forward), FETCH_SIZE and WRITE_SIZE in separate passes
 rocprofv3 --kernel-trace --pmc FETCH_SIZE --output-format csv -d "$R/pmc_fetch" -- python3 "$REPO/bench.py" --no-cpu-baseline --no-secondary --pmc-forward "$R/forward.json" > /dev/null 2> "$R/pmc_fetch.log"
 rocprofv3 --kernel-trace --pmc WRITE_SIZE --output-format csv -d "$R/pmc_write" -- python3 "$REPO/bench.py" --no-cpu-baseline --no-secondary --pmc-forward "$R/forward_w.json" > /dev/null 2> "$R/pmc_write.log"
