@@ -140,7 +140,7 @@ class KeyedModel(object):
     RESCREEN = True              # re-screen the float-key contract on every forward (KN_NO_RESCREEN=1: A/B switch, read per call)
     RESCREEN_MAX_PASSES = 4
 
-    def forward_linear(self, img_cipher, overlap=None, _slots_out=None):
+    def forward_linear(self, img_cipher, overlap=None):
         """[N, D0+1] -> [N, classes+1]: the nn.Sequential of keynet/system.py:132 with the unkeyed ReLUs fused into the
         producing layer's kernel epilogue.  Stream-ordered on torch's current HIP stream.  Host synchronisation: none for key-nets whose
         layers all run under a DECLARED contract (exact=True: the permutation key-nets; exact=False: forced); a key-net with layers on the
@@ -152,68 +152,75 @@ class KeyedModel(object):
         columns of the calibration batch; an unmeasured dense layer is accepted only with its worst-case bound at half the tolerance); NaN activations
         are not screened.  The reference applies one arithmetic on every call (keynet/sparse.py:488-492): only the 'exact' contract IS that arithmetic.
         The first forward of an 'auto' layer calibrates it (host reads).
+        Batch sizes (_prepare): an odd device batch of a tiled-conv key-net is padded with zero images to whole 128-image tiles, with the activations
+        and workspaces of the padded batch (VGG-16: one image costs what 128 cost, 1.6 GB for its largest layer).  The result: the first N rows of the
+        transposed view of a feature-major [classes+1, N'] block (N' = the padded batch); a host batch gets a host tensor.
         `overlap`: run the batch as two half-batch column windows on two side streams, one kernel apart (see _forward_overlapped);
         None = automatically for device-resident feature-major batches that are a multiple of 256 images, False = never.
         Memory: the overlapped forward keeps two ping-pong workspaces of max_rows x N floats per (device, N) plan (VGG-16 at N = 256:
         2 x 3.3 GB) plus two side streams; at most OVERLAP_PLANS_KEPT plans are cached (least recently used dropped),
         release_workspace() drops them all."""
-        if not img_cipher.is_cuda and img_cipher.dim() == 2 and torch.cuda.is_available() and _slots_out is None:
-            # a host tensor (how the reference's users call it): ONE copy to the device here instead of one per layer, so that the layers
-            # chain on the device and the per-forward contract screen sees them; the result goes back where the input lives
-            return self.forward_linear(img_cipher.detach().float().cuda(), overlap=overlap).to(img_cipher.device)
+        (x, windows) = self._prepare(img_cipher)
+        y = self._forward_passes(x, windows, overlap)[0][:img_cipher.shape[0]]
+        return y if img_cipher.is_cuda else y.to(img_cipher.device)
+
+    def _prepare(self, x):
+        """What the kernels get to see: (x, windows), the image ranges of the passes.  A host batch goes to the device ONCE (the layers chain
+        there; the screen sees them).  A float32 device batch of a tiled-conv key-net becomes one feature-major block of whole BATCH_TILE tiles
+        (ragged conv-taps forms are slow: VGG-16, stored order, 186 ms at 64 images against 72 ms at 128, profiles/r06_vgg16_other_batches.txt;
+        zero images raise no layer's max |x|; feature-major memory takes the overlapped form: 58.7 -> 57.0 ms at 256, tools/layout_time.py).
+        The fast loaders take 32-bit element offsets: a batch whose largest layer would hold MAX_BLOCK_ELEMENTS activations runs as passes of the
+        largest multiple of 256 images that keeps every layer inside (VGG-16 at 1 024 images: conv1_2 113.7 ms against 2 x 31 for two passes of 512);
+        each pass copies its window into a block of its own (a padded batch is then held twice while the passes run).  Anything else -- float64,
+        an untiled key-net, no image -- passes through as one window."""
+        if not x.is_cuda and x.dim() == 2 and torch.cuda.is_available():
+            x = x.detach().float().cuda()
         keyed = [c for c in self._keynet.children() if isinstance(c, klayer.KeyedLayer)]
-        on_dev = img_cipher.is_cuda and img_cipher.dim() == 2
-        capturing = on_dev and torch.cuda.is_current_stream_capturing()
-        if on_dev and not capturing and _slots_out is None and img_cipher.dtype == torch.float32 and self._has_tiled_conv(keyed):
-            # The fast loaders address an activation block with 32-bit element offsets: a layer of R rows takes them while R x N < 2^31.  VGG-16's conv1_2 (3.2 M rows) leaves
-            # them at 1 024 images -- 113.7 ms in the stored order against 2 x 31 ms for two passes of 512 (profiles/r06_vgg16_other_batches.txt) -- so a batch that large runs
-            # as passes of the largest multiple of 256 images that keeps every layer inside.
-            big = max(max(c.W.shape) for c in keyed)
-            chunk = (self.MAX_BLOCK_ELEMENTS - 1) // big // 256 * 256
-            if 0 < chunk < img_cipher.shape[0]:
-                n = img_cipher.shape[0]
-                self._chunked_forwards = getattr(self, '_chunked_forwards', 0) + 1
-                outs = []
-                for lo in range(0, n, chunk):
-                    part = img_cipher[lo:lo + chunk]
-                    if img_cipher.t().is_contiguous():             # (a window of feature-major memory: its own feature-major block, so that a pass takes the overlapped form)
-                        part = part.detach().t().contiguous().t()
-                    outs.append(self.forward_linear(part, overlap=overlap))
-                return torch.cat(outs, dim=0)
-        if (on_dev and not capturing and _slots_out is None and img_cipher.dtype == torch.float32 and img_cipher.shape[0] % self.BATCH_TILE == 0 and
-                not img_cipher.t().is_contiguous() and self._has_tiled_conv(keyed)):
-            # a row-major [N, D] batch (how a caller of the reference holds it): the kernels read feature-major memory, so the first layer would copy it anyway -- done here, once,
-            # the forward can also take its two-window overlapped form (VGG-16 at 256 images: 58.7 -> 57.0 ms, tools/layout_time.py)
-            img_cipher = img_cipher.detach().t().contiguous().t()
-        if on_dev and not capturing and _slots_out is None and img_cipher.shape[0] % self.BATCH_TILE and img_cipher.dtype == torch.float32 and self._has_tiled_conv(keyed):
-            # The conv-taps kernels tile the batch in 128 / 256 columns: an odd batch runs their ragged forms (VGG-16, stored order: 186 ms at 64 images, 131 ms at 192, against
-            # 72 ms at 128 and 122 ms at 256; matrix cores: 73 ms at 192 against 56 ms at 256 -- profiles/r06_vgg16_other_batches.txt).  Such a batch is padded with zero
-            # images to whole tiles, in the feature-major layout the kernels read; every image is its own column of every product, so its logits are what they are in any
-            # batch (bit for bit under the stored-order contract), and zero images raise no layer's max |x|.
-            n = img_cipher.shape[0]
-            padded = -(-n // self.BATCH_TILE) * self.BATCH_TILE
-            xp = torch.zeros((img_cipher.shape[1], padded), dtype=torch.float32, device=img_cipher.device).t()
-            xp[:n] = img_cipher.detach()
+        n = x.shape[0]
+        if not (x.is_cuda and x.dim() == 2 and x.dtype == torch.float32 and n > 0 and any(isinstance(c.W, ksp.Conv2dTiledMatrix) for c in keyed)):
+            return (x, [(0, n)])
+        npad = -(-n // self.BATCH_TILE) * self.BATCH_TILE
+        chunk = (self.MAX_BLOCK_ELEMENTS - 1) // max(max(c.W.shape) for c in keyed) // 256 * 256
+        windows = [(lo, min(lo + chunk, npad)) for lo in range(0, npad, chunk)] if 0 < chunk < npad else [(0, npad)]
+        if len(windows) > 1:
+            self._chunked_forwards = getattr(self, '_chunked_forwards', 0) + 1
+        if npad > n:
+            xp = torch.zeros((x.shape[1], npad), dtype=torch.float32, device=x.device).t()
+            xp[:n] = x.detach()
+            x = xp
             self._padded_forwards = getattr(self, '_padded_forwards', 0) + 1
-            return self.forward_linear(xp, overlap=overlap)[:n]
-        y = None
-        for _ in range(self.RESCREEN_MAX_PASSES):
+        elif len(windows) == 1 and not x.t().is_contiguous():
+            x = x.detach().t().contiguous().t()
+        return (x, windows)
+
+    def _forward_passes(self, x, windows, overlap):
+        """The screened forward of a prepared batch: (y, screens).  A pass whose screen re-calibrates a layer runs again (calibrating on its own images),
+        then every other pass again: the batch comes out of ONE set of contracts.  At most RESCREEN_MAX_PASSES runs of a pass; then only the last pass is
+        re-screened (the next forward decides).  Under a HIP-graph capture nothing is read: `screens` = (slots, screened) per pass, for capture's replay."""
+        keyed = [c for c in self._keynet.children() if isinstance(c, klayer.KeyedLayer)]
+        on_dev = x.is_cuda and x.dim() == 2
+        read = (on_dev and not torch.cuda.is_current_stream_capturing() and
+                os.environ.get('KN_RESCREEN_NOREAD') != '1')      # DIAGNOSTIC (tools/ab_rescreen.py): gather the maxima but skip the host read -- what the read itself costs
+        ys = [None] * len(windows)
+        (todo, screens, redos) = (list(range(len(windows))), [], 0)
+        while todo:
+            k = todo.pop(0)
             screened = set()
             if on_dev and self.RESCREEN and os.environ.get('KN_NO_RESCREEN') != '1' and not any(getattr(c, '_exact', True) == 'auto' for c in keyed):
-                screened = set(k for (k, c) in enumerate(keyed) if c.screened())
-            slots = torch.zeros(len(keyed) + 1, dtype=torch.float32, device=img_cipher.device) if screened else None
-            y = self._forward_once(img_cipher, overlap, slots, screened)
+                screened = set(j for (j, c) in enumerate(keyed) if c.screened())
+            slots = torch.zeros(len(keyed) + 1, dtype=torch.float32, device=x.device) if screened else None
+            (lo, hi) = windows[k]
+            # (a window of a wider block: its own feature-major block, so that the pass can take the overlapped form)
+            ys[k] = self._forward_once(x if len(windows) == 1 else x[lo:hi].t().contiguous().t(), overlap, slots, screened)
             if slots is None:
-                return y
-            if capturing:
-                if _slots_out is not None:
-                    _slots_out.append((slots, screened))        # a graph replay checks them after the launch (KeyedModel.capture)
-                return y
-            if os.environ.get('KN_RESCREEN_NOREAD') == '1':      # DIAGNOSTIC (tools/ab_rescreen.py): gather the maxima but skip the host read -- what the read itself costs
-                return y
-            if not self._rescreen(slots.tolist(), keyed, screened):
-                return y
-        return y
+                continue
+            screens.append((slots, screened))
+            if not read or (todo and redos + 1 == self.RESCREEN_MAX_PASSES):
+                continue
+            if self._rescreen(slots.tolist(), keyed, screened) and redos + 1 < self.RESCREEN_MAX_PASSES:
+                redos += 1
+                todo = [k] + [j for j in range(len(windows)) if j != k]
+        return (ys[0] if len(ys) == 1 else torch.cat([y.t() for y in ys], dim=1).t(), screens)
 
     def _rescreen(self, xmax, keyed, screened):
         """Host side of the per-forward screen: layers whose input magnitude has outgrown their calibration go back to 'auto' (decided
@@ -229,12 +236,8 @@ class KeyedModel(object):
             self.__dict__.pop('_overlap_plans', None)
         return redo
 
-    BATCH_TILE = 128           # forward_linear pads a device batch of a tiled-conv key-net to whole multiples of this many images
+    BATCH_TILE = 128           # _prepare pads a device batch of a tiled-conv key-net to whole multiples of this many images
     MAX_BLOCK_ELEMENTS = 1 << 31   # ... and splits a batch whose largest layer would hold this many activations or more into passes
-
-    @staticmethod
-    def _has_tiled_conv(keyed):
-        return any(isinstance(c.W, ksp.Conv2dTiledMatrix) for c in keyed)
 
     def _forward_once(self, img_cipher, overlap, slots, screened):
         """One pass over the keyed layers.  `slots` (device f32 [L + 1], zeroed) / `screened` (indices of the keyed layers whose contract
@@ -567,44 +570,40 @@ class KeyedModel(object):
     def capture(self, img_cipher):
         """Capture forward_linear for this input shape into a HIP graph (torch.cuda.CUDAGraph on ROCm) and return a callable
         `replay(x) -> [N, classes+1]`.  Small key-nets are launch-bound (LeNet at N=1024: 7 kernels in 0.25 ms); one graph
-        launch replaces them.  The operators must already be resident and every 'auto' layer decided (one eager forward is run first); the
-        returned tensor is the graph's static output buffer (clone it to keep a result across replays).  A key-net with calibrated layers
-        keeps its per-forward screen: the graph gathers max |x| per layer like the eager forward, replay() reads it back after the launch
-        and, when a layer's input has outgrown its calibration, re-runs the batch eagerly (re-calibrating) and captures a new graph."""
+        launch replaces them.  The graph runs the passes of the eager forward on the block _prepare made; replay(x) copies x into its first N images.
+        The operators must already be resident and every 'auto' layer decided (one eager forward is run first); the returned tensor is the first N
+        rows of the graph's static output buffer (clone it to keep a result across replays).  A key-net with calibrated layers keeps its per-forward
+        screen: the graph gathers max |x| per layer like the eager forward, replay() reads it back after the launch and, when a layer's input has
+        outgrown its calibration, re-runs the batch eagerly (re-calibrating) and captures a new graph."""
         assert img_cipher.is_cuda, 'capture() needs a device tensor'
-        static_in = img_cipher.detach().clone()
-        # keep the layout the layers expect: a transposed view of a feature-major block
-        if not static_in.t().is_contiguous():
-            static_in = static_in.t().contiguous().t()
+        n = img_cipher.shape[0]
+        (static_in, windows) = self._prepare(img_cipher.detach().t().clone(memory_format=torch.contiguous_format).t())     # the graph's own input block
+        keyed = [c for c in self._keynet.children() if isinstance(c, klayer.KeyedLayer)]
         state = {}
 
         def build():
-            self.forward_linear(static_in, overlap=False)       # uploads operators, sizes workspaces, calibrates (not capturable)
+            self._forward_passes(static_in, windows, False)       # uploads operators, sizes workspaces, calibrates (not capturable)
             torch.cuda.synchronize()
             side = torch.cuda.Stream()
             side.wait_stream(torch.cuda.current_stream())
             with torch.cuda.stream(side):
-                self.forward_linear(static_in, overlap=False)   # warm-up on the capture stream
+                self._forward_passes(static_in, windows, False)   # warm-up on the capture stream
             torch.cuda.current_stream().wait_stream(side)
             graph = torch.cuda.CUDAGraph()
-            slots = []
             # capture ON THE WARMED STREAM: per-stream state of the operators (the split-K workspace of a dense layer, kn_api.hip) was sized
             # by the warm-up forward above; torch's default capture stream would be a fresh one, and a hipMalloc inside a capture is refused
             with torch.cuda.graph(graph, stream=side):
-                out = self.forward_linear(static_in, overlap=False, _slots_out=slots)
-            state.update(graph=graph, out=out, slots=slots[0] if slots else None)
+                (out, screens) = self._forward_passes(static_in, windows, False)
+            state.update(graph=graph, out=out[:n], screens=screens)
 
         build()
 
         def replay(x):
-            static_in.copy_(x)
+            static_in[:n].copy_(x)
             state['graph'].replay()
-            if state['slots'] is not None:
-                (slots, screened) = state['slots']
-                keyed = [c for c in self._keynet.children() if isinstance(c, klayer.KeyedLayer)]
-                if self._rescreen(slots.tolist(), keyed, screened):
-                    build()                                      # eager forward on this batch re-calibrates; then a fresh graph
-                    state['graph'].replay()
+            if any(self._rescreen(slots.tolist(), keyed, screened) for (slots, screened) in state['screens']):
+                build()                                          # eager forward on this batch re-calibrates; then a fresh graph
+                state['graph'].replay()
             replay.graph = state['graph']
             return state['out']
         replay.graph = state['graph']

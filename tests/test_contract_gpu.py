@@ -220,6 +220,25 @@ def test_contract_holds_when_later_batches_are_larger(golden, family, batch, cap
     assert knet.contract_report()['recalibrations'] == n0
 
 
+def test_a_batch_in_passes_comes_out_of_one_set_of_contracts(golden):
+    """A batch too large for one pass (the limit lowered: 512 images as two passes of 256) whose SECOND pass outgrows the calibration that the
+    first pass decided: the re-calibration moves a layer to another kernel, and the first pass is computed again under the new contracts -- the
+    forward equals a second forward of the same batch bit for bit, and that second forward re-calibrates nothing."""
+    g = torch.Generator(device=dev()).manual_seed(10)
+    x = torch.randn((256, 2, 16, 16), generator=g, device=dev())
+    (sensor, knet) = gain_keynet(golden)
+    xc = sensor.fromtensor(torch.cat((x, 1000.0 * x))).encrypt().astensor()
+    (_, first) = gain_keynet(golden)                           # the same keys: what the first pass alone decides
+    first.forward_linear(xc[:256])
+    knet.MAX_BLOCK_ELEMENTS = max(max(c.W.shape) for (_, c) in keyed(knet)) * 256 + 1
+    y = knet.forward_linear(xc)
+    rep = knet.contract_report()
+    assert knet._chunked_forwards == 1 and rep['recalibrations'] >= 1 and not rep['undecided']
+    assert {n: c._exact for (n, c) in keyed(knet)} != {n: c._exact for (n, c) in keyed(first)}, rep
+    assert torch.equal(y, knet.forward_linear(xc))
+    assert knet.contract_report()['recalibrations'] == rep['recalibrations']
+
+
 def test_host_tensors_are_screened_too(golden):
     """The reference's users hand host tensors over; the forward moves them to the device once, so the screen covers that route as well."""
     (sensor, knet) = gain_keynet(golden)
@@ -273,6 +292,27 @@ def test_graph_replay_keeps_the_screen(golden):
     g1 = replay.graph
     assert torch.equal(replay(xc), y) or layerwise_within_tolerance(knet, xc) <= 1.0
     assert replay.graph is g1                                # smaller inputs: same graph
+
+
+def test_graph_replay_keeps_the_screen_of_every_pass(golden):
+    """A batch captured as two passes of 256 images (the limit lowered): the graph records both, replays equal the eager forward, and replay()
+    re-screens each pass -- a batch whose SECOND pass outgrows the calibration re-calibrates and captures a new graph."""
+    (sensor, knet) = gain_keynet(golden)
+    knet.MAX_BLOCK_ELEMENTS = max(max(c.W.shape) for (_, c) in keyed(knet)) * 256 + 1
+    g = torch.Generator(device=dev()).manual_seed(12)
+    x = torch.randn((512, 2, 16, 16), generator=g, device=dev())
+    xc = sensor.fromtensor(x).encrypt().astensor()
+    replay = knet.capture(xc)
+    assert knet._chunked_forwards == 1                       # prepared once, for the graph's input block
+    y = replay(xc).clone()
+    assert torch.equal(y, knet.forward_linear(xc, overlap=False))
+    (g0, n0) = (replay.graph, knet.contract_report()['recalibrations'])
+    mixed = sensor.fromtensor(torch.cat((x[:256], 50.0 * x[256:]))).encrypt().astensor()
+    ym = replay(mixed).clone()
+    n1 = knet.contract_report()['recalibrations']
+    assert n1 > n0 and replay.graph is not g0
+    assert torch.equal(ym, knet.forward_linear(mixed, overlap=False))
+    assert knet.contract_report()['recalibrations'] == n1
 
 
 def test_capture_refuses_an_undecided_layer(golden):

@@ -1919,8 +1919,8 @@ def test_a_batch_too_large_for_32_bit_offsets_runs_in_passes(golden):
 
 @pytest.mark.parametrize('name', ['mini_tiled_permutation.npz', 'mini_tiled_stochastic.npz', 'lenet_perm.npz'])
 def test_graph_capture_at_any_batch_size(golden, name):
-    """KeyedModel.capture on batches of 1 / 37 / 128 / 300 images (the eager forward pads a tiled-conv key-net's odd batch to whole tiles; a capture records the batch as it is):
-    the replayed graph returns the eager logits bit for bit, on the captured input and on other data of the same shape."""
+    """KeyedModel.capture on batches of 1 / 37 / 128 / 300 images records what the eager forward runs -- a tiled-conv key-net's odd batch padded to whole tiles, once, when
+    the graph's input block is prepared: the replayed graph returns the eager logits bit for bit, on the captured input and on other data of the same shape."""
     z = golden(name)
     knet = kio.keynet_from_arrays(z)
     rng = np.random.RandomState(0)
@@ -1928,7 +1928,9 @@ def test_graph_capture_at_any_batch_size(golden, name):
     for n in (1, 37, 128, 300):
         x = big[:n]
         eager = knet.forward_linear(x)
+        before = getattr(knet, '_padded_forwards', 0)
         replay = knet.capture(x)
+        assert getattr(knet, '_padded_forwards', 0) == before + (1 if (n % 128 and 'tiled' in name) else 0), n
         assert torch.equal(replay(x).clone(), eager), n
         other = big[300 - n:]
         assert torch.equal(replay(other).clone(), knet.forward_linear(other)), n
