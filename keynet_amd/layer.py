@@ -3,6 +3,7 @@
 Construction (host, offline) restates the reference's keying; `forward` -- the drop-in boundary -- hands the activation
 block to the HIP operator stored in `self.W` (its torchdot), optionally fusing the ReLU that follows.
 """
+import collections
 import logging
 import numpy as np
 import scipy.sparse
@@ -134,6 +135,10 @@ def gate(y, ref):
 
 _log = logging.getLogger('keynet_amd')
 
+# One kn_spmm launch of a keyed layer (KeyedLayer.launch): operator handle and flags, and what the planners of a key-net ask about it --
+# `exact`: the layer is under the bit-exact contract (_exact is True); `is_conv`: a Conv2dTiledMatrix operator; `is_linear`: keyed from an nn.Linear.
+Launch = collections.namedtuple('Launch', 'op flags rows cols is_conv is_linear exact')
+
 
 def _absmax_into(yt, slot):
     """Raise the one-element device tensor `slot` to max |yt| (kn_absmax: one pass over a feature-major block)."""
@@ -222,10 +227,36 @@ class KeyedLayer(nn.Module):
             if absmax is not None:
                 _absmax_into(y.t(), absmax)
             return y
-        if exact == 'split' and not (isinstance(self.W, ksp.Conv2dTiledMatrix) and self.W._taps is not None):
-            exact = False                                         # (forced with exact_mode('split') on an operator that has no split form: the matrix cores)
-        y = self.W.torchdot(x_affine.t(), relu=(fuse_relu or self.iskeyedrelu()), exact=exact, absmax=absmax).t()
-        return y
+        return self.W.torchdot(x_affine.t(), relu=(fuse_relu or self.iskeyedrelu()), exact=exact, absmax=absmax).t()
+
+    @staticmethod
+    def kernel(W, contract, relu, device=None):
+        """The one place that turns a decided contract into an operator handle and flags: (get_op, flags) of the kn_spmm launch that applies operator `W`
+        under `contract`, get_op(device) -> the handle resident there.  None when that is not one launch: 'auto' (still to calibrate), 'split' on an operator that has a split form (Conv2dTiledMatrix._torchdot_split).
+        The rules: 'split' forced on an operator without a split form, and 'bf16x3' on a non-conv operator, are the f32 matrix cores (False); a conv operator
+        runs the order-preserving kernel under True, else the matrix cores (bf16x3: the emulation where operator and batch qualify); a plain SparseMatrix
+        off the exact contract runs as a dense GEMM when it has such a handle (a large keyed nn.Linear); everything else -- tiled / factored CSR
+        containers, float64 operators, small or sparse matrices -- has the reference's order only."""
+        conv = isinstance(W, ksp.Conv2dTiledMatrix)
+        if contract == 'auto' or (contract == 'split' and conv and W._taps is not None):
+            return None
+        if contract == 'split' or (contract == 'bf16x3' and not conv):
+            contract = False
+        (get_op, exact) = (W._device_op, (contract != 'bf16x3' and bool(contract)) if conv else True)
+        if not conv and not contract and type(W) is SparseMatrix and not W.is_float64() and W._dense_device_op(device) is not None:
+            (get_op, exact) = (W._dense_device_op, False)
+        return (get_op, (_capi.KN_FLAG_RELU if relu else 0) | (_capi.KN_FLAG_EXACT if exact else 0) | (_capi.KN_FLAG_BF16X3 if contract == 'bf16x3' else 0))
+
+    def launch(self, device, relu=False):
+        """This layer under its contract in force as one launch on `device` (`relu`: the unkeyed nn.ReLU behind it is fused in), or None when it is not one
+        kn_spmm launch: see kernel(); a float64 operator (its own kernel and a float64 result: kn_spmm_f64).  What the key-net's planners read
+        (KeyedModel._chain_op / _overlap_plan); forward() -> W.torchdot() runs the same rule."""
+        W = self.W
+        kernel = None if W.is_float64() else self.kernel(W, getattr(self, '_exact', True), relu or self.iskeyedrelu(), device)
+        if kernel is None:
+            return None
+        return Launch(kernel[0](device), kernel[1], int(W.shape[0]), int(W.shape[1]), isinstance(W, ksp.Conv2dTiledMatrix), 'Linear' in self._layertype,
+                      getattr(self, '_exact', True) is True)
 
     # -- float-key contract: decided by calibration, re-screened on every forward --------------------------------------
     RESCREEN_FACTOR = 2.0        # a layer is re-calibrated when max |x| exceeds the calibrated value by more than this factor

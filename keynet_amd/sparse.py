@@ -67,32 +67,43 @@ def _on_device(W, attr, make, device=None):
     return cache[idx]
 
 
-def _run_torchdot(get_op, shape, x, relu=False, exact=True, extra_flags=0, absmax=None, f64=False):
-    """Y = W.X on the GPU.  x: torch tensor [cols, N] (any device / strides); get_op(device) -> the operator handle resident
-    on that device.  Returns [rows, N] on x's device.  `f64`: the operator is float64 -- the result is the float64 block scipy returns for it
-    (kn_spmm_f64); the activations are float32 either way (keynet/sparse.py:489-491)."""
-    assert shape[1] == x.shape[0], 'Non-conformal shape for W=%s, x=%s' % (str(shape), str(tuple(x.shape)))
+def _device_block(x):
+    """x (any device / dtype / strides) -> the detached float32 contiguous block on the GPU that the kernels read (a host tensor goes to the current
+    device; the reference coerces to FloatTensor silently, keynet/sparse.py:489-491)."""
     if not torch.cuda.is_available():
         raise _capi.KeynetHipError('keynet_amd: no MI355X visible -- the keyed forward has no CPU fallback')
-    src_device = x.device
     xd = x.detach()
     if xd.dtype != torch.float32:
-        xd = xd.float()          # the reference coerces to FloatTensor silently (keynet/sparse.py:489-491)
+        xd = xd.float()
     if not xd.is_cuda:
         xd = xd.cuda()
-    if not xd.is_contiguous():
-        xd = xd.contiguous()
+    return xd if xd.is_contiguous() else xd.contiguous()
+
+
+def _run_torchdot(W, x, relu=False, exact=True, absmax=None):
+    """Y = W.X on the GPU under the contract `exact`, on the handle and flags of KeyedLayer.kernel.  x: [cols, N], torch tensor (any device / strides) or ndarray.
+    Returns [rows, N] on x's device: float32, or for a float64 operator the float64 block scipy returns for it (kn_spmm_f64; the activations are
+    float32 either way)."""
+    from .layer import KeyedLayer            # (layer.py imports this module)
+    x = torch.as_tensor(x)
+    assert W.shape[1] == x.shape[0], 'Non-conformal shape for W=%s, x=%s' % (str(W.shape), str(tuple(x.shape)))
+    xd = _device_block(x)
     n = xd.shape[1]
-    y = torch.empty((shape[0], n), dtype=torch.float64 if f64 else torch.float32, device=xd.device)
-    flags = (_capi.KN_FLAG_RELU if relu else 0) | (_capi.KN_FLAG_EXACT if exact else 0) | int(extra_flags)
-    with torch.cuda.device(xd.device):
-        if f64:
-            get_op(xd.device).spmm_f64(xd.data_ptr(), n, n, y.data_ptr(), n, flags, _stream_ptr())
-            if absmax is not None:               # (a float64 layer is never on a re-ordering kernel; the slot still feeds the NEXT layer's screen)
-                _capi.absmax(y.float().data_ptr(), shape[0], n, n, absmax.data_ptr(), _stream_ptr())
-        else:
-            get_op(xd.device).spmm(xd.data_ptr(), n, n, y.data_ptr(), n, flags, _stream_ptr(), absmax_ptr=None if absmax is None else absmax.data_ptr())
-    return y if src_device.type == 'cuda' else y.to(src_device)
+    kernel = KeyedLayer.kernel(W, exact, relu, xd.device)
+    if kernel is None:
+        y = W._torchdot_split(xd, relu=relu, absmax=absmax)
+    else:
+        (get_op, flags) = kernel
+        f64 = W.is_float64()
+        y = torch.empty((W.shape[0], n), dtype=torch.float64 if f64 else torch.float32, device=xd.device)
+        with torch.cuda.device(xd.device):
+            if f64:
+                get_op(xd.device).spmm_f64(xd.data_ptr(), n, n, y.data_ptr(), n, flags, _stream_ptr())
+                if absmax is not None:               # (a float64 layer is never on a re-ordering kernel; the slot still feeds the NEXT layer's screen)
+                    _capi.absmax(y.float().data_ptr(), W.shape[0], n, n, absmax.data_ptr(), _stream_ptr())
+            else:
+                get_op(xd.device).spmm(xd.data_ptr(), n, n, y.data_ptr(), n, flags, _stream_ptr(), absmax_ptr=None if absmax is None else absmax.data_ptr())
+    return y if x.is_cuda else y.to(x.device)
 
 
 # ------------------------------------------------------------------------------------------------------------------
@@ -166,14 +177,7 @@ class SparseMatrix(object):
         with scipy (order-preserving CSR kernels).  exact=False: a large dense operator (keyed nn.Linear) may run as a
         split-K f32-MFMA GEMM instead (within 1e-5; used by the tiled key-nets whose conv layers are on MFMA anyway).
         `absmax`: one-element device f32 tensor raised to max |W . x| (kn_spmm_screen)."""
-        if exact == 'bf16x3':
-            exact = False            # a dense operator has no bf16x3 path (yet): f32 matrix cores
-        if self.is_float64():
-            # a float64 operator computes in float64 and returns float64, as scipy does for it (the next layer's coercion rounds to f32 once)
-            return _run_torchdot(self._device_op, self.shape, x_torch, relu=relu, exact=True, absmax=absmax, f64=True)
-        if not exact and torch.cuda.is_available() and self._dense_device_op(x_torch.device if x_torch.is_cuda else None) is not None:
-            return _run_torchdot(self._dense_device_op, self.shape, x_torch, relu=relu, exact=False, absmax=absmax)
-        return _run_torchdot(self._device_op, self.shape, x_torch, relu=relu, exact=True, absmax=absmax)
+        return _run_torchdot(self, x_torch, relu=relu, exact=exact, absmax=absmax)
 
     def dot(self, x_numpy):
         assert isinstance(x_numpy, np.ndarray)
@@ -262,9 +266,6 @@ class FactoredSparseMatrix(SparseMatrix):
     def _dense_device_op(self, device=None):
         return None
 
-    def torchdot(self, x_torch, relu=False, exact=True, absmax=None):
-        return _run_torchdot(self._device_op, self.shape, x_torch, relu=relu, exact=True, absmax=absmax)       # always the reference's order
-
     @staticmethod
     def proven(M, factored, max_zero_fraction=0.01):
         """Is the stored CSR `M` (scipy) exactly -- indptr, indices AND values, in stored order -- the canonical expansion of `factored` with its
@@ -347,9 +348,7 @@ class TiledMatrix(SparseMatrix):
 
     def torchdot(self, x, relu=False, exact=True, absmax=None):
         """[cols, N] -> [rows, N] (keynet/sparse.py:603-612); always the order-preserving path (bit-exact)."""
-        if isinstance(x, np.ndarray):
-            x = torch.as_tensor(x)
-        return _run_torchdot(self._device_op, self.shape, x, relu=relu, exact=True, absmax=absmax)
+        return _run_torchdot(self, x, relu=relu, exact=True, absmax=absmax)
 
     def dot(self, x):
         assert isinstance(x, np.ndarray)
@@ -580,14 +579,8 @@ class Conv2dTiledMatrix(TiledMatrix):
         operator applied as spatial mixing per tap, then channel mixing (see _split_ops: another association of the sum, tolerance contract only); exact='bf16x3': f32 products
         emulated on the bf16 matrix pipe (three-way exact split, six of nine cross products, f32 accumulate: KN_FLAG_BF16X3) where the
         operator and batch qualify, else the f32 MFMA path."""
-        if isinstance(x, np.ndarray):
-            x = torch.as_tensor(x)
-        if isinstance(exact, str):
-            assert exact in ('bf16x3', 'split'), "exact must be True, False, 'bf16x3' or 'split'"
-            if exact == 'split':
-                return self._torchdot_split(x, relu=relu, absmax=absmax)
-            return _run_torchdot(self._device_op, self.shape, x, relu=relu, exact=False, extra_flags=_capi.KN_FLAG_BF16X3, absmax=absmax)
-        return _run_torchdot(self._device_op, self.shape, x, relu=relu, exact=exact, absmax=absmax)
+        assert not isinstance(exact, str) or exact in ('bf16x3', 'split'), "exact must be True, False, 'bf16x3' or 'split'"
+        return _run_torchdot(self, x, relu=relu, exact=exact, absmax=absmax)
 
     # ---- the SPLIT application of a filled-in operator (tolerance contract only) -----------------------------------------------------
     # A factored keyed conv is  sum_t F_t (x) K_t  with F_t the Cout x Cin matrix of tap t and K_t = a_out S_t a_in^-1 the HoWo x HiWi spatial
@@ -652,15 +645,8 @@ class Conv2dTiledMatrix(TiledMatrix):
             return (opK, op2)
         return _on_device(self, '_op_split', make, device)
 
-    def _torchdot_split(self, x, relu=False, absmax=None):
-        assert self.shape[1] == x.shape[0], 'Non-conformal shape for W=%s, x=%s' % (str(self.shape), str(tuple(x.shape)))
-        if not torch.cuda.is_available():
-            raise _capi.KeynetHipError('keynet_amd: no MI355X visible -- the keyed forward has no CPU fallback')
-        src_device = x.device
-        xd = x.detach()
-        xd = xd if xd.dtype == torch.float32 else xd.float()
-        xd = xd if xd.is_cuda else xd.cuda()
-        xd = xd if xd.is_contiguous() else xd.contiguous()
+    def _torchdot_split(self, xd, relu=False, absmax=None):
+        """xd: the device block (_device_block) [cols, N] -> [rows, N] on its device."""
         (Cin, Hin, Win) = self._inshape
         (HoWo, HiWi, nt) = (self._outshape[1] * self._outshape[2], Hin * Win, len(self._taps['taps']))
         has_last = self._taps['lastcol'] is not None
@@ -691,7 +677,7 @@ class Conv2dTiledMatrix(TiledMatrix):
                 if has_last:
                     z[-1, :w].copy_(xd[-1, c0:c0 + w])
                 op2.spmm(z.data_ptr(), ldz, w, y.data_ptr() + 4 * c0, n, flags, st, absmax_ptr=None if absmax is None else absmax.data_ptr())
-        return y if src_device.type == 'cuda' else y.to(src_device)
+        return y
 
     def _expand_taps_host(self, pixels=None, channels=None):
         """Canonical CSR of a factored operator -- or of its output rows (co, o) for o in `pixels` only, numbered

@@ -9,7 +9,6 @@ the MI355X: layers exchange feature-major [D+1, N] blocks, ReLU is fused into th
 supported (the reference's KeyedModel.forward is N=1 only).
 """
 import copy
-import os
 import warnings
 from collections import OrderedDict
 import numpy as np
@@ -124,8 +123,7 @@ class KeyedModel(object):
         """Whole key-nets are pickled by the reference's users (test/test_keynet.py:106, vipy.util.save): device-side state -- the overlapped
         forward's workspaces and streams, the whole-net kernel's handle -- is dropped and rebuilt on first use (operators: SparseMatrix.__getstate__)."""
         d = dict(self.__dict__)
-        d.pop('_overlap_plans', None)
-        d.pop('_chain_ops', None)
+        self._drop_plans(d)
         return d
 
     def __setstate__(self, d):
@@ -137,8 +135,45 @@ class KeyedModel(object):
         return getattr(self.__dict__['_keynet'], attr)
 
     # -- the hot path -------------------------------------------------------------------------------------------
-    RESCREEN = True              # re-screen the float-key contract on every forward (KN_NO_RESCREEN=1: A/B switch, read per call)
+    RESCREEN = True              # re-screen the float-key contract on every forward
     RESCREEN_MAX_PASSES = 4
+    # A/B switches of the diagnostic tools (tools/ab_rescreen.py) and tests, read here and nowhere else:
+    RESCREEN_READ = True         # False: gather the maxima but skip the host read -- what the read itself costs
+    OVERLAP_AUTO = True          # False: forward_linear(overlap=None) never chooses the overlapped forward
+    CHAIN = True                 # False: the launch-per-layer forward instead of the whole-net kernel
+
+    # -- the launch list: one walk over the key-net's layers, read by everything that launches kernels ------------------------
+    def _keyed(self, named=False):
+        """The keyed layers in order (named: (name, layer) pairs)."""
+        return [(n, c) if named else c for (n, c) in self._keynet.named_children() if isinstance(c, klayer.KeyedLayer)]
+
+    def _steps(self):
+        """The key-net in launch order: [(k, layer, relu)] -- keyed layer number k, with `relu` when the unkeyed nn.ReLU behind it is fused into
+        its kernel (keynet/system.py:92); a stand-alone nn.ReLU (nothing in front of it to fuse it into) is the step (None, module, False)."""
+        (steps, k, fused) = ([], 0, False)
+        children = list(self._keynet.children())
+        for (i, c) in enumerate(children):
+            if isinstance(c, klayer.KeyedLayer):
+                fused = (i + 1 < len(children)) and isinstance(children[i + 1], nn.ReLU)
+                steps.append((k, c, fused))
+                k += 1
+            elif isinstance(c, nn.ReLU):
+                if not fused:
+                    steps.append((None, c, False))
+                fused = False
+            else:
+                raise ValueError('unsupported module in a key-net: %s' % str(type(c)))
+        return steps
+
+    def _signature(self):
+        """What a cached launch list is valid for: the layers' current (operator, contract) identities."""
+        return tuple((id(c.W), getattr(c, '_exact', True)) for c in self._keyed())
+
+    def _drop_plans(self, d=None):
+        """Forget the cached launch lists (_overlap_plan, _chain_op): wherever a contract changes, to release their workspaces, and from a pickled state `d`."""
+        d = self.__dict__ if d is None else d
+        d.pop('_overlap_plans', None)
+        d.pop('_chain_ops', None)
 
     def forward_linear(self, img_cipher, overlap=None):
         """[N, D0+1] -> [N, classes+1]: the nn.Sequential of keynet/system.py:132 with the unkeyed ReLUs fused into the
@@ -175,7 +210,7 @@ class KeyedModel(object):
         an untiled key-net, no image -- passes through as one window."""
         if not x.is_cuda and x.dim() == 2 and torch.cuda.is_available():
             x = x.detach().float().cuda()
-        keyed = [c for c in self._keynet.children() if isinstance(c, klayer.KeyedLayer)]
+        keyed = self._keyed()
         n = x.shape[0]
         if not (x.is_cuda and x.dim() == 2 and x.dtype == torch.float32 and n > 0 and any(isinstance(c.W, ksp.Conv2dTiledMatrix) for c in keyed)):
             return (x, [(0, n)])
@@ -197,16 +232,15 @@ class KeyedModel(object):
         """The screened forward of a prepared batch: (y, screens).  A pass whose screen re-calibrates a layer runs again (calibrating on its own images),
         then every other pass again: the batch comes out of ONE set of contracts.  At most RESCREEN_MAX_PASSES runs of a pass; then only the last pass is
         re-screened (the next forward decides).  Under a HIP-graph capture nothing is read: `screens` = (slots, screened) per pass, for capture's replay."""
-        keyed = [c for c in self._keynet.children() if isinstance(c, klayer.KeyedLayer)]
+        keyed = self._keyed()
         on_dev = x.is_cuda and x.dim() == 2
-        read = (on_dev and not torch.cuda.is_current_stream_capturing() and
-                os.environ.get('KN_RESCREEN_NOREAD') != '1')      # DIAGNOSTIC (tools/ab_rescreen.py): gather the maxima but skip the host read -- what the read itself costs
+        read = on_dev and not torch.cuda.is_current_stream_capturing() and self.RESCREEN_READ
         ys = [None] * len(windows)
         (todo, screens, redos) = (list(range(len(windows))), [], 0)
         while todo:
             k = todo.pop(0)
             screened = set()
-            if on_dev and self.RESCREEN and os.environ.get('KN_NO_RESCREEN') != '1' and not any(getattr(c, '_exact', True) == 'auto' for c in keyed):
+            if on_dev and self.RESCREEN and not any(getattr(c, '_exact', True) == 'auto' for c in keyed):
                 screened = set(j for (j, c) in enumerate(keyed) if c.screened())
             slots = torch.zeros(len(keyed) + 1, dtype=torch.float32, device=x.device) if screened else None
             (lo, hi) = windows[k]
@@ -233,7 +267,7 @@ class KeyedModel(object):
             c.__dict__.pop('_contract_record', None)
         if redo:
             self.__dict__['_recalibrations'] = self.__dict__.get('_recalibrations', 0) + len(redo)
-            self.__dict__.pop('_overlap_plans', None)
+            self._drop_plans()
         return redo
 
     BATCH_TILE = 128           # _prepare pads a device batch of a tiled-conv key-net to whole multiples of this many images
@@ -244,9 +278,9 @@ class KeyedModel(object):
         is re-screened): slot k receives max |x| of keyed layer k -- slot 0 by one pass over the input, slot k + 1 by the kernel that
         produces layer k's output."""
         forced = overlap is True
-        if overlap is None and os.environ.get('KN_NO_OVERLAP') == '1':      # A/B switch
+        if overlap is None and not self.OVERLAP_AUTO:
             overlap = False
-        if any(getattr(c, '_exact', True) == 'auto' for c in self._keynet.children() if isinstance(c, klayer.KeyedLayer)):
+        if any(getattr(c, '_exact', True) == 'auto' for c in self._keyed()):
             overlap = False        # first forward of an 'auto' key-net: the layers calibrate their contract one by one (KeyedLayer._calibrate)
         if overlap is None:
             overlap = (img_cipher.is_cuda and img_cipher.dtype == torch.float32 and img_cipher.dim() == 2 and img_cipher.shape[0] >= 256 and
@@ -261,22 +295,12 @@ class KeyedModel(object):
             plan = self._overlap_plan(img_cipher.device, img_cipher.shape[0], force=forced)
             if plan is not None and img_cipher.is_cuda and img_cipher.dtype == torch.float32 and img_cipher.t().is_contiguous():
                 return self._forward_overlapped(img_cipher.detach(), plan, slots, screened)
-        children = list(self._keynet.children())
         y = img_cipher
-        i = 0
-        k = 0
-        while i < len(children):
-            c = children[i]
-            if isinstance(c, klayer.KeyedLayer):
-                fuse = (i + 1 < len(children)) and isinstance(children[i + 1], nn.ReLU)
-                y = c.forward(y, fuse_relu=fuse, absmax=slots[k + 1:k + 2] if (slots is not None and (k + 1) in screened) else None)
-                i += 2 if fuse else 1
-                k += 1
-            elif isinstance(c, nn.ReLU):
+        for (k, c, relu) in self._steps():
+            if k is None:
                 y = _relu_block(y)
-                i += 1
             else:
-                raise ValueError('unsupported module in a key-net: %s' % str(type(c)))
+                y = c.forward(y, fuse_relu=relu, absmax=slots[k + 1:k + 2] if (slots is not None and (k + 1) in screened) else None)
         return y
 
     # -- whole-net kernel: every operator of a small untiled key-net in ONE launch, activations in LDS (csrc/kn_chain.hip) --------
@@ -285,13 +309,12 @@ class KeyedModel(object):
 
     def _chain_op(self, device):
         """kn_chain_create handle for this key-net on `device`, or None when it does not qualify: every layer a keyed layer under the
-        bit-exact contract whose operator is a plain / tiled CSR container, every ReLU fusable into its producer, at most 12 operators,
+        bit-exact contract whose operator is a plain / tiled CSR container in float32 (KeyedLayer.launch), every ReLU fusable into its producer, at most 12 operators,
         and the activations of four batch columns of any two consecutive layers within the CU's 160 KiB of LDS (LeNet_AvgPool: 92 KB).
-        KN_NO_CHAIN=1 (A/B switch, read per call) selects the launch-per-layer forward instead."""
-        if os.environ.get('KN_NO_CHAIN') == '1':
+        KeyedModel.CHAIN = False selects the launch-per-layer forward instead."""
+        if not self.CHAIN:
             return None
-        children = list(self._keynet.children())
-        sig = tuple((id(c.W), getattr(c, '_exact', True)) if isinstance(c, klayer.KeyedLayer) else None for c in children)
+        sig = self._signature()
         cache = self.__dict__.setdefault('_chain_ops', {})
         hit = cache.get(device.index)
         if hit is not None and hit[0] == sig:
@@ -299,27 +322,16 @@ class KeyedModel(object):
         if torch.cuda.is_current_stream_capturing():
             return None                  # building the chain allocates: not inside a HIP-graph capture (KeyedModel.capture runs an eager forward first)
         op = None
-        steps = []
-        i = 0
-        ok = 0 < len(children)
-        while ok and i < len(children):
-            c = children[i]
-            if (not isinstance(c, klayer.KeyedLayer) or getattr(c, '_exact', True) is not True or isinstance(c.W, ksp.Conv2dTiledMatrix) or not isinstance(c.W, ksp.SparseMatrix) or
-                    c.W.is_float64()):                  # (a float64 operator computes in float64: its own row kernel, one launch per layer)
-                ok = False
-                break
-            fuse = (i + 1 < len(children)) and isinstance(children[i + 1], nn.ReLU)
-            steps.append((c.W, _capi.KN_FLAG_RELU if (fuse or c.iskeyedrelu()) else 0))
-            i += 2 if fuse else 1
-        if ok and len(steps) <= self.CHAIN_MAX_OPS:
+        launches = [None if k is None else c.launch(device, relu) for (k, c, relu) in self._steps()]
+        if 0 < len(launches) <= self.CHAIN_MAX_OPS and all(la is not None and la.exact and not la.is_conv for la in launches):
             feat = [0, 0]
-            for (l, (W, _)) in enumerate(steps):
-                feat[l & 1] = max(feat[l & 1], int(W.shape[1]))
-                feat[(l & 1) ^ 1] = max(feat[(l & 1) ^ 1], int(W.shape[0]))
-            if (feat[0] + feat[1] + 1) * 16 <= self.CHAIN_LDS_BYTES and all(steps[l][0].shape[1] == steps[l - 1][0].shape[0] for l in range(1, len(steps))):
+            for (l, la) in enumerate(launches):
+                feat[l & 1] = max(feat[l & 1], la.cols)
+                feat[(l & 1) ^ 1] = max(feat[(l & 1) ^ 1], la.rows)
+            if (feat[0] + feat[1] + 1) * 16 <= self.CHAIN_LDS_BYTES and all(launches[l].cols == launches[l - 1].rows for l in range(1, len(launches))):
                 try:
                     with torch.cuda.device(device):
-                        op = _capi.Operator.chain([W._device_op(device) for (W, _) in steps], [f for (_, f) in steps])
+                        op = _capi.Operator.chain([la.op for la in launches], [la.flags & _capi.KN_FLAG_RELU for la in launches])
                 except _capi.KeynetHipError as e:
                     # the launch-per-layer forward computes the same thing (bit for bit): a device without 160 KiB of LDS per workgroup, or
                     # no memory left for the packed copy, must not fail the forward.  The failure is cached: no rebuild on every call.
@@ -332,11 +344,7 @@ class KeyedModel(object):
         """[N, D0+1] -> [N, classes+1] through the whole-net kernel; stream-ordered on torch's current HIP stream."""
         (rows, cols) = chain.shape()
         assert x.shape[1] == cols, 'Non-conformal shape for the key-net input: %s' % str(tuple(x.shape))
-        xt = x.detach().t()
-        if xt.dtype != torch.float32:
-            xt = xt.float()
-        if not xt.is_contiguous():
-            xt = xt.contiguous()
+        xt = ksp._device_block(x.t())
         n = xt.shape[1]
         y = torch.empty((rows, n), dtype=torch.float32, device=xt.device)
         with torch.cuda.device(xt.device):
@@ -348,55 +356,40 @@ class KeyedModel(object):
     OVERLAP_PLANS_KEPT = 2       # least-recently-used plans beyond this are dropped (a service that sees many batch sizes must not pile up workspaces)
 
     def _overlap_plan(self, device, batch, force=False):
-        """Launch list + segments for the overlapped forward, or None when this key-net / batch does not qualify.  A layer is run
-        per half only if the half batch keeps it on the same kernel instantiation as the whole batch (conv tiles are 128 or 256
-        batch columns wide) and it is a matrix-core conv layer; see the segment rule below."""
+        """Launch list (KeyedLayer.launch of every step) + segments for the overlapped forward, or None when this key-net / batch does not
+        qualify.  A layer is run per half only if the half batch keeps it on the same kernel instantiation as the whole batch (conv tiles are
+        128 or 256 batch columns wide) and it is a matrix-core conv layer; see the segment rule below."""
         key = (device.index, batch, bool(force))
         plans = self.__dict__.setdefault('_overlap_plans', OrderedDict())
-        # a plan caches operator handles and flags: it is only valid for the layers' current (operator, contract) identities
-        sig = tuple((id(c.W), getattr(c, '_exact', True)) for c in self._keynet.children() if isinstance(c, klayer.KeyedLayer))
+        sig = self._signature()
         if key in plans and plans[key][0] == sig:
             plans.move_to_end(key)
             return plans[key][1]
         plans.pop(key, None)
         plan = None
         half = batch // 2
-        children = list(self._keynet.children())
-        big = force or self._macs_per_image() * batch >= self.OVERLAP_MIN_MACS
-        f64 = any(isinstance(c, klayer.KeyedLayer) and c.W.is_float64() for c in children)      # float64 operators return float64 blocks: layer by layer
-        if big and not f64 and batch % 8 == 0 and half % 128 == 0 and all(isinstance(c, (klayer.KeyedLayer, nn.ReLU)) for c in children):
-            steps = []
-            i = 0
-            while i < len(children) and steps is not None:
-                c = children[i]
-                if not isinstance(c, klayer.KeyedLayer):
-                    steps = None                                   # a ReLU that could not be fused into a producer: simple path
+        if (force or self._macs_per_image() * batch >= self.OVERLAP_MIN_MACS) and batch % 8 == 0 and half % 128 == 0:
+            (steps, halves) = ([], [])           # halves[k]: the half batch keeps step k on the whole batch's kernel instantiation
+            for (k, c, relu) in self._steps():
+                la = None if k is None else c.launch(device, relu)
+                if la is None:
+                    # a ReLU that could not be fused into a producer, a layer still to calibrate, one applied in two steps (Conv2dTiledMatrix._split_ops),
+                    # a float64 operator (returns float64 blocks): layer by layer on the simple path
+                    steps = []
                     break
-                fuse = (i + 1 < len(children)) and isinstance(children[i + 1], nn.ReLU)
-                contract = getattr(c, '_exact', True)
-                if contract == 'split':
-                    steps = None                                   # a layer applied in two steps (Conv2dTiledMatrix._split_ops) is not one launch: simple path
-                    break
-                exact = contract is True or contract == 'auto'
-                W = c.W
-                relu = fuse or c.iskeyedrelu()
-                if type(W) is ksp.SparseMatrix and not exact and W._dense_device_op(device) is not None:
-                    (op, ex, ok) = (W._dense_device_op(device), False, half % 128 == 0)
-                elif isinstance(W, ksp.Conv2dTiledMatrix):
-                    (op, ex) = (W._device_op(device), exact)
+                ok = True
+                if la.is_conv:
                     # order-preserving conv kernels: 256-column tiles (four batch columns per lane).  They also have a 128-column form (two per lane), but
                     # that one is 5-8 % slower per layer (round 5, same-process A/B on every VGG-16 layer shape: conv5_1 4.08 against 3.88 ms) and the
                     # bit-exact forward of 256 images as two overlapped 128-column windows lost 11 % (1 884 against 2 107 images/s): not split.  MFMA tiles
                     # are 128 (Cout > 64) or 256 columns wide
-                    ok = (half % 256 == 0) if exact else (half % (128 if W._outshape[0] > 64 else 256) == 0)
-                    with torch.cuda.device(device):          # kn_spmm_plan checks the current device like kn_spmm does
-                        if contract == 'bf16x3' and 'bf16x3' in op.plan(batch, _capi.KN_FLAG_BF16X3) and 'bf16x3' not in op.plan(half, _capi.KN_FLAG_BF16X3):
-                            ok = False     # (cannot happen with 128-column tiles; kept as a guard: a half batch must keep the kernel family)
-                else:
-                    (op, ex, ok) = (W._device_op(device), True, True)
-                flags = (_capi.KN_FLAG_RELU if relu else 0) | (_capi.KN_FLAG_EXACT if ex else 0) | (_capi.KN_FLAG_BF16X3 if (contract == 'bf16x3' and not ex) else 0)
-                steps.append((op, int(W.shape[0]), int(W.shape[1]), flags, ok, 'Linear' in c._layertype, isinstance(W, ksp.Conv2dTiledMatrix)))
-                i += 2 if fuse else 1
+                    ok = (half % 256 == 0) if la.exact else (half % (128 if c.W._outshape[0] > 64 else 256) == 0)
+                    if la.flags & _capi.KN_FLAG_BF16X3:
+                        with torch.cuda.device(device):          # kn_spmm_plan checks the current device like kn_spmm does
+                            if 'bf16x3' in la.op.plan(batch, _capi.KN_FLAG_BF16X3) and 'bf16x3' not in la.op.plan(half, _capi.KN_FLAG_BF16X3):
+                                ok = False     # (cannot happen with 128-column tiles; kept as a guard: a half batch must keep the kernel family)
+                steps.append(la)
+                halves.append(ok)
             if steps:
                 # ONE split region: from the first layer after which every layer keeps its kernel instantiation on a half batch (VGG at 256
                 # images: conv1_1 / conv1_2 need 256-wide tiles and run whole) up to the trailing fully connected layers (too small to fill
@@ -406,17 +399,17 @@ class KeyedModel(object):
                 # matrix-core conv layers have short-lived workgroups and gain nothing (AllConvNet at 4096 images: 108.7 k images/s
                 # overlapped vs 109.2 k plain), so for them the plain forward is used.
                 join_at = len(steps)
-                while join_at > 0 and steps[join_at - 1][5]:
+                while join_at > 0 and steps[join_at - 1].is_linear:
                     join_at -= 1
                 split_at = join_at
-                while split_at > 0 and steps[split_at - 1][4]:
+                while split_at > 0 and halves[split_at - 1]:
                     split_at -= 1
-                mfma = any(st[6] and not (st[3] & _capi.KN_FLAG_EXACT) for st in steps[split_at:join_at])
+                mfma = any(la.is_conv and not (la.flags & _capi.KN_FLAG_EXACT) for la in steps[split_at:join_at])
                 segs = []
                 if join_at - split_at >= 2 and (mfma or force):
                     segs = [sg for sg in (('whole', 0, split_at), ('split', split_at, join_at), ('whole', join_at, len(steps))) if sg[2] > sg[1]]
                 if any(sg[0] == 'split' for sg in segs):
-                    rows_max = max(st[1] for st in steps)
+                    rows_max = max(la.rows for la in steps)
                     plan = dict(steps=steps, segments=segs,
                                 bufs=[torch.empty(rows_max * batch, dtype=torch.float32, device=device) for _ in range(2)],
                                 streams=[torch.cuda.Stream(device=device), torch.cuda.Stream(device=device)])
@@ -428,19 +421,16 @@ class KeyedModel(object):
     def _macs_per_image(self):
         """Multiply-adds per image of the keyed forward from the host descriptions (factored conv operators count their expansion)."""
         total = 0.0
-        for c in self._keynet.children():
-            if isinstance(c, klayer.KeyedLayer):
-                W = c.W
-                if isinstance(W, ksp.Conv2dTiledMatrix) and W._taps is not None:
-                    total += float(len(W._taps['ent_out'])) * W._outshape[0] * W._inshape[0]
-                else:
-                    total += float(W.nnz())
+        for W in (c.W for c in self._keyed()):
+            if isinstance(W, ksp.Conv2dTiledMatrix) and W._taps is not None:
+                total += float(len(W._taps['ent_out'])) * W._outshape[0] * W._inshape[0]
+            else:
+                total += float(W.nnz())
         return total
 
     def release_workspace(self):
         """Drop the activation workspaces and side streams of the overlapped forward (two ping-pong blocks per batch size)."""
-        self.__dict__.pop('_overlap_plans', None)
-        self.__dict__.pop('_chain_ops', None)
+        self._drop_plans()
 
     def _forward_overlapped(self, x, plan, slots=None, screened=()):
         """x: [N, D0+1] whose transpose is a contiguous feature-major block.  Layers ping-pong between two flat workspaces with the
@@ -468,8 +458,7 @@ class KeyedModel(object):
             for (kind, k0, k1) in segs:
                 if kind == 'whole':
                     for k in range(k0, k1):
-                        (op, rows, cols, flags) = steps[k][:4]
-                        op.spmm(src_of(k), N, N, bufs[k % 2].data_ptr(), N, flags, main.cuda_stream, absmax_ptr=slot_of(k))
+                        steps[k].op.spmm(src_of(k), N, N, bufs[k % 2].data_ptr(), N, steps[k].flags, main.cuda_stream, absmax_ptr=slot_of(k))
                     continue
                 for st in side:
                     st.wait_stream(main)
@@ -478,15 +467,14 @@ class KeyedModel(object):
                         kk = k - h                                 # stream 1 runs one kernel behind stream 0
                         if kk < k0 or kk >= k1:
                             continue
-                        (op, rows, cols, flags) = steps[kk][:4]
-                        op.spmm(src_of(kk) + 4 * half * h, N, half, bufs[kk % 2].data_ptr() + 4 * half * h, N, flags, st.cuda_stream, absmax_ptr=slot_of(kk))
+                        steps[kk].op.spmm(src_of(kk) + 4 * half * h, N, half, bufs[kk % 2].data_ptr() + 4 * half * h, N, steps[kk].flags, st.cuda_stream, absmax_ptr=slot_of(kk))
                     if k == k0:
                         ev = torch.cuda.Event()
                         ev.record(side[0])
                         side[1].wait_event(ev)
                 for st in side:
                     main.wait_stream(st)
-            rows_out = steps[-1][1]
+            rows_out = steps[-1].rows
             out = bufs[(n - 1) % 2][:rows_out * N].view(rows_out, N).clone()      # the workspace is reused by the next call
             plan['done'] = torch.cuda.Event()
             plan['done'].record(main)
@@ -501,18 +489,16 @@ class KeyedModel(object):
         matrix pipe (three-way split, six of nine cross products: KN_FLAG_BF16X3) and keeps it when its result, measured against the
         order-preserving kernel on the calibration batch, has 4x headroom under the tolerance (EXPERIMENTAL, opt-in); 'bf16x3' forces that
         kernel wherever it applies; None = back to the per-layer setting the key-net was built with (tiled key-nets: 'auto').  Returns self."""
-        for c in self._keynet.children():
-            if isinstance(c, klayer.KeyedLayer):
-                if not hasattr(c, '_exact_built'):
-                    c._exact_built = getattr(c, '_exact_decl', getattr(c, '_exact', True))
-                if flag == 'auto-bf16x3':        # 'auto' with the bf16x3 kernel as the first candidate (opt-in: never chosen by default)
-                    (c._exact, c._allow_bf16x3) = ('auto', True)
-                else:
-                    c._exact = c._exact_built if flag is None else klayer._contract(flag, True)
-                    c._allow_bf16x3 = False
-                c.__dict__.pop('_contract_record', None)
-        self.__dict__.pop('_overlap_plans', None)                  # the launch lists depend on the layers' contracts
-        self.__dict__.pop('_chain_ops', None)
+        for c in self._keyed():
+            if not hasattr(c, '_exact_built'):
+                c._exact_built = getattr(c, '_exact_decl', getattr(c, '_exact', True))
+            if flag == 'auto-bf16x3':        # 'auto' with the bf16x3 kernel as the first candidate (opt-in: never chosen by default)
+                (c._exact, c._allow_bf16x3) = ('auto', True)
+            else:
+                c._exact = c._exact_built if flag is None else klayer._contract(flag, True)
+                c._allow_bf16x3 = False
+            c.__dict__.pop('_contract_record', None)
+        self._drop_plans()                  # the launch lists depend on the layers' contracts
         return self
 
     def contract_report(self):
@@ -520,14 +506,11 @@ class KeyedModel(object):
         record of that decision (bound, measured difference, tolerance, max |x| it covers).  `switched` lists the layers calibration moved
         off the matrix cores; `rescreen` says whether every forward re-checks the decisions; `recalibrations` counts the layers a later,
         larger batch sent back to calibration."""
-        rows = []
-        for (n, c) in self._keynet.named_children():
-            if isinstance(c, klayer.KeyedLayer):
-                rows.append(dict(name=n, exact=getattr(c, '_exact', True), declared=getattr(c, '_exact_decl', getattr(c, '_exact', True)),
-                                 calibration=getattr(c, '_contract_record', None), screened=c.screened()))
+        rows = [dict(name=n, exact=getattr(c, '_exact', True), declared=getattr(c, '_exact_decl', getattr(c, '_exact', True)),
+                     calibration=getattr(c, '_contract_record', None), screened=c.screened()) for (n, c) in self._keyed(named=True)]
         return dict(layers=rows, switched=[r['name'] for r in rows if r['calibration'] is not None and r['calibration'].get('decided') == 'exact' and 'bound' in r['calibration']],
                     undecided=[r['name'] for r in rows if r['exact'] == 'auto'],
-                    rescreen=bool(self.RESCREEN and os.environ.get('KN_NO_RESCREEN') != '1' and any(r['screened'] for r in rows)),
+                    rescreen=bool(self.RESCREEN and any(r['screened'] for r in rows)),
                     recalibrations=int(self.__dict__.get('_recalibrations', 0)))
 
     _LEVEL = {'bf16x3': 0, 'split': 1, False: 2, True: 3}       # codes of a decided contract on the wire (sync_contract); only True (the reference's order) outranks the others
@@ -546,7 +529,7 @@ class KeyedModel(object):
         import torch.distributed as dist
         if not (dist.is_available() and dist.is_initialized()):
             return []
-        named = [(n, c) for (n, c) in self._keynet.named_children() if isinstance(c, klayer.KeyedLayer)]
+        named = self._keyed(named=True)
         mine = [self._LEVEL.get(getattr(c, '_exact', True), -1) if getattr(c, '_exact', True) != 'auto' else -1 for (_, c) in named]
         dev = torch.device('cpu') if dist.get_backend(group) == 'gloo' else torch.device('cuda', torch.cuda.current_device())
         t = torch.tensor([mine, [(-m if m >= 0 else -99) for m in mine]], dtype=torch.int32, device=dev)     # row 1: MAX of the negated codes = the smallest decided code
@@ -563,8 +546,7 @@ class KeyedModel(object):
             (c._exact, c._contract_record) = (True, rec)
             changed.append(n)
         if changed:
-            self.__dict__.pop('_overlap_plans', None)
-            self.__dict__.pop('_chain_ops', None)
+            self._drop_plans()
         return changed
 
     def capture(self, img_cipher):
@@ -578,7 +560,7 @@ class KeyedModel(object):
         assert img_cipher.is_cuda, 'capture() needs a device tensor'
         n = img_cipher.shape[0]
         (static_in, windows) = self._prepare(img_cipher.detach().t().clone(memory_format=torch.contiguous_format).t())     # the graph's own input block
-        keyed = [c for c in self._keynet.children() if isinstance(c, klayer.KeyedLayer)]
+        keyed = self._keyed()
         state = {}
 
         def build():
@@ -648,11 +630,8 @@ class KeyedModel(object):
 
 def _relu_block(y):
     """Stand-alone nn.ReLU on an [N, D+1] activation (only when it could not be fused into a producer)."""
-    if not torch.cuda.is_available():
-        raise _capi.KeynetHipError('keynet_amd: no MI355X visible -- the keyed forward has no CPU fallback')
     src = y.device
-    yt = y.detach().t().float()
-    yt = (yt if yt.is_cuda else yt.cuda()).contiguous().clone()
+    yt = ksp._device_block(y.t()).clone()
     _capi.relu(yt.data_ptr(), yt.shape[0], yt.shape[1], yt.shape[1], torch.cuda.current_stream().cuda_stream)
     out = yt.t()
     return out if src.type == 'cuda' else out.to(src)

@@ -260,10 +260,10 @@ def test_rescreen_switch_and_forced_modes(golden, monkeypatch):
     knet.forward_linear(xc)
     assert knet.contract_report()['rescreen'] is True
     big = sensor.fromtensor(1000.0 * x).encrypt().astensor()
-    monkeypatch.setenv('KN_NO_RESCREEN', '1')                # A/B switch: the round-3 behaviour
+    monkeypatch.setattr(ksys.KeyedModel, 'RESCREEN', False)  # A/B switch: the round-3 behaviour
     knet.forward_linear(big)
     assert knet.contract_report()['recalibrations'] == 0 and knet.contract_report()['rescreen'] is False
-    monkeypatch.delenv('KN_NO_RESCREEN')
+    monkeypatch.setattr(ksys.KeyedModel, 'RESCREEN', True)
     knet.exact_mode(False)                                   # forced onto the matrix cores: the caller's responsibility, not screened
     knet.forward_linear(big)
     assert knet.contract_report()['recalibrations'] == 0 and not any(r['screened'] for r in knet.contract_report()['layers'])

@@ -232,3 +232,70 @@ def test_host_expansion_sums_a_pairs_terms_in_entry_order():
     S = W.rows_csr(px).toarray()
     rows = (np.arange(Cout)[:, None] * HW + px[None, :]).ravel()
     assert np.array_equal(S, D[rows])
+
+
+def test_launch_list_and_the_contract_rule(monkeypatch):
+    """KeyedModel._steps (the one walk over a key-net's layers) and KeyedLayer.launch / kernel (the one rule contract -> operator handle + flags), without a device:
+    handle creation is stubbed, the decisions are not.  The table is the issue's: 'split' forced on an operator without a split form and 'bf16x3' on a non-conv
+    operator are the f32 matrix cores; a dense handle only for a plain SparseMatrix off the exact contract that has one; factored, tiled and float64 operators always
+    carry KN_FLAG_EXACT; 'auto', 'split' with a split form and float64 operators are not one launch."""
+    import scipy.sparse
+    from torch import nn
+    (RELU, EXACT, BF16X3) = (_capi.KN_FLAG_RELU, _capi.KN_FLAG_EXACT, _capi.KN_FLAG_BF16X3)
+    dev = torch.device('cuda', 0)
+    for cls in (ksp.SparseMatrix, ksp.FactoredSparseMatrix, ksp.TiledMatrix, ksp.Conv2dTiledMatrix):
+        monkeypatch.setattr(cls, '_device_op', lambda self, device=None: ('op', id(self), device))
+    monkeypatch.setattr(ksp.SparseMatrix, '_dense_device_op', lambda self, device=None: ('dense', id(self), device) if getattr(self, 'has_dense', False) else None)
+
+    def csr(dtype=np.float32, dense=False):
+        W = ksp.SparseMatrix(scipy.sparse.identity(5, dtype=dtype, format='csr'))
+        W.has_dense = dense
+        return W
+
+    def conv(taps=True):
+        W = ksp.Conv2dTiledMatrix.fromtaps((1, 2, 2), (1, 2, 2), np.ones((1, 1, 1), np.float32), np.arange(4), np.arange(4), np.zeros(4, np.int32), None, np.ones(5, np.float32))
+        if not taps:
+            W._taps = None              # as a block / tile description (the reference route): no split form
+        return W
+    tiled = ksp.TiledMatrix(scipy.sparse.identity(4, dtype=np.float32, format='csr'), (2, 2))
+    factored = ksp.FactoredSparseMatrix(scipy.sparse.identity(5, dtype=np.float32, format='csr'), conv())
+    table = [  # operator, contract, (handle kind, flags) or None
+        (csr(), True, ('op', EXACT)), (csr(), False, ('op', EXACT)), (csr(dense=True), True, ('op', EXACT)), (csr(dense=True), False, ('dense', 0)),
+        (csr(dense=True), 'bf16x3', ('dense', 0)), (csr(dense=True), 'split', ('dense', 0)), (csr(), 'split', ('op', EXACT)), (csr(), 'auto', None),
+        (csr(np.float64, dense=True), False, ('op', EXACT)), (factored, False, ('op', EXACT)), (factored, 'bf16x3', ('op', EXACT)), (tiled, False, ('op', EXACT)),
+        (tiled, 'split', ('op', EXACT)), (conv(), True, ('op', EXACT)), (conv(), False, ('op', 0)), (conv(), 'bf16x3', ('op', BF16X3)), (conv(), 'split', None),
+        (conv(taps=False), 'split', ('op', 0)), (conv(), 'auto', None)]
+    for (W, contract, want) in table:
+        for relu in (False, True):
+            got = KeyedLayer.kernel(W, contract, relu, dev)
+            assert (got is None) == (want is None), (W, contract)
+            if want is not None:
+                assert got[0](dev) == (want[0], id(W), dev) and got[1] == want[1] | (RELU if relu else 0), (W, contract, relu, got)
+
+    # launch(): the layer's own contract, the keyed ReLU's flag, what the planners read; a float64 operator is not one kn_spmm launch
+    c = KeyedLayer.fromoperator(conv(), "<class 'torch.nn.modules.conv.Conv2d'>", exact='bf16x3')
+    assert c.launch(dev, True) == (('op', id(c.W), dev), RELU | BF16X3, 5, 5, True, False, False)
+    r = KeyedLayer.fromoperator(csr(), "<class 'torch.nn.modules.activation.ReLU'>", exact=True)
+    la = r.launch(dev)
+    assert la.flags == RELU | EXACT and la.exact and not la.is_conv and not la.is_linear and (la.rows, la.cols) == (5, 5)
+    fc = KeyedLayer.fromoperator(csr(dense=True), "<class 'torch.nn.modules.linear.Linear'>", exact=False)
+    assert fc.launch(dev, True)[:2] == (('dense', id(fc.W), dev), RELU) and fc.launch(dev).is_linear and not fc.launch(dev).exact
+    assert KeyedLayer.fromoperator(csr(np.float64), 'x', exact=True).launch(dev) is None
+    assert KeyedLayer.fromoperator(conv(), 'x', exact='split').launch(dev) is None and KeyedLayer.fromoperator(conv(), 'x', exact='auto').launch(dev) is None
+
+    # _steps(): planted contracts, with and without a following nn.ReLU, a keyed ReLU layer, a ReLU with nothing in front of it to fuse it into
+    layers = [('a', KeyedLayer.fromoperator(csr(), 'Conv2d', exact=True)), ('relu_a', nn.ReLU()), ('b', KeyedLayer.fromoperator(conv(), 'Conv2d', exact=False)),
+              ('c', KeyedLayer.fromoperator(conv(), 'Conv2d', exact='bf16x3')), ('relu_c', nn.ReLU()), ('relu_c2', nn.ReLU()),
+              ('d', KeyedLayer.fromoperator(conv(taps=False), 'Conv2d', exact='split')), ('e', r), ('f', KeyedLayer.fromoperator(conv(), 'Conv2d', exact='auto')), ('relu_f', nn.ReLU())]
+    from collections import OrderedDict
+    knet = ksys.KeyedModel.fromlayers(OrderedDict(layers), (4, 1, 1))
+    steps = knet._steps()
+    assert [(k, relu) for (k, _, relu) in steps] == [(0, True), (1, False), (2, True), (None, False), (3, False), (4, False), (5, True)]
+    assert [c for (k, c, _) in steps if k is not None] == knet._keyed() == [m for (_, m) in layers if isinstance(m, KeyedLayer)] and steps[3][1] is knet.relu_c2
+    assert [None if (k is None or c.launch(dev, relu) is None) else c.launch(dev, relu).flags for (k, c, relu) in steps] == [RELU | EXACT, 0, RELU | BF16X3, None, 0, RELU | EXACT, None]
+    assert knet._signature() == tuple((id(m.W), m._exact) for (_, m) in layers if isinstance(m, KeyedLayer))
+    knet.__dict__.update(_overlap_plans={'x': 1}, _chain_ops={0: 1})
+    knet._drop_plans()
+    assert '_overlap_plans' not in knet.__dict__ and '_chain_ops' not in knet.__dict__
+    with pytest.raises(ValueError, match='unsupported module in a key-net'):
+        ksys.KeyedModel.fromlayers(OrderedDict(layers + [('tanh', nn.Tanh())]), (4, 1, 1))._steps()

@@ -195,10 +195,16 @@ def test_overlapped_forward_is_bit_identical(golden, name, n):
     xc = torch.as_tensor(z['x_cipher'])
     m = xc.shape[0]
     x = torch.cat([xc] * ((n + m - 1) // m), dim=0)[:n].to(dev()).t().contiguous().t()
+    y0 = knet.forward_linear(x, overlap=False)                   # (decides the tiled net's 'auto' layers: a layer still to calibrate has no launch to plan)
     assert knet._overlap_plan(x.device, n) is None                # these nets are small: the automatic choice is the plain forward
     plan = knet._overlap_plan(x.device, n, force=True)
     assert plan is not None and any(sg[0] == 'split' and sg[2] - sg[1] >= 2 for sg in plan['segments']) and plan['segments'][-1][0] == 'whole'   # trailing fc layers run whole
-    y0 = knet.forward_linear(x, overlap=False)
+    # the plan's launch list IS the layers' own rule (KeyedLayer.launch), step for step: the same handle, the same flags
+    steps = knet._steps()
+    assert len(steps) == len(plan['steps'])
+    for ((k, c, relu), st) in zip(steps, plan['steps']):
+        la = c.launch(x.device, relu)
+        assert st.op is la.op and st.flags == la.flags, (k, st, la)
     for _ in range(3):
         y1 = knet.forward_linear(x, overlap=True)
         assert torch.equal(y0, y1)
@@ -1226,7 +1232,7 @@ def test_whole_net_kernel_shares_value_sequences_between_pixels():
 
 
 def test_whole_net_kernel_is_what_small_keynets_run(golden, monkeypatch):
-    """LeNet_AvgPool (BASELINE configs[0]-[1]) takes the whole-net kernel by default; KN_NO_CHAIN=1 selects the launch-per-layer forward;
+    """LeNet_AvgPool (BASELINE configs[0]-[1]) takes the whole-net kernel by default; KeyedModel.CHAIN = False selects the launch-per-layer forward;
     both equal the reference's vectors bit for bit, for the golden batch, a ragged one and 1024 images."""
     z = golden('lenet_perm.npz')
     knet = kio.keynet_from_arrays(z)
@@ -1239,11 +1245,11 @@ def test_whole_net_kernel_is_what_small_keynets_run(golden, monkeypatch):
     assert np.array_equal(knet.forward_linear(xc[:5]).cpu().numpy(), z[last][:5])
     big = torch.cat([xc] * 128, dim=0)
     yb = knet.forward_linear(big)
-    monkeypatch.setenv('KN_NO_CHAIN', '1')
+    monkeypatch.setattr(ksys.KeyedModel, 'CHAIN', False)
     assert knet._chain_op(xc.device) is None
     assert torch.equal(yb, knet.forward_linear(big))
     assert np.array_equal(knet.forward_linear(xc).cpu().numpy(), z[last])
-    monkeypatch.delenv('KN_NO_CHAIN')
+    monkeypatch.setattr(ksys.KeyedModel, 'CHAIN', True)
     # a tiled key-net (matrix-core conv layers) and a key-net too wide for LDS do not qualify
     assert kio.keynet_from_arrays(golden('mini_tiled_permutation.npz'))._chain_op(xc.device) is None
 

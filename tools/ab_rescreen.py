@@ -1,4 +1,5 @@
-"""A/B: what the per-forward contract screen costs on the headline key-net (same process, interleaved): KN_NO_RESCREEN=1 vs default.
+"""A/B: what the per-forward contract screen costs on the headline key-net (same process, interleaved): KeyedModel.RESCREEN = False vs default
+(and RESCREEN_READ = False: gather the maxima, skip the host read).
 Also prints which kernels the screen adds (per forward) from the plan strings."""
 import os
 import sys
@@ -10,6 +11,7 @@ import torch
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 import bench  # noqa: E402
+from keynet_amd.system import KeyedModel  # noqa: E402
 
 
 def main():
@@ -32,16 +34,10 @@ def main():
     res = {'screen': [], 'noscreen': [], 'gather_only': []}
     for rnd in range(4):
         for mode in ('noscreen', 'gather_only', 'screen'):
-            os.environ.pop('KN_NO_RESCREEN', None)
-            os.environ.pop('KN_RESCREEN_NOREAD', None)
-            if mode == 'noscreen':
-                os.environ['KN_NO_RESCREEN'] = '1'
-            elif mode == 'gather_only':
-                os.environ['KN_RESCREEN_NOREAD'] = '1'
+            (KeyedModel.RESCREEN, KeyedModel.RESCREEN_READ) = (mode != 'noscreen', mode != 'gather_only')
             timed(2)
             res[mode].append(timed(10))
-    os.environ.pop('KN_NO_RESCREEN', None)
-    os.environ.pop('KN_RESCREEN_NOREAD', None)
+    (KeyedModel.RESCREEN, KeyedModel.RESCREEN_READ) = (True, True)
     for (k, v) in res.items():
         print('%-9s %s  median %.3f ms' % (k, ' '.join('%.3f' % t for t in v), float(np.median(v))))
     print('screen cost: %.3f ms per forward' % (float(np.median(res['screen'])) - float(np.median(res['noscreen']))))

@@ -12,9 +12,6 @@ import torch
 
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import bench  # noqa: E402
-from keynet_amd import _capi  # noqa: E402
-from keynet_amd import sparse as ksp  # noqa: E402
-from keynet_amd.layer import KeyedLayer  # noqa: E402
 
 
 def main():
@@ -32,20 +29,11 @@ def main():
     del x
     ref = knet.forward_linear(xc)
     torch.cuda.synchronize()
-    children = list(knet._keynet.named_children())
+    names = [n for (n, _) in knet._keyed(named=True)]
     plan = []
-    for (i, (name, c)) in enumerate(children):
-        if isinstance(c, KeyedLayer):
-            fuse = (i + 1 < len(children)) and isinstance(children[i + 1][1], torch.nn.ReLU)
-            exact = bool(getattr(c, '_exact', True))
-            if type(c.W) is ksp.SparseMatrix and not exact and c.W._dense_device_op(dev) is not None:
-                op = c.W._dense_device_op(dev)
-                ex = False
-            else:
-                op = c.W._device_op(dev)
-                ex = exact or not isinstance(c.W, ksp.Conv2dTiledMatrix)
-            flags = (_capi.KN_FLAG_RELU if (fuse or c.iskeyedrelu()) else 0) | (_capi.KN_FLAG_EXACT if ex else 0)
-            plan.append((name, op, c.W.shape[0], flags))
+    for (k, c, relu) in knet._steps():              # (every step of this key-net is one launch of a keyed layer: KeyedLayer.launch)
+        la = c.launch(dev, relu)
+        plan.append((names[k], la.op, la.rows, la.flags))
     x0 = xc.t().contiguous()                                # [D0+1, B]
     bufs = [torch.empty((rows, B), device=dev) for (_, _, rows, _) in plan]
     streams = [torch.cuda.Stream(device=dev), torch.cuda.Stream(device=dev)]
