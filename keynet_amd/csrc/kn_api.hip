@@ -23,43 +23,27 @@ int fail(int code, const std::string& msg) {
 // The library's only look at the environment: called once per operator create, the result is recorded in the handle (kn_internal.h: Tuning).
 Tuning tuning_from_env() {
     Tuning t;
-    struct Knob {
-        const char* name;
-        int Tuning::*field;
-    };
-    static const Knob knobs[] = {
-        {"KN_NO_SPTR", &Tuning::no_sptr}, {"KN_NO_SMALLK_PIPE", &Tuning::no_smallk_pipe}, {"KN_NO_GROUP_PIPE", &Tuning::no_group_pipe},
-        {"KN_NO_BIG_GROUPS", &Tuning::no_big_groups}, {"KN_NO_EXACT_TABLE", &Tuning::no_exact_table}, {"KN_GROUP_MFMA", &Tuning::group_mfma},
-        {"KN_BIG_MFMA16", &Tuning::big_mfma16}, {"KN_MF_NRB", &Tuning::mf_nrb}, {"KN_TABLE_NRB", &Tuning::table_nrb}, {"KN_NO_FILL_EXACT", &Tuning::no_fill_exact},
-        {"KN_NO_FILL_TILES2", &Tuning::no_fill_tiles2},
 #ifdef KN_ABLATION
-        {"KN_OCC", &Tuning::occ}, {"KN_NO_TAIL_SPLIT", &Tuning::no_tail_split}, {"KN_NO_SMALLK", &Tuning::no_smallk}, {"KN_EXACT_PIPE", &Tuning::exact_pipe},
-        {"KN_EXACT_COB_GROUPS", &Tuning::exact_cob_groups}, {"KN_EXACT_XD", &Tuning::exact_xd}, {"KN_EXACT_VEC", &Tuning::exact_vec}, {"KN_MF_PF", &Tuning::mf_pf},
-        {"KN_TABLE_WINDOW", &Tuning::table_window}, {"KN_TABLE_STRIP", &Tuning::table_strip}, {"KN_NO_PATCH", &Tuning::no_patch}, {"KN_CONV_BALL", &Tuning::conv_ball},
-        {"KN_NO_ROW_ORDER", &Tuning::no_row_order}, {"KN_CHAIN_NO_CL", &Tuning::chain_no_cl}, {"KN_CHAIN_NO_RPL2", &Tuning::chain_no_rpl2}, {"KN_CHAIN_NO_EARLY", &Tuning::chain_no_early}, {"KN_CHAIN_NO_SEQ", &Tuning::chain_no_seq}, {"KN_CHAIN_NO_SHARE", &Tuning::chain_no_share}, {"KN_FILL_FORM", &Tuning::fill_form}, {"KN_ABL", &Tuning::abl},
+    const bool diagnostic = true;
+#else
+    const bool diagnostic = false;
 #endif
-    };
-    for (const Knob& k : knobs)
-        if (const char* v = getenv(k.name)) t.*(k.field) = atoi(v);
+    const char* v = nullptr;
+#define KN_KNOB_ENV(name, env, def, diag) \
+    if ((diagnostic || !(diag)) && (v = getenv(env)) != nullptr) t.name = atoi(v);
+    KN_TUNING_KNOBS(KN_KNOB_ENV)
+#undef KN_KNOB_ENV
     t.mf_nrb = std::max(1, std::min(3, t.mf_nrb));
     if (t.table_nrb < 0 || t.table_nrb > 3) t.table_nrb = 0;
     return t;
 }
 
 std::string Tuning::describe() const {
-    static const Tuning d;
     std::string o;
-    auto add = [&](const char* n, int v, int dv) {
-        if (v != dv) o += (o.empty() ? "" : ",") + std::string(n) + "=" + std::to_string(v);
-    };
-    add("no_sptr", no_sptr, d.no_sptr); add("no_smallk_pipe", no_smallk_pipe, d.no_smallk_pipe); add("no_group_pipe", no_group_pipe, d.no_group_pipe);
-    add("no_big_groups", no_big_groups, d.no_big_groups); add("no_exact_table", no_exact_table, d.no_exact_table); add("group_mfma", group_mfma, d.group_mfma);
-    add("big_mfma16", big_mfma16, d.big_mfma16); add("mf_nrb", mf_nrb, d.mf_nrb); add("table_nrb", table_nrb, d.table_nrb); add("no_fill_exact", no_fill_exact, d.no_fill_exact);
-    add("no_fill_tiles2", no_fill_tiles2, d.no_fill_tiles2);
-    add("occ", occ, d.occ); add("no_tail_split", no_tail_split, d.no_tail_split); add("no_smallk", no_smallk, d.no_smallk); add("exact_pipe", exact_pipe, d.exact_pipe);
-    add("exact_cob_groups", exact_cob_groups, d.exact_cob_groups); add("exact_xd", exact_xd, d.exact_xd); add("exact_vec", exact_vec, d.exact_vec); add("mf_pf", mf_pf, d.mf_pf);
-    add("table_window", table_window, d.table_window); add("table_strip", table_strip, d.table_strip); add("no_patch", no_patch, d.no_patch); add("conv_ball", conv_ball, d.conv_ball);
-    add("no_row_order", no_row_order, d.no_row_order); add("chain_no_cl", chain_no_cl, d.chain_no_cl); add("chain_no_rpl2", chain_no_rpl2, d.chain_no_rpl2); add("chain_no_early", chain_no_early, d.chain_no_early); add("chain_no_seq", chain_no_seq, d.chain_no_seq); add("chain_no_share", chain_no_share, d.chain_no_share); add("fill_form", fill_form, d.fill_form); add("abl", abl, d.abl);
+#define KN_KNOB_TEXT(name, env, def, diag) \
+    if (name != (def)) o += (o.empty() ? "" : ",") + std::string(#name) + "=" + std::to_string(name);
+    KN_TUNING_KNOBS(KN_KNOB_TEXT)
+#undef KN_KNOB_TEXT
     return o.empty() ? o : " opts{" + o + "}";
 }
 
@@ -141,13 +125,12 @@ static int csr_create_impl(int64_t rows, int64_t cols, int64_t nnz, const int32_
 }
 
 // expanded canonical CSR of a conv-taps operator (tocsr() of the equivalent Conv2dTiledMatrix)
-static void convtaps_expand(const kn_operator* h, const std::vector<int64_t>& last_rows, const std::vector<float>& last_vals,
-                            std::vector<int32_t>& indptr, std::vector<int32_t>& indices, std::vector<float>& data) {
+static void convtaps_expand(const kn_operator* h, std::vector<int32_t>& indptr, std::vector<int32_t>& indices, std::vector<float>& data) {
     const ConvTapsDev& c = h->ct;
     const int64_t HoWo = c.Hout * c.Wout, HiWi = c.Hin * c.Win;
     std::vector<int64_t> r, cc;
     std::vector<float> v;
-    const size_t n = h->h_ent_out.size() * (size_t)(c.Cout * c.Cin) + last_rows.size();
+    const size_t n = h->h_ent_out.size() * (size_t)(c.Cout * c.Cin) + h->h_last_rows.size();
     r.reserve(n);
     cc.reserve(n);
     v.reserve(n);
@@ -161,10 +144,10 @@ static void convtaps_expand(const kn_operator* h, const std::vector<int64_t>& la
                 v.push_back(coef == 1.0f ? T[ic * c.Cin + jc] : coef * T[ic * c.Cin + jc]);
             }
     }
-    for (size_t k = 0; k < last_rows.size(); k++) {
-        r.push_back(last_rows[k]);
+    for (size_t k = 0; k < h->h_last_rows.size(); k++) {
+        r.push_back(h->h_last_rows[k]);
         cc.push_back(c.Cin * HiWi);
-        v.push_back(last_vals[k]);
+        v.push_back(h->h_last_vals[k]);
     }
     coo_to_csr(h->rows, r, cc, v, indptr, indices, data);
 }
@@ -178,7 +161,119 @@ struct ConvBuild {
     std::vector<int64_t> last_rows;   // explicit entries of the last column (row, value), may hold explicit zeros
     std::vector<float> last_vals;
     int64_t nnz_stored = 0;
+
+    // the caller's shapes, checked (both creators of a conv operator)
+    int set_shapes(const int64_t* inshape, const int64_t* outshape) {
+        for (int k = 0; k < 3; k++) {
+            KN_REQUIRE(inshape[k] > 0 && outshape[k] > 0 && inshape[k] < INT32_MAX && outshape[k] < INT32_MAX, KN_ERR_INVALID, "inshape / outshape entries must be positive");
+            this->inshape[k] = inshape[k];
+            this->outshape[k] = outshape[k];
+        }
+        return KN_OK;
+    }
 };
+
+// The slot lists of a conv-taps operator, derived from its entries and taps on the host side of the handle.  The entry order is not kept on the handle (filled-in
+// operators have up to 2^31 entries): convtaps_create_impl and kn_convtaps_drop_zero_entries both derive it here.
+struct SlotLists {
+    std::vector<char> tap_zero;     // [max(ntaps, 1)] the tap is zero altogether: it contributes nothing and its entries are dropped from the compute lists
+    std::vector<size_t> order;      // the other entries with a non-zero coefficient = the slots: grouped by output pixel, ascending input pixel inside a pixel
+    std::vector<int64_t> pix_ptr;   // [HoWo + 1] pixel o's slots are order[pix_ptr[o]] .. order[pix_ptr[o + 1]]
+};
+
+static SlotLists convtaps_slot_lists(const kn_operator* h) {
+    const ConvTapsDev& c = h->ct;
+    const int64_t HoWo = c.Hout * c.Wout, msz = c.Cout * c.Cin;
+    SlotLists sl;
+    sl.tap_zero.assign((size_t)std::max<int64_t>(c.ntaps, 1), 1);
+    for (int64_t t = 0; t < c.ntaps; t++)
+        for (int64_t k = 0; k < msz && sl.tap_zero[(size_t)t]; k++)
+            if (h->h_taps[(size_t)(t * msz + k)] != 0.0f) sl.tap_zero[(size_t)t] = 0;
+    const size_t nent = h->h_ent_out.size();
+    sl.order.reserve(nent);
+    for (size_t e = 0; e < nent; e++)
+        if (!sl.tap_zero[(size_t)h->h_ent_tap[e]] && h->h_ent_coef[e] != 0.0f) sl.order.push_back(e);
+    std::stable_sort(sl.order.begin(), sl.order.end(), [&](size_t x, size_t y) {
+        return h->h_ent_out[x] != h->h_ent_out[y] ? h->h_ent_out[x] < h->h_ent_out[y] : h->h_ent_in[x] < h->h_ent_in[y];
+    });
+    sl.pix_ptr.assign((size_t)HoWo + 1, 0);
+    for (size_t e : sl.order) sl.pix_ptr[(size_t)h->h_ent_out[e] + 1]++;
+    for (int64_t o = 0; o < HoWo; o++) sl.pix_ptr[(size_t)o + 1] += sl.pix_ptr[(size_t)o];
+    return sl;
+}
+
+// record offsets of the filled-in order-preserving kernel (convtaps_exact_fill_kernel): every pixel's slot list padded to a multiple of 8 records
+static std::vector<int32_t> convtaps_fill_offsets(ConvTapsDev& c, const SlotLists& sl) {
+    const int64_t HoWo = c.Hout * c.Wout;
+    std::vector<int32_t> fill_ptr;
+    if ((c.has_dups || c.max_slots > 64) && !c.tune.no_fill_exact && c.ntaps * c.cin_pad * c.cout_pad < ((int64_t)1 << 29) && c.nslots + 8 * HoWo < ((int64_t)1 << 31)) {
+        fill_ptr.assign((size_t)HoWo + 1, 0);
+        for (int64_t o = 0; o < HoWo; o++) fill_ptr[(size_t)o + 1] = fill_ptr[(size_t)o] + (int32_t)((sl.pix_ptr[(size_t)o + 1] - sl.pix_ptr[(size_t)o] + 7) / 8 * 8);
+        c.fill_n = fill_ptr[(size_t)HoWo];
+    }
+    return fill_ptr;
+}
+
+// nnz of the expansion = what the reference's csr holds: one stored entry per (output pixel, input pixel) PAIR and channel pair -- several slots on one pair
+// (a filled-in operator) are one stored non-zero
+static int64_t convtaps_expanded_nnz(const kn_operator* h, const SlotLists& sl) {
+    const ConvTapsDev& c = h->ct;
+    const std::vector<int32_t>&eo = h->h_ent_out, &ei = h->h_ent_in;
+    const size_t nent = eo.size();
+    int64_t n_pairs = 0;
+    if (sl.order.size() == nent) {
+        for (size_t k = 0; k < nent; k++)
+            if (k == 0 || eo[sl.order[k - 1]] != eo[sl.order[k]] || ei[sl.order[k - 1]] != ei[sl.order[k]]) n_pairs++;
+    } else {                                               // (entries of all-zero taps were left out of the slot lists but are stored by the reference)
+        std::vector<int64_t> key(nent);
+        for (size_t e = 0; e < nent; e++) key[e] = (int64_t)eo[e] * (c.Hin * c.Win) + ei[e];
+        std::sort(key.begin(), key.end());
+        n_pairs = (int64_t)(std::unique(key.begin(), key.end()) - key.begin());
+    }
+    return n_pairs * c.Cout * c.Cin + (int64_t)h->h_last_rows.size();
+}
+
+// small-K pipeline descriptors (layout: kn_conv.hip SK_DESC_HDR): eligible when one pixel's whole contraction (slots x Cin + bias
+// row) fits 28 rows, one 64-wide Cout tile covers the layer and the tap matrix fits its LDS table
+static std::vector<int32_t> convtaps_smallk_desc(kn_operator* h, const SlotLists& sl, const std::vector<float>& lastcol) {
+    ConvTapsDev& c = h->ct;
+    const int64_t Cin = c.Cin, Cout = c.Cout, ntaps = c.ntaps, HoWo = c.Hout * c.Wout, HiWi = c.Hin * c.Win;
+    std::vector<int32_t> sk_desc;
+    if ((int64_t)c.max_slots * Cin + (c.has_last ? 1 : 0) <= 28 && Cout == 64 && c.cout_pad == 64 && ntaps * c.cin_pad <= 61 && h->cols < INT32_MAX - 1) {
+        const int64_t stride = 96 + c.cout_pad;
+        const int32_t zero_off = (int32_t)(ntaps * c.cin_pad * 64);
+        sk_desc.assign((size_t)(HoWo * stride), 0);
+        for (int64_t pi = 0; pi < HoWo; pi++) {
+            const int32_t o = h->h_pix_order[(size_t)pi];
+            int32_t* d = sk_desc.data() + (size_t)(pi * stride);
+            float* df = reinterpret_cast<float*>(d);
+            for (int k = 0; k < 32; k++) {
+                d[k] = -1;
+                d[32 + k] = zero_off;
+                df[64 + k] = 0.0f;
+            }
+            int k = 0;
+            for (int64_t sl_i = sl.pix_ptr[(size_t)o]; sl_i < sl.pix_ptr[(size_t)o + 1]; sl_i++) {
+                const size_t e = sl.order[(size_t)sl_i];
+                for (int64_t ci = 0; ci < Cin; ci++, k++) {
+                    d[k] = (int32_t)(ci * HiWi + h->h_ent_in[e]);
+                    d[32 + k] = (int32_t)((h->h_ent_tap[e] * c.cin_pad + ci) * 64);
+                    df[64 + k] = h->h_ent_coef[e];
+                }
+            }
+            if (c.has_last) {
+                d[k] = (int32_t)(Cin * HiWi);             // homogeneous coordinate of X against the bias row
+                d[32 + k] = zero_off + 64;                 // marker: "this buffer's bias row"
+                df[64 + k] = 1.0f;
+                for (int64_t m = 0; m < Cout; m++) df[96 + m] = lastcol[(size_t)(m * HoWo + o)];
+            }
+            d[31] = o;
+        }
+        c.sk_stride = stride;
+        c.sk_tab_rows = ntaps * c.cin_pad;
+    }
+    return sk_desc;
+}
 
 static int convtaps_create_impl(ConvBuild& b, kn_operator** out) {
     *out = nullptr;
@@ -205,6 +300,13 @@ static int convtaps_create_impl(ConvBuild& b, kn_operator** out) {
     h->device = dev;
     h->rows = rows;
     h->cols = cols;
+    h->h_ent_out = std::move(b.ent_out);
+    h->h_ent_in = std::move(b.ent_in);
+    h->h_ent_tap = std::move(b.ent_tap);
+    h->h_ent_coef = std::move(b.ent_coef);
+    h->h_taps = std::move(b.taps);
+    h->h_last_rows = std::move(b.last_rows);
+    h->h_last_vals = std::move(b.last_vals);
     ConvTapsDev& c = h->ct;
     c.tune = tuning_from_env();
     c.Cin = Cin; c.Hin = Hin; c.Win = Win; c.Cout = Cout; c.Hout = Hout; c.Wout = Wout;
@@ -215,50 +317,28 @@ static int convtaps_create_impl(ConvBuild& b, kn_operator** out) {
     c.cout_pad = (Cout + MT - 1) / MT * MT;
     c.has_last = b.has_last;
 
-    // transposed, zero-padded taps; zero taps contribute nothing and are dropped from the compute lists
+    // transposed, zero-padded taps
     std::vector<float> tapsT((size_t)(std::max<int64_t>(ntaps, 1) * c.cin_pad * c.cout_pad), 0.0f);
-    std::vector<char> tap_zero((size_t)std::max<int64_t>(ntaps, 1), 1);
     for (int64_t t = 0; t < ntaps; t++)
         for (int64_t co = 0; co < Cout; co++)
-            for (int64_t ci = 0; ci < Cin; ci++) {
-                const float w = b.taps[(size_t)((t * Cout + co) * Cin + ci)];
-                tapsT[(size_t)((t * c.cin_pad + ci) * c.cout_pad + co)] = w;
-                if (w != 0.0f) tap_zero[(size_t)t] = 0;
-            }
-    // slots grouped by output pixel, ascending input pixel inside a pixel
-    std::vector<size_t> order;
-    order.reserve(nent);
-    for (size_t e = 0; e < nent; e++)
-        if (!tap_zero[(size_t)b.ent_tap[e]] && b.ent_coef[e] != 0.0f) order.push_back(e);
-    std::stable_sort(order.begin(), order.end(), [&](size_t x, size_t y) {
-        return b.ent_out[x] != b.ent_out[y] ? b.ent_out[x] < b.ent_out[y] : b.ent_in[x] < b.ent_in[y];
-    });
-    std::vector<int32_t> pix_ptr((size_t)HoWo + 1, 0), slot_in(order.size()), slot_tap(order.size()), pix_order((size_t)HoWo);
+            for (int64_t ci = 0; ci < Cin; ci++) tapsT[(size_t)((t * c.cin_pad + ci) * c.cout_pad + co)] = h->h_taps[(size_t)((t * Cout + co) * Cin + ci)];
+    const SlotLists sl = convtaps_slot_lists(h.get());
+    const std::vector<size_t>& order = sl.order;
+    std::vector<int32_t> pix_ptr((size_t)HoWo + 1), slot_in(order.size()), slot_tap(order.size());
     std::vector<float> slot_coef(order.size());
     c.unit_coef = true;
     for (size_t k = 0; k < order.size(); k++) {
         const size_t e = order[k];
-        pix_ptr[(size_t)b.ent_out[e] + 1]++;
-        slot_in[k] = b.ent_in[e];
-        slot_tap[k] = b.ent_tap[e];
-        slot_coef[k] = b.ent_coef[e];
-        if (b.ent_coef[e] != 1.0f) c.unit_coef = false;
-        if (k > 0 && b.ent_out[order[k - 1]] == b.ent_out[e] && b.ent_in[order[k - 1]] == b.ent_in[e]) c.has_dups = true;
+        slot_in[k] = h->h_ent_in[e];
+        slot_tap[k] = h->h_ent_tap[e];
+        slot_coef[k] = h->h_ent_coef[e];
+        if (slot_coef[k] != 1.0f) c.unit_coef = false;
+        if (k > 0 && h->h_ent_out[order[k - 1]] == h->h_ent_out[e] && slot_in[k - 1] == slot_in[k]) c.has_dups = true;
     }
-    int mx = 0;
-    for (int64_t o = 0; o < HoWo; o++) {
-        mx = std::max(mx, pix_ptr[(size_t)o + 1]);
-        pix_ptr[(size_t)o + 1] += pix_ptr[(size_t)o];
-    }
-    c.max_slots = mx;
+    for (int64_t o = 0; o <= HoWo; o++) pix_ptr[(size_t)o] = (int32_t)sl.pix_ptr[(size_t)o];
+    for (int64_t o = 0; o < HoWo; o++) c.max_slots = std::max(c.max_slots, pix_ptr[(size_t)o + 1] - pix_ptr[(size_t)o]);
     c.nslots = (int64_t)order.size();
-    // record offsets of the filled-in order-preserving kernel (convtaps_exact_fill_kernel): every pixel's slot list padded to a multiple of 8 records
-    std::vector<int32_t> fill_ptr;
-    if ((c.has_dups || mx > 64) && !c.tune.no_fill_exact && ntaps * c.cin_pad * c.cout_pad < ((int64_t)1 << 29) && (int64_t)order.size() + 8 * HoWo < ((int64_t)1 << 31)) {
-        fill_ptr.assign((size_t)HoWo + 1, 0);
-        for (int64_t o = 0; o < HoWo; o++) fill_ptr[(size_t)o + 1] = fill_ptr[(size_t)o] + (pix_ptr[(size_t)o + 1] - pix_ptr[(size_t)o] + 7) / 8 * 8;
-        c.fill_n = fill_ptr[(size_t)HoWo];
-    }
+    const std::vector<int32_t> fill_ptr = convtaps_fill_offsets(c, sl);
     // Processing order of the output pixels (kn::locality_order): two pixels are neighbours when they share an input pixel;
     // balls of 64 are, for a keyed 3x3 conv, roughly 8x8 patches of the un-keyed image.  One patch = the workgroups resident
     // on one XCD at a time (32 CUs x 4 workgroups / 2 Cout tiles), so the gathered activation rows of a patch (a ~10x10
@@ -267,93 +347,106 @@ static int convtaps_create_impl(ConvBuild& b, kn_operator** out) {
     {
         std::vector<int32_t> ids((size_t)HoWo);
         for (int64_t o = 0; o < HoWo; o++) ids[(size_t)o] = (int32_t)o;
-        pix_order = locality_order(ids, pix_ptr.data(), slot_in.data(), HiWi, std::max(1, c.tune.conv_ball), 1 << 30);
+        h->h_pix_order = locality_order(ids, pix_ptr.data(), slot_in.data(), HiWi, std::max(1, c.tune.conv_ball), 1 << 30);
     }
     std::vector<float> lastcol;
-    if (b.has_last) {
+    if (c.has_last) {
         lastcol.assign((size_t)rows, 0.0f);
-        for (size_t k = 0; k < b.last_rows.size(); k++) lastcol[(size_t)b.last_rows[k]] += b.last_vals[k];
+        for (size_t k = 0; k < h->h_last_rows.size(); k++) lastcol[(size_t)h->h_last_rows[k]] += h->h_last_vals[k];
     }
-    h->h_ent_out = b.ent_out;
-    h->h_ent_in = b.ent_in;
-    h->h_ent_tap = b.ent_tap;
-    h->h_ent_coef = b.ent_coef;
-    h->h_taps = b.taps;
-    // last column kept as explicit (row,value) pairs packed in h_lastcol as [row0,val0,row1,val1,...] bit patterns
-    h->h_lastcol.resize(b.last_rows.size() * 2);
-    for (size_t k = 0; k < b.last_rows.size(); k++) {
-        const int32_t rr = (int32_t)b.last_rows[k];
-        std::memcpy(&h->h_lastcol[2 * k], &rr, 4);
-        h->h_lastcol[2 * k + 1] = b.last_vals[k];
-    }
-    // nnz of the expansion = what the reference's csr holds: one stored entry per (output pixel, input pixel) PAIR and channel pair -- several slots on one pair
-    // (a filled-in operator) are one stored non-zero
-    int64_t n_pairs = 0;
-    if (order.size() == nent) {
-        for (size_t k = 0; k < order.size(); k++)
-            if (k == 0 || b.ent_out[order[k - 1]] != b.ent_out[order[k]] || b.ent_in[order[k - 1]] != b.ent_in[order[k]]) n_pairs++;
-    } else {                                               // (entries of all-zero taps were left out of the slot lists but are stored by the reference)
-        std::vector<int64_t> key(nent);
-        for (size_t e = 0; e < nent; e++) key[e] = (int64_t)b.ent_out[e] * HiWi + b.ent_in[e];
-        std::sort(key.begin(), key.end());
-        n_pairs = (int64_t)(std::unique(key.begin(), key.end()) - key.begin());
-    }
-    h->nnz_expanded = n_pairs * Cout * Cin + (int64_t)b.last_rows.size();
-    h->nnz_stored = b.nnz_stored > 0 ? b.nnz_stored : ntaps * Cout * Cin + (int64_t)nent + (int64_t)b.last_rows.size();
-
-    // small-K pipeline descriptors (layout: kn_conv.hip SK_DESC_HDR): eligible when one pixel's whole contraction (slots x Cin + bias
-    // row) fits 28 rows, one 64-wide Cout tile covers the layer and the tap matrix fits its LDS table
-    std::vector<int32_t> sk_desc;
-    if ((int64_t)mx * Cin + (b.has_last ? 1 : 0) <= 28 && Cout == 64 && c.cout_pad == 64 && ntaps * c.cin_pad <= 61 && cols < INT32_MAX - 1) {
-        const int64_t stride = 96 + c.cout_pad;
-        const int32_t zero_off = (int32_t)(ntaps * c.cin_pad * 64);
-        sk_desc.assign((size_t)(HoWo * stride), 0);
-        for (int64_t pi = 0; pi < HoWo; pi++) {
-            const int32_t o = pix_order[(size_t)pi];
-            int32_t* d = sk_desc.data() + (size_t)(pi * stride);
-            float* df = reinterpret_cast<float*>(d);
-            for (int k = 0; k < 32; k++) {
-                d[k] = -1;
-                d[32 + k] = zero_off;
-                df[64 + k] = 0.0f;
-            }
-            int k = 0;
-            for (int32_t sl = pix_ptr[(size_t)o]; sl < pix_ptr[(size_t)o + 1]; sl++)
-                for (int64_t ci = 0; ci < Cin; ci++, k++) {
-                    d[k] = (int32_t)(ci * HiWi + slot_in[(size_t)sl]);
-                    d[32 + k] = (int32_t)((slot_tap[(size_t)sl] * c.cin_pad + ci) * 64);
-                    df[64 + k] = slot_coef[(size_t)sl];
-                }
-            if (b.has_last) {
-                d[k] = (int32_t)(Cin * HiWi);             // homogeneous coordinate of X against the bias row
-                d[32 + k] = zero_off + 64;                 // marker: "this buffer's bias row"
-                df[64 + k] = 1.0f;
-                for (int64_t m = 0; m < Cout; m++) df[96 + m] = lastcol[(size_t)(m * HoWo + o)];
-            }
-            d[31] = o;
-        }
-        c.sk_stride = stride;
-        c.sk_tab_rows = ntaps * c.cin_pad;
-    }
+    h->nnz_expanded = convtaps_expanded_nnz(h.get(), sl);
+    h->nnz_stored = b.nnz_stored > 0 ? b.nnz_stored : ntaps * Cout * Cin + (int64_t)nent + (int64_t)h->h_last_rows.size();
+    const std::vector<int32_t> sk_desc = convtaps_smallk_desc(h.get(), sl, lastcol);
     if ((!sk_desc.empty() && (rc = upload(&c.sk_desc, sk_desc.data(), sk_desc.size()))) || (rc = upload(&c.tapsT, tapsT.data(), tapsT.size())) || (rc = upload(&c.pix_ptr, pix_ptr.data(), pix_ptr.size())) ||
         (rc = upload(&c.slot_in, slot_in.data(), slot_in.size())) || (rc = upload(&c.slot_tap, slot_tap.data(), slot_tap.size())) ||
-        (rc = upload(&c.slot_coef, slot_coef.data(), slot_coef.size())) || (rc = upload(&c.pix_order, pix_order.data(), pix_order.size())) ||
+        (rc = upload(&c.slot_coef, slot_coef.data(), slot_coef.size())) || (rc = upload(&c.pix_order, h->h_pix_order.data(), h->h_pix_order.size())) ||
         (rc = upload(&c.lastcol, lastcol.data(), lastcol.size())) || (!fill_ptr.empty() && (rc = upload(&c.fill_ptr, fill_ptr.data(), fill_ptr.size()))))
         return rc;
     *out = h.release();
     return KN_OK;
 }
 
-static void last_pairs(const kn_operator* h, std::vector<int64_t>& rows, std::vector<float>& vals) {
-    const size_t n = h->h_lastcol.size() / 2;
-    rows.resize(n);
-    vals.resize(n);
-    for (size_t k = 0; k < n; k++) {
-        int32_t rr;
-        std::memcpy(&rr, &h->h_lastcol[2 * k], 4);
-        rows[k] = rr;
-        vals[k] = h->h_lastcol[2 * k + 1];
+// Processing order of the pixels for the table kernel.  Its workgroups (one output pixel x 32 * NRB channels x 256 batch columns) sweep the
+// input channels in the same order but start as earlier ones retire, so the ~128 resident on an XCD sit at staggered phases of the sweep:
+// an activation row is found in that XCD's L2 again only when the workgroup sharing it was dispatched a few places earlier (measured:
+// row-major / ball orders keep the horizontal reuse only, ~1/3 of the gathers miss).  Strips of `w` pixels swept row by row put the vertical
+// neighbour w places back: (w + 2) / w fetches per activation byte.  The candidates are scored on the operator's own structure (no
+// knowledge of the key): visits of an input pixel not seen within the last `window` output pixels count as fetches.  Measured on the AllConvNet
+// forward (FETCH_SIZE x 2 of the seven launches): ball order 15.7 GB, this choice 12.6 GB (conv2 takes w = 8, conv5 w = 2, each the best of
+// {2, 4, 8} when forced); the times do not move (the kernel is bound by vector-ALU issue).
+static std::vector<int32_t> convtaps_table_order(const kn_operator* h, const SlotLists& sl) {
+    const ConvTapsDev& c = h->ct;
+    const int64_t HoWo = c.Hout * c.Wout, HiWi = c.Hin * c.Win;
+    auto fetches = [&](const std::vector<int32_t>& ord, int64_t window) {
+        std::vector<int64_t> seen((size_t)HiWi, -((int64_t)1 << 40));
+        int64_t n = 0;
+        for (int64_t k = 0; k < HoWo; k++) {
+            const int64_t o = ord[(size_t)k];
+            for (int64_t s = sl.pix_ptr[(size_t)o]; s < sl.pix_ptr[(size_t)o + 1]; s++) {
+                const int64_t in = h->h_ent_in[sl.order[(size_t)s]];
+                if (k - seen[(size_t)in] > window) n++;
+                seen[(size_t)in] = k;
+            }
+        }
+        return n;
+    };
+    auto strips = [&](int64_t w) {
+        std::vector<int32_t> ord;
+        ord.reserve((size_t)HoWo);
+        for (int64_t x0 = 0; x0 < c.Wout; x0 += w)
+            for (int64_t y = 0; y < c.Hout; y++)
+                for (int64_t x = x0; x < std::min(x0 + w, c.Wout); x++) ord.push_back((int32_t)(y * c.Wout + x));
+        return ord;
+    };
+    const int nrb = c.Cout % 96 == 0 ? 3 : (c.Cout % 64 == 0 ? 2 : 1);       // (the window below was tuned with three row blocks per workgroup; with one -- exact_table_launch -- its choices
+                                                                         // still measured best: conv2 strips of 8 / 4 / 2 / 16 pixels 3.4 / 4.3 / 4.3 / 7.9 GB)
+    const int64_t n_cc = c.Cout / (32 * nrb);
+    // places a sharer may lie back: the rows gathered meanwhile by the resident workgroups (~1.5 KB per place and input channel at 256 columns) within half an L2 slice
+    const int64_t env_window = c.tune.table_window, env_strip = c.tune.table_strip;      // (diagnostic build: A/B knobs; product: the rule)
+    const int64_t window = env_window > 0 ? env_window : std::max<int64_t>(2, std::min<int64_t>(64, (2048 * 2) / (3 * c.Cin * n_cc)));
+    std::vector<int32_t> best = h->h_pix_order;
+    int64_t best_n = fetches(best, window);
+    if (env_strip > 0) {
+        best = strips(env_strip);
+    } else if (env_strip < 0) {
+        for (int64_t w = 2; w <= c.Wout; w *= 2) {
+            std::vector<int32_t> cand = strips(w);
+            const int64_t n = fetches(cand, window);
+            if (n < best_n) {
+                best_n = n;
+                best.swap(cand);
+            }
+        }
     }
+    return best;
+}
+
+// a float32 or float64 CSR operator's arrays back to the caller
+template <typename TV>
+static int export_device_csr(const kn_operator* h, const TV* data_dev, int32_t* indptr, int32_t* indices, TV* data) {
+    KN_HIP(hipMemcpy(indptr, h->csr.indptr, sizeof(int32_t) * (size_t)(h->rows + 1), hipMemcpyDeviceToHost));
+    if (h->csr.nnz > 0) {
+        KN_REQUIRE(indices && data, KN_ERR_INVALID, "NULL argument");
+        KN_HIP(hipMemcpy(indices, h->csr.indices, sizeof(int32_t) * (size_t)h->csr.nnz, hipMemcpyDeviceToHost));
+        KN_HIP(hipMemcpy(data, data_dev, sizeof(TV) * (size_t)h->csr.nnz, hipMemcpyDeviceToHost));
+    }
+    return KN_OK;
+}
+
+// What the compute entry points ask of their activation blocks alike.  (Their n_vecs range and alias checks are worded per entry point and stay there,
+// in the order they have always fired: an entry point's own checks sit between these two helpers.)
+static int check_operands(const void* x_dev, int64_t ldx, const void* y_dev, int64_t ldy, int64_t n_vecs) {
+    KN_REQUIRE(x_dev && y_dev, KN_ERR_INVALID, "NULL activation pointer");
+    KN_REQUIRE(ldx >= n_vecs && ldy >= n_vecs, KN_ERR_SHAPE, "leading dimension smaller than n_vecs");
+    return KN_OK;
+}
+
+// the operator lives in ONE device's HBM: running it from another device would dereference foreign memory
+static int check_device(const kn_operator* h, const char* hint) {
+    int cur = -1;
+    KN_HIP(hipGetDevice(&cur));
+    KN_REQUIRE(cur == h->device, KN_ERR_INVALID, std::string("operator was created on another HIP device than the current one") + hint);
+    return KN_OK;
 }
 
 }  // namespace kn
@@ -445,18 +538,13 @@ int kn_conv2dtiled_create(int64_t rows, int64_t cols, const int64_t inshape[3], 
     *out = nullptr;
     KN_REQUIRE(rows >= 0 && cols >= 0 && nblocks >= 0 && nent >= 0, KN_ERR_INVALID, "negative size");
     KN_REQUIRE(inshape && outshape && (nblocks == 0 || blocks) && (nent == 0 || (tile_keys && tile_isbias)), KN_ERR_INVALID, "NULL argument");
-    for (int k = 0; k < 3; k++)
-        KN_REQUIRE(inshape[k] > 0 && outshape[k] > 0 && inshape[k] < INT32_MAX && outshape[k] < INT32_MAX, KN_ERR_INVALID, "inshape / outshape entries must be positive");
+    ConvBuild b;
+    if (int rc = b.set_shapes(inshape, outshape)) return rc;
     KN_REQUIRE(rows < INT32_MAX && cols < INT32_MAX, KN_ERR_UNSUPPORTED, "int32 index range exceeded");
     const int64_t Cin = inshape[0], HiWi = inshape[1] * inshape[2], Cout = outshape[0], HoWo = outshape[1] * outshape[2];
     const bool has_last = (rows == Cout * HoWo + 1);
     KN_REQUIRE(rows == Cout * HoWo + (has_last ? 1 : 0) && cols == Cin * HiWi + (has_last ? 1 : 0), KN_ERR_SHAPE,
                "matrix shape does not match inshape/outshape (keynet/sparse.py:731-736)");
-    ConvBuild b;
-    for (int k = 0; k < 3; k++) {
-        b.inshape[k] = inshape[k];
-        b.outshape[k] = outshape[k];
-    }
     b.has_last = has_last;
     // entries by tile id; channel matrices de-duplicated by content
     std::unordered_map<int64_t, std::vector<int64_t>> by_k;
@@ -524,13 +612,8 @@ int kn_convtaps_create(const int64_t inshape[3], const int64_t outshape[3], int6
     KN_REQUIRE(inshape && outshape && ntaps >= 0 && nent >= 0, KN_ERR_INVALID, "bad argument");
     KN_REQUIRE((ntaps == 0 || taps) && (nent == 0 || (ent_out && ent_in && ent_tap)), KN_ERR_INVALID, "NULL array");
     ConvBuild b;
-    for (int k = 0; k < 3; k++) {
-        b.inshape[k] = inshape[k];
-        b.outshape[k] = outshape[k];
-    }
+    if (int rc = b.set_shapes(inshape, outshape)) return rc;
     const int64_t Cout = outshape[0], Cin = inshape[0];
-    for (int k = 0; k < 3; k++)
-        KN_REQUIRE(inshape[k] > 0 && outshape[k] > 0 && inshape[k] < INT32_MAX && outshape[k] < INT32_MAX, KN_ERR_INVALID, "inshape / outshape entries must be positive");
     KN_REQUIRE(Cout * outshape[1] * outshape[2] < INT32_MAX && Cin * inshape[1] * inshape[2] < INT32_MAX, KN_ERR_UNSUPPORTED, "int32 index range exceeded");
     b.taps.assign(taps, taps + (size_t)(ntaps * Cout * Cin));
     b.ent_out.assign(ent_out, ent_out + nent);
@@ -558,12 +641,11 @@ int kn_convtaps_drop_zero_entries(kn_handle_t h) {
     std::lock_guard<std::mutex> g(h->lazy_mu);
     if (h->ct.zero_ent != nullptr) return KN_OK;
     const ConvTapsDev& c = h->ct;
+    const SlotLists sl = convtaps_slot_lists(h);
     std::vector<int32_t> z;
     for (int64_t t = 0; t < c.ntaps; t++) {
+        if (sl.tap_zero[(size_t)t]) continue;                 // a tap that is zero altogether has no slots at all
         const float* T = h->h_taps.data() + (size_t)(t * c.Cout * c.Cin);
-        bool any = false;
-        for (int64_t k = 0; k < c.Cout * c.Cin && !any; k++) any = T[k] != 0.0f;
-        if (!any) continue;                                   // a tap that is zero altogether has no slots at all (convtaps_create_impl)
         for (int64_t co = 0; co < c.Cout; co++)
             for (int64_t ci = 0; ci < c.Cin; ci++)
                 if (T[co * c.Cin + ci] == 0.0f) {
@@ -578,108 +660,34 @@ int kn_convtaps_drop_zero_entries(kn_handle_t h) {
     h->ct.zero_ent = d;
     h->ct.n_zero = (int64_t)(z.size() / 3);
     // The stored-column table of the expansion for the matrix-pipe kernel (kn_csr_mfma.hip, TAPS): per output pixel, channel outer and the pixel's slots
-    // by ascending input pixel inner -- the order of convtaps_create_impl's slot lists -- each column as (activation row, value row of tapsT).  Unit
+    // by ascending input pixel inner -- the order of the slot lists -- each column as (activation row, value row of tapsT).  Unit
     // coefficients only (a coefficient entry's stored value is fl(coef * tap): the conv pipeline handles those), no duplicate (pixel, pixel) pairs, and
     // at most 64 M columns (512 MB); otherwise the operator simply has no table and KN_FLAG_EXACT takes the conv pipeline.
-    if (c.unit_coef && !c.has_dups && c.Cout % 32 == 0) {
-        const int64_t HoWo = c.Hout * c.Wout, HiWi = c.Hin * c.Win;
-        const size_t nent = h->h_ent_out.size();
-        std::vector<char> tap_zero((size_t)std::max<int64_t>(c.ntaps, 1), 1);
-        for (int64_t t = 0; t < c.ntaps; t++)
-            for (int64_t k = 0; k < c.Cout * c.Cin; k++)
-                if (h->h_taps[(size_t)(t * c.Cout * c.Cin + k)] != 0.0f) {
-                    tap_zero[(size_t)t] = 0;
-                    break;
+    const int64_t HoWo = c.Hout * c.Wout, HiWi = c.Hin * c.Win, total = (int64_t)sl.order.size() * c.Cin;
+    if (c.unit_coef && !c.has_dups && c.Cout % 32 == 0 && total > 0 && total <= ((int64_t)64 << 20) && (c.Cin * HiWi + 1) < INT32_MAX && c.ntaps * c.cin_pad < INT32_MAX) {
+        std::vector<int32_t> ex_ptr((size_t)HoWo + 1), ex_tab((size_t)(2 * total));
+        for (int64_t o = 0; o <= HoWo; o++) ex_ptr[(size_t)o] = (int32_t)(sl.pix_ptr[(size_t)o] * c.Cin);
+        for (int64_t o = 0; o < HoWo; o++) {
+            const int64_t s0 = sl.pix_ptr[(size_t)o], ns = sl.pix_ptr[(size_t)o + 1] - s0;
+            int32_t* out = ex_tab.data() + (size_t)(2 * s0 * c.Cin);
+            for (int64_t ci = 0; ci < c.Cin; ci++)
+                for (int64_t k = 0; k < ns; k++) {
+                    const size_t e = sl.order[(size_t)(s0 + k)];
+                    *out++ = (int32_t)(ci * HiWi + h->h_ent_in[e]);
+                    *out++ = (int32_t)(h->h_ent_tap[e] * c.cin_pad + ci);
                 }
-        std::vector<size_t> order;
-        order.reserve(nent);
-        for (size_t e = 0; e < nent; e++)
-            if (!tap_zero[(size_t)h->h_ent_tap[e]] && h->h_ent_coef[e] != 0.0f) order.push_back(e);
-        std::stable_sort(order.begin(), order.end(), [&](size_t x, size_t y) {
-            return h->h_ent_out[x] != h->h_ent_out[y] ? h->h_ent_out[x] < h->h_ent_out[y] : h->h_ent_in[x] < h->h_ent_in[y];
-        });
-        std::vector<int64_t> pp((size_t)HoWo + 1, 0);
-        for (size_t k = 0; k < order.size(); k++) pp[(size_t)h->h_ent_out[order[k]] + 1]++;
-        for (int64_t o = 0; o < HoWo; o++) pp[(size_t)o + 1] += pp[(size_t)o];
-        const int64_t total = (int64_t)order.size() * c.Cin;
-        if (total > 0 && total <= ((int64_t)64 << 20) && (c.Cin * HiWi + 1) < INT32_MAX && c.ntaps * c.cin_pad < INT32_MAX) {
-            std::vector<int32_t> ex_ptr((size_t)HoWo + 1), ex_tab((size_t)(2 * total));
-            for (int64_t o = 0; o <= HoWo; o++) ex_ptr[(size_t)o] = (int32_t)(pp[(size_t)o] * c.Cin);
-            for (int64_t o = 0; o < HoWo; o++) {
-                const int64_t s0 = pp[(size_t)o], ns = pp[(size_t)o + 1] - s0;
-                int32_t* out = ex_tab.data() + (size_t)(2 * s0 * c.Cin);
-                for (int64_t ci = 0; ci < c.Cin; ci++)
-                    for (int64_t sl = 0; sl < ns; sl++) {
-                        const size_t e = order[(size_t)(s0 + sl)];
-                        *out++ = (int32_t)(ci * HiWi + h->h_ent_in[e]);
-                        *out++ = (int32_t)(h->h_ent_tap[e] * c.cin_pad + ci);
-                    }
-            }
-            // Processing order of the pixels for the table kernel.  Its workgroups (one output pixel x 32 * NRB channels x 256 batch columns) sweep the
-            // input channels in the same order but start as earlier ones retire, so the ~128 resident on an XCD sit at staggered phases of the sweep:
-            // an activation row is found in that XCD's L2 again only when the workgroup sharing it was dispatched a few places earlier (measured:
-            // row-major / ball orders keep the horizontal reuse only, ~1/3 of the gathers miss).  Strips of `w` pixels swept row by row put the vertical
-            // neighbour w places back: (w + 2) / w fetches per activation byte.  The candidates are scored on the operator's own structure (no
-            // knowledge of the key): visits of an input pixel not seen within the last `window` output pixels count as fetches.  Measured on the AllConvNet
-            // forward (FETCH_SIZE x 2 of the seven launches): ball order 15.7 GB, this choice 12.6 GB (conv2 takes w = 8, conv5 w = 2, each the best of
-            // {2, 4, 8} when forced); the times do not move (the kernel is bound by vector-ALU issue).
-            std::vector<int32_t> ex_order((size_t)HoWo);
-            {
-                auto fetches = [&](const std::vector<int32_t>& ord, int64_t window) {
-                    std::vector<int64_t> seen((size_t)HiWi, -((int64_t)1 << 40));
-                    int64_t n = 0;
-                    for (int64_t k = 0; k < HoWo; k++) {
-                        const int64_t o = ord[(size_t)k];
-                        for (int64_t sl = pp[(size_t)o]; sl < pp[(size_t)o + 1]; sl++) {
-                            const int64_t in = h->h_ent_in[order[(size_t)sl]];
-                            if (k - seen[(size_t)in] > window) n++;
-                            seen[(size_t)in] = k;
-                        }
-                    }
-                    return n;
-                };
-                auto strips = [&](int64_t w) {
-                    std::vector<int32_t> ord;
-                    ord.reserve((size_t)HoWo);
-                    for (int64_t x0 = 0; x0 < c.Wout; x0 += w)
-                        for (int64_t y = 0; y < c.Hout; y++)
-                            for (int64_t x = x0; x < std::min(x0 + w, c.Wout); x++) ord.push_back((int32_t)(y * c.Wout + x));
-                    return ord;
-                };
-                const int nrb = c.Cout % 96 == 0 ? 3 : (c.Cout % 64 == 0 ? 2 : 1);       // (the window below was tuned with three row blocks per workgroup; with one -- exact_table_launch -- its choices
-                                                                                     // still measured best: conv2 strips of 8 / 4 / 2 / 16 pixels 3.4 / 4.3 / 4.3 / 7.9 GB)
-                const int64_t n_cc = c.Cout / (32 * nrb);
-                // places a sharer may lie back: the rows gathered meanwhile by the resident workgroups (~1.5 KB per place and input channel at 256 columns) within half an L2 slice
-                const int64_t env_window = c.tune.table_window, env_strip = c.tune.table_strip;      // (diagnostic build: A/B knobs; product: the rule)
-                const int64_t window = env_window > 0 ? env_window : std::max<int64_t>(2, std::min<int64_t>(64, (2048 * 2) / (3 * c.Cin * n_cc)));
-                std::vector<int32_t> best((size_t)HoWo);
-                KN_HIP(hipMemcpy(best.data(), c.pix_order, (size_t)HoWo * sizeof(int32_t), hipMemcpyDeviceToHost));
-                int64_t best_n = fetches(best, window);
-                if (env_strip > 0) {
-                    best = strips(env_strip);
-                } else if (env_strip < 0) {
-                    for (int64_t w = 2; w <= c.Wout; w *= 2) {
-                        std::vector<int32_t> cand = strips(w);
-                        const int64_t n = fetches(cand, window);
-                        if (n < best_n) {
-                            best_n = n;
-                            best.swap(cand);
-                        }
-                    }
-                }
-                ex_order = best;
-            }
-            int32_t *dp = nullptr, *dt = nullptr, *dord = nullptr;
-            if ((rc = upload(&dp, ex_ptr.data(), ex_ptr.size()))) return rc;
-            if ((rc = upload(&dt, ex_tab.data(), ex_tab.size())) || (rc = upload(&dord, ex_order.data(), ex_order.size()))) {
-                (void)hipFree(dp);
-                if (dt) (void)hipFree(dt);
-                return rc;
-            }
-            h->ct.ex_ptr = dp;
-            h->ct.ex_tab = dt;
-            h->ct.ex_order = dord;
         }
+        const std::vector<int32_t> ex_order = convtaps_table_order(h, sl);
+        int32_t *dp = nullptr, *dt = nullptr, *dord = nullptr;
+        if ((rc = upload(&dp, ex_ptr.data(), ex_ptr.size()))) return rc;
+        if ((rc = upload(&dt, ex_tab.data(), ex_tab.size())) || (rc = upload(&dord, ex_order.data(), ex_order.size()))) {
+            (void)hipFree(dp);
+            if (dt) (void)hipFree(dt);
+            return rc;
+        }
+        h->ct.ex_ptr = dp;
+        h->ct.ex_tab = dt;
+        h->ct.ex_order = dord;
     }
     return KN_OK;
     });
@@ -764,7 +772,6 @@ int kn_destroy(kn_handle_t h) {
     return guarded([&]() -> int {
     if (!h) return KN_OK;
     if (h->chain) chain_free(h->chain);
-    if (h->exact) kn_destroy(h->exact);
     if (h->dense_sub) kn_destroy(h->dense_sub);
     if (h->dense_lastcol) (void)hipFree(h->dense_lastcol);
     for (auto& kv : h->dense_ws)
@@ -808,23 +815,12 @@ int kn_shape(kn_handle_t h, int64_t* rows, int64_t* cols) {
 int kn_export_csr(kn_handle_t h, int32_t* indptr, int32_t* indices, float* data) {
     return guarded([&]() -> int {
     KN_REQUIRE(h && indptr, KN_ERR_INVALID, "NULL argument");
-    if (h->kind == KIND_CSR) {
-        KN_HIP(hipMemcpy(indptr, h->csr.indptr, sizeof(int32_t) * (size_t)(h->rows + 1), hipMemcpyDeviceToHost));
-        if (h->csr.nnz > 0) {
-            KN_REQUIRE(indices && data, KN_ERR_INVALID, "NULL argument");
-            KN_HIP(hipMemcpy(indices, h->csr.indices, sizeof(int32_t) * (size_t)h->csr.nnz, hipMemcpyDeviceToHost));
-            KN_HIP(hipMemcpy(data, h->csr.data, sizeof(float) * (size_t)h->csr.nnz, hipMemcpyDeviceToHost));
-        }
-        return KN_OK;
-    }
+    if (h->kind == KIND_CSR) return export_device_csr(h, h->csr.data, indptr, indices, data);
     KN_REQUIRE(h->kind != KIND_CSR64, KN_ERR_UNSUPPORTED, "kn_export_csr: a float64 operator is exported by kn_export_csr_f64");
     KN_REQUIRE(h->kind == KIND_CONVTAPS, KN_ERR_UNSUPPORTED, "kn_export_csr: dense operators and chains are exported by their creator (the host keeps the matrices)");
     std::vector<int32_t> ip, ix;
     std::vector<float> dt;
-    std::vector<int64_t> lr;
-    std::vector<float> lv;
-    last_pairs(h, lr, lv);
-    convtaps_expand(h, lr, lv, ip, ix, dt);
+    convtaps_expand(h, ip, ix, dt);
     KN_REQUIRE((int64_t)ix.size() == h->nnz_expanded, KN_ERR_UNSUPPORTED, "duplicate (row,col) entries in a conv-taps operator: expanded nnz differs");
     std::memcpy(indptr, ip.data(), sizeof(int32_t) * ip.size());
     if (!ix.empty()) {
@@ -840,13 +836,7 @@ int kn_export_csr_f64(kn_handle_t h, int32_t* indptr, int32_t* indices, double* 
     return guarded([&]() -> int {
     KN_REQUIRE(h && indptr, KN_ERR_INVALID, "NULL argument");
     KN_REQUIRE(h->kind == KIND_CSR64, KN_ERR_UNSUPPORTED, "kn_export_csr_f64: not a float64 CSR operator (kn_csr_create_f64)");
-    KN_HIP(hipMemcpy(indptr, h->csr.indptr, sizeof(int32_t) * (size_t)(h->rows + 1), hipMemcpyDeviceToHost));
-    if (h->csr.nnz > 0) {
-        KN_REQUIRE(indices && data, KN_ERR_INVALID, "NULL argument");
-        KN_HIP(hipMemcpy(indices, h->csr.indices, sizeof(int32_t) * (size_t)h->csr.nnz, hipMemcpyDeviceToHost));
-        KN_HIP(hipMemcpy(data, h->csr.data64, sizeof(double) * (size_t)h->csr.nnz, hipMemcpyDeviceToHost));
-    }
-    return KN_OK;
+    return export_device_csr(h, h->csr.data64, indptr, indices, data);
     });
 }
 
@@ -900,18 +890,12 @@ static int spmm_impl(kn_handle_t h, const float* x_dev, int64_t ldx, int64_t n_v
     if (plan_sink() == nullptr) KN_HOST_ONLY_GUARD();
     KN_REQUIRE(n_vecs >= 0, KN_ERR_INVALID, "negative n_vecs");
     if (n_vecs == 0 || h->rows == 0) return KN_OK;
-    KN_REQUIRE(x_dev && y_dev, KN_ERR_INVALID, "NULL activation pointer");
-    KN_REQUIRE(ldx >= n_vecs && ldy >= n_vecs, KN_ERR_SHAPE, "leading dimension smaller than n_vecs");
+    int rc = KN_OK;
+    if ((rc = check_operands(x_dev, ldx, y_dev, ldy, n_vecs))) return rc;
     KN_REQUIRE(n_vecs < INT32_MAX, KN_ERR_UNSUPPORTED, "n_vecs too large");
     KN_REQUIRE(x_dev != y_dev, KN_ERR_INVALID, "x and y alias");
+    if ((rc = check_device(h, " (create it under the device of x)"))) return rc;
     hipStream_t s = reinterpret_cast<hipStream_t>(stream);
-    {
-        // the operator lives in ONE device's HBM: running it from another device would dereference foreign memory
-        int cur = -1;
-        KN_HIP(hipGetDevice(&cur));
-        KN_REQUIRE(cur == h->device, KN_ERR_INVALID, "operator was created on another HIP device than the current one (create it under the device of x)");
-    }
-    int rc = KN_OK;
     bool fused = false;
     if (h->kind == KIND_CSR) {
         rc = csr_spmm(h->csr, x_dev, ldx, n_vecs, y_dev, ldy, flags, s, absmax, &fused);
@@ -927,7 +911,7 @@ static int spmm_impl(kn_handle_t h, const float* x_dev, int64_t ldx, int64_t n_v
             rc = dense_workspace(h, s, n_vecs, &ws);
             if (rc) return rc;
         }
-        rc = convtaps_spmm(h->dense_sub->ct, outs * S, h->cols - 1, x_dev, ldx, n_vecs, ws, n_vecs, 0, s);
+        rc = convtaps_spmm(h->dense_sub->ct, x_dev, ldx, n_vecs, ws, n_vecs, 0, s);
         if (rc) return rc;
         rc = dense_reduce(ws, n_vecs, outs, S, h->dense_lastcol, x_dev + (h->cols - 1) * ldx, y_dev, ldy, n_vecs, (flags & KN_FLAG_RELU) ? 1 : 0, s);
     } else {
@@ -943,7 +927,7 @@ static int spmm_impl(kn_handle_t h, const float* x_dev, int64_t ldx, int64_t n_v
             rc = convtaps_build_fill(h->ct, s);
             if (rc) return rc;
         }
-        rc = convtaps_spmm(h->ct, h->rows, h->cols, x_dev, ldx, n_vecs, y_dev, ldy, flags, s, absmax, &fused);
+        rc = convtaps_spmm(h->ct, x_dev, ldx, n_vecs, y_dev, ldy, flags, s, absmax, &fused);
     }
     if (rc) return rc;
     if (absmax && !fused) return absmax_pass(y_dev, h->rows, ldy, n_vecs, absmax, s);
@@ -966,13 +950,10 @@ int kn_spmm_planes(kn_handle_t h, const float* x_dev, int64_t ldx, int64_t x_pla
     if (plan_sink() == nullptr) KN_HOST_ONLY_GUARD();
     KN_REQUIRE(n_vecs >= 0 && n_vecs < INT32_MAX && n_planes >= 0, KN_ERR_INVALID, "n_vecs / n_planes out of range");
     if (n_vecs == 0 || n_planes == 0 || h->rows == 0) return KN_OK;
-    KN_REQUIRE(x_dev && y_dev, KN_ERR_INVALID, "NULL activation pointer");
-    KN_REQUIRE(ldx >= n_vecs && ldy >= n_vecs, KN_ERR_SHAPE, "leading dimension smaller than n_vecs");
+    if (int rc = check_operands(x_dev, ldx, y_dev, ldy, n_vecs)) return rc;
     KN_REQUIRE(n_planes == 1 || (x_plane_stride >= h->cols * ldx && y_plane_stride >= h->rows * ldy), KN_ERR_SHAPE, "planes overlap (stride smaller than one block)");
     KN_REQUIRE(x_dev != y_dev, KN_ERR_INVALID, "x and y alias");
-    int cur = -1;
-    KN_HIP(hipGetDevice(&cur));
-    KN_REQUIRE(cur == h->device, KN_ERR_INVALID, "operator was created on another HIP device than the current one (create it under the device of x)");
+    if (int rc = check_device(h, " (create it under the device of x)")) return rc;
     return csr_spmm_planes(h->csr, x_dev, ldx, x_plane_stride, n_planes, n_vecs, y_dev, ldy, y_plane_stride, flags, reinterpret_cast<hipStream_t>(stream));
     });
 }
@@ -984,12 +965,9 @@ int kn_spmm_f64(kn_handle_t h, const float* x_dev, int64_t ldx, int64_t n_vecs, 
     if (plan_sink() == nullptr) KN_HOST_ONLY_GUARD();
     KN_REQUIRE(n_vecs >= 0 && n_vecs < INT32_MAX, KN_ERR_INVALID, "n_vecs out of range");
     if (n_vecs == 0 || h->rows == 0) return KN_OK;
-    KN_REQUIRE(x_dev && y_dev, KN_ERR_INVALID, "NULL activation pointer");
-    KN_REQUIRE(ldx >= n_vecs && ldy >= n_vecs, KN_ERR_SHAPE, "leading dimension smaller than n_vecs");
+    if (int rc = check_operands(x_dev, ldx, y_dev, ldy, n_vecs)) return rc;
     KN_REQUIRE((const void*)x_dev != (const void*)y_dev, KN_ERR_INVALID, "x and y alias");
-    int cur = -1;
-    KN_HIP(hipGetDevice(&cur));
-    KN_REQUIRE(cur == h->device, KN_ERR_INVALID, "operator was created on another HIP device than the current one (create it under the device of x)");
+    if (int rc = check_device(h, " (create it under the device of x)")) return rc;
     return csr_f64_spmm<double>(h->csr, x_dev, ldx, n_vecs, y_dev, ldy, flags, reinterpret_cast<hipStream_t>(stream));
     });
 }
@@ -1012,9 +990,7 @@ int kn_release_side_tables(kn_handle_t h) {
     int32_t* rec = __atomic_load_n(&h->ct.fill_rec, __ATOMIC_ACQUIRE);
     uint16_t* tb = __atomic_load_n(&h->ct.tapsB, __ATOMIC_ACQUIRE);
     if (!rec && !tb) return KN_OK;
-    int cur = -1;
-    KN_HIP(hipGetDevice(&cur));
-    KN_REQUIRE(cur == h->device, KN_ERR_INVALID, "operator was created on another HIP device than the current one");
+    if (int rc = check_device(h, "")) return rc;
     KN_HIP(hipDeviceSynchronize());                               // a launch on ANY stream may still be reading the tables (rare call: a layer changed its contract)
     __atomic_store_n(&h->ct.fill_rec, (int32_t*)nullptr, __ATOMIC_RELEASE);
     __atomic_store_n(&h->ct.tapsB, (uint16_t*)nullptr, __ATOMIC_RELEASE);
@@ -1029,9 +1005,7 @@ int kn_reserve_workspace(kn_handle_t h, int64_t n_vecs, void* stream) {
     KN_REQUIRE(h != nullptr, KN_ERR_INVALID, "NULL handle");
     KN_REQUIRE(n_vecs >= 0 && n_vecs < INT32_MAX, KN_ERR_INVALID, "n_vecs out of range");
     if (h->kind != KIND_DENSE || n_vecs == 0) return KN_OK;      // only a dense (split-K) operator keeps per-call state (its partial sums)
-    int cur = -1;
-    KN_HIP(hipGetDevice(&cur));
-    KN_REQUIRE(cur == h->device, KN_ERR_INVALID, "operator was created on another HIP device than the current one");
+    if (int rc = check_device(h, "")) return rc;
     float* ws = nullptr;
     return dense_workspace(h, reinterpret_cast<hipStream_t>(stream), n_vecs, &ws);
     });

@@ -2034,13 +2034,12 @@ static void launch_conv(ConvArgs a, const Tuning& tune, hipStream_t s) {
                  tail ? " tail_split" : "", occ_cap);
         return std::string(b);
     };
-    const bool fast = a.vec_ok && a.unit_coef && (a.Cin % KC == 0 || a.Cin < KC) && (a.n_vecs % NB == 0) && ((int64_t)KC * a.HiWi * a.ldx < (int64_t)1 << 31) &&
-                      a.max_slots <= MAX_FAST_SLOTS && (int64_t)a.HiWi * a.ldx < (int64_t)1 << 31 && (int64_t)a.ntaps * a.cin_pad * a.cout_pad < (int64_t)1 << 31;
+    const bool fast_shape = a.vec_ok && (a.n_vecs % NB == 0) && ((int64_t)KC * a.HiWi * a.ldx < (int64_t)1 << 31) &&      // (any number of slots per pixel: slot groups)
+                            (int64_t)a.HiWi * a.ldx < (int64_t)1 << 31 && (int64_t)a.ntaps * a.cin_pad * a.cout_pad < (int64_t)1 << 31;
+    const bool fast = fast_shape && a.unit_coef && (a.Cin % KC == 0 || a.Cin < KC) && a.max_slots <= MAX_FAST_SLOTS;
     // scalar-pointer loaders (MODE 2): 16-row chunks of whole channels, a thread's offsets inside one chunk in 31 bits.  Tuning::no_sptr
     // (KN_NO_SPTR=1 when the operator is created) keeps the other loaders for the parity tests' side-by-side.
     bool sptr = false;
-    const bool fast_shape = a.vec_ok && (a.n_vecs % NB == 0) && ((int64_t)KC * a.HiWi * a.ldx < (int64_t)1 << 31) &&      // (any number of slots per pixel: slot groups)
-                            (int64_t)a.HiWi * a.ldx < (int64_t)1 << 31 && (int64_t)a.ntaps * a.cin_pad * a.cout_pad < (int64_t)1 << 31;
     if constexpr (KC == 16) sptr = fast_shape && a.Cin % 16 == 0 && 4 * ((int64_t)(1024 / NB) * a.HiWi * a.ldx + NB) < (int64_t)1 << 31 && !tune.no_sptr;
     a.tail_main = (int32_t)chunk;
     if constexpr (MT == 128 && NB == 128 && KC == 16) {
@@ -2101,7 +2100,7 @@ static void launch_conv(ConvArgs a, const Tuning& tune, hipStream_t s) {
     else KN_LAUNCH(D("generic", false), (convtaps_mfma_kernel<MT, NB, KC, WM, WN, 0, false>), dim3((unsigned)grid), dim3(256), pad, s, a);
 }
 
-// Filled-in operators under KN_FLAG_EXACT: does this operator take convtaps_exact_fill_kernel?  (fill_ptr was laid out at create: convtaps_create_impl.)
+// Filled-in operators under KN_FLAG_EXACT: does this operator take convtaps_exact_fill_kernel?  (fill_ptr was laid out at create: convtaps_fill_offsets, kn_api.hip.)
 bool convtaps_fill_ok(const ConvTapsDev& A) { return A.fill_ptr != nullptr && A.fill_n > 0 && !A.tune.no_fill_exact; }
 
 // ... and its record lists, built on the device from the slot lists at the first kn_spmm that needs them (16 bytes per slot: VGG-16 under doubly-stochastic
@@ -2178,200 +2177,198 @@ int convtaps_build_bf16(ConvTapsDev& A, const std::vector<float>& taps /* [ntaps
     return KN_OK;
 }
 
-int convtaps_spmm(const ConvTapsDev& A, int64_t rows, int64_t cols, const float* x, int64_t ldx, int64_t n_vecs, float* y, int64_t ldy,
-                  uint32_t flags, hipStream_t s, float* absmax, bool* absmax_fused) {
-    (void)rows;
-    (void)cols;
-    ConvArgs a;
-    a.absmax = nullptr;
-    if (absmax_fused) *absmax_fused = false;
-    a.tapsT = A.tapsT;
-    a.pix_ptr = A.pix_ptr;
-    a.slot_in = A.slot_in;
-    a.slot_tap = A.slot_tap;
-    a.slot_coef = A.slot_coef;
-    a.pix_order = A.pix_order;
+// The call's operands and the operator's shape as the kernels take them.  n_mt / n_bt / tail_main / absmax (and the bf16 planes) belong to the
+// regime that launches and are set there.
+static ConvArgs conv_args(const ConvTapsDev& A, const float* x, int64_t ldx, int64_t n_vecs, float* y, int64_t ldy, uint32_t flags) {
+    ConvArgs a = {};
+    a.tapsT = A.tapsT; a.pix_ptr = A.pix_ptr; a.slot_in = A.slot_in; a.slot_tap = A.slot_tap; a.slot_coef = A.slot_coef; a.pix_order = A.pix_order;
     a.lastcol = A.has_last ? A.lastcol : nullptr;
-    a.X = x;
-    a.Y = y;
-    a.ldx = ldx;
-    a.ldy = ldy;
-    a.cin_pad = (int32_t)A.cin_pad;
-    a.cout_pad = (int32_t)A.cout_pad;
-    a.Cin = (int32_t)A.Cin;
-    a.Cout = (int32_t)A.Cout;
+    a.X = x; a.ldx = ldx; a.Y = y; a.ldy = ldy;
+    a.cin_pad = (int32_t)A.cin_pad; a.cout_pad = (int32_t)A.cout_pad; a.Cin = (int32_t)A.Cin; a.Cout = (int32_t)A.Cout;
     a.HiWi = (int32_t)(A.Hin * A.Win);
-    a.HoWo = (int32_t)(A.Hout * A.Wout);
+    a.n_pix = a.HoWo = (int32_t)(A.Hout * A.Wout);
     a.n_vecs = (int32_t)n_vecs;
     a.relu = (flags & KN_FLAG_RELU) ? 1 : 0;
     a.unit_coef = A.unit_coef ? 1 : 0;
     a.vec_ok = (n_vecs % 4 == 0 && ldx % 4 == 0 && ((uintptr_t)x) % 16 == 0) ? 1 : 0;
-    a.n_pix = a.HoWo;
-    a.ntaps = (int32_t)A.ntaps;
-    a.last_in_row = A.Cin * A.Hin * A.Win;
-
-    a.stamps = nullptr;
-#ifdef KN_ABLATION
-    a.abl = A.tune.abl;
-#endif
-    a.sk_desc = A.sk_desc;
-    a.sk_stride = (int32_t)A.sk_stride;
-    a.sk_tab_rows = (int32_t)A.sk_tab_rows;
-    a.tail_main = 0;
-    if (flags & KN_FLAG_EXACT) {
-        const bool v4 = a.vec_ok && n_vecs >= 256;
-        const int pipe_mode = A.tune.exact_pipe;
-        const bool pipe_shape = pipe_mode > 0 && !A.has_dups && A.max_slots <= 64 && (a.last_in_row + 1) * ldx < ((int64_t)1 << 31) &&
-                                (int64_t)A.ntaps * A.cin_pad * A.cout_pad < ((int64_t)1 << 31);
-        const bool pipe4 = pipe_shape && v4 && ldy % 4 == 0 && ((uintptr_t)y) % 16 == 0;
-        // two batch columns per lane (128-column tiles): a half-batch window of the overlapped forward at 256 images, or a batch that fills 128-column
-        // tiles better than 256-column ones (384 images).  Tuning::exact_vec = 2 | 4 forces either where both apply (diagnostic build).
-        const bool pipe2_ok = pipe_shape && n_vecs >= 128 && n_vecs % 2 == 0 && ldx % 2 == 0 && ldy % 2 == 0 && ((uintptr_t)x) % 8 == 0 && ((uintptr_t)y) % 8 == 0;
-        const bool pipe2 = pipe2_ok && (A.tune.exact_vec == 2 || (A.tune.exact_vec != 4 && (!pipe4 || (n_vecs + 127) / 128 * 128 < (n_vecs + 255) / 256 * 256)));
-        const bool pipe = pipe4 || pipe2;
-        const int64_t n_ct = pipe2 ? (n_vecs + 127) / 128 : (v4 ? (n_vecs + 255) / 256 : (n_vecs + 63) / 64);
-        // 16 output channels per wavefront when that still leaves every SIMD several wavefronts, else 8
-        const int rbx = (pipe && pipe_mode >= 16 && A.Cout % 16 == 0 && (int64_t)a.n_pix * (A.Cout / 16) * n_ct >= 4096) ? 16 : 8;
-        const int n_cob = (int)((A.Cout + rbx - 1) / rbx);
-        const int64_t n_rb = ((int64_t)a.n_pix * n_cob + 3) / 4;
-        // Channel-bundle groups (convtaps_exact_pipe_kernel): with g groups every XCD works on 1/g (g = 8) or 2/g of the output channels for all
-        // pixels, so its share of the taps stays in its 4 MiB L2 for the scalar tap loads -- 9.4 MB of taps on the 512-channel layers of VGG-16.
-        // Same-process A/B, exact mode, ms at 1 / 4 / 8 groups: conv3_2 (2.4 MB of taps) 13.63 / 13.49 / 14.60, conv4_1 6.99 / 6.75 / 6.84,
-        // conv4_2 14.05 / 13.54 / 13.48, conv4_3 14.01 / 13.34 / 13.53, conv5_1 4.26 / 3.82 / 3.82, conv5_2 4.24 / 3.84 / 4.10; layers with small tap
-        // matrices lose 5 % (conv1_2, conv2_x: the bundles of a pixel no longer share its gathered rows in one XCD).  Rule: 4 groups when the taps exceed half
-        // of the L2 (2 MB: VGG-16 conv3_x and up; AllConvNet's 192-channel layers, 1.3 MB at 16 column tiles per layer, lose 10 % when grouped).  Tuning::exact_cob_groups overrides (diagnostic build).
-        a.tail_main = 0;
-        {
-            const int64_t tap_bytes = 4 * A.ntaps * A.cin_pad * A.cout_pad;
-            int g = tap_bytes > (2 << 20) ? 4 : 1;
-            if (A.tune.exact_cob_groups > 0) g = A.tune.exact_cob_groups;
-            while (g > 1 && n_cob % g != 0) g >>= 1;
-            if (g > 1) a.tail_main = n_cob / g;
-        }
-        const int64_t grid = ((n_ct * n_rb + 7) / 8) * 8;
-        // a factored stand-in of an untiled CSR that carries the stored-column table (kn_convtaps_drop_zero_entries) on a wide batch: the matrix-pipe
-        // grouped kernel reads its values from the tap table (kn_csr_mfma.hip, TAPS).  Tuning::no_exact_table keeps the conv pipeline instead.
-        const bool table = A.ex_tab != nullptr && n_vecs >= 128 && !A.tune.no_exact_table;
-        if (table) {
-            int rc = convtaps_exact_table_spmm(A, x, ldx, n_vecs, y, ldy, a.relu, s);
-            if (rc) return rc;
-        }
-        // four activation rows in flight when the batch spans several 256-column tiles (the rows of a [D, 4096] block are L2 misses; at one tile --
-        // VGG-16 at 256 images -- three rows in flight measured 2-3 % slower than two).  Tuning::exact_xd = 2 | 4 overrides (diagnostic build).
-        // filled-in operators (more than 64 slots per pixel, or several slots on one pixel pair): convtaps_exact_fill_kernel (its records exist from the first kn_spmm on)
-        const bool fill = !pipe && !table && convtaps_fill_ok(A) && (A.fill_rec != nullptr || plan_sink() != nullptr) && (int64_t)a.HiWi * ldx * 4 < ((int64_t)1 << 32) &&
-                          a.HiWi < (1 << 24) && ldx * 4 < ((int64_t)1 << 24);
-        bool xd4 = n_ct >= 4;
-        if (A.tune.exact_xd > 0) xd4 = A.tune.exact_xd == 4;
-        if (table) {
-            // (launched above)
-        } else
-        if (pipe2 && rbx == 16 && A.unit_coef) KN_LAUNCH("convtaps_exact_pipe_kernel<16,128-column tiles>", (convtaps_exact_pipe_kernel<16, false, 2, 2>), dim3((unsigned)grid), dim3(256), 0, s, a, n_cob, n_rb);
-        else if (pipe2 && rbx == 16) KN_LAUNCH("convtaps_exact_pipe_kernel<16,coef,128-column tiles>", (convtaps_exact_pipe_kernel<16, true, 2, 2>), dim3((unsigned)grid), dim3(256), 0, s, a, n_cob, n_rb);
-        else if (pipe2 && A.unit_coef) KN_LAUNCH("convtaps_exact_pipe_kernel<8,128-column tiles>", (convtaps_exact_pipe_kernel<8, false, 2, 2>), dim3((unsigned)grid), dim3(256), 0, s, a, n_cob, n_rb);
-        else if (pipe2) KN_LAUNCH("convtaps_exact_pipe_kernel<8,coef,128-column tiles>", (convtaps_exact_pipe_kernel<8, true, 2, 2>), dim3((unsigned)grid), dim3(256), 0, s, a, n_cob, n_rb);
-        else if (pipe && rbx == 16 && A.unit_coef && xd4) KN_LAUNCH("convtaps_exact_pipe_kernel<16,rows in flight=4>", (convtaps_exact_pipe_kernel<16, false, 4>), dim3((unsigned)grid), dim3(256), 0, s, a, n_cob, n_rb);
-        else if (pipe && rbx == 16 && xd4) KN_LAUNCH("convtaps_exact_pipe_kernel<16,coef,rows in flight=4>", (convtaps_exact_pipe_kernel<16, true, 4>), dim3((unsigned)grid), dim3(256), 0, s, a, n_cob, n_rb);
-        else if (pipe && rbx == 16 && A.unit_coef) KN_LAUNCH("convtaps_exact_pipe_kernel<16>", (convtaps_exact_pipe_kernel<16>), dim3((unsigned)grid), dim3(256), 0, s, a, n_cob, n_rb);
-        else if (pipe && rbx == 16) KN_LAUNCH("convtaps_exact_pipe_kernel<16,coef>", (convtaps_exact_pipe_kernel<16, true>), dim3((unsigned)grid), dim3(256), 0, s, a, n_cob, n_rb);
-        else if (pipe && A.unit_coef) KN_LAUNCH("convtaps_exact_pipe_kernel<8>", (convtaps_exact_pipe_kernel<8>), dim3((unsigned)grid), dim3(256), 0, s, a, n_cob, n_rb);
-        else if (pipe) KN_LAUNCH("convtaps_exact_pipe_kernel<8,coef>", (convtaps_exact_pipe_kernel<8, true>), dim3((unsigned)grid), dim3(256), 0, s, a, n_cob, n_rb);
-        else if (fill) {
-            // 64 output channels per wavefront (the slot bookkeeping once per 64 channels) when that still leaves every SIMD its three wavefronts, else 32;
-            // two 64-column tiles per wavefront (the bookkeeping once per 128 columns) on batches of whole 128-column tiles when that still leaves every SIMD its two
-            // wavefronts (the two-tile forms hold 128 + 64 result registers: two wavefronts per SIMD).  Tuning::no_fill_tiles2 keeps one tile (parity tests' side-by-side).
-            const bool t2_ok = A.ntaps <= 16 && n_vecs % 128 == 0 && ldx % 2 == 0 && ldy % 2 == 0 && ((uintptr_t)x) % 8 == 0 && ((uintptr_t)y) % 8 == 0 && !A.tune.no_fill_tiles2;
-            const int64_t n_ct2 = n_vecs / 128;
-            const bool wide1 = A.ntaps <= 16 && A.Cout > 32 && (int64_t)a.n_pix * ((A.Cout + 63) / 64) * ((n_vecs + 63) / 64) >= 3 * 1024;
-            const bool wide2 = t2_ok && A.Cout > 32 && (int64_t)a.n_pix * ((A.Cout + 63) / 64) * n_ct2 >= 2 * 1024;
-            const bool narrow2 = t2_ok && !wide2 && !wide1 && (int64_t)a.n_pix * ((A.Cout + 31) / 32) * n_ct2 >= 2 * 1024;      // (64 channels x one tile is the same work per wavefront: kept where it qualifies)
-            bool tiles2 = wide2 || narrow2;
-            bool wide_sel = tiles2 ? wide2 : wide1;
-            if (A.tune.fill_form > 0 && A.ntaps <= 16) {             // (diagnostic build: force a form where the operands allow it -- tools/fill_bench.py)
-                const bool want2 = A.tune.fill_form >= 3 && t2_ok;
-                tiles2 = want2;
-                wide_sel = (A.tune.fill_form == 2 || A.tune.fill_form == 4) && A.Cout > 32;
-            }
-            const int n_ctf = tiles2 ? (int)n_ct2 : (int)((n_vecs + 63) / 64);
-            const bool wide = wide_sel;
-            const int n_cc = (int)((A.Cout + (wide ? 63 : 31)) / (wide ? 64 : 32));
-            const int64_t n_wg = ((int64_t)a.n_pix * n_cc * n_ctf + 3) / 4;
-            KN_REQUIRE(n_wg + 8 < ((int64_t)1 << 31), KN_ERR_UNSUPPORTED, "grid too large for the filled-in order-preserving kernel");
-            const std::string d = std::string("convtaps_exact_fill_kernel") + (A.ntaps <= 16 ? (wide ? "<taps in registers, 64 channels per wavefront" : "<taps in registers") : "") +
-                                  (A.ntaps <= 16 ? (tiles2 ? ", two column tiles per wavefront>" : ">") : "") +
-                                  " (stored values formed per lane, products on the matrix pipe, " + std::to_string(A.fill_n) + " slot records)";
-            const dim3 gridf((unsigned)(((n_wg + 7) / 8) * 8));
-            const FillRec* rec = reinterpret_cast<const FillRec*>(A.fill_rec);
-            if (tiles2 && wide) KN_LAUNCH(d, (convtaps_exact_fill_kernel<16, true, 2>), gridf, dim3(256), 0, s, a, A.fill_ptr, rec, n_cc, n_ctf, n_wg);
-            else if (tiles2) KN_LAUNCH(d, (convtaps_exact_fill_kernel<16, false, 2>), gridf, dim3(256), 0, s, a, A.fill_ptr, rec, n_cc, n_ctf, n_wg);
-            else if (wide) KN_LAUNCH(d, (convtaps_exact_fill_kernel<16, true>), gridf, dim3(256), 0, s, a, A.fill_ptr, rec, n_cc, n_ctf, n_wg);
-            else if (A.ntaps <= 16) KN_LAUNCH(d, (convtaps_exact_fill_kernel<16, false>), gridf, dim3(256), 0, s, a, A.fill_ptr, rec, n_cc, n_ctf, n_wg);
-            else KN_LAUNCH(d, (convtaps_exact_fill_kernel<0, false>), gridf, dim3(256), 0, s, a, A.fill_ptr, rec, n_cc, n_ctf, n_wg);
-        }
-        else if (v4) KN_LAUNCH("convtaps_exact_kernel<vec=4>", convtaps_exact_kernel<4>, dim3((unsigned)grid), dim3(256), 0, s, a, n_cob, n_rb);
-        else KN_LAUNCH("convtaps_exact_kernel<vec=1>", convtaps_exact_kernel<1>, dim3((unsigned)grid), dim3(256), 0, s, a, n_cob, n_rb);
-        if (A.has_last) {
-            const int64_t out_last = A.Cout * A.Hout * A.Wout;
-            KN_LAUNCH("conv_lastrow_kernel", conv_lastrow_kernel, dim3((unsigned)std::min<int64_t>((n_vecs + 255) / 256, 256)), dim3(256), 0, s, A.lastcol, out_last,
-                               x + a.last_in_row * ldx, y + out_last * ldy, n_vecs, a.relu, a.absmax);
-        }
-        if (A.n_zero > 0) {                                  // kn_convtaps_drop_zero_entries: behind the main kernel, on its stream
-            const int64_t gz = A.n_zero * a.HoWo * ((n_vecs + 255) / 256);
-            KN_REQUIRE(gz < ((int64_t)1 << 31), KN_ERR_UNSUPPORTED, "too many zero-valued tap entries for the guard launch");
-            KN_LAUNCH("convtaps_zero_guard_kernel<" + std::to_string(A.n_zero) + " zero tap entries>", convtaps_zero_guard_kernel, dim3((unsigned)gz), dim3(256), 0, s, a, A.zero_ent, A.n_zero);
-        }
-        KN_HIP(hipGetLastError());
-        return KN_OK;
-    }
     a.wide_store = (a.vec_ok && ldy % 4 == 0 && ((uintptr_t)y) % 16 == 0) ? 1 : 0;
-    // every matrix-core kernel below streams its tiles out through kn_store_tile when the stores are wide and the batch fills whole tiles of the
-    // kernel that will run (128 columns for the 128 x 128 and bf16x3 tiles -- so also the half-batch windows of the overlapped forward at 256 images --,
-    // 256 for the 64 x 256 and small-K tiles): then max |Y| rides in the epilogues (tiles + conv_lastrow_kernel for the homogeneous row)
-    const int64_t nb_tile = (((flags & KN_FLAG_BF16X3) && convtaps_bf16x3_ok(A, x, ldx, n_vecs, y, ldy)) || (A.cout_pad % 128 == 0 && A.Cout > 64)) ? 128 : 256;
-    if (absmax && a.wide_store && n_vecs % nb_tile == 0) {
-        a.absmax = absmax;
-        if (absmax_fused) *absmax_fused = true;
-    }
     a.max_slots = A.max_slots;
     a.ntaps = (int32_t)A.ntaps;
     a.last_in_row = A.Cin * A.Hin * A.Win;
+#ifdef KN_ABLATION
+    a.abl = A.tune.abl;
+#endif
+    a.sk_desc = A.sk_desc; a.sk_stride = (int32_t)A.sk_stride; a.sk_tab_rows = (int32_t)A.sk_tab_rows;
+    return a;
+}
+
+// the homogeneous row of Y, behind the main kernel of every regime
+static void launch_lastrow(const ConvTapsDev& A, const ConvArgs& a, hipStream_t s) {
+    if (!A.has_last) return;
+    const int64_t out_last = A.Cout * A.Hout * A.Wout, n_vecs = a.n_vecs;
+    KN_LAUNCH("conv_lastrow_kernel", conv_lastrow_kernel, dim3((unsigned)std::min<int64_t>((n_vecs + 255) / 256, 256)), dim3(256), 0, s, A.lastcol, out_last,
+              a.X + a.last_in_row * a.ldx, a.Y + out_last * a.ldy, n_vecs, a.relu, a.absmax);
+}
+
+// KN_FLAG_EXACT: which order-preserving kernel takes a call, decided before anything is launched
+struct ExactChoice {
+    enum Kernel { TABLE, PIPE, FILL, PLAIN } kernel = PLAIN;
+    int rbx = 8;              // PIPE: output channels per wavefront (16 | 8); the channel bundles n_cob / n_rb of PIPE and PLAIN follow from it
+    int xd = 2;               // PIPE: activation rows in flight (2 | 4)
+    int vec = 1;              // PIPE: batch columns per lane (4 | 2); PLAIN: 4 | 1
+    int64_t n_ct = 0;         // PIPE / PLAIN: column tiles of 64 * vec columns
+    bool wide = false;        // FILL: 64 output channels per wavefront instead of 32
+    bool tiles2 = false;      // FILL: two 64-column tiles per wavefront
+};
+
+static ExactChoice exact_choice(const ConvTapsDev& A, const ConvArgs& a) {
+    const int64_t n_vecs = a.n_vecs, ldx = a.ldx, ldy = a.ldy;
+    const uintptr_t x = (uintptr_t)a.X, y = (uintptr_t)a.Y;
+    ExactChoice c;
+    const bool v4 = a.vec_ok && n_vecs >= 256;
+    const int pipe_mode = A.tune.exact_pipe;
+    const bool pipe_shape = pipe_mode > 0 && !A.has_dups && A.max_slots <= 64 && (a.last_in_row + 1) * ldx < ((int64_t)1 << 31) &&
+                            (int64_t)A.ntaps * A.cin_pad * A.cout_pad < ((int64_t)1 << 31);
+    const bool pipe4 = pipe_shape && v4 && ldy % 4 == 0 && y % 16 == 0;
+    // two batch columns per lane (128-column tiles): a half-batch window of the overlapped forward at 256 images, or a batch that fills 128-column
+    // tiles better than 256-column ones (384 images).  Tuning::exact_vec = 2 | 4 forces either where both apply (diagnostic build).
+    const bool pipe2_ok = pipe_shape && n_vecs >= 128 && n_vecs % 2 == 0 && ldx % 2 == 0 && ldy % 2 == 0 && x % 8 == 0 && y % 8 == 0;
+    const bool pipe2 = pipe2_ok && (A.tune.exact_vec == 2 || (A.tune.exact_vec != 4 && (!pipe4 || (n_vecs + 127) / 128 * 128 < (n_vecs + 255) / 256 * 256)));
+    const bool pipe = pipe4 || pipe2;
+    c.vec = pipe2 ? 2 : (v4 ? 4 : 1);
+    c.n_ct = (n_vecs + 64 * c.vec - 1) / (64 * c.vec);
+    // 16 output channels per wavefront when that still leaves every SIMD several wavefronts, else 8
+    c.rbx = (pipe && pipe_mode >= 16 && A.Cout % 16 == 0 && (int64_t)a.n_pix * (A.Cout / 16) * c.n_ct >= 4096) ? 16 : 8;
+    // a factored stand-in of an untiled CSR that carries the stored-column table (kn_convtaps_drop_zero_entries) on a wide batch: the matrix-pipe
+    // grouped kernel reads its values from the tap table (kn_csr_mfma.hip, TAPS).  Tuning::no_exact_table keeps the conv pipeline instead.
+    if (A.ex_tab != nullptr && n_vecs >= 128 && !A.tune.no_exact_table) {
+        c.kernel = ExactChoice::TABLE;
+    } else if (pipe) {
+        c.kernel = ExactChoice::PIPE;
+        // four activation rows in flight when the batch spans several 256-column tiles (the rows of a [D, 4096] block are L2 misses; at one tile --
+        // VGG-16 at 256 images -- three rows in flight measured 2-3 % slower than two).  Tuning::exact_xd = 2 | 4 overrides (diagnostic build).
+        bool xd4 = c.n_ct >= 4;
+        if (A.tune.exact_xd > 0) xd4 = A.tune.exact_xd == 4;
+        c.xd = (xd4 && c.vec == 4 && c.rbx == 16) ? 4 : 2;      // (instantiated for 16 channels x 256-column tiles only)
+    } else if (convtaps_fill_ok(A) && (A.fill_rec != nullptr || plan_sink() != nullptr) && (int64_t)a.HiWi * ldx * 4 < ((int64_t)1 << 32) && a.HiWi < (1 << 24) &&
+               ldx * 4 < ((int64_t)1 << 24)) {
+        // filled-in operators (more than 64 slots per pixel, or several slots on one pixel pair): convtaps_exact_fill_kernel (its records exist from the first kn_spmm on)
+        c.kernel = ExactChoice::FILL;
+        // 64 output channels per wavefront (the slot bookkeeping once per 64 channels) when that still leaves every SIMD its three wavefronts, else 32;
+        // two 64-column tiles per wavefront (the bookkeeping once per 128 columns) on batches of whole 128-column tiles when that still leaves every SIMD its two
+        // wavefronts (the two-tile forms hold 128 + 64 result registers: two wavefronts per SIMD).  Tuning::no_fill_tiles2 keeps one tile (parity tests' side-by-side).
+        const bool t2_ok = A.ntaps <= 16 && n_vecs % 128 == 0 && ldx % 2 == 0 && ldy % 2 == 0 && x % 8 == 0 && y % 8 == 0 && !A.tune.no_fill_tiles2;
+        const int64_t n_ct2 = n_vecs / 128;
+        const bool wide1 = A.ntaps <= 16 && A.Cout > 32 && (int64_t)a.n_pix * ((A.Cout + 63) / 64) * ((n_vecs + 63) / 64) >= 3 * 1024;
+        const bool wide2 = t2_ok && A.Cout > 32 && (int64_t)a.n_pix * ((A.Cout + 63) / 64) * n_ct2 >= 2 * 1024;
+        const bool narrow2 = t2_ok && !wide2 && !wide1 && (int64_t)a.n_pix * ((A.Cout + 31) / 32) * n_ct2 >= 2 * 1024;      // (64 channels x one tile is the same work per wavefront: kept where it qualifies)
+        c.tiles2 = wide2 || narrow2;
+        c.wide = c.tiles2 ? wide2 : wide1;
+        if (A.tune.fill_form > 0 && A.ntaps <= 16) {             // (diagnostic build: force a form where the operands allow it -- tools/fill_bench.py)
+            c.tiles2 = A.tune.fill_form >= 3 && t2_ok;
+            c.wide = (A.tune.fill_form == 2 || A.tune.fill_form == 4) && A.Cout > 32;
+        }
+    }
+    return c;
+}
+
+typedef void (*ExactPipeKernel)(ConvArgs, int, int64_t);
+template <int RBX, int XD, int VEC>
+static ExactPipeKernel exact_pipe_kernel(bool coef) {
+    return coef ? convtaps_exact_pipe_kernel<RBX, true, XD, VEC> : convtaps_exact_pipe_kernel<RBX, false, XD, VEC>;
+}
+
+static int spmm_exact(const ConvTapsDev& A, ConvArgs& a, hipStream_t s) {
+    const ExactChoice c = exact_choice(A, a);
+    const int64_t n_vecs = a.n_vecs;
+    const int n_cob = (int)((A.Cout + c.rbx - 1) / c.rbx);
+    const int64_t n_rb = ((int64_t)a.n_pix * n_cob + 3) / 4;
+    // Channel-bundle groups (convtaps_exact_pipe_kernel): with g groups every XCD works on 1/g (g = 8) or 2/g of the output channels for all
+    // pixels, so its share of the taps stays in its 4 MiB L2 for the scalar tap loads -- 9.4 MB of taps on the 512-channel layers of VGG-16.
+    // Same-process A/B, exact mode, ms at 1 / 4 / 8 groups: conv3_2 (2.4 MB of taps) 13.63 / 13.49 / 14.60, conv4_1 6.99 / 6.75 / 6.84,
+    // conv4_2 14.05 / 13.54 / 13.48, conv4_3 14.01 / 13.34 / 13.53, conv5_1 4.26 / 3.82 / 3.82, conv5_2 4.24 / 3.84 / 4.10; layers with small tap
+    // matrices lose 5 % (conv1_2, conv2_x: the bundles of a pixel no longer share its gathered rows in one XCD).  Rule: 4 groups when the taps exceed half
+    // of the L2 (2 MB: VGG-16 conv3_x and up; AllConvNet's 192-channel layers, 1.3 MB at 16 column tiles per layer, lose 10 % when grouped).  Tuning::exact_cob_groups overrides (diagnostic build).
+    {
+        const int64_t tap_bytes = 4 * A.ntaps * A.cin_pad * A.cout_pad;
+        int g = tap_bytes > (2 << 20) ? 4 : 1;
+        if (A.tune.exact_cob_groups > 0) g = A.tune.exact_cob_groups;
+        while (g > 1 && n_cob % g != 0) g >>= 1;
+        a.tail_main = g > 1 ? n_cob / g : 0;
+    }
+    const dim3 grid((unsigned)(((c.n_ct * n_rb + 7) / 8) * 8));
+    if (c.kernel == ExactChoice::TABLE) {
+        int rc = convtaps_exact_table_spmm(A, a.X, a.ldx, n_vecs, a.Y, a.ldy, a.relu, s);
+        if (rc) return rc;
+    } else if (c.kernel == ExactChoice::PIPE) {
+        // the ten instantiations: 16 | 8 channels x coefficients or not, on 128-column tiles or 256-column ones, the latter with four rows in flight for 16 channels only
+        const bool coef = !A.unit_coef;
+        const ExactPipeKernel k = c.vec == 2 ? (c.rbx == 16 ? exact_pipe_kernel<16, 2, 2>(coef) : exact_pipe_kernel<8, 2, 2>(coef))
+                                  : c.rbx == 8 ? exact_pipe_kernel<8, 2, 4>(coef)
+                                               : (c.xd == 4 ? exact_pipe_kernel<16, 4, 4>(coef) : exact_pipe_kernel<16, 2, 4>(coef));
+        KN_LAUNCH("convtaps_exact_pipe_kernel<" + std::to_string(c.rbx) + (coef ? ",coef" : "") + (c.vec == 2 ? ",128-column tiles" : (c.xd == 4 ? ",rows in flight=4" : "")) + ">", k, grid,
+                  dim3(256), 0, s, a, n_cob, n_rb);
+    } else if (c.kernel == ExactChoice::FILL) {
+        const bool regs = A.ntaps <= 16;                         // taps held in registers (else one value-row load per slot: 32 channels x one tile only)
+        const int n_ctf = c.tiles2 ? (int)(n_vecs / 128) : (int)((n_vecs + 63) / 64);
+        const int n_cc = (int)((A.Cout + (c.wide ? 63 : 31)) / (c.wide ? 64 : 32));
+        const int64_t n_wg = ((int64_t)a.n_pix * n_cc * n_ctf + 3) / 4;
+        KN_REQUIRE(n_wg + 8 < ((int64_t)1 << 31), KN_ERR_UNSUPPORTED, "grid too large for the filled-in order-preserving kernel");
+        void (*const k)(ConvArgs, const int32_t*, const FillRec*, int, int, int64_t) =
+            c.tiles2 ? (c.wide ? convtaps_exact_fill_kernel<16, true, 2> : convtaps_exact_fill_kernel<16, false, 2>)
+                     : (c.wide ? convtaps_exact_fill_kernel<16, true> : (regs ? convtaps_exact_fill_kernel<16, false> : convtaps_exact_fill_kernel<0, false>));
+        KN_LAUNCH(std::string("convtaps_exact_fill_kernel") + (regs ? (c.wide ? "<taps in registers, 64 channels per wavefront" : "<taps in registers") : "") +
+                      (regs ? (c.tiles2 ? ", two column tiles per wavefront>" : ">") : "") + " (stored values formed per lane, products on the matrix pipe, " + std::to_string(A.fill_n) + " slot records)",
+                  k, dim3((unsigned)(((n_wg + 7) / 8) * 8)), dim3(256), 0, s, a, A.fill_ptr, reinterpret_cast<const FillRec*>(A.fill_rec), n_cc, n_ctf, n_wg);
+    } else {
+        KN_LAUNCH(c.vec == 4 ? "convtaps_exact_kernel<vec=4>" : "convtaps_exact_kernel<vec=1>", (c.vec == 4 ? convtaps_exact_kernel<4> : convtaps_exact_kernel<1>), grid, dim3(256), 0, s, a, n_cob, n_rb);
+    }
+    launch_lastrow(A, a, s);
+    if (A.n_zero > 0) {                                  // kn_convtaps_drop_zero_entries: behind the main kernel, on its stream
+        const int64_t gz = A.n_zero * a.HoWo * ((n_vecs + 255) / 256);
+        KN_REQUIRE(gz < ((int64_t)1 << 31), KN_ERR_UNSUPPORTED, "too many zero-valued tap entries for the guard launch");
+        KN_LAUNCH("convtaps_zero_guard_kernel<" + std::to_string(A.n_zero) + " zero tap entries>", convtaps_zero_guard_kernel, dim3((unsigned)gz), dim3(256), 0, s, a, A.zero_ent, A.n_zero);
+    }
+    return KN_OK;
+}
+
+typedef void (*ConvKernel)(ConvArgs);
+template <int MT, bool TAIL>
+static ConvKernel bf16x3_kernel(bool coef) {
+    return coef ? convtaps_bf16x3_kernel<MT, 128, 2, 2, true, TAIL> : convtaps_bf16x3_kernel<MT, 128, 2, 2, false, TAIL>;
+}
+
+static int spmm_bf16x3(const ConvTapsDev& A, ConvArgs& a, hipStream_t s) {
+    const bool wide = A.Cout > 64;                          // 128 x 128 tiles; 64-channel layers take 64 x 128 (four wavefronts of 32 x 64)
+    const bool coef = !A.unit_coef;
     a.tapsB = A.tapsB;
     a.tapsB_plane = A.tapsB_plane;
-    if ((flags & KN_FLAG_BF16X3) && convtaps_bf16x3_ok(A, x, ldx, n_vecs, y, ldy)) {
-        const bool wide = A.Cout > 64;                          // 128 x 128 tiles; 64-channel layers take 64 x 128 (four wavefronts of 32 x 64)
-        a.n_mt = (int32_t)(A.cout_pad / (wide ? 128 : 64));
-        a.n_bt = (int32_t)(n_vecs / 128);
-        const int64_t items = (int64_t)a.n_pix * a.n_bt * a.n_mt;
-        const int64_t chunk = (items + 7) / 8;
-        a.tail_main = (int32_t)chunk;
-        const std::string d = std::string("convtaps_bf16x3_kernel<") + (wide ? "128x128" : "64x128") + ", 3-way bf16 split, 6 products>" + (A.unit_coef ? "" : "+coef");
-        if (wide) {
-            // last partial round of resident workgroups as quarter tiles (same split as launch_conv)
-            static const int64_t slots0 = xcd_slots(convtaps_bf16x3_kernel<128, 128, 2, 2, false, true>);
-            static const int64_t slots1 = xcd_slots(convtaps_bf16x3_kernel<128, 128, 2, 2, true, true>);
-            const int64_t slots = A.unit_coef ? slots0 : slots1;
-            const int64_t rem = slots > 0 ? chunk % slots : 0;
-            if (rem > 0 && !A.tune.no_tail_split) {
-                a.tail_main = (int32_t)(chunk - rem);
-                const int64_t grid = 8 * ((int64_t)a.tail_main + 4 * rem);
-                if (A.unit_coef) KN_LAUNCH(d + " tail_split", (convtaps_bf16x3_kernel<128, 128, 2, 2, false, true>), dim3((unsigned)grid), dim3(256), 0, s, a);
-                else KN_LAUNCH(d + " tail_split", (convtaps_bf16x3_kernel<128, 128, 2, 2, true, true>), dim3((unsigned)grid), dim3(256), 0, s, a);
-            } else {
-                if (A.unit_coef) KN_LAUNCH(d, (convtaps_bf16x3_kernel<128, 128, 2, 2, false, false>), dim3((unsigned)(8 * chunk)), dim3(256), 0, s, a);
-                else KN_LAUNCH(d, (convtaps_bf16x3_kernel<128, 128, 2, 2, true, false>), dim3((unsigned)(8 * chunk)), dim3(256), 0, s, a);
-            }
-        } else {
-            if (A.unit_coef) KN_LAUNCH(d, (convtaps_bf16x3_kernel<64, 128, 2, 2, false, false>), dim3((unsigned)(8 * chunk)), dim3(256), 0, s, a);
-            else KN_LAUNCH(d, (convtaps_bf16x3_kernel<64, 128, 2, 2, true, false>), dim3((unsigned)(8 * chunk)), dim3(256), 0, s, a);
-        }
-        if (A.has_last) {
-            const int64_t out_last = A.Cout * A.Hout * A.Wout;
-            KN_LAUNCH("conv_lastrow_kernel", conv_lastrow_kernel, dim3((unsigned)std::min<int64_t>((n_vecs + 255) / 256, 256)), dim3(256), 0, s, A.lastcol, out_last,
-                      x + a.last_in_row * ldx, y + out_last * ldy, n_vecs, a.relu, a.absmax);
-        }
-        KN_HIP(hipGetLastError());
-        return KN_OK;
+    a.n_mt = (int32_t)(A.cout_pad / (wide ? 128 : 64));
+    a.n_bt = (int32_t)(a.n_vecs / 128);
+    const int64_t items = (int64_t)a.n_pix * a.n_bt * a.n_mt;
+    const int64_t chunk = (items + 7) / 8;
+    a.tail_main = (int32_t)chunk;
+    const std::string d = std::string("convtaps_bf16x3_kernel<") + (wide ? "128x128" : "64x128") + ", 3-way bf16 split, 6 products>" + (coef ? "+coef" : "");
+    int64_t rem = 0;
+    if (wide) {
+        // last partial round of resident workgroups as quarter tiles (same split as launch_conv)
+        static const int64_t slots[2] = {xcd_slots(bf16x3_kernel<128, true>(false)), xcd_slots(bf16x3_kernel<128, true>(true))};
+        if (slots[coef] > 0 && !A.tune.no_tail_split) rem = chunk % slots[coef];
     }
+    if (rem > 0) {
+        a.tail_main = (int32_t)(chunk - rem);
+        const ConvKernel k = bf16x3_kernel<128, true>(coef);
+        KN_LAUNCH(d + " tail_split", k, dim3((unsigned)(8 * ((int64_t)a.tail_main + 4 * rem))), dim3(256), 0, s, a);
+    } else {
+        const ConvKernel k = wide ? bf16x3_kernel<128, false>(coef) : bf16x3_kernel<64, false>(coef);
+        KN_LAUNCH(d, k, dim3((unsigned)(8 * chunk)), dim3(256), 0, s, a);
+    }
+    launch_lastrow(A, a, s);
+    return KN_OK;
+}
+
+static int spmm_mfma(const ConvTapsDev& A, ConvArgs& a, hipStream_t s) {
+    const int64_t n_vecs = a.n_vecs;
     const bool big_m = A.cout_pad % 128 == 0 && A.Cout > 64;
     const bool k16 = A.cin_pad % 16 == 0;
     if (!A.tune.no_smallk && (int64_t)A.max_slots * A.Cin + (A.has_last ? 1 : 0) <= SMALLK_MAX && a.wide_store && n_vecs % 256 == 0 && A.cout_pad % 64 == 0) {
@@ -2397,11 +2394,30 @@ int convtaps_spmm(const ConvTapsDev& A, int64_t rows, int64_t cols, const float*
         if (k16) launch_conv<64, 256, 16, 1, 4>(a, A.tune, s);
         else launch_conv<64, 256, 4, 1, 4>(a, A.tune, s);
     }
-    if (A.has_last) {
-        const int64_t out_last = A.Cout * A.Hout * A.Wout;
-        KN_LAUNCH("conv_lastrow_kernel", conv_lastrow_kernel, dim3((unsigned)std::min<int64_t>((n_vecs + 255) / 256, 256)), dim3(256), 0, s, A.lastcol, out_last,
-                           x + a.last_in_row * ldx, y + out_last * ldy, n_vecs, a.relu, a.absmax);
+    launch_lastrow(A, a, s);
+    return KN_OK;
+}
+
+int convtaps_spmm(const ConvTapsDev& A, const float* x, int64_t ldx, int64_t n_vecs, float* y, int64_t ldy, uint32_t flags, hipStream_t s, float* absmax,
+                  bool* absmax_fused) {
+    if (absmax_fused) *absmax_fused = false;
+    ConvArgs a = conv_args(A, x, ldx, n_vecs, y, ldy, flags);
+    int rc;
+    if (flags & KN_FLAG_EXACT) {
+        rc = spmm_exact(A, a, s);
+    } else {
+        const bool bf16x3 = (flags & KN_FLAG_BF16X3) && convtaps_bf16x3_ok(A, x, ldx, n_vecs, y, ldy);
+        // every matrix-core kernel streams its tiles out through kn_store_tile when the stores are wide and the batch fills whole tiles of the
+        // kernel that will run (128 columns for the 128 x 128 and bf16x3 tiles -- so also the half-batch windows of the overlapped forward at 256 images --,
+        // 256 for the 64 x 256 and small-K tiles): then max |Y| rides in the epilogues (tiles + conv_lastrow_kernel for the homogeneous row)
+        const int64_t nb_tile = (bf16x3 || (A.cout_pad % 128 == 0 && A.Cout > 64)) ? 128 : 256;
+        if (absmax && a.wide_store && n_vecs % nb_tile == 0) {
+            a.absmax = absmax;
+            if (absmax_fused) *absmax_fused = true;
+        }
+        rc = bf16x3 ? spmm_bf16x3(A, a, s) : spmm_mfma(A, a, s);
     }
+    if (rc) return rc;
     KN_HIP(hipGetLastError());
     return KN_OK;
 }

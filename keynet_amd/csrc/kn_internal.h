@@ -126,39 +126,45 @@ PlanSink*& plan_sink();   // thread-local; null outside kn_spmm_plan
 // create, kn_spmm's dispatch depends on the handle and the call's arguments only.  The first block are the switches the parity tests use to put
 // two formulations of one product side by side; the second block are measured tuning constants that only the diagnostic build (-DKN_ABLATION,
 // tools/ablate_conv.sh) reads from the environment -- in the product library they are the defaults below.
+// One line per knob: X(field, environment variable, default, read from the environment by the diagnostic build only).  struct Tuning, tuning_from_env and
+// Tuning::describe (in this order) are generated from this list.
+#define KN_TUNING_KNOBS(X) \
+    X(no_sptr, "KN_NO_SPTR", 0, false)               /* =1         conv-taps matrix-core kernel: per-thread pointers / generic loader instead of wave-uniform pointers */ \
+    X(no_smallk_pipe, "KN_NO_SMALLK_PIPE", 0, false) /* =1         first-layer operators: the one-shot small-K kernel instead of the persistent pipeline */ \
+    X(no_group_pipe, "KN_NO_GROUP_PIPE", 0, false)   /* =1         CSR pattern groups: the plain grouped kernel instead of the software-pipelined one */ \
+    X(no_big_groups, "KN_NO_BIG_GROUPS", 0, false)   /* =1         a keyed Linear's rows as ordinary 16-row bundles instead of the LDS-staged workgroup kernel */ \
+    X(no_exact_table, "KN_NO_EXACT_TABLE", 0, false) /* =1         factored untiled conv under KN_FLAG_EXACT: the conv pipeline instead of the stored-column table kernel */ \
+    X(group_mfma, "KN_GROUP_MFMA", -1, false)        /* =0|1       CSR pattern groups with their products on the matrix pipe: never / always (-1: the dispatch rule) */ \
+    X(big_mfma16, "KN_BIG_MFMA16", -1, false)        /* =0|1       a keyed Linear's 16-row chunks on the matrix pipe: never / always (-1: the dispatch rule) */ \
+    X(mf_nrb, "KN_MF_NRB", 1, false)                 /* =1|2|3     32-row blocks per chunk of the matrix-pipe grouped kernel */ \
+    X(table_nrb, "KN_TABLE_NRB", 0, false)           /* =1|2|3     32-channel blocks per workgroup of the table kernel (0: the rule) */ \
+    X(no_fill_exact, "KN_NO_FILL_EXACT", 0, false)   /* =1         filled-in conv operators (> 64 slots per pixel, or several slots on one (output, input) pixel pair) under KN_FLAG_EXACT: the generic kernel instead of convtaps_exact_fill_kernel */ \
+    X(no_fill_tiles2, "KN_NO_FILL_TILES2", 0, false) /* =1         ... on batches of whole 128-column tiles: one 64-column tile per wavefront instead of two */ \
+    /* ---- diagnostic build only ---- */ \
+    X(occ, "KN_OCC", 0, true)                        /* workgroups per CU cap of the 128 x 128 conv-taps launch (0: the rule) */ \
+    X(no_tail_split, "KN_NO_TAIL_SPLIT", 0, true) \
+    X(no_smallk, "KN_NO_SMALLK", 0, true) \
+    X(exact_pipe, "KN_EXACT_PIPE", 16, true)         /* 0 = plain exact conv kernel, 8 / 16 = channels per wavefront of the pipeline */ \
+    X(exact_cob_groups, "KN_EXACT_COB_GROUPS", 0, true) /* (0: the rule) */ \
+    X(exact_xd, "KN_EXACT_XD", 0, true)              /* 2 | 4 activation rows in flight (0: the rule) */ \
+    X(exact_vec, "KN_EXACT_VEC", 0, true)            /* 2 | 4 batch columns per lane of the exact conv pipeline (0: the rule) */ \
+    X(mf_pf, "KN_MF_PF", 8, true)                    /* operand columns in flight of the matrix-pipe grouped kernel */ \
+    X(table_window, "KN_TABLE_WINDOW", 0, true)      /* (0: the rule) */ \
+    X(table_strip, "KN_TABLE_STRIP", -1, true)       /* (-1: best of the candidates, 0: keep the ball order) */ \
+    X(no_patch, "KN_NO_PATCH", 0, true) \
+    X(conv_ball, "KN_CONV_BALL", 64, true)           /* output pixels per breadth-first ball of a conv-taps operator's processing order */ \
+    X(no_row_order, "KN_NO_ROW_ORDER", 0, true) \
+    X(chain_no_cl, "KN_CHAIN_NO_CL", 0, true) \
+    X(chain_no_rpl2, "KN_CHAIN_NO_RPL2", 0, true)    /* whole-net kernel: one output row per lane in the pattern walk */ \
+    X(chain_no_early, "KN_CHAIN_NO_EARLY", 0, true)  /* whole-net kernel: column pools staged at the start of their own layer */ \
+    X(chain_no_seq, "KN_CHAIN_NO_SEQ", 0, true)      /* whole-net kernel: thin layers read their columns from the staged pool instead of walking a re-ordered input sequentially */ \
+    X(chain_no_share, "KN_CHAIN_NO_SHARE", 0, true)  /* whole-net kernel: every lane streams its own copy of its row's values (no shared value blocks) */ \
+    X(fill_form, "KN_FILL_FORM", 0, true)            /* filled-in order-preserving kernel: 0 = the dispatch rule, 1 / 2 = 32 / 64 channels x one column tile, 3 / 4 = 32 / 64 channels x two tiles */ \
+    X(abl, "KN_ABL", 0, true)                        /* kernel ablation mask (kn_conv.hip, KN_ABLATION code paths) */
 struct Tuning {
-    int no_sptr = 0;          // KN_NO_SPTR=1         conv-taps matrix-core kernel: per-thread pointers / generic loader instead of wave-uniform pointers
-    int no_smallk_pipe = 0;   // KN_NO_SMALLK_PIPE=1  first-layer operators: the one-shot small-K kernel instead of the persistent pipeline
-    int no_group_pipe = 0;    // KN_NO_GROUP_PIPE=1   CSR pattern groups: the plain grouped kernel instead of the software-pipelined one
-    int no_big_groups = 0;    // KN_NO_BIG_GROUPS=1   a keyed Linear's rows as ordinary 16-row bundles instead of the LDS-staged workgroup kernel
-    int no_exact_table = 0;   // KN_NO_EXACT_TABLE=1  factored untiled conv under KN_FLAG_EXACT: the conv pipeline instead of the stored-column table kernel
-    int group_mfma = -1;      // KN_GROUP_MFMA=0|1    CSR pattern groups with their products on the matrix pipe: never / always (-1: the dispatch rule)
-    int big_mfma16 = -1;      // KN_BIG_MFMA16=0|1    a keyed Linear's 16-row chunks on the matrix pipe: never / always (-1: the dispatch rule)
-    int mf_nrb = 1;           // KN_MF_NRB=1|2|3      32-row blocks per chunk of the matrix-pipe grouped kernel
-    int table_nrb = 0;        // KN_TABLE_NRB=1|2|3   32-channel blocks per workgroup of the table kernel (0: the rule)
-    int no_fill_exact = 0;    // KN_NO_FILL_EXACT=1   filled-in conv operators (> 64 slots per pixel, or several slots on one (output, input) pixel pair) under KN_FLAG_EXACT: the generic kernel instead of convtaps_exact_fill_kernel
-    int no_fill_tiles2 = 0;   // KN_NO_FILL_TILES2=1  ... on batches of whole 128-column tiles: one 64-column tile per wavefront instead of two
-    // ---- diagnostic build only ----
-    int occ = 0;              // KN_OCC               workgroups per CU cap of the 128 x 128 conv-taps launch (0: the rule)
-    int no_tail_split = 0;    // KN_NO_TAIL_SPLIT
-    int no_smallk = 0;        // KN_NO_SMALLK
-    int exact_pipe = 16;      // KN_EXACT_PIPE        0 = plain exact conv kernel, 8 / 16 = channels per wavefront of the pipeline
-    int exact_cob_groups = 0; // KN_EXACT_COB_GROUPS  (0: the rule)
-    int exact_xd = 0;         // KN_EXACT_XD          2 | 4 activation rows in flight (0: the rule)
-    int exact_vec = 0;        // KN_EXACT_VEC         2 | 4 batch columns per lane of the exact conv pipeline (0: the rule)
-    int mf_pf = 8;            // KN_MF_PF             operand columns in flight of the matrix-pipe grouped kernel
-    int table_window = 0;     // KN_TABLE_WINDOW      (0: the rule)
-    int table_strip = -1;     // KN_TABLE_STRIP       (-1: best of the candidates, 0: keep the ball order)
-    int conv_ball = 64;       // KN_CONV_BALL         output pixels per breadth-first ball of a conv-taps operator's processing order
-    int no_patch = 0;         // KN_NO_PATCH
-    int no_row_order = 0;     // KN_NO_ROW_ORDER
-    int chain_no_cl = 0;      // KN_CHAIN_NO_CL
-    int chain_no_rpl2 = 0;    // KN_CHAIN_NO_RPL2     whole-net kernel: one output row per lane in the pattern walk
-    int chain_no_early = 0;   // KN_CHAIN_NO_EARLY    whole-net kernel: column pools staged at the start of their own layer
-    int chain_no_share = 0;   // KN_CHAIN_NO_SHARE    whole-net kernel: every lane streams its own copy of its row's values (no shared value blocks)
-    int chain_no_seq = 0;     // KN_CHAIN_NO_SEQ      whole-net kernel: thin layers read their columns from the staged pool instead of walking a re-ordered input sequentially
-    int fill_form = 0;        // KN_FILL_FORM         filled-in order-preserving kernel: 0 = the dispatch rule, 1 / 2 = 32 / 64 channels x one column tile, 3 / 4 = 32 / 64 channels x two tiles
-    int abl = 0;              // KN_ABL               kernel ablation mask (kn_conv.hip, KN_ABLATION code paths)
+#define KN_KNOB_FIELD(name, env, def, diag) int name = def;
+    KN_TUNING_KNOBS(KN_KNOB_FIELD)
+#undef KN_KNOB_FIELD
     std::string describe() const;   // "" when everything is at its default, else " opts{name=value,...}"
 };
 Tuning tuning_from_env();
@@ -270,11 +276,12 @@ struct kn_operator {
     int64_t nnz_expanded = 0;   // nnz of tocsr()
     kn::CsrDev csr;
     kn::ConvTapsDev ct;
-    // host description of a conv-taps operator (export / lazy exact CSR)
+    // host description of a conv-taps operator (export, kn_convtaps_drop_zero_entries)
     std::vector<int32_t> h_ent_out, h_ent_in, h_ent_tap;
-    std::vector<float> h_ent_coef, h_taps, h_lastcol;
+    std::vector<float> h_ent_coef, h_taps, h_last_vals;
+    std::vector<int64_t> h_last_rows;   // with h_last_vals: the explicit entries of the last column (row, value), may hold explicit zeros
+    std::vector<int32_t> h_pix_order;   // [HoWo] host copy of ConvTapsDev::pix_order
     std::mutex lazy_mu;
-    kn_operator* exact = nullptr;  // lazily expanded CSR twin (KN_FLAG_EXACT on a conv-taps operator)
     // dense (Linear) operator: split-K conv-taps sub-operator + ordered reduction
     kn_operator* dense_sub = nullptr;
     int64_t dense_splits = 0;
@@ -310,7 +317,7 @@ int csr_group_mfma16_spmm(const CsrDev& A, const float* x, int64_t ldx, int64_t 
 static constexpr int MF_MIN_MEMBERS = 24;   // a pattern group takes the matrix-pipe kernel when its members fill >= 3/4 of a 32-row block
 // `absmax` (device float or null): when the launch takes a kernel whose epilogue can fold max |Y| into its stores, the slot is raised atomically
 // and *absmax_fused is set; otherwise the caller runs absmax_pass over Y afterwards (kn_spmm_screen)
-int convtaps_spmm(const ConvTapsDev& A, int64_t rows, int64_t cols, const float* x, int64_t ldx, int64_t n_vecs, float* y, int64_t ldy,
+int convtaps_spmm(const ConvTapsDev& A, const float* x, int64_t ldx, int64_t n_vecs, float* y, int64_t ldy,
                   uint32_t flags, hipStream_t s, float* absmax = nullptr, bool* absmax_fused = nullptr);
 int absmax_pass(const float* y, int64_t rows, int64_t ld, int64_t n_vecs, float* absmax, hipStream_t s);
 struct MfTaps;

@@ -701,7 +701,7 @@ class Conv2dTiledMatrix(TiledMatrix):
         if len(eo) > 1 and np.any((eo[1:] == eo[:-1]) & (ei[1:] == ei[:-1])):
             # several taps on one (output, input) pixel pair: ONE stored entry per channel pair, the float32 sum of its terms fl(coef * tap) in entry order.  The selected
             # pixels' pairs become the taps of an equivalent duplicate-free operator (one [Cout, Cin] matrix per pair, summed one term position at a time), which the
-            # block-copy route below expands -- the per-entry COO route (_expand_taps_host_coo) holds 3 x 8 bytes per stored value and sorts them all.
+            # block-copy route below expands -- a per-entry COO route would hold 3 x 8 bytes per stored value and sort them all.
             first = np.ones(len(eo), dtype=bool)
             first[1:] = (eo[1:] != eo[:-1]) | (ei[1:] != ei[:-1])
             seg = np.cumsum(first) - 1
@@ -775,50 +775,6 @@ class Conv2dTiledMatrix(TiledMatrix):
             indices[-1] = self.shape[1] - 1
             data[-1] = t['lastcol'][-1]
         return scipy.sparse.csr_matrix((data, indices, indptr.astype(idt)), shape=(rows_n, self.shape[1]))
-
-    def _expand_taps_host_coo(self, pixels):
-        """General route of _expand_taps_host: duplicate (out, in) pairs become one stored entry, their terms summed in float32 in entry order."""
-        t = self._taps
-        (Cout, Hout, Wout) = self._outshape
-        (Cin, Hin, Win) = self._inshape
-        (HoWo, HiWi) = (Hout * Wout, Hin * Win)
-        npx = len(pixels)
-        pos = -np.ones(HoWo, dtype=np.int64)
-        pos[pixels] = np.arange(npx)
-        sel = np.flatnonzero(pos[t['ent_out']] >= 0)
-        coef = t['ent_coef'][sel] if t['ent_coef'] is not None else np.ones(len(sel), np.float32)
-        (ic, jc) = np.meshgrid(np.arange(Cout), np.arange(Cin), indexing='ij')
-        rows = (pos[t['ent_out'][sel]][:, None, None] + (ic * npx)[None]).ravel()
-        cols = (t['ent_in'][sel].astype(np.int64)[:, None, None] + (jc * HiWi)[None]).ravel()
-        tv = t['taps'][t['ent_tap'][sel]]
-        vals = np.where(coef[:, None, None] == 1.0, tv, coef[:, None, None] * tv).astype(np.float32).ravel()
-        rows_n = Cout * npx
-        if t['lastcol'] is not None:
-            lastv = t['lastcol'][(np.arange(Cout)[:, None] * HoWo + pixels[None, :]).ravel()]
-            if npx == HoWo:
-                lastv = np.concatenate((lastv, t['lastcol'][-1:]))
-                rows_n += 1
-            nz = np.flatnonzero(lastv)
-            rows = np.concatenate((rows, nz))
-            cols = np.concatenate((cols, np.full(len(nz), self.shape[1] - 1, dtype=np.int64)))
-            vals = np.concatenate((vals, lastv[nz]))
-        # duplicates -- several taps on one (output, input) pixel pair -- are ONE stored entry: the float32 sum of their terms in ENTRY order (what the device kernels and
-        # kn_export_csr compute).  scipy's own COO -> CSR conversion sums them behind an UNSTABLE sort, which defines no order for three or more terms: summed here.
-        order = np.lexsort((np.arange(len(rows)), cols, rows))                           # by (row, column), entry order inside a pair
-        (r, c, v) = (rows[order], cols[order], vals[order].astype(np.float32))
-        first = np.ones(len(r), dtype=bool)
-        first[1:] = (r[1:] != r[:-1]) | (c[1:] != c[:-1])
-        seg = np.cumsum(first) - 1                                                      # stored entry of every term
-        rank = np.arange(len(r)) - np.flatnonzero(first)[seg]                           # its position inside the entry
-        acc = v[first].copy()
-        for k in range(1, int(rank.max()) + 1 if len(rank) else 1):                     # one vectorised pass per term position: acc = fl(acc + term_k)
-            sel_k = np.flatnonzero(rank == k)
-            acc[seg[sel_k]] = (acc[seg[sel_k]] + v[sel_k]).astype(np.float32)
-        indptr = np.zeros(rows_n + 1, dtype=np.int64)
-        np.add.at(indptr, r[first] + 1, 1)
-        np.cumsum(indptr, out=indptr)
-        idt = np.int32 if max(len(acc), self.shape[1]) < 2 ** 31 - 1 else np.int64
-        return scipy.sparse.csr_matrix((acc, c[first].astype(idt), indptr.astype(idt)), shape=(rows_n, self.shape[1]))
 
     def rows_csr(self, pixels=None, channels=None):
         """Canonical CSR of the output rows (co, o), o in `pixels` (channel-major: row = co * len(pixels) + index of o), of a

@@ -1535,7 +1535,7 @@ def test_convtaps_exact_fill_kernel_sums_a_pairs_terms_in_entry_order():
     ref = oracle.csr_matvecs(M.shape, M.indptr, M.indices, M.data.astype(np.float32), X)
     y = W.torchdot(torch.as_tensor(X).to(dev()), exact=True).cpu().numpy()
     assert np.array_equal(y, ref), np.abs(y - ref).max()
-    Mh = W.tosparse('csr')                                         # the host expansion (Conv2dTiledMatrix._expand_taps_host_coo): the same stored values
+    Mh = W.tosparse('csr')                                         # the host expansion (Conv2dTiledMatrix._expand_taps_host): the same stored values
     Mh.sort_indices()
     assert np.array_equal(Mh.indptr, M.indptr) and np.array_equal(Mh.indices, M.indices) and np.array_equal(Mh.data, M.data.astype(np.float32))
     # kn_export_csr: the same stored values
