@@ -25,7 +25,7 @@
 extern "C" {
 #endif
 
-#define KN_ABI_VERSION 4
+#define KN_ABI_VERSION 5
 
 enum kn_status {
     KN_OK = 0,
@@ -59,6 +59,13 @@ enum kn_status {
                               ~1 ulp per term away from the f32-MFMA result; never bit-exact; ignored with KN_FLAG_EXACT and by operators /
                               operands that do not qualify (Cin % 16, Cout > 64, n_vecs % 128).  No reference counterpart: the Python host
                               sets it only for layers whose calibration measured the result inside the float-key tolerance. */
+
+#define KN_FLAG_NARROW 8u  /* low-latency form for 1 .. 8 batch columns: for n_vecs <= 8 a conv-taps operator runs the channel-lane order-preserving kernel
+                              (one wavefront = one output pixel x 64 output channels, the batch columns are a lane's running sums).  The result is the
+                              one KN_FLAG_EXACT gives, bit for bit, whether or not KN_FLAG_EXACT is set.  It wins over KN_FLAG_BF16X3.  It is ignored for
+                              n_vecs > 8 and by operators that have no narrow form (every kind but conv-taps).  No reference counterpart as a flag: the
+                              reference's forward IS one image at a time (keynet/system.py:130-133); the other conv-taps kernels give a lane batch
+                              columns and want 128 of them. */
 
 typedef struct kn_operator* kn_handle_t;   /* opaque keyed operator resident in HBM */
 

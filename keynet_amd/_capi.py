@@ -16,7 +16,8 @@ KN_OK = 0
 KN_FLAG_RELU = 1
 KN_FLAG_EXACT = 2
 KN_FLAG_BF16X3 = 4
-KN_ABI_VERSION = 4
+KN_FLAG_NARROW = 8
+KN_ABI_VERSION = 5
 
 # every symbol include/keynet_hip.h declares (tests/test_capi.py checks the header against this list)
 SYMBOLS = ['kn_abi_version', 'kn_last_error', 'kn_device_info', 'kn_csr_create', 'kn_csr_create_f64', 'kn_dtype_bits', 'kn_export_csr_f64', 'kn_spmm_f64', 'kn_tiled_create', 'kn_conv2dtiled_create',

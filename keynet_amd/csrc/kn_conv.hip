@@ -1297,6 +1297,138 @@ __global__ __launch_bounds__(256) void convtaps_exact_kernel(ConvArgs p, int n_c
     }
 }
 
+// ---- order-preserving path for 1 .. 8 batch columns (KN_FLAG_NARROW): lanes are OUTPUT CHANNELS ---------------------------------------------
+// Every kernel above gives a lane batch columns, so a batch of one image fills one lane in 64 (KeyedModel._prepare pads it to 128 zero images
+// instead).  Here one wavefront = one output pixel x 64 consecutive output channels, lane = channel, and the NV (1 | 2 | 4 | 8) running sums of a
+// lane are the batch columns.  tapsT[tap][ci][co] is contiguous in co and cout_pad is a multiple of 64: the 64 values of a step are ONE coalesced
+// 256-byte load (lanes beyond Cout read the zero padding and store nothing); the activations of a step are wave-uniform and arrive through the scalar
+// data cache, like the slot lists.  The arithmetic is convtaps_exact_kernel's, statement for statement: input channel outer, the pixel's slots by
+// ascending input pixel inner, the slots of one (output, input) pixel pair summed (in entry order) into ONE stored value before the multiply, separate
+// multiply and add, then the bias entry where it is stored, then ReLU -- bit-equal to that kernel and to scipy on the sorted expansion.
+// The walk over (input channel, slot) is FLAT: U consecutive steps form a batch whose 3 U record loads, U value-row loads and U activation loads are
+// issued before the first add, across input-channel boundaries (a 3 x 3 window has 9 slots: batches per channel would leave a lone load per channel).
+// Only the adds are a chain.  Steps of the last batch beyond the end re-read the batch's first step and are skipped.  No LDS, no barriers.
+// DUPS (operators with several slots on one pixel pair: the filled-in ones): a stored value is committed to the running sums when the walk reaches the
+// next pixel pair -- the same sequence of multiplies and adds, without looking a slot ahead.  FULL: n_vecs == NV (else the surplus columns re-read the
+// last real column and are not stored).  Work items are (channel block, pixel) with the PIXEL fastest, dealt to the XCDs in contiguous chunks: an XCD
+// then works on one or two channel blocks for many pixels, so its 64-channel share of the taps (VGG-16 conv5_x: 1.2 MB of 9.4 MB) stays in its L2, and the
+// four wavefronts of a workgroup -- four neighbouring pixels of one channel block -- request the same value rows at about the same time.
+#pragma clang fp contract(off)
+template <int NV, bool DUPS, bool FULL, bool COEF>
+__global__ __launch_bounds__(256) void convtaps_narrow_kernel(ConvArgs p, int n_cb, int64_t n_wg) {
+    constexpr int U = NV <= 4 ? 8 : 4;                      // steps in flight per wavefront (U * NV activations + 3 U records in scalar registers; 16 steps at one column spilled scalar registers into vector lanes)
+    const int64_t chunk = (n_wg + 7) >> 3;
+    const int64_t wg = (int64_t)(blockIdx.x & 7) * chunk + (blockIdx.x >> 3);
+    if (wg >= n_wg || (blockIdx.x >> 3) >= chunk) return;
+    const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+    const int lane = threadIdx.x & 63;
+    const uint32_t wi = (uint32_t)wg * 4u + (uint32_t)wave;      // (channel block, pixel in processing order), pixel fastest; below 2^31: checked by the launcher
+    if (wi >= (uint32_t)p.n_pix * (uint32_t)n_cb) return;         // (wave-uniform; no barriers in this kernel)
+    const int cb = (int)(wi / (uint32_t)p.n_pix);
+    const int o = __builtin_amdgcn_readfirstlane(p.pix_order[wi - (uint32_t)cb * (uint32_t)p.n_pix]);
+    const int s_beg = __builtin_amdgcn_readfirstlane(p.pix_ptr[o]);
+    const int n_slots = __builtin_amdgcn_readfirstlane(p.pix_ptr[o + 1]) - s_beg;
+    const int co = cb * 64 + lane;
+    // element offsets in 32 bits (checked by the launcher): value rows inside tapsT, activation rows inside X
+    const uint32_t tap_stride = (uint32_t)p.cin_pad * (uint32_t)p.cout_pad, ci_x = (uint32_t)p.HiWi * (uint32_t)p.ldx, ldx = (uint32_t)p.ldx;
+    int vcol[NV];                                           // column a running sum reads (surplus sums of a width below NV: the last real column)
+#pragma unroll
+    for (int v = 0; v < NV; v++) vcol[v] = (FULL || v < p.n_vecs) ? v : p.n_vecs - 1;
+
+    float acc[NV];
+#pragma unroll
+    for (int v = 0; v < NV; v++) acc[v] = 0.0f;
+    float ar = 0.0f, xcur[NV];                              // DUPS: the stored value being formed, the activations of its column ...
+#pragma unroll
+    for (int v = 0; v < NV; v++) xcur[v] = 0.0f;
+    uint32_t cur = 0xffffffffu;                             // ... and that column (activation row offset; none yet)
+    auto commit = [&]() {
+#pragma unroll
+        for (int v = 0; v < NV; v++) {
+            const float pr = ar * xcur[v];
+            acc[v] = acc[v] + pr;
+        }
+    };
+
+    const int total = p.Cin * n_slots;                      // steps of this pixel (31 bits: checked by the launcher against the longest slot list)
+    const float* const tap0 = p.tapsT + cb * 64;            // wave-uniform base of this channel block's value rows; the lane adds its channel
+    int s = 0;                                              // the walk's cursor: slot of the pixel, input channel as activation / value row offsets
+    uint32_t xci = 0, tci = 0;
+    auto batch = [&](const int q, auto tail) {              // U steps from step q on; tail: the pixel's last batch, which may be short
+        constexpr bool TAIL = decltype(tail)::value;
+        uint32_t xo[U], to[U];
+        float cf[U];
+        bool live[U];
+#pragma unroll
+        for (int k = 0; k < U; k++) {
+            live[k] = !TAIL || q + k < total;
+            const int sk = live[k] ? s : 0;                 // (beyond the end: any valid step -- its loads are issued, its result is not used)
+            const uint32_t xk = live[k] ? xci : 0u, tk = live[k] ? tci : 0u;
+            xo[k] = xk + (uint32_t)p.slot_in[s_beg + sk] * ldx;
+            to[k] = tk + (uint32_t)p.slot_tap[s_beg + sk] * tap_stride;
+            cf[k] = COEF ? p.slot_coef[s_beg + sk] : 1.0f;
+            if (++s == n_slots) {
+                s = 0;
+                xci += ci_x;
+                tci += (uint32_t)p.cout_pad;
+            }
+        }
+        float a[U], x[U][NV];
+#pragma unroll
+        for (int k = 0; k < U; k++) a[k] = (tap0 + to[k])[lane];
+#pragma unroll
+        for (int k = 0; k < U; k++)
+#pragma unroll
+            for (int v = 0; v < NV; v++) x[k][v] = (p.X + xo[k])[vcol[v]];
+#pragma unroll
+        for (int k = 0; k < U; k++) {
+            if (!live[k]) break;
+            const float t = COEF ? (cf[k] == 1.0f ? a[k] : cf[k] * a[k]) : a[k];      // the term as the reference stores it
+            if constexpr (DUPS) {
+                if (xo[k] != cur) {
+                    if (cur != 0xffffffffu) commit();
+                    cur = xo[k];
+                    ar = t;
+#pragma unroll
+                    for (int v = 0; v < NV; v++) xcur[v] = x[k][v];
+                } else {
+                    ar = ar + t;
+                }
+            } else {
+#pragma unroll
+                for (int v = 0; v < NV; v++) {
+                    const float pr = t * x[k][v];
+                    acc[v] = acc[v] + pr;
+                }
+            }
+        }
+    };
+    int q = 0;
+    for (; q + U <= total; q += U) batch(q, std::false_type{});
+    if (q < total) batch(q, std::true_type{});
+    if constexpr (DUPS) {
+        if (cur != 0xffffffffu) commit();
+    }
+    if (co >= p.Cout) return;
+    const int64_t row = (int64_t)co * p.HoWo + o;
+    if (p.lastcol) {
+        const float lc = p.lastcol[row];
+        if (lc != 0.0f) {                                   // the bias entry exists in the reference's row only when it is stored
+#pragma unroll
+            for (int v = 0; v < NV; v++) {
+                const float bp = lc * p.X[p.last_in_row * p.ldx + vcol[v]];
+                acc[v] = acc[v] + bp;
+            }
+        }
+    }
+#pragma unroll
+    for (int v = 0; v < NV; v++) {
+        float t = acc[v];
+        if (p.relu) t = (t < 0.0f) ? 0.0f : t;
+        if (FULL || v < p.n_vecs) p.Y[row * p.ldy + v] = t;
+    }
+}
+
 // ---- KN_FLAG_EXACT on FILLED-IN operators (round 5) ------------------------------------------------------------------------------------
 // A float key whose inverse is dense inside its blocks (the reference's doubly-stochastic keys, test/test_keynet.py:116-129) fills the keyed conv in:
 // 500 - 5 400 slots per output pixel instead of 9, and one (output pixel, input pixel) pair is hit by several taps -- ONE stored non-zero of the
@@ -2278,6 +2410,51 @@ static ExactPipeKernel exact_pipe_kernel(bool coef) {
     return coef ? convtaps_exact_pipe_kernel<RBX, true, XD, VEC> : convtaps_exact_pipe_kernel<RBX, false, XD, VEC>;
 }
 
+typedef void (*NarrowKernel)(ConvArgs, int, int64_t);
+template <int NV, bool FULL>
+static NarrowKernel narrow_kernel_of(bool dups, bool coef) {
+    return dups ? (coef ? convtaps_narrow_kernel<NV, true, FULL, true> : convtaps_narrow_kernel<NV, true, FULL, false>)
+                : (coef ? convtaps_narrow_kernel<NV, false, FULL, true> : convtaps_narrow_kernel<NV, false, FULL, false>);
+}
+
+static NarrowKernel narrow_kernel(int nv, bool full, bool dups, bool coef) {
+    switch (nv) {                                        // (a width of 1 or 2 columns always fills its form)
+        case 1: return narrow_kernel_of<1, true>(dups, coef);
+        case 2: return narrow_kernel_of<2, true>(dups, coef);
+        case 4: return full ? narrow_kernel_of<4, true>(dups, coef) : narrow_kernel_of<4, false>(dups, coef);
+        default: return full ? narrow_kernel_of<8, true>(dups, coef) : narrow_kernel_of<8, false>(dups, coef);
+    }
+}
+
+// behind the main kernel of both order-preserving launchers: the homogeneous row, and the zero guard of kn_convtaps_drop_zero_entries handles
+static int exact_tail(const ConvTapsDev& A, const ConvArgs& a, hipStream_t s) {
+    launch_lastrow(A, a, s);
+    if (A.n_zero > 0) {                                  // kn_convtaps_drop_zero_entries: behind the main kernel, on its stream
+        const int64_t gz = A.n_zero * a.HoWo * ((a.n_vecs + 255) / 256);
+        KN_REQUIRE(gz < ((int64_t)1 << 31), KN_ERR_UNSUPPORTED, "too many zero-valued tap entries for the guard launch");
+        KN_LAUNCH("convtaps_zero_guard_kernel<" + std::to_string(A.n_zero) + " zero tap entries>", convtaps_zero_guard_kernel, dim3((unsigned)gz), dim3(256), 0, s, a, A.zero_ent, A.n_zero);
+    }
+    return KN_OK;
+}
+
+// KN_FLAG_NARROW on at most NARROW_MAX_VECS columns: one wavefront per (output pixel, 64 output channels); the kernel's element offsets into tapsT and X are 32-bit
+static int spmm_narrow(const ConvTapsDev& A, ConvArgs& a, hipStream_t s) {
+    const int64_t n_vecs = a.n_vecs;
+    const int nv = n_vecs <= 1 ? 1 : (n_vecs <= 2 ? 2 : (n_vecs <= 4 ? 4 : 8));      // running sums (batch columns) per lane
+    const int n_cb = (int)((A.Cout + 63) / 64);
+    const int64_t n_wg = ((int64_t)a.n_pix * n_cb + 3) / 4;
+    KN_REQUIRE(A.cout_pad % 64 == 0, KN_ERR_UNSUPPORTED, "KN_FLAG_NARROW: the value rows are not padded to whole 64-channel blocks");
+    KN_REQUIRE(A.ntaps * A.cin_pad * A.cout_pad < ((int64_t)1 << 31) && (a.last_in_row + 1) * a.ldx + NARROW_MAX_VECS < ((int64_t)1 << 31),
+               KN_ERR_UNSUPPORTED, "KN_FLAG_NARROW: the taps or the activation block exceed 32-bit element offsets");
+    KN_REQUIRE(n_wg + 8 < ((int64_t)1 << 29) && A.Cin * (int64_t)A.max_slots < ((int64_t)1 << 31), KN_ERR_UNSUPPORTED,
+               "grid or slot walk too large for the channel-lane order-preserving kernel");
+    const bool coef = !A.unit_coef, full = n_vecs == nv;
+    KN_LAUNCH("convtaps_narrow_kernel<" + std::to_string(nv) + (full ? "" : ",masked to " + std::to_string(n_vecs)) + (A.has_dups ? ",stored values summed" : "") + (coef ? ",coef" : "") +
+                  "> (lane = output channel)",
+              narrow_kernel(nv, full, A.has_dups, coef), dim3((unsigned)(((n_wg + 7) / 8) * 8)), dim3(256), 0, s, a, n_cb, n_wg);
+    return exact_tail(A, a, s);
+}
+
 static int spmm_exact(const ConvTapsDev& A, ConvArgs& a, hipStream_t s) {
     const ExactChoice c = exact_choice(A, a);
     const int64_t n_vecs = a.n_vecs;
@@ -2323,13 +2500,7 @@ static int spmm_exact(const ConvTapsDev& A, ConvArgs& a, hipStream_t s) {
     } else {
         KN_LAUNCH(c.vec == 4 ? "convtaps_exact_kernel<vec=4>" : "convtaps_exact_kernel<vec=1>", (c.vec == 4 ? convtaps_exact_kernel<4> : convtaps_exact_kernel<1>), grid, dim3(256), 0, s, a, n_cob, n_rb);
     }
-    launch_lastrow(A, a, s);
-    if (A.n_zero > 0) {                                  // kn_convtaps_drop_zero_entries: behind the main kernel, on its stream
-        const int64_t gz = A.n_zero * a.HoWo * ((n_vecs + 255) / 256);
-        KN_REQUIRE(gz < ((int64_t)1 << 31), KN_ERR_UNSUPPORTED, "too many zero-valued tap entries for the guard launch");
-        KN_LAUNCH("convtaps_zero_guard_kernel<" + std::to_string(A.n_zero) + " zero tap entries>", convtaps_zero_guard_kernel, dim3((unsigned)gz), dim3(256), 0, s, a, A.zero_ent, A.n_zero);
-    }
-    return KN_OK;
+    return exact_tail(A, a, s);
 }
 
 typedef void (*ConvKernel)(ConvArgs);
@@ -2403,7 +2574,10 @@ int convtaps_spmm(const ConvTapsDev& A, const float* x, int64_t ldx, int64_t n_v
     if (absmax_fused) *absmax_fused = false;
     ConvArgs a = conv_args(A, x, ldx, n_vecs, y, ldy, flags);
     int rc;
-    if (flags & KN_FLAG_EXACT) {
+    // KN_FLAG_NARROW on a batch of at most 8 columns: the channel-lane order-preserving kernel, whatever the other contract flags say
+    if (narrow_call(flags, n_vecs)) {
+        rc = spmm_narrow(A, a, s);
+    } else if (flags & KN_FLAG_EXACT) {
         rc = spmm_exact(A, a, s);
     } else {
         const bool bf16x3 = (flags & KN_FLAG_BF16X3) && convtaps_bf16x3_ok(A, x, ldx, n_vecs, y, ldy);

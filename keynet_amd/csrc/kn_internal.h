@@ -317,6 +317,9 @@ int csr_group_mfma16_spmm(const CsrDev& A, const float* x, int64_t ldx, int64_t 
 static constexpr int MF_MIN_MEMBERS = 24;   // a pattern group takes the matrix-pipe kernel when its members fill >= 3/4 of a 32-row block
 // `absmax` (device float or null): when the launch takes a kernel whose epilogue can fold max |Y| into its stores, the slot is raised atomically
 // and *absmax_fused is set; otherwise the caller runs absmax_pass over Y afterwards (kn_spmm_screen)
+// KN_FLAG_NARROW: the widest batch of the channel-lane conv-taps kernel, and whether a call takes it (the one place that reads the flag)
+static constexpr int64_t NARROW_MAX_VECS = 8;
+static inline bool narrow_call(uint32_t flags, int64_t n_vecs) { return (flags & KN_FLAG_NARROW) && n_vecs <= NARROW_MAX_VECS; }
 int convtaps_spmm(const ConvTapsDev& A, const float* x, int64_t ldx, int64_t n_vecs, float* y, int64_t ldy,
                   uint32_t flags, hipStream_t s, float* absmax = nullptr, bool* absmax_fused = nullptr);
 int absmax_pass(const float* y, int64_t rows, int64_t ld, int64_t n_vecs, float* absmax, hipStream_t s);

@@ -209,16 +209,22 @@ class KeyedLayer(nn.Module):
     def iskeyedrelu(self):
         return 'ReLU' in self._layertype
 
-    def forward(self, x_affine, fuse_relu=False, absmax=None):
+    def forward(self, x_affine, fuse_relu=False, absmax=None, narrow=False):
         """[N, Din+1] -> [N, Dout+1] (keynet/layer.py:88-93).  The result is a transposed view of the feature-major
         [Dout+1, N] block the kernel wrote, so the next layer's x.t() is free.  `fuse_relu` folds the unkeyed nn.ReLU
         that follows this layer in the key-net (keynet/system.py:92) into the kernel epilogue.  `absmax`: a one-element device
         f32 tensor raised to max |y| of this call (kn_spmm_screen; KeyedModel.forward_linear re-screens the next layer's contract with it).
         A layer whose contract is still 'auto' decides it here, on this batch (blocking host reads, an extra order-preserving launch:
-        not capturable into a HIP graph -- KeyedModel.capture runs an eager forward first)."""
+        not capturable into a HIP graph -- KeyedModel.capture runs an eager forward first).
+        `narrow` (at most KeyedModel.NARROW_MAX images): a conv-taps layer runs the channel-lane order-preserving kernel (KN_FLAG_NARROW) whatever its
+        contract is -- the reference's own arithmetic, which satisfies every contract: nothing is calibrated, screened or decided; other layers run as usual."""
         if verbose():
             print('[keynet_amd.layer]: forward %s' % str(self))
         exact = getattr(self, '_exact', True)
+        if narrow and self.W.narrow_capable():
+            return self.W.torchdot(x_affine.t(), relu=(fuse_relu or self.iskeyedrelu()), exact=exact, absmax=absmax, narrow=True).t()
+        if narrow and exact == 'auto':
+            exact = True                     # an undecided layer without a narrow form: the reference's order for this call, nothing decided or recorded
         if exact == 'auto':
             if x_affine.is_cuda and torch.cuda.is_current_stream_capturing():
                 raise _capi.KeynetHipError('keynet_amd: %s has not decided its arithmetic contract yet (exact=\'auto\' calibrates on the first batch, with host reads): '
@@ -230,14 +236,20 @@ class KeyedLayer(nn.Module):
         return self.W.torchdot(x_affine.t(), relu=(fuse_relu or self.iskeyedrelu()), exact=exact, absmax=absmax).t()
 
     @staticmethod
-    def kernel(W, contract, relu, device=None):
+    def kernel(W, contract, relu, device=None, narrow=False):
         """The one place that turns a decided contract into an operator handle and flags: (get_op, flags) of the kn_spmm launch that applies operator `W`
         under `contract`, get_op(device) -> the handle resident there.  None when that is not one launch: 'auto' (still to calibrate), 'split' on an operator that has a split form (Conv2dTiledMatrix._torchdot_split).
         The rules: 'split' forced on an operator without a split form, and 'bf16x3' on a non-conv operator, are the f32 matrix cores (False); a conv operator
         runs the order-preserving kernel under True, else the matrix cores (bf16x3: the emulation where operator and batch qualify); a plain SparseMatrix
         off the exact contract runs as a dense GEMM when it has such a handle (a large keyed nn.Linear); everything else -- tiled / factored CSR
-        containers, float64 operators, small or sparse matrices -- has the reference's order only."""
+        containers, float64 operators, small or sparse matrices -- has the reference's order only.
+        `narrow` (a batch of at most KeyedModel.NARROW_MAX columns): an operator that owns a conv-taps handle (W.narrow_capable()) is ONE launch of the
+        channel-lane order-preserving kernel under EVERY contract, the undecided and the two-step ones included -- KN_FLAG_NARROW next to the flags the
+        contract sets anyway (the library ignores them below 9 columns); every other operator is what it is without the keyword."""
         conv = isinstance(W, ksp.Conv2dTiledMatrix)
+        if narrow and W.narrow_capable():
+            exact = contract is True or not conv
+            return (W._device_op, (_capi.KN_FLAG_RELU if relu else 0) | (_capi.KN_FLAG_EXACT if exact else 0) | (_capi.KN_FLAG_BF16X3 if contract == 'bf16x3' else 0) | _capi.KN_FLAG_NARROW)
         if contract == 'auto' or (contract == 'split' and conv and W._taps is not None):
             return None
         if contract == 'split' or (contract == 'bf16x3' and not conv):
@@ -247,12 +259,12 @@ class KeyedLayer(nn.Module):
             (get_op, exact) = (W._dense_device_op, False)
         return (get_op, (_capi.KN_FLAG_RELU if relu else 0) | (_capi.KN_FLAG_EXACT if exact else 0) | (_capi.KN_FLAG_BF16X3 if contract == 'bf16x3' else 0))
 
-    def launch(self, device, relu=False):
+    def launch(self, device, relu=False, narrow=False):
         """This layer under its contract in force as one launch on `device` (`relu`: the unkeyed nn.ReLU behind it is fused in), or None when it is not one
         kn_spmm launch: see kernel(); a float64 operator (its own kernel and a float64 result: kn_spmm_f64).  What the key-net's planners read
-        (KeyedModel._chain_op / _overlap_plan); forward() -> W.torchdot() runs the same rule."""
+        (KeyedModel._chain_op / _overlap_plan); forward() -> W.torchdot() runs the same rule.  `narrow`: see kernel()."""
         W = self.W
-        kernel = None if W.is_float64() else self.kernel(W, getattr(self, '_exact', True), relu or self.iskeyedrelu(), device)
+        kernel = None if W.is_float64() else self.kernel(W, getattr(self, '_exact', True), relu or self.iskeyedrelu(), device, narrow=narrow)
         if kernel is None:
             return None
         return Launch(kernel[0](device), kernel[1], int(W.shape[0]), int(W.shape[1]), isinstance(W, ksp.Conv2dTiledMatrix), 'Linear' in self._layertype,

@@ -80,16 +80,18 @@ def _device_block(x):
     return xd if xd.is_contiguous() else xd.contiguous()
 
 
-def _run_torchdot(W, x, relu=False, exact=True, absmax=None):
+def _run_torchdot(W, x, relu=False, exact=True, absmax=None, narrow=False):
     """Y = W.X on the GPU under the contract `exact`, on the handle and flags of KeyedLayer.kernel.  x: [cols, N], torch tensor (any device / strides) or ndarray.
     Returns [rows, N] on x's device: float32, or for a float64 operator the float64 block scipy returns for it (kn_spmm_f64; the activations are
-    float32 either way)."""
+    float32 either way).  `narrow`: at most NARROW_MAX columns on the channel-lane kernel where W owns a conv-taps handle (KeyedLayer.kernel)."""
     from .layer import KeyedLayer            # (layer.py imports this module)
     x = torch.as_tensor(x)
     assert W.shape[1] == x.shape[0], 'Non-conformal shape for W=%s, x=%s' % (str(W.shape), str(tuple(x.shape)))
     xd = _device_block(x)
     n = xd.shape[1]
-    kernel = KeyedLayer.kernel(W, exact, relu, xd.device)
+    if narrow and n > NARROW_MAX:
+        raise ValueError('narrow=True takes at most %d batch columns, got %d' % (NARROW_MAX, n))
+    kernel = KeyedLayer.kernel(W, exact, relu, xd.device, narrow=narrow)
     if kernel is None:
         y = W._torchdot_split(xd, relu=relu, absmax=absmax)
     else:
@@ -104,6 +106,9 @@ def _run_torchdot(W, x, relu=False, exact=True, absmax=None):
             else:
                 get_op(xd.device).spmm(xd.data_ptr(), n, n, y.data_ptr(), n, flags, _stream_ptr(), absmax_ptr=None if absmax is None else absmax.data_ptr())
     return y if x.is_cuda else y.to(x.device)
+
+
+NARROW_MAX = 8        # widest batch of the channel-lane conv-taps kernel (KN_FLAG_NARROW; KeyedModel.NARROW_MAX)
 
 
 # ------------------------------------------------------------------------------------------------------------------
@@ -146,6 +151,10 @@ class SparseMatrix(object):
             (ip, ix, dt) = _stored_order_csr(M)
             return _capi.Operator.csr(self.shape, ip, ix, dt)
         return _on_device(self, '_op', make, device)
+
+    def narrow_capable(self):
+        """Does this container's device operator have the channel-lane form for 1 .. 8 batch columns (a conv-taps handle: KN_FLAG_NARROW)?"""
+        return False
 
     def is_float64(self):
         """Does scipy compute this operator's product with float32 activations in float64 (a float64 -- or integer -- scipy matrix)?
@@ -265,6 +274,14 @@ class FactoredSparseMatrix(SparseMatrix):
 
     def _dense_device_op(self, device=None):
         return None
+
+    def narrow_capable(self):
+        return True
+
+    def torchdot(self, x_torch, relu=False, exact=True, absmax=None, narrow=False):
+        """SparseMatrix.torchdot; `narrow`: at most NARROW_MAX columns on the channel-lane kernel of the factored device form (KN_FLAG_NARROW) -- the
+        same bits as without it (the order-preserving product, which IS scipy's on the stored CSR)."""
+        return _run_torchdot(self, x_torch, relu=relu, exact=exact, absmax=absmax, narrow=narrow)
 
     @staticmethod
     def proven(M, factored, max_zero_fraction=0.01):
@@ -573,14 +590,18 @@ class Conv2dTiledMatrix(TiledMatrix):
             return _capi.Operator.conv2dtiled(self.shape, self._inshape, self._outshape, bl, tk, ib, ch, bs)
         return _on_device(self, '_op', make, device)
 
-    def torchdot(self, x, relu=False, exact=False, absmax=None):
+    def narrow_capable(self):
+        return True
+
+    def torchdot(self, x, relu=False, exact=False, absmax=None, narrow=False):
         """[cols, N] -> [rows, N].  exact=False: f32 MFMA path (f32-input matrix instructions, exact f32 products); exact=True: the
         reference's accumulation order and rounding (order-preserving kernel on the factored operator); exact='split': a filled-in factored
         operator applied as spatial mixing per tap, then channel mixing (see _split_ops: another association of the sum, tolerance contract only); exact='bf16x3': f32 products
         emulated on the bf16 matrix pipe (three-way exact split, six of nine cross products, f32 accumulate: KN_FLAG_BF16X3) where the
-        operator and batch qualify, else the f32 MFMA path."""
-        assert not isinstance(exact, str) or exact in ('bf16x3', 'split'), "exact must be True, False, 'bf16x3' or 'split'"
-        return _run_torchdot(self, x, relu=relu, exact=exact, absmax=absmax)
+        operator and batch qualify, else the f32 MFMA path.  narrow=True (N <= NARROW_MAX, ValueError beyond): the channel-lane order-preserving kernel
+        (KN_FLAG_NARROW) whatever `exact` says -- always the reference's own arithmetic, the bits of exact=True."""
+        assert not isinstance(exact, str) or exact in ('bf16x3', 'split') or (narrow and exact == 'auto'), "exact must be True, False, 'bf16x3' or 'split'"
+        return _run_torchdot(self, x, relu=relu, exact=exact, absmax=absmax, narrow=narrow)
 
     # ---- the SPLIT application of a filled-in operator (tolerance contract only) -----------------------------------------------------
     # A factored keyed conv is  sum_t F_t (x) K_t  with F_t the Cout x Cin matrix of tap t and K_t = a_out S_t a_in^-1 the HoWo x HiWi spatial

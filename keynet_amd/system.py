@@ -175,7 +175,9 @@ class KeyedModel(object):
         d.pop('_overlap_plans', None)
         d.pop('_chain_ops', None)
 
-    def forward_linear(self, img_cipher, overlap=None):
+    NARROW_MAX = ksp.NARROW_MAX    # forward_linear(narrow=True) takes at most this many images (the channel-lane conv-taps kernel keeps one running sum per image and lane)
+
+    def forward_linear(self, img_cipher, overlap=None, narrow=False):
         """[N, D0+1] -> [N, classes+1]: the nn.Sequential of keynet/system.py:132 with the unkeyed ReLUs fused into the
         producing layer's kernel epilogue.  Stream-ordered on torch's current HIP stream.  Host synchronisation: none for key-nets whose
         layers all run under a DECLARED contract (exact=True: the permutation key-nets; exact=False: forced); a key-net with layers on the
@@ -194,9 +196,39 @@ class KeyedModel(object):
         None = automatically for device-resident feature-major batches that are a multiple of 256 images, False = never.
         Memory: the overlapped forward keeps two ping-pong workspaces of max_rows x N floats per (device, N) plan (VGG-16 at N = 256:
         2 x 3.3 GB) plus two side streams; at most OVERLAP_PLANS_KEPT plans are cached (least recently used dropped),
-        release_workspace() drops them all."""
+        release_workspace() drops them all.
+        `narrow=True`: the low-latency forward of 1 .. NARROW_MAX images (ValueError beyond).  Nothing is padded: the batch is laid out feature-major once
+        and every conv-taps layer runs the channel-lane order-preserving kernel (KN_FLAG_NARROW), WHATEVER its contract is.  A narrow forward is therefore
+        always the reference's own arithmetic on the conv layers -- stored order, separate multiply and add, the bits exact=True gives -- which satisfies
+        every contract: it calibrates nothing, screens nothing, changes no layer's decision or record and leaves the cached launch lists alone.  The other
+        layers run as they do without the keyword, at the unpadded width (a layer still undecided: in the reference's order, for this call; a non-conv layer a calibration
+        put on the matrix cores stays there and is NOT re-screened by this forward); a key-net that
+        qualifies for the whole-net kernel still takes it; the overlapped form is never taken."""
+        if narrow:
+            return self._forward_narrow(img_cipher)
         (x, windows) = self._prepare(img_cipher)
         y = self._forward_passes(x, windows, overlap)[0][:img_cipher.shape[0]]
+        return y if img_cipher.is_cuda else y.to(img_cipher.device)
+
+    def _forward_narrow(self, img_cipher):
+        """forward_linear(narrow=True): see there.  Stream-ordered on torch's current HIP stream, no host read; capturable once the operators are resident."""
+        n = img_cipher.shape[0]
+        if n > self.NARROW_MAX:
+            raise ValueError('narrow=True takes at most %d images, got %d' % (self.NARROW_MAX, n))
+        x = img_cipher
+        if not x.is_cuda and x.dim() == 2 and torch.cuda.is_available():
+            x = x.detach().float().cuda()
+        if x.is_cuda and x.dim() == 2 and x.dtype == torch.float32 and not x.t().is_contiguous():
+            x = x.detach().t().contiguous().t()                  # feature-major once: every layer hands the next one such a block
+        y = None
+        if x.is_cuda and x.dim() == 2 and not any(c.W.narrow_capable() for c in self._keyed()):
+            chain = self._chain_op(x.device)                     # (a key-net without conv-taps operators: the whole-net kernel where it qualifies, as without the keyword)
+            if chain is not None:
+                y = self._forward_chain(x, chain)
+        if y is None:
+            y = x
+            for (k, c, relu) in self._steps():
+                y = _relu_block(y) if k is None else c.forward(y, fuse_relu=relu, narrow=True)
         return y if img_cipher.is_cuda else y.to(img_cipher.device)
 
     def _prepare(self, x):
@@ -549,16 +581,20 @@ class KeyedModel(object):
             self._drop_plans()
         return changed
 
-    def capture(self, img_cipher):
+    def capture(self, img_cipher, narrow=False):
         """Capture forward_linear for this input shape into a HIP graph (torch.cuda.CUDAGraph on ROCm) and return a callable
         `replay(x) -> [N, classes+1]`.  Small key-nets are launch-bound (LeNet at N=1024: 7 kernels in 0.25 ms); one graph
         launch replaces them.  The graph runs the passes of the eager forward on the block _prepare made; replay(x) copies x into its first N images.
         The operators must already be resident and every 'auto' layer decided (one eager forward is run first); the returned tensor is the first N
         rows of the graph's static output buffer (clone it to keep a result across replays).  A key-net with calibrated layers keeps its per-forward
         screen: the graph gathers max |x| per layer like the eager forward, replay() reads it back after the launch and, when a layer's input has
-        outgrown its calibration, re-runs the batch eagerly (re-calibrating) and captures a new graph."""
+        outgrown its calibration, re-runs the batch eagerly (re-calibrating) and captures a new graph.
+        `narrow=True` (at most NARROW_MAX images): the graph of forward_linear(narrow=True) -- a straight line of launches on one stream, no parallel
+        branches; nothing is screened (the conv layers run the reference's own arithmetic), so replay() reads nothing back."""
         assert img_cipher.is_cuda, 'capture() needs a device tensor'
         n = img_cipher.shape[0]
+        if narrow:
+            return self._capture_narrow(img_cipher)
         (static_in, windows) = self._prepare(img_cipher.detach().t().clone(memory_format=torch.contiguous_format).t())     # the graph's own input block
         keyed = self._keyed()
         state = {}
@@ -591,11 +627,35 @@ class KeyedModel(object):
         replay.graph = state['graph']
         return replay
 
-    def forward(self, img_cipher, outkey=None):
+    def _capture_narrow(self, img_cipher):
+        """capture(narrow=True): one eager narrow forward (operators resident), a warm-up on the capture stream (per-stream state of the operators), then the capture."""
+        if img_cipher.shape[0] > self.NARROW_MAX:
+            raise ValueError('narrow=True takes at most %d images, got %d' % (self.NARROW_MAX, img_cipher.shape[0]))
+        static_in = img_cipher.detach().float().t().clone(memory_format=torch.contiguous_format).t()      # the graph's own feature-major input block
+        self._forward_narrow(static_in)
+        torch.cuda.synchronize()
+        side = torch.cuda.Stream()
+        side.wait_stream(torch.cuda.current_stream())
+        with torch.cuda.stream(side):
+            self._forward_narrow(static_in)
+        torch.cuda.current_stream().wait_stream(side)
+        graph = torch.cuda.CUDAGraph()
+        with torch.cuda.graph(graph, stream=side):
+            out = self._forward_narrow(static_in)
+
+        def replay(x):
+            static_in.copy_(x)
+            graph.replay()
+            return out
+        replay.graph = graph
+        return replay
+
+    def forward(self, img_cipher, outkey=None, narrow=False):
         """Encrypted image(s) [N, D0+1] -> logits.  N == 1 returns the reference's shape `outshape` = (C,1,1)
-        (keynet/system.py:130-133); N > 1 (an extension: the reference cannot) returns (N, C, 1, 1)."""
+        (keynet/system.py:130-133); N > 1 (an extension: the reference cannot) returns (N, C, 1, 1).  `narrow`: forward_linear(narrow=True), the
+        low-latency form of this very call for 1 .. NARROW_MAX images."""
         outkey = outkey if outkey is not None else self.embeddingkey()
-        y = self.forward_linear(img_cipher)
+        y = self.forward_linear(img_cipher, narrow=narrow)
         if outkey is not None:
             y = self.decrypt(y, outkey)
         n = y.shape[0]
