@@ -178,7 +178,19 @@ int kn_export_csr_f64(kn_handle_t h, int32_t* indptr, int32_t* indices, double* 
 
 /* Replaces SparseMatrix.torchdot / TiledMatrix.torchdot (keynet/sparse.py:488-492, 603-612):
  *   Y[rows, n_vecs] = W . X[cols, n_vecs]      (+ ReLU when KN_FLAG_RELU)
- * x_dev/y_dev: device f32, feature-major, leading dimensions ldx/ldy >= n_vecs (floats).  x and y must not alias. */
+ * x_dev/y_dev: device f32, feature-major, leading dimensions ldx/ldy >= n_vecs (floats).  x and y must not alias.
+ *
+ * What a caller may pass.  ANY ldx, ldy >= n_vecs whose blocks (cols * ldx and rows * ldy floats) fit in device memory are accepted, blocks of more than 2^31 elements
+ * included: every kernel forms row * ldy, and the general kernels col * ldx, in 64 bits.  The fast forms keep narrower offsets into X and are chosen only while these hold
+ * (HiWi = Hin * Win, D = Cin * HiWi of a conv-taps operator); beyond a threshold the next slower form runs, with the same result under the same flags:
+ *   CSR pattern groups, software-pipelined kernel       cols * ldx < 2^31                                  else the plain grouped kernel
+ *   conv-taps, matrix cores (no KN_FLAG_EXACT)          wave-uniform loaders: 4 * (T * HiWi * ldx + NB) < 2^31, NB = 128 | 256 batch columns per tile, T = 1024 / NB;
+ *                                                       straight-line loaders: 16 * HiWi * ldx < 2^31 (4 * for Cin < 16); else the generic loader
+ *   conv-taps, KN_FLAG_EXACT, pipelined kernel          (D + 1) * ldx < 2^31                               else the plain order-preserving kernel
+ *   conv-taps, KN_FLAG_EXACT, filled-in operators       4 * ldx < 2^24, 4 * HiWi * ldx < 2^32, HiWi < 2^24  else the plain order-preserving kernel
+ * The small-K matrix-core kernels of first-layer operators (slots * Cin + bias <= 28 contraction rows) form row * ldx in 64 bits and take any ldx.
+ * KN_FLAG_NARROW (n_vecs <= 8 on a conv-taps operator) does NOT fall back: it returns KN_ERR_UNSUPPORTED, Y untouched, unless (D + 1) * ldx + 8 < 2^31.
+ * kn_spmm_plan names the kernel a call takes; tests/test_large_offsets_gpu.py runs each of these on both sides of its threshold. */
 int kn_spmm(kn_handle_t h, const float* x_dev, int64_t ldx, int64_t n_vecs,
             float* y_dev, int64_t ldy, uint32_t flags, void* stream);
 

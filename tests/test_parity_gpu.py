@@ -1902,7 +1902,8 @@ def test_odd_batches_of_a_tiled_keynet_are_padded_to_whole_tiles(golden, name):
 def test_a_batch_too_large_for_32_bit_offsets_runs_in_passes(golden):
     """Round 6: a layer's fast loaders take an activation block of fewer than 2^31 elements; KeyedModel.forward_linear runs a larger batch as passes of whole 256-image tiles
     (VGG-16 in the stored order at 1 024 images: conv1_2 113.7 ms -> 2 x 31 ms).  Here the limit is lowered so that the mini-net's 600 images take three passes: same logits,
-    bit for bit, as the one-pass forward; feature-major and row-major batches."""
+    bit for bit, as the one-pass forward; feature-major and row-major batches.
+    The real boundary -- blocks at and beyond 2^31 elements through the C ABI, both sides of every launcher guard -- is exercised in tests/test_large_offsets_gpu.py."""
     z = golden('mini_tiled_permutation.npz')
     knet = kio.keynet_from_arrays(z)
     rng = np.random.RandomState(1)
