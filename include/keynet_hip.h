@@ -67,6 +67,15 @@ enum kn_status {
                               reference's forward IS one image at a time (keynet/system.py:130-133); the other conv-taps kernels give a lane batch
                               columns and want 128 of them. */
 
+#define KN_FLAG_NARROW_MFMA 16u  /* KN_FLAG_NARROW for callers that accept the float-key tolerance: for n_vecs <= 8, without KN_FLAG_EXACT, an ELIGIBLE conv-taps operator runs
+                              convtaps_narrow_mfma_kernel -- an implicit GEMM on v_mfma_f32_32x32x2_f32 whose N dimension is output pixels x batch columns (32 / NV pixels x
+                              NV = 1 | 2 | 4 | 8 columns per tile), K = tap x input channel split over the four wavefronts of a workgroup and summed in a fixed order:
+                              deterministic (the same bits on every call), not the reference's order of additions.  Eligible: no (output pixel, tap) pair holds more than 2
+                              slots, no output pixel more than 64, and the per-pair records (16 bytes per pair, built at first use) stay below 2^22 -- identity / permutation / block-diagonal keys; the
+                              filled-in operators of dense float keys are not.  In EVERY other case the flag means KN_FLAG_NARROW, bit for bit: with KN_FLAG_EXACT, on an
+                              ineligible operator, on any other operator kind, at n_vecs > 8 (ignored).  Same size rule and refusal as KN_FLAG_NARROW.  kn_spmm_plan names
+                              the kernel, its tile and NV.  No reference counterpart. */
+
 typedef struct kn_operator* kn_handle_t;   /* opaque keyed operator resident in HBM */
 
 int         kn_abi_version(void);
@@ -189,7 +198,7 @@ int kn_export_csr_f64(kn_handle_t h, int32_t* indptr, int32_t* indices, double* 
  *   conv-taps, KN_FLAG_EXACT, pipelined kernel          (D + 1) * ldx < 2^31                               else the plain order-preserving kernel
  *   conv-taps, KN_FLAG_EXACT, filled-in operators       4 * ldx < 2^24, 4 * HiWi * ldx < 2^32, HiWi < 2^24  else the plain order-preserving kernel
  * The small-K matrix-core kernels of first-layer operators (slots * Cin + bias <= 28 contraction rows) form row * ldx in 64 bits and take any ldx.
- * KN_FLAG_NARROW (n_vecs <= 8 on a conv-taps operator) does NOT fall back: it returns KN_ERR_UNSUPPORTED, Y untouched, unless (D + 1) * ldx + 8 < 2^31.
+ * KN_FLAG_NARROW / KN_FLAG_NARROW_MFMA (n_vecs <= 8 on a conv-taps operator) do NOT fall back: they return KN_ERR_UNSUPPORTED, Y untouched, unless (D + 1) * ldx + 8 < 2^31.
  * kn_spmm_plan names the kernel a call takes; tests/test_large_offsets_gpu.py runs each of these on both sides of its threshold. */
 int kn_spmm(kn_handle_t h, const float* x_dev, int64_t ldx, int64_t n_vecs,
             float* y_dev, int64_t ldy, uint32_t flags, void* stream);

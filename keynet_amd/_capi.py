@@ -17,6 +17,7 @@ KN_FLAG_RELU = 1
 KN_FLAG_EXACT = 2
 KN_FLAG_BF16X3 = 4
 KN_FLAG_NARROW = 8
+KN_FLAG_NARROW_MFMA = 16      # KN_FLAG_NARROW on the matrix cores where operator and contract allow (include/keynet_hip.h); else KN_FLAG_NARROW
 KN_ABI_VERSION = 5
 
 # every symbol include/keynet_hip.h declares (tests/test_capi.py checks the header against this list)

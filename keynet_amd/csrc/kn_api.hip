@@ -214,6 +214,49 @@ static std::vector<int32_t> convtaps_fill_offsets(ConvTapsDev& c, const SlotList
     return fill_ptr;
 }
 
+// KN_FLAG_NARROW_MFMA: is the operator eligible (no (output pixel, tap) pair holds more than PT_MAX_SLOTS slots, no pixel more than 64 slots -- the filled-in
+// operators of dense float keys gather hundreds of rows per pixel and tap table entry: not this kernel's shape --, the record table stays small)?
+static void convtaps_pt_eligibility(kn_operator* h, const SlotLists& sl) {
+    ConvTapsDev& c = h->ct;
+    const int64_t HoWo = c.Hout * c.Wout;
+    c.pt_ok = c.pt_two = false;
+    if (c.ntaps <= 0 || c.max_slots > 64 || HoWo * c.ntaps > PT_MAX_RECORDS || c.cout_pad % 64 != 0 || c.ntaps * c.cin_pad * c.cout_pad >= ((int64_t)1 << 31)) return;
+    std::vector<int32_t> count((size_t)c.ntaps, 0);
+    for (int64_t o = 0; o < HoWo; o++) {
+        for (int64_t s = sl.pix_ptr[(size_t)o]; s < sl.pix_ptr[(size_t)o + 1]; s++) {
+            const int32_t n = ++count[(size_t)h->h_ent_tap[sl.order[(size_t)s]]];
+            if (n > PT_MAX_SLOTS) return;
+            if (n == 2) c.pt_two = true;
+        }
+        for (int64_t s = sl.pix_ptr[(size_t)o]; s < sl.pix_ptr[(size_t)o + 1]; s++) count[(size_t)h->h_ent_tap[sl.order[(size_t)s]]] = 0;
+    }
+    c.pt_ok = true;
+}
+
+// ... and its records (layout: kn_conv.hip PtRec), built from the handle's host description at the first kn_spmm that asks for them; the caller holds lazy_mu
+int convtaps_build_pt(kn_operator* h) {
+    ConvTapsDev& c = h->ct;
+    if (c.pt_rec || !c.pt_ok) return KN_OK;
+    const int64_t HoWo = c.Hout * c.Wout;
+    const SlotLists sl = convtaps_slot_lists(h);
+    std::vector<int32_t> rec((size_t)(HoWo * c.ntaps * 4), 0);
+    for (size_t k = 0; k < rec.size(); k += 2) rec[k] = -1;
+    for (int64_t o = 0; o < HoWo; o++)
+        for (int64_t s = sl.pix_ptr[(size_t)o]; s < sl.pix_ptr[(size_t)o + 1]; s++) {
+            const size_t e = sl.order[(size_t)s];
+            int32_t* r = rec.data() + (size_t)((o * c.ntaps + h->h_ent_tap[e]) * 4);
+            if (r[0] >= 0) r += 2;                          // the pair's second slot (entry order is kept: ascending input pixel)
+            KN_REQUIRE(r[0] < 0, KN_ERR_INVALID, "more slots on one (output pixel, tap) pair than the record holds");
+            r[0] = h->h_ent_in[e];
+            std::memcpy(r + 1, &h->h_ent_coef[e], sizeof(float));
+        }
+    int32_t* d = nullptr;
+    int rc = upload(&d, rec.data(), rec.size());
+    if (rc) return rc;
+    __atomic_store_n(&c.pt_rec, d, __ATOMIC_RELEASE);       // upload() is a synchronous copy: the records are in HBM before the pointer is visible
+    return KN_OK;
+}
+
 // nnz of the expansion = what the reference's csr holds: one stored entry per (output pixel, input pixel) PAIR and channel pair -- several slots on one pair
 // (a filled-in operator) are one stored non-zero
 static int64_t convtaps_expanded_nnz(const kn_operator* h, const SlotLists& sl) {
@@ -339,6 +382,7 @@ static int convtaps_create_impl(ConvBuild& b, kn_operator** out) {
     for (int64_t o = 0; o < HoWo; o++) c.max_slots = std::max(c.max_slots, pix_ptr[(size_t)o + 1] - pix_ptr[(size_t)o]);
     c.nslots = (int64_t)order.size();
     const std::vector<int32_t> fill_ptr = convtaps_fill_offsets(c, sl);
+    convtaps_pt_eligibility(h.get(), sl);
     // Processing order of the output pixels (kn::locality_order): two pixels are neighbours when they share an input pixel;
     // balls of 64 are, for a keyed 3x3 conv, roughly 8x8 patches of the un-keyed image.  One patch = the workgroups resident
     // on one XCD at a time (32 CUs x 4 workgroups / 2 Cout tiles), so the gathered activation rows of a patch (a ~10x10
@@ -918,6 +962,11 @@ static int spmm_impl(kn_handle_t h, const float* x_dev, int64_t ldx, int64_t n_v
         // KN_FLAG_EXACT is honoured inside convtaps_spmm by the order-preserving kernel on the factored operator
         // KN_FLAG_NARROW on at most 8 columns takes the channel-lane kernel, which reads the slot lists themselves: no side table is built for it
         const bool narrow = narrow_call(flags, n_vecs);
+        if (narrow_mfma_call(h->ct, flags, n_vecs) && __atomic_load_n(&h->ct.pt_rec, __ATOMIC_ACQUIRE) == nullptr && plan_sink() == nullptr) {
+            std::lock_guard<std::mutex> g(h->lazy_mu);           // per-(pixel, tap) records of the matrix-core narrow kernel, once (not capturable: like any first use)
+            rc = convtaps_build_pt(h);
+            if (rc) return rc;
+        }
         // lazily built side tables: double-checked under Handle::lazy_mu; both builders publish their pointer (release) only after the data is in HBM
         if (!narrow && (flags & KN_FLAG_BF16X3) && !(flags & KN_FLAG_EXACT) && __atomic_load_n(&h->ct.tapsB, __ATOMIC_ACQUIRE) == nullptr && plan_sink() == nullptr) {
             std::lock_guard<std::mutex> g(h->lazy_mu);           // bf16 planes of the taps, once (not capturable: like any first use)
@@ -991,11 +1040,14 @@ int kn_release_side_tables(kn_handle_t h) {
     std::lock_guard<std::mutex> g(h->lazy_mu);
     int32_t* rec = __atomic_load_n(&h->ct.fill_rec, __ATOMIC_ACQUIRE);
     uint16_t* tb = __atomic_load_n(&h->ct.tapsB, __ATOMIC_ACQUIRE);
-    if (!rec && !tb) return KN_OK;
+    int32_t* pt = __atomic_load_n(&h->ct.pt_rec, __ATOMIC_ACQUIRE);
+    if (!rec && !tb && !pt) return KN_OK;
     if (int rc = check_device(h, "")) return rc;
     KN_HIP(hipDeviceSynchronize());                               // a launch on ANY stream may still be reading the tables (rare call: a layer changed its contract)
     __atomic_store_n(&h->ct.fill_rec, (int32_t*)nullptr, __ATOMIC_RELEASE);
     __atomic_store_n(&h->ct.tapsB, (uint16_t*)nullptr, __ATOMIC_RELEASE);
+    __atomic_store_n(&h->ct.pt_rec, (int32_t*)nullptr, __ATOMIC_RELEASE);
+    if (pt) (void)hipFree(pt);
     if (rec) (void)hipFree(rec);
     if (tb) (void)hipFree(tb);
     return KN_OK;

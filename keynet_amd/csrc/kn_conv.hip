@@ -1429,6 +1429,157 @@ __global__ __launch_bounds__(256) void convtaps_narrow_kernel(ConvArgs p, int n_
     }
 }
 
+// ---- matrix-core path for 1 .. 8 batch columns (KN_FLAG_NARROW_MFMA): an implicit GEMM whose N dimension is output pixels x images ---------------
+// Y[co, (pixel, image)] = sum over (tap t, input channel ci) of tapsT[t][ci][co] * B[t, ci, (pixel, image)], on v_mfma_f32_32x32x2_f32.  The tolerance
+// contract: the association of the sum is free, and here it is fixed by the tiling alone (never by timing), so a call gives the same bits every time.
+//   M  one workgroup = 32 * TM consecutive output channels (tapsT is contiguous in co: an A fragment is one coalesced 128-byte row per k).
+//   N  32 columns = 32 / NV output pixels, consecutive in pix_order, x NV (1 | 2 | 4 | 8) images; column n = pixel * NV + image, so the images of a
+//      pixel are neighbouring lanes reading neighbouring floats.  Widths between the forms run the next NV up; the surplus columns load and store nothing.
+//   K  tap x input channel, cut into UNITS of (one tap, 16 channels) = 8 matrix instructions per 32 x 32 block.  The four wavefronts of a workgroup take
+//      the units round robin (unit u goes to wavefront u & 3) into accumulators of their own -- a split over K inside the workgroup, which is what lets
+//      conv5_x (196 pixels, K = 4 608: 112 tiles of 32 x 32) occupy 448 wavefronts -- and the four partial tiles are summed through LDS in wavefront order.
+//   B  the element for (t, ci, pixel p, image b) is the sum over the slots of p with slot_tap == t of coef * x[(ci * HiWi + slot_in) * ldx + b]: the
+//      per-(pixel, tap) records of ConvTapsDev::pt_rec (at most PT_MAX_SLOTS slots each) say where to gather.  An absent slot, a channel beyond Cin and a
+//      column beyond the batch contribute NOTHING -- the lane's operand is 0.0f by a select, no product 0 * x is ever formed with an activation the slot
+//      lists do not hold -- so a non-finite activation reaches only the outputs whose slot lists hold it (the zeros of the cin_pad / cout_pad padding
+//      never meet an activation either: channels beyond Cin are masked on both operands, rows beyond Cout are not stored).
+// A unit's 8 (x TM) value loads and 8 (x 2) gathers are issued together, one unit ahead of the matrix instructions that consume them, and the record of the
+// unit after that is in flight meanwhile; nothing in the loop waits on LDS or a barrier.  Epilogue: the last-column (bias x homogeneous row) term where it
+// is stored, ReLU, one store per element straight from the accumulator layout (32 lanes = 32 columns of one output channel).  Element offsets into tapsT
+// and X are 32-bit (checked by the launcher: KN_FLAG_NARROW's size rule), rows of Y are formed in 64 bits.
+struct PtRec {
+    int32_t in0;       // input pixel of the first slot of this (output pixel, tap), or -1
+    float c0;
+    int32_t in1;       // ... of the second one, or -1
+    float c1;
+};
+static_assert(sizeof(PtRec) == 16, "one 16-byte load per record");
+
+template <int TM, bool S2, bool COEF>
+__global__ __launch_bounds__(256) void convtaps_narrow_mfma_kernel(ConvArgs p, const PtRec* __restrict__ pt, int nv_log2, int n_nt, int64_t n_wg) {
+    typedef float f32x16 __attribute__((ext_vector_type(16)));
+    __shared__ float red[4][16 * TM][64];
+    const int64_t chunk = (n_wg + 7) >> 3;
+    const int64_t wg = (int64_t)(blockIdx.x & 7) * chunk + (blockIdx.x >> 3);      // work items dealt to the XCDs in contiguous chunks (a chunk = few channel tiles, many pixels)
+    if (wg >= n_wg || (blockIdx.x >> 3) >= chunk) return;                           // (uniform over the workgroup: before any barrier)
+    const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+    const int lane = threadIdx.x & 63;
+    const int mt = (int)(wg / n_nt), nt = (int)(wg - (int64_t)mt * n_nt);
+    const int n = lane & 31, kh = lane >> 5;                 // column of the B / C fragment (and row of the A fragment), k of the pair this lane supplies
+    const int col = nt * 32 + n;
+    const int pi = col >> nv_log2, b = col & ((1 << nv_log2) - 1);
+    const bool colok = pi < p.n_pix && b < p.n_vecs;
+    const int o = colok ? p.pix_order[pi] : 0;
+    const int co0 = mt * 32 * TM;
+    const int nchunk = (p.Cin + 15) >> 4;
+    const int n_units = p.ntaps * nchunk;
+    const uint32_t ldx = (uint32_t)p.ldx, ci_x = (uint32_t)p.HiWi * ldx;
+
+    f32x16 acc[TM];
+#pragma unroll
+    for (int i = 0; i < TM; i++)
+#pragma unroll
+        for (int j = 0; j < 16; j++) acc[i][j] = 0.0f;
+
+    // Every load below is issued unconditionally at a valid address and a lane that must not see the element keeps 0.0f by a SELECT on the loaded
+    // value (never a multiply by zero): an absent slot reads its column's own row of input pixel 0, a channel beyond Cin reads channel 0, a column beyond
+    // the batch reads column 0 of pixel pix_order[0].  Straight-line load blocks are what lets the waits of a unit's matrix instructions leave the next
+    // unit's loads in flight (a load under a branch makes the counter wait for everything issued before the join).
+    const uint32_t bcol = colok ? (uint32_t)b : 0u;
+    struct Unit {                                           // one unit's operands as loaded, and what masks them when they are multiplied
+        float a[TM][8], v0[8], v1[S2 ? 8 : 1];
+        PtRec r;
+        int crem;                                           // step k of this lane is a real channel when 2 k < crem
+    };
+    auto record = [&](const int u) -> PtRec {               // the (pixel, tap) record of unit u (beyond the last unit: the last tap's, unused)
+        const int t = u < n_units ? u / nchunk : p.ntaps - 1;
+        PtRec r = pt[(int64_t)o * p.ntaps + t];
+        if (!colok) r.in0 = r.in1 = -1;
+        return r;
+    };
+    auto load = [&](const int u, const PtRec r, Unit& w) {
+        const int t = u / nchunk, c0 = (u - t * nchunk) << 4;
+        const float* const arow = p.tapsT + ((uint32_t)t * (uint32_t)p.cin_pad * (uint32_t)p.cout_pad + (uint32_t)(co0 + n));
+        const uint32_t x0off = (r.in0 >= 0 ? (uint32_t)r.in0 : 0u) * ldx + bcol, x1off = (r.in1 >= 0 ? (uint32_t)r.in1 : 0u) * ldx + bcol;
+        w.r = r;
+        w.crem = p.Cin - c0 - kh;
+#pragma unroll
+        for (int k = 0; k < 8; k++) {
+            const uint32_t cic = 2 * k < w.crem ? (uint32_t)(c0 + 2 * k + kh) : 0u;
+#pragma unroll
+            for (int i = 0; i < TM; i++) w.a[i][k] = arow[cic * (uint32_t)p.cout_pad + 32u * i];
+            w.v0[k] = p.X[cic * ci_x + x0off];
+            if constexpr (S2) w.v1[k] = p.X[cic * ci_x + x1off];
+        }
+    };
+    auto mfma = [&](const Unit& w) {
+        const bool s0 = w.r.in0 >= 0, s1 = S2 && w.r.in1 >= 0;
+#pragma unroll
+        for (int k = 0; k < 8; k++) {
+            const bool cok = 2 * k < w.crem;
+            float xv = (cok && s0) ? (COEF ? w.r.c0 * w.v0[k] : w.v0[k]) : 0.0f;
+            if constexpr (S2) {
+                const float w1 = (cok && s1) ? (COEF ? w.r.c1 * w.v1[k] : w.v1[k]) : 0.0f;
+                xv = xv + w1;
+            }
+#pragma unroll
+            for (int i = 0; i < TM; i++) acc[i] = __builtin_amdgcn_mfma_f32_32x32x2f32(cok ? w.a[i][k] : 0.0f, xv, acc[i], 0, 0, 0);
+        }
+    };
+
+    // two register sets in turn, no copies: the loads of unit u + 4 and the record of unit u + 8 are in flight while unit u is multiplied
+    Unit w0, w1;
+    int u = wave;
+    if (u < n_units) {
+        PtRec rn = record(u + 4);
+        load(u, record(u), w0);
+        for (;;) {
+            if (u + 4 >= n_units) {
+                mfma(w0);
+                break;
+            }
+            load(u + 4, rn, w1);
+            rn = record(u + 8);
+            mfma(w0);
+            u += 4;
+            if (u + 4 >= n_units) {
+                mfma(w1);
+                break;
+            }
+            load(u + 4, rn, w0);
+            rn = record(u + 8);
+            mfma(w1);
+            u += 4;
+        }
+    }
+
+    // the four partial tiles, summed in wavefront order; wavefront w finishes accumulator registers 4 TM w .. 4 TM (w + 1) - 1 of the tile
+#pragma unroll
+    for (int i = 0; i < TM; i++)
+#pragma unroll
+        for (int j = 0; j < 16; j++) red[wave][i * 16 + j][lane] = acc[i][j];
+    __syncthreads();
+    if (!colok) return;
+    const float xlast = p.lastcol ? p.X[p.last_in_row * p.ldx + b] : 0.0f;
+#pragma unroll
+    for (int q = 0; q < 4 * TM; q++) {
+        const int r = wave * 4 * TM + q;
+        float v = red[0][r][lane] + red[1][r][lane];
+        v = v + red[2][r][lane];
+        v = v + red[3][r][lane];
+        const int j = r & 15;
+        const int co = co0 + (r >> 4) * 32 + (j >> 2) * 8 + kh * 4 + (j & 3);      // row of accumulator register j on this lane (32 x 32 layout)
+        if (co >= p.Cout) continue;
+        const int64_t row = (int64_t)co * p.HoWo + o;
+        if (p.lastcol) {
+            const float lc = p.lastcol[row];
+            if (lc != 0.0f) v = v + lc * xlast;
+        }
+        if (p.relu) v = (v < 0.0f) ? 0.0f : v;
+        p.Y[row * p.ldy + b] = v;
+    }
+}
+
 // ---- KN_FLAG_EXACT on FILLED-IN operators (round 5) ------------------------------------------------------------------------------------
 // A float key whose inverse is dense inside its blocks (the reference's doubly-stochastic keys, test/test_keynet.py:116-129) fills the keyed conv in:
 // 500 - 5 400 slots per output pixel instead of 9, and one (output pixel, input pixel) pair is hit by several taps -- ONE stored non-zero of the
@@ -2115,7 +2266,7 @@ __global__ __launch_bounds__(256) void conv_lastrow_kernel(const float* __restri
 }
 
 void convtaps_free(ConvTapsDev& c) {
-    void* ptrs[] = {c.tapsT, c.pix_ptr, c.slot_in, c.slot_tap, c.slot_coef, c.pix_order, c.lastcol, c.sk_desc, c.tapsB, c.zero_ent, c.ex_ptr, c.ex_tab, c.ex_order, c.fill_ptr, c.fill_rec};
+    void* ptrs[] = {c.tapsT, c.pix_ptr, c.slot_in, c.slot_tap, c.slot_coef, c.pix_order, c.lastcol, c.sk_desc, c.tapsB, c.zero_ent, c.ex_ptr, c.ex_tab, c.ex_order, c.fill_ptr, c.fill_rec, c.pt_rec};
     for (void* q : ptrs)
         if (q) (void)hipFree(q);
     c = ConvTapsDev();
@@ -2455,6 +2606,39 @@ static int spmm_narrow(const ConvTapsDev& A, ConvArgs& a, hipStream_t s) {
     return exact_tail(A, a, s);
 }
 
+// KN_FLAG_NARROW_MFMA on an eligible operator: 32 TM output channels x 32 (pixel, image) columns per workgroup, K split over its four wavefronts.
+// TM = 2 (one gathered B fragment feeds two matrix instructions; 160 - 184 registers and 32 KB of LDS: two wavefronts per SIMD, two workgroups per CU)
+// where the 64-channel tiling has at least 1 024 workgroups; else 32-channel tiles (<= 120 registers, 16 KB: four wavefronts per SIMD), so that the small
+// layers spread over the chip (VGG-16 conv5_x: 16 x 7 tiles).  Measured in profiles/r08_narrow_mfma.txt: layers that cross the threshold with more images do
+// twice the work in no more time, i.e. the threshold is not too low (512 is unmeasured).  Same 32-bit offset rule as the channel-lane kernel.
+typedef void (*NarrowMfmaKernel)(ConvArgs, const PtRec*, int, int, int64_t);
+template <int TM>
+static NarrowMfmaKernel narrow_mfma_kernel(bool two, bool coef) {
+    return two ? (coef ? convtaps_narrow_mfma_kernel<TM, true, true> : convtaps_narrow_mfma_kernel<TM, true, false>)
+               : (coef ? convtaps_narrow_mfma_kernel<TM, false, true> : convtaps_narrow_mfma_kernel<TM, false, false>);
+}
+
+static int spmm_narrow_mfma(const ConvTapsDev& A, ConvArgs& a, hipStream_t s) {
+    const int64_t n_vecs = a.n_vecs;
+    const int nv_log2 = n_vecs <= 1 ? 0 : (n_vecs <= 2 ? 1 : (n_vecs <= 4 ? 2 : 3));
+    const int64_t n_nt = (((int64_t)a.n_pix << nv_log2) + 31) / 32;
+    KN_REQUIRE(A.cout_pad % 64 == 0, KN_ERR_UNSUPPORTED, "KN_FLAG_NARROW_MFMA: the value rows are not padded to whole 64-channel blocks");
+    KN_REQUIRE(A.ntaps * A.cin_pad * A.cout_pad < ((int64_t)1 << 31) && (a.last_in_row + 1) * a.ldx + NARROW_MAX_VECS < ((int64_t)1 << 31),
+               KN_ERR_UNSUPPORTED, "KN_FLAG_NARROW_MFMA: the taps or the activation block exceed 32-bit element offsets");
+    const int tm = ((A.Cout + 63) / 64) * n_nt >= 1024 ? 2 : 1;
+    const int64_t n_wg = ((A.Cout + 32 * tm - 1) / (32 * tm)) * n_nt;
+    KN_REQUIRE(n_wg + 8 < ((int64_t)1 << 29) && n_nt < ((int64_t)1 << 26), KN_ERR_UNSUPPORTED, "grid too large for the matrix-core narrow kernel");
+    const PtRec* pt = reinterpret_cast<const PtRec*>(__atomic_load_n(&A.pt_rec, __ATOMIC_ACQUIRE));
+    KN_REQUIRE(pt != nullptr || plan_sink() != nullptr, KN_ERR_INVALID, "KN_FLAG_NARROW_MFMA: the (pixel, tap) records were not built");
+    const bool coef = !A.unit_coef;
+    KN_LAUNCH("convtaps_narrow_mfma_kernel<" + std::to_string(32 * tm) + " channels x " + std::to_string(32 >> nv_log2) + " pixels x NV=" + std::to_string(1 << nv_log2) +
+                  ((1 << nv_log2) == n_vecs ? "" : " masked to " + std::to_string(n_vecs)) + ", K split over 4 wavefronts" + (A.pt_two ? ", two slots per tap" : "") + (coef ? ",coef" : "") +
+                  "> (v_mfma_f32_32x32x2_f32, at most " + std::to_string(PT_MAX_SLOTS) + " slots per (pixel, tap))",
+              (tm == 2 ? narrow_mfma_kernel<2>(A.pt_two, coef) : narrow_mfma_kernel<1>(A.pt_two, coef)), dim3((unsigned)(((n_wg + 7) / 8) * 8)), dim3(256), 0, s, a, pt, nv_log2, (int)n_nt, n_wg);
+    launch_lastrow(A, a, s);
+    return KN_OK;
+}
+
 static int spmm_exact(const ConvTapsDev& A, ConvArgs& a, hipStream_t s) {
     const ExactChoice c = exact_choice(A, a);
     const int64_t n_vecs = a.n_vecs;
@@ -2575,7 +2759,9 @@ int convtaps_spmm(const ConvTapsDev& A, const float* x, int64_t ldx, int64_t n_v
     ConvArgs a = conv_args(A, x, ldx, n_vecs, y, ldy, flags);
     int rc;
     // KN_FLAG_NARROW on a batch of at most 8 columns: the channel-lane order-preserving kernel, whatever the other contract flags say
-    if (narrow_call(flags, n_vecs)) {
+    if (narrow_mfma_call(A, flags, n_vecs)) {
+        rc = spmm_narrow_mfma(A, a, s);
+    } else if (narrow_call(flags, n_vecs)) {
         rc = spmm_narrow(A, a, s);
     } else if (flags & KN_FLAG_EXACT) {
         rc = spmm_exact(A, a, s);

@@ -264,6 +264,12 @@ struct ConvTapsDev {
     // bf16x3 path (kn_conv.hip, convtaps_bf16x3_kernel): the taps as three bf16 planes, built at the first kn_spmm that asks for them
     uint16_t* tapsB = nullptr;
     int64_t tapsB_plane = 0;
+    // matrix-core path for 1 .. 8 columns (kn_conv.hip, convtaps_narrow_mfma_kernel): the slot lists seen per (output pixel, tap) -- 16-byte records
+    // {input pixel, coefficient} x PT_MAX_SLOTS, -1 where a pair has fewer slots.  pt_ok at create (no pair holds more slots, the table stays small); the
+    // records are built at the first kn_spmm that asks for them
+    bool pt_ok = false;
+    bool pt_two = false;                // some (pixel, tap) pair holds two slots
+    int32_t* pt_rec = nullptr;          // [HoWo][ntaps][4]
 };
 
 }  // namespace kn
@@ -319,7 +325,22 @@ static constexpr int MF_MIN_MEMBERS = 24;   // a pattern group takes the matrix-
 // and *absmax_fused is set; otherwise the caller runs absmax_pass over Y afterwards (kn_spmm_screen)
 // KN_FLAG_NARROW: the widest batch of the channel-lane conv-taps kernel, and whether a call takes it (the one place that reads the flag)
 static constexpr int64_t NARROW_MAX_VECS = 8;
-static inline bool narrow_call(uint32_t flags, int64_t n_vecs) { return (flags & KN_FLAG_NARROW) && n_vecs <= NARROW_MAX_VECS; }
+static inline bool narrow_call(uint32_t flags, int64_t n_vecs) { return (flags & (KN_FLAG_NARROW | KN_FLAG_NARROW_MFMA)) && n_vecs <= NARROW_MAX_VECS; }
+// KN_FLAG_NARROW_MFMA: the most slots one (output pixel, tap) pair may hold for the matrix-core narrow kernel, the largest record table built for it, and
+// whether a narrow call takes that kernel (otherwise the flag means KN_FLAG_NARROW)
+static constexpr int PT_MAX_SLOTS = 2;
+static constexpr int64_t PT_MAX_RECORDS = (int64_t)1 << 22;
+// The one SHAPE that stays on the channel-lane kernel (measured, profiles/r08_narrow_mfma.txt): a K unit of the matrix-core kernel is (one tap, 16 input
+// channels), so with Cin <= 4 at least three quarters of its matrix instructions and value loads are padding, while the channel-lane kernel walks Cin
+// channels only and carries 8 columns per lane for the price of one.  VGG-16 conv1_1 (Cin 3, 50 176 pixels): 0.73x at 5 .. 8 images (1.03x at 4, 1.25x
+// at 2, 1.46x at 1).  Only where the channel-lane grid fills the chip (>= 1 024 workgroups of four (pixel, 64 channels) items); smaller layers were not
+// measured slower and keep the kernel.
+static inline bool narrow_mfma_loses(const ConvTapsDev& A, int64_t n_vecs) {
+    return A.Cin <= 4 && n_vecs > 4 && A.Hout * A.Wout * ((A.Cout + 63) / 64) >= 4 * 1024;
+}
+static inline bool narrow_mfma_call(const ConvTapsDev& A, uint32_t flags, int64_t n_vecs) {
+    return (flags & KN_FLAG_NARROW_MFMA) && !(flags & KN_FLAG_EXACT) && n_vecs <= NARROW_MAX_VECS && A.pt_ok && !narrow_mfma_loses(A, n_vecs);
+}
 int convtaps_spmm(const ConvTapsDev& A, const float* x, int64_t ldx, int64_t n_vecs, float* y, int64_t ldy,
                   uint32_t flags, hipStream_t s, float* absmax = nullptr, bool* absmax_fused = nullptr);
 int absmax_pass(const float* y, int64_t rows, int64_t ld, int64_t n_vecs, float* absmax, hipStream_t s);
@@ -364,6 +385,7 @@ int chain_forward(const ChainDev* c, const float* x, int64_t ldx, int64_t n_vecs
 void chain_free(ChainDev* c);
 int convtaps_build_bf16(ConvTapsDev& A, const std::vector<float>& taps);
 int convtaps_build_fill(ConvTapsDev& A, hipStream_t s);
+int convtaps_build_pt(kn_operator* h);      // kn_api.hip (it reads the host description of the handle)
 bool convtaps_fill_ok(const ConvTapsDev& A);
 bool convtaps_bf16x3_ok(const ConvTapsDev& A, const float* x, int64_t ldx, int64_t n_vecs, const float* y, int64_t ldy);
 void csr_free(CsrDev& c);

@@ -15,7 +15,9 @@ Schema (also the schema of tests/golden/*.npz, written by tests/golden/make_gold
                                      absent (golden files) = the default.  (Older archives hold a bool, or the string 'auto'.)
     L.<name>.exact_decl              (save_keynet only) the contract the layer was DECLARED with (what exact_mode(None) returns to)
     L.<name>.contract_record         (save_keynet only) JSON of the calibration record behind a decided 'auto' layer (measured difference,
-                                     tolerance, the max |x| the decision covers): a loaded key-net keeps re-screening against it
+                                     tolerance, the max |x| the decision covers): a loaded key-net keeps re-screening against it.  The record of a
+                                     layer's narrow='mfma' measurement rides inside it (key 'narrow': KeyedLayer.narrow_mode), so a loaded key-net
+                                     keeps that decision and its screen too
     outshape                         (C,1,1) of the logits
     sensor.*                         (optional) the image key pair as stored-order CSR + 'sensor.inshape'
 

@@ -217,12 +217,16 @@ class KeyedLayer(nn.Module):
         A layer whose contract is still 'auto' decides it here, on this batch (blocking host reads, an extra order-preserving launch:
         not capturable into a HIP graph -- KeyedModel.capture runs an eager forward first).
         `narrow` (at most KeyedModel.NARROW_MAX images): a conv-taps layer runs the channel-lane order-preserving kernel (KN_FLAG_NARROW) whatever its
-        contract is -- the reference's own arithmetic, which satisfies every contract: nothing is calibrated, screened or decided; other layers run as usual."""
+        contract is -- the reference's own arithmetic, which satisfies every contract: nothing is calibrated, screened or decided; other layers run as usual.
+        `narrow='mfma'`: the matrix-core narrow kernel (KN_FLAG_NARROW_MFMA) where this layer's contract in force allows re-ordered sums (narrow_mode():
+        declared -> always; decided by calibration -> measured once on the first such batch, recorded under _contract_record['narrow']); else narrow=True."""
         if verbose():
             print('[keynet_amd.layer]: forward %s' % str(self))
         exact = getattr(self, '_exact', True)
         if narrow and self.W.narrow_capable():
-            return self.W.torchdot(x_affine.t(), relu=(fuse_relu or self.iskeyedrelu()), exact=exact, absmax=absmax, narrow=True).t()
+            relu = fuse_relu or self.iskeyedrelu()
+            mode = self.narrow_mode(narrow, x_affine.t(), relu) if narrow == 'mfma' else True
+            return self.W.torchdot(x_affine.t(), relu=relu, exact=exact, absmax=absmax, narrow=mode).t()
         if narrow and exact == 'auto':
             exact = True                     # an undecided layer without a narrow form: the reference's order for this call, nothing decided or recorded
         if exact == 'auto':
@@ -245,8 +249,14 @@ class KeyedLayer(nn.Module):
         containers, float64 operators, small or sparse matrices -- has the reference's order only.
         `narrow` (a batch of at most KeyedModel.NARROW_MAX columns): an operator that owns a conv-taps handle (W.narrow_capable()) is ONE launch of the
         channel-lane order-preserving kernel under EVERY contract, the undecided and the two-step ones included -- KN_FLAG_NARROW next to the flags the
-        contract sets anyway (the library ignores them below 9 columns); every other operator is what it is without the keyword."""
+        contract sets anyway (the library ignores them below 9 columns); every other operator is what it is without the keyword.
+        `narrow='mfma'`: a CONV operator under a re-ordering contract (False, 'bf16x3', 'split') is one launch with KN_FLAG_NARROW_MFMA (the matrix-core narrow
+        kernel) and no other contract flag; under True / 'auto', and for every other operator, exactly narrow=True.  (Whether a CALIBRATED layer may pass 'mfma'
+        here is KeyedLayer.narrow_mode's decision.)"""
         conv = isinstance(W, ksp.Conv2dTiledMatrix)
+        if narrow == 'mfma' and conv and W.narrow_capable() and contract in (False, 'bf16x3', 'split'):
+            # a conv operator under a re-ordering contract: the matrix-core narrow kernel (the library falls back to the channel-lane kernel on an ineligible operator)
+            return (W._device_op, (_capi.KN_FLAG_RELU if relu else 0) | _capi.KN_FLAG_NARROW_MFMA)
         if narrow and W.narrow_capable():
             exact = contract is True or not conv
             return (W._device_op, (_capi.KN_FLAG_RELU if relu else 0) | (_capi.KN_FLAG_EXACT if exact else 0) | (_capi.KN_FLAG_BF16X3 if contract == 'bf16x3' else 0) | _capi.KN_FLAG_NARROW)
@@ -262,8 +272,10 @@ class KeyedLayer(nn.Module):
     def launch(self, device, relu=False, narrow=False):
         """This layer under its contract in force as one launch on `device` (`relu`: the unkeyed nn.ReLU behind it is fused in), or None when it is not one
         kn_spmm launch: see kernel(); a float64 operator (its own kernel and a float64 result: kn_spmm_f64).  What the key-net's planners read
-        (KeyedModel._chain_op / _overlap_plan); forward() -> W.torchdot() runs the same rule.  `narrow`: see kernel()."""
+        (KeyedModel._chain_op / _overlap_plan); forward() -> W.torchdot() runs the same rule.  `narrow`: see kernel(); 'mfma' goes through narrow_mode() first, without a batch."""
         W = self.W
+        if narrow == 'mfma':
+            narrow = self.narrow_mode(narrow)                 # (a calibrated layer without a narrow record yet: the channel-lane kernel -- forward() measures, a planner does not)
         kernel = None if W.is_float64() else self.kernel(W, getattr(self, '_exact', True), relu or self.iskeyedrelu(), device, narrow=narrow)
         if kernel is None:
             return None
@@ -280,14 +292,83 @@ class KeyedLayer(nn.Module):
         rec = getattr(self, '_contract_record', None)
         return getattr(self, '_exact', True) in (False, 'bf16x3', 'split') and rec is not None and rec.get('max_abs_x') is not None
 
-    def rescreen(self, xmax):
+    def rescreen(self, xmax, narrow=False):
         """max |x| of a later batch against the calibrated one: True = the decision does not cover this batch (re-calibrate).  The measured
         difference of a re-ordered f32 sum scales with the activations while the tolerance 1e-5 max(1, |y|) has a floor, so a decision
-        taken with 2x headroom (accepted at <= 0.5 tol) is kept for inputs up to RESCREEN_FACTOR x the calibrated magnitude."""
-        cal = float(self._contract_record['max_abs_x'])
+        taken with 2x headroom (accepted at <= 0.5 tol) is kept for inputs up to RESCREEN_FACTOR x the calibrated magnitude.
+        `narrow`: against the narrow record (the measurement of the matrix-core narrow kernel) instead of the wide one."""
+        cal = float((self._contract_record['narrow'] if narrow else self._contract_record)['max_abs_x'])
         if not np.isfinite(cal):
             return False                                          # calibrated on non-finite activations: there is no larger batch to learn from
         return not (xmax <= self.RESCREEN_FACTOR * cal)          # also True for NaN
+
+    # -- narrow='mfma': the matrix-core narrow kernel under the layer's contract ------------------------------------------
+    def narrow_record(self):
+        """The record of this layer's narrow='mfma' measurement (a calibrated layer only), or None."""
+        rec = getattr(self, '_contract_record', None)
+        return None if rec is None else rec.get('narrow')
+
+    def narrow_screened(self):
+        """Does a narrow='mfma' forward run this layer on the matrix-core narrow kernel BY A MEASUREMENT (then it re-screens max |x| like the wide forward)?"""
+        rec = self.narrow_record()
+        return self.screened() and rec is not None and rec.get('decided') == 'mfma' and rec.get('max_abs_x') is not None
+
+    def narrow_mode(self, narrow, xt=None, relu=False):
+        """What `narrow='mfma'` means for this layer now: 'mfma' (KN_FLAG_NARROW_MFMA) or True (the channel-lane kernel, the bits of narrow=True).
+        Contract True, or 'auto' still undecided, or not a conv-taps operator: True, nothing decided.  A DECLARED re-ordering contract (exact=False,
+        'bf16x3' forced): 'mfma', unscreened -- the caller's responsibility, as on the wide path.  A contract DECIDED BY CALIBRATION (screened()): the kernel is
+        one more association of the sum that the wide record does not cover, so the first eager call with a batch `xt` ([cols, N <= 8]) measures it -- the
+        channel-lane kernel and the matrix-core kernel on these very columns, gate() -- and accepts by _calibrate's rule: the worst element uses at most half
+        its tolerance, a quarter where the bound screen 2 eps32 max_row sum|a| max|x| <= 1e-5 fails.  The outcome is _contract_record['narrow'] = {decided:
+        'mfma' | 'exact', gate_ratio, max_abs_x, measured_on_columns, ...}; the wide decision and its fields are never touched.  Without a batch (a planner
+        asking) an unmeasured layer answers True."""
+        W = self.W
+        exact = getattr(self, '_exact', True)
+        if narrow != 'mfma' or not isinstance(W, ksp.Conv2dTiledMatrix) or not W.narrow_capable() or exact not in (False, 'bf16x3', 'split'):
+            return True if narrow else False
+        if not self.screened():
+            return 'mfma'
+        rec = self.narrow_record()
+        if rec is None:
+            if xt is None:
+                return True
+            if xt.is_cuda and torch.cuda.is_current_stream_capturing():
+                raise _capi.KeynetHipError('keynet_amd: %s has not measured the matrix-core narrow kernel yet (host reads): run one eager narrow=\'mfma\' forward '
+                                           'before capturing a HIP graph (KeyedModel.capture does)' % self._repr)
+            rec = self._contract_record['narrow'] = self._measure_narrow(xt, relu)
+        return 'mfma' if rec['decided'] == 'mfma' else True
+
+    def _measure_narrow(self, xt, relu):
+        """The narrow record of a calibrated layer, measured on the batch xt ([cols, N <= 8]): see narrow_mode()."""
+        W = self.W
+        xt = ksp._device_block(xt)
+        n = int(xt.shape[1])
+        dev = xt.device
+        with torch.cuda.device(xt.device):
+            # the widest of these columns the library runs on the matrix-core kernel (a shape rule of the handle may keep a wide batch of a layer on the
+            # channel-lane kernel, where both sides of the measurement would be the same launch): the measurement is of that kernel, on those columns
+            for m in (n, 4, 2, 1):
+                plan = W._device_op(dev).plan(max(min(m, n), 1), _capi.KN_FLAG_NARROW_MFMA | (_capi.KN_FLAG_RELU if relu else 0))
+                if 'convtaps_narrow_mfma_kernel' in plan:
+                    break
+        if 0 < m < n and 'convtaps_narrow_mfma_kernel' in plan:
+            (xt, n) = (xt[:, :m].contiguous(), m)
+        if n == 0 or 'convtaps_narrow_mfma_kernel' not in plan:
+            return dict(layer=self._repr, decided='exact', reason='an empty batch' if n == 0 else 'the operator has no matrix-core narrow form (more than two slots on a (pixel, tap) pair)',
+                        gate_ratio=None, max_abs_x=None, measured_on_columns=n)
+        xmax = float(xt.detach().abs().max())
+        asum = getattr(self, '_abs_rowsum', None)
+        if asum is None:
+            asum = self._abs_rowsum = W.max_abs_rowsum()
+        bound = 2.0 * EPS32 * asum * xmax
+        ye = W.torchdot(xt, relu=relu, exact=True, narrow=True)
+        ym = W.torchdot(xt, relu=relu, exact=False, narrow='mfma')
+        (ratio, measured, tol, dmax) = gate(ym, ye)
+        ok = ratio <= 0.5 and (bound <= FLOAT_KEY_ATOL or ratio <= 0.25)
+        if not ok:
+            _log.warning('keynet_amd: %s keeps the channel-lane kernel on narrow forwards: matrix-core narrow result off by %.3g where the tolerance is %.3g', self._repr, measured, tol)
+        return dict(layer=self._repr, decided='mfma' if ok else 'exact', measured_narrow_mfma_vs_exact=measured, tol=tol, bound=bound, gate_ratio=ratio, max_abs_diff=dmax,
+                    max_abs_x=xmax, measured_on_columns=n)
 
     def mfma_capable(self, device=None):
         """Does tolerance mode run this layer on the matrix cores at all (conv-taps operator, or a large dense nn.Linear)?"""

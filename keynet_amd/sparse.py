@@ -83,7 +83,8 @@ def _device_block(x):
 def _run_torchdot(W, x, relu=False, exact=True, absmax=None, narrow=False):
     """Y = W.X on the GPU under the contract `exact`, on the handle and flags of KeyedLayer.kernel.  x: [cols, N], torch tensor (any device / strides) or ndarray.
     Returns [rows, N] on x's device: float32, or for a float64 operator the float64 block scipy returns for it (kn_spmm_f64; the activations are
-    float32 either way).  `narrow`: at most NARROW_MAX columns on the channel-lane kernel where W owns a conv-taps handle (KeyedLayer.kernel)."""
+    float32 either way).  `narrow`: at most NARROW_MAX columns on the channel-lane kernel where W owns a conv-taps handle (KeyedLayer.kernel); 'mfma': on the
+    matrix-core narrow kernel (KN_FLAG_NARROW_MFMA) where `exact` is a re-ordering contract, else exactly narrow=True."""
     from .layer import KeyedLayer            # (layer.py imports this module)
     x = torch.as_tensor(x)
     assert W.shape[1] == x.shape[0], 'Non-conformal shape for W=%s, x=%s' % (str(W.shape), str(tuple(x.shape)))
@@ -279,7 +280,7 @@ class FactoredSparseMatrix(SparseMatrix):
         return True
 
     def torchdot(self, x_torch, relu=False, exact=True, absmax=None, narrow=False):
-        """SparseMatrix.torchdot; `narrow`: at most NARROW_MAX columns on the channel-lane kernel of the factored device form (KN_FLAG_NARROW) -- the
+        """SparseMatrix.torchdot; `narrow` (True or 'mfma': the same here, the operator is under the bit-exact contract): at most NARROW_MAX columns on the channel-lane kernel of the factored device form (KN_FLAG_NARROW) -- the
         same bits as without it (the order-preserving product, which IS scipy's on the stored CSR)."""
         return _run_torchdot(self, x_torch, relu=relu, exact=exact, absmax=absmax, narrow=narrow)
 
@@ -599,7 +600,9 @@ class Conv2dTiledMatrix(TiledMatrix):
         operator applied as spatial mixing per tap, then channel mixing (see _split_ops: another association of the sum, tolerance contract only); exact='bf16x3': f32 products
         emulated on the bf16 matrix pipe (three-way exact split, six of nine cross products, f32 accumulate: KN_FLAG_BF16X3) where the
         operator and batch qualify, else the f32 MFMA path.  narrow=True (N <= NARROW_MAX, ValueError beyond): the channel-lane order-preserving kernel
-        (KN_FLAG_NARROW) whatever `exact` says -- always the reference's own arithmetic, the bits of exact=True."""
+        (KN_FLAG_NARROW) whatever `exact` says -- always the reference's own arithmetic, the bits of exact=True.  narrow='mfma': the matrix-core narrow kernel
+        (KN_FLAG_NARROW_MFMA: an implicit GEMM over output pixels x images, another association of the sum) when `exact` is False / 'bf16x3' / 'split' and the
+        operator is eligible (no (pixel, tap) pair with more than two slots); under True / 'auto', and on an ineligible operator, exactly narrow=True."""
         assert not isinstance(exact, str) or exact in ('bf16x3', 'split') or (narrow and exact == 'auto'), "exact must be True, False, 'bf16x3' or 'split'"
         return _run_torchdot(self, x, relu=relu, exact=exact, absmax=absmax, narrow=narrow)
 

@@ -203,33 +203,59 @@ class KeyedModel(object):
         every contract: it calibrates nothing, screens nothing, changes no layer's decision or record and leaves the cached launch lists alone.  The other
         layers run as they do without the keyword, at the unpadded width (a layer still undecided: in the reference's order, for this call; a non-conv layer a calibration
         put on the matrix cores stays there and is NOT re-screened by this forward); a key-net that
-        qualifies for the whole-net kernel still takes it; the overlapped form is never taken."""
+        qualifies for the whole-net kernel still takes it; the overlapped form is never taken.
+        `narrow='mfma'`: the same forward with the conv-taps layers on the matrix-core narrow kernel (KN_FLAG_NARROW_MFMA: an implicit GEMM whose N dimension is
+        output pixels x images) WHERE THE LAYER'S CONTRACT IN FORCE ALLOWS RE-ORDERED SUMS (KeyedLayer.narrow_mode): a declared exact=False / 'bf16x3' layer always,
+        unscreened; a layer calibration put on a re-ordering kernel after ITS OWN measurement on the first such batch (channel-lane against matrix-core kernel on these
+        columns, the rule of _calibrate; recorded under the layer's calibration record as 'narrow', the wide decision untouched); a layer under True, or still
+        undecided, exactly as narrow=True -- nothing is decided for it.  Layers accepted by measurement are re-screened on every narrow='mfma' forward like their
+        wide counterparts: max |x| of each comes from kn_spmm_screen on its producer (behind the narrow kernels that is one kn_absmax-style reduction launch per
+        screened layer, one more for the input when the first layer is screened), is read back once at the end of the forward, and a layer whose input exceeds
+        RESCREEN_FACTOR x its narrow record's max_abs_x drops that record, is measured again on this batch, and the batch runs again (_rescreen)."""
         if narrow:
-            return self._forward_narrow(img_cipher)
+            return self._forward_narrow(img_cipher, narrow)[0]
         (x, windows) = self._prepare(img_cipher)
         y = self._forward_passes(x, windows, overlap)[0][:img_cipher.shape[0]]
         return y if img_cipher.is_cuda else y.to(img_cipher.device)
 
-    def _forward_narrow(self, img_cipher):
-        """forward_linear(narrow=True): see there.  Stream-ordered on torch's current HIP stream, no host read; capturable once the operators are resident."""
+    def _forward_narrow(self, img_cipher, mode=True):
+        """forward_linear(narrow=True | 'mfma'): see there; returns (y, screens).  Stream-ordered on torch's current HIP stream.  narrow=True: no host read, capturable
+        once the operators are resident.  'mfma': layers on the matrix-core narrow kernel by a measurement are screened -- `screens` = [(slots, screened)] as in
+        _forward_passes, read back here once per pass unless the stream is capturing (capture's replay reads them)."""
         n = img_cipher.shape[0]
         if n > self.NARROW_MAX:
-            raise ValueError('narrow=True takes at most %d images, got %d' % (self.NARROW_MAX, n))
+            raise ValueError('narrow=%r takes at most %d images, got %d' % (mode, self.NARROW_MAX, n))
         x = img_cipher
         if not x.is_cuda and x.dim() == 2 and torch.cuda.is_available():
             x = x.detach().float().cuda()
         if x.is_cuda and x.dim() == 2 and x.dtype == torch.float32 and not x.t().is_contiguous():
             x = x.detach().t().contiguous().t()                  # feature-major once: every layer hands the next one such a block
         y = None
-        if x.is_cuda and x.dim() == 2 and not any(c.W.narrow_capable() for c in self._keyed()):
+        keyed = self._keyed()
+        if x.is_cuda and x.dim() == 2 and not any(c.W.narrow_capable() for c in keyed):
             chain = self._chain_op(x.device)                     # (a key-net without conv-taps operators: the whole-net kernel where it qualifies, as without the keyword)
             if chain is not None:
                 y = self._forward_chain(x, chain)
-        if y is None:
+        screens = []
+        read = x.is_cuda and x.dim() == 2 and not torch.cuda.is_current_stream_capturing() and self.RESCREEN_READ
+        for attempt in range(self.RESCREEN_MAX_PASSES if y is None else 0):
+            # layers measured DURING this pass were measured on this very batch: only the records that existed before it are screened
+            screened = set(j for (j, c) in enumerate(keyed) if c.narrow_screened()) if (mode == 'mfma' and self.RESCREEN and x.is_cuda and x.dim() == 2) else set()
+            slots = torch.zeros(len(keyed) + 1, dtype=torch.float32, device=x.device) if screened else None
+            if slots is not None and 0 in screened:
+                klayer._absmax_into(x.detach().t().float(), slots[0:1])
             y = x
             for (k, c, relu) in self._steps():
-                y = _relu_block(y) if k is None else c.forward(y, fuse_relu=relu, narrow=True)
-        return y if img_cipher.is_cuda else y.to(img_cipher.device)
+                if k is None:
+                    y = _relu_block(y)
+                else:
+                    y = c.forward(y, fuse_relu=relu, narrow=mode, absmax=slots[k + 1:k + 2] if (slots is not None and (k + 1) in screened) else None)
+            if slots is None:
+                break
+            screens = [(slots, screened)]
+            if not read or not self._rescreen(slots.tolist(), keyed, screened, narrow=True):
+                break
+        return (y if img_cipher.is_cuda else y.to(img_cipher.device), screens)
 
     def _prepare(self, x):
         """What the kernels get to see: (x, windows), the image ranges of the passes.  A host batch goes to the device ONCE (the layers chain
@@ -288,16 +314,24 @@ class KeyedModel(object):
                 todo = [k] + [j for j in range(len(windows)) if j != k]
         return (ys[0] if len(ys) == 1 else torch.cat([y.t() for y in ys], dim=1).t(), screens)
 
-    def _rescreen(self, xmax, keyed, screened):
+    def _rescreen(self, xmax, keyed, screened, narrow=False):
         """Host side of the per-forward screen: layers whose input magnitude has outgrown their calibration go back to 'auto' (decided
-        again by the next forward, on that batch).  Returns their indices."""
-        redo = [k for k in sorted(screened) if keyed[k].rescreen(xmax[k])]
+        again by the next forward, on that batch).  Returns their indices.  `narrow`: the screen of a narrow='mfma' forward -- against the layers' NARROW
+        records; an outgrown one is dropped (measured again by the next narrow='mfma' pass, on that batch), the wide decision and the launch lists stay."""
+        redo = [k for k in sorted(screened) if keyed[k].rescreen(xmax[k], narrow=narrow)]
         for k in redo:
             c = keyed[k]
-            klayer._log.info('keynet_amd: %s: max |x| = %.3g against %.3g at calibration: re-calibrating on this batch', c._repr, xmax[k], c._contract_record['max_abs_x'])
+            rec = c._contract_record['narrow'] if narrow else c._contract_record
+            klayer._log.info('keynet_amd: %s: max |x| = %.3g against %.3g at %s: re-calibrating on this batch', c._repr, xmax[k], rec['max_abs_x'],
+                             'its narrow measurement' if narrow else 'calibration')
+            if narrow:
+                c._contract_record.pop('narrow', None)
+                continue
             c._exact = 'auto'
             c.__dict__.pop('_contract_record', None)
-        if redo:
+        if redo and narrow:
+            self.__dict__['_narrow_remeasurements'] = self.__dict__.get('_narrow_remeasurements', 0) + len(redo)
+        elif redo:
             self.__dict__['_recalibrations'] = self.__dict__.get('_recalibrations', 0) + len(redo)
             self._drop_plans()
         return redo
@@ -537,9 +571,10 @@ class KeyedModel(object):
         """Per keyed layer: the contract in force (True / False / 'auto' = not decided yet) and, for layers decided by calibration, the
         record of that decision (bound, measured difference, tolerance, max |x| it covers).  `switched` lists the layers calibration moved
         off the matrix cores; `rescreen` says whether every forward re-checks the decisions; `recalibrations` counts the layers a later,
-        larger batch sent back to calibration."""
+        larger batch sent back to calibration.  `narrow` per layer: the record of its narrow='mfma' measurement (KeyedLayer.narrow_mode; also inside
+        `calibration`), None for layers that have none."""
         rows = [dict(name=n, exact=getattr(c, '_exact', True), declared=getattr(c, '_exact_decl', getattr(c, '_exact', True)),
-                     calibration=getattr(c, '_contract_record', None), screened=c.screened()) for (n, c) in self._keyed(named=True)]
+                     calibration=getattr(c, '_contract_record', None), screened=c.screened(), narrow=c.narrow_record()) for (n, c) in self._keyed(named=True)]
         return dict(layers=rows, switched=[r['name'] for r in rows if r['calibration'] is not None and r['calibration'].get('decided') == 'exact' and 'bound' in r['calibration']],
                     undecided=[r['name'] for r in rows if r['exact'] == 'auto'],
                     rescreen=bool(self.RESCREEN and any(r['screened'] for r in rows)),
@@ -590,11 +625,14 @@ class KeyedModel(object):
         screen: the graph gathers max |x| per layer like the eager forward, replay() reads it back after the launch and, when a layer's input has
         outgrown its calibration, re-runs the batch eagerly (re-calibrating) and captures a new graph.
         `narrow=True` (at most NARROW_MAX images): the graph of forward_linear(narrow=True) -- a straight line of launches on one stream, no parallel
-        branches; nothing is screened (the conv layers run the reference's own arithmetic), so replay() reads nothing back."""
+        branches; nothing is screened (the conv layers run the reference's own arithmetic), so replay() reads nothing back.
+        `narrow='mfma'`: the graph of forward_linear(narrow='mfma'), decided by one eager forward first; still one stream, no parallel branches.  With layers on the
+        matrix-core narrow kernel by a measurement the graph gathers their max |x|, replay() reads the slots after the launch and on a trip runs the batch eagerly
+        (measuring again) and captures a new graph, as the wide capture does; with no such layer it reads nothing."""
         assert img_cipher.is_cuda, 'capture() needs a device tensor'
         n = img_cipher.shape[0]
         if narrow:
-            return self._capture_narrow(img_cipher)
+            return self._capture_narrow(img_cipher, narrow)
         (static_in, windows) = self._prepare(img_cipher.detach().t().clone(memory_format=torch.contiguous_format).t())     # the graph's own input block
         keyed = self._keyed()
         state = {}
@@ -627,33 +665,45 @@ class KeyedModel(object):
         replay.graph = state['graph']
         return replay
 
-    def _capture_narrow(self, img_cipher):
-        """capture(narrow=True): one eager narrow forward (operators resident), a warm-up on the capture stream (per-stream state of the operators), then the capture."""
+    def _capture_narrow(self, img_cipher, mode=True):
+        """capture(narrow=True | 'mfma'): one eager narrow forward (operators resident, narrow records measured), a warm-up on the capture stream (per-stream state
+        of the operators), then the capture."""
         if img_cipher.shape[0] > self.NARROW_MAX:
-            raise ValueError('narrow=True takes at most %d images, got %d' % (self.NARROW_MAX, img_cipher.shape[0]))
+            raise ValueError('narrow=%r takes at most %d images, got %d' % (mode, self.NARROW_MAX, img_cipher.shape[0]))
         static_in = img_cipher.detach().float().t().clone(memory_format=torch.contiguous_format).t()      # the graph's own feature-major input block
-        self._forward_narrow(static_in)
-        torch.cuda.synchronize()
-        side = torch.cuda.Stream()
-        side.wait_stream(torch.cuda.current_stream())
-        with torch.cuda.stream(side):
-            self._forward_narrow(static_in)
-        torch.cuda.current_stream().wait_stream(side)
-        graph = torch.cuda.CUDAGraph()
-        with torch.cuda.graph(graph, stream=side):
-            out = self._forward_narrow(static_in)
+        keyed = self._keyed()
+        state = {}
+
+        def build():
+            self._forward_narrow(static_in, mode)
+            torch.cuda.synchronize()
+            side = torch.cuda.Stream()
+            side.wait_stream(torch.cuda.current_stream())
+            with torch.cuda.stream(side):
+                self._forward_narrow(static_in, mode)
+            torch.cuda.current_stream().wait_stream(side)
+            graph = torch.cuda.CUDAGraph()
+            with torch.cuda.graph(graph, stream=side):
+                (out, screens) = self._forward_narrow(static_in, mode)
+            state.update(graph=graph, out=out, screens=screens)
+
+        build()
 
         def replay(x):
             static_in.copy_(x)
-            graph.replay()
-            return out
-        replay.graph = graph
+            state['graph'].replay()
+            if any(self._rescreen(slots.tolist(), keyed, screened, narrow=True) for (slots, screened) in state['screens']):
+                build()                                          # the eager forward on this batch measures again; then a fresh graph
+                state['graph'].replay()
+            replay.graph = state['graph']
+            return state['out']
+        replay.graph = state['graph']
         return replay
 
     def forward(self, img_cipher, outkey=None, narrow=False):
         """Encrypted image(s) [N, D0+1] -> logits.  N == 1 returns the reference's shape `outshape` = (C,1,1)
-        (keynet/system.py:130-133); N > 1 (an extension: the reference cannot) returns (N, C, 1, 1).  `narrow`: forward_linear(narrow=True), the
-        low-latency form of this very call for 1 .. NARROW_MAX images."""
+        (keynet/system.py:130-133); N > 1 (an extension: the reference cannot) returns (N, C, 1, 1).  `narrow`: forward_linear(narrow=True | 'mfma'), the
+        low-latency forms of this very call for 1 .. NARROW_MAX images."""
         outkey = outkey if outkey is not None else self.embeddingkey()
         y = self.forward_linear(img_cipher, narrow=narrow)
         if outkey is not None:

@@ -1,7 +1,7 @@
 #!/usr/bin/env python
 """Latency of the low-latency (narrow) forward against the padded forward, on ONE key-net in ONE process.
 
-    python tools/narrow_latency.py [--workload vgg16|allconv] [--forwards 20] [--warmup 3] [--out profiles/r07_narrow_forward.txt]
+    python tools/narrow_latency.py [--workload vgg16|allconv] [--forwards 20] [--warmup 3] [--out FILE]         # default profiles/r07_narrow_forward.txt
     python tools/narrow_latency.py --one-forward [-n 1]        # keys, warms up, then runs ONE narrow forward: the program for a kernel trace
                                                                # (rocprofv3 --kernel-trace --stats -- python tools/narrow_latency.py --one-forward)
 
@@ -9,7 +9,19 @@ Keys the headline workload (benchlegs.workloads: TiledPermutationKeynet VGG-16, 
 AllConvNet, whose conv layers are factored stand-ins) and, for n in (1, 2, 4, 8) images, times three forwards of the SAME images on that key-net:
 forward_linear(x) (padded to 128 images: the code path of every earlier release), forward_linear(x, narrow=True) eager, and the replay of
 capture(x, narrow=True).  HIP events around each forward, a warm-up, the median over --forwards forwards (min and max beside it).  The narrow logits must be
-torch.equal to the padded ones before any time is printed.  Prints one table and appends it to --out."""
+torch.equal to the padded ones before any time is printed.  Prints one table and appends it to --out.
+
+    python tools/narrow_latency.py --mfma [--out profiles/r08_narrow_mfma.txt]
+    python tools/narrow_latency.py --mfma --one-forward          # the program for a kernel trace: for n in (1, 2, 4, 8) ONE narrow=True forward, then ONE
+                                                                 # narrow='mfma' forward (rocprofv3 --kernel-trace --stats --output-format csv -d DIR -- python ...)
+    python tools/narrow_latency.py --from-trace DIR/.../*_kernel_trace.csv [--convs 13] [--out ...]   # no GPU: the conv launches of those forwards, layer by layer
+
+--mfma: the same key-net under exact_mode('auto') after ONE calibrating wide forward (every conv layer of the permutation-keyed VGG-16 stays on the matrix
+cores), three forwards of the same images in this one process: padded, narrow=True (the channel-lane kernel), narrow='mfma' (the matrix-core narrow kernel,
+measured and accepted layer by layer on the first call), and the gate ratios of the narrow records (the measured distance between the two narrow
+arithmetics).  The narrow='mfma' logits must be inside the float-key gate against narrow=True before any time is printed.  The times of the conv LAUNCHES
+themselves (no Python, no launch overhead, no screen reduction) come from the kernel trace: --from-trace reads the device timestamps of the last eight
+forwards of a --mfma --one-forward run and prints every conv launch of both kernels beside each other, and their sums."""
 import argparse
 import os
 import statistics
@@ -39,15 +51,97 @@ def timed(fn, forwards, warmup):
     return out
 
 
+def mfma_table(args, knet, xc, desc):
+    """--mfma: see the module docstring."""
+    from keynet_amd import sparse as ksp
+    from keynet_amd.layer import gate
+    knet.exact_mode('auto')
+    knet.forward_linear(xc)                       # the calibrating wide forward (8 images, padded to 128)
+    rep = knet.contract_report()
+    convs = [(name, c) for (name, c) in knet._keyed(named=True) if isinstance(c.W, ksp.Conv2dTiledMatrix)]
+    wide = dict((r['name'], r['exact']) for r in rep['layers'])
+    if args.one_forward:
+        for n in (1, 2, 4, 8):                    # operators resident, narrow records measured
+            knet.forward_linear(xc[:n].t().contiguous().t(), narrow='mfma')
+        torch.cuda.synchronize()
+        print("TRACE-FROM-HERE: for n in (1, 2, 4, 8) one narrow=True forward, then one narrow='mfma' forward; %d conv layers" % len(convs), flush=True)
+        for n in (1, 2, 4, 8):
+            x = xc[:n].t().contiguous().t()
+            knet.forward_linear(x, narrow=True)
+            knet.forward_linear(x, narrow='mfma')
+            torch.cuda.synchronize()
+        return
+    out = args.out or os.path.join(ROOT, 'profiles', 'r08_narrow_mfma.txt')
+    lines = ['', "== tools/narrow_latency.py --mfma: %s under exact_mode('auto') after one calibrating wide forward" % desc,
+             '   %s, torch %s; HIP events, %d warm-up + median of %d forwards (min .. max)' % (torch.cuda.get_device_name(0), torch.__version__, args.warmup, args.forwards),
+             '   conv layers left on the matrix cores by calibration: %d of %d' % (sum(1 for (name, _) in convs if wide[name] is False), len(convs)),
+             '   %6s | %-28s | %-28s | %-28s | %s' % ('images', 'padded forward_linear [ms]', 'narrow=True [ms]', "narrow='mfma' [ms]", "narrow=True / narrow='mfma'")]
+    for n in (1, 2, 4, 8):
+        x = xc[:n].t().contiguous().t()
+        ye = knet.forward_linear(x, narrow=True)
+        ym = knet.forward_linear(x, narrow='mfma')
+        torch.cuda.synchronize()
+        ratio = gate(ym, ye)[0]
+        assert ratio <= 1.0, "narrow='mfma' logits outside the float-key gate against narrow=True at %d image(s): %g" % (n, ratio)
+        t = [timed(lambda: knet.forward_linear(x), args.forwards, args.warmup),
+             timed(lambda: knet.forward_linear(x, narrow=True), args.forwards, args.warmup),
+             timed(lambda: knet.forward_linear(x, narrow='mfma'), args.forwards, args.warmup)]
+        v = [(statistics.median(u), min(u), max(u)) for u in t]
+        cell = ['%8.3f (%.3f .. %.3f)' % u for u in v]
+        lines.append('   %6d | %-28s | %-28s | %-28s | %.2fx   (logits: gate ratio %.3g)' % (n, cell[0], cell[1], cell[2], v[1][0] / v[2][0], ratio))
+        print('n = %d done' % n, flush=True)
+    lines.append('')
+    lines.append("   narrow records (the measured distance between the two narrow arithmetics: worst element's share of its tolerance 1e-5 + 1e-5 |ref|):")
+    for r in knet.contract_report()['layers']:
+        if r['narrow'] is not None:
+            lines.append('     %-12s decided %-5s gate ratio %-10.3g max |x| %-10.3g on %d column(s)' % (r['name'], r['narrow']['decided'], r['narrow']['gate_ratio'] or 0.0, r['narrow']['max_abs_x'] or 0.0, r['narrow']['measured_on_columns']))
+    text = '\n'.join(lines) + '\n'
+    print(text)
+    with open(out, 'a') as f:
+        f.write(text)
+
+
+def trace_table(args):
+    """--from-trace: the conv launches of the last eight forwards of a `--mfma --one-forward` run under rocprofv3 --kernel-trace (device timestamps)."""
+    import csv
+    with open(args.from_trace, newline='') as f:
+        rows = [r for r in csv.DictReader(f) if 'convtaps_narrow' in r['Kernel_Name']]
+    rows.sort(key=lambda r: int(r['Start_Timestamp']))
+    k = args.convs
+    assert len(rows) >= 8 * k, 'the trace holds %d narrow conv launches, fewer than 8 forwards of %d' % (len(rows), k)
+    rows = rows[-8 * k:]
+    lines = ['', '== tools/narrow_latency.py --from-trace: the conv launches of one narrow=True and one narrow=\'mfma\' forward (rocprofv3 --kernel-trace, device timestamps)']
+    for (i, n) in enumerate((1, 2, 4, 8)):
+        (lane, mfma) = (rows[(2 * i) * k:(2 * i + 1) * k], rows[(2 * i + 1) * k:(2 * i + 2) * k])
+        assert all('mfma' not in r['Kernel_Name'] for r in lane), 'the narrow=True forward launched a matrix-core kernel'
+        lines.append('')
+        lines.append('   %d image(s) [us]: conv launch | workgroups | channel-lane | narrow=\'mfma\' | ratio | kernel of the narrow=\'mfma\' forward' % n)
+        us = lambda r: (int(r['End_Timestamp']) - int(r['Start_Timestamp'])) / 1e3
+        for (j, (a, b)) in enumerate(zip(lane, mfma)):
+            lines.append('     %2d | %6d | %9.1f | %9.1f | %5.2fx | %s' % (j + 1, int(b.get('Grid_Size_X') or 0) // max(1, int(b.get('Workgroup_Size_X') or 1)), us(a), us(b), us(a) / us(b),
+                                                                  'matrix-core' if 'mfma' in b['Kernel_Name'] else 'channel-lane'))
+        (sa, sb) = (sum(us(r) for r in lane), sum(us(r) for r in mfma))
+        lines.append('     sum of the %d conv launches: %9.1f | %9.1f | %5.2fx' % (k, sa, sb, sa / sb))
+    text = '\n'.join(lines) + '\n'
+    print(text)
+    with open(args.out or os.path.join(ROOT, 'profiles', 'r08_narrow_mfma.txt'), 'a') as f:
+        f.write(text)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument('--workload', default='vgg16', choices=['vgg16', 'allconv'])
     ap.add_argument('--forwards', type=int, default=20)
     ap.add_argument('--warmup', type=int, default=3)
-    ap.add_argument('--out', default=os.path.join(ROOT, 'profiles', 'r07_narrow_forward.txt'))
+    ap.add_argument('--out', default=None, help='the file the table is appended to (default: profiles/r07_narrow_forward.txt, with --mfma or --from-trace profiles/r08_narrow_mfma.txt)')
+    ap.add_argument('--from-trace', default=None, help='a *_kernel_trace.csv of a --mfma --one-forward run: print its conv launches, layer by layer (no GPU)')
+    ap.add_argument('--convs', type=int, default=13, help='conv layers per forward in --from-trace')
     ap.add_argument('--one-forward', action='store_true', help='key, warm up, run one narrow forward and exit (for a kernel trace)')
     ap.add_argument('-n', type=int, default=1, help='images of --one-forward')
+    ap.add_argument('--mfma', action='store_true', help="exact_mode('auto') after one calibrating wide forward: padded, narrow=True, narrow='mfma'")
     args = ap.parse_args()
+    if args.from_trace:
+        return trace_table(args)
     assert args.forwards >= 20 or args.one_forward, 'the median of at least 20 forwards'
     t0 = time.time()
     (sensor, knet, inshape, _, desc, _) = workloads.build_workload(args.workload, 0, fanout=True)
@@ -57,6 +151,8 @@ def main():
     xc = sensor.fromtensor(imgs.to(dev)).encrypt().astensor()
     xc = xc.t().contiguous().t()                  # feature-major, as the layers hand blocks on
     print('keyed %s in %.0f s' % (desc, time.time() - t0), flush=True)
+    if args.mfma:
+        return mfma_table(args, knet, xc, desc)
     if args.one_forward:
         x = xc[:args.n].t().contiguous().t()
         knet.forward_linear(x, narrow=True)       # operators resident
@@ -92,7 +188,7 @@ def main():
         lines.append('   %6d | %-28s | %-28s | %-28s | %.2fx, %.2fx' % (n, cell[0], cell[1], cell[2], t[0][0] / t[1][0], t[0][0] / t[2][0]))
     text = '\n'.join(lines) + '\n'
     print(text)
-    with open(args.out, 'a') as f:
+    with open(args.out or os.path.join(ROOT, 'profiles', 'r07_narrow_forward.txt'), 'a') as f:
         f.write(text)
 
 
