@@ -76,6 +76,21 @@ enum kn_status {
                               ineligible operator, on any other operator kind, at n_vecs > 8 (ignored).  Same size rule and refusal as KN_FLAG_NARROW.  kn_spmm_plan names
                               the kernel, its tile and NV.  No reference counterpart. */
 
+#define KN_FLAG_NARROW_ROWS 32u  /* low-latency form of the float32 CSR operators for 1 .. 8 batch columns.  An opt-in of its own: KN_FLAG_NARROW and KN_FLAG_NARROW_MFMA
+                              stay ignored by CSR handles, and this flag is ignored by conv-taps handles.
+                              What runs.  For n_vecs <= 8 a float32 CSR handle (kn_csr_create, kn_tiled_create) runs csr_narrow_kernel on its pattern groups and loose rows.
+                              The lane is the OUTPUT ROW and the batch columns are its NV = 1 | 2 | 4 | 8 running sums.  The walk over a row's stored columns is serial, in
+                              stored order, with separate multiply and add: bit for bit the result without the flag.  Long loose rows (>= 1 024 entries) and the patched-row
+                              guard run as without the flag.  So do the loose rows of an operator whose longest loose row holds more than 64 entries.
+                              Where it is IGNORED (same kernels, same plan string, same bits as without it; the call falls back, it does not refuse):
+                                - at n_vecs > 8;
+                                - by conv-taps, dense, float64 and chain handles, and by kn_spmm_planes;
+                                - where the kernel's 32-bit byte offsets into X would not hold (it runs while cols * ldx + 8 < 2^30);
+                                - on the shape measured slower than the kernels it has: an operator with a keyed Linear's big pattern group (>= 256 rows over >= 2 048 shared
+                                  columns) at more than 2 columns (profiles/r09_narrow_rows.txt).
+                              Honoured by kn_spmm, by kn_spmm_screen (max |Y| by the library's reduction pass over Y) and by kn_spmm_plan, which names the kernel, NV and the
+                              rows-per-wavefront form.  No reference counterpart. */
+
 typedef struct kn_operator* kn_handle_t;   /* opaque keyed operator resident in HBM */
 
 int         kn_abi_version(void);
@@ -197,6 +212,7 @@ int kn_export_csr_f64(kn_handle_t h, int32_t* indptr, int32_t* indices, double* 
  *                                                       straight-line loaders: 16 * HiWi * ldx < 2^31 (4 * for Cin < 16); else the generic loader
  *   conv-taps, KN_FLAG_EXACT, pipelined kernel          (D + 1) * ldx < 2^31                               else the plain order-preserving kernel
  *   conv-taps, KN_FLAG_EXACT, filled-in operators       4 * ldx < 2^24, 4 * HiWi * ldx < 2^32, HiWi < 2^24  else the plain order-preserving kernel
+ *   CSR, KN_FLAG_NARROW_ROWS (n_vecs <= 8)               cols * ldx + 8 < 2^30                              else the kernels the call takes without the flag
  * The small-K matrix-core kernels of first-layer operators (slots * Cin + bias <= 28 contraction rows) form row * ldx in 64 bits and take any ldx.
  * KN_FLAG_NARROW / KN_FLAG_NARROW_MFMA (n_vecs <= 8 on a conv-taps operator) do NOT fall back: they return KN_ERR_UNSUPPORTED, Y untouched, unless (D + 1) * ldx + 8 < 2^31.
  * kn_spmm_plan names the kernel a call takes; tests/test_large_offsets_gpu.py runs each of these on both sides of its threshold. */

@@ -522,7 +522,7 @@ __global__ __launch_bounds__(256) void csr_big_group_kernel(int64_t n_big, const
 void csr_free(CsrDev& c) {
     void* ptrs[] = {c.indptr, c.indices, c.data, c.data64, c.grp_colptr, c.grp_cols, c.grp_rowptr, c.grp_rows, c.grp_valptr, c.grp_vals,
                     c.work_grp, c.work_r0, c.loose_rows, c.big_grp, c.big_r0, c.long_rows, c.patch_rows, c.patch_ptr, c.patch_cols,
-                    c.mf_grp[0], c.mf_grp[1], c.mf_grp[2], c.mf_r0[0], c.mf_r0[1], c.mf_r0[2], c.ws_grp, c.ws_r0, c.mf16_grp, c.mf16_r0};
+                    c.mf_grp[0], c.mf_grp[1], c.mf_grp[2], c.mf_r0[0], c.mf_r0[1], c.mf_r0[2], c.ws_grp, c.ws_r0, c.mf16_grp, c.mf16_r0, c.nr_grp, c.nr_r0};
     for (void* p : ptrs)
         if (p) (void)hipFree(p);
     c = CsrDev();
@@ -604,7 +604,7 @@ int csr_build_groups(kn_operator* h, const int32_t* indptr, const int32_t* indic
         }
     }
     std::vector<int32_t> patch_rows, patch_ptr{0}, patch_cols;
-    std::vector<int32_t> colptr{0}, cols, rowptr{0}, grows, wgrp, wr0, bgrp, br0, loose, mfg[3], mfr[3], wsg, wsr, m16g, m16r;
+    std::vector<int32_t> colptr{0}, cols, rowptr{0}, grows, wgrp, wr0, bgrp, br0, loose, mfg[3], mfr[3], wsg, wsr, m16g, m16r, nrg, nrr;
     int64_t mf_rows = 0, mf_nnz = 0;
     std::vector<int64_t> valptr{0};
     std::vector<float> vals;
@@ -649,6 +649,10 @@ int csr_build_groups(kn_operator* h, const int32_t* indptr, const int32_t* indic
             in_group[(size_t)r] = 1;
         }
         valptr.push_back((int64_t)vals.size());
+        for (int64_t r0 = 0; r0 < n_mem; r0 += 64) {                           // every group in 64-row chunks for the row-lane kernel (1 .. 8 batch columns)
+            nrg.push_back(gid);
+            nrr.push_back((int32_t)r0);
+        }
         if (n_mem >= 256 && ncol >= 2048 && !A.tune.no_big_groups) {      // a keyed nn.Linear: LDS-staged kernel, 32 rows per workgroup
             for (int64_t r0 = 0; r0 < n_mem; r0 += BIG_ROWS) {
                 bgrp.push_back(gid);
@@ -686,6 +690,7 @@ int csr_build_groups(kn_operator* h, const int32_t* indptr, const int32_t* indic
         }
         grouped_nnz += n_mem * ncol;
     }
+    int rc;
     std::vector<int32_t> longrows;
     const bool use_long = !A.tune.no_big_groups;
     for (int64_t r = 0; r < rows; r++)
@@ -699,6 +704,11 @@ int csr_build_groups(kn_operator* h, const int32_t* indptr, const int32_t* indic
         for (int32_t r : loose) lnnz += indptr[r + 1] - indptr[r];
         if (lnnz <= 64 * (int64_t)loose.size()) loose = locality_order(loose, indptr, indices, h->cols, 64, 64);
     }
+    for (int32_t r : loose) A.loose_max = std::max<int64_t>(A.loose_max, indptr[r + 1] - indptr[r]);
+    cols.resize(cols.size() + NARROW_ROWS_COL_PAD, 0);        // the row-lane kernel's scalar look-ahead reads past a group's sequence (column 0: a valid row of X)
+    A.n_nr = (int64_t)nrg.size();
+    if ((rc = upload(&A.nr_grp, nrg.data(), nrg.size()))) return rc;
+    if ((rc = upload(&A.nr_r0, nrr.data(), nrr.size()))) return rc;
     A.n_groups = (int64_t)colptr.size() - 1;
     A.n_work = (int64_t)wgrp.size();
     A.n_big = (int64_t)bgrp.size();
@@ -706,7 +716,6 @@ int csr_build_groups(kn_operator* h, const int32_t* indptr, const int32_t* indic
     A.n_loose = (int64_t)loose.size();
     A.grouped_nnz = grouped_nnz;
     A.n_patch = (int64_t)patch_rows.size();
-    int rc;
     if ((rc = upload(&A.patch_rows, patch_rows.data(), patch_rows.size()))) return rc;
     if ((rc = upload(&A.patch_ptr, patch_ptr.data(), patch_ptr.size()))) return rc;
     if ((rc = upload(&A.patch_cols, patch_cols.data(), patch_cols.size()))) return rc;
@@ -1033,11 +1042,30 @@ __global__ __launch_bounds__(256) void csr_patch_guard_kernel(int64_t n_patch, c
 
 static int csr_spmm_groups(const CsrDev& A, const float* x, int64_t ldx, int64_t n_vecs, float* y, int64_t ldy, uint32_t flags, hipStream_t s, float* rows_only_absmax = nullptr);
 
+// KN_FLAG_NARROW_ROWS on 1 .. 8 columns: the long loose rows in the deep-queue role of the big-group launch, as without the flag; loose rows too long for a lane
+// (narrow_rows_loose) on csr_rows_kernel, as without the flag; everything else in one launch of the row-lane kernel.  csr_spmm adds the patch guard.
+static int csr_spmm_row_lanes(const CsrDev& A, const float* x, int64_t ldx, int64_t n_vecs, float* y, int64_t ldy, uint32_t flags, hipStream_t s) {
+    const int relu = (flags & KN_FLAG_RELU) ? 1 : 0;
+    if (A.n_long > 0) {
+        KN_LAUNCH("csr_big_group_kernel (long rows)", csr_big_group_kernel, dim3((unsigned)A.n_long), dim3(256), 0, s, (int64_t)0, A.big_grp, A.big_r0, A.grp_colptr, A.grp_cols, A.grp_rowptr,
+                  A.grp_rows, A.grp_valptr, A.grp_vals, x, ldx, y, ldy, n_vecs, relu, (int64_t)0, A.long_rows, A.n_long, A.indptr, A.indices, A.data);
+        KN_HIP(hipGetLastError());
+    }
+    const bool loose = narrow_rows_loose(A);
+    if (!loose && A.n_loose > 0) {
+        CsrDev R = A;                                    // (a view: the loose rows only)
+        R.n_work = 0;
+        if (int rc = launch_csr<1, 8>(R, x, ldx, n_vecs, y, ldy, relu, s)) return rc;
+    }
+    return csr_narrow_rows_spmm(A, x, ldx, n_vecs, y, ldy, relu, loose, s);
+}
+
 int csr_spmm(const CsrDev& A, const float* x, int64_t ldx, int64_t n_vecs, float* y, int64_t ldy, uint32_t flags, hipStream_t s, float* absmax, bool* absmax_fused) {
     // an operator of loose rows only (keyed pooling) is ONE launch of a row kernel: max |Y| (kn_spmm_screen) rides in its epilogue
-    const bool rows_only = A.n_work == 0 && A.n_big == 0 && A.n_long == 0 && A.n_patch == 0 && A.n_loose > 0;
+    const bool row_lanes = narrow_rows_call(A, flags, n_vecs, ldx);       // KN_FLAG_NARROW_ROWS: max |Y| comes from the caller's reduction pass, as behind the other narrow kernels
+    const bool rows_only = !row_lanes && A.n_work == 0 && A.n_big == 0 && A.n_long == 0 && A.n_patch == 0 && A.n_loose > 0;
     if (absmax_fused) *absmax_fused = absmax != nullptr && rows_only;
-    const int rc = csr_spmm_groups(A, x, ldx, n_vecs, y, ldy, flags, s, rows_only ? absmax : nullptr);
+    const int rc = row_lanes ? csr_spmm_row_lanes(A, x, ldx, n_vecs, y, ldy, flags, s) : csr_spmm_groups(A, x, ldx, n_vecs, y, ldy, flags, s, rows_only ? absmax : nullptr);
     if (rc != KN_OK || A.n_patch == 0) return rc;
     const int64_t n_ct = (n_vecs + 255) / 256;
     KN_LAUNCH("csr_patch_guard_kernel<" + std::to_string(A.n_patch) + " patched rows>", csr_patch_guard_kernel, dim3((unsigned)(A.n_patch * n_ct)), dim3(256), 0, s, A.n_patch,

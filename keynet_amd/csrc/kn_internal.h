@@ -203,7 +203,13 @@ struct CsrDev {
     int64_t n_long = 0;
     int32_t* loose_rows = nullptr;
     int64_t n_loose = 0;
+    int64_t loose_max = 0;           // stored entries of the longest loose row (long rows are not loose rows)
     int64_t grouped_nnz = 0;
+    // the row-lane kernel for 1 .. 8 batch columns (kn_csr_narrow.hip, KN_FLAG_NARROW_ROWS): EVERY pattern group, the big ones included, in chunks of 64
+    // member rows (a last chunk may be partly filled); grp_cols carries NARROW_ROWS_COL_PAD entries of padding for its look-ahead
+    int32_t* nr_grp = nullptr;
+    int32_t* nr_r0 = nullptr;
+    int64_t n_nr = 0;
     // PATCHED group members: rows whose stored column sequence is a group's sequence minus a few entries (a keyed conv row that lost a weight to an
     // exact zero) ride in the group with 0.0f at the missing positions; csr_patch_guard_kernel recomputes them in the reference's own sequence for
     // the batch columns whose activation at a missing position is not finite (see kn_csr.hip)
@@ -341,6 +347,25 @@ static inline bool narrow_mfma_loses(const ConvTapsDev& A, int64_t n_vecs) {
 static inline bool narrow_mfma_call(const ConvTapsDev& A, uint32_t flags, int64_t n_vecs) {
     return (flags & KN_FLAG_NARROW_MFMA) && !(flags & KN_FLAG_EXACT) && n_vecs <= NARROW_MAX_VECS && A.pt_ok && !narrow_mfma_loses(A, n_vecs);
 }
+// KN_FLAG_NARROW_ROWS: an f32 CSR operator's pattern groups and loose rows on the row-lane kernel (kn_csr_narrow.hip) for at most NARROW_MAX_VECS columns, while the
+// kernel's 32-bit BYTE offsets into X hold; else the flag is ignored (the other kernels give the same bits).  The one place that reads the flag.
+static constexpr int NARROW_ROWS_COL_PAD = 80;
+// The SHAPES that stay on the existing kernels (measured, profiles/r09_narrow_rows.txt): an operator with BIG pattern groups -- a keyed Linear, >= 256 rows over >= 2 048
+// shared columns -- at more than two columns.  Its wavefronts sit alone on their SIMDs, the bytes in flight are bounded by the 48-step value rings, and each step's
+// activations are a scalar-cache round trip that only 16 / NV steps of arithmetic cover, while csr_big_group_kernel carries 64 columns per lane for the price of one.
+// Inside a VGG-16 forward (kernel trace, values cold): fc6 1.91x at 1 image and 1.42x at 2; fc7 1.86x / 1.39x, fc8 1.78x / 1.33x; at 4 images fc7 0.94x and fc8 0.91x
+// (alone on a warm block 1.19x / 1.12x: not what a forward sees); alone: fc6 0.88x at 4 and 0.47x at 8, fc7 / fc8 0.95x / 0.93x at 3 (masked form) and 0.67x / 0.65x at 8.
+// Operators without big groups (pools: 1.46x .. 5.1x at every width 1 .. 8; conv-like groups: not measured) keep the kernel.
+static inline bool narrow_rows_loses(const CsrDev& A, int64_t n_vecs) { return A.n_big > 0 && n_vecs > 2; }
+static inline bool narrow_rows_call(const CsrDev& A, uint32_t flags, int64_t n_vecs, int64_t ldx) {
+    return (flags & KN_FLAG_NARROW_ROWS) && n_vecs <= NARROW_MAX_VECS && A.cols * ldx + NARROW_MAX_VECS < ((int64_t)1 << 30) && !narrow_rows_loses(A, n_vecs);
+}
+// Loose rows take a LANE each in that kernel, which walks a row with two dependent loads per four entries and nothing else in flight: right for pools and
+// homogeneous rows (a handful of entries), wrong for a long ragged row, which csr_rows_kernel walks 64 entries at a time with a whole wavefront.  An operator
+// whose longest loose row holds more entries than this keeps csr_rows_kernel for its loose rows (its pattern groups still take the row-lane kernel).
+static constexpr int64_t NARROW_ROWS_LOOSE_MAX = 64;
+static inline bool narrow_rows_loose(const CsrDev& A) { return A.loose_max <= NARROW_ROWS_LOOSE_MAX; }
+int csr_narrow_rows_spmm(const CsrDev& A, const float* x, int64_t ldx, int64_t n_vecs, float* y, int64_t ldy, int relu, bool loose, hipStream_t s);      // kn_csr_narrow.hip
 int convtaps_spmm(const ConvTapsDev& A, const float* x, int64_t ldx, int64_t n_vecs, float* y, int64_t ldy,
                   uint32_t flags, hipStream_t s, float* absmax = nullptr, bool* absmax_fused = nullptr);
 int absmax_pass(const float* y, int64_t rows, int64_t ld, int64_t n_vecs, float* absmax, hipStream_t s);

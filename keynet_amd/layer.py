@@ -209,7 +209,7 @@ class KeyedLayer(nn.Module):
     def iskeyedrelu(self):
         return 'ReLU' in self._layertype
 
-    def forward(self, x_affine, fuse_relu=False, absmax=None, narrow=False):
+    def forward(self, x_affine, fuse_relu=False, absmax=None, narrow=False, narrow_rows=False):
         """[N, Din+1] -> [N, Dout+1] (keynet/layer.py:88-93).  The result is a transposed view of the feature-major
         [Dout+1, N] block the kernel wrote, so the next layer's x.t() is free.  `fuse_relu` folds the unkeyed nn.ReLU
         that follows this layer in the key-net (keynet/system.py:92) into the kernel epilogue.  `absmax`: a one-element device
@@ -219,7 +219,9 @@ class KeyedLayer(nn.Module):
         `narrow` (at most KeyedModel.NARROW_MAX images): a conv-taps layer runs the channel-lane order-preserving kernel (KN_FLAG_NARROW) whatever its
         contract is -- the reference's own arithmetic, which satisfies every contract: nothing is calibrated, screened or decided; other layers run as usual.
         `narrow='mfma'`: the matrix-core narrow kernel (KN_FLAG_NARROW_MFMA) where this layer's contract in force allows re-ordered sums (narrow_mode():
-        declared -> always; decided by calibration -> measured once on the first such batch, recorded under _contract_record['narrow']); else narrow=True."""
+        declared -> always; decided by calibration -> measured once on the first such batch, recorded under _contract_record['narrow']); else narrow=True.
+        `narrow_rows` (with `narrow`): a layer whose operator is a float32 CSR handle (W.rows_capable()) runs its stored-order product on the row-lane kernel
+        (KN_FLAG_NARROW_ROWS, kernel()) -- the same bits; conv-taps layers and everything else are what `narrow` alone makes them.  Nothing is decided or recorded."""
         if verbose():
             print('[keynet_amd.layer]: forward %s' % str(self))
         exact = getattr(self, '_exact', True)
@@ -237,10 +239,12 @@ class KeyedLayer(nn.Module):
             if absmax is not None:
                 _absmax_into(y.t(), absmax)
             return y
+        if narrow and narrow_rows and self.W.rows_capable():
+            return self.W.torchdot(x_affine.t(), relu=(fuse_relu or self.iskeyedrelu()), exact=exact, absmax=absmax, narrow_rows=True).t()
         return self.W.torchdot(x_affine.t(), relu=(fuse_relu or self.iskeyedrelu()), exact=exact, absmax=absmax).t()
 
     @staticmethod
-    def kernel(W, contract, relu, device=None, narrow=False):
+    def kernel(W, contract, relu, device=None, narrow=False, narrow_rows=False):
         """The one place that turns a decided contract into an operator handle and flags: (get_op, flags) of the kn_spmm launch that applies operator `W`
         under `contract`, get_op(device) -> the handle resident there.  None when that is not one launch: 'auto' (still to calibrate), 'split' on an operator that has a split form (Conv2dTiledMatrix._torchdot_split).
         The rules: 'split' forced on an operator without a split form, and 'bf16x3' on a non-conv operator, are the f32 matrix cores (False); a conv operator
@@ -252,7 +256,10 @@ class KeyedLayer(nn.Module):
         contract sets anyway (the library ignores them below 9 columns); every other operator is what it is without the keyword.
         `narrow='mfma'`: a CONV operator under a re-ordering contract (False, 'bf16x3', 'split') is one launch with KN_FLAG_NARROW_MFMA (the matrix-core narrow
         kernel) and no other contract flag; under True / 'auto', and for every other operator, exactly narrow=True.  (Whether a CALIBRATED layer may pass 'mfma'
-        here is KeyedLayer.narrow_mode's decision.)"""
+        here is KeyedLayer.narrow_mode's decision.)
+        `narrow_rows` (the same batches): an operator with W.rows_capable() that runs in the stored order on its CSR handle -- contract True, or any non-conv operator
+        without a dense handle in play -- gets KN_FLAG_NARROW_ROWS (the row-lane kernel, the same bits) next to the flags it has without the keyword.  A float64
+        operator, a plain SparseMatrix that a re-ordering contract put on its dense handle, and conv-taps operators keep what they have."""
         conv = isinstance(W, ksp.Conv2dTiledMatrix)
         if narrow == 'mfma' and conv and W.narrow_capable() and contract in (False, 'bf16x3', 'split'):
             # a conv operator under a re-ordering contract: the matrix-core narrow kernel (the library falls back to the channel-lane kernel on an ineligible operator)
@@ -267,16 +274,18 @@ class KeyedLayer(nn.Module):
         (get_op, exact) = (W._device_op, (contract != 'bf16x3' and bool(contract)) if conv else True)
         if not conv and not contract and type(W) is SparseMatrix and not W.is_float64() and W._dense_device_op(device) is not None:
             (get_op, exact) = (W._dense_device_op, False)
-        return (get_op, (_capi.KN_FLAG_RELU if relu else 0) | (_capi.KN_FLAG_EXACT if exact else 0) | (_capi.KN_FLAG_BF16X3 if contract == 'bf16x3' else 0))
+        rows = narrow_rows and not conv and get_op == W._device_op and W.rows_capable()
+        return (get_op, (_capi.KN_FLAG_RELU if relu else 0) | (_capi.KN_FLAG_EXACT if exact else 0) | (_capi.KN_FLAG_BF16X3 if contract == 'bf16x3' else 0) |
+                (_capi.KN_FLAG_NARROW_ROWS if rows else 0))
 
-    def launch(self, device, relu=False, narrow=False):
+    def launch(self, device, relu=False, narrow=False, narrow_rows=False):
         """This layer under its contract in force as one launch on `device` (`relu`: the unkeyed nn.ReLU behind it is fused in), or None when it is not one
         kn_spmm launch: see kernel(); a float64 operator (its own kernel and a float64 result: kn_spmm_f64).  What the key-net's planners read
-        (KeyedModel._chain_op / _overlap_plan); forward() -> W.torchdot() runs the same rule.  `narrow`: see kernel(); 'mfma' goes through narrow_mode() first, without a batch."""
+        (KeyedModel._chain_op / _overlap_plan); forward() -> W.torchdot() runs the same rule.  `narrow`, `narrow_rows`: see kernel(); 'mfma' goes through narrow_mode() first, without a batch."""
         W = self.W
         if narrow == 'mfma':
             narrow = self.narrow_mode(narrow)                 # (a calibrated layer without a narrow record yet: the channel-lane kernel -- forward() measures, a planner does not)
-        kernel = None if W.is_float64() else self.kernel(W, getattr(self, '_exact', True), relu or self.iskeyedrelu(), device, narrow=narrow)
+        kernel = None if W.is_float64() else self.kernel(W, getattr(self, '_exact', True), relu or self.iskeyedrelu(), device, narrow=narrow, narrow_rows=bool(narrow and narrow_rows))
         if kernel is None:
             return None
         return Launch(kernel[0](device), kernel[1], int(W.shape[0]), int(W.shape[1]), isinstance(W, ksp.Conv2dTiledMatrix), 'Linear' in self._layertype,

@@ -80,19 +80,21 @@ def _device_block(x):
     return xd if xd.is_contiguous() else xd.contiguous()
 
 
-def _run_torchdot(W, x, relu=False, exact=True, absmax=None, narrow=False):
+def _run_torchdot(W, x, relu=False, exact=True, absmax=None, narrow=False, narrow_rows=False):
     """Y = W.X on the GPU under the contract `exact`, on the handle and flags of KeyedLayer.kernel.  x: [cols, N], torch tensor (any device / strides) or ndarray.
     Returns [rows, N] on x's device: float32, or for a float64 operator the float64 block scipy returns for it (kn_spmm_f64; the activations are
     float32 either way).  `narrow`: at most NARROW_MAX columns on the channel-lane kernel where W owns a conv-taps handle (KeyedLayer.kernel); 'mfma': on the
-    matrix-core narrow kernel (KN_FLAG_NARROW_MFMA) where `exact` is a re-ordering contract, else exactly narrow=True."""
+    matrix-core narrow kernel (KN_FLAG_NARROW_MFMA) where `exact` is a re-ordering contract, else exactly narrow=True.  `narrow_rows`: at most NARROW_MAX columns
+    on the row-lane kernel (KN_FLAG_NARROW_ROWS) where W's device form is a float32 CSR handle run in the stored order (W.rows_capable(), KeyedLayer.kernel): the
+    same bits; every other operator is what it is without the keyword."""
     from .layer import KeyedLayer            # (layer.py imports this module)
     x = torch.as_tensor(x)
     assert W.shape[1] == x.shape[0], 'Non-conformal shape for W=%s, x=%s' % (str(W.shape), str(tuple(x.shape)))
     xd = _device_block(x)
     n = xd.shape[1]
-    if narrow and n > NARROW_MAX:
-        raise ValueError('narrow=True takes at most %d batch columns, got %d' % (NARROW_MAX, n))
-    kernel = KeyedLayer.kernel(W, exact, relu, xd.device, narrow=narrow)
+    if (narrow or narrow_rows) and n > NARROW_MAX:
+        raise ValueError('%s=True takes at most %d batch columns, got %d' % ('narrow' if narrow else 'narrow_rows', NARROW_MAX, n))
+    kernel = KeyedLayer.kernel(W, exact, relu, xd.device, narrow=narrow, narrow_rows=narrow_rows)
     if kernel is None:
         y = W._torchdot_split(xd, relu=relu, absmax=absmax)
     else:
@@ -157,6 +159,10 @@ class SparseMatrix(object):
         """Does this container's device operator have the channel-lane form for 1 .. 8 batch columns (a conv-taps handle: KN_FLAG_NARROW)?"""
         return False
 
+    def rows_capable(self):
+        """Does this container's device operator have the row-lane form for 1 .. 8 batch columns (a float32 CSR handle: KN_FLAG_NARROW_ROWS)?"""
+        return not self.is_float64()
+
     def is_float64(self):
         """Does scipy compute this operator's product with float32 activations in float64 (a float64 -- or integer -- scipy matrix)?
         Dense ndarray operators go through BLAS in the reference (no defined order) and stay float32 here."""
@@ -182,12 +188,14 @@ class SparseMatrix(object):
             return False
         return _on_device(self, '_op_dense', make, device) or None
 
-    def torchdot(self, x_torch, relu=False, exact=True, absmax=None):
+    def torchdot(self, x_torch, relu=False, exact=True, absmax=None, narrow_rows=False):
         """W . x for x of shape [W.shape[1], N]: the hot path (keynet/sparse.py:488-492).  exact=True (default): bit-exact
         with scipy (order-preserving CSR kernels).  exact=False: a large dense operator (keyed nn.Linear) may run as a
         split-K f32-MFMA GEMM instead (within 1e-5; used by the tiled key-nets whose conv layers are on MFMA anyway).
-        `absmax`: one-element device f32 tensor raised to max |W . x| (kn_spmm_screen)."""
-        return _run_torchdot(self, x_torch, relu=relu, exact=exact, absmax=absmax)
+        `absmax`: one-element device f32 tensor raised to max |W . x| (kn_spmm_screen).
+        `narrow_rows` (N <= NARROW_MAX, ValueError beyond): the stored-order product on the row-lane kernel (KN_FLAG_NARROW_ROWS), the same bits; an operator
+        on its dense handle (exact=False) or in float64 is what it is without the keyword."""
+        return _run_torchdot(self, x_torch, relu=relu, exact=exact, absmax=absmax, narrow_rows=narrow_rows)
 
     def dot(self, x_numpy):
         assert isinstance(x_numpy, np.ndarray)
@@ -279,6 +287,9 @@ class FactoredSparseMatrix(SparseMatrix):
     def narrow_capable(self):
         return True
 
+    def rows_capable(self):
+        return False                     # (a conv-taps handle on the device)
+
     def torchdot(self, x_torch, relu=False, exact=True, absmax=None, narrow=False):
         """SparseMatrix.torchdot; `narrow` (True or 'mfma': the same here, the operator is under the bit-exact contract): at most NARROW_MAX columns on the channel-lane kernel of the factored device form (KN_FLAG_NARROW) -- the
         same bits as without it (the order-preserving product, which IS scipy's on the stored CSR)."""
@@ -364,9 +375,10 @@ class TiledMatrix(SparseMatrix):
             return _capi.Operator.tiled(self.shape, np.array(list(self), dtype=np.int64).reshape(-1, 3), ptr, tr, tc, tv)
         return _on_device(self, '_op', make, device)
 
-    def torchdot(self, x, relu=False, exact=True, absmax=None):
-        """[cols, N] -> [rows, N] (keynet/sparse.py:603-612); always the order-preserving path (bit-exact)."""
-        return _run_torchdot(self, x, relu=relu, exact=True, absmax=absmax)
+    def torchdot(self, x, relu=False, exact=True, absmax=None, narrow_rows=False):
+        """[cols, N] -> [rows, N] (keynet/sparse.py:603-612); always the order-preserving path (bit-exact).  `narrow_rows` (N <= NARROW_MAX, ValueError beyond):
+        on the row-lane kernel (KN_FLAG_NARROW_ROWS), the same bits."""
+        return _run_torchdot(self, x, relu=relu, exact=True, absmax=absmax, narrow_rows=narrow_rows)
 
     def dot(self, x):
         assert isinstance(x, np.ndarray)
@@ -593,6 +605,9 @@ class Conv2dTiledMatrix(TiledMatrix):
 
     def narrow_capable(self):
         return True
+
+    def rows_capable(self):
+        return False                     # (a conv-taps handle on the device)
 
     def torchdot(self, x, relu=False, exact=False, absmax=None, narrow=False):
         """[cols, N] -> [rows, N].  exact=False: f32 MFMA path (f32-input matrix instructions, exact f32 products); exact=True: the

@@ -177,7 +177,7 @@ class KeyedModel(object):
 
     NARROW_MAX = ksp.NARROW_MAX    # forward_linear(narrow=True) takes at most this many images (the channel-lane conv-taps kernel keeps one running sum per image and lane)
 
-    def forward_linear(self, img_cipher, overlap=None, narrow=False):
+    def forward_linear(self, img_cipher, overlap=None, narrow=False, narrow_rows=False):
         """[N, D0+1] -> [N, classes+1]: the nn.Sequential of keynet/system.py:132 with the unkeyed ReLUs fused into the
         producing layer's kernel epilogue.  Stream-ordered on torch's current HIP stream.  Host synchronisation: none for key-nets whose
         layers all run under a DECLARED contract (exact=True: the permutation key-nets; exact=False: forced); a key-net with layers on the
@@ -211,17 +211,23 @@ class KeyedModel(object):
         undecided, exactly as narrow=True -- nothing is decided for it.  Layers accepted by measurement are re-screened on every narrow='mfma' forward like their
         wide counterparts: max |x| of each comes from kn_spmm_screen on its producer (behind the narrow kernels that is one kn_absmax-style reduction launch per
         screened layer, one more for the input when the first layer is screened), is read back once at the end of the forward, and a layer whose input exceeds
-        RESCREEN_FACTOR x its narrow record's max_abs_x drops that record, is measured again on this batch, and the batch runs again (_rescreen)."""
+        RESCREEN_FACTOR x its narrow record's max_abs_x drops that record, is measured again on this batch, and the batch runs again (_rescreen).
+        `narrow_rows=True` (only together with `narrow`, ValueError otherwise): the layers that are float32 CSR operators in the stored order -- keyed Linear layers
+        under the bit-exact contract, pools, every layer of an untiled key-net -- run the row-lane kernel (KN_FLAG_NARROW_ROWS: the lane is the output row, the images
+        its running sums) instead of the wide-batch CSR kernels at the unpadded width.  The same bits layer by layer; orthogonal to which conv kernel `narrow` selects;
+        nothing is calibrated, decided, recorded or saved, and the cached launch lists and the whole-net kernel are left alone."""
+        if narrow_rows and not narrow:
+            raise ValueError('narrow_rows=True is a form of the narrow forward: pass narrow=True or narrow=\'mfma\' with it')
         if narrow:
-            return self._forward_narrow(img_cipher, narrow)[0]
+            return self._forward_narrow(img_cipher, narrow, bool(narrow_rows))[0]
         (x, windows) = self._prepare(img_cipher)
         y = self._forward_passes(x, windows, overlap)[0][:img_cipher.shape[0]]
         return y if img_cipher.is_cuda else y.to(img_cipher.device)
 
-    def _forward_narrow(self, img_cipher, mode=True):
+    def _forward_narrow(self, img_cipher, mode=True, rows=False):
         """forward_linear(narrow=True | 'mfma'): see there; returns (y, screens).  Stream-ordered on torch's current HIP stream.  narrow=True: no host read, capturable
         once the operators are resident.  'mfma': layers on the matrix-core narrow kernel by a measurement are screened -- `screens` = [(slots, screened)] as in
-        _forward_passes, read back here once per pass unless the stream is capturing (capture's replay reads them)."""
+        _forward_passes, read back here once per pass unless the stream is capturing (capture's replay reads them).  `rows`: narrow_rows of forward_linear."""
         n = img_cipher.shape[0]
         if n > self.NARROW_MAX:
             raise ValueError('narrow=%r takes at most %d images, got %d' % (mode, self.NARROW_MAX, n))
@@ -249,7 +255,7 @@ class KeyedModel(object):
                 if k is None:
                     y = _relu_block(y)
                 else:
-                    y = c.forward(y, fuse_relu=relu, narrow=mode, absmax=slots[k + 1:k + 2] if (slots is not None and (k + 1) in screened) else None)
+                    y = c.forward(y, fuse_relu=relu, narrow=mode, narrow_rows=rows, absmax=slots[k + 1:k + 2] if (slots is not None and (k + 1) in screened) else None)
             if slots is None:
                 break
             screens = [(slots, screened)]
@@ -616,7 +622,7 @@ class KeyedModel(object):
             self._drop_plans()
         return changed
 
-    def capture(self, img_cipher, narrow=False):
+    def capture(self, img_cipher, narrow=False, narrow_rows=False):
         """Capture forward_linear for this input shape into a HIP graph (torch.cuda.CUDAGraph on ROCm) and return a callable
         `replay(x) -> [N, classes+1]`.  Small key-nets are launch-bound (LeNet at N=1024: 7 kernels in 0.25 ms); one graph
         launch replaces them.  The graph runs the passes of the eager forward on the block _prepare made; replay(x) copies x into its first N images.
@@ -628,11 +634,14 @@ class KeyedModel(object):
         branches; nothing is screened (the conv layers run the reference's own arithmetic), so replay() reads nothing back.
         `narrow='mfma'`: the graph of forward_linear(narrow='mfma'), decided by one eager forward first; still one stream, no parallel branches.  With layers on the
         matrix-core narrow kernel by a measurement the graph gathers their max |x|, replay() reads the slots after the launch and on a trip runs the batch eagerly
-        (measuring again) and captures a new graph, as the wide capture does; with no such layer it reads nothing."""
+        (measuring again) and captures a new graph, as the wide capture does; with no such layer it reads nothing.
+        `narrow_rows=True` (only with `narrow`): the graph of forward_linear(narrow=..., narrow_rows=True): the same straight line of launches."""
         assert img_cipher.is_cuda, 'capture() needs a device tensor'
         n = img_cipher.shape[0]
+        if narrow_rows and not narrow:
+            raise ValueError('narrow_rows=True is a form of the narrow forward: pass narrow=True or narrow=\'mfma\' with it')
         if narrow:
-            return self._capture_narrow(img_cipher, narrow)
+            return self._capture_narrow(img_cipher, narrow, bool(narrow_rows))
         (static_in, windows) = self._prepare(img_cipher.detach().t().clone(memory_format=torch.contiguous_format).t())     # the graph's own input block
         keyed = self._keyed()
         state = {}
@@ -665,7 +674,7 @@ class KeyedModel(object):
         replay.graph = state['graph']
         return replay
 
-    def _capture_narrow(self, img_cipher, mode=True):
+    def _capture_narrow(self, img_cipher, mode=True, rows=False):
         """capture(narrow=True | 'mfma'): one eager narrow forward (operators resident, narrow records measured), a warm-up on the capture stream (per-stream state
         of the operators), then the capture."""
         if img_cipher.shape[0] > self.NARROW_MAX:
@@ -675,16 +684,16 @@ class KeyedModel(object):
         state = {}
 
         def build():
-            self._forward_narrow(static_in, mode)
+            self._forward_narrow(static_in, mode, rows)
             torch.cuda.synchronize()
             side = torch.cuda.Stream()
             side.wait_stream(torch.cuda.current_stream())
             with torch.cuda.stream(side):
-                self._forward_narrow(static_in, mode)
+                self._forward_narrow(static_in, mode, rows)
             torch.cuda.current_stream().wait_stream(side)
             graph = torch.cuda.CUDAGraph()
             with torch.cuda.graph(graph, stream=side):
-                (out, screens) = self._forward_narrow(static_in, mode)
+                (out, screens) = self._forward_narrow(static_in, mode, rows)
             state.update(graph=graph, out=out, screens=screens)
 
         build()
@@ -700,12 +709,12 @@ class KeyedModel(object):
         replay.graph = state['graph']
         return replay
 
-    def forward(self, img_cipher, outkey=None, narrow=False):
+    def forward(self, img_cipher, outkey=None, narrow=False, narrow_rows=False):
         """Encrypted image(s) [N, D0+1] -> logits.  N == 1 returns the reference's shape `outshape` = (C,1,1)
         (keynet/system.py:130-133); N > 1 (an extension: the reference cannot) returns (N, C, 1, 1).  `narrow`: forward_linear(narrow=True | 'mfma'), the
-        low-latency forms of this very call for 1 .. NARROW_MAX images."""
+        low-latency forms of this very call for 1 .. NARROW_MAX images; `narrow_rows`: with them, the CSR layers on the row-lane kernel (forward_linear)."""
         outkey = outkey if outkey is not None else self.embeddingkey()
-        y = self.forward_linear(img_cipher, narrow=narrow)
+        y = self.forward_linear(img_cipher, narrow=narrow, narrow_rows=narrow_rows)
         if outkey is not None:
             y = self.decrypt(y, outkey)
         n = y.shape[0]

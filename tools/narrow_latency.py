@@ -21,7 +21,15 @@ cores), three forwards of the same images in this one process: padded, narrow=Tr
 measured and accepted layer by layer on the first call), and the gate ratios of the narrow records (the measured distance between the two narrow
 arithmetics).  The narrow='mfma' logits must be inside the float-key gate against narrow=True before any time is printed.  The times of the conv LAUNCHES
 themselves (no Python, no launch overhead, no screen reduction) come from the kernel trace: --from-trace reads the device timestamps of the last eight
-forwards of a --mfma --one-forward run and prints every conv launch of both kernels beside each other, and their sums."""
+forwards of a --mfma --one-forward run and prints every conv launch of both kernels beside each other, and their sums.
+
+    python tools/narrow_latency.py --rows [--out profiles/r09_narrow_rows.txt]
+    python tools/narrow_latency.py --rows --one-forward          # for n in (1, 2, 4, 8) ONE narrow=True forward, then ONE with narrow_rows=True (for a kernel trace)
+    python tools/narrow_latency.py --rows --from-trace DIR/.../*_kernel_trace.csv [--convs 13]       # no GPU: the NON-conv launches of those forwards side by side
+
+--rows: whole forwards with and without narrow_rows in one process, alternating -- narrow=True under the default contract, then narrow='mfma' under
+exact_mode('auto') after one calibrating wide forward -- the logits torch.equal before any time is printed; and every layer that takes the row-lane kernel alone,
+its kn_spmm with and without KN_FLAG_NARROW_ROWS on the same block (HIP events, median)."""
 import argparse
 import os
 import statistics
@@ -101,6 +109,112 @@ def mfma_table(args, knet, xc, desc):
         f.write(text)
 
 
+def rows_table(args, knet, xc, desc):
+    """--rows: see the module docstring."""
+    dev = xc.device
+    if args.one_forward:
+        for n in (1, 2, 4, 8):                    # operators resident
+            knet.forward_linear(xc[:n].t().contiguous().t(), narrow=True, narrow_rows=True)
+        torch.cuda.synchronize()
+        print('TRACE-FROM-HERE: for n in (1, 2, 4, 8) one narrow=True forward, then one with narrow_rows=True', flush=True)
+        for n in (1, 2, 4, 8):
+            x = xc[:n].t().contiguous().t()
+            knet.forward_linear(x, narrow=True)
+            knet.forward_linear(x, narrow=True, narrow_rows=True)
+            torch.cuda.synchronize()
+        return
+    med = lambda v: '%8.3f (%.3f .. %.3f)' % (statistics.median(v), min(v), max(v))
+    lines = ['', '== tools/narrow_latency.py --rows: %s' % desc,
+             '   %s, torch %s; HIP events, %d warm-up + median of %d forwards (min .. max), the two forms alternating; logits torch.equal: yes'
+             % (torch.cuda.get_device_name(0), torch.__version__, args.warmup, args.forwards)]
+
+    def forwards(mode, title):
+        lines.append('   %s' % title)
+        lines.append('   %6s | %-28s | %-28s | %s' % ('images', 'narrow=%r [ms]' % (mode,), '+ narrow_rows=True [ms]', 'without / with'))
+        for n in (1, 2, 4, 8):
+            x = xc[:n].t().contiguous().t()
+            (y0, y1) = (knet.forward_linear(x, narrow=mode), knet.forward_linear(x, narrow=mode, narrow_rows=True))
+            torch.cuda.synchronize()
+            assert torch.equal(y0, y1), 'narrow_rows changed the logits at %d image(s), narrow=%r' % (n, mode)
+            (a, b) = ([], [])
+            for _ in range(4):                    # alternate in quarters
+                a += timed(lambda: knet.forward_linear(x, narrow=mode), args.forwards // 4, args.warmup)
+                b += timed(lambda: knet.forward_linear(x, narrow=mode, narrow_rows=True), args.forwards // 4, args.warmup)
+            lines.append('   %6d | %-28s | %-28s | %.2fx' % (n, med(a), med(b), statistics.median(a) / statistics.median(b)))
+            print('narrow=%r n = %d done' % (mode, n), flush=True)
+
+    forwards(True, 'whole forwards, default contract')
+    lines.append('')
+    widths = (1, 2, 3, 4, 5, 6, 7, 8)
+    lines.append('   every layer that carries KN_FLAG_NARROW_ROWS, alone: kn_spmm on one block, without / with the flag [us] and their ratio; "=" where the handle rule')
+    lines.append('   keeps the kernels of the call without the flag (the same plan string)')
+    lines.append('   %-10s %-16s | %s' % ('layer', 'rows x cols', ' | '.join('%d image(s)%s' % (n, ' ' * 11) for n in widths)))
+    st = torch.cuda.current_stream().cuda_stream
+    sums = dict((n, [0.0, 0.0]) for n in widths)
+    for (name, c) in knet._keyed(named=True):
+        (la0, la1) = (c.launch(dev, narrow=True), c.launch(dev, narrow=True, narrow_rows=True))
+        if la1 is None or la1.flags == la0.flags:
+            continue
+        cells = []
+        for n in widths:
+            x = torch.randn((la1.cols, n), device=dev)
+            y = torch.empty((la1.rows, n), device=dev)
+            same = la1.op.plan(n, la1.flags) == la0.op.plan(n, la0.flags)
+            (a, b) = ([], [])
+            for _ in range(2):
+                a += timed(lambda: la0.op.spmm(x.data_ptr(), n, n, y.data_ptr(), n, la0.flags, st), args.forwards, args.warmup)
+                b += timed(lambda: la1.op.spmm(x.data_ptr(), n, n, y.data_ptr(), n, la1.flags, st), args.forwards, args.warmup)
+            (ma, mb) = (statistics.median(a) * 1e3, statistics.median(b) * 1e3)
+            sums[n][0] += ma
+            sums[n][1] += mb
+            cells.append('%7.1f %7.1f %s' % (ma, mb, '    =' if same else '%4.2fx' % (ma / mb)))
+        lines.append('   %-10s %-16s | %s' % (name, '%d x %d' % (la1.rows, la1.cols), ' | '.join(cells)))
+        lines.append('   %-10s %-16s   %s' % ('', '', la1.op.plan(1, la1.flags)))
+    lines.append('   %-10s %-16s | %s' % ('sum', '', ' | '.join('%7.1f %7.1f %4.2fx' % (sums[n][0], sums[n][1], sums[n][0] / max(sums[n][1], 1e-9)) for n in widths)))
+    lines.append('')
+    knet.exact_mode('auto')
+    knet.forward_linear(xc)                       # the calibrating wide forward
+    forwards('mfma', "whole forwards, exact_mode('auto') after one calibrating wide forward")
+    text = '\n'.join(lines) + '\n'
+    print(text)
+    with open(args.out or os.path.join(ROOT, 'profiles', 'r09_narrow_rows.txt'), 'a') as f:
+        f.write(text)
+
+
+def rows_trace_table(args):
+    """--rows --from-trace: the NON-conv launches of the last eight forwards of a `--rows --one-forward` run (device timestamps), forward by forward."""
+    import csv
+    with open(args.from_trace, newline='') as f:
+        rows = sorted(csv.DictReader(f), key=lambda r: int(r['Start_Timestamp']))
+    first = next(i for (i, r) in enumerate(rows) if 'convtaps' in r['Kernel_Name'])
+    (fw, seen) = ([[]], 0)
+    for r in rows[first:]:                        # a forward = its k conv launches and the launches between and behind them, up to the next conv launch
+        conv = 'convtaps' in r['Kernel_Name']
+        if conv and seen == args.convs:
+            fw.append([])
+            seen = 0
+        seen += conv
+        fw[-1].append(r)
+    fw = fw[-8:]
+    assert len(fw) == 8, 'the trace holds %d forwards, fewer than 8' % len(fw)
+    us = lambda r: (int(r['End_Timestamp']) - int(r['Start_Timestamp'])) / 1e3
+    lines = ['', '== tools/narrow_latency.py --rows --from-trace: the launches of fc6 - fc8 and the pools (with their helpers) in one narrow=True forward and one with narrow_rows=True (rocprofv3 --kernel-trace)']
+    for (i, n) in enumerate((1, 2, 4, 8)):
+        # (the conv launches' own helper, conv_lastrow_kernel, and torch's copy kernels between two forwards are neither fc nor pool launches)
+        (a, b) = [[r for r in f if 'kn::' in r['Kernel_Name'] and 'conv' not in r['Kernel_Name']] for f in (fw[2 * i], fw[2 * i + 1])]
+        lines.append('')
+        lines.append('   %d image(s) [us]: without narrow_rows | with narrow_rows' % n)
+        for j in range(max(len(a), len(b))):
+            cell = lambda L: ('%9.1f %-60s' % (us(L[j]), L[j]['Kernel_Name'][:60])) if j < len(L) else ' ' * 70
+            lines.append('     %s | %s' % (cell(a), cell(b)))
+        (sa, sb) = (sum(us(r) for r in a), sum(us(r) for r in b))
+        lines.append('     sum of the non-conv launches: %9.1f | %9.1f | %5.2fx' % (sa, sb, sa / max(sb, 1e-9)))
+    text = '\n'.join(lines) + '\n'
+    print(text)
+    with open(args.out or os.path.join(ROOT, 'profiles', 'r09_narrow_rows.txt'), 'a') as f:
+        f.write(text)
+
+
 def trace_table(args):
     """--from-trace: the conv launches of the last eight forwards of a `--mfma --one-forward` run under rocprofv3 --kernel-trace (device timestamps)."""
     import csv
@@ -138,10 +252,11 @@ def main():
     ap.add_argument('--convs', type=int, default=13, help='conv layers per forward in --from-trace')
     ap.add_argument('--one-forward', action='store_true', help='key, warm up, run one narrow forward and exit (for a kernel trace)')
     ap.add_argument('-n', type=int, default=1, help='images of --one-forward')
+    ap.add_argument('--rows', action='store_true', help='whole forwards and single layers with and without narrow_rows=True (profiles/r09_narrow_rows.txt)')
     ap.add_argument('--mfma', action='store_true', help="exact_mode('auto') after one calibrating wide forward: padded, narrow=True, narrow='mfma'")
     args = ap.parse_args()
     if args.from_trace:
-        return trace_table(args)
+        return rows_trace_table(args) if args.rows else trace_table(args)
     assert args.forwards >= 20 or args.one_forward, 'the median of at least 20 forwards'
     t0 = time.time()
     (sensor, knet, inshape, _, desc, _) = workloads.build_workload(args.workload, 0, fanout=True)
@@ -153,6 +268,8 @@ def main():
     print('keyed %s in %.0f s' % (desc, time.time() - t0), flush=True)
     if args.mfma:
         return mfma_table(args, knet, xc, desc)
+    if args.rows:
+        return rows_table(args, knet, xc, desc)
     if args.one_forward:
         x = xc[:args.n].t().contiguous().t()
         knet.forward_linear(x, narrow=True)       # operators resident
