@@ -497,6 +497,16 @@ static int check_device(const kn_operator* h, const char* hint) {
 
 using namespace kn;
 
+// A side table (the (pixel, tap) records, the bf16 planes, the fill records) that a kn_spmm wants and finds missing (null under acquire) is built now, once:
+// double-checked under Handle::lazy_mu -- the builder looks again and publishes its pointer (release) only after the data is in HBM.  A kn_spmm_plan call
+// builds nothing; a first use allocates, so it is not capturable.
+template <typename T, typename F>
+static int first_use(kn_handle_t h, T*& table, F&& build) {
+    if (__atomic_load_n(&table, __ATOMIC_ACQUIRE) != nullptr || plan_sink() != nullptr) return KN_OK;
+    std::lock_guard<std::mutex> g(h->lazy_mu);
+    return build();
+}
+
 extern "C" {
 
 int kn_abi_version(void) { return KN_ABI_VERSION; }
@@ -962,22 +972,9 @@ static int spmm_impl(kn_handle_t h, const float* x_dev, int64_t ldx, int64_t n_v
         // KN_FLAG_EXACT is honoured inside convtaps_spmm by the order-preserving kernel on the factored operator
         // KN_FLAG_NARROW on at most 8 columns takes the channel-lane kernel, which reads the slot lists themselves: no side table is built for it
         const bool narrow = narrow_call(flags, n_vecs);
-        if (narrow_mfma_call(h->ct, flags, n_vecs) && __atomic_load_n(&h->ct.pt_rec, __ATOMIC_ACQUIRE) == nullptr && plan_sink() == nullptr) {
-            std::lock_guard<std::mutex> g(h->lazy_mu);           // per-(pixel, tap) records of the matrix-core narrow kernel, once (not capturable: like any first use)
-            rc = convtaps_build_pt(h);
-            if (rc) return rc;
-        }
-        // lazily built side tables: double-checked under Handle::lazy_mu; both builders publish their pointer (release) only after the data is in HBM
-        if (!narrow && (flags & KN_FLAG_BF16X3) && !(flags & KN_FLAG_EXACT) && __atomic_load_n(&h->ct.tapsB, __ATOMIC_ACQUIRE) == nullptr && plan_sink() == nullptr) {
-            std::lock_guard<std::mutex> g(h->lazy_mu);           // bf16 planes of the taps, once (not capturable: like any first use)
-            rc = convtaps_build_bf16(h->ct, h->h_taps);
-            if (rc) return rc;
-        }
-        if (!narrow && (flags & KN_FLAG_EXACT) && __atomic_load_n(&h->ct.fill_rec, __ATOMIC_ACQUIRE) == nullptr && plan_sink() == nullptr && convtaps_fill_ok(h->ct)) {
-            std::lock_guard<std::mutex> g(h->lazy_mu);           // record lists of the filled-in order-preserving kernel, once (built on the device on this stream, waited for, then published)
-            rc = convtaps_build_fill(h->ct, s);
-            if (rc) return rc;
-        }
+        if (narrow_mfma_call(h->ct, flags, n_vecs) && (rc = first_use(h, h->ct.pt_rec, [&] { return convtaps_build_pt(h); }))) return rc;
+        if (!narrow && (flags & KN_FLAG_BF16X3) && !(flags & KN_FLAG_EXACT) && (rc = first_use(h, h->ct.tapsB, [&] { return convtaps_build_bf16(h->ct, h->h_taps); }))) return rc;
+        if (!narrow && (flags & KN_FLAG_EXACT) && convtaps_fill_ok(h->ct) && (rc = first_use(h, h->ct.fill_rec, [&] { return convtaps_build_fill(h->ct, s); }))) return rc;
         rc = convtaps_spmm(h->ct, x_dev, ldx, n_vecs, y_dev, ldy, flags, s, absmax, &fused);
     }
     if (rc) return rc;

@@ -2588,21 +2588,26 @@ static int exact_tail(const ConvTapsDev& A, const ConvArgs& a, hipStream_t s) {
     return KN_OK;
 }
 
-// KN_FLAG_NARROW on at most NARROW_MAX_VECS columns: one wavefront per (output pixel, 64 output channels); the kernel's element offsets into tapsT and X are 32-bit
+// What the two narrow conv launchers (flag `flag`) require of operator and batch: value rows in whole 64-channel blocks, and 32-bit element offsets into tapsT and X
+static int narrow_limits(const ConvTapsDev& A, const ConvArgs& a, const char* flag) {
+    KN_REQUIRE(A.cout_pad % 64 == 0, KN_ERR_UNSUPPORTED, std::string(flag) + ": the value rows are not padded to whole 64-channel blocks");
+    KN_REQUIRE(A.ntaps * A.cin_pad * A.cout_pad < ((int64_t)1 << 31) && (a.last_in_row + 1) * a.ldx + NARROW_MAX_VECS < ((int64_t)1 << 31),
+               KN_ERR_UNSUPPORTED, std::string(flag) + ": the taps or the activation block exceed 32-bit element offsets");
+    return KN_OK;
+}
+
+// KN_FLAG_NARROW on at most NARROW_MAX_VECS columns: one wavefront per (output pixel, 64 output channels), NarrowWidth::nv running sums (batch columns) per lane
 static int spmm_narrow(const ConvTapsDev& A, ConvArgs& a, hipStream_t s) {
-    const int64_t n_vecs = a.n_vecs;
-    const int nv = n_vecs <= 1 ? 1 : (n_vecs <= 2 ? 2 : (n_vecs <= 4 ? 4 : 8));      // running sums (batch columns) per lane
+    const NarrowWidth w = narrow_width(a.n_vecs);
     const int n_cb = (int)((A.Cout + 63) / 64);
     const int64_t n_wg = ((int64_t)a.n_pix * n_cb + 3) / 4;
-    KN_REQUIRE(A.cout_pad % 64 == 0, KN_ERR_UNSUPPORTED, "KN_FLAG_NARROW: the value rows are not padded to whole 64-channel blocks");
-    KN_REQUIRE(A.ntaps * A.cin_pad * A.cout_pad < ((int64_t)1 << 31) && (a.last_in_row + 1) * a.ldx + NARROW_MAX_VECS < ((int64_t)1 << 31),
-               KN_ERR_UNSUPPORTED, "KN_FLAG_NARROW: the taps or the activation block exceed 32-bit element offsets");
+    if (int rc = narrow_limits(A, a, "KN_FLAG_NARROW")) return rc;
     KN_REQUIRE(n_wg + 8 < ((int64_t)1 << 29) && A.Cin * (int64_t)A.max_slots < ((int64_t)1 << 31), KN_ERR_UNSUPPORTED,
                "grid or slot walk too large for the channel-lane order-preserving kernel");
-    const bool coef = !A.unit_coef, full = n_vecs == nv;
-    KN_LAUNCH("convtaps_narrow_kernel<" + std::to_string(nv) + (full ? "" : ",masked to " + std::to_string(n_vecs)) + (A.has_dups ? ",stored values summed" : "") + (coef ? ",coef" : "") +
+    const bool coef = !A.unit_coef;
+    KN_LAUNCH("convtaps_narrow_kernel<" + std::to_string(w.nv) + (w.full ? "" : ",masked to " + std::to_string(a.n_vecs)) + (A.has_dups ? ",stored values summed" : "") + (coef ? ",coef" : "") +
                   "> (lane = output channel)",
-              narrow_kernel(nv, full, A.has_dups, coef), dim3((unsigned)(((n_wg + 7) / 8) * 8)), dim3(256), 0, s, a, n_cb, n_wg);
+              narrow_kernel(w.nv, w.full, A.has_dups, coef), dim3((unsigned)(((n_wg + 7) / 8) * 8)), dim3(256), 0, s, a, n_cb, n_wg);
     return exact_tail(A, a, s);
 }
 
@@ -2619,22 +2624,19 @@ static NarrowMfmaKernel narrow_mfma_kernel(bool two, bool coef) {
 }
 
 static int spmm_narrow_mfma(const ConvTapsDev& A, ConvArgs& a, hipStream_t s) {
-    const int64_t n_vecs = a.n_vecs;
-    const int nv_log2 = n_vecs <= 1 ? 0 : (n_vecs <= 2 ? 1 : (n_vecs <= 4 ? 2 : 3));
-    const int64_t n_nt = (((int64_t)a.n_pix << nv_log2) + 31) / 32;
-    KN_REQUIRE(A.cout_pad % 64 == 0, KN_ERR_UNSUPPORTED, "KN_FLAG_NARROW_MFMA: the value rows are not padded to whole 64-channel blocks");
-    KN_REQUIRE(A.ntaps * A.cin_pad * A.cout_pad < ((int64_t)1 << 31) && (a.last_in_row + 1) * a.ldx + NARROW_MAX_VECS < ((int64_t)1 << 31),
-               KN_ERR_UNSUPPORTED, "KN_FLAG_NARROW_MFMA: the taps or the activation block exceed 32-bit element offsets");
+    const NarrowWidth w = narrow_width(a.n_vecs);
+    const int64_t n_nt = (((int64_t)a.n_pix << w.log2) + 31) / 32;
+    if (int rc = narrow_limits(A, a, "KN_FLAG_NARROW_MFMA")) return rc;
     const int tm = ((A.Cout + 63) / 64) * n_nt >= 1024 ? 2 : 1;
     const int64_t n_wg = ((A.Cout + 32 * tm - 1) / (32 * tm)) * n_nt;
     KN_REQUIRE(n_wg + 8 < ((int64_t)1 << 29) && n_nt < ((int64_t)1 << 26), KN_ERR_UNSUPPORTED, "grid too large for the matrix-core narrow kernel");
     const PtRec* pt = reinterpret_cast<const PtRec*>(__atomic_load_n(&A.pt_rec, __ATOMIC_ACQUIRE));
     KN_REQUIRE(pt != nullptr || plan_sink() != nullptr, KN_ERR_INVALID, "KN_FLAG_NARROW_MFMA: the (pixel, tap) records were not built");
     const bool coef = !A.unit_coef;
-    KN_LAUNCH("convtaps_narrow_mfma_kernel<" + std::to_string(32 * tm) + " channels x " + std::to_string(32 >> nv_log2) + " pixels x NV=" + std::to_string(1 << nv_log2) +
-                  ((1 << nv_log2) == n_vecs ? "" : " masked to " + std::to_string(n_vecs)) + ", K split over 4 wavefronts" + (A.pt_two ? ", two slots per tap" : "") + (coef ? ",coef" : "") +
+    KN_LAUNCH("convtaps_narrow_mfma_kernel<" + std::to_string(32 * tm) + " channels x " + std::to_string(32 >> w.log2) + " pixels x NV=" + std::to_string(w.nv) +
+                  (w.full ? "" : " masked to " + std::to_string(a.n_vecs)) + ", K split over 4 wavefronts" + (A.pt_two ? ", two slots per tap" : "") + (coef ? ",coef" : "") +
                   "> (v_mfma_f32_32x32x2_f32, at most " + std::to_string(PT_MAX_SLOTS) + " slots per (pixel, tap))",
-              (tm == 2 ? narrow_mfma_kernel<2>(A.pt_two, coef) : narrow_mfma_kernel<1>(A.pt_two, coef)), dim3((unsigned)(((n_wg + 7) / 8) * 8)), dim3(256), 0, s, a, pt, nv_log2, (int)n_nt, n_wg);
+              (tm == 2 ? narrow_mfma_kernel<2>(A.pt_two, coef) : narrow_mfma_kernel<1>(A.pt_two, coef)), dim3((unsigned)(((n_wg + 7) / 8) * 8)), dim3(256), 0, s, a, pt, w.log2, (int)n_nt, n_wg);
     launch_lastrow(A, a, s);
     return KN_OK;
 }

@@ -211,8 +211,7 @@ static NarrowRowsKernel narrow_rows_kernel(int nv, bool full) {
 // ONE launch, 64 member rows per wavefront.  A keyed Linear puts at most one wavefront on a SIMD whatever the height (VGG-16 fc6: 65 wavefronts at 64 rows, 257 at
 // 16, on 1 024 SIMDs), and the bytes its value rings keep in flight are rows x 48 steps x 4 bytes at every height: the form with whole 256-byte value segments.
 int csr_narrow_rows_spmm(const CsrDev& A, const float* x, int64_t ldx, int64_t n_vecs, float* y, int64_t ldy, int relu, bool loose, hipStream_t s) {
-    const int nv = n_vecs <= 1 ? 1 : (n_vecs <= 2 ? 2 : (n_vecs <= 4 ? 4 : 8));
-    const bool full = n_vecs == nv;
+    const NarrowWidth w = narrow_width(n_vecs);
     const int64_t n_loose = loose ? A.n_loose : 0;
     const int64_t grid_grp = (A.n_nr + 3) / 4, grid_loose = (n_loose + 255) / 256;
     if (grid_grp + grid_loose == 0) return KN_OK;
@@ -239,9 +238,9 @@ int csr_narrow_rows_spmm(const CsrDev& A, const float* x, int64_t ldx, int64_t n
     a.n_vecs = (int)n_vecs;
     a.relu = relu;
     a.grid_grp = (uint32_t)grid_grp;
-    KN_LAUNCH("csr_narrow_kernel<nv=" + std::to_string(nv) + (full ? "" : ",masked to " + std::to_string(n_vecs)) + ",rows=64> (lane = output row: " +
+    KN_LAUNCH("csr_narrow_kernel<nv=" + std::to_string(w.nv) + (w.full ? "" : ",masked to " + std::to_string(n_vecs)) + ",rows=64> (lane = output row: " +
                   std::to_string(A.n_nr) + " group chunks, " + std::to_string(n_loose) + " loose rows)",
-              narrow_rows_kernel(nv, full), dim3((unsigned)(grid_grp + grid_loose)), dim3(256), 0, s, a);
+              narrow_rows_kernel(w.nv, w.full), dim3((unsigned)(grid_grp + grid_loose)), dim3(256), 0, s, a);
     KN_HIP(hipGetLastError());
     return KN_OK;
 }

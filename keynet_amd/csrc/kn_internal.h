@@ -332,6 +332,12 @@ static constexpr int MF_MIN_MEMBERS = 24;   // a pattern group takes the matrix-
 // KN_FLAG_NARROW: the widest batch of the channel-lane conv-taps kernel, and whether a call takes it (the one place that reads the flag)
 static constexpr int64_t NARROW_MAX_VECS = 8;
 static inline bool narrow_call(uint32_t flags, int64_t n_vecs) { return (flags & (KN_FLAG_NARROW | KN_FLAG_NARROW_MFMA)) && n_vecs <= NARROW_MAX_VECS; }
+// The width a narrow launcher instantiates its kernel for: the next of 1 | 2 | 4 | 8 columns, its log2, and whether the batch fills it (else the columns beyond n_vecs are masked)
+struct NarrowWidth { int nv, log2; bool full; };
+static inline NarrowWidth narrow_width(int64_t n_vecs) {
+    const int l = n_vecs <= 1 ? 0 : (n_vecs <= 2 ? 1 : (n_vecs <= 4 ? 2 : 3));
+    return {1 << l, l, n_vecs == (1 << l)};
+}
 // KN_FLAG_NARROW_MFMA: the most slots one (output pixel, tap) pair may hold for the matrix-core narrow kernel, the largest record table built for it, and
 // whether a narrow call takes that kernel (otherwise the flag means KN_FLAG_NARROW)
 static constexpr int PT_MAX_SLOTS = 2;

@@ -225,23 +225,24 @@ class KeyedLayer(nn.Module):
         if verbose():
             print('[keynet_amd.layer]: forward %s' % str(self))
         exact = getattr(self, '_exact', True)
+        relu = fuse_relu or self.iskeyedrelu()
+        form = {}                            # what `narrow` / `narrow_rows` make of this layer: the keyword its operator's torchdot takes, if any
         if narrow and self.W.narrow_capable():
-            relu = fuse_relu or self.iskeyedrelu()
-            mode = self.narrow_mode(narrow, x_affine.t(), relu) if narrow == 'mfma' else True
-            return self.W.torchdot(x_affine.t(), relu=relu, exact=exact, absmax=absmax, narrow=mode).t()
-        if narrow and exact == 'auto':
-            exact = True                     # an undecided layer without a narrow form: the reference's order for this call, nothing decided or recorded
-        if exact == 'auto':
+            form = dict(narrow=self.narrow_mode(narrow, x_affine.t(), relu) if narrow == 'mfma' else True)
+        elif narrow:
+            if exact == 'auto':
+                exact = True                 # an undecided layer without a narrow form: the reference's order for this call, nothing decided or recorded
+            if narrow_rows and self.W.rows_capable():
+                form = dict(narrow_rows=True)
+        elif exact == 'auto':
             if x_affine.is_cuda and torch.cuda.is_current_stream_capturing():
                 raise _capi.KeynetHipError('keynet_amd: %s has not decided its arithmetic contract yet (exact=\'auto\' calibrates on the first batch, with host reads): '
                                            'run one eager forward before capturing a HIP graph (KeyedModel.capture does), or declare exact=True / False' % self._repr)
-            y = self._calibrate(x_affine, fuse_relu or self.iskeyedrelu())
+            y = self._calibrate(x_affine, relu)
             if absmax is not None:
                 _absmax_into(y.t(), absmax)
             return y
-        if narrow and narrow_rows and self.W.rows_capable():
-            return self.W.torchdot(x_affine.t(), relu=(fuse_relu or self.iskeyedrelu()), exact=exact, absmax=absmax, narrow_rows=True).t()
-        return self.W.torchdot(x_affine.t(), relu=(fuse_relu or self.iskeyedrelu()), exact=exact, absmax=absmax).t()
+        return self.W.torchdot(x_affine.t(), relu=relu, exact=exact, absmax=absmax, **form).t()
 
     @staticmethod
     def kernel(W, contract, relu, device=None, narrow=False, narrow_rows=False):
@@ -261,22 +262,21 @@ class KeyedLayer(nn.Module):
         without a dense handle in play -- gets KN_FLAG_NARROW_ROWS (the row-lane kernel, the same bits) next to the flags it has without the keyword.  A float64
         operator, a plain SparseMatrix that a re-ordering contract put on its dense handle, and conv-taps operators keep what they have."""
         conv = isinstance(W, ksp.Conv2dTiledMatrix)
-        if narrow == 'mfma' and conv and W.narrow_capable() and contract in (False, 'bf16x3', 'split'):
-            # a conv operator under a re-ordering contract: the matrix-core narrow kernel (the library falls back to the channel-lane kernel on an ineligible operator)
-            return (W._device_op, (_capi.KN_FLAG_RELU if relu else 0) | _capi.KN_FLAG_NARROW_MFMA)
-        if narrow and W.narrow_capable():
-            exact = contract is True or not conv
-            return (W._device_op, (_capi.KN_FLAG_RELU if relu else 0) | (_capi.KN_FLAG_EXACT if exact else 0) | (_capi.KN_FLAG_BF16X3 if contract == 'bf16x3' else 0) | _capi.KN_FLAG_NARROW)
-        if contract == 'auto' or (contract == 'split' and conv and W._taps is not None):
-            return None
-        if contract == 'split' or (contract == 'bf16x3' and not conv):
-            contract = False
-        (get_op, exact) = (W._device_op, (contract != 'bf16x3' and bool(contract)) if conv else True)
+        lane = bool(narrow) and W.narrow_capable()          # one launch of a narrow conv kernel, whatever the contract
+        mfma = lane and narrow == 'mfma' and conv and contract in (False, 'bf16x3', 'split')      # (the library falls back to the channel-lane kernel on an ineligible operator)
+        if not lane:
+            if contract == 'auto' or (contract == 'split' and conv and W._taps is not None):
+                return None
+            if contract == 'split' or (contract == 'bf16x3' and not conv):
+                contract = False
+        (get_op, exact, bf16x3) = (W._device_op, contract is True or not conv, contract == 'bf16x3')
         if not conv and not contract and type(W) is SparseMatrix and not W.is_float64() and W._dense_device_op(device) is not None:
             (get_op, exact) = (W._dense_device_op, False)
-        rows = narrow_rows and not conv and get_op == W._device_op and W.rows_capable()
-        return (get_op, (_capi.KN_FLAG_RELU if relu else 0) | (_capi.KN_FLAG_EXACT if exact else 0) | (_capi.KN_FLAG_BF16X3 if contract == 'bf16x3' else 0) |
-                (_capi.KN_FLAG_NARROW_ROWS if rows else 0))
+        rows = narrow_rows and not lane and not conv and get_op == W._device_op and W.rows_capable()
+        if mfma:
+            (exact, bf16x3) = (False, False)
+        return (get_op, (_capi.KN_FLAG_RELU if relu else 0) | (_capi.KN_FLAG_EXACT if exact else 0) | (_capi.KN_FLAG_BF16X3 if bf16x3 else 0) |
+                (_capi.KN_FLAG_NARROW_MFMA if mfma else _capi.KN_FLAG_NARROW if lane else 0) | (_capi.KN_FLAG_NARROW_ROWS if rows else 0))
 
     def launch(self, device, relu=False, narrow=False, narrow_rows=False):
         """This layer under its contract in force as one launch on `device` (`relu`: the unkeyed nn.ReLU behind it is fused in), or None when it is not one
@@ -301,15 +301,28 @@ class KeyedLayer(nn.Module):
         rec = getattr(self, '_contract_record', None)
         return getattr(self, '_exact', True) in (False, 'bf16x3', 'split') and rec is not None and rec.get('max_abs_x') is not None
 
+    def screen_record(self, narrow=False):
+        """The record whose max_abs_x a forward screens: the calibration record, or under `narrow` the narrow record inside it (narrow_record())."""
+        return self._contract_record['narrow'] if narrow else self._contract_record
+
     def rescreen(self, xmax, narrow=False):
         """max |x| of a later batch against the calibrated one: True = the decision does not cover this batch (re-calibrate).  The measured
         difference of a re-ordered f32 sum scales with the activations while the tolerance 1e-5 max(1, |y|) has a floor, so a decision
         taken with 2x headroom (accepted at <= 0.5 tol) is kept for inputs up to RESCREEN_FACTOR x the calibrated magnitude.
         `narrow`: against the narrow record (the measurement of the matrix-core narrow kernel) instead of the wide one."""
-        cal = float((self._contract_record['narrow'] if narrow else self._contract_record)['max_abs_x'])
+        cal = float(self.screen_record(narrow)['max_abs_x'])
         if not np.isfinite(cal):
             return False                                          # calibrated on non-finite activations: there is no larger batch to learn from
         return not (xmax <= self.RESCREEN_FACTOR * cal)          # also True for NaN
+
+    def unscreen(self, narrow=False):
+        """Drop the record a screen has outgrown: the layer is 'auto' again (decided by the next forward, on that batch); under `narrow` only the narrow
+        record goes (measured again by the next narrow='mfma' pass) and the wide decision stays."""
+        if narrow:
+            self._contract_record.pop('narrow', None)
+        else:
+            self._exact = 'auto'
+            self.__dict__.pop('_contract_record', None)
 
     # -- narrow='mfma': the matrix-core narrow kernel under the layer's contract ------------------------------------------
     def narrow_record(self):

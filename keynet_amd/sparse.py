@@ -92,8 +92,7 @@ def _run_torchdot(W, x, relu=False, exact=True, absmax=None, narrow=False, narro
     assert W.shape[1] == x.shape[0], 'Non-conformal shape for W=%s, x=%s' % (str(W.shape), str(tuple(x.shape)))
     xd = _device_block(x)
     n = xd.shape[1]
-    if (narrow or narrow_rows) and n > NARROW_MAX:
-        raise ValueError('%s=True takes at most %d batch columns, got %d' % ('narrow' if narrow else 'narrow_rows', NARROW_MAX, n))
+    _narrow_args(n, narrow, narrow_rows, 'batch columns', alone=True)
     kernel = KeyedLayer.kernel(W, exact, relu, xd.device, narrow=narrow, narrow_rows=narrow_rows)
     if kernel is None:
         y = W._torchdot_split(xd, relu=relu, absmax=absmax)
@@ -112,6 +111,16 @@ def _run_torchdot(W, x, relu=False, exact=True, absmax=None, narrow=False, narro
 
 
 NARROW_MAX = 8        # widest batch of the channel-lane conv-taps kernel (KN_FLAG_NARROW; KeyedModel.NARROW_MAX)
+
+
+def _narrow_args(n, narrow, narrow_rows, what='images', alone=False):
+    """The argument rule of the narrow forms, for a batch of `n`: `narrow_rows` only together with `narrow` (`alone`: a container's torchdot, which takes one
+    keyword or the other), at most NARROW_MAX columns.  ValueError, or the normalised (mode, rows): mode False | True | 'mfma', rows a bool."""
+    if narrow_rows and not narrow and not alone:
+        raise ValueError('narrow_rows=True is a form of the narrow forward: pass narrow=True or narrow=\'mfma\' with it')
+    if (narrow or narrow_rows) and n > NARROW_MAX:
+        raise ValueError('%s takes at most %d %s, got %d' % ('narrow=%r' % (narrow,) if narrow else 'narrow_rows=True', NARROW_MAX, what, n))
+    return (narrow if narrow == 'mfma' else bool(narrow), bool(narrow_rows))
 
 
 # ------------------------------------------------------------------------------------------------------------------

@@ -216,54 +216,12 @@ class KeyedModel(object):
         under the bit-exact contract, pools, every layer of an untiled key-net -- run the row-lane kernel (KN_FLAG_NARROW_ROWS: the lane is the output row, the images
         its running sums) instead of the wide-batch CSR kernels at the unpadded width.  The same bits layer by layer; orthogonal to which conv kernel `narrow` selects;
         nothing is calibrated, decided, recorded or saved, and the cached launch lists and the whole-net kernel are left alone."""
-        if narrow_rows and not narrow:
-            raise ValueError('narrow_rows=True is a form of the narrow forward: pass narrow=True or narrow=\'mfma\' with it')
-        if narrow:
-            return self._forward_narrow(img_cipher, narrow, bool(narrow_rows))[0]
-        (x, windows) = self._prepare(img_cipher)
-        y = self._forward_passes(x, windows, overlap)[0][:img_cipher.shape[0]]
+        (mode, rows) = ksp._narrow_args(img_cipher.shape[0], narrow, narrow_rows)
+        (x, windows) = self._prepare(img_cipher, mode)
+        y = self._forward_passes(x, windows, False if mode else overlap, mode, rows)[0][:img_cipher.shape[0]]
         return y if img_cipher.is_cuda else y.to(img_cipher.device)
 
-    def _forward_narrow(self, img_cipher, mode=True, rows=False):
-        """forward_linear(narrow=True | 'mfma'): see there; returns (y, screens).  Stream-ordered on torch's current HIP stream.  narrow=True: no host read, capturable
-        once the operators are resident.  'mfma': layers on the matrix-core narrow kernel by a measurement are screened -- `screens` = [(slots, screened)] as in
-        _forward_passes, read back here once per pass unless the stream is capturing (capture's replay reads them).  `rows`: narrow_rows of forward_linear."""
-        n = img_cipher.shape[0]
-        if n > self.NARROW_MAX:
-            raise ValueError('narrow=%r takes at most %d images, got %d' % (mode, self.NARROW_MAX, n))
-        x = img_cipher
-        if not x.is_cuda and x.dim() == 2 and torch.cuda.is_available():
-            x = x.detach().float().cuda()
-        if x.is_cuda and x.dim() == 2 and x.dtype == torch.float32 and not x.t().is_contiguous():
-            x = x.detach().t().contiguous().t()                  # feature-major once: every layer hands the next one such a block
-        y = None
-        keyed = self._keyed()
-        if x.is_cuda and x.dim() == 2 and not any(c.W.narrow_capable() for c in keyed):
-            chain = self._chain_op(x.device)                     # (a key-net without conv-taps operators: the whole-net kernel where it qualifies, as without the keyword)
-            if chain is not None:
-                y = self._forward_chain(x, chain)
-        screens = []
-        read = x.is_cuda and x.dim() == 2 and not torch.cuda.is_current_stream_capturing() and self.RESCREEN_READ
-        for attempt in range(self.RESCREEN_MAX_PASSES if y is None else 0):
-            # layers measured DURING this pass were measured on this very batch: only the records that existed before it are screened
-            screened = set(j for (j, c) in enumerate(keyed) if c.narrow_screened()) if (mode == 'mfma' and self.RESCREEN and x.is_cuda and x.dim() == 2) else set()
-            slots = torch.zeros(len(keyed) + 1, dtype=torch.float32, device=x.device) if screened else None
-            if slots is not None and 0 in screened:
-                klayer._absmax_into(x.detach().t().float(), slots[0:1])
-            y = x
-            for (k, c, relu) in self._steps():
-                if k is None:
-                    y = _relu_block(y)
-                else:
-                    y = c.forward(y, fuse_relu=relu, narrow=mode, narrow_rows=rows, absmax=slots[k + 1:k + 2] if (slots is not None and (k + 1) in screened) else None)
-            if slots is None:
-                break
-            screens = [(slots, screened)]
-            if not read or not self._rescreen(slots.tolist(), keyed, screened, narrow=True):
-                break
-        return (y if img_cipher.is_cuda else y.to(img_cipher.device), screens)
-
-    def _prepare(self, x):
+    def _prepare(self, x, narrow=False):
         """What the kernels get to see: (x, windows), the image ranges of the passes.  A host batch goes to the device ONCE (the layers chain
         there; the screen sees them).  A float32 device batch of a tiled-conv key-net becomes one feature-major block of whole BATCH_TILE tiles
         (ragged conv-taps forms are slow: VGG-16, stored order, 186 ms at 64 images against 72 ms at 128, profiles/r06_vgg16_other_batches.txt;
@@ -271,12 +229,15 @@ class KeyedModel(object):
         The fast loaders take 32-bit element offsets: a batch whose largest layer would hold MAX_BLOCK_ELEMENTS activations runs as passes of the
         largest multiple of 256 images that keeps every layer inside (VGG-16 at 1 024 images: conv1_2 113.7 ms against 2 x 31 for two passes of 512);
         each pass copies its window into a block of its own (a padded batch is then held twice while the passes run).  Anything else -- float64,
-        an untiled key-net, no image -- passes through as one window."""
+        an untiled key-net, no image -- passes through as one window.  `narrow` (forward_linear): never padded or split, laid out feature-major once."""
         if not x.is_cuda and x.dim() == 2 and torch.cuda.is_available():
             x = x.detach().float().cuda()
-        keyed = self._keyed()
         n = x.shape[0]
-        if not (x.is_cuda and x.dim() == 2 and x.dtype == torch.float32 and n > 0 and any(isinstance(c.W, ksp.Conv2dTiledMatrix) for c in keyed)):
+        dev32 = x.is_cuda and x.dim() == 2 and x.dtype == torch.float32
+        keyed = None if narrow else self._keyed()
+        if narrow or not (dev32 and n > 0 and any(isinstance(c.W, ksp.Conv2dTiledMatrix) for c in keyed)):
+            if narrow and dev32 and not x.t().is_contiguous():
+                x = x.detach().t().contiguous().t()              # every layer hands the next one such a block
             return (x, [(0, n)])
         npad = -(-n // self.BATCH_TILE) * self.BATCH_TILE
         chunk = (self.MAX_BLOCK_ELEMENTS - 1) // max(max(c.W.shape) for c in keyed) // 256 * 256
@@ -292,10 +253,13 @@ class KeyedModel(object):
             x = x.detach().t().contiguous().t()
         return (x, windows)
 
-    def _forward_passes(self, x, windows, overlap):
+    def _forward_passes(self, x, windows, overlap, narrow=False, rows=False):
         """The screened forward of a prepared batch: (y, screens).  A pass whose screen re-calibrates a layer runs again (calibrating on its own images),
         then every other pass again: the batch comes out of ONE set of contracts.  At most RESCREEN_MAX_PASSES runs of a pass; then only the last pass is
-        re-screened (the next forward decides).  Under a HIP-graph capture nothing is read: `screens` = (slots, screened) per pass, for capture's replay."""
+        re-screened (the next forward decides).  Under a HIP-graph capture nothing is read: `screens` = (slots, screened) per pass, for capture's replay.
+        `narrow` / `rows` (the normalised keywords of forward_linear): the screened layers are those a MEASUREMENT put on the matrix-core narrow kernel (none under
+        narrow=True; an 'auto' layer does not switch the screen off: it runs in the reference's order for this call), screened against their narrow records; layers
+        measured during a pass were measured on this very batch, so only the records that existed before it are screened."""
         keyed = self._keyed()
         on_dev = x.is_cuda and x.dim() == 2
         read = on_dev and not torch.cuda.is_current_stream_capturing() and self.RESCREEN_READ
@@ -304,18 +268,18 @@ class KeyedModel(object):
         while todo:
             k = todo.pop(0)
             screened = set()
-            if on_dev and self.RESCREEN and not any(getattr(c, '_exact', True) == 'auto' for c in keyed):
-                screened = set(j for (j, c) in enumerate(keyed) if c.screened())
+            if on_dev and self.RESCREEN and (narrow == 'mfma' if narrow else not any(getattr(c, '_exact', True) == 'auto' for c in keyed)):
+                screened = set(j for (j, c) in enumerate(keyed) if (c.narrow_screened() if narrow else c.screened()))
             slots = torch.zeros(len(keyed) + 1, dtype=torch.float32, device=x.device) if screened else None
             (lo, hi) = windows[k]
             # (a window of a wider block: its own feature-major block, so that the pass can take the overlapped form)
-            ys[k] = self._forward_once(x if len(windows) == 1 else x[lo:hi].t().contiguous().t(), overlap, slots, screened)
+            ys[k] = self._forward_once(x if len(windows) == 1 else x[lo:hi].t().contiguous().t(), keyed, overlap, slots, screened, narrow, rows)
             if slots is None:
                 continue
             screens.append((slots, screened))
             if not read or (todo and redos + 1 == self.RESCREEN_MAX_PASSES):
                 continue
-            if self._rescreen(slots.tolist(), keyed, screened) and redos + 1 < self.RESCREEN_MAX_PASSES:
+            if self._rescreen(slots.tolist(), keyed, screened, bool(narrow)) and redos + 1 < self.RESCREEN_MAX_PASSES:
                 redos += 1
                 todo = [k] + [j for j in range(len(windows)) if j != k]
         return (ys[0] if len(ys) == 1 else torch.cat([y.t() for y in ys], dim=1).t(), screens)
@@ -326,38 +290,32 @@ class KeyedModel(object):
         records; an outgrown one is dropped (measured again by the next narrow='mfma' pass, on that batch), the wide decision and the launch lists stay."""
         redo = [k for k in sorted(screened) if keyed[k].rescreen(xmax[k], narrow=narrow)]
         for k in redo:
-            c = keyed[k]
-            rec = c._contract_record['narrow'] if narrow else c._contract_record
-            klayer._log.info('keynet_amd: %s: max |x| = %.3g against %.3g at %s: re-calibrating on this batch', c._repr, xmax[k], rec['max_abs_x'],
+            klayer._log.info('keynet_amd: %s: max |x| = %.3g against %.3g at %s: re-calibrating on this batch', keyed[k]._repr, xmax[k], keyed[k].screen_record(narrow)['max_abs_x'],
                              'its narrow measurement' if narrow else 'calibration')
-            if narrow:
-                c._contract_record.pop('narrow', None)
-                continue
-            c._exact = 'auto'
-            c.__dict__.pop('_contract_record', None)
-        if redo and narrow:
-            self.__dict__['_narrow_remeasurements'] = self.__dict__.get('_narrow_remeasurements', 0) + len(redo)
-        elif redo:
-            self.__dict__['_recalibrations'] = self.__dict__.get('_recalibrations', 0) + len(redo)
-            self._drop_plans()
+            keyed[k].unscreen(narrow)
+        if redo:
+            count = '_narrow_remeasurements' if narrow else '_recalibrations'
+            self.__dict__[count] = self.__dict__.get(count, 0) + len(redo)
+            if not narrow:
+                self._drop_plans()
         return redo
 
     BATCH_TILE = 128           # _prepare pads a device batch of a tiled-conv key-net to whole multiples of this many images
     MAX_BLOCK_ELEMENTS = 1 << 31   # ... and splits a batch whose largest layer would hold this many activations or more into passes
 
-    def _forward_once(self, img_cipher, overlap, slots, screened):
-        """One pass over the keyed layers.  `slots` (device f32 [L + 1], zeroed) / `screened` (indices of the keyed layers whose contract
+    def _forward_once(self, img_cipher, keyed, overlap, slots, screened, narrow=False, rows=False):
+        """One pass over the keyed layers `keyed` (_keyed()).  `slots` (device f32 [L + 1], zeroed) / `screened` (indices of the keyed layers whose contract
         is re-screened): slot k receives max |x| of keyed layer k -- slot 0 by one pass over the input, slot k + 1 by the kernel that
-        produces layer k's output."""
+        produces layer k's output.  `narrow` / `rows`: every layer in its narrow form (KeyedLayer.forward); the whole-net kernel only where no layer has one."""
         forced = overlap is True
         if overlap is None and not self.OVERLAP_AUTO:
             overlap = False
-        if any(getattr(c, '_exact', True) == 'auto' for c in self._keyed()):
+        if any(getattr(c, '_exact', True) == 'auto' for c in keyed):
             overlap = False        # first forward of an 'auto' key-net: the layers calibrate their contract one by one (KeyedLayer._calibrate)
         if overlap is None:
             overlap = (img_cipher.is_cuda and img_cipher.dtype == torch.float32 and img_cipher.dim() == 2 and img_cipher.shape[0] >= 256 and
                        img_cipher.shape[0] % 256 == 0 and img_cipher.t().is_contiguous() and not torch.cuda.is_current_stream_capturing())
-        if not forced and img_cipher.is_cuda and img_cipher.dim() == 2 and not screened:
+        if not forced and img_cipher.is_cuda and img_cipher.dim() == 2 and not screened and not (narrow and any(c.W.narrow_capable() for c in keyed)):
             chain = self._chain_op(img_cipher.device)
             if chain is not None:
                 return self._forward_chain(img_cipher, chain)
@@ -372,7 +330,7 @@ class KeyedModel(object):
             if k is None:
                 y = _relu_block(y)
             else:
-                y = c.forward(y, fuse_relu=relu, absmax=slots[k + 1:k + 2] if (slots is not None and (k + 1) in screened) else None)
+                y = c.forward(y, fuse_relu=relu, absmax=slots[k + 1:k + 2] if (slots is not None and (k + 1) in screened) else None, narrow=narrow, narrow_rows=rows)
         return y
 
     # -- whole-net kernel: every operator of a small untiled key-net in ONE launch, activations in LDS (csrc/kn_chain.hip) --------
@@ -638,27 +596,25 @@ class KeyedModel(object):
         `narrow_rows=True` (only with `narrow`): the graph of forward_linear(narrow=..., narrow_rows=True): the same straight line of launches."""
         assert img_cipher.is_cuda, 'capture() needs a device tensor'
         n = img_cipher.shape[0]
-        if narrow_rows and not narrow:
-            raise ValueError('narrow_rows=True is a form of the narrow forward: pass narrow=True or narrow=\'mfma\' with it')
-        if narrow:
-            return self._capture_narrow(img_cipher, narrow, bool(narrow_rows))
-        (static_in, windows) = self._prepare(img_cipher.detach().t().clone(memory_format=torch.contiguous_format).t())     # the graph's own input block
+        (mode, rows) = ksp._narrow_args(n, narrow, narrow_rows)
+        src = img_cipher.detach().float() if mode else img_cipher.detach()
+        (static_in, windows) = self._prepare(src.t().clone(memory_format=torch.contiguous_format).t(), mode)     # the graph's own input block
         keyed = self._keyed()
         state = {}
 
         def build():
-            self._forward_passes(static_in, windows, False)       # uploads operators, sizes workspaces, calibrates (not capturable)
+            self._forward_passes(static_in, windows, False, mode, rows)       # uploads operators, sizes workspaces, calibrates (not capturable)
             torch.cuda.synchronize()
             side = torch.cuda.Stream()
             side.wait_stream(torch.cuda.current_stream())
             with torch.cuda.stream(side):
-                self._forward_passes(static_in, windows, False)   # warm-up on the capture stream
+                self._forward_passes(static_in, windows, False, mode, rows)   # warm-up on the capture stream
             torch.cuda.current_stream().wait_stream(side)
             graph = torch.cuda.CUDAGraph()
             # capture ON THE WARMED STREAM: per-stream state of the operators (the split-K workspace of a dense layer, kn_api.hip) was sized
             # by the warm-up forward above; torch's default capture stream would be a fresh one, and a hipMalloc inside a capture is refused
             with torch.cuda.graph(graph, stream=side):
-                (out, screens) = self._forward_passes(static_in, windows, False)
+                (out, screens) = self._forward_passes(static_in, windows, False, mode, rows)
             state.update(graph=graph, out=out[:n], screens=screens)
 
         build()
@@ -666,43 +622,8 @@ class KeyedModel(object):
         def replay(x):
             static_in[:n].copy_(x)
             state['graph'].replay()
-            if any(self._rescreen(slots.tolist(), keyed, screened) for (slots, screened) in state['screens']):
-                build()                                          # eager forward on this batch re-calibrates; then a fresh graph
-                state['graph'].replay()
-            replay.graph = state['graph']
-            return state['out']
-        replay.graph = state['graph']
-        return replay
-
-    def _capture_narrow(self, img_cipher, mode=True, rows=False):
-        """capture(narrow=True | 'mfma'): one eager narrow forward (operators resident, narrow records measured), a warm-up on the capture stream (per-stream state
-        of the operators), then the capture."""
-        if img_cipher.shape[0] > self.NARROW_MAX:
-            raise ValueError('narrow=%r takes at most %d images, got %d' % (mode, self.NARROW_MAX, img_cipher.shape[0]))
-        static_in = img_cipher.detach().float().t().clone(memory_format=torch.contiguous_format).t()      # the graph's own feature-major input block
-        keyed = self._keyed()
-        state = {}
-
-        def build():
-            self._forward_narrow(static_in, mode, rows)
-            torch.cuda.synchronize()
-            side = torch.cuda.Stream()
-            side.wait_stream(torch.cuda.current_stream())
-            with torch.cuda.stream(side):
-                self._forward_narrow(static_in, mode, rows)
-            torch.cuda.current_stream().wait_stream(side)
-            graph = torch.cuda.CUDAGraph()
-            with torch.cuda.graph(graph, stream=side):
-                (out, screens) = self._forward_narrow(static_in, mode, rows)
-            state.update(graph=graph, out=out, screens=screens)
-
-        build()
-
-        def replay(x):
-            static_in.copy_(x)
-            state['graph'].replay()
-            if any(self._rescreen(slots.tolist(), keyed, screened, narrow=True) for (slots, screened) in state['screens']):
-                build()                                          # the eager forward on this batch measures again; then a fresh graph
+            if any(self._rescreen(slots.tolist(), keyed, screened, bool(mode)) for (slots, screened) in state['screens']):
+                build()                                          # eager forward on this batch re-calibrates (narrow: measures again); then a fresh graph
                 state['graph'].replay()
             replay.graph = state['graph']
             return state['out']

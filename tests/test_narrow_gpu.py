@@ -13,6 +13,7 @@ from keynet_amd import _capi
 from keynet_amd.layer import KeyedLayer
 from test_parity_gpu import _random_convtaps, close, dev
 from fuzz_nets import random_net
+from narrow_helpers import _spmm
 
 pytestmark = pytest.mark.gpu
 
@@ -98,17 +99,6 @@ def test_narrow_kernel_against_the_oracle_and_the_128_column_kernels(case, n_vec
     assert torch.equal(y, y128[:, :n_vecs])
 
 
-def _spmm(op, xd, n, flags, ld=None):
-    """kn_spmm on the first n columns of the contiguous block xd [cols, ldx]: (result [rows, n] as a tensor, plan string)."""
-    (rows, _) = op.shape()
-    ldx = int(xd.shape[1])
-    y = torch.full((rows, n), 7.5, dtype=torch.float32, device=xd.device)
-    with torch.cuda.device(xd.device):
-        op.spmm(xd.data_ptr(), ldx, n, y.data_ptr(), n, flags, torch.cuda.current_stream().cuda_stream)
-        plan = op.plan(n, flags, ldx=ldx, ldy=n)
-    return (y, plan)
-
-
 def test_flag_semantics():
     """KN_FLAG_NARROW alone, with KN_FLAG_EXACT and with KN_FLAG_BF16X3 are the same bits; at nine columns the flag is ignored; without the flag nothing moved."""
     (W, M, X, _) = _build(('semantics', 16, 64, 8, 3, 1, True, True), seed=9)
@@ -118,21 +108,21 @@ def test_flag_semantics():
         t = W._taps
         op2 = _capi.Operator.convtaps(W._inshape, W._outshape, t['taps'], t['ent_out'], t['ent_in'], t['ent_tap'], t['ent_coef'], t['lastcol'])      # a second handle of the same operator
     for n in (1, 4, 8):
-        (ye, pe) = _spmm(op, xd, n, EXACT | NARROW)
+        (ye, _, pe) = _spmm(op, xd, n, EXACT | NARROW)
         for flags in (NARROW, NARROW | BF16X3, NARROW | BF16X3 | EXACT):
-            (y, p) = _spmm(op, xd, n, flags)
+            (y, _, p) = _spmm(op, xd, n, flags)
             assert KERNEL in p and torch.equal(y, ye), (n, flags, p)
         assert np.array_equal(ye.cpu().numpy(), _oracle(M, X[:, :n]))
-        (yr, _) = _spmm(op, xd, n, NARROW | RELU)
+        (yr, _, _) = _spmm(op, xd, n, NARROW | RELU)
         assert torch.equal(yr, torch.clamp(ye, min=0))
     for flags in (0, EXACT, BF16X3):
-        (y9, p9) = _spmm(op, xd, 9, flags | NARROW)
-        (y0, p0) = _spmm(op, xd, 9, flags)
+        (y9, _, p9) = _spmm(op, xd, 9, flags | NARROW)
+        (y0, _, p0) = _spmm(op, xd, 9, flags)
         assert KERNEL not in p9 and p9 == p0 and torch.equal(y9, y0), (flags, p9, p0)
     for n in (1, 8, 64):                                                # without the flag: plan and bits as on a handle that never saw it
         for flags in (0, EXACT, RELU, BF16X3):
-            (ya, pa) = _spmm(op, xd, n, flags)
-            (yb, pb) = _spmm(op2, xd, n, flags)
+            (ya, _, pa) = _spmm(op, xd, n, flags)
+            (yb, _, pb) = _spmm(op2, xd, n, flags)
             assert KERNEL not in pa and pa == pb and torch.equal(ya, yb), (n, flags, pa, pb)
     with torch.cuda.device(dev()):
         assert 'convtaps_exact_kernel' in op.plan(64, EXACT)            # (what the existing tests pin at 64 columns)
@@ -146,8 +136,8 @@ def test_a_csr_operator_ignores_the_flag():
     xd = torch.as_tensor(rng.randn(30, 8).astype(np.float32)).to(dev())
     with torch.cuda.device(dev()):
         op = W._device_op(dev())
-    (y1, p1) = _spmm(op, xd, 4, EXACT | NARROW)
-    (y0, p0) = _spmm(op, xd, 4, EXACT)
+    (y1, _, p1) = _spmm(op, xd, 4, EXACT | NARROW)
+    (y0, _, p0) = _spmm(op, xd, 4, EXACT)
     assert p1 == p0 and torch.equal(y1, y0)
 
 

@@ -14,6 +14,7 @@ from keynet_amd import _capi
 from keynet_amd.layer import KeyedLayer, gate
 from test_parity_gpu import _random_convtaps, close, close_conditioned, dev
 from test_narrow_gpu import SHAPES as NARROW_SHAPES, _build, _last, _oracle, _sorted_csr, _spmm
+from narrow_helpers import _spmm_calls
 
 pytestmark = pytest.mark.gpu
 
@@ -78,25 +79,25 @@ def test_flag_semantics():
         t = W._taps
         op2 = _capi.Operator.convtaps(W._inshape, W._outshape, t['taps'], t['ent_out'], t['ent_in'], t['ent_tap'], t['ent_coef'], t['lastcol'])
     for n in (1, 4, 8):
-        (ym, pm) = _spmm(op, xd, n, MFMA)
+        (ym, _, pm) = _spmm(op, xd, n, MFMA)
         assert KERNEL in pm, pm
-        (yn, pn) = _spmm(op, xd, n, NARROW)
+        (yn, _, pn) = _spmm(op, xd, n, NARROW)
         assert close_conditioned(ym.cpu().numpy().T, yn.cpu().numpy().T, (M.shape, M.indptr, M.indices, M.data), X[:, :n].T)
         for extra in (EXACT, EXACT | RELU, EXACT | BF16X3):
-            (y, p) = _spmm(op, xd, n, MFMA | extra)
-            (y0, p0) = _spmm(op, xd, n, NARROW | extra)
+            (y, _, p) = _spmm(op, xd, n, MFMA | extra)
+            (y0, _, p0) = _spmm(op, xd, n, NARROW | extra)
             assert KERNEL not in p and p == p0 and torch.equal(y, y0), (n, extra, p, p0)
-        (y, p) = _spmm(op, xd, n, MFMA | NARROW)                          # both flags: the matrix-core form
+        (y, _, p) = _spmm(op, xd, n, MFMA | NARROW)                          # both flags: the matrix-core form
         assert p == pm and torch.equal(y, ym)
     for flags in (0, EXACT, BF16X3):
-        (y9, p9) = _spmm(op, xd, 9, flags | MFMA)
-        (y0, p0) = _spmm(op, xd, 9, flags | NARROW)
-        (yp, pp) = _spmm(op, xd, 9, flags)
+        (y9, _, p9) = _spmm(op, xd, 9, flags | MFMA)
+        (y0, _, p0) = _spmm(op, xd, 9, flags | NARROW)
+        (yp, _, pp) = _spmm(op, xd, 9, flags)
         assert KERNEL not in p9 and p9 == p0 == pp and torch.equal(y9, y0) and torch.equal(y9, yp), (flags, p9, p0)
     for n in (1, 8, 64):
         for flags in (0, EXACT, RELU, BF16X3, NARROW):
-            (ya, pa) = _spmm(op, xd, n, flags)
-            (yb, pb) = _spmm(op2, xd, n, flags)
+            (ya, _, pa) = _spmm(op, xd, n, flags)
+            (yb, _, pb) = _spmm(op2, xd, n, flags)
             assert KERNEL not in pa and pa == pb and torch.equal(ya, yb), (n, flags, pa, pb)
     # a CSR operator
     import scipy.sparse
@@ -104,8 +105,8 @@ def test_flag_semantics():
     xs = torch.as_tensor(np.random.RandomState(2).randn(30, 8).astype(np.float32)).to(dev())
     with torch.cuda.device(dev()):
         opc = ksp.SparseMatrix(A)._device_op(dev())
-    (y1, p1) = _spmm(opc, xs, 4, EXACT | MFMA)
-    (y0, p0) = _spmm(opc, xs, 4, EXACT | NARROW)
+    (y1, _, p1) = _spmm(opc, xs, 4, EXACT | MFMA)
+    (y0, _, p0) = _spmm(opc, xs, 4, EXACT | NARROW)
     assert p1 == p0 and torch.equal(y1, y0)
     # the filled-in 9 x 9 operator: more than 64 slots per pixel, many on one (pixel, tap) pair
     filled = [c for c in NARROW_SHAPES if c[0].startswith('filled')][0]
@@ -114,8 +115,8 @@ def test_flag_semantics():
     with torch.cuda.device(dev()):
         opf = Wf._device_op(dev())
     for n in (1, 5):
-        (y1, p1) = _spmm(opf, xf, n, MFMA | RELU)
-        (y0, p0) = _spmm(opf, xf, n, NARROW | RELU)
+        (y1, _, p1) = _spmm(opf, xf, n, MFMA | RELU)
+        (y0, _, p0) = _spmm(opf, xf, n, NARROW | RELU)
         assert KERNEL not in p1 and LANE in p1 and p1 == p0 and torch.equal(y1, y0), (n, p1, p0)
 
 
@@ -328,18 +329,6 @@ def test_capture(golden, mode):
         knet.capture(torch.cat([x, x, x])[:9], narrow='mfma')
 
 
-def _spmm_calls(monkeypatch):
-    """Records (plan of the call, flags) of every kn_spmm / kn_spmm_screen the Python host issues from here on: the path a forward really takes."""
-    calls = []
-    spmm = _capi.Operator.spmm
-
-    def recording(self, x_ptr, ldx, n_vecs, y_ptr, ldy, flags, stream, absmax_ptr=None):
-        calls.append((self.plan(n_vecs, flags, ldx=ldx, ldy=ldy), int(flags)))
-        return spmm(self, x_ptr, ldx, n_vecs, y_ptr, ldy, flags, stream, absmax_ptr)
-    monkeypatch.setattr(_capi.Operator, 'spmm', recording)
-    return calls
-
-
 @pytest.mark.parametrize('n', [1, 3, 8])
 def test_the_forward_itself_launches_the_kernel(golden, monkeypatch, n):
     """Not the planner's word for it: the kn_spmm calls forward_linear(x[:n], narrow='mfma') ISSUES on a declared key-net carry KN_FLAG_NARROW_MFMA once per
@@ -388,12 +377,12 @@ def test_the_shape_that_keeps_the_channel_lane_kernel():
     with torch.cuda.device(dev()):
         op = W._device_op(dev())
     for n in (5, 8):
-        (y, plan) = _spmm(op, xd, n, MFMA)
-        (ye, plan_e) = _spmm(op, xd, n, NARROW)
+        (y, _, plan) = _spmm(op, xd, n, MFMA)
+        (ye, _, plan_e) = _spmm(op, xd, n, NARROW)
         assert plan == plan_e and LANE in plan and KERNEL not in plan and torch.equal(y, ye), plan
-    (y4, plan) = _spmm(op, xd, 4, MFMA)
+    (y4, _, plan) = _spmm(op, xd, 4, MFMA)
     assert KERNEL in plan, plan
-    (ye4, _) = _spmm(op, xd, 4, NARROW)
+    (ye4, _, _) = _spmm(op, xd, 4, NARROW)
     assert gate(y4, ye4)[0] <= 1.0
     for (cin, h) in ((5, 64), (3, 32)):
         V = _random_convtaps(rng, cin, 64, h, 3, 1, True, True)

@@ -14,12 +14,12 @@ from keynet_amd import sparse as ksp
 from keynet_amd import _capi
 from test_parity_gpu import dev
 from test_narrow_gpu import _build, _last
+from narrow_helpers import SENTINEL, _spmm, _spmm_calls
 
 pytestmark = pytest.mark.gpu
 
 (RELU, EXACT, NARROW, MFMA, ROWS) = (_capi.KN_FLAG_RELU, _capi.KN_FLAG_EXACT, _capi.KN_FLAG_NARROW, _capi.KN_FLAG_NARROW_MFMA, _capi.KN_FLAG_NARROW_ROWS)
 KERNEL = 'csr_narrow_kernel'
-SENTINEL = 7.5
 
 
 # ---- operators: each the smallest that reaches its role -------------------------------------------------------------------------------------------------
@@ -108,20 +108,6 @@ def _ref(csr, X):
 
 def _relu(r):
     return np.where(r < 0, np.float32(0), r)                            # torch relu: NaN stays NaN
-
-
-def _spmm(op, xd, n, flags, ld=None, start=0, absmax=None):
-    """kn_spmm on columns start .. start + n of the contiguous block xd [cols, ldx] into the same window of a sentinel-filled block with ldy = ld (None: compact):
-    (the window as a tensor, the whole y block, the plan)."""
-    (rows, _) = op.shape()
-    ldx = int(xd.shape[1])
-    ldy = n if ld is None else ld
-    y = torch.full((rows, ldy), SENTINEL, dtype=torch.float32, device=xd.device)
-    with torch.cuda.device(xd.device):
-        op.spmm(xd.data_ptr() + 4 * start, ldx, n, y.data_ptr() + 4 * start, ldy, flags, torch.cuda.current_stream().cuda_stream,
-                absmax_ptr=None if absmax is None else absmax.data_ptr())
-        plan = op.plan(n, flags, ldx=ldx, ldy=ldy)
-    return (y[:, start:start + n], y, plan)
 
 
 def _nv(n):
@@ -367,18 +353,6 @@ def test_whole_keynets(golden, name):
     print(name, 'max |narrow_rows - reference| =', float(np.abs(out - _last(z)).max()))
     assert np.array_equal(out, _last(z))
     assert knet._padded_forwards == 0
-
-
-def _spmm_calls(monkeypatch):
-    """Records (plan of the call, flags) of every kn_spmm / kn_spmm_screen the Python host issues from here on: the path a forward really takes."""
-    calls = []
-    spmm = _capi.Operator.spmm
-
-    def recording(self, x_ptr, ldx, n_vecs, y_ptr, ldy, flags, stream, absmax_ptr=None):
-        calls.append((self.plan(n_vecs, flags, ldx=ldx, ldy=ldy), int(flags)))
-        return spmm(self, x_ptr, ldx, n_vecs, y_ptr, ldy, flags, stream, absmax_ptr)
-    monkeypatch.setattr(_capi.Operator, 'spmm', recording)
-    return calls
 
 
 @pytest.mark.parametrize('n', [1, 3, 8])

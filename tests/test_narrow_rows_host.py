@@ -13,7 +13,7 @@ from keynet_amd import _capi
 from keynet_amd import sparse as ksp
 from keynet_amd import system as ksys
 from keynet_amd.build import SOURCES
-from keynet_amd.layer import KeyedLayer
+from keynet_amd.layer import CONTRACTS, KeyedLayer, _contract
 from test_isa_lint import FUSED, INT_DIVISION_LITERALS, _isa, _kernel_bodies
 from test_narrow_host import _tiny_conv
 
@@ -113,3 +113,102 @@ def test_kernel_isa_has_no_fused_multiply_add_and_no_scratch(tmp_path):
     for m in entries:
         k = re.compile(r'\.private_segment_fixed_size:\s+(\d+)').search(s, m.end())
         assert k and int(k.group(1)) == 0, m.group(1)
+
+
+(BF16X3, MFMA) = (_capi.KN_FLAG_BF16X3, _capi.KN_FLAG_NARROW_MFMA)
+# (contract, narrow, narrow_rows) -> the flag word without / with a fused ReLU; None = not one launch
+KERNEL_FLAGS_CONV = {
+    ('exact', False, False): (EXACT, RELU + EXACT),
+    ('exact', False, True): (EXACT, RELU + EXACT),
+    ('exact', True, False): (EXACT + NARROW, RELU + EXACT + NARROW),
+    ('exact', True, True): (EXACT + NARROW, RELU + EXACT + NARROW),
+    ('exact', 'mfma', False): (EXACT + NARROW, RELU + EXACT + NARROW),
+    ('exact', 'mfma', True): (EXACT + NARROW, RELU + EXACT + NARROW),
+    ('mfma', False, False): (0, RELU),
+    ('mfma', False, True): (0, RELU),
+    ('mfma', True, False): (NARROW, RELU + NARROW),
+    ('mfma', True, True): (NARROW, RELU + NARROW),
+    ('mfma', 'mfma', False): (MFMA, RELU + MFMA),
+    ('mfma', 'mfma', True): (MFMA, RELU + MFMA),
+    ('auto', False, False): (None, None),
+    ('auto', False, True): (None, None),
+    ('auto', True, False): (NARROW, RELU + NARROW),
+    ('auto', True, True): (NARROW, RELU + NARROW),
+    ('auto', 'mfma', False): (NARROW, RELU + NARROW),
+    ('auto', 'mfma', True): (NARROW, RELU + NARROW),
+    ('bf16x3', False, False): (BF16X3, RELU + BF16X3),
+    ('bf16x3', False, True): (BF16X3, RELU + BF16X3),
+    ('bf16x3', True, False): (BF16X3 + NARROW, RELU + BF16X3 + NARROW),
+    ('bf16x3', True, True): (BF16X3 + NARROW, RELU + BF16X3 + NARROW),
+    ('bf16x3', 'mfma', False): (MFMA, RELU + MFMA),
+    ('bf16x3', 'mfma', True): (MFMA, RELU + MFMA),
+    ('split', False, False): (None, None),
+    ('split', False, True): (None, None),
+    ('split', True, False): (NARROW, RELU + NARROW),
+    ('split', True, True): (NARROW, RELU + NARROW),
+    ('split', 'mfma', False): (MFMA, RELU + MFMA),
+    ('split', 'mfma', True): (MFMA, RELU + MFMA),
+}
+KERNEL_FLAGS_CSR = {
+    ('exact', False, False): (EXACT, RELU + EXACT),
+    ('exact', False, True): (EXACT + ROWS, RELU + EXACT + ROWS),
+    ('exact', True, False): (EXACT, RELU + EXACT),
+    ('exact', True, True): (EXACT + ROWS, RELU + EXACT + ROWS),
+    ('exact', 'mfma', False): (EXACT, RELU + EXACT),
+    ('exact', 'mfma', True): (EXACT + ROWS, RELU + EXACT + ROWS),
+    ('mfma', False, False): (EXACT, RELU + EXACT),
+    ('mfma', False, True): (EXACT + ROWS, RELU + EXACT + ROWS),
+    ('mfma', True, False): (EXACT, RELU + EXACT),
+    ('mfma', True, True): (EXACT + ROWS, RELU + EXACT + ROWS),
+    ('mfma', 'mfma', False): (EXACT, RELU + EXACT),
+    ('mfma', 'mfma', True): (EXACT + ROWS, RELU + EXACT + ROWS),
+    ('auto', False, False): (None, None),
+    ('auto', False, True): (None, None),
+    ('auto', True, False): (None, None),
+    ('auto', True, True): (None, None),
+    ('auto', 'mfma', False): (None, None),
+    ('auto', 'mfma', True): (None, None),
+    ('bf16x3', False, False): (EXACT, RELU + EXACT),
+    ('bf16x3', False, True): (EXACT + ROWS, RELU + EXACT + ROWS),
+    ('bf16x3', True, False): (EXACT, RELU + EXACT),
+    ('bf16x3', True, True): (EXACT + ROWS, RELU + EXACT + ROWS),
+    ('bf16x3', 'mfma', False): (EXACT, RELU + EXACT),
+    ('bf16x3', 'mfma', True): (EXACT + ROWS, RELU + EXACT + ROWS),
+    ('split', False, False): (EXACT, RELU + EXACT),
+    ('split', False, True): (EXACT + ROWS, RELU + EXACT + ROWS),
+    ('split', True, False): (EXACT, RELU + EXACT),
+    ('split', True, True): (EXACT + ROWS, RELU + EXACT + ROWS),
+    ('split', 'mfma', False): (EXACT, RELU + EXACT),
+    ('split', 'mfma', True): (EXACT + ROWS, RELU + EXACT + ROWS),
+}
+
+
+def test_kernel_flag_word_for_every_contract_and_narrow_form(monkeypatch):
+    """KeyedLayer.kernel() on the tiny conv-taps operator and on a 12 x 9 CSR operator, for every contract x narrow x narrow_rows x relu, against the two
+    tables above.  The tables were filled from kernel() as it stood BEFORE its flag word was assembled in one place (two early narrow returns and the
+    original rule): they pin that rule, the odd rows included -- a narrow conv launch keeps the contract's EXACT / BF16X3 next to NARROW, an 'mfma' launch
+    carries no contract flag, 'auto' and two-step 'split' are one launch when narrow, and kernel() itself sets NARROW_ROWS without `narrow` (launch() and
+    forward() are what tie it to a narrow forward).  Every launch is on the operator's own handle."""
+    conv = _tiny_conv()
+    csr = _csr_operator()
+    monkeypatch.setattr(csr, '_dense_device_op', lambda device=None: None, raising=False)      # (12 x 9: no dense handle; asking for one needs a device)
+    seen = 0
+    for (W, table) in ((conv, KERNEL_FLAGS_CONV), (csr, KERNEL_FLAGS_CSR)):
+        assert sorted(table, key=str) == sorted(((c, n, r) for c in CONTRACTS for n in (False, True, 'mfma') for r in (False, True)), key=str)
+        for ((name, narrow, rows), words) in table.items():
+            for (relu, want) in zip((False, True), words):
+                got = KeyedLayer.kernel(W, _contract(name, True), relu, None, narrow=narrow, narrow_rows=rows)
+                assert got == (None if want is None else (W._device_op, want)), (name, narrow, rows, relu, got)
+                seen += 1
+    assert seen == 2 * len(CONTRACTS) * 3 * 2 * 2
+    # ... and with a dense handle in play (a large keyed nn.Linear): the re-ordering contracts take it, with (0, RELU) and never NARROW_ROWS, whatever the keywords;
+    # 'exact' and 'auto' are the rows of KERNEL_FLAGS_CSR
+    dense = (lambda device=None: 'a dense handle')
+    monkeypatch.setattr(csr, '_dense_device_op', dense, raising=False)
+    for ((name, narrow, rows), words) in KERNEL_FLAGS_CSR.items():
+        for (relu, want) in zip((False, True), words):
+            got = KeyedLayer.kernel(csr, _contract(name, True), relu, None, narrow=narrow, narrow_rows=rows)
+            if name in ('mfma', 'bf16x3', 'split'):
+                assert got == (dense, RELU if relu else 0), (name, narrow, rows, relu, got)
+            else:
+                assert got == (None if want is None else (csr._device_op, want)), (name, narrow, rows, relu, got)

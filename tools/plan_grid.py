@@ -1,7 +1,8 @@
 """Dispatch grid of the conv-taps host side: which kernel kn_spmm would launch for which call, as text.
 
 Loads the library named by KEYNET_HIP_LIB (default: the product library) through keynet_amd/_capi.py WITHOUT torch, creates a fixed list of operators and
-prints, per operator, kn_nnz / kn_nnz_expanded / a hash of kn_export_csr and one line per (n_vecs, ldx = ldy, flags) with the text of kn_spmm_plan.  Nothing is
+prints, per operator, kn_nnz / kn_nnz_expanded / a hash of kn_export_csr and one line per (n_vecs, ldx = ldy, flags) with the text of kn_spmm_plan; the
+batches include 1, 2, 3, 4, 8 and 9 columns and the flags the three narrow ones (KN_FLAG_NARROW, _MFMA, _ROWS), and three float32 CSR operators close the list.  Nothing is
 launched, so the KN_HOST_PACK_ONLY build answers on a machine without a GPU.  Two builds of the library dispatch alike when their outputs are byte-identical:
 
     KEYNET_HIP_LIB=/path/to/libkeynet_hip.so python tools/plan_grid.py > grid.txt
@@ -21,17 +22,20 @@ capi = importlib.util.module_from_spec(spec)
 spec.loader.exec_module(capi)
 GOLD = os.path.join(ROOT, 'tests', 'golden')
 
-BATCHES = (1, 2, 64, 128, 130, 256, 384, 1024, 4096)
+BATCHES = (1, 2, 3, 4, 8, 9, 64, 128, 130, 256, 384, 1024, 4096)
 FLAGS = (0, capi.KN_FLAG_RELU, capi.KN_FLAG_EXACT, capi.KN_FLAG_EXACT | capi.KN_FLAG_RELU, capi.KN_FLAG_BF16X3)
+# the three narrow flags as the Python host sets them (KeyedLayer.kernel), at every batch: beyond 8 columns the library ignores them
+FLAGS += (capi.KN_FLAG_NARROW, capi.KN_FLAG_NARROW | capi.KN_FLAG_EXACT | capi.KN_FLAG_RELU, capi.KN_FLAG_NARROW | capi.KN_FLAG_BF16X3, capi.KN_FLAG_NARROW_MFMA,
+          capi.KN_FLAG_NARROW_MFMA | capi.KN_FLAG_RELU, capi.KN_FLAG_NARROW_ROWS | capi.KN_FLAG_EXACT, capi.KN_FLAG_NARROW_ROWS | capi.KN_FLAG_EXACT | capi.KN_FLAG_RELU)
 SWITCHES = (('KN_NO_SPTR', '1'), ('KN_NO_SMALLK_PIPE', '1'), ('KN_NO_EXACT_TABLE', '1'), ('KN_NO_FILL_EXACT', '1'), ('KN_NO_FILL_TILES2', '1'), ('KN_TABLE_NRB', '2'))
 EXPORT_MAX_NNZ = 1 << 22
 
 
-def report(name, op, out):
+def report(name, op, out, export=True):
     L = capi.lib()
     nx = op.nnz_expanded()
     digest = '-'
-    if nx <= EXPORT_MAX_NNZ:
+    if nx <= EXPORT_MAX_NNZ and export:
         try:
             h = hashlib.sha256()
             for a in op.export_csr():
@@ -126,6 +130,13 @@ def main():
     D[-1, :] = 0
     D[-1, -1] = 1
     with_switches('dense 37x513', lambda: capi.Operator.dense(D), out)
+    # float32 CSR operators (KN_FLAG_NARROW_ROWS): scattered rows, a pool-like operator (loose rows only), a keyed-Linear-like one with a big pattern group
+    import scipy.sparse
+    pool = scipy.sparse.kron(scipy.sparse.identity(40), np.full((1, 4), 0.25)).tocsr()
+    for (name, M) in (('csr random 300x257', scipy.sparse.random(300, 257, density=0.1, format='csr', random_state=2)), ('csr pool 40x160', pool),
+                      ('csr linear 300x2100', scipy.sparse.csr_matrix(rng.randn(300, 2100)))):
+        M = M.astype(np.float32)
+        report(name, capi.Operator.csr(M.shape, M.indptr.astype(np.int32), M.indices.astype(np.int32), M.data), out, export=False)
 
 
 if __name__ == '__main__':
