@@ -91,6 +91,16 @@ enum kn_status {
                               Honoured by kn_spmm, by kn_spmm_screen (max |Y| by the library's reduction pass over Y) and by kn_spmm_plan, which names the kernel, NV and the
                               rows-per-wavefront form.  No reference counterpart. */
 
+#define KN_FLAG_NARROW32 64u  /* a MODIFIER of KN_FLAG_NARROW and KN_FLAG_NARROW_MFMA: with either of them on a conv-taps handle it raises that flag's column range from 8 to 32.
+                              For 9 <= n_vecs <= 32 KN_FLAG_NARROW then runs convtaps_narrow32_kernel -- the channel-lane order-preserving kernel with the columns in blocks of
+                              NV = 8 | 16 | 32 running sums per lane, bit for bit the result of KN_FLAG_EXACT -- and KN_FLAG_NARROW_MFMA runs convtaps_narrow_mfma_kernel at NV = 16 | 32
+                              (two pixels | one pixel per 32-column tile): the association of a column's sum depends on the K split alone, so every column has the bits the flag
+                              gives that column in a batch of at most 8.  Every rule of the two flags carries over: KN_FLAG_EXACT, an ineligible operator and the Cin <= 4 shape
+                              (beyond 4 columns on a chip-filling layer) turn KN_FLAG_NARROW_MFMA into KN_FLAG_NARROW, and the size rule REFUSES (KN_ERR_UNSUPPORTED, no fall-back)
+                              unless (D + 1) * ldx + 32 < 2^31.
+                              Where it changes NOTHING (same kernels, same plan string, same bits as without it): without one of the two flags; at n_vecs <= 8; at n_vecs > 32;
+                              on CSR, dense, float64 and chain handles.  kn_spmm_plan names the kernel, NV and the number of column blocks.  No reference counterpart. */
+
 typedef struct kn_operator* kn_handle_t;   /* opaque keyed operator resident in HBM */
 
 int         kn_abi_version(void);
@@ -214,7 +224,8 @@ int kn_export_csr_f64(kn_handle_t h, int32_t* indptr, int32_t* indices, double* 
  *   conv-taps, KN_FLAG_EXACT, filled-in operators       4 * ldx < 2^24, 4 * HiWi * ldx < 2^32, HiWi < 2^24  else the plain order-preserving kernel
  *   CSR, KN_FLAG_NARROW_ROWS (n_vecs <= 8)               cols * ldx + 8 < 2^30                              else the kernels the call takes without the flag
  * The small-K matrix-core kernels of first-layer operators (slots * Cin + bias <= 28 contraction rows) form row * ldx in 64 bits and take any ldx.
- * KN_FLAG_NARROW / KN_FLAG_NARROW_MFMA (n_vecs <= 8 on a conv-taps operator) do NOT fall back: they return KN_ERR_UNSUPPORTED, Y untouched, unless (D + 1) * ldx + 8 < 2^31.
+ * KN_FLAG_NARROW / KN_FLAG_NARROW_MFMA (n_vecs <= 8 on a conv-taps operator) do NOT fall back: they return KN_ERR_UNSUPPORTED, Y untouched, unless (D + 1) * ldx + 8 < 2^31
+ * (with KN_FLAG_NARROW32 at 9 <= n_vecs <= 32: unless (D + 1) * ldx + 32 < 2^31).
  * kn_spmm_plan names the kernel a call takes; tests/test_large_offsets_gpu.py runs each of these on both sides of its threshold. */
 int kn_spmm(kn_handle_t h, const float* x_dev, int64_t ldx, int64_t n_vecs,
             float* y_dev, int64_t ldy, uint32_t flags, void* stream);

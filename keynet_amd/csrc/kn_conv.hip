@@ -1429,12 +1429,233 @@ __global__ __launch_bounds__(256) void convtaps_narrow_kernel(ConvArgs p, int n_
     }
 }
 
-// ---- matrix-core path for 1 .. 8 batch columns (KN_FLAG_NARROW_MFMA): an implicit GEMM whose N dimension is output pixels x images ---------------
+// ---- order-preserving path for 9 .. 32 batch columns (KN_FLAG_NARROW32 next to KN_FLAG_NARROW): lanes are OUTPUT CHANNELS, columns come in blocks ---
+// convtaps_narrow_kernel's work item and arithmetic, statement for statement (input channel outer, the pixel's slots by ascending input pixel inner, DUPS committed
+// when the walk reaches the next pixel pair, separate multiply and add, the bias entry where it is stored, ReLU), with three differences of FORM:
+//   * work items are (column block, channel block, pixel), pixel fastest: a wavefront owns the NV (8 | 16 | 32) columns c0 = block * NV ..
+//     of its pixel and channel block.  Columns are independent sums, so the blocking cannot change a bit; which width runs is spmm_narrow32's rule.
+//   * a block that the batch does not fill (nh < NV real columns: widths 9 .. 15, 17 .. 31 and the last block of the others) still fetches a step's activations as
+//     ONE segment of NV dwords at X + xo + c0 through the scalar cache.  The segment lies inside the caller's block whenever xo + c0 + NV <= the block's minimal
+//     extent (last row) * ldx + n_vecs, and because a pixel's slots ascend by input pixel that is tested ONCE per wavefront on the last channel's last slot: with a
+//     homogeneous row behind the activations every wavefront passes, without one only the pixels whose window touches the last input row at the last channel fail.
+//     Those walk with one vector load per step (lane l reads column min(l, nh - 1)) and v_readlane.  Surplus running sums are formed from the neighbouring row's
+//     first floats and are never stored.
+//   * NV = 8 | 16, two sets of operand registers in turn: the value rows and activation segments of batch k + 1 (U = 16 / NV steps) are issued before batch k is
+//     multiplied, and the slot records of batch k + 2 behind them -- a lone wavefront per SIMD (VGG-16 conv5_x) no longer waits record -> address -> operand per step.
+//     NV = 32 keeps ONE set, with the records a batch ahead: two sets are 64 scalar registers of activations, and every such form -- also one with two sets of value
+//     rows and one of activations, which the scheduler turns back into two -- compiled with scalar registers spilled into vector lanes (v_writelane).  What its lone
+//     wavefronts wait for per step is not hidden.  DUPS forms (the filled-in operators) keep one set as well -- the stored value being formed holds NV
+//     activations of its own -- and exist for NV = 8 | 16 only.
+// No LDS, no barriers, no atomics, no scratch; 32-bit element offsets into tapsT and X (narrow_limits).
+#pragma clang fp contract(off)
+template <int NV, bool DUPS, bool COEF>
+__global__ __launch_bounds__(256) void convtaps_narrow32_kernel(ConvArgs p, int n_cb, int n_colb, int64_t n_wg) {
+    static_assert(NV == 8 || NV == 16 || (NV == 32 && !DUPS), "column block widths");
+    constexpr int U = NV == 8 ? 2 : 1;                      // steps per batch
+    constexpr bool TWO = !DUPS && NV < 32;                  // two operand sets in turn (2 U NV = 32 scalar registers of activations)
+    const int64_t chunk = (n_wg + 7) >> 3;
+    const int64_t wg = (int64_t)(blockIdx.x & 7) * chunk + (blockIdx.x >> 3);
+    if (wg >= n_wg || (blockIdx.x >> 3) >= chunk) return;
+    const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+    const int lane = threadIdx.x & 63;
+    const uint32_t wi = (uint32_t)wg * 4u + (uint32_t)wave;      // (column block, channel block, pixel in processing order), pixel fastest; below 2^31: checked by the launcher
+    const uint32_t per_colb = (uint32_t)p.n_pix * (uint32_t)n_cb;
+    if (wi >= per_colb * (uint32_t)n_colb) return;                // (wave-uniform; no barriers in this kernel)
+    const int colb = (int)(wi / per_colb);
+    const uint32_t wr = wi - (uint32_t)colb * per_colb;
+    const int cb = (int)(wr / (uint32_t)p.n_pix);
+    const int o = __builtin_amdgcn_readfirstlane(p.pix_order[wr - (uint32_t)cb * (uint32_t)p.n_pix]);
+    const int s_beg = __builtin_amdgcn_readfirstlane(p.pix_ptr[o]);
+    const int n_slots = __builtin_amdgcn_readfirstlane(p.pix_ptr[o + 1]) - s_beg;
+    const int co = cb * 64 + lane;
+    const int c0 = colb * NV;                               // first column of this block, and how many of its NV columns the batch holds
+    const int nh = p.n_vecs - c0 < NV ? p.n_vecs - c0 : NV;
+    const int lcol = lane < nh ? lane : nh - 1;             // per-column path: the column lane l fetches for everybody
+    const uint32_t tap_stride = (uint32_t)p.cin_pad * (uint32_t)p.cout_pad, ci_x = (uint32_t)p.HiWi * (uint32_t)p.ldx, ldx = (uint32_t)p.ldx;
+
+    float acc[NV];
+#pragma unroll
+    for (int v = 0; v < NV; v++) acc[v] = 0.0f;
+    float ar = 0.0f, xcur[NV];                              // DUPS: the stored value being formed, the activations of its column ...
+#pragma unroll
+    for (int v = 0; v < NV; v++) xcur[v] = 0.0f;
+    uint32_t cur = 0xffffffffu;                             // ... and that column (activation row offset; none yet)
+    auto commit = [&]() {
+#pragma unroll
+        for (int v = 0; v < NV; v++) {
+            const float pr = ar * xcur[v];
+            acc[v] = acc[v] + pr;
+        }
+    };
+
+    const int total = p.Cin * n_slots;                      // steps of this pixel (31 bits: checked by the launcher against the longest slot list)
+    const float* const tap0 = p.tapsT + cb * 64;            // wave-uniform base of this channel block's value rows; the lane adds its channel
+    const float* const x0 = p.X + c0;                       // ... and of this column block's activations
+    struct Rec {                                            // the slot records of a batch as loaded
+        int32_t in[U], tap[U];
+        float cf[U];
+    };
+    struct Ops {                                            // a batch's value rows as loaded, and where its activations are
+        float a[U], cf[U];
+        uint32_t xo[U];
+    };
+    struct Act {                                            // a batch's activations as loaded
+        float x[U][NV];
+    };
+    int sf = 0;                                             // the record cursor: slot of the pixel
+    auto fetch = [&](Rec& r, const int qf) {                // the records of steps qf .. qf + U - 1 (beyond the pixel's last step: its first slot -- loaded, not used)
+#pragma unroll
+        for (int k = 0; k < U; k++) {
+            const int sk = qf + k < total ? sf : 0;
+            r.in[k] = p.slot_in[s_beg + sk];
+            r.tap[k] = p.slot_tap[s_beg + sk];
+            r.cf[k] = COEF ? p.slot_coef[s_beg + sk] : 1.0f;
+            if (++sf == n_slots) sf = 0;
+        }
+    };
+    int sa = 0;                                             // the operand cursor: slot of the pixel, input channel as activation / value row offsets
+    uint32_t xci = 0, tci = 0;
+    auto issue_a = [&](const Rec& r, Ops& w, const int qa) {      // the value-row loads of steps qa .. qa + U - 1
+        uint32_t to[U];
+#pragma unroll
+        for (int k = 0; k < U; k++) {
+            const bool live = qa + k < total;               // (beyond the end: channel 0 of the first slot)
+            w.xo[k] = (live ? xci : 0u) + (uint32_t)r.in[k] * ldx;
+            to[k] = (live ? tci : 0u) + (uint32_t)r.tap[k] * tap_stride;
+            w.cf[k] = r.cf[k];
+            if (++sa == n_slots) {
+                sa = 0;
+                xci += ci_x;
+                tci += (uint32_t)p.cout_pad;
+            }
+        }
+#pragma unroll
+        for (int k = 0; k < U; k++) w.a[k] = (tap0 + to[k])[lane];
+    };
+    auto issue_x = [&](const Ops& w, Act& x, auto seg) {    // ... and their activation loads; seg: whole segments (else one column per lane and v_readlane)
+#pragma unroll
+        for (int k = 0; k < U; k++) {
+            if constexpr (decltype(seg)::value) {
+#pragma unroll
+                for (int v = 0; v < NV; v++) x.x[k][v] = (x0 + w.xo[k])[v];
+            } else {
+                const int xv = __builtin_bit_cast(int, (x0 + w.xo[k])[lcol]);
+#pragma unroll
+                for (int v = 0; v < NV; v++) x.x[k][v] = __builtin_bit_cast(float, __builtin_amdgcn_readlane(xv, v));
+            }
+        }
+    };
+    auto compute = [&](const Ops& w, const Act& x, const int n_live) {
+#pragma unroll
+        for (int k = 0; k < U; k++) {
+            if (U > 1 && k >= n_live) break;
+            const float t = COEF ? (w.cf[k] == 1.0f ? w.a[k] : w.cf[k] * w.a[k]) : w.a[k];      // the term as the reference stores it
+            if constexpr (DUPS) {
+                if (w.xo[k] != cur) {
+                    if (cur != 0xffffffffu) commit();
+                    cur = w.xo[k];
+                    ar = t;
+#pragma unroll
+                    for (int v = 0; v < NV; v++) xcur[v] = x.x[k][v];
+                } else {
+                    ar = ar + t;
+                }
+            } else {
+#pragma unroll
+                for (int v = 0; v < NV; v++) {
+                    const float pr = t * x.x[k][v];
+                    acc[v] = acc[v] + pr;
+                }
+            }
+        }
+    };
+    auto walk = [&](auto seg) {
+        constexpr bool PIPE = TWO && decltype(seg)::value;          // (the per-column path keeps one set: it is the exception, and a second set there cost every form scalar registers)
+        Rec r;
+        Ops w0;
+        Act x0s;
+        fetch(r, 0);
+        issue_a(r, w0, 0);
+        issue_x(w0, x0s, seg);
+        fetch(r, U);
+        int q = 0;
+        if constexpr (PIPE) {                          // value rows and activations of batch k + 1 in flight while batch k is multiplied: two sets in turn, no copies
+            Ops w1;
+            Act x1s;
+            for (;;) {
+                if (q + U >= total) {
+                    compute(w0, x0s, total - q);
+                    break;
+                }
+                issue_a(r, w1, q + U);
+                issue_x(w1, x1s, seg);
+                fetch(r, q + 2 * U);
+                compute(w0, x0s, U);
+                q += U;
+                if (q + U >= total) {
+                    compute(w1, x1s, total - q);
+                    break;
+                }
+                issue_a(r, w0, q + U);
+                issue_x(w0, x0s, seg);
+                fetch(r, q + 2 * U);
+                compute(w1, x1s, U);
+                q += U;
+            }
+        } else {
+            for (;;) {
+                compute(w0, x0s, total - q < U ? total - q : U);
+                q += U;
+                if (q >= total) break;
+                issue_a(r, w0, q);
+                issue_x(w0, x0s, seg);
+                fetch(r, q + U);
+            }
+        }
+    };
+    if (total > 0) {
+        // the farthest segment of this wavefront: last input channel, last (= highest) input pixel of the slot list
+        const uint32_t far = (uint32_t)(p.Cin - 1) * ci_x + (uint32_t)p.slot_in[s_beg + n_slots - 1] * ldx + (uint32_t)(c0 + NV);
+        const int64_t extent = (p.last_in_row - (p.lastcol ? 0 : 1)) * p.ldx + p.n_vecs;
+        if (__builtin_amdgcn_readfirstlane((int64_t)far <= extent)) walk(std::true_type{});
+        else walk(std::false_type{});
+    }
+    if constexpr (DUPS) {
+        if (cur != 0xffffffffu) commit();
+    }
+    float xl[NV];                                           // the homogeneous row ends the caller's block: one column per lane, fetched while every lane is still here
+    if (p.lastcol) {
+        const int t = __builtin_bit_cast(int, (x0 + p.last_in_row * p.ldx)[lcol]);
+#pragma unroll
+        for (int v = 0; v < NV; v++) xl[v] = __builtin_bit_cast(float, __builtin_amdgcn_readlane(t, v));
+    }
+    if (co >= p.Cout) return;
+    const int64_t row = (int64_t)co * p.HoWo + o;
+    if (p.lastcol) {
+        const float lc = p.lastcol[row];
+        if (lc != 0.0f) {                                   // the bias entry exists in the reference's row only when it is stored
+#pragma unroll
+            for (int v = 0; v < NV; v++) {
+                const float bp = lc * xl[v];
+                acc[v] = acc[v] + bp;
+            }
+        }
+    }
+#pragma unroll
+    for (int v = 0; v < NV; v++) {
+        float t = acc[v];
+        if (p.relu) t = (t < 0.0f) ? 0.0f : t;
+        if (v < nh) p.Y[row * p.ldy + c0 + v] = t;
+    }
+}
+
+// ---- matrix-core path for 1 .. 8 batch columns (KN_FLAG_NARROW_MFMA; 9 .. 32 with KN_FLAG_NARROW32): an implicit GEMM whose N dimension is output pixels x images ----
 // Y[co, (pixel, image)] = sum over (tap t, input channel ci) of tapsT[t][ci][co] * B[t, ci, (pixel, image)], on v_mfma_f32_32x32x2_f32.  The tolerance
 // contract: the association of the sum is free, and here it is fixed by the tiling alone (never by timing), so a call gives the same bits every time.
 //   M  one workgroup = 32 * TM consecutive output channels (tapsT is contiguous in co: an A fragment is one coalesced 128-byte row per k).
-//   N  32 columns = 32 / NV output pixels, consecutive in pix_order, x NV (1 | 2 | 4 | 8) images; column n = pixel * NV + image, so the images of a
-//      pixel are neighbouring lanes reading neighbouring floats.  Widths between the forms run the next NV up; the surplus columns load and store nothing.
+//   N  32 columns = 32 / NV output pixels, consecutive in pix_order, x NV (1 | 2 | 4 | 8; KN_FLAG_NARROW32 calls: 16 | 32, i.e. two pixels or one per tile -- nv_log2 is
+//      a run-time argument of the same instantiations) images; column n = pixel * NV + image, so the images of a pixel are neighbouring lanes reading neighbouring floats
+//      (NV = 32: the gather of a B fragment is one coalesced 128-byte segment).  What a column's sum is does not depend on NV or on the column's lane.  Widths between the forms run the next NV up; the surplus columns load and store nothing.
 //   K  tap x input channel, cut into UNITS of (one tap, 16 channels) = 8 matrix instructions per 32 x 32 block.  The four wavefronts of a workgroup take
 //      the units round robin (unit u goes to wavefront u & 3) into accumulators of their own -- a split over K inside the workgroup, which is what lets
 //      conv5_x (196 pixels, K = 4 608: 112 tiles of 32 x 32) occupy 448 wavefronts -- and the four partial tiles are summed through LDS in wavefront order.
@@ -2591,7 +2812,7 @@ static int exact_tail(const ConvTapsDev& A, const ConvArgs& a, hipStream_t s) {
 // What the two narrow conv launchers (flag `flag`) require of operator and batch: value rows in whole 64-channel blocks, and 32-bit element offsets into tapsT and X
 static int narrow_limits(const ConvTapsDev& A, const ConvArgs& a, const char* flag) {
     KN_REQUIRE(A.cout_pad % 64 == 0, KN_ERR_UNSUPPORTED, std::string(flag) + ": the value rows are not padded to whole 64-channel blocks");
-    KN_REQUIRE(A.ntaps * A.cin_pad * A.cout_pad < ((int64_t)1 << 31) && (a.last_in_row + 1) * a.ldx + NARROW_MAX_VECS < ((int64_t)1 << 31),
+    KN_REQUIRE(A.ntaps * A.cin_pad * A.cout_pad < ((int64_t)1 << 31) && (a.last_in_row + 1) * a.ldx + (a.n_vecs > NARROW_MAX_VECS ? NARROW32_MAX_VECS : NARROW_MAX_VECS) < ((int64_t)1 << 31),
                KN_ERR_UNSUPPORTED, std::string(flag) + ": the taps or the activation block exceed 32-bit element offsets");
     return KN_OK;
 }
@@ -2608,6 +2829,41 @@ static int spmm_narrow(const ConvTapsDev& A, ConvArgs& a, hipStream_t s) {
     KN_LAUNCH("convtaps_narrow_kernel<" + std::to_string(w.nv) + (w.full ? "" : ",masked to " + std::to_string(a.n_vecs)) + (A.has_dups ? ",stored values summed" : "") + (coef ? ",coef" : "") +
                   "> (lane = output channel)",
               narrow_kernel(w.nv, w.full, A.has_dups, coef), dim3((unsigned)(((n_wg + 7) / 8) * 8)), dim3(256), 0, s, a, n_cb, n_wg);
+    return exact_tail(A, a, s);
+}
+
+// KN_FLAG_NARROW | KN_FLAG_NARROW32 on 9 .. NARROW32_MAX_VECS columns: one wavefront per (column block, output pixel, 64 output channels).  Columns per block: the
+// width's form, 16 | 32 (operators that sum stored values: 16).  Narrower blocks, down to 8 columns, while (pixels x channel blocks x column blocks) leaves SIMDs without
+// their four wavefronts (4 096 items) AND the operator's taps stay in an XCD's L2 (2 MB, half of it: spmm_exact's threshold): every column block walks the layer's value rows
+// again, and those loads are what the walk waits for.  Both sides were measured (profiles/r10_narrow32.txt): the keyed AllConvNet (layers of 1 024 pixels and fewer, at most 1.3 MB of
+// taps) at 16 images takes 1.58 ms with the narrower blocks and 2.40 ms with the width's form; a VGG-16 conv5_x-shaped operator (196 pixels, 9.4 MB of taps) at 32 columns takes
+// 1 670 us as one block of 32, 2 000 us as two of 16 and 2 080 us as four of 8.  Nothing between 1.3 and 9.4 MB was measured: the threshold is the L2 argument.
+// Tuning::narrow32_nv forces a block width (diagnostic build).
+typedef void (*Narrow32Kernel)(ConvArgs, int, int, int64_t);
+template <int NV>
+static Narrow32Kernel narrow32_kernel_of(bool dups, bool coef) {
+    return dups ? (coef ? convtaps_narrow32_kernel<NV, true, true> : convtaps_narrow32_kernel<NV, true, false>)
+                : (coef ? convtaps_narrow32_kernel<NV, false, true> : convtaps_narrow32_kernel<NV, false, false>);
+}
+
+static int spmm_narrow32(const ConvTapsDev& A, ConvArgs& a, hipStream_t s) {
+    const int n_cb = (int)((A.Cout + 63) / 64);
+    const int64_t items = (int64_t)a.n_pix * n_cb;
+    int nv = A.has_dups ? 16 : narrow_width(a.n_vecs).nv;
+    if (4 * A.ntaps * A.cin_pad * A.cout_pad <= (2 << 20))
+        while (nv > 8 && items * ((a.n_vecs + nv - 1) / nv) < 4096) nv >>= 1;
+    if (A.tune.narrow32_nv == 8 || A.tune.narrow32_nv == 16 || (A.tune.narrow32_nv == 32 && !A.has_dups)) nv = A.tune.narrow32_nv;
+    const int n_colb = (int)((a.n_vecs + nv - 1) / nv);
+    const int64_t n_wg = (items * n_colb + 3) / 4;
+    if (int rc = narrow_limits(A, a, "KN_FLAG_NARROW | KN_FLAG_NARROW32")) return rc;
+    KN_REQUIRE(n_wg + 8 < ((int64_t)1 << 29) && A.Cin * (int64_t)A.max_slots < ((int64_t)1 << 31), KN_ERR_UNSUPPORTED,
+               "grid or slot walk too large for the channel-lane order-preserving kernel");
+    const bool coef = !A.unit_coef;
+    const Narrow32Kernel k = nv == 8 ? narrow32_kernel_of<8>(A.has_dups, coef) : nv == 16 ? narrow32_kernel_of<16>(A.has_dups, coef)
+                                     : (coef ? convtaps_narrow32_kernel<32, false, true> : convtaps_narrow32_kernel<32, false, false>);
+    KN_LAUNCH("convtaps_narrow32_kernel<NV=" + std::to_string(nv) + (a.n_vecs % nv ? ", masked to " + std::to_string(a.n_vecs) : "") + ", " + std::to_string(n_colb) +
+                  (n_colb == 1 ? " column block" : " column blocks") + (A.has_dups ? ", stored values summed" : "") + (coef ? ", coef" : "") + "> (lane = output channel)",
+              k, dim3((unsigned)(((n_wg + 7) / 8) * 8)), dim3(256), 0, s, a, n_cb, n_colb, n_wg);
     return exact_tail(A, a, s);
 }
 
@@ -2764,7 +3020,7 @@ int convtaps_spmm(const ConvTapsDev& A, const float* x, int64_t ldx, int64_t n_v
     if (narrow_mfma_call(A, flags, n_vecs)) {
         rc = spmm_narrow_mfma(A, a, s);
     } else if (narrow_call(flags, n_vecs)) {
-        rc = spmm_narrow(A, a, s);
+        rc = n_vecs > NARROW_MAX_VECS ? spmm_narrow32(A, a, s) : spmm_narrow(A, a, s);      // (beyond 8 columns: KN_FLAG_NARROW32 is in force)
     } else if (flags & KN_FLAG_EXACT) {
         rc = spmm_exact(A, a, s);
     } else {

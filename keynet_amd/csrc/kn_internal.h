@@ -159,6 +159,7 @@ PlanSink*& plan_sink();   // thread-local; null outside kn_spmm_plan
     X(chain_no_early, "KN_CHAIN_NO_EARLY", 0, true)  /* whole-net kernel: column pools staged at the start of their own layer */ \
     X(chain_no_seq, "KN_CHAIN_NO_SEQ", 0, true)      /* whole-net kernel: thin layers read their columns from the staged pool instead of walking a re-ordered input sequentially */ \
     X(chain_no_share, "KN_CHAIN_NO_SHARE", 0, true)  /* whole-net kernel: every lane streams its own copy of its row's values (no shared value blocks) */ \
+    X(narrow32_nv, "KN_NARROW32_NV", 0, true)        /* convtaps_narrow32_kernel: 8 | 16 | 32 columns per block (0: the rule, spmm_narrow32) */ \
     X(fill_form, "KN_FILL_FORM", 0, true)            /* filled-in order-preserving kernel: 0 = the dispatch rule, 1 / 2 = 32 / 64 channels x one column tile, 3 / 4 = 32 / 64 channels x two tiles */ \
     X(abl, "KN_ABL", 0, true)                        /* kernel ablation mask (kn_conv.hip, KN_ABLATION code paths) */
 struct Tuning {
@@ -331,11 +332,16 @@ static constexpr int MF_MIN_MEMBERS = 24;   // a pattern group takes the matrix-
 // and *absmax_fused is set; otherwise the caller runs absmax_pass over Y afterwards (kn_spmm_screen)
 // KN_FLAG_NARROW: the widest batch of the channel-lane conv-taps kernel, and whether a call takes it (the one place that reads the flag)
 static constexpr int64_t NARROW_MAX_VECS = 8;
-static inline bool narrow_call(uint32_t flags, int64_t n_vecs) { return (flags & (KN_FLAG_NARROW | KN_FLAG_NARROW_MFMA)) && n_vecs <= NARROW_MAX_VECS; }
-// The width a narrow launcher instantiates its kernel for: the next of 1 | 2 | 4 | 8 columns, its log2, and whether the batch fills it (else the columns beyond n_vecs are masked)
+// KN_FLAG_NARROW32, a modifier of the two flags above: their column range is 1 .. NARROW32_MAX_VECS instead (9 .. 32 columns: convtaps_narrow32_kernel, and the matrix-core
+// kernel at NV = 16 | 32).  Alone, and on every handle kind but conv-taps, it changes nothing.  narrow_max is the one place that reads it.
+static constexpr int64_t NARROW32_MAX_VECS = 32;
+static inline int64_t narrow_max(uint32_t flags) { return (flags & KN_FLAG_NARROW32) ? NARROW32_MAX_VECS : NARROW_MAX_VECS; }
+static inline bool narrow_call(uint32_t flags, int64_t n_vecs) { return (flags & (KN_FLAG_NARROW | KN_FLAG_NARROW_MFMA)) && n_vecs <= narrow_max(flags); }
+// The width a narrow launcher instantiates its kernel for: the next of 1 | 2 | 4 | 8 (| 16 | 32: KN_FLAG_NARROW32 calls only) columns, its log2, and whether the batch fills it
+// (else the columns beyond n_vecs are masked)
 struct NarrowWidth { int nv, log2; bool full; };
 static inline NarrowWidth narrow_width(int64_t n_vecs) {
-    const int l = n_vecs <= 1 ? 0 : (n_vecs <= 2 ? 1 : (n_vecs <= 4 ? 2 : 3));
+    const int l = n_vecs <= 1 ? 0 : (n_vecs <= 2 ? 1 : (n_vecs <= 4 ? 2 : (n_vecs <= 8 ? 3 : (n_vecs <= 16 ? 4 : 5))));
     return {1 << l, l, n_vecs == (1 << l)};
 }
 // KN_FLAG_NARROW_MFMA: the most slots one (output pixel, tap) pair may hold for the matrix-core narrow kernel, the largest record table built for it, and
@@ -351,7 +357,7 @@ static inline bool narrow_mfma_loses(const ConvTapsDev& A, int64_t n_vecs) {
     return A.Cin <= 4 && n_vecs > 4 && A.Hout * A.Wout * ((A.Cout + 63) / 64) >= 4 * 1024;
 }
 static inline bool narrow_mfma_call(const ConvTapsDev& A, uint32_t flags, int64_t n_vecs) {
-    return (flags & KN_FLAG_NARROW_MFMA) && !(flags & KN_FLAG_EXACT) && n_vecs <= NARROW_MAX_VECS && A.pt_ok && !narrow_mfma_loses(A, n_vecs);
+    return (flags & KN_FLAG_NARROW_MFMA) && !(flags & KN_FLAG_EXACT) && n_vecs <= narrow_max(flags) && A.pt_ok && !narrow_mfma_loses(A, n_vecs);
 }
 // KN_FLAG_NARROW_ROWS: an f32 CSR operator's pattern groups and loose rows on the row-lane kernel (kn_csr_narrow.hip) for at most NARROW_MAX_VECS columns, while the
 // kernel's 32-bit BYTE offsets into X hold; else the flag is ignored (the other kernels give the same bits).  The one place that reads the flag.

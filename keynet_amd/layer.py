@@ -209,7 +209,7 @@ class KeyedLayer(nn.Module):
     def iskeyedrelu(self):
         return 'ReLU' in self._layertype
 
-    def forward(self, x_affine, fuse_relu=False, absmax=None, narrow=False, narrow_rows=False):
+    def forward(self, x_affine, fuse_relu=False, absmax=None, narrow=False, narrow_rows=False, narrow32=False):
         """[N, Din+1] -> [N, Dout+1] (keynet/layer.py:88-93).  The result is a transposed view of the feature-major
         [Dout+1, N] block the kernel wrote, so the next layer's x.t() is free.  `fuse_relu` folds the unkeyed nn.ReLU
         that follows this layer in the key-net (keynet/system.py:92) into the kernel epilogue.  `absmax`: a one-element device
@@ -221,14 +221,16 @@ class KeyedLayer(nn.Module):
         `narrow='mfma'`: the matrix-core narrow kernel (KN_FLAG_NARROW_MFMA) where this layer's contract in force allows re-ordered sums (narrow_mode():
         declared -> always; decided by calibration -> measured once on the first such batch, recorded under _contract_record['narrow']); else narrow=True.
         `narrow_rows` (with `narrow`): a layer whose operator is a float32 CSR handle (W.rows_capable()) runs its stored-order product on the row-lane kernel
-        (KN_FLAG_NARROW_ROWS, kernel()) -- the same bits; conv-taps layers and everything else are what `narrow` alone makes them.  Nothing is decided or recorded."""
+        (KN_FLAG_NARROW_ROWS, kernel()) -- the same bits; conv-taps layers and everything else are what `narrow` alone makes them.  Nothing is decided or recorded.
+        `narrow32` (with `narrow`): at most KeyedModel.NARROW32_MAX images; a conv-taps layer gets KN_FLAG_NARROW32 next to its narrow flag (kernel()), every other
+        layer runs as without it."""
         if verbose():
             print('[keynet_amd.layer]: forward %s' % str(self))
         exact = getattr(self, '_exact', True)
         relu = fuse_relu or self.iskeyedrelu()
         form = {}                            # what `narrow` / `narrow_rows` make of this layer: the keyword its operator's torchdot takes, if any
         if narrow and self.W.narrow_capable():
-            form = dict(narrow=self.narrow_mode(narrow, x_affine.t(), relu) if narrow == 'mfma' else True)
+            form = dict(narrow=self.narrow_mode(narrow, x_affine.t(), relu) if narrow == 'mfma' else True, narrow32=bool(narrow32))
         elif narrow:
             if exact == 'auto':
                 exact = True                 # an undecided layer without a narrow form: the reference's order for this call, nothing decided or recorded
@@ -245,7 +247,7 @@ class KeyedLayer(nn.Module):
         return self.W.torchdot(x_affine.t(), relu=relu, exact=exact, absmax=absmax, **form).t()
 
     @staticmethod
-    def kernel(W, contract, relu, device=None, narrow=False, narrow_rows=False):
+    def kernel(W, contract, relu, device=None, narrow=False, narrow_rows=False, narrow32=False):
         """The one place that turns a decided contract into an operator handle and flags: (get_op, flags) of the kn_spmm launch that applies operator `W`
         under `contract`, get_op(device) -> the handle resident there.  None when that is not one launch: 'auto' (still to calibrate), 'split' on an operator that has a split form (Conv2dTiledMatrix._torchdot_split).
         The rules: 'split' forced on an operator without a split form, and 'bf16x3' on a non-conv operator, are the f32 matrix cores (False); a conv operator
@@ -260,7 +262,9 @@ class KeyedLayer(nn.Module):
         here is KeyedLayer.narrow_mode's decision.)
         `narrow_rows` (the same batches): an operator with W.rows_capable() that runs in the stored order on its CSR handle -- contract True, or any non-conv operator
         without a dense handle in play -- gets KN_FLAG_NARROW_ROWS (the row-lane kernel, the same bits) next to the flags it has without the keyword.  A float64
-        operator, a plain SparseMatrix that a re-ordering contract put on its dense handle, and conv-taps operators keep what they have."""
+        operator, a plain SparseMatrix that a re-ordering contract put on its dense handle, and conv-taps operators keep what they have.
+        `narrow32` (with `narrow`; a batch of at most KeyedModel.NARROW32_MAX columns): a narrow-capable operator gets KN_FLAG_NARROW32 next to the flags it has
+        without the keyword (the library then honours its narrow flag up to 32 columns); every other operator keeps its flags."""
         conv = isinstance(W, ksp.Conv2dTiledMatrix)
         lane = bool(narrow) and W.narrow_capable()          # one launch of a narrow conv kernel, whatever the contract
         mfma = lane and narrow == 'mfma' and conv and contract in (False, 'bf16x3', 'split')      # (the library falls back to the channel-lane kernel on an ineligible operator)
@@ -276,16 +280,18 @@ class KeyedLayer(nn.Module):
         if mfma:
             (exact, bf16x3) = (False, False)
         return (get_op, (_capi.KN_FLAG_RELU if relu else 0) | (_capi.KN_FLAG_EXACT if exact else 0) | (_capi.KN_FLAG_BF16X3 if bf16x3 else 0) |
-                (_capi.KN_FLAG_NARROW_MFMA if mfma else _capi.KN_FLAG_NARROW if lane else 0) | (_capi.KN_FLAG_NARROW_ROWS if rows else 0))
+                (_capi.KN_FLAG_NARROW_MFMA if mfma else _capi.KN_FLAG_NARROW if lane else 0) | (_capi.KN_FLAG_NARROW32 if lane and narrow32 else 0) |
+                (_capi.KN_FLAG_NARROW_ROWS if rows else 0))
 
-    def launch(self, device, relu=False, narrow=False, narrow_rows=False):
+    def launch(self, device, relu=False, narrow=False, narrow_rows=False, narrow32=False):
         """This layer under its contract in force as one launch on `device` (`relu`: the unkeyed nn.ReLU behind it is fused in), or None when it is not one
         kn_spmm launch: see kernel(); a float64 operator (its own kernel and a float64 result: kn_spmm_f64).  What the key-net's planners read
-        (KeyedModel._chain_op / _overlap_plan); forward() -> W.torchdot() runs the same rule.  `narrow`, `narrow_rows`: see kernel(); 'mfma' goes through narrow_mode() first, without a batch."""
+        (KeyedModel._chain_op / _overlap_plan); forward() -> W.torchdot() runs the same rule.  `narrow`, `narrow_rows`, `narrow32`: see kernel(); 'mfma' goes through narrow_mode() first, without a batch."""
         W = self.W
         if narrow == 'mfma':
             narrow = self.narrow_mode(narrow)                 # (a calibrated layer without a narrow record yet: the channel-lane kernel -- forward() measures, a planner does not)
-        kernel = None if W.is_float64() else self.kernel(W, getattr(self, '_exact', True), relu or self.iskeyedrelu(), device, narrow=narrow, narrow_rows=bool(narrow and narrow_rows))
+        kernel = None if W.is_float64() else self.kernel(W, getattr(self, '_exact', True), relu or self.iskeyedrelu(), device, narrow=narrow, narrow_rows=bool(narrow and narrow_rows),
+                                                               narrow32=bool(narrow and narrow32))
         if kernel is None:
             return None
         return Launch(kernel[0](device), kernel[1], int(W.shape[0]), int(W.shape[1]), isinstance(W, ksp.Conv2dTiledMatrix), 'Linear' in self._layertype,
@@ -339,7 +345,8 @@ class KeyedLayer(nn.Module):
         """What `narrow='mfma'` means for this layer now: 'mfma' (KN_FLAG_NARROW_MFMA) or True (the channel-lane kernel, the bits of narrow=True).
         Contract True, or 'auto' still undecided, or not a conv-taps operator: True, nothing decided.  A DECLARED re-ordering contract (exact=False,
         'bf16x3' forced): 'mfma', unscreened -- the caller's responsibility, as on the wide path.  A contract DECIDED BY CALIBRATION (screened()): the kernel is
-        one more association of the sum that the wide record does not cover, so the first eager call with a batch `xt` ([cols, N <= 8]) measures it -- the
+        one more association of the sum that the wide record does not cover, so the first eager call with a batch `xt` ([cols, N]; of a narrow32 batch the 8-column
+        window that holds its largest |x|: a column's bits do not depend on the width of the launch, so the record covers NV = 16 | 32 too) measures it -- the
         channel-lane kernel and the matrix-core kernel on these very columns, gate() -- and accepts by _calibrate's rule: the worst element uses at most half
         its tolerance, a quarter where the bound screen 2 eps32 max_row sum|a| max|x| <= 1e-5 fails.  The outcome is _contract_record['narrow'] = {decided:
         'mfma' | 'exact', gate_ratio, max_abs_x, measured_on_columns, ...}; the wide decision and its fields are never touched.  Without a batch (a planner
@@ -361,10 +368,14 @@ class KeyedLayer(nn.Module):
         return 'mfma' if rec['decided'] == 'mfma' else True
 
     def _measure_narrow(self, xt, relu):
-        """The narrow record of a calibrated layer, measured on the batch xt ([cols, N <= 8]): see narrow_mode()."""
+        """The narrow record of a calibrated layer, measured on the batch xt ([cols, N]): see narrow_mode().  Of more than NARROW_MAX columns the window of
+        NARROW_MAX that holds the largest |x| is measured, placed as _calibrate places its window; max_abs_x is the maximum of those columns = of the batch."""
         W = self.W
         xt = ksp._device_block(xt)
         n = int(xt.shape[1])
+        if n > ksp.NARROW_MAX:
+            c0 = min((int(torch.argmax(xt.detach().abs().amax(dim=0))) // ksp.NARROW_MAX) * ksp.NARROW_MAX, n - ksp.NARROW_MAX)
+            (xt, n) = (xt[:, c0:c0 + ksp.NARROW_MAX].contiguous(), ksp.NARROW_MAX)
         dev = xt.device
         with torch.cuda.device(xt.device):
             # the widest of these columns the library runs on the matrix-core kernel (a shape rule of the handle may keep a wide batch of a layer on the

@@ -29,7 +29,18 @@ forwards of a --mfma --one-forward run and prints every conv launch of both kern
 
 --rows: whole forwards with and without narrow_rows in one process, alternating -- narrow=True under the default contract, then narrow='mfma' under
 exact_mode('auto') after one calibrating wide forward -- the logits torch.equal before any time is printed; and every layer that takes the row-lane kernel alone,
-its kn_spmm with and without KN_FLAG_NARROW_ROWS on the same block (HIP events, median)."""
+its kn_spmm with and without KN_FLAG_NARROW_ROWS on the same block (HIP events, median).
+
+    python tools/narrow_latency.py --narrow32 [--out profiles/r10_narrow32.txt]
+    python tools/narrow_latency.py --narrow32 --one-forward      # for n in (16, 32) ONE narrow=True, narrow32=True forward, then ONE narrow='mfma', narrow32=True forward
+    python tools/narrow_latency.py --narrow32 --from-trace DIR/.../*_kernel_trace.csv          # no GPU: the 13 conv launches of those four forwards
+    KEYNET_HIP_LIB=<diagnostic build> python tools/narrow_latency.py --narrow32 --blocks        # one conv5_x-shaped operator at 32 columns per column-block width
+
+--narrow32: for 8, 9, 12, 16, 24 and 32 images, in one process with the forms alternating: the padded forward (no keyword) and narrow=True, narrow32=True under the
+default contract -- logits torch.equal before any time is printed --, then under exact_mode('auto') after one calibrating wide forward the padded forward and
+narrow='mfma', narrow32=True (inside the float-key gate against narrow=True, narrow32=True); at 8 images the plain narrow forwards are the yardstick.  The bars of
+the file are computed from the table.  --blocks: convtaps_narrow32_kernel on a 14 x 14 pixel, 512 -> 512 channel 3 x 3 operator at 32 columns with the block
+width forced by KN_NARROW32_NV (read at create by the diagnostic build only: keynet_amd.build.build(out=..., defines=('KN_ABLATION',))) against the launcher's rule."""
 import argparse
 import os
 import statistics
@@ -106,6 +117,157 @@ def mfma_table(args, knet, xc, desc):
     text = '\n'.join(lines) + '\n'
     print(text)
     with open(out, 'a') as f:
+        f.write(text)
+
+
+N32_IMAGES = (8, 9, 12, 16, 24, 32)
+
+
+def narrow32_table(args, knet, xc, desc):
+    """--narrow32: see the module docstring."""
+    from keynet_amd.layer import gate
+    blk = lambda n: xc[:n].t().contiguous().t()
+    if args.one_forward:
+        knet.exact_mode('auto')
+        knet.forward_linear(blk(8))
+        for n in (16, 32):                        # operators resident, narrow records measured
+            knet.forward_linear(blk(n), narrow=True, narrow32=True)
+            knet.forward_linear(blk(n), narrow='mfma', narrow32=True)
+        torch.cuda.synchronize()
+        print("TRACE-FROM-HERE: for n in (16, 32) one narrow=True, narrow32=True forward, then one narrow='mfma', narrow32=True forward", flush=True)
+        for n in (16, 32):
+            knet.forward_linear(blk(n), narrow=True, narrow32=True)
+            knet.forward_linear(blk(n), narrow='mfma', narrow32=True)
+            torch.cuda.synchronize()
+        return
+    cell = lambda v: '%8.3f (%.3f .. %.3f)' % (statistics.median(v), min(v), max(v))
+    lines = ['', '== tools/narrow_latency.py --narrow32%s: %s' % ('' if args.workload == 'vgg16' else ' --workload %s' % args.workload, desc),
+             '   %s, torch %s; HIP events, %d warm-up + median of %d forwards (min .. max), the forms of a row alternating in quarters'
+             % (torch.cuda.get_device_name(0), torch.__version__, args.warmup, args.forwards)]
+    med = {}
+
+    def table(mode, title, check):
+        lines.append('   %s' % title)
+        lines.append('   %6s | %-28s | %-28s | %-9s | %s' % ('images', 'no keyword [ms]', 'narrow=%r, narrow32=True [ms]' % (mode,), 'speed-up', 'narrow=%r alone (8 images) [ms]' % (mode,)))
+        for n in args.images:
+            x = blk(n)
+            check(n, knet.forward_linear(x), knet.forward_linear(x, narrow=mode, narrow32=True))
+            forms = [lambda: knet.forward_linear(x), lambda: knet.forward_linear(x, narrow=mode, narrow32=True)] + ([lambda: knet.forward_linear(x, narrow=mode)] if n <= 8 else [])
+            t = [[] for _ in forms]
+            for _ in range(4):                    # alternate in quarters
+                for (u, f) in zip(t, forms):
+                    u += timed(f, args.forwards // 4, args.warmup)
+            med[(mode, n)] = [statistics.median(u) for u in t] + [max(u) - min(u) for u in t]
+            lines.append('   %6d | %-28s | %-28s | %8.2fx | %s' % (n, cell(t[0]), cell(t[1]), statistics.median(t[0]) / statistics.median(t[1]), cell(t[2]) if n <= 8 else ''))
+            print('narrow=%r n = %d done' % (mode, n), flush=True)
+        lines.append('')
+
+    def equal(n, y0, y1):
+        torch.cuda.synchronize()
+        assert torch.equal(y0, y1), 'narrow32 logits differ from the forward without the keyword at %d images: max %g' % (n, float((y0 - y1).abs().max()))
+
+    def inside(n, y0, y1):
+        ye = knet.forward_linear(blk(n), narrow=True, narrow32=True)
+        torch.cuda.synchronize()
+        ratio = gate(y1, ye)[0]
+        assert ratio <= 1.0, "narrow='mfma', narrow32=True logits outside the float-key gate against narrow=True, narrow32=True at %d images: %g" % (n, ratio)
+
+    pads0 = getattr(knet, '_padded_forwards', 0)
+    table(True, 'default contract (bit-exact); logits torch.equal: yes', equal)
+    padded = getattr(knet, '_padded_forwards', 0) > pads0
+    if args.workload == 'vgg16':
+        knet.exact_mode('auto')
+        knet.forward_linear(blk(8))               # the calibrating wide forward
+        table('mfma', "exact_mode('auto') after one calibrating wide forward; logits inside the float-key gate against narrow=True, narrow32=True: yes", inside)
+        for r in knet.contract_report()['layers']:
+            if r['narrow'] is not None:
+                lines.append('     %-12s decided %-5s gate ratio %-10.3g max |x| %-10.3g on %d column(s)' % (r['name'], r['narrow']['decided'], r['narrow']['gate_ratio'] or 0.0, r['narrow']['max_abs_x'] or 0.0, r['narrow']['measured_on_columns']))
+        lines.append('')
+    lines.append('   the forward without the keyword is %s' % ('padded to 128 images' if padded else 'NOT padded (an untiled key-net runs at the width it is given)'))
+    for mode in (True, 'mfma'):
+        if (mode, 8) in med and (mode, 16) in med:
+            (m8, m16) = (med[(mode, 8)], med[(mode, 16)])
+            lines.append('   narrow=%r: (a) 16 images / 8 images on the plain narrow forward = %.2fx (bar: <= 2);  (b) no keyword / narrow32 at 16 images = %.2fx (bar: >= 1.5)%s'
+                         % (mode, m16[1] / m8[2], m16[0] / m16[1],
+                            ';  at 32 images %.3f ms against %.3f ms, spread of the two forms %.3f / %.3f ms' % (med[(mode, 32)][0], med[(mode, 32)][1], med[(mode, 32)][2], med[(mode, 32)][3])
+                            if (mode, 32) in med else ''))
+    text = '\n'.join(lines) + '\n'
+    print(text)
+    with open(args.out or os.path.join(ROOT, 'profiles', 'r10_narrow32.txt'), 'a') as f:
+        f.write(text)
+
+
+def narrow32_blocks(args):
+    """--narrow32 --blocks: see the module docstring."""
+    import copy
+    import numpy as np
+    from keynet_amd import _capi, direct as kdirect, sparse as ksp
+    dev = torch.device('cuda:0')
+    rng = np.random.RandomState(0)
+    (H, C, n) = (14, 512, 32)
+    w = (rng.randn(C, C, 3, 3) / np.sqrt(9 * C)).astype(np.float32)
+    (pi, po) = (rng.permutation(H * H), rng.permutation(H * H))
+    (eo, ei, et) = ([], [], [])
+    for (t, (_, S)) in enumerate(kdirect.shift_matrices((H, H), 3, 1)):
+        S = S.tocoo()
+        eo.append(po[S.row]); ei.append(pi[S.col]); et.append(np.full(S.nnz, t))
+    taps = np.stack([w[:, :, i, j] for i in range(3) for j in range(3)])
+    lastcol = np.concatenate((rng.randn(C * H * H), [1.0])).astype(np.float32)
+    W = ksp.Conv2dTiledMatrix.fromtaps((C, H, H), (C, H, H), taps, np.concatenate(eo), np.concatenate(ei), np.concatenate(et), None, lastcol)
+    x = torch.randn(W.shape[1], n, device=dev)
+    x[-1] = 1.0
+    flags = _capi.KN_FLAG_NARROW | _capi.KN_FLAG_NARROW32 | _capi.KN_FLAG_RELU
+    lines = ['', '== tools/narrow_latency.py --narrow32 --blocks: a conv5_x-shaped operator (14 x 14 pixels, 512 -> 512 channels, 3 x 3, permuted pixels) at 32 columns,',
+             '   convtaps_narrow32_kernel per column-block width (KN_NARROW32_NV, diagnostic build); HIP events, %d warm-up + median of %d launches (min .. max)' % (args.warmup, args.forwards)]
+    ref = None
+    for nv in (0, 8, 16, 32, 0):
+        if nv:
+            os.environ['KN_NARROW32_NV'] = str(nv)
+        else:
+            os.environ.pop('KN_NARROW32_NV', None)
+        Wv = copy.copy(W)
+        Wv._op = None
+        with torch.cuda.device(dev):
+            op = Wv._device_op(dev)
+            plan = op.plan(n, flags).split(' (')[0]
+            y = torch.empty((W.shape[0], n), device=dev)
+            st = torch.cuda.current_stream().cuda_stream
+            t = timed(lambda: op.spmm(x.data_ptr(), n, n, y.data_ptr(), n, flags, st), args.forwards, args.warmup)
+        torch.cuda.synchronize()
+        ref = y if ref is None else ref
+        lines.append('   %-8s %-80s %9.1f us (%.1f .. %.1f)   bit-equal to the rule\'s: %s' % ('rule' if not nv else 'NV=%d' % nv, plan[:80], statistics.median(t) * 1e3, min(t) * 1e3, max(t) * 1e3,
+                                                                                          bool(torch.equal(y, ref))))
+    text = '\n'.join(lines) + '\n'
+    print(text)
+    with open(args.out or os.path.join(ROOT, 'profiles', 'r10_narrow32.txt'), 'a') as f:
+        f.write(text)
+
+
+def narrow32_trace_table(args):
+    """--narrow32 --from-trace: the conv launches of the last four forwards of a `--narrow32 --one-forward` run (device timestamps)."""
+    import csv
+    with open(args.from_trace, newline='') as f:
+        rows = [r for r in csv.DictReader(f) if 'convtaps_narrow' in r['Kernel_Name']]
+    rows.sort(key=lambda r: int(r['Start_Timestamp']))
+    k = args.convs
+    assert len(rows) >= 4 * k, 'the trace holds %d narrow conv launches, fewer than 4 forwards of %d' % (len(rows), k)
+    rows = rows[-4 * k:]
+    us = lambda r: (int(r['End_Timestamp']) - int(r['Start_Timestamp'])) / 1e3
+    wgs = lambda r: int(r.get('Grid_Size_X') or 0) // max(1, int(r.get('Workgroup_Size_X') or 1))
+    short = lambda r: 'matrix-core' if 'mfma' in r['Kernel_Name'] else ('narrow32 ' + r['Kernel_Name'].split('<')[1].split('>')[0] if '<' in r['Kernel_Name'] else 'narrow32')
+    lines = ['', "== tools/narrow_latency.py --narrow32 --from-trace: the conv launches of one narrow=True and one narrow='mfma' forward with narrow32=True (rocprofv3 --kernel-trace, device timestamps)"]
+    for (i, n) in enumerate((16, 32)):
+        (lane, mfma) = (rows[(2 * i) * k:(2 * i + 1) * k], rows[(2 * i + 1) * k:(2 * i + 2) * k])
+        assert all('mfma' not in r['Kernel_Name'] for r in lane), 'the narrow=True forward launched a matrix-core kernel'
+        lines.append('')
+        lines.append("   %d images [us]: conv launch | workgroups, channel-lane | channel-lane | workgroups, narrow='mfma' | narrow='mfma' | ratio | kernels" % n)
+        for (j, (a, b)) in enumerate(zip(lane, mfma)):
+            lines.append('     %2d | %6d | %9.1f | %6d | %9.1f | %5.2fx | %s / %s' % (j + 1, wgs(a), us(a), wgs(b), us(b), us(a) / us(b), short(a), short(b)))
+        (sa, sb) = (sum(us(r) for r in lane), sum(us(r) for r in mfma))
+        lines.append('     sum of the %d conv launches: %9.1f | %9.1f | %5.2fx' % (k, sa, sb, sa / sb))
+    text = '\n'.join(lines) + '\n'
+    print(text)
+    with open(args.out or os.path.join(ROOT, 'profiles', 'r10_narrow32.txt'), 'a') as f:
         f.write(text)
 
 
@@ -254,18 +416,25 @@ def main():
     ap.add_argument('-n', type=int, default=1, help='images of --one-forward')
     ap.add_argument('--rows', action='store_true', help='whole forwards and single layers with and without narrow_rows=True (profiles/r09_narrow_rows.txt)')
     ap.add_argument('--mfma', action='store_true', help="exact_mode('auto') after one calibrating wide forward: padded, narrow=True, narrow='mfma'")
+    ap.add_argument('--narrow32', action='store_true', help='9 .. 32 images: no keyword against narrow32=True, both contracts (profiles/r10_narrow32.txt)')
+    ap.add_argument('--images', type=lambda v: tuple(int(k) for k in v.split(',')), default=N32_IMAGES, help='image counts of --narrow32')
+    ap.add_argument('--blocks', action='store_true', help='with --narrow32: one conv5_x-shaped operator per column-block width (diagnostic build)')
     args = ap.parse_args()
     if args.from_trace:
-        return rows_trace_table(args) if args.rows else trace_table(args)
+        return narrow32_trace_table(args) if args.narrow32 else rows_trace_table(args) if args.rows else trace_table(args)
+    if args.narrow32 and args.blocks:
+        return narrow32_blocks(args)
     assert args.forwards >= 20 or args.one_forward, 'the median of at least 20 forwards'
     t0 = time.time()
     (sensor, knet, inshape, _, desc, _) = workloads.build_workload(args.workload, 0, fanout=True)
     dev = torch.device('cuda:0')
     torch.manual_seed(1)
-    imgs = torch.randn((8,) + tuple(inshape))
+    imgs = torch.randn((max(args.images) if args.narrow32 else 8,) + tuple(inshape))
     xc = sensor.fromtensor(imgs.to(dev)).encrypt().astensor()
     xc = xc.t().contiguous().t()                  # feature-major, as the layers hand blocks on
     print('keyed %s in %.0f s' % (desc, time.time() - t0), flush=True)
+    if args.narrow32:
+        return narrow32_table(args, knet, xc, desc)
     if args.mfma:
         return mfma_table(args, knet, xc, desc)
     if args.rows:
