@@ -35,7 +35,6 @@
 #include <cstring>
 #include <numeric>
 #include <type_traits>
-#include <unordered_map>
 
 #pragma clang fp contract(off)
 
@@ -843,36 +842,6 @@ static int chain_upload(ChainDev* c, const T** dst, const std::vector<T>& h) {
     return KN_OK;
 }
 
-// column patterns of a layer: rows with an identical stored column sequence share one id (pat[r]); pat_rep[id] = a row that carries it
-static void chain_patterns(int64_t rows, const std::vector<int32_t>& ip, const std::vector<int32_t>& ix, std::vector<int32_t>& pat, std::vector<int32_t>& pat_rep) {
-    pat.assign((size_t)rows, -1);
-    pat_rep.clear();
-    std::unordered_map<uint64_t, std::vector<int32_t>> buckets;
-    for (int64_t r = 0; r < rows; r++) {
-        const int32_t s = ip[(size_t)r], e = ip[(size_t)r + 1];
-        uint64_t h = 1469598103934665603ull ^ (uint64_t)(e - s);
-        for (int32_t k = s; k < e; k++) {
-            h ^= (uint64_t)(uint32_t)ix[(size_t)k];
-            h *= 1099511628211ull;
-        }
-        auto& cand = buckets[h];
-        int32_t found = -1;
-        for (int32_t g : cand) {
-            const int32_t rs = ip[(size_t)pat_rep[(size_t)g]], re = ip[(size_t)pat_rep[(size_t)g] + 1];
-            if (re - rs == e - s && (e == s || std::memcmp(ix.data() + rs, ix.data() + s, sizeof(int32_t) * (size_t)(e - s)) == 0)) {
-                found = g;
-                break;
-            }
-        }
-        if (found < 0) {
-            found = (int32_t)pat_rep.size();
-            pat_rep.push_back((int32_t)r);
-            cand.push_back(found);
-        }
-        pat[(size_t)r] = found;
-    }
-}
-
 // Does a layer take the SEQUENTIAL thin walk (chain_rows_thin_seq)?  A keyed nn.Linear behind another layer: (nearly) all rows share ONE stored column sequence P of distinct
 // columns, few enough rows for two wavefronts per slice, a walk long enough to be bound by one wavefront's instruction issue.  pos = where the layer BEFORE it must put each of
 // its output rows: pos[P_k] = k, the features P does not name behind them.
@@ -885,7 +854,7 @@ static ChainSeqPlan chain_plan_seq(int64_t l, int64_t rows, int64_t cols, const 
     ChainSeqPlan P;
     if (l == 0 || rows == 0 || tune.chain_no_seq) return P;              // (layer 0 reads the caller's input: staged as it is)
     std::vector<int32_t> pat, pat_rep;
-    chain_patterns(rows, ip, ix, pat, pat_rep);
+    row_patterns(rows, ip.data(), ix.data(), true, pat, pat_rep);          // column patterns of the layer; empty rows share one
     std::vector<int64_t> cnt(pat_rep.size(), 0);
     for (int64_t r = 0; r < rows; r++) cnt[(size_t)pat[(size_t)r]]++;
     const int32_t g = (int32_t)(std::max_element(cnt.begin(), cnt.end()) - cnt.begin());
@@ -920,7 +889,7 @@ static int chain_build_layer(ChainDev* c, ChainLayerArg& L, ChainLayerArg& LX, i
     const std::vector<int32_t>* in_pos = plan.on ? &plan.pos : nullptr;
     auto off = [&](int32_t col) { return in_base + 16 * (in_pos ? (*in_pos)[(size_t)col] : col); };
     std::vector<int32_t> pat, pat_rep;
-    chain_patterns(rows, ip, ix, pat, pat_rep);
+    row_patterns(rows, ip.data(), ix.data(), true, pat, pat_rep);          // column patterns of the layer; empty rows share one
     struct Built {
         std::vector<float> vals;
         std::vector<int32_t> colpool, lane_meta, info;

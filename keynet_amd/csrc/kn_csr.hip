@@ -521,24 +521,26 @@ __global__ __launch_bounds__(256) void csr_big_group_kernel(int64_t n_big, const
 
 void csr_free(CsrDev& c) {
     void* ptrs[] = {c.indptr, c.indices, c.data, c.data64, c.grp_colptr, c.grp_cols, c.grp_rowptr, c.grp_rows, c.grp_valptr, c.grp_vals,
-                    c.work_grp, c.work_r0, c.loose_rows, c.big_grp, c.big_r0, c.long_rows, c.patch_rows, c.patch_ptr, c.patch_cols,
-                    c.mf_grp[0], c.mf_grp[1], c.mf_grp[2], c.mf_r0[0], c.mf_r0[1], c.mf_r0[2], c.ws_grp, c.ws_r0, c.mf16_grp, c.mf16_r0, c.nr_grp, c.nr_r0};
+                    c.loose_rows, c.long_rows, c.patch_rows, c.patch_ptr, c.patch_cols};
     for (void* p : ptrs)
         if (p) (void)hipFree(p);
+    for (WorkList* w : {&c.work, &c.big, &c.ws, &c.mf[0], &c.mf[1], &c.mf[2], &c.mf16, &c.nr}) {
+        if (w->grp) (void)hipFree(w->grp);
+        if (w->r0) (void)hipFree(w->r0);
+    }
     c = CsrDev();
 }
 
-// Host analysis: bucket rows by their exact column sequence.  Groups need >= 2 members and >= 1 column.
-int csr_build_groups(kn_operator* h, const int32_t* indptr, const int32_t* indices, const float* data) {
-    CsrDev& A = h->csr;
-    const int64_t rows = A.rows;
-    std::unordered_map<uint64_t, std::vector<int32_t>> buckets;   // hash -> group ids with that hash
-    std::vector<std::vector<int32_t>> members;                    // group -> rows (ascending)
-    std::vector<int32_t> rep;                                     // group -> representative row
+// ---- csr_build_groups (host), step by step ----------------------------------------------------------------------------------
+
+void row_patterns(int64_t rows, const int32_t* indptr, const int32_t* indices, bool empty_rows, std::vector<int32_t>& pat, std::vector<int32_t>& pat_rep) {
+    pat.assign((size_t)rows, -1);
+    pat_rep.clear();
+    std::unordered_map<uint64_t, std::vector<int32_t>> buckets;   // hash -> pattern ids with that hash
     buckets.reserve((size_t)rows);
     for (int64_t r = 0; r < rows; r++) {
         const int32_t s = indptr[r], e = indptr[r + 1];
-        if (e <= s) continue;
+        if (e <= s && !empty_rows) continue;
         uint64_t hsh = 1469598103934665603ull ^ (uint64_t)(e - s);
         for (int32_t k = s; k < e; k++) {
             hsh ^= (uint64_t)(uint32_t)indices[k];
@@ -547,89 +549,102 @@ int csr_build_groups(kn_operator* h, const int32_t* indptr, const int32_t* indic
         auto& cand = buckets[hsh];
         int32_t found = -1;
         for (int32_t g : cand) {
-            const int32_t rs = indptr[rep[g]], re = indptr[rep[g] + 1];
-            if (re - rs == e - s && std::memcmp(indices + rs, indices + s, sizeof(int32_t) * (size_t)(e - s)) == 0) {
+            const int32_t rs = indptr[pat_rep[(size_t)g]], re = indptr[pat_rep[(size_t)g] + 1];
+            if (re - rs == e - s && (e == s || std::memcmp(indices + rs, indices + s, sizeof(int32_t) * (size_t)(e - s)) == 0)) {
                 found = g;
                 break;
             }
         }
         if (found < 0) {
-            found = (int32_t)members.size();
-            members.emplace_back();
-            rep.push_back((int32_t)r);
+            found = (int32_t)pat_rep.size();
+            pat_rep.push_back((int32_t)r);
             cand.push_back(found);
         }
-        members[found].push_back((int32_t)r);
+        pat[(size_t)r] = found;
     }
-    // PATCHED members.  A permutation-keyed conv layer whose filter holds an exact zero has rows that are their pixel group's column sequence minus
-    // that entry (AllConvNet conv5: 752 of 49 153 rows; walked alone they cost 1.9 ms of the layer's 11.4 -- a serial gather walk per row against one
-    // shared gather per sixteen rows).  Such a row joins the group with 0.0f at the missing positions: a running sum that started at +0.0 is never
-    // -0.0, so adding +-0.0 = 0.0f * x leaves it unchanged bit for bit whenever x is finite; csr_patch_guard_kernel rewrites the output for batch
-    // columns where x at a missing position is NOT finite (0 * Inf would leak a NaN the reference's row does not have).
+}
+
+// PATCHED members.  A permutation-keyed conv layer whose filter holds an exact zero has rows that are their pixel group's column sequence minus
+// that entry (AllConvNet conv5: 752 of 49 153 rows; walked alone they cost 1.9 ms of the layer's 11.4 -- a serial gather walk per row against one
+// shared gather per sixteen rows).  Such a row joins the group with 0.0f at the missing positions: a running sum that started at +0.0 is never
+// -0.0, so adding +-0.0 = 0.0f * x leaves it unchanged bit for bit whenever x is finite; csr_patch_guard_kernel rewrites the output for batch
+// columns where x at a missing position is NOT finite (0 * Inf would leak a NaN the reference's row does not have).
+// Returns pattern -> (row, missing positions in the pattern's sequence); a row that joins a group this way leaves its own pattern (members[.] is cleared).
+typedef std::vector<std::vector<std::pair<int32_t, std::vector<int32_t>>>> PatchedRows;
+static PatchedRows csr_find_patched_rows(const int32_t* indptr, const int32_t* indices, const std::vector<int32_t>& rep, std::vector<std::vector<int32_t>>& members) {
     constexpr int MAX_PATCH = 4;
-    std::vector<std::vector<std::pair<int32_t, std::vector<int32_t>>>> patched(members.size());    // group -> (row, missing positions in the group's sequence)
-    if (!A.tune.no_patch) {
-        std::unordered_map<int32_t, std::vector<int32_t>> by_col;      // one of a group's first MAX_PATCH + 1 columns -> group
-        for (size_t g = 0; g < members.size(); g++) {
-            const int32_t s = indptr[rep[g]], e = indptr[rep[g] + 1];
-            if (members[g].size() < 8 || e - s < 32) continue;
-            for (int32_t t = 0; t <= MAX_PATCH && s + t < e; t++) by_col[indices[s + t]].push_back((int32_t)g);
-        }
-        for (size_t g1 = 0; g1 < members.size() && !by_col.empty(); g1++) {
-            if (members[g1].size() != 1) continue;
-            const int32_t r = members[g1][0];
-            const int32_t rs = indptr[r], re = indptr[r + 1];
-            if (re - rs < 32 - MAX_PATCH) continue;
-            auto it = by_col.find(indices[rs]);
-            if (it == by_col.end()) continue;
-            for (int32_t G : it->second) {
-                const int32_t gs = indptr[rep[G]], ge = indptr[rep[G] + 1];
-                const int32_t miss = (ge - gs) - (re - rs);
-                if (miss < 1 || miss > MAX_PATCH) continue;
-                std::vector<int32_t> pos;
-                int32_t k = rs;
-                for (int32_t j = gs; j < ge; j++) {
-                    if (k < re && indices[k] == indices[j]) k++;
-                    else {
-                        pos.push_back(j - gs);
-                        if ((int)pos.size() > miss) break;
-                    }
+    PatchedRows patched(members.size());
+    std::unordered_map<int32_t, std::vector<int32_t>> by_col;      // one of a group's first MAX_PATCH + 1 columns -> group
+    for (size_t g = 0; g < members.size(); g++) {
+        const int32_t s = indptr[rep[g]], e = indptr[rep[g] + 1];
+        if (members[g].size() < 8 || e - s < 32) continue;
+        for (int32_t t = 0; t <= MAX_PATCH && s + t < e; t++) by_col[indices[s + t]].push_back((int32_t)g);
+    }
+    for (size_t g1 = 0; g1 < members.size() && !by_col.empty(); g1++) {
+        if (members[g1].size() != 1) continue;
+        const int32_t r = members[g1][0];
+        const int32_t rs = indptr[r], re = indptr[r + 1];
+        if (re - rs < 32 - MAX_PATCH) continue;
+        auto it = by_col.find(indices[rs]);
+        if (it == by_col.end()) continue;
+        for (int32_t G : it->second) {
+            const int32_t gs = indptr[rep[G]], ge = indptr[rep[G] + 1];
+            const int32_t miss = (ge - gs) - (re - rs);
+            if (miss < 1 || miss > MAX_PATCH) continue;
+            std::vector<int32_t> pos;
+            int32_t k = rs;
+            for (int32_t j = gs; j < ge; j++) {
+                if (k < re && indices[k] == indices[j]) k++;
+                else {
+                    pos.push_back(j - gs);
+                    if ((int)pos.size() > miss) break;
                 }
-                if (k == re && (int)pos.size() == miss) {
-                    patched[(size_t)G].emplace_back(r, std::move(pos));
-                    members[g1].clear();
-                    break;
-                }
+            }
+            if (k == re && (int)pos.size() == miss) {
+                patched[(size_t)G].emplace_back(r, std::move(pos));
+                members[g1].clear();
+                break;
             }
         }
     }
-    std::vector<int32_t> patch_rows, patch_ptr{0}, patch_cols;
-    std::vector<int32_t> colptr{0}, cols, rowptr{0}, grows, wgrp, wr0, bgrp, br0, loose, mfg[3], mfr[3], wsg, wsr, m16g, m16r, nrg, nrr;
-    int64_t mf_rows = 0, mf_nnz = 0;
+    return patched;
+}
+
+// The group tables as the kernels read them.  Groups need >= 2 members and >= 1 column; a group's values are laid out [col j][member r], r padded to RB,
+// its patched rows behind its members.
+struct GroupTables {
+    std::vector<int32_t> colptr{0}, cols, rowptr{0}, rows, patch_rows, patch_ptr{0}, patch_cols;
     std::vector<int64_t> valptr{0};
     std::vector<float> vals;
+    std::vector<char> in_group;      // [rows of the operator]
     int64_t grouped_nnz = 0;
-    std::vector<char> in_group((size_t)rows, 0);
+    int64_t n_groups() const { return (int64_t)colptr.size() - 1; }
+    int64_t members(int64_t g) const { return rowptr[(size_t)g + 1] - rowptr[(size_t)g]; }
+    int64_t ncol(int64_t g) const { return colptr[(size_t)g + 1] - colptr[(size_t)g]; }
+};
+static GroupTables csr_layout_groups(int64_t rows, const int32_t* indptr, const int32_t* indices, const float* data, const std::vector<int32_t>& rep,
+                                     const std::vector<std::vector<int32_t>>& members, const PatchedRows& patched) {
+    GroupTables T;
+    T.in_group.assign((size_t)rows, 0);
     for (size_t g = 0; g < members.size(); g++) {
         const auto& m = members[g];
         if (m.size() < 2) continue;
         const int32_t s = indptr[rep[g]], e = indptr[rep[g] + 1];
         const int32_t ncol = e - s;
-        const int32_t gid = (int32_t)(colptr.size() - 1);
-        cols.insert(cols.end(), indices + s, indices + e);
-        colptr.push_back((int32_t)cols.size());
-        grows.insert(grows.end(), m.begin(), m.end());
+        T.cols.insert(T.cols.end(), indices + s, indices + e);
+        T.colptr.push_back((int32_t)T.cols.size());
+        T.rows.insert(T.rows.end(), m.begin(), m.end());
         const auto& pm = patched[g];
-        for (const auto& pr : pm) grows.push_back(pr.first);
-        rowptr.push_back((int32_t)grows.size());
+        for (const auto& pr : pm) T.rows.push_back(pr.first);
+        T.rowptr.push_back((int32_t)T.rows.size());
         const int64_t n_mem = (int64_t)m.size() + (int64_t)pm.size();
         const int64_t rpad = (n_mem + RB - 1) / RB * RB;
-        const int64_t v0 = (int64_t)vals.size();
-        vals.resize((size_t)(v0 + rpad * ncol), 0.0f);
+        const int64_t v0 = (int64_t)T.vals.size();
+        T.vals.resize((size_t)(v0 + rpad * ncol), 0.0f);
         for (size_t mi = 0; mi < m.size(); mi++) {
             const int32_t rs = indptr[m[mi]];
-            for (int32_t j = 0; j < ncol; j++) vals[(size_t)(v0 + (int64_t)j * rpad + (int64_t)mi)] = data[rs + j];
-            in_group[(size_t)m[mi]] = 1;
+            for (int32_t j = 0; j < ncol; j++) T.vals[(size_t)(v0 + (int64_t)j * rpad + (int64_t)mi)] = data[rs + j];
+            T.in_group[(size_t)m[mi]] = 1;
         }
         for (size_t pi = 0; pi < pm.size(); pi++) {
             const int32_t r = pm[pi].first;
@@ -638,114 +653,139 @@ int csr_build_groups(kn_operator* h, const int32_t* indptr, const int32_t* indic
             size_t pp = 0;
             for (int32_t j = 0; j < ncol; j++) {
                 if (pp < pos.size() && pos[pp] == j) {                  // missing here: the value stays 0.0f
-                    patch_cols.push_back(indices[s + j]);
+                    T.patch_cols.push_back(indices[s + j]);
                     pp++;
                 } else {
-                    vals[(size_t)(v0 + (int64_t)j * rpad + (int64_t)(m.size() + pi))] = data[k++];
+                    T.vals[(size_t)(v0 + (int64_t)j * rpad + (int64_t)(m.size() + pi))] = data[k++];
                 }
             }
-            patch_rows.push_back(r);
-            patch_ptr.push_back((int32_t)patch_cols.size());
-            in_group[(size_t)r] = 1;
+            T.patch_rows.push_back(r);
+            T.patch_ptr.push_back((int32_t)T.patch_cols.size());
+            T.in_group[(size_t)r] = 1;
         }
-        valptr.push_back((int64_t)vals.size());
-        for (int64_t r0 = 0; r0 < n_mem; r0 += 64) {                           // every group in 64-row chunks for the row-lane kernel (1 .. 8 batch columns)
-            nrg.push_back(gid);
-            nrr.push_back((int32_t)r0);
-        }
-        if (n_mem >= 256 && ncol >= 2048 && !A.tune.no_big_groups) {      // a keyed nn.Linear: LDS-staged kernel, 32 rows per workgroup
-            for (int64_t r0 = 0; r0 < n_mem; r0 += BIG_ROWS) {
-                bgrp.push_back(gid);
-                br0.push_back((int32_t)r0);
-            }
-            for (int64_t r0 = 0; r0 < n_mem; r0 += 16) {                       // the same group for the 16-row matrix-pipe kernel (narrow batches)
-                m16g.push_back(gid);
-                m16r.push_back((int32_t)r0);
-            }
-        } else {
-            for (int64_t r0 = 0; r0 < n_mem; r0 += RB) {
-                wgrp.push_back(gid);
-                wr0.push_back((int32_t)r0);
-            }
-            if (n_mem >= MF_MIN_MEMBERS) {
-                // matrix-pipe kernel: chunks of ONE 32-row block (a last block may be partly filled): 125 registers, four wavefronts per SIMD -- the adds of a result
-                // block wait for its matrix instruction and only other wavefronts fill that wait.  AllConvNet kept in CSR form, whole forward, chunks of 3 / 2 / 1
-                // blocks (229 / 157 / 125 registers): 32.84 / 32.26 / 31.38 ms.  Tuning::mf_nrb (KN_MF_NRB when the operator is created) picks another.
-                const int nrb_max = A.tune.mf_nrb;
-                for (int64_t r0 = 0; r0 < n_mem;) {
-                    const int64_t left = n_mem - r0;
-                    const int nrb = left >= 32 * nrb_max ? nrb_max : (int)((left + 31) / 32);
-                    mfg[nrb - 1].push_back(gid);
-                    mfr[nrb - 1].push_back((int32_t)r0);
-                    r0 += 32 * nrb;
-                }
-                mf_rows += n_mem;
-                mf_nnz += n_mem * ncol;
-            } else {
-                for (int64_t r0 = 0; r0 < n_mem; r0 += RB) {
-                    wsg.push_back(gid);
-                    wsr.push_back((int32_t)r0);
-                }
-            }
-        }
-        grouped_nnz += n_mem * ncol;
+        T.valptr.push_back((int64_t)T.vals.size());
+        T.grouped_nnz += n_mem * ncol;
     }
-    int rc;
-    std::vector<int32_t> longrows;
-    const bool use_long = !A.tune.no_big_groups;
+    T.cols.resize(T.cols.size() + NARROW_ROWS_COL_PAD, 0);        // the row-lane kernel's scalar look-ahead reads past a group's sequence (column 0: a valid row of X)
+    T.vals.resize(T.vals.size() + 64, 0.0f);     // the matrix-pipe kernel reads whole 32-row blocks: a partly filled last block reads past its column's rpad values
+    return T;
+}
+
+// Host image of a WorkList.  cut(): one group's member rows in chunks of `height`, a last chunk may be partly filled.
+struct HostList {
+    std::vector<int32_t> grp, r0;
+    void add(int64_t g, int64_t first) {
+        grp.push_back((int32_t)g);
+        r0.push_back((int32_t)first);
+    }
+    void cut(int64_t g, int64_t n_mem, int64_t height) {
+        for (int64_t first = 0; first < n_mem; first += height) add(g, first);
+    }
+};
+struct HostLists {
+    HostList work, big, ws, mf[3], mf16, nr;
+    int64_t mf_rows = 0, mf_nnz = 0;
+};
+// Each kernel's chunk rule, one line per list: which groups, what chunk height.  Every list is in group order, a group's chunks in member order.
+static HostLists csr_cut_work_lists(const GroupTables& T, const Tuning& tune) {
+    HostLists L;
+    for (int64_t g = 0; g < T.n_groups(); g++) {
+        const int64_t n_mem = T.members(g), ncol = T.ncol(g);
+        const bool big = n_mem >= 256 && ncol >= 2048 && !tune.no_big_groups;      // a keyed nn.Linear
+        const bool mf = !big && n_mem >= MF_MIN_MEMBERS;
+        L.nr.cut(g, n_mem, 64);                        // every group in 64-row chunks for the row-lane kernel (1 .. 8 batch columns)
+        if (big) L.big.cut(g, n_mem, BIG_ROWS);        // LDS-staged kernel, 32 rows per workgroup
+        if (big) L.mf16.cut(g, n_mem, 16);             // the same group for the 16-row matrix-pipe kernel (narrow batches)
+        if (!big) L.work.cut(g, n_mem, RB);            // the vector-ALU grouped kernels: bundles of RB rows
+        if (!big && !mf) L.ws.cut(g, n_mem, RB);       // ... and what is left to them behind the matrix-pipe launch
+        if (mf) {
+            // matrix-pipe kernel: chunks of ONE 32-row block (a last block may be partly filled): 125 registers, four wavefronts per SIMD -- the adds of a result
+            // block wait for its matrix instruction and only other wavefronts fill that wait.  AllConvNet kept in CSR form, whole forward, chunks of 3 / 2 / 1
+            // blocks (229 / 157 / 125 registers): 32.84 / 32.26 / 31.38 ms.  Tuning::mf_nrb (KN_MF_NRB when the operator is created) picks another.
+            const int nrb_max = tune.mf_nrb;
+            for (int64_t r0 = 0; r0 < n_mem;) {
+                const int64_t left = n_mem - r0;
+                const int nrb = left >= 32 * nrb_max ? nrb_max : (int)((left + 31) / 32);
+                L.mf[nrb - 1].add(g, r0);
+                r0 += 32 * nrb;
+            }
+            L.mf_rows += n_mem;
+            L.mf_nnz += n_mem * ncol;
+        }
+    }
+    return L;
+}
+
+// The rows outside every group: long rows (the deep-queue role), the rest loose -- in locality order where that pays
+struct UngroupedRows {
+    std::vector<int32_t> loose, longrows;
+    int64_t loose_max = 0;
+};
+static UngroupedRows csr_ungrouped_rows(int64_t rows, int64_t cols, const int32_t* indptr, const int32_t* indices, const std::vector<char>& in_group, const Tuning& tune) {
+    UngroupedRows U;
+    const bool use_long = !tune.no_big_groups;
     for (int64_t r = 0; r < rows; r++)
         if (!in_group[(size_t)r]) {
-            if (use_long && indptr[r + 1] - indptr[r] >= 1024) longrows.push_back((int32_t)r);   // one wave would walk them latency-bound: deep-queue role
-            else loose.push_back((int32_t)r);                     // includes empty rows (they must still be zeroed)
+            if (use_long && indptr[r + 1] - indptr[r] >= 1024) U.longrows.push_back((int32_t)r);   // one wave would walk them latency-bound: deep-queue role
+            else U.loose.push_back((int32_t)r);                     // includes empty rows (they must still be zeroed)
         }
     // loose rows of a big operator (keyed pooling: ~9 non-zeros per row, windows overlap): order them for L2 reuse of the gathers
-    if (loose.size() >= 4096 && !A.tune.no_row_order) {
+    if (U.loose.size() >= 4096 && !tune.no_row_order) {
         int64_t lnnz = 0;
-        for (int32_t r : loose) lnnz += indptr[r + 1] - indptr[r];
-        if (lnnz <= 64 * (int64_t)loose.size()) loose = locality_order(loose, indptr, indices, h->cols, 64, 64);
+        for (int32_t r : U.loose) lnnz += indptr[r + 1] - indptr[r];
+        if (lnnz <= 64 * (int64_t)U.loose.size()) U.loose = locality_order(U.loose, indptr, indices, cols, 64, 64);
     }
-    for (int32_t r : loose) A.loose_max = std::max<int64_t>(A.loose_max, indptr[r + 1] - indptr[r]);
-    cols.resize(cols.size() + NARROW_ROWS_COL_PAD, 0);        // the row-lane kernel's scalar look-ahead reads past a group's sequence (column 0: a valid row of X)
-    A.n_nr = (int64_t)nrg.size();
-    if ((rc = upload(&A.nr_grp, nrg.data(), nrg.size()))) return rc;
-    if ((rc = upload(&A.nr_r0, nrr.data(), nrr.size()))) return rc;
-    A.n_groups = (int64_t)colptr.size() - 1;
-    A.n_work = (int64_t)wgrp.size();
-    A.n_big = (int64_t)bgrp.size();
-    A.n_long = (int64_t)longrows.size();
-    A.n_loose = (int64_t)loose.size();
-    A.grouped_nnz = grouped_nnz;
-    A.n_patch = (int64_t)patch_rows.size();
-    if ((rc = upload(&A.patch_rows, patch_rows.data(), patch_rows.size()))) return rc;
-    if ((rc = upload(&A.patch_ptr, patch_ptr.data(), patch_ptr.size()))) return rc;
-    if ((rc = upload(&A.patch_cols, patch_cols.data(), patch_cols.size()))) return rc;
-    if ((rc = upload(&A.grp_colptr, colptr.data(), colptr.size()))) return rc;
-    if ((rc = upload(&A.grp_cols, cols.data(), cols.size()))) return rc;
-    if ((rc = upload(&A.grp_rowptr, rowptr.data(), rowptr.size()))) return rc;
-    if ((rc = upload(&A.grp_rows, grows.data(), grows.size()))) return rc;
-    if ((rc = upload(&A.grp_valptr, valptr.data(), valptr.size()))) return rc;
-    vals.resize(vals.size() + 64, 0.0f);         // the matrix-pipe kernel reads whole 32-row blocks: a partly filled last block reads past its column's rpad values
-    if ((rc = upload(&A.grp_vals, vals.data(), vals.size()))) return rc;
-    for (int k = 0; k < 3; k++) {
-        A.n_mf[k] = (int64_t)mfg[k].size();
-        if ((rc = upload(&A.mf_grp[k], mfg[k].data(), mfg[k].size()))) return rc;
-        if ((rc = upload(&A.mf_r0[k], mfr[k].data(), mfr[k].size()))) return rc;
-    }
-    A.mf_rows = mf_rows;
-    A.mf_nnz = mf_nnz;
-    A.n_mf16 = (int64_t)m16g.size();
-    if ((rc = upload(&A.mf16_grp, m16g.data(), m16g.size()))) return rc;
-    if ((rc = upload(&A.mf16_r0, m16r.data(), m16r.size()))) return rc;
-    A.n_ws = (int64_t)wsg.size();
-    if ((rc = upload(&A.ws_grp, wsg.data(), wsg.size()))) return rc;
-    if ((rc = upload(&A.ws_r0, wsr.data(), wsr.size()))) return rc;
-    if ((rc = upload(&A.work_grp, wgrp.data(), wgrp.size()))) return rc;
-    if ((rc = upload(&A.work_r0, wr0.data(), wr0.size()))) return rc;
-    if ((rc = upload(&A.big_grp, bgrp.data(), bgrp.size()))) return rc;
-    if ((rc = upload(&A.big_r0, br0.data(), br0.size()))) return rc;
-    if ((rc = upload(&A.long_rows, longrows.data(), longrows.size()))) return rc;
-    if ((rc = upload(&A.loose_rows, loose.data(), loose.size()))) return rc;
+    for (int32_t r : U.loose) U.loose_max = std::max<int64_t>(U.loose_max, indptr[r + 1] - indptr[r]);
+    return U;
+}
+
+// (destination, host vector) pairs, in the order the arrays have always been allocated in: the order decides where they land in HBM
+static int csr_upload(CsrDev& A, const GroupTables& T, const HostLists& L, const UngroupedRows& U) {
+    typedef std::pair<int32_t**, const std::vector<int32_t>*> Array;
+    auto arrays = [](std::initializer_list<Array> list) {
+        for (const Array& a : list)
+            if (int rc = upload(a.first, a.second->data(), a.second->size())) return rc;
+        return (int)KN_OK;
+    };
+    auto work_list = [&](WorkList& w, const HostList& h) {
+        w.n = (int64_t)h.grp.size();
+        return arrays({{&w.grp, &h.grp}, {&w.r0, &h.r0}});
+    };
+    int rc;
+    if ((rc = work_list(A.nr, L.nr))) return rc;
+    if ((rc = arrays({{&A.patch_rows, &T.patch_rows}, {&A.patch_ptr, &T.patch_ptr}, {&A.patch_cols, &T.patch_cols}, {&A.grp_colptr, &T.colptr}, {&A.grp_cols, &T.cols},
+                      {&A.grp_rowptr, &T.rowptr}, {&A.grp_rows, &T.rows}})))
+        return rc;
+    if ((rc = upload(&A.grp_valptr, T.valptr.data(), T.valptr.size()))) return rc;
+    if ((rc = upload(&A.grp_vals, T.vals.data(), T.vals.size()))) return rc;
+    const std::pair<WorkList*, const HostList*> lists[] = {{&A.mf[0], &L.mf[0]}, {&A.mf[1], &L.mf[1]}, {&A.mf[2], &L.mf[2]}, {&A.mf16, &L.mf16}, {&A.ws, &L.ws}, {&A.work, &L.work}, {&A.big, &L.big}};
+    for (const auto& l : lists)
+        if ((rc = work_list(*l.first, *l.second))) return rc;
+    if ((rc = arrays({{&A.long_rows, &U.longrows}, {&A.loose_rows, &U.loose}}))) return rc;
+    A.n_groups = T.n_groups();
+    A.grouped_nnz = T.grouped_nnz;
+    A.n_patch = (int64_t)T.patch_rows.size();
+    A.mf_rows = L.mf_rows;
+    A.mf_nnz = L.mf_nnz;
+    A.n_long = (int64_t)U.longrows.size();
+    A.n_loose = (int64_t)U.loose.size();
+    A.loose_max = U.loose_max;
     return KN_OK;
+}
+
+// Host analysis: bucket rows by their exact column sequence, lay the groups out, cut each kernel's work list, sort the remaining rows, upload.
+int csr_build_groups(kn_operator* h, const int32_t* indptr, const int32_t* indices, const float* data) {
+    CsrDev& A = h->csr;
+    std::vector<int32_t> pat, rep;                                // row -> pattern (none for an empty row), pattern -> representative row
+    row_patterns(A.rows, indptr, indices, false, pat, rep);
+    std::vector<std::vector<int32_t>> members(rep.size());        // pattern -> rows (ascending)
+    for (int64_t r = 0; r < A.rows; r++)
+        if (pat[(size_t)r] >= 0) members[(size_t)pat[(size_t)r]].push_back((int32_t)r);
+    const PatchedRows patched = A.tune.no_patch ? PatchedRows(members.size()) : csr_find_patched_rows(indptr, indices, rep, members);
+    const GroupTables T = csr_layout_groups(A.rows, indptr, indices, data, rep, members, patched);
+    const HostLists L = csr_cut_work_lists(T, A.tune);
+    const UngroupedRows U = csr_ungrouped_rows(A.rows, h->cols, indptr, indices, T.in_group, A.tune);
+    return csr_upload(A, T, L, U);
 }
 
 // ---- locality order (host) --------------------------------------------------------------------------------------------------
@@ -971,23 +1011,25 @@ struct Planes {            // kn_spmm_planes: n independent activation blocks (b
     int64_t n = 1, x_stride = 0, y_stride = 0;
 };
 
+// `groups` through csr_group_kernel<VEC, RBK>, the `n_loose` rows of `loose_rows` through csr_rows_kernel<VEC>
 template <int VEC, int RBK>
-static int launch_csr(const CsrDev& A, const float* x, int64_t ldx, int64_t n_vecs, float* y, int64_t ldy, int relu, hipStream_t s, float* absmax = nullptr, const Planes pl = Planes()) {
+static int launch_csr(const CsrDev& A, const WorkList& groups, const int32_t* loose_rows, int64_t n_loose, const float* x, int64_t ldx, int64_t n_vecs, float* y, int64_t ldy, int relu,
+                      hipStream_t s, float* absmax = nullptr, const Planes pl = Planes()) {
     const int64_t n_ct = (n_vecs + 64 * VEC - 1) / (64 * VEC);
     const std::string np = pl.n > 1 ? (" x " + std::to_string(pl.n) + " planes in one launch") : std::string();
-    if (A.n_work > 0) {
-        const int64_t n_rb = (A.n_work * (RB / RBK) + WAVES - 1) / WAVES;
+    if (groups.n > 0) {
+        const int64_t n_rb = (groups.n * (RB / RBK) + WAVES - 1) / WAVES;
         const int64_t items = n_ct * n_rb;
         const int64_t grid = ((items + 7) / 8) * 8;
-        KN_LAUNCH("csr_group_kernel<vec=" + std::to_string(VEC) + ",rows=" + std::to_string(RBK) + ">" + np, (csr_group_kernel<VEC, RBK>), dim3((unsigned)grid, (unsigned)pl.n), dim3(256), 0, s, A.n_work, A.work_grp, A.work_r0, A.grp_colptr, A.grp_cols,
-                           A.grp_rowptr, A.grp_rows, A.grp_valptr, A.grp_vals, x, ldx, y, ldy, n_vecs, relu, n_rb, pl.x_stride, pl.y_stride);
+        KN_LAUNCH("csr_group_kernel<vec=" + std::to_string(VEC) + ",rows=" + std::to_string(RBK) + ">" + np, (csr_group_kernel<VEC, RBK>), dim3((unsigned)grid, (unsigned)pl.n), dim3(256), 0, s, groups.n, groups.grp, groups.r0,
+                  KN_GROUP_TABLES(A), x, ldx, y, ldy, n_vecs, relu, n_rb, pl.x_stride, pl.y_stride);
     }
-    if (A.n_loose > 0) {
-        const int64_t n_rb = (A.n_loose + WAVES - 1) / WAVES;
+    if (n_loose > 0) {
+        const int64_t n_rb = (n_loose + WAVES - 1) / WAVES;
         const int64_t items = n_ct * n_rb;
         const int64_t grid = ((items + 7) / 8) * 8;
-        KN_LAUNCH("csr_rows_kernel<vec=" + std::to_string(VEC) + ">" + np, csr_rows_kernel<VEC>, dim3((unsigned)grid, (unsigned)pl.n), dim3(256), 0, s, A.loose_rows, A.n_loose, A.indptr, A.indices, A.data, x, ldx,
-                           y, ldy, n_vecs, relu, n_rb, absmax, pl.x_stride, pl.y_stride);
+        KN_LAUNCH("csr_rows_kernel<vec=" + std::to_string(VEC) + ">" + np, csr_rows_kernel<VEC>, dim3((unsigned)grid, (unsigned)pl.n), dim3(256), 0, s, loose_rows, n_loose, A.indptr, A.indices, A.data, x, ldx,
+                  y, ldy, n_vecs, relu, n_rb, absmax, pl.x_stride, pl.y_stride);
     }
     KN_HIP(hipGetLastError());
     return KN_OK;
@@ -995,19 +1037,20 @@ static int launch_csr(const CsrDev& A, const float* x, int64_t ldx, int64_t n_ve
 
 // grouped rows through the software-pipelined kernel (RBX member rows per wavefront), loose rows as in launch_csr<4, .>
 template <int RBX>
-static int launch_csr_pipe(const CsrDev& A, const float* x, int64_t ldx, int64_t n_vecs, float* y, int64_t ldy, int relu, hipStream_t s) {
+static int launch_csr_pipe(const CsrDev& A, const WorkList& groups, const int32_t* loose_rows, int64_t n_loose, const float* x, int64_t ldx, int64_t n_vecs, float* y, int64_t ldy, int relu,
+                           hipStream_t s) {
     const int64_t n_ct = (n_vecs + 255) / 256;
     {
-        const int64_t n_rb = (A.n_work * (RB / RBX) + WAVES - 1) / WAVES;
+        const int64_t n_rb = (groups.n * (RB / RBX) + WAVES - 1) / WAVES;
         const int64_t grid = ((n_ct * n_rb + 7) / 8) * 8;
-        KN_LAUNCH("csr_group_pipe_kernel<rows=" + std::to_string(RBX) + ">", (csr_group_pipe_kernel<RBX>), dim3((unsigned)grid), dim3(256), 0, s, A.n_work, A.work_grp, A.work_r0, A.grp_colptr, A.grp_cols,
-                           A.grp_rowptr, A.grp_rows, A.grp_valptr, A.grp_vals, x, ldx, y, ldy, n_vecs, relu, n_rb);
+        KN_LAUNCH("csr_group_pipe_kernel<rows=" + std::to_string(RBX) + ">", (csr_group_pipe_kernel<RBX>), dim3((unsigned)grid), dim3(256), 0, s, groups.n, groups.grp, groups.r0, KN_GROUP_TABLES(A),
+                  x, ldx, y, ldy, n_vecs, relu, n_rb);
     }
-    if (A.n_loose > 0) {
-        const int64_t n_rb = (A.n_loose + WAVES - 1) / WAVES;
+    if (n_loose > 0) {
+        const int64_t n_rb = (n_loose + WAVES - 1) / WAVES;
         const int64_t grid = ((n_ct * n_rb + 7) / 8) * 8;
-        KN_LAUNCH("csr_rows_kernel<vec=4>", csr_rows_kernel<4>, dim3((unsigned)grid), dim3(256), 0, s, A.loose_rows, A.n_loose, A.indptr, A.indices, A.data, x, ldx, y, ldy,
-                           n_vecs, relu, n_rb);
+        KN_LAUNCH("csr_rows_kernel<vec=4>", csr_rows_kernel<4>, dim3((unsigned)grid), dim3(256), 0, s, loose_rows, n_loose, A.indptr, A.indices, A.data, x, ldx, y, ldy,
+                  n_vecs, relu, n_rb);
     }
     KN_HIP(hipGetLastError());
     return KN_OK;
@@ -1040,88 +1083,91 @@ __global__ __launch_bounds__(256) void csr_patch_guard_kernel(int64_t n_patch, c
     Y[(int64_t)r * ldy + c] = acc;
 }
 
-static int csr_spmm_groups(const CsrDev& A, const float* x, int64_t ldx, int64_t n_vecs, float* y, int64_t ldy, uint32_t flags, hipStream_t s, float* rows_only_absmax = nullptr);
+// ---- decide, then launch ----------------------------------------------------------------------------------------------------
 
-// KN_FLAG_NARROW_ROWS on 1 .. 8 columns: the long loose rows in the deep-queue role of the big-group launch, as without the flag; loose rows too long for a lane
-// (narrow_rows_loose) on csr_rows_kernel, as without the flag; everything else in one launch of the row-lane kernel.  csr_spmm adds the patch guard.
-static int csr_spmm_row_lanes(const CsrDev& A, const float* x, int64_t ldx, int64_t n_vecs, float* y, int64_t ldy, uint32_t flags, hipStream_t s) {
-    const int relu = (flags & KN_FLAG_RELU) ? 1 : 0;
-    if (A.n_long > 0) {
-        KN_LAUNCH("csr_big_group_kernel (long rows)", csr_big_group_kernel, dim3((unsigned)A.n_long), dim3(256), 0, s, (int64_t)0, A.big_grp, A.big_r0, A.grp_colptr, A.grp_cols, A.grp_rowptr,
-                  A.grp_rows, A.grp_valptr, A.grp_vals, x, ldx, y, ldy, n_vecs, relu, (int64_t)0, A.long_rows, A.n_long, A.indptr, A.indices, A.data);
-        KN_HIP(hipGetLastError());
-    }
-    const bool loose = narrow_rows_loose(A);
-    if (!loose && A.n_loose > 0) {
-        CsrDev R = A;                                    // (a view: the loose rows only)
-        R.n_work = 0;
-        if (int rc = launch_csr<1, 8>(R, x, ldx, n_vecs, y, ldy, relu, s)) return rc;
-    }
-    return csr_narrow_rows_spmm(A, x, ldx, n_vecs, y, ldy, relu, loose, s);
-}
-
-int csr_spmm(const CsrDev& A, const float* x, int64_t ldx, int64_t n_vecs, float* y, int64_t ldy, uint32_t flags, hipStream_t s, float* absmax, bool* absmax_fused) {
-    // an operator of loose rows only (keyed pooling) is ONE launch of a row kernel: max |Y| (kn_spmm_screen) rides in its epilogue
-    const bool row_lanes = narrow_rows_call(A, flags, n_vecs, ldx);       // KN_FLAG_NARROW_ROWS: max |Y| comes from the caller's reduction pass, as behind the other narrow kernels
-    const bool rows_only = !row_lanes && A.n_work == 0 && A.n_big == 0 && A.n_long == 0 && A.n_patch == 0 && A.n_loose > 0;
-    if (absmax_fused) *absmax_fused = absmax != nullptr && rows_only;
-    const int rc = row_lanes ? csr_spmm_row_lanes(A, x, ldx, n_vecs, y, ldy, flags, s) : csr_spmm_groups(A, x, ldx, n_vecs, y, ldy, flags, s, rows_only ? absmax : nullptr);
-    if (rc != KN_OK || A.n_patch == 0) return rc;
-    const int64_t n_ct = (n_vecs + 255) / 256;
-    KN_LAUNCH("csr_patch_guard_kernel<" + std::to_string(A.n_patch) + " patched rows>", csr_patch_guard_kernel, dim3((unsigned)(A.n_patch * n_ct)), dim3(256), 0, s, A.n_patch,
-              A.patch_rows, A.patch_ptr, A.patch_cols, A.indptr, A.indices, A.data, x, ldx, y, ldy, n_vecs, (flags & KN_FLAG_RELU) ? 1 : 0);
-    KN_HIP(hipGetLastError());
-    return KN_OK;
-}
-
-static int csr_spmm_groups(const CsrDev& A, const float* x, int64_t ldx, int64_t n_vecs, float* y, int64_t ldy, uint32_t flags, hipStream_t s, float* rows_only_absmax) {
-    const int relu = (flags & KN_FLAG_RELU) ? 1 : 0;
+// What the vector-width rules read of a call: the work behind it and how its operands are aligned
+struct CsrCall {
+    int64_t n_work = 0, n_loose = 0;      // bundles of RB member rows, loose rows
+    const float* x = nullptr;
+    int64_t ldx = 0;
+    const float* y = nullptr;
+    int64_t ldy = 0, n_vecs = 0;
+    Planes pl;
     // a vector width is usable when pointers / strides allow it AND it keeps the wavefronts filled (64 * v columns per wave): n_vecs = 128
     // (a half-batch column window) takes v = 2 with every lane active rather than v = 4 with lanes 32..63 idle
-    auto aligned = [&](int v) {
-        return (n_vecs % v == 0) && (ldx % v == 0) && (ldy % v == 0) && (((uintptr_t)x) % (4 * v) == 0) && (((uintptr_t)y) % (4 * v) == 0) &&
-               (v == 1 || 4 * n_vecs >= 3 * ((n_vecs + 64 * v - 1) / (64 * v)) * (64 * v));     // >= 75 % of the lanes busy
-    };
-    // (rows per wavefront, batch columns per lane): the most accumulators per lane that still gives the chip >= 2048
-    // wavefronts; operators with few rows (a 121-row Linear, a dense Linear at n_vecs = 256) fall through to thinner
-    // bundles / narrower vectors -- the walk over a row's columns is serial by contract, so parallelism can only come
-    // from rows and batch columns.
+    bool aligned(int v) const {
+        return (n_vecs % v == 0) && (ldx % v == 0) && (ldy % v == 0) && (pl.x_stride % v == 0) && (pl.y_stride % v == 0) && (((uintptr_t)x) % (4 * v) == 0) &&
+               (((uintptr_t)y) % (4 * v) == 0) && (v == 1 || 4 * n_vecs >= 3 * ((n_vecs + 64 * v - 1) / (64 * v)) * (64 * v));     // >= 75 % of the lanes busy
+    }
+    int64_t waves(int v, int rbk) const { return (n_work * (RB / rbk) + (n_loose + WAVES - 1) / WAVES * WAVES) * ((n_vecs + 64 * v - 1) / (64 * v)) * pl.n; }
+};
+static constexpr int64_t ENOUGH = 2048;
+
+// (batch columns per lane, rows per wavefront): the most accumulators per lane that still gives the chip >= 2048
+// wavefronts; operators with few rows (a 121-row Linear, a dense Linear at n_vecs = 256) fall through to thinner
+// bundles / narrower vectors -- the walk over a row's columns is serial by contract, so parallelism can only come
+// from rows and batch columns.  `thin_groups`: what an operator WITH pattern groups takes when no step gives enough wavefronts -- one row per wavefront
+// (kn_spmm), or (kn_spmm_planes) what loose rows alone take.
+struct VecRows { int vec, rbk; };
+static VecRows csr_vec_rows(const CsrCall& c, bool thin_groups) {
+    static constexpr VecRows ladder[] = {{4, 8}, {2, 8}, {4, 2}, {1, 8}, {2, 2}, {1, 2}};
+    for (const VecRows& t : ladder)
+        if (c.aligned(t.vec) && c.waves(t.vec, t.rbk) >= ENOUGH) return t;
+    if (c.n_work > 0 && thin_groups) return {1, 1};
+    // loose rows only: the bundle height is irrelevant, take the widest aligned vector
+    if (c.aligned(4) && c.n_vecs >= 256) return {4, 8};
+    if (c.aligned(2) && c.n_vecs >= 128) return {2, 8};
+    return {1, 8};
+}
+static int launch_csr_as(VecRows t, const CsrDev& A, const WorkList& groups, const int32_t* loose_rows, int64_t n_loose, const float* x, int64_t ldx, int64_t n_vecs, float* y, int64_t ldy,
+                         int relu, hipStream_t s, float* absmax, const Planes pl);      // launch_csr<t.vec, t.rbk>; defined behind csr_spmm: the compiler emits the kernel
+                                                                                        // instantiations in the order this file names them, and the code object keeps its layout
+
+// What a kn_spmm on a CSR handle launches, in launch order; decided before anything is launched (csr_choice), launched by csr_spmm
+struct CsrChoice {
+    enum LongRows { LONG_NONE, LONG_AS_ROWS, LONG_DEEP } long_rows = LONG_NONE;      // csr_rows_kernel<4> of their own | the deep-queue role of the big-group launch
+    enum Big { BIG_NONE, BIG_MFMA16, BIG_LDS } big = BIG_NONE;                       // csr_group_mfma16_kernel | csr_big_group_kernel
+    bool mfma = false;               // the matrix-pipe lists run; the vector-ALU kernels then take `ws` instead of `work`
+    bool loose_first = false;        // ROW_LANES: loose rows too long for a lane, on csr_rows_kernel<1> ahead of the row-lane launch
+    enum Kernel { NONE, ROW_LANES, ROWS_PAIR, PIPE, PLAIN } kernel = NONE;           // what takes `groups` and the first `n_loose` loose rows
+    WorkList groups;
+    int64_t n_loose = 0;
+    VecRows t = {1, 1};              // PLAIN: launch_csr<vec, rbk>; PIPE: rbk = 16 | 8
+    bool absmax_rides = false;       // max |Y| (kn_spmm_screen) in the epilogue of the row kernel
+};
+
+static CsrChoice csr_choice(const CsrDev& A, const float* x, int64_t ldx, const float* y, int64_t ldy, int64_t n_vecs, uint32_t flags) {
+    CsrChoice c;
+    const bool align4 = (n_vecs % 4 == 0) && (ldx % 4 == 0) && (ldy % 4 == 0) && (((uintptr_t)x) % 16 == 0) && (((uintptr_t)y) % 16 == 0);
+    // KN_FLAG_NARROW_ROWS on 1 .. 8 columns: the long loose rows in the deep-queue role of the big-group launch, as without the flag; loose rows too long for a lane
+    // (narrow_rows_loose) on csr_rows_kernel, as without the flag; everything else in one launch of the row-lane kernel.  max |Y| comes from the caller's reduction
+    // pass, as behind the other narrow kernels.
+    if (narrow_rows_call(A, flags, n_vecs, ldx)) {
+        if (A.n_long > 0) c.long_rows = CsrChoice::LONG_DEEP;
+        c.kernel = CsrChoice::ROW_LANES;
+        c.groups = A.nr;
+        c.loose_first = !narrow_rows_loose(A) && A.n_loose > 0;
+        c.n_loose = narrow_rows_loose(A) ? A.n_loose : 0;
+        return c;
+    }
+    // an operator of loose rows only (keyed pooling) is ONE launch of a row kernel: max |Y| (kn_spmm_screen) rides in its epilogue
+    c.absmax_rides = A.work.n == 0 && A.big.n == 0 && A.n_long == 0 && A.n_patch == 0 && A.n_loose > 0;
     // Long loose rows (>= 1024 stored entries: a row of a keyed Linear, or of a wide permutation-keyed conv, whose pattern lost an entry to
     // an exact zero).  The deep-queue role of the big-group launch (one wave per row and 64 batch columns, 4 bytes per lane) exists for
     // NARROW batches, where such a row would otherwise be walked by a single wave; with a wide batch there are enough (row, 256-column
     // tile) pairs to fill the chip with the plain row kernel at 16 bytes per lane (AllConvNet conv5 at 4 096 images: 752 such rows took
     // 1.80 ms in the deep-queue role -- 15 % of the layer -- against ~0.2 ms this way).
-    const bool long_as_rows = A.n_long > 0 && (n_vecs % 4 == 0) && (ldx % 4 == 0) && (ldy % 4 == 0) && (((uintptr_t)x) % 16 == 0) && (((uintptr_t)y) % 16 == 0) &&
-                              A.n_long * ((n_vecs + 255) / 256) >= 1024;
-    const int64_t n_long_deep = long_as_rows ? 0 : A.n_long;
-    if (long_as_rows) {
-        const int64_t n_ct4 = (n_vecs + 255) / 256;
-        const int64_t n_rb = (A.n_long + WAVES - 1) / WAVES;
-        KN_LAUNCH("csr_rows_kernel<vec=4> (long rows)", csr_rows_kernel<4>, dim3((unsigned)(((n_ct4 * n_rb + 7) / 8) * 8)), dim3(256), 0, s, A.long_rows, A.n_long, A.indptr, A.indices,
-                  A.data, x, ldx, y, ldy, n_vecs, relu, n_rb);
-        KN_HIP(hipGetLastError());
-    }
+    if (A.n_long > 0) c.long_rows = (align4 && A.n_long * ((n_vecs + 255) / 256) >= 1024) ? CsrChoice::LONG_AS_ROWS : CsrChoice::LONG_DEEP;
     // Big pattern groups (a keyed Linear in the reference's order): 16-row chunks with their products on the matrix pipe, one wavefront per chunk and 64 batch
-    // columns, when that gives every SIMD two wavefronts (>= 2048 of them).  Same-process A/B against the LDS-staged kernel below (ms, 4096 x 25088 at 512 /
+    // columns, when that gives every SIMD two wavefronts (>= 2048 of them).  Same-process A/B against the LDS-staged kernel (ms, 4096 x 25088 at 512 /
     // 1024 / 2048 columns: 3.38 / 5.85 / 11.17 against 2.68 / 4.37 / 8.17; 4096 x 4096 at 512 / 1024: 0.59 / 1.02 against 0.49 / 0.77); with ONE wavefront per
     // SIMD (VGG-16 fc6 at 256 images: 1 024 chunks) it loses -- 2.16 against 1.74 ms, a lone wavefront pays ~9 cycles per instruction -- and the LDS-staged
     // kernel stays.  Tuning::big_mfma16 (KN_BIG_MFMA16=0|1 when the operator is created) forces either.
-    bool big_done = false;
-    if (A.n_big > 0 && A.n_mf16 > 0 && n_vecs >= 64 && (A.tune.big_mfma16 < 0 ? A.n_mf16 * ((n_vecs + 63) / 64) >= 2048 : A.tune.big_mfma16 > 0)) {
-        const int rc = csr_group_mfma16_spmm(A, x, ldx, n_vecs, y, ldy, relu, s);
-        if (rc) return rc;
-        big_done = true;
+    if (A.big.n > 0) {
+        const bool mfma16 = A.mf16.n > 0 && n_vecs >= 64 && (A.tune.big_mfma16 < 0 ? A.mf16.n * ((n_vecs + 63) / 64) >= ENOUGH : A.tune.big_mfma16 > 0);
+        c.big = mfma16 ? CsrChoice::BIG_MFMA16 : CsrChoice::BIG_LDS;
     }
-    if ((A.n_big > 0 && !big_done) || n_long_deep > 0) {
-        const int64_t n_ct = (n_vecs + 63) / 64;
-        const int64_t n_big = big_done ? 0 : A.n_big;
-        const int64_t grid_big = ((n_ct * n_big + 7) / 8) * 8;
-        const int64_t grid_long = n_long_deep * ((n_ct + 3) / 4);
-        KN_LAUNCH("csr_big_group_kernel", csr_big_group_kernel, dim3((unsigned)(grid_big + grid_long)), dim3(256), 0, s, n_big, A.big_grp, A.big_r0, A.grp_colptr, A.grp_cols,
-                           A.grp_rowptr, A.grp_rows, A.grp_valptr, A.grp_vals, x, ldx, y, ldy, n_vecs, relu, grid_big, A.long_rows, n_long_deep, A.indptr, A.indices, A.data);
-        KN_HIP(hipGetLastError());
-    }
-    if ((A.n_big > 0 || A.n_long > 0) && A.n_work == 0 && A.n_loose == 0) return KN_OK;
+    if ((A.big.n > 0 || A.n_long > 0) && A.work.n == 0 && A.n_loose == 0) return c;
     // Pattern groups with >= MF_MIN_MEMBERS members and long stored sequences on a wide batch: products on the matrix pipe, sums on the vector
     // ALU (kn_csr_mfma.hip: same bits; an activation row is fetched once per 96 member rows instead of once per 16 -- AllConvNet conv2 reads
     // 11.7 GB from the fabric per launch instead of 27.8).  Same-process A/B under sustained load (tools/ab_allconv.py): the two formulations
@@ -1129,58 +1175,105 @@ static int csr_spmm_groups(const CsrDev& A, const float* x, int64_t ldx, int64_t
     // other, and layers with short sequences (AllConvNet conv1: 28 columns, conv8: 193) are faster on the vector-ALU pipeline, whose five
     // wavefronts per SIMD hide the ring's start-up better: those stay there (mean stored columns per member row < 256).  The remaining small
     // groups and the loose rows go through the kernels below.  Tuning::group_mfma (KN_GROUP_MFMA=0|1 when the operator is created) forces either.
-    {
-        const int64_t n_mf = A.n_mf[0] + A.n_mf[1] + A.n_mf[2];
-        const bool long_rows = A.mf_rows > 0 && A.mf_nnz >= 256 * A.mf_rows;
-        const bool want = A.tune.group_mfma < 0 ? long_rows : A.tune.group_mfma > 0;
-        if (want && n_mf > 0 && n_vecs >= 128 && n_mf * ((n_vecs + 255) / 256) * WAVES >= 2048) {
-            int rc = csr_group_mfma_spmm(A, x, ldx, n_vecs, y, ldy, relu, s);
-            if (rc) return rc;
-            if (A.n_ws == 0 && A.n_loose == 0) return KN_OK;
-            CsrDev R = A;                                // (a view: same device arrays, the small groups' bundle list in place of all groups')
-            R.work_grp = A.ws_grp;
-            R.work_r0 = A.ws_r0;
-            R.n_work = A.n_ws;
-            R.n_mf[0] = R.n_mf[1] = R.n_mf[2] = 0;
-            R.n_big = R.n_long = 0;
-            return csr_spmm_groups(R, x, ldx, n_vecs, y, ldy, flags, s);
-        }
-    }
+    const int64_t n_mf = A.mf[0].n + A.mf[1].n + A.mf[2].n;
+    const bool long_seqs = A.mf_rows > 0 && A.mf_nnz >= 256 * A.mf_rows;
+    c.mfma = (A.tune.group_mfma < 0 ? long_seqs : A.tune.group_mfma > 0) && n_mf > 0 && n_vecs >= 128 && n_mf * ((n_vecs + 255) / 256) * WAVES >= ENOUGH;
+    if (c.mfma && A.ws.n == 0 && A.n_loose == 0) return c;
+    c.groups = c.mfma ? A.ws : A.work;
+    c.n_loose = A.n_loose;
     // short loose rows over a batch window that fills only half of a 256-column wave tile: one row per half wavefront
-    if (A.n_work == 0 && A.n_loose >= 4096 && A.nnz <= 32 * A.n_loose && n_vecs % 128 == 0 && (n_vecs / 128) % 2 == 1 && (ldx % 4 == 0) && (ldy % 4 == 0) &&
+    if (c.groups.n == 0 && A.n_loose >= 4096 && A.nnz <= 32 * A.n_loose && n_vecs % 128 == 0 && (n_vecs / 128) % 2 == 1 && (ldx % 4 == 0) && (ldy % 4 == 0) &&
         (((uintptr_t)x) % 16 == 0) && (((uintptr_t)y) % 16 == 0)) {
-        const int64_t n_rb = (A.n_loose + 2 * WAVES - 1) / (2 * WAVES);
-        const int64_t items = ((n_vecs + 127) / 128) * n_rb;
-        KN_LAUNCH("csr_rows_pair_kernel", csr_rows_pair_kernel, dim3((unsigned)(((items + 7) / 8) * 8)), dim3(256), 0, s, A.loose_rows, A.n_loose, A.indptr, A.indices, A.data, x, ldx, y,
-                           ldy, n_vecs, relu, n_rb, rows_only_absmax);
-        KN_HIP(hipGetLastError());
-        return KN_OK;
+        c.kernel = CsrChoice::ROWS_PAIR;
+        return c;
     }
-    const int64_t loose = (A.n_loose + WAVES - 1) / WAVES * WAVES;
-    auto waves = [&](int v, int rbk) { return (A.n_work * (RB / rbk) + loose) * ((n_vecs + 64 * v - 1) / (64 * v)); };
-    constexpr int64_t ENOUGH = 2048;
-#define KN_TRY(V, R) \
-    if (aligned(V) && waves(V, R) >= ENOUGH) return launch_csr<V, R>(A, x, ldx, n_vecs, y, ldy, relu, s, rows_only_absmax);
+    const CsrCall call{c.groups.n, A.n_loose, x, ldx, y, ldy, n_vecs, Planes()};
     // wide case: the software-pipelined grouped kernel, 16 member rows per wavefront when the groups fill such bundles, else 8
     // (Tuning::no_group_pipe: the plain grouped kernel, for the parity tests' side-by-side)
-    if (A.n_work > 0 && aligned(4) && A.cols * ldx < ((int64_t)1 << 31) && !A.tune.no_group_pipe) {
-        const int64_t grouped_rows = A.rows - A.n_loose - A.n_long - A.n_big * 32;           // upper bound (a big group's last bundle may be partial)
-        if (waves(4, 16) >= ENOUGH && 10 * grouped_rows >= 7 * A.n_work * 16) return launch_csr_pipe<16>(A, x, ldx, n_vecs, y, ldy, relu, s);
-        if (waves(4, 8) >= ENOUGH) return launch_csr_pipe<8>(A, x, ldx, n_vecs, y, ldy, relu, s);
+    if (c.groups.n > 0 && call.aligned(4) && A.cols * ldx < ((int64_t)1 << 31) && !A.tune.no_group_pipe) {
+        // upper bound (a big group's last bundle may be partial; behind the matrix-pipe launch its rows, the big groups' and the long rows count as well)
+        const int64_t grouped_rows = A.rows - A.n_loose - (c.mfma ? 0 : A.n_long + A.big.n * 32);
+        c.kernel = CsrChoice::PIPE;
+        c.t = {4, 16};
+        if (call.waves(4, 16) >= ENOUGH && 10 * grouped_rows >= 7 * c.groups.n * 16) return c;
+        c.t = {4, 8};
+        if (call.waves(4, 8) >= ENOUGH) return c;
     }
-    KN_TRY(4, 8)
-    KN_TRY(2, 8)
-    KN_TRY(4, 2)
-    KN_TRY(1, 8)
-    KN_TRY(2, 2)
-    KN_TRY(1, 2)
-#undef KN_TRY
-    if (A.n_work == 0) {   // loose rows only: the bundle height is irrelevant, take the widest aligned vector
-        if (aligned(4) && n_vecs >= 256) return launch_csr<4, 8>(A, x, ldx, n_vecs, y, ldy, relu, s, rows_only_absmax);
-        if (aligned(2) && n_vecs >= 128) return launch_csr<2, 8>(A, x, ldx, n_vecs, y, ldy, relu, s, rows_only_absmax);
-        return launch_csr<1, 8>(A, x, ldx, n_vecs, y, ldy, relu, s, rows_only_absmax);
+    c.kernel = CsrChoice::PLAIN;
+    c.t = csr_vec_rows(call, true);
+    return c;
+}
+
+// CsrChoice::ROW_LANES: loose rows too long for a lane on csr_rows_kernel<1>, then `groups` and the other loose rows in one launch of the row-lane kernel
+static int launch_row_lanes(const CsrDev& A, const CsrChoice& c, const float* x, int64_t ldx, int64_t n_vecs, float* y, int64_t ldy, int relu, hipStream_t s) {
+    if (c.loose_first)
+        if (int rc = launch_csr<1, 8>(A, WorkList(), A.loose_rows, A.n_loose, x, ldx, n_vecs, y, ldy, relu, s)) return rc;
+    return csr_narrow_rows_spmm(A, c.groups, A.loose_rows, c.n_loose, x, ldx, n_vecs, y, ldy, relu, s);
+}
+
+int csr_spmm(const CsrDev& A, const float* x, int64_t ldx, int64_t n_vecs, float* y, int64_t ldy, uint32_t flags, hipStream_t s, float* absmax, bool* absmax_fused) {
+    const CsrChoice c = csr_choice(A, x, ldx, y, ldy, n_vecs, flags);
+    const int relu = (flags & KN_FLAG_RELU) ? 1 : 0;
+    if (absmax_fused) *absmax_fused = absmax != nullptr && c.absmax_rides;
+    if (!c.absmax_rides) absmax = nullptr;
+    int rc = KN_OK;
+    if (c.long_rows == CsrChoice::LONG_AS_ROWS) {
+        const int64_t n_ct4 = (n_vecs + 255) / 256;
+        const int64_t n_rb = (A.n_long + WAVES - 1) / WAVES;
+        KN_LAUNCH("csr_rows_kernel<vec=4> (long rows)", csr_rows_kernel<4>, dim3((unsigned)(((n_ct4 * n_rb + 7) / 8) * 8)), dim3(256), 0, s, A.long_rows, A.n_long, A.indptr, A.indices,
+                  A.data, x, ldx, y, ldy, n_vecs, relu, n_rb);
+        KN_HIP(hipGetLastError());
     }
-    return launch_csr<1, 1>(A, x, ldx, n_vecs, y, ldy, relu, s, rows_only_absmax);
+    if (c.big == CsrChoice::BIG_MFMA16 && (rc = csr_group_mfma16_spmm(A, A.mf16, x, ldx, n_vecs, y, ldy, relu, s))) return rc;
+    if (c.big == CsrChoice::BIG_LDS || c.long_rows == CsrChoice::LONG_DEEP) {
+        const int64_t n_ct = (n_vecs + 63) / 64;
+        const int64_t n_big = c.big == CsrChoice::BIG_LDS ? A.big.n : 0, n_long_deep = c.long_rows == CsrChoice::LONG_DEEP ? A.n_long : 0;
+        const int64_t grid_big = ((n_ct * n_big + 7) / 8) * 8;
+        const int64_t grid_long = n_long_deep * ((n_ct + 3) / 4);
+        KN_LAUNCH(c.kernel == CsrChoice::ROW_LANES ? "csr_big_group_kernel (long rows)" : "csr_big_group_kernel", csr_big_group_kernel, dim3((unsigned)(grid_big + grid_long)), dim3(256), 0, s, n_big,
+                  A.big.grp, A.big.r0, KN_GROUP_TABLES(A), x, ldx, y, ldy, n_vecs, relu, grid_big, A.long_rows, n_long_deep, A.indptr, A.indices, A.data);
+        KN_HIP(hipGetLastError());
+    }
+    if (c.mfma && (rc = csr_group_mfma_spmm(A, A.mf, x, ldx, n_vecs, y, ldy, relu, s))) return rc;
+    switch (c.kernel) {
+        case CsrChoice::NONE: break;
+        case CsrChoice::ROW_LANES: rc = launch_row_lanes(A, c, x, ldx, n_vecs, y, ldy, relu, s); break;
+        case CsrChoice::ROWS_PAIR: {
+            const int64_t n_rb = (c.n_loose + 2 * WAVES - 1) / (2 * WAVES);
+            const int64_t items = ((n_vecs + 127) / 128) * n_rb;
+            KN_LAUNCH("csr_rows_pair_kernel", csr_rows_pair_kernel, dim3((unsigned)(((items + 7) / 8) * 8)), dim3(256), 0, s, A.loose_rows, c.n_loose, A.indptr, A.indices, A.data, x, ldx, y,
+                      ldy, n_vecs, relu, n_rb, absmax);
+            KN_HIP(hipGetLastError());
+            break;
+        }
+        case CsrChoice::PIPE:
+            rc = c.t.rbk == 16 ? launch_csr_pipe<16>(A, c.groups, A.loose_rows, c.n_loose, x, ldx, n_vecs, y, ldy, relu, s)
+                               : launch_csr_pipe<8>(A, c.groups, A.loose_rows, c.n_loose, x, ldx, n_vecs, y, ldy, relu, s);
+            break;
+        case CsrChoice::PLAIN: rc = launch_csr_as(c.t, A, c.groups, A.loose_rows, c.n_loose, x, ldx, n_vecs, y, ldy, relu, s, absmax, Planes()); break;
+    }
+    if (rc != KN_OK || A.n_patch == 0) return rc;
+    // patched rows: behind the group kernels, on their stream
+    const int64_t n_ct = (n_vecs + 255) / 256;
+    KN_LAUNCH("csr_patch_guard_kernel<" + std::to_string(A.n_patch) + " patched rows>", csr_patch_guard_kernel, dim3((unsigned)(A.n_patch * n_ct)), dim3(256), 0, s, A.n_patch,
+              A.patch_rows, A.patch_ptr, A.patch_cols, A.indptr, A.indices, A.data, x, ldx, y, ldy, n_vecs, relu);
+    KN_HIP(hipGetLastError());
+    return KN_OK;
+}
+
+static int launch_csr_as(VecRows t, const CsrDev& A, const WorkList& groups, const int32_t* loose_rows, int64_t n_loose, const float* x, int64_t ldx, int64_t n_vecs, float* y, int64_t ldy,
+                         int relu, hipStream_t s, float* absmax, const Planes pl) {
+#define KN_CASE(V, R) \
+    if (t.vec == V && t.rbk == R) return launch_csr<V, R>(A, groups, loose_rows, n_loose, x, ldx, n_vecs, y, ldy, relu, s, absmax, pl);
+    KN_CASE(4, 8)
+    KN_CASE(2, 8)
+    KN_CASE(4, 2)
+    KN_CASE(1, 8)
+    KN_CASE(2, 2)
+    KN_CASE(1, 2)
+    KN_CASE(1, 1)
+#undef KN_CASE
+    return fail(KN_ERR_INVALID, "csr: no kernel for this (vector width, bundle height)");
 }
 
 // kn_spmm_planes: Y_p = W . X_p for p = 0 .. n_planes - 1 with ONE launch per kernel (grid dimension y = plane) instead of n_planes launches.  What it is for: the split
@@ -1188,32 +1281,10 @@ static int csr_spmm_groups(const CsrDev& A, const float* x, int64_t ldx, int64_t
 // the chip).  Same kernels, same instruction sequence per output element: bit-identical to n_planes kn_spmm calls.  Operators that need more than the grouped / loose-row
 // kernels (big groups, long rows, matrix-pipe groups, patched rows) are refused with KN_ERR_UNSUPPORTED: the caller loops over kn_spmm then.
 int csr_spmm_planes(const CsrDev& A, const float* x, int64_t ldx, int64_t x_stride, int64_t n_planes, int64_t n_vecs, float* y, int64_t ldy, int64_t y_stride, uint32_t flags, hipStream_t s) {
-    KN_REQUIRE(A.n_big == 0 && A.n_long == 0 && A.n_patch == 0, KN_ERR_UNSUPPORTED, "kn_spmm_planes: operator has big / long / patched rows (loop over kn_spmm)");
+    KN_REQUIRE(A.big.n == 0 && A.n_long == 0 && A.n_patch == 0, KN_ERR_UNSUPPORTED, "kn_spmm_planes: operator has big / long / patched rows (loop over kn_spmm)");
     KN_REQUIRE(n_planes >= 1 && n_planes <= 65535, KN_ERR_UNSUPPORTED, "kn_spmm_planes: 1 .. 65535 planes");
-    const int relu = (flags & KN_FLAG_RELU) ? 1 : 0;
-    Planes pl;
-    pl.n = n_planes;
-    pl.x_stride = x_stride;
-    pl.y_stride = y_stride;
-    auto aligned = [&](int v) {
-        return (n_vecs % v == 0) && (ldx % v == 0) && (ldy % v == 0) && (x_stride % v == 0) && (y_stride % v == 0) && (((uintptr_t)x) % (4 * v) == 0) && (((uintptr_t)y) % (4 * v) == 0) &&
-               (v == 1 || 4 * n_vecs >= 3 * ((n_vecs + 64 * v - 1) / (64 * v)) * (64 * v));
-    };
-    const int64_t loose = (A.n_loose + WAVES - 1) / WAVES * WAVES;
-    auto waves = [&](int v, int rbk) { return (A.n_work * (RB / rbk) + loose) * ((n_vecs + 64 * v - 1) / (64 * v)) * n_planes; };
-    constexpr int64_t ENOUGH = 2048;
-#define KN_TRY(V, R) \
-    if (aligned(V) && waves(V, R) >= ENOUGH) return launch_csr<V, R>(A, x, ldx, n_vecs, y, ldy, relu, s, nullptr, pl);
-    KN_TRY(4, 8)
-    KN_TRY(2, 8)
-    KN_TRY(4, 2)
-    KN_TRY(1, 8)
-    KN_TRY(2, 2)
-    KN_TRY(1, 2)
-#undef KN_TRY
-    if (aligned(4) && n_vecs >= 256) return launch_csr<4, 8>(A, x, ldx, n_vecs, y, ldy, relu, s, nullptr, pl);
-    if (aligned(2) && n_vecs >= 128) return launch_csr<2, 8>(A, x, ldx, n_vecs, y, ldy, relu, s, nullptr, pl);
-    return launch_csr<1, 8>(A, x, ldx, n_vecs, y, ldy, relu, s, nullptr, pl);
+    const CsrCall call{A.work.n, A.n_loose, x, ldx, y, ldy, n_vecs, Planes{n_planes, x_stride, y_stride}};
+    return launch_csr_as(csr_vec_rows(call, false), A, A.work, A.loose_rows, A.n_loose, x, ldx, n_vecs, y, ldy, (flags & KN_FLAG_RELU) ? 1 : 0, s, nullptr, call.pl);
 }
 
 }  // namespace kn

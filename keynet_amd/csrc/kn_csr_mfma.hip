@@ -287,7 +287,7 @@ __global__ __launch_bounds__(64 * NW, NW == 4 ? 2 : 1) void csr_group_mfma_kerne
 // The 16-row form for BIG pattern groups (a keyed nn.Linear in the reference's order: 4 096 rows x 25 089 stored columns): the walk over a row's stored columns
 // is serial by contract, so parallelism can only come from rows x batch columns.  v_mfma_f32_16x16x1_4b_f32 with a zero accumulator = the rounded products of
 // 16 member rows x 4 blocks of 16 batch columns (lane l supplies ITS OWN column as the B operand and value l % 16 as the A operand; bit-identical to v_mul_f32:
-// tools/micro/mfma16_product.hip), 8 packed adds per stored column.  Taken when it puts two wavefronts on every SIMD (csr_spmm_groups: 21-27 % faster than the
+// tools/micro/mfma16_product.hip), 8 packed adds per stored column.  Taken when it puts two wavefronts on every SIMD (csr_choice: 21-27 % faster than the
 // LDS-staged big-group kernel there; slower with one).
 // One wavefront = 16 rows x 64 columns; a workgroup = four 64-column blocks of the same 16 rows.  Same operand ring as above (2 loads per stored column).
 template <int PF>
@@ -465,38 +465,34 @@ int convtaps_exact_table_spmm(const ConvTapsDev& A, const float* x, int64_t ldx,
     return exact_table_launch(t, A.Hout * A.Wout, A.Hin * A.Win > A.Hout * A.Wout, A.tune.table_nrb, x, ldx, n_vecs, y, ldy, relu, s);
 }
 
-// work lists per NRB (CsrDev::mf_*): chunks of 32 * NRB member rows of the pattern groups with >= MF_MIN_MEMBERS members
-int csr_group_mfma_spmm(const CsrDev& A, const float* x, int64_t ldx, int64_t n_vecs, float* y, int64_t ldy, int relu, hipStream_t s) {
+// work lists per NRB (CsrDev::mf): chunks of 32 * NRB member rows of the pattern groups with >= MF_MIN_MEMBERS members
+int csr_group_mfma_spmm(const CsrDev& A, const WorkList* mf, const float* x, int64_t ldx, int64_t n_vecs, float* y, int64_t ldy, int relu, hipStream_t s) {
     const int64_t n_ct = (n_vecs + 255) / 256;
     for (int k = 0; k < 3; k++) {
-        if (A.n_mf[k] == 0) continue;
-        const int64_t items = n_ct * A.n_mf[k];
+        const WorkList& w = mf[k];
+        if (w.n == 0) continue;
+        const int64_t items = n_ct * w.n;
         const int64_t grid = ((items + 7) / 8) * 8;
         const std::string d = "csr_group_mfma_kernel<row blocks=" + std::to_string(k + 1) + "> (products on the matrix pipe, K = 1, zero accumulator)";
-        if (k == 0) KN_LAUNCH(d, (csr_group_mfma_kernel<1, 6>), dim3((unsigned)grid), dim3(256), 0, s, A.n_mf[k], A.mf_grp[k], A.mf_r0[k], A.grp_colptr, A.grp_cols, A.grp_rowptr, A.grp_rows,
-                              A.grp_valptr, A.grp_vals, x, ldx, y, ldy, n_vecs, relu);
-        if (k == 1) KN_LAUNCH(d, (csr_group_mfma_kernel<2, 6>), dim3((unsigned)grid), dim3(256), 0, s, A.n_mf[k], A.mf_grp[k], A.mf_r0[k], A.grp_colptr, A.grp_cols, A.grp_rowptr, A.grp_rows,
-                              A.grp_valptr, A.grp_vals, x, ldx, y, ldy, n_vecs, relu);
+        if (k == 0) KN_LAUNCH(d, (csr_group_mfma_kernel<1, 6>), dim3((unsigned)grid), dim3(256), 0, s, w.n, w.grp, w.r0, KN_GROUP_TABLES(A), x, ldx, y, ldy, n_vecs, relu);
+        if (k == 1) KN_LAUNCH(d, (csr_group_mfma_kernel<2, 6>), dim3((unsigned)grid), dim3(256), 0, s, w.n, w.grp, w.r0, KN_GROUP_TABLES(A), x, ldx, y, ldy, n_vecs, relu);
         if (k == 2) {
             const int pf = A.tune.mf_pf;      // operand columns in flight (diagnostic build: A/B knob) (AllConvNet forward, same box: 33.79 / 33.38 / 33.53 ms at 6 / 8 / 10)
-            if (pf == 10) KN_LAUNCH(d + " pf=10", (csr_group_mfma_kernel<3, 10>), dim3((unsigned)grid), dim3(256), 0, s, A.n_mf[k], A.mf_grp[k], A.mf_r0[k], A.grp_colptr, A.grp_cols, A.grp_rowptr,
-                                    A.grp_rows, A.grp_valptr, A.grp_vals, x, ldx, y, ldy, n_vecs, relu);
-            else if (pf == 8) KN_LAUNCH(d + " pf=8", (csr_group_mfma_kernel<3, 8>), dim3((unsigned)grid), dim3(256), 0, s, A.n_mf[k], A.mf_grp[k], A.mf_r0[k], A.grp_colptr, A.grp_cols, A.grp_rowptr,
-                                        A.grp_rows, A.grp_valptr, A.grp_vals, x, ldx, y, ldy, n_vecs, relu);
-            else KN_LAUNCH(d, (csr_group_mfma_kernel<3, 6>), dim3((unsigned)grid), dim3(256), 0, s, A.n_mf[k], A.mf_grp[k], A.mf_r0[k], A.grp_colptr, A.grp_cols, A.grp_rowptr, A.grp_rows,
-                                        A.grp_valptr, A.grp_vals, x, ldx, y, ldy, n_vecs, relu);
+            if (pf == 10) KN_LAUNCH(d + " pf=10", (csr_group_mfma_kernel<3, 10>), dim3((unsigned)grid), dim3(256), 0, s, w.n, w.grp, w.r0, KN_GROUP_TABLES(A), x, ldx, y, ldy, n_vecs, relu);
+            else if (pf == 8) KN_LAUNCH(d + " pf=8", (csr_group_mfma_kernel<3, 8>), dim3((unsigned)grid), dim3(256), 0, s, w.n, w.grp, w.r0, KN_GROUP_TABLES(A), x, ldx, y, ldy, n_vecs, relu);
+            else KN_LAUNCH(d, (csr_group_mfma_kernel<3, 6>), dim3((unsigned)grid), dim3(256), 0, s, w.n, w.grp, w.r0, KN_GROUP_TABLES(A), x, ldx, y, ldy, n_vecs, relu);
         }
     }
     KN_HIP(hipGetLastError());
     return KN_OK;
 }
 
-// big pattern groups (CsrDev::mf16_*: chunks of 16 member rows)
-int csr_group_mfma16_spmm(const CsrDev& A, const float* x, int64_t ldx, int64_t n_vecs, float* y, int64_t ldy, int relu, hipStream_t s) {
-    const int64_t items = ((n_vecs + 255) / 256) * A.n_mf16;
+// big pattern groups (CsrDev::mf16: chunks of 16 member rows)
+int csr_group_mfma16_spmm(const CsrDev& A, const WorkList& chunks, const float* x, int64_t ldx, int64_t n_vecs, float* y, int64_t ldy, int relu, hipStream_t s) {
+    const int64_t items = ((n_vecs + 255) / 256) * chunks.n;
     const int64_t grid = ((items + 7) / 8) * 8;
     KN_LAUNCH("csr_group_mfma16_kernel (big pattern groups: products of 16 rows x 64 columns on the matrix pipe, K = 1, zero accumulator)", (csr_group_mfma16_kernel<8>),
-              dim3((unsigned)grid), dim3(256), 0, s, A.n_mf16, A.mf16_grp, A.mf16_r0, A.grp_colptr, A.grp_cols, A.grp_rowptr, A.grp_rows, A.grp_valptr, A.grp_vals, x, ldx, y, ldy, n_vecs, relu);
+              dim3((unsigned)grid), dim3(256), 0, s, chunks.n, chunks.grp, chunks.r0, KN_GROUP_TABLES(A), x, ldx, y, ldy, n_vecs, relu);
     KN_HIP(hipGetLastError());
     return KN_OK;
 }

@@ -207,19 +207,19 @@ static NarrowRowsKernel narrow_rows_kernel(int nv, bool full) {
     }
 }
 
-// KN_FLAG_NARROW_ROWS on at most NARROW_MAX_VECS columns (narrow_rows_call): the pattern groups -- big ones included -- and, with `loose`, the loose rows in
-// ONE launch, 64 member rows per wavefront.  A keyed Linear puts at most one wavefront on a SIMD whatever the height (VGG-16 fc6: 65 wavefronts at 64 rows, 257 at
+// KN_FLAG_NARROW_ROWS on at most NARROW_MAX_VECS columns (narrow_rows_call): `groups` (CsrDev::nr: every pattern group, big ones included) and the `n_loose` rows of
+// `loose_rows` in ONE launch, 64 member rows per wavefront.  A keyed Linear puts at most one wavefront on a SIMD whatever the height (VGG-16 fc6: 65 wavefronts at 64 rows, 257 at
 // 16, on 1 024 SIMDs), and the bytes its value rings keep in flight are rows x 48 steps x 4 bytes at every height: the form with whole 256-byte value segments.
-int csr_narrow_rows_spmm(const CsrDev& A, const float* x, int64_t ldx, int64_t n_vecs, float* y, int64_t ldy, int relu, bool loose, hipStream_t s) {
+int csr_narrow_rows_spmm(const CsrDev& A, const WorkList& groups, const int32_t* loose_rows, int64_t n_loose, const float* x, int64_t ldx, int64_t n_vecs, float* y, int64_t ldy, int relu,
+                         hipStream_t s) {
     const NarrowWidth w = narrow_width(n_vecs);
-    const int64_t n_loose = loose ? A.n_loose : 0;
-    const int64_t grid_grp = (A.n_nr + 3) / 4, grid_loose = (n_loose + 255) / 256;
+    const int64_t grid_grp = (groups.n + 3) / 4, grid_loose = (n_loose + 255) / 256;
     if (grid_grp + grid_loose == 0) return KN_OK;
     KN_REQUIRE(grid_grp + grid_loose < ((int64_t)1 << 31), KN_ERR_UNSUPPORTED, "grid too large for the row-lane kernel");
     NarrowRowsArgs a;
-    a.n_items = A.n_nr;
-    a.nr_grp = A.nr_grp;
-    a.nr_r0 = A.nr_r0;
+    a.n_items = groups.n;
+    a.nr_grp = groups.grp;
+    a.nr_r0 = groups.r0;
     a.grp_colptr = A.grp_colptr;
     a.grp_cols = A.grp_cols;
     a.grp_rowptr = A.grp_rowptr;
@@ -227,7 +227,7 @@ int csr_narrow_rows_spmm(const CsrDev& A, const float* x, int64_t ldx, int64_t n
     a.grp_valptr = A.grp_valptr;
     a.grp_vals = A.grp_vals;
     a.n_loose = n_loose;
-    a.loose_rows = A.loose_rows;
+    a.loose_rows = loose_rows;
     a.indptr = A.indptr;
     a.indices = A.indices;
     a.data = A.data;
@@ -239,7 +239,7 @@ int csr_narrow_rows_spmm(const CsrDev& A, const float* x, int64_t ldx, int64_t n
     a.relu = relu;
     a.grid_grp = (uint32_t)grid_grp;
     KN_LAUNCH("csr_narrow_kernel<nv=" + std::to_string(w.nv) + (w.full ? "" : ",masked to " + std::to_string(n_vecs)) + ",rows=64> (lane = output row: " +
-                  std::to_string(A.n_nr) + " group chunks, " + std::to_string(n_loose) + " loose rows)",
+                  std::to_string(groups.n) + " group chunks, " + std::to_string(n_loose) + " loose rows)",
               narrow_rows_kernel(w.nv, w.full), dim3((unsigned)(grid_grp + grid_loose)), dim3(256), 0, s, a);
     KN_HIP(hipGetLastError());
     return KN_OK;

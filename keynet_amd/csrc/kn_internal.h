@@ -18,10 +18,33 @@
 // compiled with -fsanitize=address,undefined and run on a box WITHOUT a GPU.  "Device" memory is host heap here, so every create path
 // runs to completion under the sanitizers (the packing loops, the copies INTO the packed buffers and the frees included); every compute
 // entry point returns KN_ERR_NODEVICE before touching anything.
+#include <cstdio>
 #include <cstdlib>
 #include <cstring>
 namespace kn {
 namespace hostonly {
+// KN_UPLOAD_TRACE=<file>: every host-to-"device" copy appends one line -- element size, element count, 64-bit FNV-1a of the bytes -- and every kn_*_create
+// entry (they all open with a device query) one blank line, so two builds pack an operator alike when the blocks between blank lines are equal as multisets
+// (profiles/csr_host_before_after.txt).  An empty array (upload() zero-fills one element for it) is a line with count 0.
+template <typename T> inline size_t elem_size(T*) { return sizeof(T); }
+inline size_t elem_size(void*) { return 1; }
+inline size_t elem_size(const void*) { return 1; }
+inline void trace_write(bool blank, size_t elem, size_t count, const void* p) {
+    static bool after_blank = true;
+    const char* path = std::getenv("KN_UPLOAD_TRACE");
+    if (!path || !*path || (blank && after_blank)) return;
+    std::FILE* f = std::fopen(path, "a");
+    if (!f) return;
+    if (blank) {
+        std::fputc('\n', f);
+    } else {
+        uint64_t h = 14695981039346656037ull;
+        for (size_t i = 0; i < elem * count; i++) h = (h ^ ((const unsigned char*)p)[i]) * 1099511628211ull;
+        std::fprintf(f, "%zu %zu %016llx\n", elem, count, (unsigned long long)h);
+    }
+    std::fclose(f);
+    after_blank = blank;
+}
 inline hipError_t Malloc(void** p, size_t n) {
     *p = std::malloc(n ? n : 1);
     return *p ? hipSuccess : hipErrorOutOfMemory;
@@ -30,20 +53,24 @@ inline hipError_t Free(void* p) {
     std::free(p);
     return hipSuccess;
 }
-inline hipError_t Memcpy(void* d, const void* s, size_t n, hipMemcpyKind) {
+inline hipError_t Memcpy(void* d, const void* s, size_t n, hipMemcpyKind k, size_t elem) {
     std::memcpy(d, s, n);
+    if (k == hipMemcpyHostToDevice) trace_write(false, elem, n / elem, s);
     return hipSuccess;
 }
-inline hipError_t Memset(void* d, int v, size_t n) {
+inline hipError_t Memset(void* d, int v, size_t n, size_t elem) {
     std::memset(d, v, n);
+    trace_write(false, elem, 0, d);
     return hipSuccess;
 }
 inline hipError_t GetDeviceCount(int* n) {
     *n = 1;
+    trace_write(true, 0, 0, nullptr);
     return hipSuccess;
 }
 inline hipError_t GetDevice(int* d) {
     *d = 0;
+    trace_write(true, 0, 0, nullptr);
     return hipSuccess;
 }
 inline hipError_t DeviceGetAttribute(int* v, hipDeviceAttribute_t, int) {
@@ -55,8 +82,8 @@ inline hipError_t Ok() { return hipSuccess; }
 }  // namespace kn
 #define hipMalloc(p, n) kn::hostonly::Malloc((void**)(p), (n))
 #define hipFree(p) kn::hostonly::Free((void*)(p))
-#define hipMemcpy(d, s, n, k) kn::hostonly::Memcpy((void*)(d), (const void*)(s), (n), (k))
-#define hipMemset(d, v, n) kn::hostonly::Memset((void*)(d), (v), (n))
+#define hipMemcpy(d, s, n, k) kn::hostonly::Memcpy((void*)(d), (const void*)(s), (n), (k), kn::hostonly::elem_size(d))
+#define hipMemset(d, v, n) kn::hostonly::Memset((void*)(d), (v), (n), kn::hostonly::elem_size(d))
 #define hipGetDeviceCount(n) kn::hostonly::GetDeviceCount(n)
 #define hipGetDevice(d) kn::hostonly::GetDevice(d)
 #define hipDeviceGetAttribute(v, a, d) kn::hostonly::DeviceGetAttribute((v), (a), (d))
@@ -173,6 +200,14 @@ Tuning tuning_from_env();
 enum Kind { KIND_CSR = 0, KIND_CONVTAPS = 1, KIND_DENSE = 2, KIND_CHAIN = 3, KIND_CSR64 = 4 };
 struct ChainDev;   // kn_chain.hip
 
+// What a grouped kernel is launched over: n (pattern group, first member row) pairs, each a chunk of member rows whose height is the kernel's own.  The kernels
+// take the two arrays and the count as separate parameters.
+struct WorkList {
+    int32_t* grp = nullptr;
+    int32_t* r0 = nullptr;
+    int64_t n = 0;
+};
+
 // Order-preserving CSR resident in HBM.
 struct CsrDev {
     Tuning tune;                 // recorded at create
@@ -190,14 +225,11 @@ struct CsrDev {
     int32_t* grp_rows = nullptr;     // member rows
     int64_t* grp_valptr = nullptr;   // [n_groups+1] into grp_vals (layout [col j][member r], r padded to RB)
     float* grp_vals = nullptr;
-    int32_t* work_grp = nullptr;     // work items: (group, first member) pairs of RB rows
-    int32_t* work_r0 = nullptr;
-    int64_t n_work = 0;
+    // work lists of the grouped kernels: see WorkList (cut in one place, csr_cut_work_lists in kn_csr.hip)
+    WorkList work;                   // every group but the big ones, in bundles of RB rows
     // big groups (a keyed nn.Linear: thousands of member rows over thousands of shared columns) run in the LDS-staged kernel:
-    // work items = (group, first member) pairs of 32 rows; their members are NOT in work_grp/work_r0
-    int32_t* big_grp = nullptr;
-    int32_t* big_r0 = nullptr;
-    int64_t n_big = 0;
+    // chunks of 32 rows; their members are NOT in `work`
+    WorkList big;
     // loose rows with thousands of non-zeros (a row of a keyed nn.Linear whose pattern lost an entry to an exact zero): one wave per
     // (row, 64 batch columns) with a deep gather queue, as extra workgroups of the big-group launch
     int32_t* long_rows = nullptr;
@@ -208,25 +240,17 @@ struct CsrDev {
     int64_t grouped_nnz = 0;
     // the row-lane kernel for 1 .. 8 batch columns (kn_csr_narrow.hip, KN_FLAG_NARROW_ROWS): EVERY pattern group, the big ones included, in chunks of 64
     // member rows (a last chunk may be partly filled); grp_cols carries NARROW_ROWS_COL_PAD entries of padding for its look-ahead
-    int32_t* nr_grp = nullptr;
-    int32_t* nr_r0 = nullptr;
-    int64_t n_nr = 0;
+    WorkList nr;
+    // matrix-pipe products (kn_csr_mfma.hip): pattern groups with >= MF_MIN_MEMBERS members cut into chunks of 32 * (k + 1) member rows, k = 0..2
+    // (list k holds the chunks of k + 1 row blocks); ws = the 16-row bundles of the REMAINING (small) groups for the vector-ALU kernels
+    WorkList mf[3];
+    int64_t mf_rows = 0;             // member rows covered by the mf lists
+    int64_t mf_nnz = 0;              // their stored entries (mf_nnz / mf_rows = mean stored columns per row: the dispatch rule of csr_choice)
+    WorkList mf16;                   // big pattern groups (a keyed Linear) in chunks of 16 member rows: csr_group_mfma16_kernel on narrow batches
+    WorkList ws;
     // PATCHED group members: rows whose stored column sequence is a group's sequence minus a few entries (a keyed conv row that lost a weight to an
     // exact zero) ride in the group with 0.0f at the missing positions; csr_patch_guard_kernel recomputes them in the reference's own sequence for
     // the batch columns whose activation at a missing position is not finite (see kn_csr.hip)
-    // matrix-pipe products (kn_csr_mfma.hip): pattern groups with >= MF_MIN_MEMBERS members cut into chunks of 32 * (k + 1) member rows, k = 0..2
-    // (list k holds the chunks of k + 1 row blocks); ws_* = the 16-row bundles of the REMAINING (small) groups for the vector-ALU kernels
-    int32_t* mf_grp[3] = {nullptr, nullptr, nullptr};
-    int32_t* mf_r0[3] = {nullptr, nullptr, nullptr};
-    int64_t n_mf[3] = {0, 0, 0};
-    int64_t mf_rows = 0;             // member rows covered by the mf_* lists
-    int64_t mf_nnz = 0;              // their stored entries (mf_nnz / mf_rows = mean stored columns per row: the dispatch rule of csr_spmm_groups)
-    int32_t* mf16_grp = nullptr;     // big pattern groups (a keyed Linear) in chunks of 16 member rows: csr_group_mfma16_kernel on narrow batches
-    int32_t* mf16_r0 = nullptr;
-    int64_t n_mf16 = 0;
-    int32_t* ws_grp = nullptr;
-    int32_t* ws_r0 = nullptr;
-    int64_t n_ws = 0;
     int32_t* patch_rows = nullptr;   // [n_patch]
     int32_t* patch_ptr = nullptr;    // [n_patch+1] into patch_cols
     int32_t* patch_cols = nullptr;   // the missing column indices
@@ -325,8 +349,10 @@ int csr_spmm(const CsrDev& A, const float* x, int64_t ldx, int64_t n_vecs, float
              bool* absmax_fused = nullptr);
 template <typename TOUT>
 int csr_f64_spmm(const CsrDev& A, const float* x, int64_t ldx, int64_t n_vecs, TOUT* y, int64_t ldy, uint32_t flags, hipStream_t s);      // kn_csr_f64.hip
-int csr_group_mfma_spmm(const CsrDev& A, const float* x, int64_t ldx, int64_t n_vecs, float* y, int64_t ldy, int relu, hipStream_t s);
-int csr_group_mfma16_spmm(const CsrDev& A, const float* x, int64_t ldx, int64_t n_vecs, float* y, int64_t ldy, int relu, hipStream_t s);
+// the six group tables every grouped kernel takes, in the kernels' parameter order
+#define KN_GROUP_TABLES(A) (A).grp_colptr, (A).grp_cols, (A).grp_rowptr, (A).grp_rows, (A).grp_valptr, (A).grp_vals
+int csr_group_mfma_spmm(const CsrDev& A, const WorkList* mf, const float* x, int64_t ldx, int64_t n_vecs, float* y, int64_t ldy, int relu, hipStream_t s);       // mf[0 .. 2]
+int csr_group_mfma16_spmm(const CsrDev& A, const WorkList& chunks, const float* x, int64_t ldx, int64_t n_vecs, float* y, int64_t ldy, int relu, hipStream_t s);
 static constexpr int MF_MIN_MEMBERS = 24;   // a pattern group takes the matrix-pipe kernel when its members fill >= 3/4 of a 32-row block
 // `absmax` (device float or null): when the launch takes a kernel whose epilogue can fold max |Y| into its stores, the slot is raised atomically
 // and *absmax_fused is set; otherwise the caller runs absmax_pass over Y afterwards (kn_spmm_screen)
@@ -368,7 +394,7 @@ static constexpr int NARROW_ROWS_COL_PAD = 80;
 // Inside a VGG-16 forward (kernel trace, values cold): fc6 1.91x at 1 image and 1.42x at 2; fc7 1.86x / 1.39x, fc8 1.78x / 1.33x; at 4 images fc7 0.94x and fc8 0.91x
 // (alone on a warm block 1.19x / 1.12x: not what a forward sees); alone: fc6 0.88x at 4 and 0.47x at 8, fc7 / fc8 0.95x / 0.93x at 3 (masked form) and 0.67x / 0.65x at 8.
 // Operators without big groups (pools: 1.46x .. 5.1x at every width 1 .. 8; conv-like groups: not measured) keep the kernel.
-static inline bool narrow_rows_loses(const CsrDev& A, int64_t n_vecs) { return A.n_big > 0 && n_vecs > 2; }
+static inline bool narrow_rows_loses(const CsrDev& A, int64_t n_vecs) { return A.big.n > 0 && n_vecs > 2; }
 static inline bool narrow_rows_call(const CsrDev& A, uint32_t flags, int64_t n_vecs, int64_t ldx) {
     return (flags & KN_FLAG_NARROW_ROWS) && n_vecs <= NARROW_MAX_VECS && A.cols * ldx + NARROW_MAX_VECS < ((int64_t)1 << 30) && !narrow_rows_loses(A, n_vecs);
 }
@@ -377,7 +403,8 @@ static inline bool narrow_rows_call(const CsrDev& A, uint32_t flags, int64_t n_v
 // whose longest loose row holds more entries than this keeps csr_rows_kernel for its loose rows (its pattern groups still take the row-lane kernel).
 static constexpr int64_t NARROW_ROWS_LOOSE_MAX = 64;
 static inline bool narrow_rows_loose(const CsrDev& A) { return A.loose_max <= NARROW_ROWS_LOOSE_MAX; }
-int csr_narrow_rows_spmm(const CsrDev& A, const float* x, int64_t ldx, int64_t n_vecs, float* y, int64_t ldy, int relu, bool loose, hipStream_t s);      // kn_csr_narrow.hip
+int csr_narrow_rows_spmm(const CsrDev& A, const WorkList& groups, const int32_t* loose_rows, int64_t n_loose, const float* x, int64_t ldx, int64_t n_vecs, float* y, int64_t ldy, int relu,
+                         hipStream_t s);      // kn_csr_narrow.hip
 int convtaps_spmm(const ConvTapsDev& A, const float* x, int64_t ldx, int64_t n_vecs, float* y, int64_t ldy,
                   uint32_t flags, hipStream_t s, float* absmax = nullptr, bool* absmax_fused = nullptr);
 int absmax_pass(const float* y, int64_t rows, int64_t ld, int64_t n_vecs, float* absmax, hipStream_t s);
@@ -417,6 +444,10 @@ int linear_to_affine(const float* y, int64_t ldy, int64_t n, int64_t d, float* o
 // a global breadth-first sweep.  Columns referenced by more than `max_degree` of the rows (a bias column) do not link rows.
 std::vector<int32_t> locality_order(const std::vector<int32_t>& row_ids, const int32_t* indptr, const int32_t* indices, int64_t n_cols, int patch,
                                     int max_degree);
+// Column patterns of a CSR (host): rows with an identical stored column sequence share one id, numbered in order of first appearance.  pat[r] = the id of row r,
+// pat_rep[id] = the first row that carries it.  Empty rows share one id when `empty_rows` (the whole-net packer), else they get none (pat[r] = -1: the CSR packer
+// leaves them loose).
+void row_patterns(int64_t rows, const int32_t* indptr, const int32_t* indices, bool empty_rows, std::vector<int32_t>& pat, std::vector<int32_t>& pat_rep);
 int chain_create(int64_t n_ops, kn_operator* const* ops, const uint32_t* flags, ChainDev** out, int64_t* rows_out, int64_t* cols_out, int64_t* nnz_out);
 int chain_forward(const ChainDev* c, const float* x, int64_t ldx, int64_t n_vecs, float* y, int64_t ldy, hipStream_t s);
 void chain_free(ChainDev* c);

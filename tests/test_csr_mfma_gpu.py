@@ -146,6 +146,42 @@ def test_matrix_pipe_with_patched_members(monkeypatch):
         assert np.array_equal(got, ref, equal_nan=True), poison
 
 
+def mixed_operator(rng, n):
+    """180 groups of 96 members (540 chunks of one 32-row block: enough for the matrix-pipe dispatch at 256 columns), 60 groups of 2 .. 23 members (too few
+    for a 32-row block) and 20 loose rows, the row order shuffled."""
+    rows = []
+    for g in range(180):
+        rows += [rng.randint(0, n, 5 + (g * 7) % 30).astype(np.int32)] * 96
+    for g in range(60):
+        rows += [rng.randint(0, n, 1 + g % 30).astype(np.int32)] * (2 + (g * 5) % 22)
+    rows += [rng.randint(0, n, rng.randint(0, 12)).astype(np.int32) for _ in range(20)]
+    rows = [rows[i] for i in rng.permutation(len(rows))]
+    indptr = np.concatenate(([0], np.cumsum([len(r) for r in rows]))).astype(np.int32)
+    indices = np.concatenate(rows).astype(np.int32)
+    return (len(rows), indptr, indices, rng.randn(len(indices)).astype(np.float32))
+
+
+def test_small_groups_behind_the_matrix_pipe_launch(monkeypatch):
+    """Small pattern groups and loose rows beside the matrix-pipe groups: the matrix-pipe lists run first, then the vector-ALU kernels take the small groups'
+    bundle list (CsrDev::ws) and the loose rows.  One call, three kernels, every row written once: bit-equal to the oracle, ReLU on and off."""
+    monkeypatch.setenv('KN_GROUP_MFMA', '1')
+    rng = np.random.RandomState(17)
+    (n, n_vecs) = (700, 256)
+    (m, indptr, indices, data) = mixed_operator(rng, n)
+    op = _capi.Operator.csr((m, n), indptr, indices, data)
+    with torch.cuda.device(dev()):
+        plan = op.plan(n_vecs, _capi.KN_FLAG_EXACT)
+    assert 'csr_group_mfma_kernel' in plan and 'csr_group_kernel<' in plan and 'csr_rows_kernel<' in plan, plan
+    X = rng.randn(n, n_vecs).astype(np.float32)
+    ref = oracle.csr_matvecs((m, n), indptr, indices, data, X)
+    xd = torch.as_tensor(X).to(dev())
+    for relu in (False, True):
+        y = torch.empty((m, n_vecs), device=dev())
+        with torch.cuda.device(dev()):
+            op.spmm(xd.data_ptr(), n_vecs, n_vecs, y.data_ptr(), n_vecs, _capi.KN_FLAG_EXACT | (_capi.KN_FLAG_RELU if relu else 0), torch.cuda.current_stream().cuda_stream)
+        assert np.array_equal(y.cpu().numpy(), np.maximum(ref, 0) if relu else ref), relu
+
+
 def test_default_dispatch_rule():
     """By default the matrix-pipe kernel serves pattern groups with long stored sequences (mean >= 256 columns per member row: the 3x3 conv
     layers of AllConvNet with 96 / 192 input channels); short sequences stay on the vector-ALU pipeline (same bits either way)."""

@@ -1,8 +1,9 @@
-"""Dispatch grid of the conv-taps host side: which kernel kn_spmm would launch for which call, as text.
+"""Dispatch grid of the host side: which kernel kn_spmm would launch for which call, as text.
 
 Loads the library named by KEYNET_HIP_LIB (default: the product library) through keynet_amd/_capi.py WITHOUT torch, creates a fixed list of operators and
 prints, per operator, kn_nnz / kn_nnz_expanded / a hash of kn_export_csr and one line per (n_vecs, ldx = ldy, flags) with the text of kn_spmm_plan; the
-batches include 1, 2, 3, 4, 8 and 9 columns and the flags the three narrow ones (KN_FLAG_NARROW, _MFMA, _ROWS), and three float32 CSR operators close the list.  Nothing is
+batches include 1, 2, 3, 4, 8 and 9 columns and the flags the three narrow ones (KN_FLAG_NARROW, _MFMA, _ROWS).  Float32 CSR operators close the list: three at every flag word, then (csr_cases) the shapes that reach
+every launch site of the three CSR sources, a kn_tiled_create operator and a kn_chain_create handle, at the flags a CSR handle reads (--csr: these alone).  Nothing is
 launched, so the KN_HOST_PACK_ONLY build answers on a machine without a GPU.  Two builds of the library dispatch alike when their outputs are byte-identical:
 
     KEYNET_HIP_LIB=/path/to/libkeynet_hip.so python tools/plan_grid.py > grid.txt
@@ -31,7 +32,7 @@ SWITCHES = (('KN_NO_SPTR', '1'), ('KN_NO_SMALLK_PIPE', '1'), ('KN_NO_EXACT_TABLE
 EXPORT_MAX_NNZ = 1 << 22
 
 
-def report(name, op, out, export=True):
+def report(name, op, out, export=True, flags=None):
     L = capi.lib()
     nx = op.nnz_expanded()
     digest = '-'
@@ -47,7 +48,7 @@ def report(name, op, out, export=True):
     buf = ctypes.create_string_buffer(4096)
     for n in BATCHES:
         for ld in (n, n + 1):
-            for fl in FLAGS:
+            for fl in (flags or FLAGS):
                 rc = L.kn_spmm_plan(op.handle, n, ld, ld, fl, buf, 4096)
                 text = buf.value.decode() if rc == 0 else 'rc=%d %s' % (rc, L.kn_last_error().decode())
                 out.write('%s n=%d ld=%d flags=%d: %s\n' % (name, n, ld, fl, text))
@@ -103,8 +104,104 @@ def factored(cin, cout, hw, ntaps=9, per_pixel=9, coef=False, last=True, dup=Fal
     return op.drop_zero_entries() if drop else op
 
 
+# ---- float32 CSR operators: every launch site of kn_csr.hip, kn_csr_mfma.hip and kn_csr_narrow.hip (the thresholds: csr_build_groups, csr_choice) ----
+# the flags a CSR handle reads: ReLU and KN_FLAG_NARROW_ROWS
+CSR_FLAGS = (0, capi.KN_FLAG_RELU, capi.KN_FLAG_NARROW_ROWS | capi.KN_FLAG_EXACT, capi.KN_FLAG_NARROW_ROWS | capi.KN_FLAG_EXACT | capi.KN_FLAG_RELU)
+
+
+def csr_from_rows(row_cols, n_cols, seed, shuffle=True):
+    """A CSR operator from per-row column sequences (stored order = the order given), N(0, 1) values, the rows in a fixed random order."""
+    rng = np.random.RandomState(seed)
+    if shuffle:
+        row_cols = [row_cols[i] for i in rng.permutation(len(row_cols))]
+    indptr = np.concatenate(([0], np.cumsum([len(c) for c in row_cols]))).astype(np.int32)
+    indices = (np.concatenate(row_cols) if indptr[-1] else np.zeros(0)).astype(np.int32)
+    return ((len(row_cols), n_cols), indptr, indices, rng.randn(len(indices)).astype(np.float32))
+
+
+def groups(rng, n_cols, sizes, seq_len):
+    """One pattern group per entry of `sizes`: that many rows over one random sequence of `seq_len` distinct columns."""
+    rows = []
+    for n in sizes:
+        seq = rng.choice(n_cols, seq_len, replace=False)
+        rows += [seq] * n
+    return rows
+
+
+def ragged(rng, n_cols, n_rows, lo, hi):
+    """Rows no other row shares a sequence with (almost surely): lo .. hi distinct random columns each."""
+    return [rng.choice(n_cols, rng.randint(lo, hi + 1), replace=False) for _ in range(n_rows)]
+
+
+def csr_cases():
+    """(name, (shape, indptr, indices, data), environment switches that change its plan)."""
+    empty = [np.zeros(0, np.int64)] * 3
+    rng = np.random.RandomState(11)
+    # 42 chunks of 32 member rows over 256-column sequences: the matrix-pipe lists at 4 096 columns (n_mf * 16 * 4 >= 2 048); groups of 64 / 96 members fill the
+    # 2- and 3-block chunks under KN_MF_NRB; five small groups (the ws list behind the matrix-pipe launch), loose and empty rows
+    mf = groups(rng, 4096, [32] * 30 + [64, 64, 96, 96, 40], 256) + groups(rng, 4096, [2, 5, 9, 16, 23], 64) + ragged(rng, 4096, 10, 5, 30) + empty
+    yield ('csr matrix-pipe groups', csr_from_rows(mf, 4096, 12), (('KN_MF_NRB', '2'), ('KN_MF_NRB', '3'), ('KN_GROUP_MFMA', '0'), ('KN_NO_GROUP_PIPE', '1')))
+    # conv-like groups with short sequences: the rule keeps them on the vector ALU (pipelined kernel, 16 rows per wavefront), KN_GROUP_MFMA=1 moves them
+    rng = np.random.RandomState(13)
+    yield ('csr conv-like groups', csr_from_rows(groups(rng, 1024, [32] * 64, 28), 1024, 14), (('KN_GROUP_MFMA', '1'), ('KN_NO_GROUP_PIPE', '1')))
+    # groups that leave 16-row bundles half empty (8 rows per wavefront of the pipelined kernel) and loose rows behind them
+    rng = np.random.RandomState(15)
+    yield ('csr thin groups', csr_from_rows(groups(rng, 1024, [9] * 300, 28) + ragged(rng, 1024, 50, 3, 12), 1024, 16), (('KN_NO_GROUP_PIPE', '1'),))
+    # a keyed Linear: one big group; 32 chunks of 16 rows reach the matrix pipe by rule at 4 096 columns (n_mf16 * 64 >= 2 048)
+    rng = np.random.RandomState(17)
+    yield ('csr linear 512x2100', csr_from_rows(groups(rng, 2100, [512], 2100), 2100, 18, shuffle=False),
+           (('KN_BIG_MFMA16', '0'), ('KN_BIG_MFMA16', '1'), ('KN_NO_BIG_GROUPS', '1')))
+    # patched rows: groups of 12 members over 40 columns, and single rows that are a group's sequence minus 1 .. 4 entries
+    rng = np.random.RandomState(19)
+    rows = []
+    for g in range(4):
+        seq = rng.choice(512, 40, replace=False)
+        rows += [seq] * 12 + [np.delete(seq, rng.choice(40, miss, replace=False)) for miss in (1, 2, 3, 4)]
+    yield ('csr patched rows', csr_from_rows(rows + ragged(rng, 512, 6, 2, 9), 512, 20), ())
+    # long ungrouped rows (>= 1 024 entries): three of them take the deep-queue role, 64 the row kernel at 4 096 columns (64 * 16 tiles >= 1 024)
+    rng = np.random.RandomState(21)
+    yield ('csr long rows few', csr_from_rows(ragged(rng, 2048, 3, 1024, 1500) + ragged(rng, 2048, 20, 4, 40), 2048, 22), (('KN_NO_BIG_GROUPS', '1'),))
+    yield ('csr long rows many', csr_from_rows(ragged(rng, 2048, 64, 1024, 1100) + groups(rng, 2048, [20], 48), 2048, 23), ())
+    # 4 096 short loose rows (overlapping 3-column windows): the locality order, csr_rows_pair_kernel at 128 and 384 columns
+    yield ('csr pool 4096x4100', csr_from_rows([np.arange(r, r + 3) for r in range(4096)], 4100, 24), ())
+    # a bit of everything, and loose rows too long for a lane of the row-lane kernel (> 64 entries)
+    rng = np.random.RandomState(25)
+    seq = rng.choice(3000, 48, replace=False)
+    rows = [seq] * 30 + [np.delete(seq, [7])] + groups(rng, 3000, [3, 17], 20) + ragged(rng, 3000, 2, 1024, 1030) + ragged(rng, 3000, 12, 70, 100) + empty
+    yield ('csr mixed', csr_from_rows(rows, 3000, 26), (('KN_NO_BIG_GROUPS', '1'),))
+
+
+def csr_operators(out):
+    for (name, (shape, ip, ix, dt), switches) in csr_cases():
+        for (k, v) in ((None, None),) + tuple(switches):
+            if k:
+                os.environ[k] = v
+            try:
+                op = capi.Operator.csr(shape, ip, ix, dt)
+            finally:
+                if k:
+                    del os.environ[k]
+            report(name + ('[%s=%s]' % (k, v) if k else ''), op, out, export=False, flags=CSR_FLAGS)
+    # kn_tiled_create: a block-diagonal tiled operator (expanded to CSR on the host, packed like one)
+    rng = np.random.RandomState(27)
+    tile = rng.randn(8, 8).astype(np.float32)
+    (tr, tc) = np.nonzero(np.ones((8, 8)))
+    blocks = np.array([[8 * i, 8 * i, 0] for i in range(40)], np.int64)
+    report('tiled 320x320', capi.Operator.tiled((320, 320), blocks, np.array([0, 64], np.int64), tr.astype(np.int32), tc.astype(np.int32), tile.ravel()), out, flags=CSR_FLAGS)
+    # kn_chain_create over the CSR layers of the LeNet golden key-net: its plan names the LDS and operator bytes of the packed layout
+    z = np.load(os.path.join(GOLD, 'lenet_perm.npz'), allow_pickle=False)
+    ops = []
+    for lname in [str(n) for n in z['layer_names']]:
+        p = 'L.%s.' % lname
+        if str(z[p + 'kind']) == 'csr':
+            ops.append(capi.Operator.csr(tuple(int(v) for v in z[p + 'shape']), z[p + 'indptr'], z[p + 'indices'], z[p + 'data'].astype(np.float32)))
+    report('chain lenet_perm', capi.Operator.chain(ops, [capi.KN_FLAG_RELU] * (len(ops) - 1) + [0]), out, export=False, flags=CSR_FLAGS)
+
+
 def main():
     out = sys.stdout
+    if '--csr' in sys.argv[1:]:
+        return csr_operators(out)
     golden_conv2dtiled(out)
     for cin in (3, 5, 16, 32, 64):
         for cout in (7, 64, 128, 192):
@@ -137,6 +234,7 @@ def main():
                       ('csr linear 300x2100', scipy.sparse.csr_matrix(rng.randn(300, 2100)))):
         M = M.astype(np.float32)
         report(name, capi.Operator.csr(M.shape, M.indptr.astype(np.int32), M.indices.astype(np.int32), M.data), out, export=False)
+    csr_operators(out)
 
 
 if __name__ == '__main__':
