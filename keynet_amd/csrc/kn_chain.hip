@@ -50,8 +50,8 @@ static constexpr int CHAIN_OVERREAD_QUADS = 16;                // >= ring depth 
 struct ChainLayerArg {
     const float* vals;          // quads: [slice][q][lane][row of the lane (rpl)][4]
     const int32_t* cols;        // pool of column quads; an entry is the LDS BYTE offset of the feature in this layer's input buffer
-    const int32_t* lane_meta;   // [n_slices * 64][4]: output row (-1 = empty slot), index of the lane's first column QUAD in `cols`, second output row (rpl = 2) or -1, 0
-    const int32_t* slice_info;  // [n_slices][4]: quads, column quad stride, first value quad / (64 * rpl), 0
+    const int32_t* lane_meta;   // [n_slices * 64][4]: one ChainLaneRec per lane (the host half of this file names the fields)
+    const int32_t* slice_info;  // [n_slices][4]: one ChainSliceRec per slice
     int32_t n_slices, n_rows, relu;
     int32_t cols_quads;         // size of the layer's column pool in quads when the pool is staged in LDS before the walk:
                                 //   > 0 a THIN layer (chain_rows_thin, two copies), < 0 a layer of shared patterns on all wavefronts
@@ -60,7 +60,7 @@ struct ChainLayerArg {
     int32_t stage_off;          // float4 index of the LDS area the pool is staged in
     int32_t early;              // 1 = the pool is staged while the PREVIOUS layer runs (layer 0: with the input), 0 = at the start of this layer
     int32_t vstride;            // general / pattern walks: distance between a lane's consecutive value quads, in units of 16 * rpl bytes (64 = every lane its own copy; the number of
-                                // lanes per pixel when lanes that carry the SAME value sequence share one copy: see chain_build_layer)
+                                // lanes per pixel when lanes that carry the SAME value sequence share one copy: see chain_layout_values_shared)
     int32_t seq_len;            // > 0: a SEQUENTIAL thin layer (chain_rows_thin_seq) -- the stored entries of the one column pattern all of these rows share; the
     int32_t seq_base;           //      layer's input buffer (LDS byte offset seq_base) is laid out in that pattern's order by the layer before it
 };
@@ -817,12 +817,43 @@ __global__ __launch_bounds__(CHAIN_THREADS) void chain_kernel(ChainArgs a) {
 }
 
 // ---- host -----------------------------------------------------------------------------------------------------------------------
+constexpr int RPS = 64;          // lanes of a slice (= one wavefront); a lane owns one output row, or two (ChainLayerArg::rpl)
+
+// The records the walks read (ChainLayerArg::lane_meta / slice_info), as the packer fills them; uploaded as the same bytes, the kernel reads them as int32_t[4].
+struct ChainLaneRec {
+    int32_t row;                 // LDS position of the lane's output row (= the row itself unless the next layer is sequential), -1 = empty slot
+    int32_t col_quad;            // index of the lane's first column QUAD in `cols`
+    int32_t row2;                // second output row (rpl = 2), or -1
+    int32_t val_base;            // the lane's first value quad, in units of 16 * rpl bytes (consecutive quads: ChainLayerArg::vstride apart)
+};
+struct ChainSliceRec {
+    int32_t quads;               // quads every lane of the slice walks: its longest row
+    int32_t col_stride;          // distance between a lane's consecutive column quads: 1 = shared patterns, 64 = stored per lane like the values
+    int32_t val_quad;            // first value quad / (64 * rpl) of a layer of private value copies: the quads of the slices before it
+    int32_t zero;
+};
+static_assert(sizeof(ChainLaneRec) == 16 && sizeof(ChainSliceRec) == 16, "the kernel reads both records as int32_t[4]");
+
+// The sign convention of ChainLayerArg::cols_quads is written and read HERE only.
+enum ChainWalkKind { CHAIN_WALK_MEMORY, CHAIN_WALK_THIN, CHAIN_WALK_POOL, CHAIN_WALK_SEQ };      // chain_rows / chain_rows_thin / chain_rows_cl / chain_rows_thin_seq
+static int32_t chain_cols_quads(const ChainWalkKind walk, const size_t pool_quads) {
+    return walk == CHAIN_WALK_THIN ? (int32_t)pool_quads : walk == CHAIN_WALK_POOL ? -(int32_t)pool_quads : 0;
+}
+static ChainWalkKind chain_walk_of(const ChainLayerArg& L) {
+    return L.seq_len > 0 ? CHAIN_WALK_SEQ : L.cols_quads > 0 ? CHAIN_WALK_THIN : L.cols_quads < 0 ? CHAIN_WALK_POOL : CHAIN_WALK_MEMORY;
+}
+static size_t chain_lds_quads(const ChainWalkKind walk, const size_t pool_quads) {      // what the staged pool takes: a thin layer stages two copies
+    return walk == CHAIN_WALK_THIN ? 2 * pool_quads : walk == CHAIN_WALK_POOL ? pool_quads : 0;
+}
+static size_t chain_lds_quads(const ChainLayerArg& L) { return chain_lds_quads(chain_walk_of(L), (size_t)std::abs((int64_t)L.cols_quads)); }
+
 struct ChainDev {
     std::vector<void*> allocs;
     ChainArgs args;
     size_t lds_bytes = 0;
     size_t stream_bytes = 0;     // operator words ONE workgroup requests from L2 per forward (values, columns read from memory or staged, lane and slice records): the kernel's real
                                  // traffic is n_workgroups x this -- for LeNet 256 x 2.3 MB against an L2 that delivers 28 TB/s (tools/micro/l2_read_rate.hip)
+    std::string desc;            // what kn_spmm_plan prints for the launch (chain_describe)
 };
 
 void chain_free(ChainDev* c) {
@@ -833,14 +864,23 @@ void chain_free(ChainDev* c) {
 }
 
 template <typename T>
-static int chain_upload(ChainDev* c, const T** dst, const std::vector<T>& h) {
+static int chain_upload(ChainDev* c, const T** dst, const T* h, const size_t n) {
     T* d = nullptr;
-    int rc = upload(&d, h.data(), h.size());
+    int rc = upload(&d, h, n);
     if (rc) return rc;
     c->allocs.push_back(d);
     *dst = d;
     return KN_OK;
 }
+
+// an operator on the host: the CSR the reference holds (stored order) and its column patterns (row_patterns; empty rows share one)
+struct ChainHostCsr {
+    int64_t rows = 0, cols = 0;
+    std::vector<int32_t> ip, ix;
+    std::vector<float> dt;
+    std::vector<int32_t> pat, pat_rep;
+    int32_t len(const int32_t r) const { return ip[(size_t)r + 1] - ip[(size_t)r]; }
+};
 
 // Does a layer take the SEQUENTIAL thin walk (chain_rows_thin_seq)?  A keyed nn.Linear behind another layer: (nearly) all rows share ONE stored column sequence P of distinct
 // columns, few enough rows for two wavefronts per slice, a walk long enough to be bound by one wavefront's instruction issue.  pos = where the layer BEFORE it must put each of
@@ -850,361 +890,375 @@ struct ChainSeqPlan {
     int32_t len = 0;
     std::vector<int32_t> pos, main_rows, other_rows;
 };
-static ChainSeqPlan chain_plan_seq(int64_t l, int64_t rows, int64_t cols, const std::vector<int32_t>& ip, const std::vector<int32_t>& ix, const Tuning& tune) {
+static ChainSeqPlan chain_plan_seq(int64_t l, const ChainHostCsr& h, const Tuning& tune) {
     ChainSeqPlan P;
-    if (l == 0 || rows == 0 || tune.chain_no_seq) return P;              // (layer 0 reads the caller's input: staged as it is)
-    std::vector<int32_t> pat, pat_rep;
-    row_patterns(rows, ip.data(), ix.data(), true, pat, pat_rep);          // column patterns of the layer; empty rows share one
-    std::vector<int64_t> cnt(pat_rep.size(), 0);
-    for (int64_t r = 0; r < rows; r++) cnt[(size_t)pat[(size_t)r]]++;
+    if (l == 0 || h.rows == 0 || tune.chain_no_seq) return P;              // (layer 0 reads the caller's input: staged as it is)
+    std::vector<int64_t> cnt(h.pat_rep.size(), 0);
+    for (int64_t r = 0; r < h.rows; r++) cnt[(size_t)h.pat[(size_t)r]]++;
     const int32_t g = (int32_t)(std::max_element(cnt.begin(), cnt.end()) - cnt.begin());
-    const int32_t rs = ip[(size_t)pat_rep[(size_t)g]], len = ip[(size_t)pat_rep[(size_t)g] + 1] - rs;
-    const int64_t n_main = cnt[(size_t)g], n_other = rows - n_main;
+    const int32_t rs = h.ip[(size_t)h.pat_rep[(size_t)g]], len = h.len(h.pat_rep[(size_t)g]);
+    const int64_t n_main = cnt[(size_t)g], n_other = h.rows - n_main;
     const int64_t ns = (n_main + 63) / 64;
     if (len < 64 || n_other > 64 || CHAIN_SEQ_WPS * ns + (n_other > 0 ? 1 : 0) > CHAIN_THREADS / 64 || ns > 8) return P;
-    std::vector<int32_t> pos((size_t)cols, -1);
+    std::vector<int32_t> pos((size_t)h.cols, -1);
     for (int32_t k = 0; k < len; k++) {
-        const int32_t col = ix[(size_t)(rs + k)];
-        if (col < 0 || col >= cols || pos[(size_t)col] >= 0) return P;   // a column named twice (non-canonical rows may): no sequential layout
+        const int32_t col = h.ix[(size_t)(rs + k)];
+        if (col < 0 || col >= h.cols || pos[(size_t)col] >= 0) return P;   // a column named twice (non-canonical rows may): no sequential layout
         pos[(size_t)col] = k;
     }
     int32_t nxt = len;
-    for (int64_t col = 0; col < cols; col++)
+    for (int64_t col = 0; col < h.cols; col++)
         if (pos[(size_t)col] < 0) pos[(size_t)col] = nxt++;
     P.on = true;
     P.len = len;
     P.pos = std::move(pos);
-    for (int64_t r = 0; r < rows; r++) (pat[(size_t)r] == g ? P.main_rows : P.other_rows).push_back((int32_t)r);
+    for (int64_t r = 0; r < h.rows; r++) (h.pat[(size_t)r] == g ? P.main_rows : P.other_rows).push_back((int32_t)r);
     return P;
 }
 
-// one layer: CSR (host copy, stored order) -> the sliced layout above.  in_base / zero_byte: LDS byte offsets of the layer's input buffer
-// and of the always-zero feature.  in_pos / out_pos (or null): where the layer's input features / output rows sit inside their LDS buffers when the layer itself / the layer
-// behind it is walked sequentially (chain_plan_seq).
-static int chain_build_layer(ChainDev* c, ChainLayerArg& L, ChainLayerArg& LX, int64_t rows, int64_t cols, const std::vector<int32_t>& ip, const std::vector<int32_t>& ix,
-                             const std::vector<float>& dt, int relu, int32_t in_base, int32_t zero_byte, const Tuning& tune, const size_t room_quads,
-                             const ChainSeqPlan& plan, const std::vector<int32_t>* out_pos) {
-    constexpr int RPS = 64;                      // room_quads: LDS left beside the activations, in 16-byte quads (what a staged column pool may take)
-    (void)cols;
-    const std::vector<int32_t>* in_pos = plan.on ? &plan.pos : nullptr;
-    auto off = [&](int32_t col) { return in_base + 16 * (in_pos ? (*in_pos)[(size_t)col] : col); };
-    std::vector<int32_t> pat, pat_rep;
-    row_patterns(rows, ip.data(), ix.data(), true, pat, pat_rep);          // column patterns of the layer; empty rows share one
-    struct Built {
-        std::vector<float> vals;
-        std::vector<int32_t> colpool, lane_meta, info;
-        int64_t n_slices = 0;
-        size_t pool_quads = 0;
-        bool thin = false, all_shared = false;
-        int longest = 0;
-        int vstride = 64;                 // see ChainLayerArg::vstride
-        size_t val_line_bytes = 0;        // 64-byte lines the wavefronts' value requests of one forward touch (what they ask the L2 for)
-    };
-    // R output rows per lane (R = 2: two rows of ONE column pattern; a pattern with an odd number of rows leaves one lane half empty)
-    // `share` (general / pattern walks): lanes whose rows carry the SAME value sequence read ONE copy of it.  A keyed conv stores one weight sequence per (output channel, border
-    // class) -- LeNet conv2: 145 distinct sequences for 3 137 rows, its pooling layers 4 for 1 177 -- while the walk used to stream a private copy per lane: 1.0 of the 2.3 MB a
-    // workgroup asks the L2 for per forward, in a kernel whose 256 workgroups together run at 60-70 % of the L2's measured read rate (profiles/r06_lenet_chain_breakdown.txt).
-    // Layout: the lanes of one column pattern (the channels of a pixel, `U` lanes) keep their order; patterns whose lanes carry identical sequences share a block
-    // [quad][lane of the pattern][row of the lane][4] -- a quad's request of such a pattern is U * 16 * R contiguous bytes, the same for every pixel of the class.  A lane's base
-    // goes into its record (lane_meta.w), the quad stride U into the layer record.  Reads past a block's last quad (a shorter row in a slice of longer ones) hit the next block's
-    // finite values and multiply the always-zero feature: +-0.0 onto a sum that started at +0.0, as with the 0.0f padding before.
-    auto build = [&](const int R, const std::vector<int32_t>* subset = nullptr, const bool share = false) {
-        Built B;
-        std::vector<int32_t> rows_sorted((size_t)rows);
-        std::iota(rows_sorted.begin(), rows_sorted.end(), 0);
-        if (subset) rows_sorted = *subset;                       // (a sequential thin layer: its main-pattern rows and the others are laid out separately)
-        std::stable_sort(rows_sorted.begin(), rows_sorted.end(), [&](int32_t x, int32_t y) {
-            const int32_t lx = ip[(size_t)x + 1] - ip[(size_t)x], ly = ip[(size_t)y + 1] - ip[(size_t)y];
-            if (lx != ly) return lx > ly;
-            if (pat[(size_t)x] != pat[(size_t)y]) return pat[(size_t)x] < pat[(size_t)y];
-            // share: the rows of one pattern (the channels of a pixel) in a canonical order -- by their value sequences -- so that two pixels whose channels carry the same
-            // sequences form the same block whatever order the output key gave their rows (which lane of a pattern takes which of its rows changes no result)
-            return share && lx > 0 && std::memcmp(dt.data() + ip[(size_t)x], dt.data() + ip[(size_t)y], sizeof(float) * (size_t)lx) < 0;
-        });
-        // units = what a lane owns: R consecutive rows of the sorted order when they share a pattern (equal pattern => equal length), else one row
-        std::vector<std::array<int32_t, 2>> units;
-        for (size_t i = 0; i < rows_sorted.size();) {
-            std::array<int32_t, 2> u = {rows_sorted[i], -1};
-            if (R == 2 && i + 1 < rows_sorted.size() && pat[(size_t)rows_sorted[i + 1]] == pat[(size_t)rows_sorted[i]]) {
-                u[1] = rows_sorted[i + 1];
-                i += 2;
-            } else {
-                i += 1;
-            }
-            units.push_back(u);
-        }
-        const int64_t n_units = (int64_t)units.size();
-        const int64_t n_slices = (n_units + RPS - 1) / RPS;
-        B.n_slices = n_slices;
-        auto len_of = [&](int32_t r) { return ip[(size_t)r + 1] - ip[(size_t)r]; };
-        B.lane_meta.assign((size_t)(n_slices * RPS) * 4, 0);
-        B.info.assign((size_t)(n_slices * 4), 0);
-        for (size_t o = 0; o < (size_t)(n_slices * RPS); o++) B.lane_meta[4 * o] = B.lane_meta[4 * o + 2] = -1;
-        // pass 1: per slice its longest row and whether its lanes share column patterns; per shared pattern the quads it must be readable for
-        // (every lane of a slice walks up to the slice's LONGEST row)
-        std::vector<int> s_max((size_t)n_slices, 0);
-        std::vector<char> s_shared((size_t)n_slices, 0);
-        std::vector<int> pat_quads(pat_rep.size(), 0);
-        for (int64_t s = 0; s < n_slices; s++) {
-            int mx = 0, distinct = 0;
-            int32_t last_pat = -2;
-            const int real = (int)std::min<int64_t>(RPS, n_units - s * RPS);
-            for (int i = 0; i < real; i++) {
-                const std::array<int32_t, 2>& u = units[(size_t)(s * RPS + i)];
-                mx = std::max(mx, len_of(u[0]));
-                if (pat[(size_t)u[0]] != last_pat) distinct++;
-                last_pat = pat[(size_t)u[0]];
-                B.lane_meta[4 * (size_t)(s * RPS + i)] = u[0];
-                B.lane_meta[4 * (size_t)(s * RPS + i) + 2] = u[1];
-            }
-            s_max[(size_t)s] = mx;
-            s_shared[(size_t)s] = (distinct * 2 <= real || R == 2) ? 1 : 0;     // most lanes share a pattern with a neighbour: one copy per pattern
-        }
-        // a layer that is shared almost everywhere (a conv layer and its odd last slice: the homogeneous row) stores every slice that way -- one layout
-        // per layer lets its whole pool be staged in LDS (chain_rows_cl); the few unrelated rows then read scattered instead of lane-adjacent quads
-        {
-            int64_t units_shared = 0;
-            for (int64_t s = 0; s < n_slices; s++)
-                if (s_shared[(size_t)s]) units_shared += std::min<int64_t>(RPS, n_units - s * RPS);
-            if (units_shared * 10 >= n_units * 9)
-                for (int64_t s = 0; s < n_slices; s++) s_shared[(size_t)s] = 1;
-        }
-        for (int64_t s = 0; s < n_slices; s++) {
-            if (!s_shared[(size_t)s]) continue;
-            const int real = (int)std::min<int64_t>(RPS, n_units - s * RPS);
-            for (int i = 0; i < real; i++) {
-                const int32_t p = pat[(size_t)units[(size_t)(s * RPS + i)][0]];
-                pat_quads[(size_t)p] = std::max(pat_quads[(size_t)p], (s_max[(size_t)s] + 3) / 4);
-            }
-        }
-        // pass 2: storage.  Padding = (zero feature, 0.0f).
-        B.colpool.assign(4, zero_byte);
-        std::vector<int64_t> pat_cq(pat_rep.size(), -1);         // column quad offset of a pattern stored once
-        int64_t vq = 0;                                          // running value-quad offset, in units of RPS * R quads
-        int U = 1;                                               // share: lanes per column pattern (the longest run of units of one pattern)
-        if (share) {
-            std::map<std::string, int64_t> blocks;               // value sequences of a pattern's lanes -> base of their block, in units of 16 * R bytes
-            for (size_t a = 0; a < units.size();) {
-                size_t b = a + 1;
-                while (b < units.size() && pat[(size_t)units[b][0]] == pat[(size_t)units[a][0]]) b++;
-                U = std::max(U, (int)(b - a));
-                a = b;
-            }
-            B.vstride = U;
-            int64_t next_base = 0;
-            for (size_t a = 0; a < units.size();) {
-                size_t b = a + 1;
-                while (b < units.size() && pat[(size_t)units[b][0]] == pat[(size_t)units[a][0]]) b++;
-                std::string key;
-                int len = 0;
-                for (size_t u = a; u < b; u++)
-                    for (int rr = 0; rr < R; rr++) {
-                        const int32_t r = units[u][(size_t)rr];
-                        const int l = r < 0 ? 0 : len_of(r);
-                        len = std::max(len, l);
-                        key.append(reinterpret_cast<const char*>(&l), sizeof(l));
-                        if (l > 0) key.append(reinterpret_cast<const char*>(dt.data() + ip[(size_t)r]), sizeof(float) * (size_t)l);
-                    }
-                auto it = blocks.find(key);
-                if (it == blocks.end()) {
-                    const int nqc = std::max((len + 3) / 4, 1);
-                    it = blocks.emplace(key, next_base).first;
-                    const size_t f0 = (size_t)next_base * 4 * (size_t)R;
-                    B.vals.resize(f0 + (size_t)nqc * (size_t)U * (size_t)R * 4, 0.0f);
-                    for (size_t u = a; u < b; u++)
-                        for (int rr = 0; rr < R; rr++) {
-                            const int32_t r = units[u][(size_t)rr];
-                            if (r < 0) continue;
-                            const int32_t rs = ip[(size_t)r];
-                            const int l = len_of(r);
-                            for (int k = 0; k < l; k++) B.vals[f0 + ((((size_t)(k >> 2) * (size_t)U + (u - a)) * (size_t)R + (size_t)rr) * 4) + (size_t)(k & 3)] = dt[(size_t)(rs + k)];
-                        }
-                    next_base += (int64_t)nqc * U;
-                }
-                for (size_t u = a; u < b; u++) B.lane_meta[4 * u + 3] = (int32_t)(it->second + (int64_t)(u - a));
-                a = b;
-            }
-        }
-        for (int64_t s = 0; s < n_slices; s++) {
-            const int nq = (s_max[(size_t)s] + 3) / 4;
-            const int real = (int)std::min<int64_t>(RPS, n_units - s * RPS);
-            if (!share) {
-                const size_t v0 = B.vals.size();
-                B.vals.resize(v0 + (size_t)nq * RPS * R * 4, 0.0f);
-                for (int i = 0; i < real; i++)
-                    for (int rr = 0; rr < R; rr++) {
-                        const int32_t r = units[(size_t)(s * RPS + i)][(size_t)rr];
-                        if (r < 0) continue;
-                        const int32_t rs = ip[(size_t)r];
-                        const int len = len_of(r);
-                        for (int k = 0; k < len; k++) B.vals[v0 + ((((size_t)(k >> 2) * RPS + (size_t)i) * R + (size_t)rr) * 4) + (size_t)(k & 3)] = dt[(size_t)(rs + k)];
-                    }
-                for (int i = 0; i < RPS; i++) B.lane_meta[4 * (size_t)(s * RPS + i) + 3] = (int32_t)(vq * RPS + i);      // (every lane its own copy: base = slice's first quad * 64 + lane, stride 64)
-            }
-            {
-                // 64-byte lines one wavefront's requests of this slice touch, quad by quad (what it asks the L2 for; identical addresses and neighbours inside a line are one request)
-                std::vector<int64_t> lines;
-                for (int q = 0; q < nq; q++) {
-                    lines.clear();
-                    for (int i = 0; i < real; i++) {
-                        const int64_t byte0 = (int64_t)16 * R * ((int64_t)B.lane_meta[4 * (size_t)(s * RPS + i) + 3] + (int64_t)q * B.vstride);
-                        for (int64_t l = byte0 / 64; l <= (byte0 + 16 * R - 1) / 64; l++) lines.push_back(l);
-                    }
-                    std::sort(lines.begin(), lines.end());
-                    B.val_line_bytes += 64 * (size_t)(std::unique(lines.begin(), lines.end()) - lines.begin());
-                }
-            }
-            int cstride = 1;
-            if (s_shared[(size_t)s]) {
-                for (int i = 0; i < RPS; i++) {
-                    const size_t o = (size_t)(s * RPS + i);
-                    if (i >= real) {                             // empty slots of the last slice read along with a real row's pattern (their values are 0)
-                        B.lane_meta[4 * o + 1] = B.lane_meta[4 * (size_t)(s * RPS) + 1];
-                        continue;
-                    }
-                    const int32_t r = units[o][0];
-                    const int32_t p = pat[(size_t)r];
-                    if (pat_cq[(size_t)p] < 0) {
-                        pat_cq[(size_t)p] = (int64_t)B.colpool.size() / 4;
-                        const int32_t rs = ip[(size_t)r];
-                        const int len = len_of(r);
-                        const size_t c0 = B.colpool.size();
-                        B.colpool.resize(c0 + (size_t)std::max(pat_quads[(size_t)p], 1) * 4, zero_byte);
-                        for (int k = 0; k < len; k++) B.colpool[c0 + (size_t)k] = off(ix[(size_t)(rs + k)]);
-                    }
-                    B.lane_meta[4 * o + 1] = (int32_t)pat_cq[(size_t)p];
-                }
-            } else {
-                cstride = RPS;
-                const size_t c0 = B.colpool.size();
-                B.colpool.resize(c0 + (size_t)std::max(nq, 1) * RPS * 4, zero_byte);
-                for (int i = 0; i < real; i++) {
-                    const int32_t r = units[(size_t)(s * RPS + i)][0];
-                    const int32_t rs = ip[(size_t)r];
-                    const int len = len_of(r);
-                    for (int k = 0; k < len; k++) B.colpool[c0 + ((size_t)(k >> 2) * RPS + (size_t)i) * 4 + (size_t)(k & 3)] = off(ix[(size_t)(rs + k)]);
-                }
-                for (int i = 0; i < RPS; i++) B.lane_meta[4 * (size_t)(s * RPS + i) + 1] = (int32_t)(c0 / 4 + (size_t)i);
-            }
-            B.info[(size_t)(4 * s + 0)] = nq;
-            B.info[(size_t)(4 * s + 1)] = cstride;
-            B.info[(size_t)(4 * s + 2)] = (int32_t)vq;
-            vq += nq;
-        }
-        B.vals.resize(B.vals.size() + (size_t)CHAIN_OVERREAD_QUADS * (size_t)std::max(B.vstride, RPS) * R * 4, 0.0f);     // requests run past a slice's (and the array's) last quad: readable, never used
-        if (share) {
-            // ... and past a BLOCK's last quad: every lane of a slice walks the slice's longest row, a short row's lane (a keyed Linear's homogeneous row in a slice of
-            // 2 000-entry rows) from its own small block on through whatever follows it, `vstride` lanes per quad.  The array must reach as far as the furthest such request
-            // (found by the fuzzer's keyed-Linear layers: a first layer of 336 rows x 2 179 entries read 2.8 MB past the end).
-            size_t reach = 0;                                                                     // in units of 16 * R bytes
-            for (int64_t s = 0; s < n_slices; s++) {
-                const size_t nq = (size_t)((s_max[(size_t)s] + 3) / 4) + (size_t)CHAIN_OVERREAD_QUADS;
-                const int real = (int)std::min<int64_t>(RPS, n_units - s * RPS);
-                for (int i = 0; i < real; i++) reach = std::max(reach, (size_t)B.lane_meta[4 * (size_t)(s * RPS + i) + 3] + nq * (size_t)B.vstride + 1);
-            }
-            if (B.vals.size() < reach * R * 4) B.vals.resize(reach * R * 4, 0.0f);
-        }
-        B.pool_quads = B.colpool.size() / 4 + 3;                                           // what is staged: the patterns + the three quads a walk requests ahead
-        B.colpool.resize(B.colpool.size() + (size_t)CHAIN_OVERREAD_QUADS * RPS * 4, zero_byte);
-        // thin layer: two wavefronts per slice fit the workgroup, every slice on shared patterns, a walk long enough to be bound by one wavefront's
-        // instruction issue, a column pool of a few KB (staged twice)
-        B.thin = n_slices >= 1 && 2 * n_slices <= CHAIN_THREADS / 64 && B.pool_quads * 16 <= CHAIN_THIN_POOL_BYTES;
-        B.all_shared = n_slices >= 1;
-        for (int64_t s = 0; s < n_slices; s++) {
-            B.thin = B.thin && s_shared[(size_t)s];
-            B.all_shared = B.all_shared && s_shared[(size_t)s];
-            B.longest = std::max(B.longest, s_max[(size_t)s]);
-        }
-        return B;
-    };
-    auto place = [&](Built& X) {                                  // lane records carry the LDS position of an output row (= the row itself unless the next layer is sequential)
-        if (!out_pos) return;
-        for (size_t o = 0; o + 3 < X.lane_meta.size(); o += 4)
-            for (int w : {0, 2})
-                if (X.lane_meta[o + (size_t)w] >= 0) X.lane_meta[o + (size_t)w] = (*out_pos)[(size_t)X.lane_meta[o + (size_t)w]];
-    };
-    auto upload_built = [&](ChainLayerArg& T, const Built& X, const int value_readers = 1, const bool cols_read = true) -> int {
-        // what a workgroup's wavefronts ask the L2 for per forward: the 64-byte lines of their value requests (a thin layer: once per wavefront of the slice), the column pool
-        // (once: staged, or walked from memory), a 16-byte lane record per lane, the slice records.  The over-read padding behind the arrays is not counted.
-        const size_t pad_c = (size_t)CHAIN_OVERREAD_QUADS * 64 * 4;
-        c->stream_bytes += X.val_line_bytes * (size_t)value_readers + 4 * ((cols_read && X.colpool.size() > pad_c ? X.colpool.size() - pad_c : 0) + X.lane_meta.size() + X.info.size());
-        T.vstride = X.vstride;
-        int rc;
-        if ((rc = chain_upload(c, &T.vals, X.vals)) || (rc = chain_upload(c, &T.cols, X.colpool)) || (rc = chain_upload(c, &T.lane_meta, X.lane_meta)) ||
-            (rc = chain_upload(c, &T.slice_info, X.info)))
-            return rc;
-        return KN_OK;
-    };
-    std::memset(&LX, 0, sizeof(LX));
-    if (plan.on) {
-        // sequential thin layer: the rows of the main pattern in slices of their own (values only: their columns are implicit), the others as a general-walk layer
-        Built Bm = build(1, &plan.main_rows);
-        place(Bm);
-        L.n_slices = (int32_t)Bm.n_slices;
-        L.n_rows = (int32_t)rows;
-        L.relu = relu;
-        L.cols_quads = 0;
-        L.rpl = 1;
-        L.stage_off = 0;
-        L.early = 0;
-        L.seq_len = plan.len;
-        L.seq_base = in_base;
-        for (int64_t sl = 0; sl < Bm.n_slices; sl++)               // (chain_rows_thin_pre computes a slice's value base instead of loading its record)
-            if (Bm.info[(size_t)(4 * sl + 2)] != (int32_t)(sl * ((plan.len + 3) / 4)) || Bm.vstride != RPS) return KN_ERR_UNSUPPORTED;      // (cannot happen: equal rows, private copies)
-        int rc = upload_built(L, Bm, CHAIN_SEQ_WPS, false);       // (columns implicit: nothing read)
-        if (rc) return rc;
-        if (!plan.other_rows.empty()) {
-            Built Bx = build(1, &plan.other_rows, true);
-            place(Bx);
-            LX.n_slices = (int32_t)Bx.n_slices;
-            LX.n_rows = (int32_t)plan.other_rows.size();
-            LX.relu = relu;
-            LX.rpl = 1;
-            if ((rc = upload_built(LX, Bx))) return rc;
-        }
-        return KN_OK;
+// Step 1, the deal: which lane of which slice owns which rows.  The rows sorted by (length descending, column pattern, row) and cut into units = what a lane owns: R consecutive
+// rows of the sorted order when they share a pattern (equal pattern => equal length; a pattern with an odd number of rows leaves one lane half empty), else one row.  Lane o of the
+// layer owns units[o]; a slice is 64 lanes.
+struct ChainDeal {
+    int R = 1;
+    std::vector<std::array<int32_t, 2>> units;
+    int64_t n_slices = 0;
+    std::vector<int> s_max;         // per slice: its longest row (every lane of the slice walks that far)
+    std::vector<char> s_shared;     // per slice: its lanes read their columns from one copy per pattern
+    std::vector<int> pat_quads;     // per pattern stored once: the quads it must be readable for
+    int real(const int64_t s) const { return (int)std::min<int64_t>(RPS, (int64_t)units.size() - s * RPS); }
+    int quads(const int64_t s) const { return (s_max[(size_t)s] + 3) / 4; }
+};
+// by_values: the rows of one pattern (the channels of a pixel) in a canonical order -- by their value sequences -- so that two pixels whose channels carry the same sequences
+// form the same value block whatever order the output key gave their rows (which lane of a pattern takes which of its rows changes no result, and nothing but the lanes' rows)
+static ChainDeal chain_deal_rows(const ChainHostCsr& h, std::vector<int32_t> rows, const int R, const bool by_values) {
+    ChainDeal D;
+    D.R = R;
+    std::stable_sort(rows.begin(), rows.end(), [&](int32_t x, int32_t y) {
+        const int32_t lx = h.len(x), ly = h.len(y);
+        if (lx != ly) return lx > ly;
+        if (h.pat[(size_t)x] != h.pat[(size_t)y]) return h.pat[(size_t)x] < h.pat[(size_t)y];
+        return by_values && lx > 0 && std::memcmp(h.dt.data() + h.ip[(size_t)x], h.dt.data() + h.ip[(size_t)y], sizeof(float) * (size_t)lx) < 0;
+    });
+    for (size_t i = 0; i < rows.size();) {
+        const bool pair = R == 2 && i + 1 < rows.size() && h.pat[(size_t)rows[i + 1]] == h.pat[(size_t)rows[i]];
+        D.units.push_back({rows[i], pair ? rows[i + 1] : -1});
+        i += pair ? 2 : 1;
     }
-    Built B = build(1);
-    // (chain_create drops either choice when the staging area does not fit beside the activations)
-    int32_t cols_quads = (B.thin && B.longest >= 64) ? (int32_t)B.pool_quads : (B.all_shared && !tune.chain_no_cl) ? -(int32_t)B.pool_quads : 0;
-    if ((cols_quads > 0 ? 2 * (size_t)cols_quads : (size_t)(-(int64_t)cols_quads)) > room_quads) cols_quads = 0;      // no room for the pool: columns from memory (general walk)
-    int rpl = 1;
-    if (cols_quads < 0 && !tune.chain_no_rpl2) {
-        // Two rows per lane for a pattern layer whose patterns mostly hold two rows or more (the output channels of a conv pixel): halves the LDS reads
-        // per multiply-add (see chain_rows_cl).  Not when it would leave fewer slices than wavefronts of work worth having (a thin layer stays thin).
-        int64_t paired = 0;
-        {
-            std::vector<int32_t> cnt(pat_rep.size(), 0);
-            for (int64_t r = 0; r < rows; r++) cnt[(size_t)pat[(size_t)r]]++;
-            for (int32_t n : cnt) paired += n / 2 * 2;
+    const int64_t n_units = (int64_t)D.units.size();
+    D.n_slices = (n_units + RPS - 1) / RPS;
+    D.s_max.assign((size_t)D.n_slices, 0);
+    D.s_shared.assign((size_t)D.n_slices, 0);
+    D.pat_quads.assign(h.pat_rep.size(), 0);
+    int64_t units_shared = 0;
+    for (int64_t s = 0; s < D.n_slices; s++) {
+        int mx = 0, distinct = 0;
+        int32_t last_pat = -2;
+        for (int i = 0; i < D.real(s); i++) {
+            const int32_t r = D.units[(size_t)(s * RPS + i)][0];
+            mx = std::max(mx, h.len(r));
+            if (h.pat[(size_t)r] != last_pat) distinct++;
+            last_pat = h.pat[(size_t)r];
         }
-        if (paired * 10 >= rows * 9 && rows >= 2 * RPS * 8) {
-            Built B2 = build(2);
-            if (B2.pool_quads <= room_quads) {
-                B = std::move(B2);
-                cols_quads = -(int32_t)B.pool_quads;
-                rpl = 2;
-            }
+        D.s_max[(size_t)s] = mx;
+        D.s_shared[(size_t)s] = (distinct * 2 <= D.real(s) || R == 2) ? 1 : 0;     // most lanes share a pattern with a neighbour: one copy per pattern
+        if (D.s_shared[(size_t)s]) units_shared += D.real(s);
+    }
+    // a layer that is shared almost everywhere (a conv layer and its odd last slice: the homogeneous row) stores every slice that way -- one layout
+    // per layer lets its whole pool be staged in LDS (chain_rows_cl); the few unrelated rows then read scattered instead of lane-adjacent quads
+    if (units_shared * 10 >= n_units * 9) std::fill(D.s_shared.begin(), D.s_shared.end(), (char)1);
+    for (int64_t s = 0; s < D.n_slices; s++) {
+        if (!D.s_shared[(size_t)s]) continue;
+        for (int i = 0; i < D.real(s); i++) {
+            int& pq = D.pat_quads[(size_t)h.pat[(size_t)D.units[(size_t)(s * RPS + i)][0]]];
+            pq = std::max(pq, D.quads(s));
         }
     }
-    if (cols_quads <= 0 && !tune.chain_no_share) B = build(rpl, nullptr, true);      // general / pattern walks: one copy per distinct value sequence (same rows, same lanes, same columns)
-    place(B);
-    L.n_slices = (int32_t)B.n_slices;
-    L.n_rows = (int32_t)rows;
-    L.relu = relu;
-    L.cols_quads = cols_quads;
-    L.rpl = rpl;
-    L.stage_off = 0;
-    L.early = 0;
-    L.seq_len = 0;
-    L.seq_base = 0;
-    return upload_built(L, B, cols_quads > 0 ? 2 : 1);
+    return D;
 }
 
-int chain_create(int64_t n_ops, kn_operator* const* ops, const uint32_t* flags, ChainDev** out, int64_t* rows_out, int64_t* cols_out, int64_t* nnz_out) {
-    *out = nullptr;
+// where a layer's input features, the always-zero feature and its output rows sit in LDS: byte offsets of the input buffer and of the zero feature; in_pos / out_pos (or null)
+// = the position of an input feature / output row inside its buffer when the layer itself / the layer behind it is walked sequentially (chain_plan_seq)
+struct ChainLds {
+    int32_t in_base, zero_byte;
+    const std::vector<int32_t>*in_pos, *out_pos;
+    int32_t off(const int32_t col) const { return in_base + 16 * (in_pos ? (*in_pos)[(size_t)col] : col); }
+};
+
+// Step 2, the columns: an entry is the LDS byte offset of the feature; padding = the zero feature.  A slice on shared patterns reads ONE copy per pattern (per-lane base, quad
+// stride 1), a slice of unrelated rows stores them like the values, [q][lane][4] (quad stride 64).  Depends on the deal alone, not on a single value.
+struct ChainColumns {
+    std::vector<int32_t> pool;
+    std::vector<int32_t> lane_quad;      // per lane: its first column quad
+    std::vector<int32_t> stride;         // per slice: 1 or 64
+    size_t pool_quads = 0;               // what a staged pool holds: the patterns + the three quads a walk requests ahead
+    bool thin = false, all_shared = false;
+    int longest = 0;
+};
+static ChainColumns chain_layout_columns(const ChainHostCsr& h, const ChainDeal& D, const ChainLds& lds) {
+    ChainColumns C;
+    C.pool.assign(4, lds.zero_byte);
+    C.lane_quad.assign((size_t)(D.n_slices * RPS), 0);
+    C.stride.assign((size_t)D.n_slices, 1);
+    std::vector<int64_t> pat_cq(h.pat_rep.size(), -1);         // column quad offset of a pattern stored once
+    for (int64_t s = 0; s < D.n_slices; s++) {
+        const size_t o0 = (size_t)(s * RPS);
+        if (D.s_shared[(size_t)s]) {
+            for (int i = 0; i < D.real(s); i++) {
+                const int32_t r = D.units[o0 + (size_t)i][0];
+                const int32_t p = h.pat[(size_t)r];
+                if (pat_cq[(size_t)p] < 0) {
+                    pat_cq[(size_t)p] = (int64_t)C.pool.size() / 4;
+                    const size_t c0 = C.pool.size();
+                    C.pool.resize(c0 + (size_t)std::max(D.pat_quads[(size_t)p], 1) * 4, lds.zero_byte);
+                    for (int k = 0; k < h.len(r); k++) C.pool[c0 + (size_t)k] = lds.off(h.ix[(size_t)(h.ip[(size_t)r] + k)]);
+                }
+                C.lane_quad[o0 + (size_t)i] = (int32_t)pat_cq[(size_t)p];
+            }
+            for (int i = D.real(s); i < RPS; i++) C.lane_quad[o0 + (size_t)i] = C.lane_quad[o0];      // empty slots of the last slice read along with a real row's pattern (their values are 0)
+        } else {
+            C.stride[(size_t)s] = RPS;
+            const size_t c0 = C.pool.size();
+            C.pool.resize(c0 + (size_t)std::max(D.quads(s), 1) * RPS * 4, lds.zero_byte);
+            for (int i = 0; i < D.real(s); i++) {
+                const int32_t r = D.units[o0 + (size_t)i][0];
+                for (int k = 0; k < h.len(r); k++) C.pool[c0 + ((size_t)(k >> 2) * RPS + (size_t)i) * 4 + (size_t)(k & 3)] = lds.off(h.ix[(size_t)(h.ip[(size_t)r] + k)]);
+            }
+            for (int i = 0; i < RPS; i++) C.lane_quad[o0 + (size_t)i] = (int32_t)(c0 / 4 + (size_t)i);
+        }
+    }
+    C.pool_quads = C.pool.size() / 4 + 3;
+    C.pool.resize(C.pool.size() + (size_t)CHAIN_OVERREAD_QUADS * RPS * 4, lds.zero_byte);      // requests run past a slice's (and the array's) last quad: readable, never used
+    // thin layer: two wavefronts per slice fit the workgroup, every slice on shared patterns, a walk long enough to be bound by one wavefront's
+    // instruction issue (chain_choose_walk asks for that), a column pool of a few KB (staged twice)
+    C.all_shared = D.n_slices >= 1 && std::find(D.s_shared.begin(), D.s_shared.end(), (char)0) == D.s_shared.end();
+    C.thin = C.all_shared && 2 * D.n_slices <= CHAIN_THREADS / 64 && C.pool_quads * 16 <= CHAIN_THIN_POOL_BYTES;
+    for (int64_t s = 0; s < D.n_slices; s++) C.longest = std::max(C.longest, D.s_max[(size_t)s]);
+    return C;
+}
+
+// Step 3, the values, in one of two formats: sliced ELL in quads, padding = 0.0f.  lane_base / vstride: ChainLaneRec::val_base, ChainLayerArg::vstride.
+struct ChainValues {
+    std::vector<float> vals;
+    std::vector<int32_t> lane_base;
+    int vstride = RPS;
+};
+// Every lane its own copy: [slice][q][lane][row of the lane][4]; a lane's base = the slice's first quad * 64 + lane, stride 64.
+static ChainValues chain_layout_values_private(const ChainHostCsr& h, const ChainDeal& D) {
+    ChainValues V;
+    const size_t R = (size_t)D.R;
+    V.lane_base.assign((size_t)(D.n_slices * RPS), 0);
+    int64_t vq = 0;                                          // running value-quad offset, in units of RPS * R quads
+    for (int64_t s = 0; s < D.n_slices; s++) {
+        const size_t v0 = V.vals.size();
+        V.vals.resize(v0 + (size_t)D.quads(s) * RPS * R * 4, 0.0f);
+        for (int i = 0; i < D.real(s); i++)
+            for (size_t rr = 0; rr < R; rr++) {
+                const int32_t r = D.units[(size_t)(s * RPS + i)][rr];
+                if (r < 0) continue;
+                for (int k = 0; k < h.len(r); k++) V.vals[v0 + ((((size_t)(k >> 2) * RPS + (size_t)i) * R + rr) * 4) + (size_t)(k & 3)] = h.dt[(size_t)(h.ip[(size_t)r] + k)];
+            }
+        for (int i = 0; i < RPS; i++) V.lane_base[(size_t)(s * RPS + i)] = (int32_t)(vq * RPS + i);
+        vq += D.quads(s);
+    }
+    V.vals.resize(V.vals.size() + (size_t)CHAIN_OVERREAD_QUADS * RPS * R * 4, 0.0f);     // requests run past a slice's (and the array's) last quad: readable, never used
+    return V;
+}
+// Lanes whose rows carry the SAME value sequence read ONE copy of it (general / pattern walks).  A keyed conv stores one weight sequence per (output channel, border class) --
+// LeNet conv2: 145 distinct sequences for 3 137 rows, its pooling layers 4 for 1 177 -- while a private copy per lane is 1.0 of the 2.3 MB a workgroup asks the L2 for per
+// forward, in a kernel whose 256 workgroups together run at 60-70 % of the L2's measured read rate (profiles/r06_lenet_chain_breakdown.txt).
+// Layout: the lanes of one column pattern (the channels of a pixel, `U` lanes) keep their order; patterns whose lanes carry identical sequences share a block
+// [quad][lane of the pattern][row of the lane][4] -- a quad's request of such a pattern is U * 16 * R contiguous bytes, the same for every pixel of the class.  A lane's base
+// goes into its record (val_base), the quad stride U into the layer record.  Reads past a block's last quad (a shorter row in a slice of longer ones) hit the next block's
+// finite values and multiply the always-zero feature: +-0.0 onto a sum that started at +0.0, as with the 0.0f padding of the private format.
+static ChainValues chain_layout_values_shared(const ChainHostCsr& h, const ChainDeal& D) {
+    ChainValues V;
+    const size_t R = (size_t)D.R, n_units = D.units.size();
+    V.lane_base.assign((size_t)(D.n_slices * RPS), 0);
+    auto run_end = [&](size_t a) {                           // the lanes of one column pattern are a run of units
+        size_t b = a + 1;
+        while (b < n_units && h.pat[(size_t)D.units[b][0]] == h.pat[(size_t)D.units[a][0]]) b++;
+        return b;
+    };
+    size_t U = 1;                                            // lanes per column pattern: the longest run
+    for (size_t a = 0; a < n_units; a = run_end(a)) U = std::max(U, run_end(a) - a);
+    V.vstride = (int)U;
+    std::map<std::string, int64_t> blocks;                   // value sequences of a pattern's lanes -> base of their block, in units of 16 * R bytes
+    int64_t next_base = 0;
+    for (size_t a = 0; a < n_units; a = run_end(a)) {
+        const size_t b = run_end(a);
+        std::string key;
+        int len = 0;
+        for (size_t u = a; u < b; u++)
+            for (size_t rr = 0; rr < R; rr++) {
+                const int32_t r = D.units[u][rr];
+                const int l = r < 0 ? 0 : h.len(r);
+                len = std::max(len, l);
+                key.append(reinterpret_cast<const char*>(&l), sizeof(l));
+                if (l > 0) key.append(reinterpret_cast<const char*>(h.dt.data() + h.ip[(size_t)r]), sizeof(float) * (size_t)l);
+            }
+        auto it = blocks.find(key);
+        if (it == blocks.end()) {
+            const int nqc = std::max((len + 3) / 4, 1);
+            it = blocks.emplace(key, next_base).first;
+            const size_t f0 = (size_t)next_base * 4 * R;
+            V.vals.resize(f0 + (size_t)nqc * U * R * 4, 0.0f);
+            for (size_t u = a; u < b; u++)
+                for (size_t rr = 0; rr < R; rr++) {
+                    const int32_t r = D.units[u][rr];
+                    if (r < 0) continue;
+                    for (int k = 0; k < h.len(r); k++) V.vals[f0 + ((((size_t)(k >> 2) * U + (u - a)) * R + rr) * 4) + (size_t)(k & 3)] = h.dt[(size_t)(h.ip[(size_t)r] + k)];
+                }
+            next_base += (int64_t)nqc * (int64_t)U;
+        }
+        for (size_t u = a; u < b; u++) V.lane_base[u] = (int32_t)(it->second + (int64_t)(u - a));
+    }
+    V.vals.resize(V.vals.size() + (size_t)CHAIN_OVERREAD_QUADS * std::max(U, (size_t)RPS) * R * 4, 0.0f);     // requests run past the array's last quad: readable, never used
+    // ... and past a BLOCK's last quad: every lane of a slice walks the slice's longest row, a short row's lane (a keyed Linear's homogeneous row in a slice of
+    // 2 000-entry rows) from its own small block on through whatever follows it, `vstride` lanes per quad.  The array must reach as far as the furthest such request
+    // (found by the fuzzer's keyed-Linear layers: a first layer of 336 rows x 2 179 entries read 2.8 MB past the end).
+    size_t reach = 0;                                                                     // in units of 16 * R bytes
+    for (int64_t s = 0; s < D.n_slices; s++)
+        for (int i = 0; i < D.real(s); i++) reach = std::max(reach, (size_t)V.lane_base[(size_t)(s * RPS + i)] + ((size_t)D.quads(s) + (size_t)CHAIN_OVERREAD_QUADS) * U + 1);
+    if (V.vals.size() < reach * R * 4) V.vals.resize(reach * R * 4, 0.0f);
+    return V;
+}
+
+// 64-byte lines the wavefronts' value requests of one forward touch, quad by quad (what they ask the L2 for; identical addresses and neighbours inside a line are one request), in bytes
+static size_t chain_count_value_lines(const ChainDeal& D, const ChainValues& V) {
+    size_t bytes = 0;
+    std::vector<int64_t> lines;
+    for (int64_t s = 0; s < D.n_slices; s++)
+        for (int q = 0; q < D.quads(s); q++) {
+            lines.clear();
+            for (int i = 0; i < D.real(s); i++) {
+                const int64_t byte0 = (int64_t)16 * D.R * ((int64_t)V.lane_base[(size_t)(s * RPS + i)] + (int64_t)q * V.vstride);
+                for (int64_t l = byte0 / 64; l <= (byte0 + 16 * D.R - 1) / 64; l++) lines.push_back(l);
+            }
+            std::sort(lines.begin(), lines.end());
+            bytes += 64 * (size_t)(std::unique(lines.begin(), lines.end()) - lines.begin());
+        }
+    return bytes;
+}
+
+// One record of ChainArgs (L[l], or LX[l]) for the rows `rows` of a layer: deal, columns, ONE value layout, the lane and slice records; uploaded as vals, cols, lane_meta,
+// slice_info.  value_readers / cols_read: wavefronts that request a slice's values, and whether the column pool is read at all (for ChainDev::stream_bytes).
+static int chain_build_record(ChainDev* c, ChainLayerArg& T, const ChainHostCsr& h, const std::vector<int32_t>& rows, const ChainLds& lds, const int R, const bool share,
+                              const int value_readers, const bool cols_read) {
+    const ChainDeal D = chain_deal_rows(h, rows, R, share);
+    const ChainColumns C = chain_layout_columns(h, D, lds);
+    const ChainValues V = share ? chain_layout_values_shared(h, D) : chain_layout_values_private(h, D);
+    auto placed = [&](int32_t r) { return (r >= 0 && lds.out_pos) ? (*lds.out_pos)[(size_t)r] : r; };
+    std::vector<ChainLaneRec> lanes((size_t)(D.n_slices * RPS));
+    for (size_t o = 0; o < lanes.size(); o++) {
+        const std::array<int32_t, 2> u = o < D.units.size() ? D.units[o] : std::array<int32_t, 2>{-1, -1};
+        lanes[o] = {placed(u[0]), C.lane_quad[o], placed(u[1]), V.lane_base[o]};
+    }
+    std::vector<ChainSliceRec> slices((size_t)D.n_slices);
+    int32_t vq = 0;
+    for (int64_t s = 0; s < D.n_slices; s++) {
+        slices[(size_t)s] = {D.quads(s), C.stride[(size_t)s], vq, 0};
+        vq += D.quads(s);
+    }
+    // what a workgroup's wavefronts ask the L2 for per forward: the 64-byte lines of their value requests (a thin layer: once per wavefront of the slice), the column pool
+    // (once: staged, or walked from memory), a 16-byte lane record per lane, the slice records.  The over-read padding behind the arrays is not counted.
+    const size_t pad_c = (size_t)CHAIN_OVERREAD_QUADS * RPS * 4;
+    c->stream_bytes += chain_count_value_lines(D, V) * (size_t)value_readers + 4 * ((cols_read && C.pool.size() > pad_c ? C.pool.size() - pad_c : 0)) + 16 * (lanes.size() + slices.size());
+    T.n_slices = (int32_t)D.n_slices;
+    T.rpl = R;
+    T.vstride = V.vstride;
+    int rc;
+    if ((rc = chain_upload(c, &T.vals, V.vals.data(), V.vals.size())) || (rc = chain_upload(c, &T.cols, C.pool.data(), C.pool.size())) ||
+        (rc = chain_upload(c, &T.lane_meta, reinterpret_cast<const int32_t*>(lanes.data()), 4 * lanes.size())) ||
+        (rc = chain_upload(c, &T.slice_info, reinterpret_cast<const int32_t*>(slices.data()), 4 * slices.size())))
+        return rc;
+    return KN_OK;
+}
+
+// The layer's ONE decision, from deals and column layouts alone (no value is laid out for it): which walk, rows per lane, shared value blocks, LDS quads of the staged pool.
+struct ChainWalk {
+    ChainWalkKind kind = CHAIN_WALK_MEMORY;
+    int rpl = 1;
+    bool share = false;
+    size_t pool_quads = 0;       // of the staged pool (thin: one copy)
+    size_t lds_quads() const { return chain_lds_quads(kind, pool_quads); }
+};
+static ChainWalk chain_choose_walk(const ChainHostCsr& h, const ChainLds& lds, const Tuning& tune, const size_t room_quads, const std::vector<int32_t>& all_rows) {
+    ChainWalk W;
+    const ChainColumns C = chain_layout_columns(h, chain_deal_rows(h, all_rows, 1, false), lds);
+    W.kind = (C.thin && C.longest >= 64) ? CHAIN_WALK_THIN : (C.all_shared && !tune.chain_no_cl) ? CHAIN_WALK_POOL : CHAIN_WALK_MEMORY;
+    W.pool_quads = C.pool_quads;
+    if (W.lds_quads() > room_quads) W.kind = CHAIN_WALK_MEMORY;      // no room for the pool beside the activations: columns from memory (general walk)
+    if (W.kind == CHAIN_WALK_POOL && !tune.chain_no_rpl2) {
+        // Two rows per lane for a pattern layer whose patterns mostly hold two rows or more (the output channels of a conv pixel): halves the LDS reads
+        // per multiply-add (see chain_rows_cl).  Not when it would leave fewer slices than wavefronts of work worth having (a thin layer stays thin).
+        std::vector<int32_t> cnt(h.pat_rep.size(), 0);
+        for (int64_t r = 0; r < h.rows; r++) cnt[(size_t)h.pat[(size_t)r]]++;
+        int64_t paired = 0;
+        for (int32_t n : cnt) paired += n / 2 * 2;
+        if (paired * 10 >= h.rows * 9 && h.rows >= 2 * RPS * 8) {
+            const ChainColumns C2 = chain_layout_columns(h, chain_deal_rows(h, all_rows, 2, false), lds);      // (its pool differs: padded to the longest row of other slices)
+            if (C2.pool_quads <= room_quads) {
+                W.pool_quads = C2.pool_quads;
+                W.rpl = 2;
+            }
+        }
+    }
+    if (W.kind == CHAIN_WALK_MEMORY) W.pool_quads = 0;
+    W.share = W.kind != CHAIN_WALK_THIN && !tune.chain_no_share;      // general / pattern walks: one copy per distinct value sequence
+    return W;
+}
+
+// one layer: CSR (host copy, stored order) -> the sliced layout above, as L (and LX: the rows of a sequential layer that do not share its main pattern).
+// room_quads: LDS left beside the activations, in 16-byte quads (what a staged column pool may take)
+static int chain_build_layer(ChainDev* c, ChainLayerArg& L, ChainLayerArg& LX, const ChainHostCsr& h, const int relu, const ChainLds& lds, const Tuning& tune,
+                             const size_t room_quads, const ChainSeqPlan& plan) {
+    L.n_rows = (int32_t)h.rows;
+    L.relu = relu;
+    if (plan.on) {
+        // sequential thin layer: the rows of the main pattern in slices of their own (values only: their columns are implicit, nothing of the pool is read), the others as a
+        // general-walk layer on shared value blocks
+        L.seq_len = plan.len;
+        L.seq_base = lds.in_base;
+        // chain_rows_thin_pre computes a slice's value base instead of loading its record: every slice must hold ceil(seq_len / 4) quads of private copies
+        for (int32_t r : plan.main_rows)
+            if (h.len(r) != plan.len) return KN_ERR_UNSUPPORTED;      // (cannot happen: rows of one pattern)
+        int rc = chain_build_record(c, L, h, plan.main_rows, lds, 1, false, CHAIN_SEQ_WPS, false);
+        if (rc || plan.other_rows.empty()) return rc;
+        LX.n_rows = (int32_t)plan.other_rows.size();
+        LX.relu = relu;
+        return chain_build_record(c, LX, h, plan.other_rows, lds, 1, true, 1, true);
+    }
+    std::vector<int32_t> all_rows((size_t)h.rows);
+    std::iota(all_rows.begin(), all_rows.end(), 0);
+    const ChainWalk W = chain_choose_walk(h, lds, tune, room_quads, all_rows);
+    L.cols_quads = chain_cols_quads(W.kind, W.pool_quads);
+    return chain_build_record(c, L, h, all_rows, lds, W.rpl, W.share, W.kind == CHAIN_WALK_THIN ? 2 : 1, true);
+}
+
+#ifdef KN_HOST_PACK_ONLY
+// KN_UPLOAD_TRACE (kn_internal.h): what the kernel receives by value, pointers left out -- one line per layer record, one for the chain
+static void chain_trace_scalars(const ChainDev* c) {
+    auto layer = [](const char* which, int l, const ChainLayerArg& A) {
+        std::string t = std::string("chain ") + which + "[" + std::to_string(l) + "]";
+        const std::pair<const char*, int32_t> f[] = {{"n_slices", A.n_slices}, {"n_rows", A.n_rows}, {"relu", A.relu}, {"cols_quads", A.cols_quads}, {"rpl", A.rpl},
+                                                     {"stage_off", A.stage_off}, {"early", A.early}, {"vstride", A.vstride}, {"seq_len", A.seq_len}, {"seq_base", A.seq_base}};
+        for (const auto& kv : f) t += std::string(" ") + kv.first + "=" + std::to_string(kv.second);
+        hostonly::trace_text(t);
+    };
+    const ChainArgs& a = c->args;
+    for (int l = 0; l < a.n_layers; l++) {
+        layer("L", l, a.L[l]);
+        layer("LX", l, a.LX[l]);
+    }
+    hostonly::trace_text("chain n_layers=" + std::to_string(a.n_layers) + " n_in=" + std::to_string(a.n_in) + " n_out=" + std::to_string(a.n_out) + " buf1_off=" + std::to_string(a.buf1_off) +
+                         " zero_off=" + std::to_string(a.zero_off) + " lds_bytes=" + std::to_string(c->lds_bytes) + " stream_bytes=" + std::to_string(c->stream_bytes));
+}
+#endif
+
+// chain_create, step by step.  Validate the operators and size the activations: feat = features held by the even / odd activation buffer
+static int chain_size_activations(int64_t n_ops, kn_operator* const* ops, size_t feat[2], size_t* lds_out, int64_t* nnz_out) {
     KN_REQUIRE(n_ops >= 1 && n_ops <= CHAIN_MAX_LAYERS, KN_ERR_UNSUPPORTED, "a chain holds 1..12 operators");
-    size_t feat[2] = {0, 0};      // features held by the even / odd activation buffer
     int64_t nnz = 0;
     for (int64_t l = 0; l < n_ops; l++) {
         KN_REQUIRE(ops[l] != nullptr && ops[l]->kind == KIND_CSR, KN_ERR_UNSUPPORTED, "chain operators must be CSR handles (kn_csr_create / kn_tiled_create)");
@@ -1216,43 +1270,100 @@ int chain_create(int64_t n_ops, kn_operator* const* ops, const uint32_t* flags, 
     }
     const size_t lds = (feat[0] + feat[1] + 1) * CHAIN_BT * sizeof(float);      // two activation buffers + the always-zero feature
     KN_REQUIRE(lds <= CHAIN_LDS_BYTES, KN_ERR_UNSUPPORTED, "activations of four batch columns do not fit the CU's 160 KiB of LDS");
-    {
-        // the kernel is written for gfx950's 160 KiB of LDS per workgroup: ask the device rather than assume (the caller falls back to one
-        // launch per layer on KN_ERR_UNSUPPORTED)
-        int dev = 0, max_lds = 0;
-        KN_HIP(hipGetDevice(&dev));
-        KN_HIP(hipDeviceGetAttribute(&max_lds, hipDeviceAttributeMaxSharedMemoryPerBlock, dev));
-        KN_REQUIRE((size_t)max_lds >= CHAIN_LDS_BYTES, KN_ERR_UNSUPPORTED, "this device offers less than 160 KiB of LDS per workgroup: the whole-net kernel does not apply");
+    // the kernel is written for gfx950's 160 KiB of LDS per workgroup: ask the device rather than assume (the caller falls back to one
+    // launch per layer on KN_ERR_UNSUPPORTED)
+    int dev = 0, max_lds = 0;
+    KN_HIP(hipGetDevice(&dev));
+    KN_HIP(hipDeviceGetAttribute(&max_lds, hipDeviceAttributeMaxSharedMemoryPerBlock, dev));
+    KN_REQUIRE((size_t)max_lds >= CHAIN_LDS_BYTES, KN_ERR_UNSUPPORTED, "this device offers less than 160 KiB of LDS per workgroup: the whole-net kernel does not apply");
+    *lds_out = lds;
+    *nnz_out = nnz;
+    return KN_OK;
+}
+
+static int chain_fetch_operator(const CsrDev& A, ChainHostCsr& h) {
+    h.rows = A.rows;
+    h.cols = A.cols;
+    h.ip.resize((size_t)A.rows + 1);
+    h.ix.resize((size_t)A.nnz);
+    h.dt.resize((size_t)A.nnz);
+    KN_HIP(hipMemcpy(h.ip.data(), A.indptr, sizeof(int32_t) * h.ip.size(), hipMemcpyDeviceToHost));
+    if (A.nnz > 0) {
+        KN_HIP(hipMemcpy(h.ix.data(), A.indices, sizeof(int32_t) * h.ix.size(), hipMemcpyDeviceToHost));
+        KN_HIP(hipMemcpy(h.dt.data(), A.data, sizeof(float) * h.dt.size(), hipMemcpyDeviceToHost));
     }
+    row_patterns(A.rows, h.ip.data(), h.ix.data(), true, h.pat, h.pat_rep);
+    return KN_OK;
+}
+
+// Staging areas of the column pools, behind the activations (base4 / limit4: float4 indices of their end and of the end of LDS).  A pool is staged EARLY -- while the previous
+// layer runs (layer 0: with the input) -- when it can have an area that layer does not read: the base area when the previous layer has no pool, else right behind the previous
+// layer's area when that still fits.  Returns the end of the furthest area through stage_end4.
+static int chain_place_staging(ChainArgs& args, int64_t n_ops, kn_operator* const* ops, const size_t base4, const size_t limit4, size_t* stage_end4) {
+    *stage_end4 = base4;
+    size_t prev_end4 = base4;                                      // end of the area the previous layer reads (base4: none)
+    for (int64_t l = 0; l < n_ops; l++) {
+        ChainLayerArg& L = args.L[l];
+        const size_t need = chain_lds_quads(L);
+        if (need == 0) {
+            prev_end4 = base4;
+            continue;
+        }
+        KN_REQUIRE(base4 + need <= limit4, KN_ERR_INVALID, "internal: a column pool larger than the room chain_build_layer was given");
+        const bool may = !ops[l]->csr.tune.chain_no_early;
+        if (may && prev_end4 + need <= limit4) {
+            L.stage_off = (int32_t)prev_end4;
+            L.early = 1;
+        } else {
+            L.stage_off = (int32_t)base4;
+            L.early = (may && prev_end4 == base4) ? 1 : 0;
+        }
+        prev_end4 = (size_t)L.stage_off + need;
+        *stage_end4 = std::max(*stage_end4, prev_end4);
+    }
+    return KN_OK;
+}
+
+// what kn_spmm_plan prints for the launch: depends on the handle alone
+static std::string chain_describe(const ChainDev* c) {
+    const ChainArgs& a = c->args;
+    int n_thin = 0, n_cl = 0, n_rpl2 = 0, n_early = 0, n_seq = 0;
+    for (int l = 0; l < a.n_layers; l++) {
+        const ChainWalkKind walk = chain_walk_of(a.L[l]);
+        n_seq += walk == CHAIN_WALK_SEQ ? 1 : 0;
+        n_thin += (walk == CHAIN_WALK_THIN || walk == CHAIN_WALK_SEQ) ? 1 : 0;
+        n_cl += walk == CHAIN_WALK_POOL ? 1 : 0;
+        n_rpl2 += a.L[l].rpl == 2 ? 1 : 0;
+        n_early += (chain_lds_quads(a.L[l]) != 0 && a.L[l].early) ? 1 : 0;
+    }
+    return "chain_kernel<" + std::to_string(a.n_layers) + " operators (" + std::to_string(n_thin) + " on the thin walk -- " + std::to_string(n_seq) + " of them sequentially, " + std::to_string(n_cl) +
+           " with column patterns in LDS), " + std::to_string(n_rpl2) + " with two rows per lane, " + std::to_string(n_early) +
+           " column pools staged a layer early, 4 batch columns per workgroup, " + std::to_string(c->lds_bytes) + " B LDS, " + std::to_string(c->stream_bytes) +
+           " B of operator words per workgroup from L2>";
+}
+
+int chain_create(int64_t n_ops, kn_operator* const* ops, const uint32_t* flags, ChainDev** out, int64_t* rows_out, int64_t* cols_out, int64_t* nnz_out) {
+    *out = nullptr;
+    size_t feat[2] = {0, 0}, lds = 0;
+    int64_t nnz = 0;
+    int rc = chain_size_activations(n_ops, ops, feat, &lds, &nnz);
+    if (rc) return rc;
     std::unique_ptr<ChainDev, void (*)(ChainDev*)> c(new ChainDev(), chain_free);
     std::memset(&c->args, 0, sizeof(ChainArgs));
-    // pass 1: the operators on the host, and which layers are walked sequentially (that decides the LDS order of the layer before them)
-    struct HostCsr {
-        std::vector<int32_t> ip, ix;
-        std::vector<float> dt;
-    };
-    std::vector<HostCsr> H((size_t)n_ops);
+    // the operators on the host, and which layers are walked sequentially (that decides the LDS order of the layer before them)
+    std::vector<ChainHostCsr> H((size_t)n_ops);
     std::vector<ChainSeqPlan> plans((size_t)n_ops);
     for (int64_t l = 0; l < n_ops; l++) {
-        const CsrDev& A = ops[l]->csr;
-        HostCsr& h = H[(size_t)l];
-        h.ip.resize((size_t)A.rows + 1);
-        h.ix.resize((size_t)A.nnz);
-        h.dt.resize((size_t)A.nnz);
-        KN_HIP(hipMemcpy(h.ip.data(), A.indptr, sizeof(int32_t) * h.ip.size(), hipMemcpyDeviceToHost));
-        if (A.nnz > 0) {
-            KN_HIP(hipMemcpy(h.ix.data(), A.indices, sizeof(int32_t) * h.ix.size(), hipMemcpyDeviceToHost));
-            KN_HIP(hipMemcpy(h.dt.data(), A.data, sizeof(float) * h.dt.size(), hipMemcpyDeviceToHost));
-        }
-        plans[(size_t)l] = chain_plan_seq(l, A.rows, A.cols, h.ip, h.ix, A.tune);
+        if ((rc = chain_fetch_operator(ops[l]->csr, H[(size_t)l]))) return rc;
+        plans[(size_t)l] = chain_plan_seq(l, H[(size_t)l], ops[l]->csr.tune);
     }
-    // pass 2: the layouts
+    // the layouts
     for (int64_t l = 0; l < n_ops; l++) {
-        const CsrDev& A = ops[l]->csr;
-        const HostCsr& h = H[(size_t)l];
-        const std::vector<int32_t>* out_pos = (l + 1 < n_ops && plans[(size_t)l + 1].on) ? &plans[(size_t)l + 1].pos : nullptr;
-        int rc = chain_build_layer(c.get(), c->args.L[l], c->args.LX[l], A.rows, A.cols, h.ip, h.ix, h.dt, (flags && (flags[l] & KN_FLAG_RELU)) ? 1 : 0,
-                                   (int32_t)((l & 1) ? 16 * feat[0] : 0), (int32_t)(16 * (feat[0] + feat[1])), A.tune, (CHAIN_LDS_BYTES - lds) / 16, plans[(size_t)l], out_pos);
+        const ChainSeqPlan& plan = plans[(size_t)l];
+        const ChainLds where = {(int32_t)((l & 1) ? 16 * feat[0] : 0), (int32_t)(16 * (feat[0] + feat[1])), plan.on ? &plan.pos : nullptr,
+                                (l + 1 < n_ops && plans[(size_t)l + 1].on) ? &plans[(size_t)l + 1].pos : nullptr};
+        rc = chain_build_layer(c.get(), c->args.L[l], c->args.LX[l], H[(size_t)l], (flags && (flags[l] & KN_FLAG_RELU)) ? 1 : 0, where, ops[l]->csr.tune,
+                               (CHAIN_LDS_BYTES - lds) / 16, plan);
         if (rc) return rc;
     }
     c->args.n_layers = (int32_t)n_ops;
@@ -1260,35 +1371,15 @@ int chain_create(int64_t n_ops, kn_operator* const* ops, const uint32_t* flags, 
     c->args.n_out = (int32_t)ops[n_ops - 1]->rows;
     c->args.buf1_off = (int32_t)feat[0];
     c->args.zero_off = (int32_t)(feat[0] + feat[1]);
-    // Staging areas of the column pools, behind the activations.  A layer whose pool does not fit beside the activations reads its columns from memory
-    // (general walk).  A pool is staged EARLY -- while the previous layer runs (layer 0: with the input) -- when it can have an area that layer does not
-    // read: the base area when the previous layer has no pool, else right behind the previous layer's area when that still fits.
-    const size_t base4 = feat[0] + feat[1] + 1;                   // float4 index
-    const size_t limit4 = CHAIN_LDS_BYTES / 16;
+    const size_t base4 = feat[0] + feat[1] + 1;                   // float4 index: the end of the activations
     size_t stage_end4 = base4;
-    size_t prev_end4 = base4;                                      // end of the area the previous layer reads (base4: none)
-    for (int64_t l = 0; l < n_ops; l++) {
-        ChainLayerArg& L = c->args.L[l];
-        const size_t need = L.cols_quads > 0 ? 2 * (size_t)L.cols_quads : (size_t)(-(int64_t)L.cols_quads);
-        if (need == 0) {
-            prev_end4 = base4;
-            continue;
-        }
-        KN_REQUIRE(base4 + need <= limit4, KN_ERR_INVALID, "internal: a column pool larger than the room chain_build_layer was given");
-        const bool small = !ops[l]->csr.tune.chain_no_early;      // (name kept: every pool qualifies for early staging)
-        if (small && prev_end4 + need <= limit4) {
-            L.stage_off = (int32_t)prev_end4;
-            L.early = 1;
-        } else {
-            L.stage_off = (int32_t)base4;
-            L.early = (small && prev_end4 == base4) ? 1 : 0;
-        }
-        prev_end4 = (size_t)L.stage_off + need;
-        stage_end4 = std::max(stage_end4, prev_end4);
-    }
-    const size_t stage_quads = stage_end4 - base4;
-    c->lds_bytes = lds + stage_quads * 16;
+    if ((rc = chain_place_staging(c->args, n_ops, ops, base4, CHAIN_LDS_BYTES / 16, &stage_end4))) return rc;
+    c->lds_bytes = lds + (stage_end4 - base4) * 16;
+    c->desc = chain_describe(c.get());
     KN_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(chain_kernel<false>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)CHAIN_LDS_BYTES));
+#ifdef KN_HOST_PACK_ONLY
+    chain_trace_scalars(c.get());
+#endif
     *rows_out = ops[n_ops - 1]->rows;
     *cols_out = ops[0]->cols;
     *nnz_out = nnz;
@@ -1316,20 +1407,8 @@ int chain_forward(const ChainDev* c, const float* x, int64_t ldx, int64_t n_vecs
         if (n_stamps > (size_t)grid * 16) a.wstamps = a.stamps + (size_t)grid * 16;
     }
 #endif
-    int n_thin = 0, n_cl = 0, n_rpl2 = 0, n_early = 0, n_seq = 0;
-    for (int l = 0; l < a.n_layers; l++) {
-        n_seq += a.L[l].seq_len > 0 ? 1 : 0;
-        n_thin += (a.L[l].cols_quads > 0 || a.L[l].seq_len > 0) ? 1 : 0;
-        n_cl += a.L[l].cols_quads < 0 ? 1 : 0;
-        n_rpl2 += a.L[l].rpl == 2 ? 1 : 0;
-        n_early += (a.L[l].cols_quads != 0 && a.L[l].early) ? 1 : 0;
-    }
-    const std::string d = "chain_kernel<" + std::to_string(a.n_layers) + " operators (" + std::to_string(n_thin) + " on the thin walk -- " + std::to_string(n_seq) + " of them sequentially, " + std::to_string(n_cl) +
-                          " with column patterns in LDS), " + std::to_string(n_rpl2) + " with two rows per lane, " + std::to_string(n_early) +
-                          " column pools staged a layer early, 4 batch columns per workgroup, " + std::to_string(c->lds_bytes) + " B LDS, " + std::to_string(c->stream_bytes) +
-                          " B of operator words per workgroup from L2>";
-    if (2 * c->lds_bytes > CHAIN_LDS_BYTES) KN_LAUNCH(d, chain_kernel<true>, dim3((unsigned)grid), dim3(CHAIN_THREADS), 0, s, a);       // one workgroup per CU either way
-    else KN_LAUNCH(d, chain_kernel<false>, dim3((unsigned)grid), dim3(CHAIN_THREADS), c->lds_bytes, s, a);
+    if (2 * c->lds_bytes > CHAIN_LDS_BYTES) KN_LAUNCH(c->desc, chain_kernel<true>, dim3((unsigned)grid), dim3(CHAIN_THREADS), 0, s, a);       // one workgroup per CU either way
+    else KN_LAUNCH(c->desc, chain_kernel<false>, dim3((unsigned)grid), dim3(CHAIN_THREADS), c->lds_bytes, s, a);
     KN_HIP(hipGetLastError());
 #ifdef KN_ABLATION
     if (a.stamps) {

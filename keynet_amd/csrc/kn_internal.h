@@ -25,7 +25,8 @@ namespace kn {
 namespace hostonly {
 // KN_UPLOAD_TRACE=<file>: every host-to-"device" copy appends one line -- element size, element count, 64-bit FNV-1a of the bytes -- and every kn_*_create
 // entry (they all open with a device query) one blank line, so two builds pack an operator alike when the blocks between blank lines are equal as multisets
-// (profiles/csr_host_before_after.txt).  An empty array (upload() zero-fills one element for it) is a line with count 0.
+// (profiles/csr_host_before_after.txt).  An empty array (upload() zero-fills one element for it) is a line with count 0.  What reaches a kernel BY VALUE is
+// appended as text (trace_text: kn_chain.hip writes the scalars of its ChainArgs, one line per layer record and one for the chain).
 template <typename T> inline size_t elem_size(T*) { return sizeof(T); }
 inline size_t elem_size(void*) { return 1; }
 inline size_t elem_size(const void*) { return 1; }
@@ -44,6 +45,14 @@ inline void trace_write(bool blank, size_t elem, size_t count, const void* p) {
     }
     std::fclose(f);
     after_blank = blank;
+}
+inline void trace_text(const std::string& line) {
+    const char* path = std::getenv("KN_UPLOAD_TRACE");
+    if (!path || !*path) return;
+    if (std::FILE* f = std::fopen(path, "a")) {
+        std::fprintf(f, "%s\n", line.c_str());
+        std::fclose(f);
+    }
 }
 inline hipError_t Malloc(void** p, size_t n) {
     *p = std::malloc(n ? n : 1);

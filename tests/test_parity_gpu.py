@@ -1120,12 +1120,12 @@ def test_whole_net_kernel_layout_choices_vs_oracle():
             ip.append(len(ix))
         return (np.array(ip, np.int32), np.array(ix, np.int32), np.array(dt, np.float32))
 
-    def dense(rows, cols):
-        perm = rng.permutation(cols)
+    def dense(rows, cols, seq_len=None):
+        perm = rng.permutation(cols)[:seq_len]
         (ip, ix, dt) = ([0], [], [])
         for r in range(rows):
             ix.extend(int(v) for v in perm)
-            dt.extend(rng.randn(cols).astype(np.float32))
+            dt.extend(rng.randn(len(perm)).astype(np.float32))
             ip.append(len(ix))
         return (np.array(ip, np.int32), np.array(ix, np.int32), np.array(dt, np.float32))
 
@@ -1188,6 +1188,20 @@ def test_whole_net_kernel_layout_choices_vs_oracle():
     # (found by the fuzzer's keyed-Linear layers in round 6: a memory access fault 2.8 MB behind the array)
     run([((336, 2184), dense_plus(336, 2184, 9), 0), ((50, 336), dense_plus(50, 336, 1), 1)],
         '2 operators (1 on the thin walk -- 1 of them sequentially, 1 with column patterns in LDS)')
+    # a thin first operator whose column pool would be staged twice: 704 quads, 22.5 KB for the two copies, beside 9 000 + 70 + 1 activations that leave 18.7 KB -- columns
+    # from memory (general walk)
+    run([((70, 9000), dense(70, 9000, 2800), 0)], '1 operators (0 on the thin walk -- 0 of them sequentially, 0 with column patterns in LDS)')
+    # two rows per lane tried and dropped: the 64 rows of one 400-column pattern fill a slice at one row per lane; at two they leave half of it to 32 four-column patterns, each
+    # then stored at 100 quads -- a pool of 4 772 quads against 3 175 of room, where the pool of one row per lane takes 1 604
+    def pairs():
+        short = rng.randint(0, 4000, size=(1500, 4))
+        row_cols = [rng.randint(0, 4000, size=400)] * 64 + [c for c in short for _ in range(2)]
+        ip = np.concatenate(([0], np.cumsum([len(c) for c in row_cols]))).astype(np.int32)
+        return (ip, np.concatenate(row_cols).astype(np.int32), rng.randn(ip[-1]).astype(np.float32))
+    run([((3064, 4000), pairs(), 1)], '1 operators (0 on the thin walk -- 0 of them sequentially, 1 with column patterns in LDS), 0 with two rows per lane, 1 column pools staged')
+    # two pattern pools (2 504 and 3 004 quads) that fit beside the activations (5 239 quads of room) one at a time only: the second is staged at the start of its own layer
+    run([((2000, 3000), grouped(2000, 3000, 8, 40, 0), 1), ((400, 2000), grouped(400, 2000, 8, 240, 0), 0)],
+        '2 operators (0 on the thin walk -- 0 of them sequentially, 2 with column patterns in LDS), 1 with two rows per lane, 1 column pools staged a layer early')
 
 
 def test_whole_net_kernel_shares_value_sequences_between_pixels():

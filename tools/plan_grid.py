@@ -3,7 +3,9 @@
 Loads the library named by KEYNET_HIP_LIB (default: the product library) through keynet_amd/_capi.py WITHOUT torch, creates a fixed list of operators and
 prints, per operator, kn_nnz / kn_nnz_expanded / a hash of kn_export_csr and one line per (n_vecs, ldx = ldy, flags) with the text of kn_spmm_plan; the
 batches include 1, 2, 3, 4, 8 and 9 columns and the flags the three narrow ones (KN_FLAG_NARROW, _MFMA, _ROWS).  Float32 CSR operators close the list: three at every flag word, then (csr_cases) the shapes that reach
-every launch site of the three CSR sources, a kn_tiled_create operator and a kn_chain_create handle, at the flags a CSR handle reads (--csr: these alone).  Nothing is
+every launch site of the three CSR sources, a kn_tiled_create operator and a kn_chain_create handle, at the flags a CSR handle reads (--csr: these alone); last
+(chain_cases) the operator stacks the whole-net kernel's GPU tests run, as kn_chain_create handles (--chain: these alone; the KN_CHAIN_NO_* knobs of a -DKN_ABLATION
+build are set in the environment of the whole run).  Nothing is
 launched, so the KN_HOST_PACK_ONLY build answers on a machine without a GPU.  Two builds of the library dispatch alike when their outputs are byte-identical:
 
     KEYNET_HIP_LIB=/path/to/libkeynet_hip.so python tools/plan_grid.py > grid.txt
@@ -198,10 +200,122 @@ def csr_operators(out):
     report('chain lenet_perm', capi.Operator.chain(ops, [capi.KN_FLAG_RELU] * (len(ops) - 1) + [0]), out, export=False, flags=CSR_FLAGS)
 
 
+# ---- kn_chain_create handles: every layer decision of kn_chain.hip's packer (chain_choose_walk, chain_place_staging) ----
+CHAIN_BATCHES = (1, 3, 4, 5, 37, 1024)          # the plan text depends on the batch through the grid alone
+
+
+def _csr_arrays(row_cols, rng, row_vals=None):
+    """(indptr, indices, data) from per-row column sequences, stored order as given; N(0, 1) values unless `row_vals` gives them."""
+    indptr = np.concatenate(([0], np.cumsum([len(c) for c in row_cols]))).astype(np.int32)
+    indices = (np.concatenate(row_cols) if indptr[-1] else np.zeros(0)).astype(np.int32)
+    data = np.concatenate(row_vals).astype(np.float32) if row_vals is not None else rng.randn(len(indices)).astype(np.float32)
+    return (indptr, indices, data)
+
+
+def chain_grouped(rng, rows, cols, group, nnz, tail_loose):
+    """Conv-like: groups of `group` rows over one unsorted sequence of `nnz` columns (duplicates allowed), `tail_loose` short rows of their own at the end."""
+    (rc, shared) = ([], None)
+    for r in range(rows):
+        if r >= rows - tail_loose:
+            rc.append(rng.randint(0, cols, size=rng.randint(1, 6)))
+        else:
+            if r % group == 0:
+                shared = rng.randint(0, cols, size=nnz)
+            rc.append(shared)
+    return _csr_arrays(rc, rng)
+
+
+def chain_dense(rng, rows, cols, n_other=0, seq_len=None):
+    """A keyed Linear: `rows - n_other` rows over one sequence of `seq_len` (default: all) distinct columns, `n_other` rows of 1 .. 3 columns of their own behind them."""
+    perm = rng.permutation(cols)[:seq_len]
+    return _csr_arrays([perm] * (rows - n_other) + [rng.choice(cols, size=rng.randint(1, 4), replace=False) for _ in range(n_other)], rng)
+
+
+def chain_random(rng, rows, cols, kind):
+    """The layers of the random stack: 'grouped' (a new sequence of 1 .. 39 columns every 7 rows), 'dense' (one permutation, a row in eleven an entry short),
+    'loose' (0 .. 13 random columns per row, duplicates and empty rows among them)."""
+    (rc, shared) = ([], None)
+    for r in range(rows):
+        if kind == 'grouped':
+            if r % 7 == 0:
+                shared = rng.randint(0, cols, size=rng.randint(1, 40))
+            rc.append(shared)
+        elif kind == 'dense':
+            if shared is None:
+                shared = rng.permutation(cols)
+            rc.append(shared if r % 11 else shared[:-1])
+        else:
+            rc.append(rng.randint(0, cols, size=(0 if r % 13 == 5 else rng.randint(1, 14))))
+    return _csr_arrays(rc, rng)
+
+
+def chain_pixels(rng, shared_values, pixels=600, ch=8, nnz=22, cols=500):
+    """`pixels` column sequences of `ch` rows each, the rows in a random order; shared_values: every pixel carries the same `ch` value sequences, permuted per pixel."""
+    base_vals = rng.randn(ch, nnz).astype(np.float32)
+    order = rng.permutation(pixels * ch)
+    pat = [rng.randint(0, cols, size=nnz) for _ in range(pixels)]
+    rows = [None] * (pixels * ch)
+    for p in range(pixels):
+        perm_ch = rng.permutation(ch)
+        for c in range(ch):
+            rows[order[p * ch + c]] = (pat[p], base_vals[perm_ch[c]] if shared_values else rng.randn(nnz).astype(np.float32))
+    return _csr_arrays([r[0] for r in rows], rng, [r[1] for r in rows])
+
+
+def chain_cases():
+    """(name, [((rows, cols), (indptr, indices, data), relu), ...]): the operator stacks of tests/test_parity_gpu.py's test_whole_net_kernel_* tests, restated."""
+    rng = np.random.RandomState(103)
+    yield ('chain random', [((r, c), chain_random(rng, r, c, kind), relu)
+                            for (r, c, kind, relu) in ((301, 97, 'grouped', 1), (150, 301, 'loose', 0), (70, 150, 'dense', 1), (33, 70, 'dense', 1), (9, 33, 'dense', 0))])
+    rng = np.random.RandomState(7)
+    (G, D) = (lambda *a: chain_grouped(rng, *a), lambda *a: chain_dense(rng, *a))
+    yield ('chain pattern pools', [((645, 200), G(645, 200, 6, 11, 5), 1), ((130, 645), G(130, 645, 16, 50, 2), 0), ((70, 130), D(70, 130), 1), ((10, 70), D(10, 70), 0)])
+    yield ('chain keyed linears', [((645, 200), G(645, 200, 6, 11, 5), 1), ((131, 645), G(131, 645, 16, 50, 2), 0), ((121, 131), D(121, 131, 1), 1), ((85, 121), D(85, 121, 3), 1),
+                                   ((11, 85), D(11, 85, 1), 0)])
+    yield ('chain linear first', [((70, 130), D(70, 130), 1), ((10, 70), D(10, 70, 1), 0)])
+    yield ('chain pool does not fit', [((4100, 4200), G(4100, 4200, 6, 110, 2), 1), ((64, 4100), G(64, 4100, 8, 9, 0), 0)])
+    yield ('chain two rows per lane 6 16', [((2051, 300), G(2051, 300, 6, 11, 5), 1), ((1300, 2051), G(1300, 2051, 1, 7, 0), 0), ((1609, 1300), G(1609, 1300, 16, 50, 9), 1),
+                                            ((90, 1609), D(90, 1609), 1), ((10, 90), D(10, 90), 0)])
+    yield ('chain two rows per lane 11', [((1500, 257), G(1500, 257, 11, 13, 1), 0), ((33, 1500), D(33, 1500), 0)])
+    yield ('chain linear 336x2184 first', [((336, 2184), D(336, 2184, 9), 0), ((50, 336), D(50, 336, 1), 1)])
+    # a thin first operator whose two pool copies do not fit beside 9 000 + 70 + 1 activations: 704 quads twice = 22.5 KB against 18.7 KB of room (at 8 600 columns they fit)
+    yield ('chain thin pool does not fit', [((70, 9000), D(70, 9000, 0, 2800), 0)])
+    yield ('chain thin pool fits', [((70, 8600), D(70, 8600, 0, 2800), 0)])
+    # two rows per lane tried and dropped: 64 rows of one 400-column pattern fill a slice of their own at one row per lane; at two they leave half of it to 32 four-column
+    # patterns, each then stored at 100 quads -- 4 772 quads against 3 175 of room, where the one-row pool takes 1 604
+    yield ('chain two rows per lane do not fit', [((3064, 4000), _csr_arrays([rng.randint(0, 4000, size=400)] * 64 + [c for c in rng.randint(0, 4000, size=(1500, 4)) for _ in range(2)], rng), 1)])
+    # two pattern pools that fit beside the activations one at a time only: the second is staged at the start of its own layer
+    yield ('chain pool staged late', [((2000, 3000), G(2000, 3000, 8, 40, 0), 1), ((400, 2000), G(400, 2000, 8, 240, 0), 0)])
+    rng = np.random.RandomState(21)
+    for shared_values in (True, False):
+        yield ('chain pixels shared_values=%d' % shared_values, [((4800, 500), chain_pixels(rng, shared_values), 1)])
+    rng = np.random.RandomState(29)
+    yield ('chain 0 rows', [((0, 7), _csr_arrays([], rng), 0)])
+    yield ('chain empty rows', [((5, 7), _csr_arrays([np.zeros(0, np.int64)] * 5, rng), 1)])
+
+
+def chain_operators(out):
+    L = capi.lib()
+    buf = ctypes.create_string_buffer(4096)
+    for (name, layers) in chain_cases():
+        try:
+            ops = [capi.Operator.csr(shape, ip, ix, dt) for (shape, (ip, ix, dt), relu) in layers]
+            chain = capi.Operator.chain(ops, [capi.KN_FLAG_RELU if relu else 0 for (shape, csr, relu) in layers])
+        except capi.KeynetHipError as e:
+            out.write('%s: %s\n' % (name, e))
+            continue
+        out.write('%s shape=%s nnz=%d\n' % (name, chain.shape(), chain.nnz()))
+        for n in CHAIN_BATCHES:
+            rc = L.kn_spmm_plan(chain.handle, n, n, n, capi.KN_FLAG_EXACT, buf, 4096)
+            out.write('%s n=%d: %s\n' % (name, n, buf.value.decode() if rc == 0 else 'rc=%d %s' % (rc, L.kn_last_error().decode())))
+
+
 def main():
     out = sys.stdout
     if '--csr' in sys.argv[1:]:
         return csr_operators(out)
+    if '--chain' in sys.argv[1:]:
+        return chain_operators(out)
     golden_conv2dtiled(out)
     for cin in (3, 5, 16, 32, 64):
         for cout in (7, 64, 128, 192):
@@ -235,6 +349,7 @@ def main():
         M = M.astype(np.float32)
         report(name, capi.Operator.csr(M.shape, M.indptr.astype(np.int32), M.indices.astype(np.int32), M.data), out, export=False)
     csr_operators(out)
+    chain_operators(out)
 
 
 if __name__ == '__main__':
