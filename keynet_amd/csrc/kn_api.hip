@@ -233,24 +233,27 @@ static void convtaps_pt_eligibility(kn_operator* h, const SlotLists& sl) {
     c.pt_ok = true;
 }
 
-// ... and its records (layout: kn_conv.hip PtRec), built from the handle's host description at the first kn_spmm that asks for them; the caller holds lazy_mu
+// ... and its records (PtRec, kn_internal.h), built from the handle's host description at the first kn_spmm that asks for them; the caller holds lazy_mu
 int convtaps_build_pt(kn_operator* h) {
     ConvTapsDev& c = h->ct;
     if (c.pt_rec || !c.pt_ok) return KN_OK;
     const int64_t HoWo = c.Hout * c.Wout;
     const SlotLists sl = convtaps_slot_lists(h);
-    std::vector<int32_t> rec((size_t)(HoWo * c.ntaps * 4), 0);
-    for (size_t k = 0; k < rec.size(); k += 2) rec[k] = -1;
+    std::vector<PtRec> rec((size_t)(HoWo * c.ntaps), PtRec{-1, 0.0f, -1, 0.0f});
     for (int64_t o = 0; o < HoWo; o++)
         for (int64_t s = sl.pix_ptr[(size_t)o]; s < sl.pix_ptr[(size_t)o + 1]; s++) {
             const size_t e = sl.order[(size_t)s];
-            int32_t* r = rec.data() + (size_t)((o * c.ntaps + h->h_ent_tap[e]) * 4);
-            if (r[0] >= 0) r += 2;                          // the pair's second slot (entry order is kept: ascending input pixel)
-            KN_REQUIRE(r[0] < 0, KN_ERR_INVALID, "more slots on one (output pixel, tap) pair than the record holds");
-            r[0] = h->h_ent_in[e];
-            std::memcpy(r + 1, &h->h_ent_coef[e], sizeof(float));
+            PtRec& r = rec[(size_t)(o * c.ntaps + h->h_ent_tap[e])];
+            KN_REQUIRE(r.in0 < 0 || r.in1 < 0, KN_ERR_INVALID, "more slots on one (output pixel, tap) pair than the record holds");
+            if (r.in0 < 0) {
+                r.in0 = h->h_ent_in[e];
+                r.c0 = h->h_ent_coef[e];
+            } else {                                        // the pair's second slot (entry order is kept: ascending input pixel)
+                r.in1 = h->h_ent_in[e];
+                r.c1 = h->h_ent_coef[e];
+            }
         }
-    int32_t* d = nullptr;
+    PtRec* d = nullptr;
     int rc = upload(&d, rec.data(), rec.size());
     if (rc) return rc;
     __atomic_store_n(&c.pt_rec, d, __ATOMIC_RELEASE);       // upload() is a synchronous copy: the records are in HBM before the pointer is visible
@@ -276,41 +279,41 @@ static int64_t convtaps_expanded_nnz(const kn_operator* h, const SlotLists& sl) 
     return n_pairs * c.Cout * c.Cin + (int64_t)h->h_last_rows.size();
 }
 
-// small-K pipeline descriptors (layout: kn_conv.hip SK_DESC_HDR): eligible when one pixel's whole contraction (slots x Cin + bias
-// row) fits 28 rows, one 64-wide Cout tile covers the layer and the tap matrix fits its LDS table
+// small-K pipeline descriptors (layout: kn_internal.h, SK_DESC_HDR): eligible when one pixel's whole contraction (slots x Cin + bias
+// row) fits SMALLK_MAX rows, one 64-wide Cout tile covers the layer and the tap matrix fits its LDS table
 static std::vector<int32_t> convtaps_smallk_desc(kn_operator* h, const SlotLists& sl, const std::vector<float>& lastcol) {
     ConvTapsDev& c = h->ct;
     const int64_t Cin = c.Cin, Cout = c.Cout, ntaps = c.ntaps, HoWo = c.Hout * c.Wout, HiWi = c.Hin * c.Win;
     std::vector<int32_t> sk_desc;
-    if ((int64_t)c.max_slots * Cin + (c.has_last ? 1 : 0) <= 28 && Cout == 64 && c.cout_pad == 64 && ntaps * c.cin_pad <= 61 && h->cols < INT32_MAX - 1) {
-        const int64_t stride = 96 + c.cout_pad;
-        const int32_t zero_off = (int32_t)(ntaps * c.cin_pad * 64);
+    if ((int64_t)c.max_slots * Cin + (c.has_last ? 1 : 0) <= SMALLK_MAX && Cout == SK_TAB_ROW && c.cout_pad == SK_TAB_ROW && ntaps * c.cin_pad <= SK_TAB_MAX && h->cols < INT32_MAX - 1) {
+        const int64_t stride = SK_DESC_HDR + c.cout_pad;
+        const int32_t zero_off = (int32_t)(ntaps * c.cin_pad * SK_TAB_ROW);
         sk_desc.assign((size_t)(HoWo * stride), 0);
         for (int64_t pi = 0; pi < HoWo; pi++) {
             const int32_t o = h->h_pix_order[(size_t)pi];
             int32_t* d = sk_desc.data() + (size_t)(pi * stride);
             float* df = reinterpret_cast<float*>(d);
-            for (int k = 0; k < 32; k++) {
-                d[k] = -1;
-                d[32 + k] = zero_off;
-                df[64 + k] = 0.0f;
+            for (int k = 0; k < 32; k++) {                 // (a section is 32 dwords: one per lane of a half wavefront)
+                d[SK_DESC_XROW + k] = -1;
+                d[SK_DESC_TAPOFF + k] = zero_off;
+                df[SK_DESC_COEF + k] = 0.0f;
             }
             int k = 0;
             for (int64_t sl_i = sl.pix_ptr[(size_t)o]; sl_i < sl.pix_ptr[(size_t)o + 1]; sl_i++) {
                 const size_t e = sl.order[(size_t)sl_i];
                 for (int64_t ci = 0; ci < Cin; ci++, k++) {
-                    d[k] = (int32_t)(ci * HiWi + h->h_ent_in[e]);
-                    d[32 + k] = (int32_t)((h->h_ent_tap[e] * c.cin_pad + ci) * 64);
-                    df[64 + k] = h->h_ent_coef[e];
+                    d[SK_DESC_XROW + k] = (int32_t)(ci * HiWi + h->h_ent_in[e]);
+                    d[SK_DESC_TAPOFF + k] = (int32_t)((h->h_ent_tap[e] * c.cin_pad + ci) * SK_TAB_ROW);
+                    df[SK_DESC_COEF + k] = h->h_ent_coef[e];
                 }
             }
             if (c.has_last) {
-                d[k] = (int32_t)(Cin * HiWi);             // homogeneous coordinate of X against the bias row
-                d[32 + k] = zero_off + 64;                 // marker: "this buffer's bias row"
-                df[64 + k] = 1.0f;
-                for (int64_t m = 0; m < Cout; m++) df[96 + m] = lastcol[(size_t)(m * HoWo + o)];
+                d[SK_DESC_XROW + k] = (int32_t)(Cin * HiWi);             // homogeneous coordinate of X against the bias row
+                d[SK_DESC_TAPOFF + k] = zero_off + SK_TAB_ROW;            // marker: "this buffer's bias row"
+                df[SK_DESC_COEF + k] = 1.0f;
+                for (int64_t m = 0; m < Cout; m++) df[SK_DESC_HDR + m] = lastcol[(size_t)(m * HoWo + o)];
             }
-            d[31] = o;
+            d[SK_DESC_PIX] = o;
         }
         c.sk_stride = stride;
         c.sk_tab_rows = ntaps * c.cin_pad;
@@ -969,12 +972,14 @@ static int spmm_impl(kn_handle_t h, const float* x_dev, int64_t ldx, int64_t n_v
         if (rc) return rc;
         rc = dense_reduce(ws, n_vecs, outs, S, h->dense_lastcol, x_dev + (h->cols - 1) * ldx, y_dev, ldy, n_vecs, (flags & KN_FLAG_RELU) ? 1 : 0, s);
     } else {
-        // KN_FLAG_EXACT is honoured inside convtaps_spmm by the order-preserving kernel on the factored operator
-        // KN_FLAG_NARROW on at most 8 columns takes the channel-lane kernel, which reads the slot lists themselves: no side table is built for it
-        const bool narrow = narrow_call(flags, n_vecs);
-        if (narrow_mfma_call(h->ct, flags, n_vecs) && (rc = first_use(h, h->ct.pt_rec, [&] { return convtaps_build_pt(h); }))) return rc;
-        if (!narrow && (flags & KN_FLAG_BF16X3) && !(flags & KN_FLAG_EXACT) && (rc = first_use(h, h->ct.tapsB, [&] { return convtaps_build_bf16(h->ct, h->h_taps); }))) return rc;
-        if (!narrow && (flags & KN_FLAG_EXACT) && convtaps_fill_ok(h->ct) && (rc = first_use(h, h->ct.fill_rec, [&] { return convtaps_build_fill(h->ct, s); }))) return rc;
+        // the side table the call's regime reads, built at its first use (the channel-lane kernels read the slot lists themselves, the f32 matrix-core kernels the taps)
+        switch (conv_regime(h->ct, flags, n_vecs)) {
+            case NARROW_MFMA: rc = first_use(h, h->ct.pt_rec, [&] { return convtaps_build_pt(h); }); break;
+            case BF16X3: rc = first_use(h, h->ct.tapsB, [&] { return convtaps_build_bf16(h->ct, h->h_taps); }); break;
+            case EXACT: if (convtaps_fill_ok(h->ct)) rc = first_use(h, h->ct.fill_rec, [&] { return convtaps_build_fill(h->ct, s); }); break;
+            default: break;
+        }
+        if (rc) return rc;
         rc = convtaps_spmm(h->ct, x_dev, ldx, n_vecs, y_dev, ldy, flags, s, absmax, &fused);
     }
     if (rc) return rc;
@@ -1035,15 +1040,15 @@ int kn_release_side_tables(kn_handle_t h) {
     KN_REQUIRE(h != nullptr, KN_ERR_INVALID, "NULL handle");
     if (h->kind != KIND_CONVTAPS) return KN_OK;
     std::lock_guard<std::mutex> g(h->lazy_mu);
-    int32_t* rec = __atomic_load_n(&h->ct.fill_rec, __ATOMIC_ACQUIRE);
+    FillRec* rec = __atomic_load_n(&h->ct.fill_rec, __ATOMIC_ACQUIRE);
     uint16_t* tb = __atomic_load_n(&h->ct.tapsB, __ATOMIC_ACQUIRE);
-    int32_t* pt = __atomic_load_n(&h->ct.pt_rec, __ATOMIC_ACQUIRE);
+    PtRec* pt = __atomic_load_n(&h->ct.pt_rec, __ATOMIC_ACQUIRE);
     if (!rec && !tb && !pt) return KN_OK;
     if (int rc = check_device(h, "")) return rc;
     KN_HIP(hipDeviceSynchronize());                               // a launch on ANY stream may still be reading the tables (rare call: a layer changed its contract)
-    __atomic_store_n(&h->ct.fill_rec, (int32_t*)nullptr, __ATOMIC_RELEASE);
+    __atomic_store_n(&h->ct.fill_rec, (FillRec*)nullptr, __ATOMIC_RELEASE);
     __atomic_store_n(&h->ct.tapsB, (uint16_t*)nullptr, __ATOMIC_RELEASE);
-    __atomic_store_n(&h->ct.pt_rec, (int32_t*)nullptr, __ATOMIC_RELEASE);
+    __atomic_store_n(&h->ct.pt_rec, (PtRec*)nullptr, __ATOMIC_RELEASE);
     if (pt) (void)hipFree(pt);
     if (rec) (void)hipFree(rec);
     if (tb) (void)hipFree(tb);

@@ -917,8 +917,6 @@ __global__ __launch_bounds__(256, 2) void convtaps_bf16x3_kernel(ConvArgs p) {
 // K = slots*Cin + 1 (bias via the homogeneous row) <= 28 rows, while the output tile is 64 x 256 floats -- the layer is
 // bound by its 3.3 GB of output writes, not by MFMA.  So no chunk loop: gather all K activation rows and tap rows into
 // LDS once, one barrier, K/2 MFMA steps per wavefront, wide store.  Four workgroups per CU overlap each other's phases.
-constexpr int SMALLK_MAX = 28;
-
 __global__ __launch_bounds__(256, 4) void convtaps_smallk_kernel(ConvArgs p) {
     constexpr int MT = 64, NB = 256, TM = 2, TN = 2, KM = SMALLK_MAX;
     __shared__ __attribute__((aligned(16))) float lds[KM * MT + KM * NB];
@@ -1028,9 +1026,6 @@ __global__ __launch_bounds__(256, 4) void convtaps_smallk_kernel(ConvArgs p) {
 // output pixel, bias values.  The tap matrix of the layer (9 x 3 x 64 floats for VGG conv1_1) stays resident in LDS for the
 // workgroup's lifetime, so the A operand is never re-staged: fragments are read straight from the table through the descriptor's
 // row offsets.
-constexpr int SK_DESC_HDR = 96;       // dwords: [0..27] X row (-1 = none), [31] output pixel, [32..59] tap-row LDS offset, [64..91] coefficient
-constexpr int SK_TAB_MAX = 61;        // tap-table rows that fit the LDS budget (+1 zero row, +2 bias rows = 16 KiB)
-
 __global__ __launch_bounds__(256, 2) void convtaps_smallk_pipe_kernel(ConvArgs p) {
     constexpr int MT = 64, NB = 256, TM = 2, TN = 2, KM = SMALLK_MAX, KR = KM / 4;
     __shared__ __attribute__((aligned(16))) float lds[2 * KM * NB + (SK_TAB_MAX + 3) * MT];
@@ -1433,7 +1428,7 @@ __global__ __launch_bounds__(256) void convtaps_narrow_kernel(ConvArgs p, int n_
 // convtaps_narrow_kernel's work item and arithmetic, statement for statement (input channel outer, the pixel's slots by ascending input pixel inner, DUPS committed
 // when the walk reaches the next pixel pair, separate multiply and add, the bias entry where it is stored, ReLU), with three differences of FORM:
 //   * work items are (column block, channel block, pixel), pixel fastest: a wavefront owns the NV (8 | 16 | 32) columns c0 = block * NV ..
-//     of its pixel and channel block.  Columns are independent sums, so the blocking cannot change a bit; which width runs is spmm_narrow32's rule.
+//     of its pixel and channel block.  Columns are independent sums, so the blocking cannot change a bit; which width runs is narrow_choice's rule.
 //   * a block that the batch does not fill (nh < NV real columns: widths 9 .. 15, 17 .. 31 and the last block of the others) still fetches a step's activations as
 //     ONE segment of NV dwords at X + xo + c0 through the scalar cache.  The segment lies inside the caller's block whenever xo + c0 + NV <= the block's minimal
 //     extent (last row) * ldx + n_vecs, and because a pixel's slots ascend by input pixel that is tested ONCE per wavefront on the last channel's last slot: with a
@@ -1668,14 +1663,6 @@ __global__ __launch_bounds__(256) void convtaps_narrow32_kernel(ConvArgs p, int 
 // unit after that is in flight meanwhile; nothing in the loop waits on LDS or a barrier.  Epilogue: the last-column (bias x homogeneous row) term where it
 // is stored, ReLU, one store per element straight from the accumulator layout (32 lanes = 32 columns of one output channel).  Element offsets into tapsT
 // and X are 32-bit (checked by the launcher: KN_FLAG_NARROW's size rule), rows of Y are formed in 64 bits.
-struct PtRec {
-    int32_t in0;       // input pixel of the first slot of this (output pixel, tap), or -1
-    float c0;
-    int32_t in1;       // ... of the second one, or -1
-    float c1;
-};
-static_assert(sizeof(PtRec) == 16, "one 16-byte load per record");
-
 template <int TM, bool S2, bool COEF>
 __global__ __launch_bounds__(256) void convtaps_narrow_mfma_kernel(ConvArgs p, const PtRec* __restrict__ pt, int nv_log2, int n_nt, int64_t n_wg) {
     typedef float f32x16 __attribute__((ext_vector_type(16)));
@@ -1825,12 +1812,6 @@ __global__ __launch_bounds__(256) void convtaps_narrow_mfma_kernel(ConvArgs p, c
 // columns c0 + 2 l, c0 + 2 l + 1 of a slot's activation row with ONE 8-byte load; the stored value of a column -- formed once, as before -- multiplies both column tiles: two (four)
 // matrix instructions and twice the packed adds per stored column for the SAME slot bookkeeping, which is what separates this kernel from the no-FMA roof.
 // Two result blocks alternate, so a block's adds sit behind the next block's matrix instruction instead of waiting for their own.
-struct FillRec {
-    int32_t in, tapoff;     // tapoff: offset of the tap's plane in tapsT (floats), or the tap index (TREG)
-    float coef;
-    int32_t flags;          // bit 0: first slot of a stored column, bit 1: last
-};
-
 __global__ __launch_bounds__(256) void convtaps_fill_records_kernel(const int32_t* __restrict__ pix_ptr, const int32_t* __restrict__ fill_ptr, const int32_t* __restrict__ slot_in,
                                                                     const int32_t* __restrict__ slot_tap, const float* __restrict__ slot_coef, int unit_coef, int tap_stride /* 1: tap index (TREG) */,
                                                                     int HoWo, FillRec* __restrict__ rec) {
@@ -2515,95 +2496,6 @@ static unsigned lds_pad_for_occupancy(size_t static_lds, int want) {
     return (static_lds + pad <= 64 * 1024) ? (unsigned)pad : 0;     // beyond 64 KiB per workgroup needs a function attribute: not used
 }
 
-template <int MT, int NB, int KC, int WM, int WN>
-static void launch_conv(ConvArgs a, const Tuning& tune, hipStream_t s) {
-    const int64_t items = (int64_t)a.n_pix * a.n_bt * a.n_mt;
-    const int64_t chunk = (items + 7) / 8;
-    constexpr size_t static_lds = sizeof(float) * (2 * KC * MT + 2 * KC * NB + 4 * MAX_FAST_SLOTS + 2 * (MT + NB));
-    // Workgroups per CU.  All of a launch's workgroups take the same time, so a launch proceeds in "rounds" of the resident set; with
-    // only a few rounds (VGG conv5_x: 196 items per XCD = 1.53 rounds of 128) a third of the work would fall into the last, partial
-    // round.  Three workgroups per CU run as fast as four on the long layers (-1.5 %), and 196 items = 2.04 rounds of 96: when a
-    // launch has fewer than four rounds, the resident set whose partial round is the smaller fraction wins (measured on conv5_x:
-    // 122.9 -> 125.4 TFLOP/s, same-process A/B).  Tuning::occ forces a cap (diagnostic build).
-    int occ_cap = tune.occ;
-    if (occ_cap == 0 && MT == 128 && NB == 128 && KC == 16) {
-        const double r4 = (double)chunk / 128.0, r3 = (double)chunk / 96.0;
-        const double f4 = r4 - (double)(int64_t)r4, f3 = r3 - (double)(int64_t)r3;
-        if (r4 < 4.0 && f4 > 0.0 && f3 < f4) occ_cap = 3;
-    }
-    const unsigned pad = lds_pad_for_occupancy(static_lds, occ_cap);
-    auto D = [&](const char* loader, bool tail) {        // evaluated only by kn_spmm_plan
-        char b[200];
-        snprintf(b, sizeof(b), "convtaps_mfma_kernel<MT=%d,NB=%d,KC=%d> loader=%s%s%s occ_cap=%d", MT, NB, KC, loader, a.unit_coef ? "" : "+coef",
-                 tail ? " tail_split" : "", occ_cap);
-        return std::string(b);
-    };
-    const bool fast_shape = a.vec_ok && (a.n_vecs % NB == 0) && ((int64_t)KC * a.HiWi * a.ldx < (int64_t)1 << 31) &&      // (any number of slots per pixel: slot groups)
-                            (int64_t)a.HiWi * a.ldx < (int64_t)1 << 31 && (int64_t)a.ntaps * a.cin_pad * a.cout_pad < (int64_t)1 << 31;
-    const bool fast = fast_shape && a.unit_coef && (a.Cin % KC == 0 || a.Cin < KC) && a.max_slots <= MAX_FAST_SLOTS;
-    // scalar-pointer loaders (MODE 2): 16-row chunks of whole channels, a thread's offsets inside one chunk in 31 bits.  Tuning::no_sptr
-    // (KN_NO_SPTR=1 when the operator is created) keeps the other loaders for the parity tests' side-by-side.
-    bool sptr = false;
-    if constexpr (KC == 16) sptr = fast_shape && a.Cin % 16 == 0 && 4 * ((int64_t)(1024 / NB) * a.HiWi * a.ldx + NB) < (int64_t)1 << 31 && !tune.no_sptr;
-    a.tail_main = (int32_t)chunk;
-    if constexpr (MT == 128 && NB == 128 && KC == 16) {
-        if ((fast || sptr) && a.wide_store && !tune.no_tail_split && a.max_slots <= MAX_FAST_SLOTS) {
-            // resident workgroups per XCD of the instantiation that is actually launched (the two loader modes may differ in registers)
-            static const int64_t slots_free_1 = xcd_slots(convtaps_mfma_kernel<MT, NB, KC, WM, WN, 1, true>);
-            static const int64_t slots_free_2 = xcd_slots(convtaps_mfma_kernel<MT, NB, KC, WM, WN, 2, true>);
-            const int64_t slots_free = sptr ? slots_free_2 : slots_free_1;
-            const int64_t slots = (pad > 0 && slots_free > 0) ? std::min<int64_t>(slots_free, (int64_t)occ_cap * 32) : slots_free;
-            const int64_t rem = slots > 0 ? chunk % slots : 0;
-            if (rem > 0) {   // the last, partial round of resident workgroups (measured: pays even when it fills half the machine)
-                a.tail_main = (int32_t)(chunk - rem);
-                const int64_t grid = 8 * ((int64_t)a.tail_main + 4 * rem);
-#ifdef KN_ABLATION
-                // DIAGNOSTIC BUILD ONLY (tools/ablate_conv.sh): per-workgroup time stamps of this launch, appended to a file.  Synchronises the
-                // stream and uses one process-wide device buffer: not thread-safe, not capturable, never compiled into the product library.
-                if (const char* path = getenv("KN_STAMPS")) {
-                    static int64_t* dbuf = nullptr;
-                    static int seq = 0;
-                    const size_t cap = (size_t)1 << 22;
-                    if (!dbuf && hipMalloc((void**)&dbuf, cap * 4 * sizeof(int64_t)) != hipSuccess) dbuf = nullptr;
-                    if (dbuf && (size_t)grid <= cap) {
-                        (void)hipMemsetAsync(dbuf, 0, (size_t)grid * 4 * sizeof(int64_t), s);
-                        a.stamps = dbuf;
-                        if (sptr) hipLaunchKernelGGL((convtaps_mfma_kernel<MT, NB, KC, WM, WN, 2, true>), dim3((unsigned)grid), dim3(256), pad, s, a);
-                        else hipLaunchKernelGGL((convtaps_mfma_kernel<MT, NB, KC, WM, WN, 1, true>), dim3((unsigned)grid), dim3(256), pad, s, a);
-                        (void)hipStreamSynchronize(s);
-                        std::vector<int64_t> h((size_t)grid * 4);
-                        (void)hipMemcpy(h.data(), dbuf, h.size() * sizeof(int64_t), hipMemcpyDeviceToHost);
-                        if (FILE* f = fopen(path, "ab")) {
-                            const int64_t hdr[4] = {(int64_t)0x7374616d70, (int64_t)seq++, grid, ((int64_t)a.n_pix << 32) | (int64_t)(a.cin_pad * 1000 + a.n_mt)};
-                            fwrite(hdr, sizeof(int64_t), 4, f);
-                            fwrite(h.data(), sizeof(int64_t), h.size(), f);
-                            fclose(f);
-                        }
-                        return;
-                    }
-                }
-#endif
-                if (sptr) KN_LAUNCH(D("sptr(wave-uniform pointers)", true), (convtaps_mfma_kernel<MT, NB, KC, WM, WN, 2, true>), dim3((unsigned)grid), dim3(256), pad, s, a);
-                else KN_LAUNCH(D("fast(per-thread pointers)", true), (convtaps_mfma_kernel<MT, NB, KC, WM, WN, 1, true>), dim3((unsigned)grid), dim3(256), pad, s, a);
-                return;
-            }
-        }
-    }
-    const int64_t grid = 8 * chunk;
-    if constexpr (KC == 16) {
-        if (sptr && a.max_slots > MAX_FAST_SLOTS) {      // pixels with more than 64 slots: the slot-group instantiation (no tail split: such launches are long)
-            KN_LAUNCH(D("sptr(wave-uniform pointers, slot groups)", false), (convtaps_mfma_kernel<MT, NB, KC, WM, WN, 3, false>), dim3((unsigned)grid), dim3(256), pad, s, a);
-            return;
-        }
-        if (sptr) {
-            KN_LAUNCH(D("sptr(wave-uniform pointers)", false), (convtaps_mfma_kernel<MT, NB, KC, WM, WN, 2, false>), dim3((unsigned)grid), dim3(256), pad, s, a);
-            return;
-        }
-    }
-    if (fast) KN_LAUNCH(D("fast(per-thread pointers)", false), (convtaps_mfma_kernel<MT, NB, KC, WM, WN, 1, false>), dim3((unsigned)grid), dim3(256), pad, s, a);
-    else KN_LAUNCH(D("generic", false), (convtaps_mfma_kernel<MT, NB, KC, WM, WN, 0, false>), dim3((unsigned)grid), dim3(256), pad, s, a);
-}
-
 // Filled-in operators under KN_FLAG_EXACT: does this operator take convtaps_exact_fill_kernel?  (fill_ptr was laid out at create: convtaps_fill_offsets, kn_api.hip.)
 bool convtaps_fill_ok(const ConvTapsDev& A) { return A.fill_ptr != nullptr && A.fill_n > 0 && !A.tune.no_fill_exact; }
 
@@ -2611,11 +2503,11 @@ bool convtaps_fill_ok(const ConvTapsDev& A) { return A.fill_ptr != nullptr && A.
 // keys 0.4 - 4 GB per layer that runs in the reference's order)
 int convtaps_build_fill(ConvTapsDev& A, hipStream_t s) {
     if (A.fill_rec || !convtaps_fill_ok(A)) return KN_OK;
-    int32_t* d = nullptr;
+    FillRec* d = nullptr;
     KN_HIP(hipMalloc(reinterpret_cast<void**>(&d), (size_t)A.fill_n * sizeof(FillRec)));
     const int HoWo = (int)(A.Hout * A.Wout);
     hipLaunchKernelGGL(convtaps_fill_records_kernel, dim3((unsigned)((HoWo + 3) / 4)), dim3(256), 0, s, A.pix_ptr, A.fill_ptr, A.slot_in, A.slot_tap, A.slot_coef, A.unit_coef ? 1 : 0,
-                       A.ntaps <= 16 ? 1 : (int)(A.cin_pad * A.cout_pad), HoWo, reinterpret_cast<FillRec*>(d));
+                       A.ntaps <= 16 ? 1 : (int)(A.cin_pad * A.cout_pad), HoWo, d);
     if (hipGetLastError() != hipSuccess) {
         (void)hipFree(d);
         return fail(KN_ERR_HIP, "convtaps_fill_records_kernel launch failed");
@@ -2628,14 +2520,6 @@ int convtaps_build_fill(ConvTapsDev& A, hipStream_t s) {
     }
     __atomic_store_n(&A.fill_rec, d, __ATOMIC_RELEASE);
     return KN_OK;
-}
-
-// Can this operator / operand take convtaps_bf16x3_kernel?  (The planes must exist: convtaps_build_bf16 at first use, kn_api.hip.)
-bool convtaps_bf16x3_ok(const ConvTapsDev& A, const float* x, int64_t ldx, int64_t n_vecs, const float* y, int64_t ldy) {
-    const bool wide = A.Cout > 64;
-    const bool planes = A.tapsB != nullptr || plan_sink() != nullptr;      // kn_spmm_plan allocates nothing: the first real kn_spmm builds the planes
-    return planes && A.Cin % 16 == 0 && A.cin_pad == A.Cin && (wide ? (A.cout_pad % 128 == 0) : (A.cout_pad == 64)) && n_vecs > 0 && n_vecs % 128 == 0 &&
-           ldx % 4 == 0 && ldy % 4 == 0 && ((uintptr_t)x) % 16 == 0 && ((uintptr_t)y) % 16 == 0 && A.max_slots <= MAX_FAST_SLOTS;
 }
 
 // Three bf16 planes of the taps, laid out as the kernel's LDS image: [plane][tap][channel chunk of 16][cout_pad][16 k], the two 8-k halves of
@@ -2776,6 +2660,110 @@ static ExactChoice exact_choice(const ConvTapsDev& A, const ConvArgs& a) {
     return c;
 }
 
+// The matrix-core regime: which kernel runs on which tile over which grid, decided before anything is launched
+struct MfmaChoice {
+    enum Kernel { SMALLK, SMALLK_PIPE, TILE, BF16X3 } kernel = TILE;
+    int mt = 64, nb = 256;    // output channels x batch columns of a tile
+    int kc = 16;              // TILE: contraction rows per chunk (16 | 4)
+    int mode = 0;             // TILE: the loaders -- 0 generic, 1 straight-line with per-thread pointers, 2 with wave-uniform pointers, 3 ... and slot groups (> MAX_FAST_SLOTS slots per pixel)
+    bool coef = false;        // BF16X3: the instantiation that applies the slot coefficients (the other kernels read ConvArgs::unit_coef)
+    bool tail = false;        // TILE (128 x 128 x 16, mode 1 | 2) and BF16X3 (128 x 128): the last, partial round of resident workgroups runs as quarter tiles
+    int32_t tail_main = 0;    // ConvArgs::tail_main: work items per XCD ahead of the quarter tiles (without a tail: all of them)
+    int32_t n_mt = 0, n_bt = 0;
+    int64_t grid = 0;
+    int occ_cap = 0;          // TILE: workgroups per CU (0: what fits) ...
+    unsigned lds_pad = 0;     // ... and the dynamic LDS that enforces the cap
+    bool absmax_rides = false;   // the stores are wide and the batch fills whole tiles: max |Y| can ride in the epilogues
+};
+
+// resident workgroups per XCD of the instantiations whose grid depends on them, cached per instantiation (defined with the kernel selector, behind the other launchers: the
+// code object keeps the kernels in the order this file names them)
+static int64_t tile_tail_slots(bool sptr);
+static int64_t bf16x3_tail_slots(bool coef);
+static int64_t smallk_pipe_slots();
+
+// Can this operator / operand take convtaps_bf16x3_kernel?  (The planes must exist: convtaps_build_bf16 at first use, kn_api.hip.)
+static bool bf16x3_ok(const ConvTapsDev& A, const ConvArgs& a) {
+    const bool wide = A.Cout > 64;
+    const bool planes = A.tapsB != nullptr || plan_sink() != nullptr;      // kn_spmm_plan allocates nothing: the first real kn_spmm builds the planes
+    return planes && A.Cin % 16 == 0 && A.cin_pad == A.Cin && (wide ? (A.cout_pad % 128 == 0) : (A.cout_pad == 64)) && a.n_vecs > 0 && a.n_vecs % 128 == 0 &&
+           a.ldx % 4 == 0 && a.ldy % 4 == 0 && ((uintptr_t)a.X) % 16 == 0 && ((uintptr_t)a.Y) % 16 == 0 && A.max_slots <= MAX_FAST_SLOTS;
+}
+
+// The loaders of an f32 tile of nb columns at kc contraction rows per chunk (MfmaChoice::mode)
+static int tile_loaders(const ConvTapsDev& A, const ConvArgs& a, int nb, int kc) {
+    const bool fast_shape = a.vec_ok && (a.n_vecs % nb == 0) && ((int64_t)kc * a.HiWi * a.ldx < (int64_t)1 << 31) &&      // (any number of slots per pixel: slot groups)
+                            (int64_t)a.HiWi * a.ldx < (int64_t)1 << 31 && (int64_t)a.ntaps * a.cin_pad * a.cout_pad < (int64_t)1 << 31;
+    const bool fast = fast_shape && a.unit_coef && (a.Cin % kc == 0 || a.Cin < kc) && a.max_slots <= MAX_FAST_SLOTS;
+    // scalar-pointer loaders: 16-row chunks of whole channels, a thread's offsets inside one chunk in 31 bits.  Tuning::no_sptr
+    // (KN_NO_SPTR=1 when the operator is created) keeps the other loaders for the parity tests' side-by-side.
+    const bool sptr = kc == 16 && fast_shape && a.Cin % 16 == 0 && 4 * ((int64_t)(1024 / nb) * a.HiWi * a.ldx + nb) < (int64_t)1 << 31 && !A.tune.no_sptr;
+    return sptr ? (a.max_slots > MAX_FAST_SLOTS ? 3 : 2) : (fast ? 1 : 0);
+}
+
+// Workgroups per CU of the 128 x 128 x 16 tile over `chunk` work items per XCD (0: what fits, four).  All of a launch's workgroups take the same time, so a launch
+// proceeds in "rounds" of the resident set; with only a few rounds (VGG conv5_x: 196 items per XCD = 1.53 rounds of 128) a third of the work would fall into the
+// last, partial round.  Three workgroups per CU run as fast as four on the long layers (-1.5 %), and 196 items = 2.04 rounds of 96: when a launch has fewer than four
+// rounds, the resident set whose partial round is the smaller fraction wins (measured on conv5_x: 122.9 -> 125.4 TFLOP/s, same-process A/B).
+static int tile_occ_cap(int64_t chunk) {
+    const double r4 = (double)chunk / 128.0, r3 = (double)chunk / 96.0;
+    const double f4 = r4 - (double)(int64_t)r4, f3 = r3 - (double)(int64_t)r3;
+    return (r4 < 4.0 && f4 > 0.0 && f3 < f4) ? 3 : 0;
+}
+
+static MfmaChoice mfma_choice(const ConvTapsDev& A, const ConvArgs& a, bool bf16x3_requested) {
+    MfmaChoice c;
+    const int64_t n_vecs = a.n_vecs;
+    const bool big_m = A.cout_pad % 128 == 0 && A.Cout > 64;      // 128 x 128 tiles; 64-channel layers take 64 x 256 (bf16x3: 64 x 128, four wavefronts of 32 x 64)
+    // 1. kernel and tile
+    if (bf16x3_requested && bf16x3_ok(A, a)) {
+        c.kernel = MfmaChoice::BF16X3;
+        c.mt = big_m ? 128 : 64;
+        c.nb = 128;
+        c.coef = !A.unit_coef;
+    } else if (!A.tune.no_smallk && (int64_t)A.max_slots * A.Cin + (A.has_last ? 1 : 0) <= SMALLK_MAX && a.wide_store && n_vecs % 256 == 0 && A.cout_pad % 64 == 0) {
+        // Tuning::no_smallk_pipe: the one-shot kernel, for the parity tests' side-by-side
+        c.kernel = (a.sk_desc && A.cout_pad == 64 && !A.tune.no_smallk_pipe) ? MfmaChoice::SMALLK_PIPE : MfmaChoice::SMALLK;
+    } else {
+        c.mt = big_m ? 128 : 64;
+        c.nb = big_m ? 128 : 256;
+        c.kc = A.cin_pad % 16 == 0 ? 16 : 4;
+    }
+    c.n_mt = (int32_t)(A.cout_pad / c.mt);
+    c.n_bt = (int32_t)((n_vecs + c.nb - 1) / c.nb);
+    c.absmax_rides = a.wide_store && n_vecs % c.nb == 0;
+    const int64_t chunk = ((int64_t)a.n_pix * c.n_bt * c.n_mt + 7) / 8;      // work items per XCD
+    c.grid = 8 * chunk;
+    if (c.kernel == MfmaChoice::SMALLK) return c;
+    if (c.kernel == MfmaChoice::SMALLK_PIPE) {                               // persistent: the resident set, at least 32 and at most one workgroup per item
+        c.grid = 8 * std::min<int64_t>(std::max<int64_t>(smallk_pipe_slots(), 32), chunk);
+        return c;
+    }
+    c.tail_main = (int32_t)chunk;
+    const bool split = !A.tune.no_tail_split;
+    int64_t slots = 0;        // resident workgroups per XCD of the quarter-tile instantiation, where the call can take one
+    if (c.kernel == MfmaChoice::BF16X3) {
+        if (c.mt == 128) slots = bf16x3_tail_slots(c.coef);
+    } else {
+        const bool top = c.mt == 128 && c.kc == 16;                          // the 128 x 128 x 16 tile: the one with an occupancy rule and a tail split
+        c.mode = tile_loaders(A, a, c.nb, c.kc);
+        c.occ_cap = (A.tune.occ != 0 || !top) ? A.tune.occ : tile_occ_cap(chunk);      // Tuning::occ forces a cap (diagnostic build)
+        c.lds_pad = lds_pad_for_occupancy(sizeof(float) * (2 * c.kc * c.mt + 2 * c.kc * c.nb + 4 * MAX_FAST_SLOTS + 2 * (c.mt + c.nb)), c.occ_cap);
+        if (top && (c.mode == 1 || c.mode == 2) && a.wide_store && split) {
+            slots = tile_tail_slots(c.mode == 2);
+            if (c.lds_pad > 0 && slots > 0) slots = std::min<int64_t>(slots, (int64_t)c.occ_cap * 32);
+        }
+    }
+    // 2. the last, partial round of resident workgroups as quarter tiles (measured: pays even when it fills half the machine)
+    const int64_t rem = (slots > 0 && split) ? chunk % slots : 0;
+    if (rem > 0) {
+        c.tail = true;
+        c.tail_main = (int32_t)(chunk - rem);
+        c.grid = 8 * ((int64_t)c.tail_main + 4 * rem);
+    }
+    return c;
+}
+
 typedef void (*ExactPipeKernel)(ConvArgs, int, int64_t);
 template <int RBX, int XD, int VEC>
 static ExactPipeKernel exact_pipe_kernel(bool coef) {
@@ -2809,7 +2797,7 @@ static int exact_tail(const ConvTapsDev& A, const ConvArgs& a, hipStream_t s) {
     return KN_OK;
 }
 
-// What the two narrow conv launchers (flag `flag`) require of operator and batch: value rows in whole 64-channel blocks, and 32-bit element offsets into tapsT and X
+// What the three narrow regimes (flag `flag`: launch_narrow) require of operator and batch: value rows in whole 64-channel blocks, and 32-bit element offsets into tapsT and X
 static int narrow_limits(const ConvTapsDev& A, const ConvArgs& a, const char* flag) {
     KN_REQUIRE(A.cout_pad % 64 == 0, KN_ERR_UNSUPPORTED, std::string(flag) + ": the value rows are not padded to whole 64-channel blocks");
     KN_REQUIRE(A.ntaps * A.cin_pad * A.cout_pad < ((int64_t)1 << 31) && (a.last_in_row + 1) * a.ldx + (a.n_vecs > NARROW_MAX_VECS ? NARROW32_MAX_VECS : NARROW_MAX_VECS) < ((int64_t)1 << 31),
@@ -2817,22 +2805,9 @@ static int narrow_limits(const ConvTapsDev& A, const ConvArgs& a, const char* fl
     return KN_OK;
 }
 
-// KN_FLAG_NARROW on at most NARROW_MAX_VECS columns: one wavefront per (output pixel, 64 output channels), NarrowWidth::nv running sums (batch columns) per lane
-static int spmm_narrow(const ConvTapsDev& A, ConvArgs& a, hipStream_t s) {
-    const NarrowWidth w = narrow_width(a.n_vecs);
-    const int n_cb = (int)((A.Cout + 63) / 64);
-    const int64_t n_wg = ((int64_t)a.n_pix * n_cb + 3) / 4;
-    if (int rc = narrow_limits(A, a, "KN_FLAG_NARROW")) return rc;
-    KN_REQUIRE(n_wg + 8 < ((int64_t)1 << 29) && A.Cin * (int64_t)A.max_slots < ((int64_t)1 << 31), KN_ERR_UNSUPPORTED,
-               "grid or slot walk too large for the channel-lane order-preserving kernel");
-    const bool coef = !A.unit_coef;
-    KN_LAUNCH("convtaps_narrow_kernel<" + std::to_string(w.nv) + (w.full ? "" : ",masked to " + std::to_string(a.n_vecs)) + (A.has_dups ? ",stored values summed" : "") + (coef ? ",coef" : "") +
-                  "> (lane = output channel)",
-              narrow_kernel(w.nv, w.full, A.has_dups, coef), dim3((unsigned)(((n_wg + 7) / 8) * 8)), dim3(256), 0, s, a, n_cb, n_wg);
-    return exact_tail(A, a, s);
-}
-
-// KN_FLAG_NARROW | KN_FLAG_NARROW32 on 9 .. NARROW32_MAX_VECS columns: one wavefront per (column block, output pixel, 64 output channels).  Columns per block: the
+// The three narrow regimes (narrow_choice decides, launch_narrow launches):
+// NARROW -- KN_FLAG_NARROW on at most NARROW_MAX_VECS columns: one wavefront per (output pixel, 64 output channels), NarrowWidth::nv running sums (batch columns) per lane.
+// NARROW32 -- KN_FLAG_NARROW | KN_FLAG_NARROW32 on 9 .. NARROW32_MAX_VECS columns: one wavefront per (column block, output pixel, 64 output channels).  Columns per block: the
 // width's form, 16 | 32 (operators that sum stored values: 16).  Narrower blocks, down to 8 columns, while (pixels x channel blocks x column blocks) leaves SIMDs without
 // their four wavefronts (4 096 items) AND the operator's taps stay in an XCD's L2 (2 MB, half of it: spmm_exact's threshold): every column block walks the layer's value rows
 // again, and those loads are what the walk waits for.  Both sides were measured (profiles/r10_narrow32.txt): the keyed AllConvNet (layers of 1 024 pixels and fewer, at most 1.3 MB of
@@ -2846,28 +2821,7 @@ static Narrow32Kernel narrow32_kernel_of(bool dups, bool coef) {
                 : (coef ? convtaps_narrow32_kernel<NV, false, true> : convtaps_narrow32_kernel<NV, false, false>);
 }
 
-static int spmm_narrow32(const ConvTapsDev& A, ConvArgs& a, hipStream_t s) {
-    const int n_cb = (int)((A.Cout + 63) / 64);
-    const int64_t items = (int64_t)a.n_pix * n_cb;
-    int nv = A.has_dups ? 16 : narrow_width(a.n_vecs).nv;
-    if (4 * A.ntaps * A.cin_pad * A.cout_pad <= (2 << 20))
-        while (nv > 8 && items * ((a.n_vecs + nv - 1) / nv) < 4096) nv >>= 1;
-    if (A.tune.narrow32_nv == 8 || A.tune.narrow32_nv == 16 || (A.tune.narrow32_nv == 32 && !A.has_dups)) nv = A.tune.narrow32_nv;
-    const int n_colb = (int)((a.n_vecs + nv - 1) / nv);
-    const int64_t n_wg = (items * n_colb + 3) / 4;
-    if (int rc = narrow_limits(A, a, "KN_FLAG_NARROW | KN_FLAG_NARROW32")) return rc;
-    KN_REQUIRE(n_wg + 8 < ((int64_t)1 << 29) && A.Cin * (int64_t)A.max_slots < ((int64_t)1 << 31), KN_ERR_UNSUPPORTED,
-               "grid or slot walk too large for the channel-lane order-preserving kernel");
-    const bool coef = !A.unit_coef;
-    const Narrow32Kernel k = nv == 8 ? narrow32_kernel_of<8>(A.has_dups, coef) : nv == 16 ? narrow32_kernel_of<16>(A.has_dups, coef)
-                                     : (coef ? convtaps_narrow32_kernel<32, false, true> : convtaps_narrow32_kernel<32, false, false>);
-    KN_LAUNCH("convtaps_narrow32_kernel<NV=" + std::to_string(nv) + (a.n_vecs % nv ? ", masked to " + std::to_string(a.n_vecs) : "") + ", " + std::to_string(n_colb) +
-                  (n_colb == 1 ? " column block" : " column blocks") + (A.has_dups ? ", stored values summed" : "") + (coef ? ", coef" : "") + "> (lane = output channel)",
-              k, dim3((unsigned)(((n_wg + 7) / 8) * 8)), dim3(256), 0, s, a, n_cb, n_colb, n_wg);
-    return exact_tail(A, a, s);
-}
-
-// KN_FLAG_NARROW_MFMA on an eligible operator: 32 TM output channels x 32 (pixel, image) columns per workgroup, K split over its four wavefronts.
+// NARROW_MFMA -- KN_FLAG_NARROW_MFMA on an eligible operator: 32 TM output channels x 32 (pixel, image) columns per workgroup, K split over its four wavefronts.
 // TM = 2 (one gathered B fragment feeds two matrix instructions; 160 - 184 registers and 32 KB of LDS: two wavefronts per SIMD, two workgroups per CU)
 // where the 64-channel tiling has at least 1 024 workgroups; else 32-channel tiles (<= 120 registers, 16 KB: four wavefronts per SIMD), so that the small
 // layers spread over the chip (VGG-16 conv5_x: 16 x 7 tiles).  Measured in profiles/r08_narrow_mfma.txt: layers that cross the threshold with more images do
@@ -2879,22 +2833,78 @@ static NarrowMfmaKernel narrow_mfma_kernel(bool two, bool coef) {
                : (coef ? convtaps_narrow_mfma_kernel<TM, false, true> : convtaps_narrow_mfma_kernel<TM, false, false>);
 }
 
-static int spmm_narrow_mfma(const ConvTapsDev& A, ConvArgs& a, hipStream_t s) {
-    const NarrowWidth w = narrow_width(a.n_vecs);
-    const int64_t n_nt = (((int64_t)a.n_pix << w.log2) + 31) / 32;
-    if (int rc = narrow_limits(A, a, "KN_FLAG_NARROW_MFMA")) return rc;
-    const int tm = ((A.Cout + 63) / 64) * n_nt >= 1024 ? 2 : 1;
-    const int64_t n_wg = ((A.Cout + 32 * tm - 1) / (32 * tm)) * n_nt;
-    KN_REQUIRE(n_wg + 8 < ((int64_t)1 << 29) && n_nt < ((int64_t)1 << 26), KN_ERR_UNSUPPORTED, "grid too large for the matrix-core narrow kernel");
-    const PtRec* pt = reinterpret_cast<const PtRec*>(__atomic_load_n(&A.pt_rec, __ATOMIC_ACQUIRE));
-    KN_REQUIRE(pt != nullptr || plan_sink() != nullptr, KN_ERR_INVALID, "KN_FLAG_NARROW_MFMA: the (pixel, tap) records were not built");
+struct NarrowChoice {
+    ConvRegime regime = NARROW;
+    NarrowWidth w = {1, 0, true};   // columns per lane (NARROW32: per column block) and whether the batch fills them, else the last ones are masked
+    int n_colb = 1;                 // NARROW32: column blocks
+    int tm = 1;                     // NARROW_MFMA: 32-channel blocks per workgroup
+    int n_cb = 0;                   // 64-channel blocks
+    int64_t n_nt = 0;               // NARROW_MFMA: tiles of 32 (pixel, image) columns
+    int64_t n_wg = 0;               // work items (channel-lane kernels: of four wavefronts each)
+    union {                         // the instantiation, by regime
+        NarrowKernel lanes;
+        Narrow32Kernel lanes32;
+        NarrowMfmaKernel mfma;
+    } kernel = {nullptr};
+};
+
+static NarrowChoice narrow_choice(const ConvTapsDev& A, const ConvArgs& a, ConvRegime regime) {
+    NarrowChoice c;
+    c.regime = regime;
+    c.w = narrow_width(a.n_vecs);
+    c.n_cb = (int)((A.Cout + 63) / 64);
+    const int64_t items = (int64_t)a.n_pix * c.n_cb;
     const bool coef = !A.unit_coef;
-    KN_LAUNCH("convtaps_narrow_mfma_kernel<" + std::to_string(32 * tm) + " channels x " + std::to_string(32 >> w.log2) + " pixels x NV=" + std::to_string(w.nv) +
-                  (w.full ? "" : " masked to " + std::to_string(a.n_vecs)) + ", K split over 4 wavefronts" + (A.pt_two ? ", two slots per tap" : "") + (coef ? ",coef" : "") +
-                  "> (v_mfma_f32_32x32x2_f32, at most " + std::to_string(PT_MAX_SLOTS) + " slots per (pixel, tap))",
-              (tm == 2 ? narrow_mfma_kernel<2>(A.pt_two, coef) : narrow_mfma_kernel<1>(A.pt_two, coef)), dim3((unsigned)(((n_wg + 7) / 8) * 8)), dim3(256), 0, s, a, pt, w.log2, (int)n_nt, n_wg);
-    launch_lastrow(A, a, s);
-    return KN_OK;
+    if (regime == NARROW) {
+        c.n_wg = (items + 3) / 4;
+        c.kernel.lanes = narrow_kernel(c.w.nv, c.w.full, A.has_dups, coef);
+    } else if (regime == NARROW32) {
+        int nv = A.has_dups ? 16 : c.w.nv;
+        if (4 * A.ntaps * A.cin_pad * A.cout_pad <= (2 << 20))
+            while (nv > 8 && items * ((a.n_vecs + nv - 1) / nv) < 4096) nv >>= 1;
+        if (A.tune.narrow32_nv == 8 || A.tune.narrow32_nv == 16 || (A.tune.narrow32_nv == 32 && !A.has_dups)) nv = A.tune.narrow32_nv;
+        c.w = {nv, nv == 8 ? 3 : (nv == 16 ? 4 : 5), a.n_vecs % nv == 0};
+        c.n_colb = (int)((a.n_vecs + nv - 1) / nv);
+        c.n_wg = (items * c.n_colb + 3) / 4;
+        c.kernel.lanes32 = nv == 8 ? narrow32_kernel_of<8>(A.has_dups, coef) : nv == 16 ? narrow32_kernel_of<16>(A.has_dups, coef)
+                                   : (coef ? convtaps_narrow32_kernel<32, false, true> : convtaps_narrow32_kernel<32, false, false>);
+    } else {
+        c.n_nt = (((int64_t)a.n_pix << c.w.log2) + 31) / 32;
+        c.tm = c.n_cb * c.n_nt >= 1024 ? 2 : 1;
+        c.n_wg = ((A.Cout + 32 * c.tm - 1) / (32 * c.tm)) * c.n_nt;
+        c.kernel.mfma = c.tm == 2 ? narrow_mfma_kernel<2>(A.pt_two, coef) : narrow_mfma_kernel<1>(A.pt_two, coef);
+    }
+    return c;
+}
+
+static int launch_narrow(const ConvTapsDev& A, const ConvArgs& a, const NarrowChoice& c, hipStream_t s) {
+    const int64_t n_wg = c.n_wg, n_nt = c.n_nt;
+    const NarrowWidth w = c.w;
+    const bool coef = !A.unit_coef;
+    const dim3 grid((unsigned)(((n_wg + 7) / 8) * 8));
+    if (int rc = narrow_limits(A, a, c.regime == NARROW ? "KN_FLAG_NARROW" : (c.regime == NARROW32 ? "KN_FLAG_NARROW | KN_FLAG_NARROW32" : "KN_FLAG_NARROW_MFMA"))) return rc;
+    if (c.regime == NARROW_MFMA) {
+        KN_REQUIRE(n_wg + 8 < ((int64_t)1 << 29) && n_nt < ((int64_t)1 << 26), KN_ERR_UNSUPPORTED, "grid too large for the matrix-core narrow kernel");
+        const PtRec* pt = __atomic_load_n(&A.pt_rec, __ATOMIC_ACQUIRE);
+        KN_REQUIRE(pt != nullptr || plan_sink() != nullptr, KN_ERR_INVALID, "KN_FLAG_NARROW_MFMA: the (pixel, tap) records were not built");
+        KN_LAUNCH("convtaps_narrow_mfma_kernel<" + std::to_string(32 * c.tm) + " channels x " + std::to_string(32 >> w.log2) + " pixels x NV=" + std::to_string(w.nv) +
+                      (w.full ? "" : " masked to " + std::to_string(a.n_vecs)) + ", K split over 4 wavefronts" + (A.pt_two ? ", two slots per tap" : "") + (coef ? ",coef" : "") +
+                      "> (v_mfma_f32_32x32x2_f32, at most " + std::to_string(PT_MAX_SLOTS) + " slots per (pixel, tap))",
+                  c.kernel.mfma, grid, dim3(256), 0, s, a, pt, w.log2, (int)n_nt, n_wg);
+        launch_lastrow(A, a, s);
+        return KN_OK;
+    }
+    KN_REQUIRE(n_wg + 8 < ((int64_t)1 << 29) && A.Cin * (int64_t)A.max_slots < ((int64_t)1 << 31), KN_ERR_UNSUPPORTED,
+               "grid or slot walk too large for the channel-lane order-preserving kernel");
+    if (c.regime == NARROW32)
+        KN_LAUNCH("convtaps_narrow32_kernel<NV=" + std::to_string(w.nv) + (w.full ? "" : ", masked to " + std::to_string(a.n_vecs)) + ", " + std::to_string(c.n_colb) +
+                      (c.n_colb == 1 ? " column block" : " column blocks") + (A.has_dups ? ", stored values summed" : "") + (coef ? ", coef" : "") + "> (lane = output channel)",
+                  c.kernel.lanes32, grid, dim3(256), 0, s, a, c.n_cb, c.n_colb, n_wg);
+    else
+        KN_LAUNCH("convtaps_narrow_kernel<" + std::to_string(w.nv) + (w.full ? "" : ",masked to " + std::to_string(a.n_vecs)) + (A.has_dups ? ",stored values summed" : "") + (coef ? ",coef" : "") +
+                      "> (lane = output channel)",
+                  c.kernel.lanes, grid, dim3(256), 0, s, a, c.n_cb, n_wg);
+    return exact_tail(A, a, s);
 }
 
 static int spmm_exact(const ConvTapsDev& A, ConvArgs& a, hipStream_t s) {
@@ -2938,75 +2948,114 @@ static int spmm_exact(const ConvTapsDev& A, ConvArgs& a, hipStream_t s) {
                      : (c.wide ? convtaps_exact_fill_kernel<16, true> : (regs ? convtaps_exact_fill_kernel<16, false> : convtaps_exact_fill_kernel<0, false>));
         KN_LAUNCH(std::string("convtaps_exact_fill_kernel") + (regs ? (c.wide ? "<taps in registers, 64 channels per wavefront" : "<taps in registers") : "") +
                       (regs ? (c.tiles2 ? ", two column tiles per wavefront>" : ">") : "") + " (stored values formed per lane, products on the matrix pipe, " + std::to_string(A.fill_n) + " slot records)",
-                  k, dim3((unsigned)(((n_wg + 7) / 8) * 8)), dim3(256), 0, s, a, A.fill_ptr, reinterpret_cast<const FillRec*>(A.fill_rec), n_cc, n_ctf, n_wg);
+                  k, dim3((unsigned)(((n_wg + 7) / 8) * 8)), dim3(256), 0, s, a, A.fill_ptr, A.fill_rec, n_cc, n_ctf, n_wg);
     } else {
         KN_LAUNCH(c.vec == 4 ? "convtaps_exact_kernel<vec=4>" : "convtaps_exact_kernel<vec=1>", (c.vec == 4 ? convtaps_exact_kernel<4> : convtaps_exact_kernel<1>), grid, dim3(256), 0, s, a, n_cob, n_rb);
     }
     return exact_tail(A, a, s);
 }
 
+// The instantiation a MfmaChoice names.  (The kernels appear here in the order the code object has always held them.)
 typedef void (*ConvKernel)(ConvArgs);
 template <int MT, bool TAIL>
 static ConvKernel bf16x3_kernel(bool coef) {
     return coef ? convtaps_bf16x3_kernel<MT, 128, 2, 2, true, TAIL> : convtaps_bf16x3_kernel<MT, 128, 2, 2, false, TAIL>;
 }
 
-static int spmm_bf16x3(const ConvTapsDev& A, ConvArgs& a, hipStream_t s) {
-    const bool wide = A.Cout > 64;                          // 128 x 128 tiles; 64-channel layers take 64 x 128 (four wavefronts of 32 x 64)
-    const bool coef = !A.unit_coef;
-    a.tapsB = A.tapsB;
-    a.tapsB_plane = A.tapsB_plane;
-    a.n_mt = (int32_t)(A.cout_pad / (wide ? 128 : 64));
-    a.n_bt = (int32_t)(a.n_vecs / 128);
-    const int64_t items = (int64_t)a.n_pix * a.n_bt * a.n_mt;
-    const int64_t chunk = (items + 7) / 8;
-    a.tail_main = (int32_t)chunk;
-    const std::string d = std::string("convtaps_bf16x3_kernel<") + (wide ? "128x128" : "64x128") + ", 3-way bf16 split, 6 products>" + (coef ? "+coef" : "");
-    int64_t rem = 0;
-    if (wide) {
-        // last partial round of resident workgroups as quarter tiles (same split as launch_conv)
-        static const int64_t slots[2] = {xcd_slots(bf16x3_kernel<128, true>(false)), xcd_slots(bf16x3_kernel<128, true>(true))};
-        if (slots[coef] > 0 && !A.tune.no_tail_split) rem = chunk % slots[coef];
-    }
-    if (rem > 0) {
-        a.tail_main = (int32_t)(chunk - rem);
-        const ConvKernel k = bf16x3_kernel<128, true>(coef);
-        KN_LAUNCH(d + " tail_split", k, dim3((unsigned)(8 * ((int64_t)a.tail_main + 4 * rem))), dim3(256), 0, s, a);
-    } else {
-        const ConvKernel k = wide ? bf16x3_kernel<128, false>(coef) : bf16x3_kernel<64, false>(coef);
-        KN_LAUNCH(d, k, dim3((unsigned)(8 * chunk)), dim3(256), 0, s, a);
-    }
-    launch_lastrow(A, a, s);
-    return KN_OK;
+static int64_t bf16x3_tail_slots(bool coef) {
+    static const int64_t slots[2] = {xcd_slots(bf16x3_kernel<128, true>(false)), xcd_slots(bf16x3_kernel<128, true>(true))};
+    return slots[coef];
 }
 
-static int spmm_mfma(const ConvTapsDev& A, ConvArgs& a, hipStream_t s) {
-    const int64_t n_vecs = a.n_vecs;
-    const bool big_m = A.cout_pad % 128 == 0 && A.Cout > 64;
-    const bool k16 = A.cin_pad % 16 == 0;
-    if (!A.tune.no_smallk && (int64_t)A.max_slots * A.Cin + (A.has_last ? 1 : 0) <= SMALLK_MAX && a.wide_store && n_vecs % 256 == 0 && A.cout_pad % 64 == 0) {
-        a.n_mt = (int32_t)(A.cout_pad / 64);
-        a.n_bt = (int32_t)(n_vecs / 256);
-        const int64_t items = (int64_t)a.n_pix * a.n_bt * a.n_mt;
-        const bool no_pipe = A.tune.no_smallk_pipe != 0;      // (the one-shot kernel, for the parity tests' side-by-side)
-        if (a.sk_desc && a.n_mt == 1 && !no_pipe) {
-            static const int64_t slots = xcd_slots(convtaps_smallk_pipe_kernel);
-            const int64_t per_xcd = std::min<int64_t>(std::max<int64_t>(slots, 32), (items + 7) / 8);
-            KN_LAUNCH("convtaps_smallk_pipe_kernel", convtaps_smallk_pipe_kernel, dim3((unsigned)(8 * per_xcd)), dim3(256), 0, s, a);
-        } else {
-            KN_LAUNCH("convtaps_smallk_kernel", convtaps_smallk_kernel, dim3((unsigned)(((items + 7) / 8) * 8)), dim3(256), 0, s, a);
-        }
-    } else if (big_m) {
-        a.n_mt = (int32_t)(A.cout_pad / 128);
-        a.n_bt = (int32_t)((n_vecs + 127) / 128);
-        if (k16) launch_conv<128, 128, 16, 2, 2>(a, A.tune, s);
-        else launch_conv<128, 128, 4, 2, 2>(a, A.tune, s);
-    } else {
-        a.n_mt = (int32_t)(A.cout_pad / 64);
-        a.n_bt = (int32_t)((n_vecs + 255) / 256);
-        if (k16) launch_conv<64, 256, 16, 1, 4>(a, A.tune, s);
-        else launch_conv<64, 256, 4, 1, 4>(a, A.tune, s);
+static int64_t smallk_pipe_slots() {
+    static const int64_t slots = xcd_slots(convtaps_smallk_pipe_kernel);
+    return slots;
+}
+
+template <int MT, int NB, int KC, int WM, int WN>
+static ConvKernel tile_kernel(int mode, bool tail) {
+    if constexpr (MT == 128 && NB == 128 && KC == 16) {
+        if (tail) return mode == 1 ? convtaps_mfma_kernel<MT, NB, KC, WM, WN, 1, true> : convtaps_mfma_kernel<MT, NB, KC, WM, WN, 2, true>;
     }
+    if constexpr (KC == 16) {
+        if (mode == 3) return convtaps_mfma_kernel<MT, NB, KC, WM, WN, 3, false>;
+        if (mode == 2) return convtaps_mfma_kernel<MT, NB, KC, WM, WN, 2, false>;
+    }
+    return mode == 1 ? convtaps_mfma_kernel<MT, NB, KC, WM, WN, 1, false> : convtaps_mfma_kernel<MT, NB, KC, WM, WN, 0, false>;
+}
+
+static ConvKernel mfma_kernel(const MfmaChoice& c) {
+    switch (c.kernel) {
+        case MfmaChoice::BF16X3: return c.tail ? bf16x3_kernel<128, true>(c.coef) : (c.mt == 128 ? bf16x3_kernel<128, false>(c.coef) : bf16x3_kernel<64, false>(c.coef));
+        case MfmaChoice::SMALLK_PIPE: return convtaps_smallk_pipe_kernel;
+        case MfmaChoice::SMALLK: return convtaps_smallk_kernel;
+        default: break;
+    }
+    if (c.mt == 128) return c.kc == 16 ? tile_kernel<128, 128, 16, 2, 2>(c.mode, c.tail) : tile_kernel<128, 128, 4, 2, 2>(c.mode, c.tail);
+    return c.kc == 16 ? tile_kernel<64, 256, 16, 1, 4>(c.mode, c.tail) : tile_kernel<64, 256, 4, 1, 4>(c.mode, c.tail);
+}
+
+// (the two loader modes may differ in registers)
+static int64_t tile_tail_slots(bool sptr) {
+    static const int64_t slots_1 = xcd_slots(tile_kernel<128, 128, 16, 2, 2>(1, true));
+    static const int64_t slots_2 = xcd_slots(tile_kernel<128, 128, 16, 2, 2>(2, true));
+    return sptr ? slots_2 : slots_1;
+}
+
+// what kn_spmm_plan prints for the launch (never formed on a launching call)
+static std::string mfma_describe(const MfmaChoice& c, const ConvArgs& a) {
+    if (c.kernel == MfmaChoice::SMALLK_PIPE) return "convtaps_smallk_pipe_kernel";
+    if (c.kernel == MfmaChoice::SMALLK) return "convtaps_smallk_kernel";
+    if (c.kernel == MfmaChoice::BF16X3)
+        return std::string("convtaps_bf16x3_kernel<") + (c.mt == 128 ? "128x128" : "64x128") + ", 3-way bf16 split, 6 products>" + (c.coef ? "+coef" : "") + (c.tail ? " tail_split" : "");
+    static const char* const loader[4] = {"generic", "fast(per-thread pointers)", "sptr(wave-uniform pointers)", "sptr(wave-uniform pointers, slot groups)"};
+    char b[200];
+    snprintf(b, sizeof(b), "convtaps_mfma_kernel<MT=%d,NB=%d,KC=%d> loader=%s%s%s occ_cap=%d", c.mt, c.nb, c.kc, loader[c.mode], a.unit_coef ? "" : "+coef", c.tail ? " tail_split" : "",
+             c.occ_cap);
+    return std::string(b);
+}
+
+#ifdef KN_ABLATION
+// DIAGNOSTIC BUILD ONLY (tools/ablate_conv.sh): per-workgroup time stamps of a tail-split launch of the f32 tile, appended to the file KN_STAMPS names; false when
+// nothing was launched (never under kn_spmm_plan, whose operand pointers are stand-ins).  Synchronises the stream and uses one process-wide device buffer: not thread-safe, not capturable, never compiled into the product library.
+static bool launch_conv_stamped(const MfmaChoice& c, ConvArgs a, hipStream_t s) {
+    const char* path = getenv("KN_STAMPS");
+    if (!path || plan_sink() != nullptr) return false;
+    static int64_t* dbuf = nullptr;
+    static int seq = 0;
+    const size_t cap = (size_t)1 << 22;
+    if (!dbuf && hipMalloc((void**)&dbuf, cap * 4 * sizeof(int64_t)) != hipSuccess) dbuf = nullptr;
+    if (!dbuf || (size_t)c.grid > cap) return false;
+    (void)hipMemsetAsync(dbuf, 0, (size_t)c.grid * 4 * sizeof(int64_t), s);
+    a.stamps = dbuf;
+    hipLaunchKernelGGL(mfma_kernel(c), dim3((unsigned)c.grid), dim3(256), c.lds_pad, s, a);
+    (void)hipStreamSynchronize(s);
+    std::vector<int64_t> h((size_t)c.grid * 4);
+    (void)hipMemcpy(h.data(), dbuf, h.size() * sizeof(int64_t), hipMemcpyDeviceToHost);
+    if (FILE* f = fopen(path, "ab")) {
+        const int64_t hdr[4] = {(int64_t)0x7374616d70, (int64_t)seq++, c.grid, ((int64_t)a.n_pix << 32) | (int64_t)(a.cin_pad * 1000 + a.n_mt)};
+        fwrite(hdr, sizeof(int64_t), 4, f);
+        fwrite(h.data(), sizeof(int64_t), h.size(), f);
+        fclose(f);
+    }
+    return true;
+}
+#endif
+
+// the matrix-core regime: every kernel of it takes the call's ConvArgs and nothing else
+static int spmm_mfma(const ConvTapsDev& A, ConvArgs& a, const MfmaChoice& c, hipStream_t s) {
+    a.n_mt = c.n_mt;
+    a.n_bt = c.n_bt;
+    a.tail_main = c.tail_main;
+    if (c.kernel == MfmaChoice::BF16X3) {
+        a.tapsB = A.tapsB;
+        a.tapsB_plane = A.tapsB_plane;
+    }
+    bool stamped = false;
+#ifdef KN_ABLATION
+    stamped = c.kernel == MfmaChoice::TILE && c.tail && launch_conv_stamped(c, a, s);
+#endif
+    if (!stamped) KN_LAUNCH(mfma_describe(c, a), mfma_kernel(c), dim3((unsigned)c.grid), dim3(256), c.lds_pad, s, a);
     launch_lastrow(A, a, s);
     return KN_OK;
 }
@@ -3016,24 +3065,22 @@ int convtaps_spmm(const ConvTapsDev& A, const float* x, int64_t ldx, int64_t n_v
     if (absmax_fused) *absmax_fused = false;
     ConvArgs a = conv_args(A, x, ldx, n_vecs, y, ldy, flags);
     int rc;
-    // KN_FLAG_NARROW on a batch of at most 8 columns: the channel-lane order-preserving kernel, whatever the other contract flags say
-    if (narrow_mfma_call(A, flags, n_vecs)) {
-        rc = spmm_narrow_mfma(A, a, s);
-    } else if (narrow_call(flags, n_vecs)) {
-        rc = n_vecs > NARROW_MAX_VECS ? spmm_narrow32(A, a, s) : spmm_narrow(A, a, s);      // (beyond 8 columns: KN_FLAG_NARROW32 is in force)
-    } else if (flags & KN_FLAG_EXACT) {
-        rc = spmm_exact(A, a, s);
-    } else {
-        const bool bf16x3 = (flags & KN_FLAG_BF16X3) && convtaps_bf16x3_ok(A, x, ldx, n_vecs, y, ldy);
-        // every matrix-core kernel streams its tiles out through kn_store_tile when the stores are wide and the batch fills whole tiles of the
-        // kernel that will run (128 columns for the 128 x 128 and bf16x3 tiles -- so also the half-batch windows of the overlapped forward at 256 images --,
-        // 256 for the 64 x 256 and small-K tiles): then max |Y| rides in the epilogues (tiles + conv_lastrow_kernel for the homogeneous row)
-        const int64_t nb_tile = (bf16x3 || (A.cout_pad % 128 == 0 && A.Cout > 64)) ? 128 : 256;
-        if (absmax && a.wide_store && n_vecs % nb_tile == 0) {
-            a.absmax = absmax;
-            if (absmax_fused) *absmax_fused = true;
+    const ConvRegime regime = conv_regime(A, flags, n_vecs);
+    switch (regime) {
+        case NARROW_MFMA:
+        case NARROW:
+        case NARROW32: rc = launch_narrow(A, a, narrow_choice(A, a, regime), s); break;
+        case EXACT: rc = spmm_exact(A, a, s); break;
+        default: {
+            const MfmaChoice c = mfma_choice(A, a, regime == BF16X3);
+            // every matrix-core kernel streams its tiles out through kn_store_tile: where the choice says so, max |Y| rides in the epilogues (tiles + conv_lastrow_kernel
+            // for the homogeneous row)
+            if (absmax && c.absmax_rides) {
+                a.absmax = absmax;
+                if (absmax_fused) *absmax_fused = true;
+            }
+            rc = spmm_mfma(A, a, c, s);
         }
-        rc = bf16x3 ? spmm_bf16x3(A, a, s) : spmm_mfma(A, a, s);
     }
     if (rc) return rc;
     KN_HIP(hipGetLastError());

@@ -195,7 +195,7 @@ PlanSink*& plan_sink();   // thread-local; null outside kn_spmm_plan
     X(chain_no_early, "KN_CHAIN_NO_EARLY", 0, true)  /* whole-net kernel: column pools staged at the start of their own layer */ \
     X(chain_no_seq, "KN_CHAIN_NO_SEQ", 0, true)      /* whole-net kernel: thin layers read their columns from the staged pool instead of walking a re-ordered input sequentially */ \
     X(chain_no_share, "KN_CHAIN_NO_SHARE", 0, true)  /* whole-net kernel: every lane streams its own copy of its row's values (no shared value blocks) */ \
-    X(narrow32_nv, "KN_NARROW32_NV", 0, true)        /* convtaps_narrow32_kernel: 8 | 16 | 32 columns per block (0: the rule, spmm_narrow32) */ \
+    X(narrow32_nv, "KN_NARROW32_NV", 0, true)        /* convtaps_narrow32_kernel: 8 | 16 | 32 columns per block (0: the rule, narrow_choice) */ \
     X(fill_form, "KN_FILL_FORM", 0, true)            /* filled-in order-preserving kernel: 0 = the dispatch rule, 1 / 2 = 32 / 64 channels x one column tile, 3 / 4 = 32 / 64 channels x two tiles */ \
     X(abl, "KN_ABL", 0, true)                        /* kernel ablation mask (kn_conv.hip, KN_ABLATION code paths) */
 struct Tuning {
@@ -266,6 +266,30 @@ struct CsrDev {
     int64_t n_patch = 0;
 };
 
+// Record layouts that a host-side packer writes and a kernel of kn_conv.hip reads.
+// Small-K descriptor (convtaps_smallk_desc, kn_api.hip -> convtaps_smallk_pipe_kernel): per output pixel SK_DESC_HDR header dwords, then cout_pad bias values.  Header:
+// [SK_DESC_XROW + k] X row of contraction row k (-1 = none), [SK_DESC_PIX] output pixel, [SK_DESC_TAPOFF + k] LDS offset of its tap row, [SK_DESC_COEF + k] coefficient,
+// k < SMALLK_MAX.  The kernel reads a header with one dword per lane and section.
+static constexpr int SMALLK_MAX = 28;        // contraction rows (slots x Cin + bias row) of the small-K kernels
+static constexpr int SK_DESC_HDR = 96;
+static constexpr int SK_DESC_XROW = 0, SK_DESC_PIX = 31, SK_DESC_TAPOFF = 32, SK_DESC_COEF = 64;
+static constexpr int SK_TAB_MAX = 61;        // tap-table rows that fit the LDS budget (+1 zero row, +2 bias rows = 16 KiB)
+static constexpr int SK_TAB_ROW = 64;        // floats per tap-table row: the one 64-channel tile of an eligible layer
+// (output pixel, tap) record of the matrix-core narrow kernel (convtaps_build_pt, kn_api.hip -> convtaps_narrow_mfma_kernel)
+struct PtRec {
+    int32_t in0;       // input pixel of the first slot of this (output pixel, tap), or -1
+    float c0;
+    int32_t in1;       // ... of the second one, or -1
+    float c1;
+};
+static_assert(sizeof(PtRec) == 16, "one 16-byte load per record");
+// slot record of a filled-in operator (convtaps_fill_records_kernel -> convtaps_exact_fill_kernel)
+struct FillRec {
+    int32_t in, tapoff;     // tapoff: offset of the tap's plane in tapsT (floats), or the tap index (TREG)
+    float coef;
+    int32_t flags;          // bit 0: first slot of a stored column, bit 1: last
+};
+
 // Factored conv operator  W = sum_e coef_e * taps[tap_e] (x) E[out_e,in_e] + lastcol + e_last.
 struct ConvTapsDev {
     Tuning tune;                        // recorded at create
@@ -299,7 +323,7 @@ struct ConvTapsDev {
     // filled-in operators under KN_FLAG_EXACT (kn_conv.hip, convtaps_exact_fill_kernel): per-pixel record lists {input pixel, tap offset, coefficient, first / last slot of
     // a stored column}, each padded to a multiple of 8 records; fill_ptr at create, the records on the device at the first kn_spmm that asks for them
     int32_t* fill_ptr = nullptr;        // [HoWo + 1] record offsets, or null when the operator is not eligible
-    int32_t* fill_rec = nullptr;        // [fill_n][4]
+    FillRec* fill_rec = nullptr;        // [fill_n]
     int64_t fill_n = 0;
     // bf16x3 path (kn_conv.hip, convtaps_bf16x3_kernel): the taps as three bf16 planes, built at the first kn_spmm that asks for them
     uint16_t* tapsB = nullptr;
@@ -309,7 +333,7 @@ struct ConvTapsDev {
     // records are built at the first kn_spmm that asks for them
     bool pt_ok = false;
     bool pt_two = false;                // some (pixel, tap) pair holds two slots
-    int32_t* pt_rec = nullptr;          // [HoWo][ntaps][4]
+    PtRec* pt_rec = nullptr;            // [HoWo][ntaps]
 };
 
 }  // namespace kn
@@ -394,6 +418,15 @@ static inline bool narrow_mfma_loses(const ConvTapsDev& A, int64_t n_vecs) {
 static inline bool narrow_mfma_call(const ConvTapsDev& A, uint32_t flags, int64_t n_vecs) {
     return (flags & KN_FLAG_NARROW_MFMA) && !(flags & KN_FLAG_EXACT) && n_vecs <= narrow_max(flags) && A.pt_ok && !narrow_mfma_loses(A, n_vecs);
 }
+// The regime a call on a conv-taps handle takes: the one place that turns the flag word into one.  convtaps_spmm switches on it, kn_spmm asks it which side table
+// the call reads.  BF16X3 is the REQUEST (its planes are built for it): operands that do not qualify run as MFMA (mfma_choice, kn_conv.hip).
+enum ConvRegime { NARROW_MFMA, NARROW, NARROW32, EXACT, BF16X3, MFMA };
+static inline ConvRegime conv_regime(const ConvTapsDev& A, uint32_t flags, int64_t n_vecs) {
+    if (narrow_mfma_call(A, flags, n_vecs)) return NARROW_MFMA;
+    if (narrow_call(flags, n_vecs)) return n_vecs > NARROW_MAX_VECS ? NARROW32 : NARROW;      // (beyond 8 columns: KN_FLAG_NARROW32 is in force)
+    if (flags & KN_FLAG_EXACT) return EXACT;
+    return (flags & KN_FLAG_BF16X3) ? BF16X3 : MFMA;
+}
 // KN_FLAG_NARROW_ROWS: an f32 CSR operator's pattern groups and loose rows on the row-lane kernel (kn_csr_narrow.hip) for at most NARROW_MAX_VECS columns, while the
 // kernel's 32-bit BYTE offsets into X hold; else the flag is ignored (the other kernels give the same bits).  The one place that reads the flag.
 static constexpr int NARROW_ROWS_COL_PAD = 80;
@@ -464,7 +497,6 @@ int convtaps_build_bf16(ConvTapsDev& A, const std::vector<float>& taps);
 int convtaps_build_fill(ConvTapsDev& A, hipStream_t s);
 int convtaps_build_pt(kn_operator* h);      // kn_api.hip (it reads the host description of the handle)
 bool convtaps_fill_ok(const ConvTapsDev& A);
-bool convtaps_bf16x3_ok(const ConvTapsDev& A, const float* x, int64_t ldx, int64_t n_vecs, const float* y, int64_t ldy);
 void csr_free(CsrDev& c);
 void convtaps_free(ConvTapsDev& c);
 

@@ -417,7 +417,7 @@ class KeyedModel(object):
                     # order-preserving conv kernels: 256-column tiles (four batch columns per lane).  They also have a 128-column form (two per lane), but
                     # that one is 5-8 % slower per layer (round 5, same-process A/B on every VGG-16 layer shape: conv5_1 4.08 against 3.88 ms) and the
                     # bit-exact forward of 256 images as two overlapped 128-column windows lost 11 % (1 884 against 2 107 images/s): not split.  MFMA tiles
-                    # are 128 (Cout > 64) or 256 columns wide
+                    # are 128 (Cout > 64) or 256 columns wide: this mirrors MfmaChoice::nb, the tile rule of mfma_choice in csrc/kn_conv.hip
                     ok = (half % 256 == 0) if la.exact else (half % (128 if c.W._outshape[0] > 64 else 256) == 0)
                     if la.flags & _capi.KN_FLAG_BF16X3:
                         with torch.cuda.device(device):          # kn_spmm_plan checks the current device like kn_spmm does

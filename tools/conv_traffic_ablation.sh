@@ -1,7 +1,7 @@
 #!/bin/bash
 # HBM traffic / speed trade of the conv-taps matrix-core kernel on the keyed VGG-16 forward (256 images), one variant per run:
 #   ball  = output pixels per breadth-first ball of the processing order (default 64: what one XCD's resident workgroups cover)
-#   occ   = workgroups per CU cap of the 128 x 128 launches (default: the rule of launch_conv, 4 or 3)
+#   occ   = workgroups per CU cap of the 128 x 128 launches (default: the rule of mfma_choice, 4 or 3)
 # Per variant: rocprofv3 --kernel-trace --pmc FETCH_SIZE (KiB; doubled per the guide's gfx950 note) and, separately, WRITE_SIZE over one warm forward;
 # the conv-taps time is the sum of the kernel-trace durations of the same launches.  Diagnostic build (-DKN_ABLATION) under /tmp.
 #   gpurun --timeout 2400 -- 'bash tools/conv_traffic_ablation.sh gpurun_out/r05_abl > gpurun_out/r05_conv_traffic_ablation.txt 2>&1'

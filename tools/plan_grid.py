@@ -5,7 +5,8 @@ prints, per operator, kn_nnz / kn_nnz_expanded / a hash of kn_export_csr and one
 batches include 1, 2, 3, 4, 8 and 9 columns and the flags the three narrow ones (KN_FLAG_NARROW, _MFMA, _ROWS).  Float32 CSR operators close the list: three at every flag word, then (csr_cases) the shapes that reach
 every launch site of the three CSR sources, a kn_tiled_create operator and a kn_chain_create handle, at the flags a CSR handle reads (--csr: these alone); last
 (chain_cases) the operator stacks the whole-net kernel's GPU tests run, as kn_chain_create handles (--chain: these alone; the KN_CHAIN_NO_* knobs of a -DKN_ABLATION
-build are set in the environment of the whole run).  Nothing is
+build are set in the environment of the whole run), and (conv_cases) the conv-taps operators that reach every launch site of the matrix-core and narrow regimes, also at
+leading dimensions beyond 32-bit offsets and under KN_FLAG_NARROW32 (--conv: these alone).  Nothing is
 launched, so the KN_HOST_PACK_ONLY build answers on a machine without a GPU.  Two builds of the library dispatch alike when their outputs are byte-identical:
 
     KEYNET_HIP_LIB=/path/to/libkeynet_hip.so python tools/plan_grid.py > grid.txt
@@ -310,8 +311,63 @@ def chain_operators(out):
             out.write('%s n=%d: %s\n' % (name, n, buf.value.decode() if rc == 0 else 'rc=%d %s' % (rc, L.kn_last_error().decode())))
 
 
+# ---- conv-taps handles: every launch site of the matrix-core and the narrow regimes (mfma_choice / narrow_choice in kn_conv.hip) ----
+N32 = capi.KN_FLAG_NARROW32
+# leading dimensions that cross the 32-bit offset tests of a 36-pixel operator: the wave-uniform pointers of the 128-column tiles (1 << 21), the straight-line loaders
+# and the narrow kernels' size rule (1 << 22), everything (1 << 26)
+BIG_LDS = (1 << 21, 1 << 22, 1 << 26)
+
+
+def conv_cases():
+    """(name, make, [(n_vecs, flags), ...], environment switches that change its plan): the smallest operators that reach each site.  Sites only the occupancy
+    query decides (tail_split, occ_cap, the grid of the persistent small-K kernel) show on a machine with a GPU; the CPU-only build answers that query with 0."""
+    (NARROW, MFMA, BF16X3, EXACT) = (capi.KN_FLAG_NARROW, capi.KN_FLAG_NARROW_MFMA, capi.KN_FLAG_BF16X3, capi.KN_FLAG_EXACT)
+    wide = [(n, fl) for n in (128, 130, 256) for fl in (0, BF16X3)]
+    narrow = [(n, fl) for fl in (NARROW, MFMA, NARROW | EXACT) for n in (1, 2, 3, 4, 5, 8)] + [(n, fl | N32) for fl in (NARROW, MFMA) for n in (9, 16, 17, 24, 32)]
+    # small-K: the persistent kernel (one 64-channel tile), the one-shot kernel under KN_NO_SMALLK_PIPE and at two channel tiles; at 128 columns the KC = 4 tiles
+    yield ('conv cin=3 cout=64', lambda: factored(3, 64, 6), wide + narrow, (('KN_NO_SMALLK_PIPE', '1'),))
+    yield ('conv cin=3 cout=128', lambda: factored(3, 128, 6), wide, ())
+    # ten slots x 3 channels exceed the small-K contraction: the KC = 4 tiles with straight-line loaders (Cin < 4) at whole tiles, generic ones else
+    yield ('conv cin=3 cout=64 slots10', lambda: factored(3, 64, 6, per_pixel=10), wide, ())
+    yield ('conv cin=3 cout=128 slots10', lambda: factored(3, 128, 6, per_pixel=10), wide, ())
+    yield ('conv cin=5 cout=128', lambda: factored(5, 128, 6), wide, ())
+    # the KC = 16 tiles: wave-uniform pointers, per-thread pointers under KN_NO_SPTR, generic loaders at 130 columns and with coefficients under KN_NO_SPTR; bf16x3
+    for (cin, cout) in ((16, 64), (16, 128), (32, 128)):
+        for coef in (False, True):
+            yield ('conv cin=%d cout=%d coef=%d' % (cin, cout, coef), lambda: factored(cin, cout, 6, coef=coef), wide + (narrow if cin == 16 else []), (('KN_NO_SPTR', '1'),))
+    # more than 64 slots per pixel: slot groups
+    yield ('conv slots70 cin=32 cout=64', lambda: factored(32, 64, 9, per_pixel=70), wide, (('KN_NO_SPTR', '1'),))
+    yield ('conv slots70 cin=32 cout=128', lambda: factored(32, 128, 9, per_pixel=70), wide, (('KN_NO_SPTR', '1'),))
+    # several slots on one pixel pair: the narrow kernels that sum stored values (at most 16 columns per block beyond 8)
+    for coef in (False, True):
+        yield ('conv dup cin=16 cout=64 coef=%d' % coef, lambda: factored(16, 64, 6, coef=coef, dup=True), narrow, ())
+    # 2.4 MB of taps: the 9 .. 32 column kernel keeps the width's form (16 | 32 columns per block) on a small layer
+    yield ('conv cin=256 cout=256', lambda: factored(256, 256, 6), narrow, ())
+
+
+def conv_operators(out):
+    L = capi.lib()
+    buf = ctypes.create_string_buffer(4096)
+    for (name, make, calls, switches) in conv_cases():
+        for (k, v) in ((None, None),) + tuple(switches):
+            if k:
+                os.environ[k] = v
+            try:
+                op = make()
+            finally:
+                if k:
+                    del os.environ[k]
+            tag = name + ('[%s=%s]' % (k, v) if k else '')
+            for (n, fl) in calls:
+                for ld in (n, n + 1) + BIG_LDS:
+                    rc = L.kn_spmm_plan(op.handle, n, ld, ld, fl, buf, 4096)
+                    out.write('%s n=%d ld=%d flags=%d: %s\n' % (tag, n, ld, fl, buf.value.decode() if rc == 0 else 'rc=%d %s' % (rc, L.kn_last_error().decode())))
+
+
 def main():
     out = sys.stdout
+    if '--conv' in sys.argv[1:]:
+        return conv_operators(out)
     if '--csr' in sys.argv[1:]:
         return csr_operators(out)
     if '--chain' in sys.argv[1:]:
@@ -350,6 +406,7 @@ def main():
         report(name, capi.Operator.csr(M.shape, M.indptr.astype(np.int32), M.indices.astype(np.int32), M.data), out, export=False)
     csr_operators(out)
     chain_operators(out)
+    conv_operators(out)
 
 
 if __name__ == '__main__':
