@@ -101,6 +101,19 @@ enum kn_status {
                               Where it changes NOTHING (same kernels, same plan string, same bits as without it): without one of the two flags; at n_vecs <= 8; at n_vecs > 32;
                               on CSR, dense, float64 and chain handles.  kn_spmm_plan names the kernel, NV and the number of column blocks.  No reference counterpart. */
 
+#define KN_FLAG_NARROW64 0x80u  /* = 128.  A second MODIFIER of KN_FLAG_NARROW and KN_FLAG_NARROW_MFMA: with either of them on a conv-taps handle it opens the range 33 <= n_vecs <= 64.
+                              There the call is the order-preserving product -- bit for bit the result of KN_FLAG_EXACT, and of the same columns inside a wider batch -- on the
+                              software-pipelined kernel with ONE column per lane (convtaps_exact_pipe64_kernel: one wavefront = one output pixel x 16 | 8 output channels x one
+                              64-column tile, the packed multiplies and adds run over output-channel pairs, half the vector-ALU work per step of a 128-column tile, lanes beyond
+                              n_vecs masked).  No condition on the alignment of x and y or on ldx, ldy.  There is no matrix-core form at this width: KN_FLAG_NARROW_MFMA means
+                              KN_FLAG_NARROW here, and KN_FLAG_EXACT / KN_FLAG_BF16X3 next to the flags change nothing.
+                              Unlike KN_FLAG_NARROW / KN_FLAG_NARROW32 the range NEVER REFUSES: an operator without the pipeline's shape (filled-in operators: more than 64 slots
+                              per output pixel or a pixel pair hit twice) and a block beyond (D + 1) * ldx < 2^31 run what KN_FLAG_EXACT runs at that width -- same plan string,
+                              same bits.
+                              Where it changes NOTHING (same kernels, same plan string, same bits as without it): without one of the two flags; at n_vecs <= 32 (the call is what its
+                              other flags make it, KN_FLAG_NARROW32 included); at n_vecs > 64; on CSR, dense, float64 and chain handles; in kn_spmm_planes.  In particular KN_FLAG_EXACT
+                              alone at 64 columns keeps the generic kernel.  kn_spmm_plan names the form ("64-column tiles").  No reference counterpart. */
+
 typedef struct kn_operator* kn_handle_t;   /* opaque keyed operator resident in HBM */
 
 int         kn_abi_version(void);
@@ -222,6 +235,7 @@ int kn_export_csr_f64(kn_handle_t h, int32_t* indptr, int32_t* indices, double* 
  *                                                       straight-line loaders: 16 * HiWi * ldx < 2^31 (4 * for Cin < 16); else the generic loader
  *   conv-taps, KN_FLAG_EXACT, pipelined kernel          (D + 1) * ldx < 2^31                               else the plain order-preserving kernel
  *   conv-taps, KN_FLAG_EXACT, filled-in operators       4 * ldx < 2^24, 4 * HiWi * ldx < 2^32, HiWi < 2^24  else the plain order-preserving kernel
+ *   conv-taps, KN_FLAG_NARROW64 (33 <= n_vecs <= 64)    (D + 1) * ldx < 2^31                               else the plain order-preserving kernel
  *   CSR, KN_FLAG_NARROW_ROWS (n_vecs <= 8)               cols * ldx + 8 < 2^30                              else the kernels the call takes without the flag
  * The small-K matrix-core kernels of first-layer operators (slots * Cin + bias <= 28 contraction rows) form row * ldx in 64 bits and take any ldx.
  * KN_FLAG_NARROW / KN_FLAG_NARROW_MFMA (n_vecs <= 8 on a conv-taps operator) do NOT fall back: they return KN_ERR_UNSUPPORTED, Y untouched, unless (D + 1) * ldx + 8 < 2^31

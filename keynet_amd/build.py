@@ -4,6 +4,7 @@ import subprocess
 
 HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(HERE, 'csrc')
+INCLUDED = ['kn_internal.h', 'kn_conv_exact_pipe.inc']      # what the sources include from csrc/ (kn_conv_exact_pipe.inc: the body two kernels of kn_conv.hip share)
 SOURCES = ['kn_api.hip', 'kn_csr.hip', 'kn_csr_narrow.hip', 'kn_csr_f64.hip', 'kn_csr_mfma.hip', 'kn_conv.hip', 'kn_elementwise.hip', 'kn_chain.hip']
 LIB = os.path.join(HERE, 'libkeynet_hip.so')
 
@@ -12,7 +13,7 @@ def needs_build():
     if not os.path.exists(LIB):
         return True
     t = os.path.getmtime(LIB)
-    deps = [os.path.join(CSRC, s) for s in SOURCES] + [os.path.join(CSRC, 'kn_internal.h'), os.path.join(HERE, '..', 'include', 'keynet_hip.h')]
+    deps = [os.path.join(CSRC, s) for s in SOURCES] + [os.path.join(CSRC, h) for h in INCLUDED] + [os.path.join(HERE, '..', 'include', 'keynet_hip.h')]
     return any(os.path.getmtime(d) > t for d in deps)
 
 
@@ -33,7 +34,7 @@ def build(force=False, verbose=False, out=None, defines=(), extra=()):
     variant = out is not None or defines or extra
     objdir = tempfile.mkdtemp(prefix='kn_obj_') if variant else os.path.join(HERE, 'build')
     os.makedirs(objdir, exist_ok=True)
-    headers = [os.path.join(CSRC, 'kn_internal.h'), os.path.join(HERE, '..', 'include', 'keynet_hip.h')]
+    headers = [os.path.join(CSRC, h) for h in INCLUDED] + [os.path.join(HERE, '..', 'include', 'keynet_hip.h')]
     tag = hashlib.sha256(' '.join(flags).encode()).hexdigest()[:8]
 
     def compile_one(src):

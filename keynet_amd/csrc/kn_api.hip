@@ -976,6 +976,7 @@ static int spmm_impl(kn_handle_t h, const float* x_dev, int64_t ldx, int64_t n_v
         switch (conv_regime(h->ct, flags, n_vecs)) {
             case NARROW_MFMA: rc = first_use(h, h->ct.pt_rec, [&] { return convtaps_build_pt(h); }); break;
             case BF16X3: rc = first_use(h, h->ct.tapsB, [&] { return convtaps_build_bf16(h->ct, h->h_taps); }); break;
+            case NARROW64:
             case EXACT: if (convtaps_fill_ok(h->ct)) rc = first_use(h, h->ct.fill_rec, [&] { return convtaps_build_fill(h->ct, s); }); break;
             default: break;
         }

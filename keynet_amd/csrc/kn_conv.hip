@@ -2138,273 +2138,26 @@ __global__ __launch_bounds__(256, 2) void convtaps_exact_fill_kernel(ConvArgs p,
 // VEC = batch columns per lane: 4 (a wavefront covers 256 columns, 16-byte row loads) or 2 (128 columns, 8-byte loads: the half-batch windows of the
 // overlapped forward at 256 images, and batches that fill 128-column tiles better than 256-column ones).  Same instruction count per MAC either way
 // (one packed multiply and one packed add per output channel and column pair); what VEC = 2 halves is the work per wavefront -- finer balance.
+// VEC = 1 (KN_FLAG_NARROW64: 33 .. 64 columns, convtaps_exact_pipe64_kernel below): ONE column per lane, and the packed instructions run over output-channel PAIRS
+// instead -- RBX / 2 packed multiplies and RBX / 2 packed adds per step where VEC = 2 on a padded 128-column tile issues RBX of each, half of every pair on padding.
+// The aligned SGPR tap pair {a[r], a[r + 1]} is one source, both halves read straight; the activation is the other, the low half of a VGPR pair broadcast to both
+// halves by op_sel_hi (the pair's high half is never written or read: the row load fills the low register, no v_mov per step -- read off the compiled ISA).  A
+// lane's sum for channel r is still "product rounded, then added, channel outer, slots ascending inner": the bits of the other forms.  The row load is one dword
+// per lane (a 256-byte row), lanes beyond n_vecs load column 0 and store nothing: every width 33 .. 64 is one form, with no condition on alignment or leading dimensions.
+// With half the packed instructions a step is bound by its scalar instructions, so this form fetches both operands through ONE cursor (see the body; measured 1.07x -> 1.51x
+// against the padded 128-column forward of keyed VGG-16, profiles/r11_narrow64.txt).
 template <int RBX, bool COEF = false, int XD = 2, int VEC = 4>       // XD = activation rows in flight per wavefront (2, or 4 for wide batches: see the launcher)
 __global__ __launch_bounds__(256) void convtaps_exact_pipe_kernel(ConvArgs p, int n_cob, int64_t n_rb) {
-    static_assert(VEC == 4 || VEC == 2, "two or four batch columns per lane");
-    constexpr int NP = VEC / 2;                                           // column pairs per lane
-    typedef float xrow_t __attribute__((ext_vector_type(VEC)));
-    const int64_t n_ct = (p.n_vecs + 64 * VEC - 1) / (64 * VEC);
-    const int64_t n_items = n_ct * n_rb;
-    const int64_t chunk = (n_items + 7) >> 3;
-    const int64_t xl = blockIdx.x & 7;
-    const int64_t item = xl * chunk + (blockIdx.x >> 3);
-    if (item >= ((xl + 1) * chunk < n_items ? (xl + 1) * chunk : n_items)) return;
-    const int64_t ct = item / n_rb;
-    const int64_t rb = item - ct * n_rb;
-    const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
-    const int lane = threadIdx.x & 63;
-    const int64_t w = rb * 4 + wave;
-    if (w >= (int64_t)p.n_pix * n_cob) return;
-    // wave-uniform by construction; pinned to SGPRs here so that the whole step-advance logic below stays on the scalar ALU (a value
-    // that comes out of a vector-memory load counts as divergent for the compiler, and would drag the loop counters into VGPRs)
-    // w -> (channel-bundle group, pixel, bundle inside the group), bundle fastest: the bundles of a pixel that run side by side share its gathered
-    // activation rows in L2.  G = p.tail_main bundles per group (0 = all n_cob: one group).  With G = n_cob / 8 every XCD's contiguous share of the
-    // items is ONE group over all pixels, so its slice of the taps (1/8 of 9.4 MB on the 512-channel layers) stays L2-resident for the scalar loads.
-    const int G = p.tail_main > 0 ? p.tail_main : n_cob;
-    const int64_t per_group = (int64_t)p.n_pix * G;
-    const int cg = (int)(w / per_group);
-    const int64_t rem = w - (int64_t)cg * per_group;
-    const int o = __builtin_amdgcn_readfirstlane(p.pix_order[rem / G]);
-    const int co0 = __builtin_amdgcn_readfirstlane((cg * G + (int)(rem % G)) * RBX);
-    const int s_beg = __builtin_amdgcn_readfirstlane(p.pix_ptr[o]);
-    const int n_slots = __builtin_amdgcn_readfirstlane(p.pix_ptr[o + 1]) - s_beg;
-    const int64_t c = ct * (64 * VEC) + (int64_t)lane * VEC;
-    const bool active = c < p.n_vecs;
-    const uint32_t lane_off_bytes = 4u * (uint32_t)(active ? c : 0);      // byte offset: (uniform base) + zext(VGPR) selects the saddr load form
+    static_assert(VEC == 4 || VEC == 2, "two or four batch columns per lane (one: convtaps_exact_pipe64_kernel)");
+#include "kn_conv_exact_pipe.inc"
+}
 
-    typedef float f32x2 __attribute__((ext_vector_type(2)));
-    f32x2 acc[RBX][NP];                                                   // [output channel][columns 0-1 | 2-3]
-#pragma unroll
-    for (int r = 0; r < RBX; r++)
-#pragma unroll
-        for (int h = 0; h < NP; h++) acc[r][h] = f32x2{0.f, 0.f};
-
-    if (n_slots > 0) {
-        // lane s: element offsets of slot s (32-bit: the launcher checks the ranges)
-        int my_xoff = 0, my_aoff = 0;
-        float my_coef = 1.0f;                                     // COEF: lane s = coefficient of slot s
-        if (lane < n_slots) {
-            my_xoff = p.slot_in[s_beg + lane] * (int)p.ldx;
-            my_aoff = p.slot_tap[s_beg + lane] * (p.cin_pad * p.cout_pad);
-            if constexpr (COEF) my_coef = p.slot_coef[s_beg + lane];
-        }
-        const int ch_x = __builtin_amdgcn_readfirstlane(p.HiWi * (int)p.ldx);      // one input channel of X
-        const float* a_base = p.tapsT + co0;
-        const int n_q = n_slots * p.Cin;
-        // two wave-uniform cursors over the steps (slot inner, channel outer): the activation rows may run further ahead than the tap values
-        int s = 0, ci_x = 0, q_next = 0;                         // cursor of the activation-row requests
-        int s_a = 0, ci_a = 0, q_a = 0;                          // cursor of the tap-value requests
-        // Operand fetch of one step, written as inline asm so that both addresses stay scalar: the activation row is a saddr-form vector
-        // load (wave-uniform 64-bit base in SGPRs + the lane's constant byte offset: no per-step vector address arithmetic), the step's
-        // RBX tap values one s_load into an SGPR tuple that the packed multiplies read directly.  The compiler's waitcnt bookkeeping does
-        // not see these loads; the waits are written out below.  Each fetch advances its cursor, branch-free (selects on wave-uniform
-        // values, all on the scalar ALU); past the end the last step's operands are fetched again, so the waits stay counted ones.
-        typedef float taps_t __attribute__((ext_vector_type(RBX)));
-        auto fetch_x = [&](xrow_t& xr) {
-            const int xo = __builtin_amdgcn_readlane(my_xoff, s) + ci_x;
-            const uint64_t xaddr = reinterpret_cast<uint64_t>(p.X + xo);
-            if constexpr (VEC == 4) asm volatile("global_load_dwordx4 %0, %1, %2" : "=&v"(xr) : "v"(lane_off_bytes), "s"(xaddr));
-            else asm volatile("global_load_dwordx2 %0, %1, %2" : "=&v"(xr) : "v"(lane_off_bytes), "s"(xaddr));
-            q_next++;
-            const bool more = q_next < n_q;
-            const bool wrap = (s + 1 == n_slots);
-            s = more ? (wrap ? 0 : s + 1) : s;
-            ci_x = __builtin_amdgcn_readfirstlane(ci_x + ((more && wrap) ? ch_x : 0));
-        };
-        auto fetch_a = [&](taps_t& ar, float& cf) {
-            const int ao = __builtin_amdgcn_readlane(my_aoff, s_a) + ci_a;
-            const uint64_t aaddr = reinterpret_cast<uint64_t>(a_base + ao);
-            if constexpr (RBX == 16) asm volatile("s_load_dwordx16 %0, %1, 0x0" : "=&s"(ar) : "s"(aaddr));
-            else asm volatile("s_load_dwordx8 %0, %1, 0x0" : "=&s"(ar) : "s"(aaddr));
-            if constexpr (COEF) cf = __builtin_bit_cast(float, __builtin_amdgcn_readlane(__builtin_bit_cast(int, my_coef), s_a));
-            q_a++;
-            const bool more = q_a < n_q;
-            const bool wrap = (s_a + 1 == n_slots);
-            s_a = more ? (wrap ? 0 : s_a + 1) : s_a;
-            ci_a = ci_a + ((more && wrap) ? p.cout_pad : 0);
-        };
-        auto advance = [&]() {};                                 // (the fetches advance their own cursors)
-        // the "+" operands make the multiplies that follow depend on the wait
-        auto taps_landed = [&](taps_t& ar) { asm volatile("s_waitcnt lgkmcnt(0)" : "+s"(ar)); };
-        auto row_landed = [&](xrow_t& xr, auto younger) {                 // vector loads return in order
-            asm volatile("s_waitcnt vmcnt(%1)" : "+v"(xr) : "n"(decltype(younger)::value));
-        };
-        // acc[r] += x * av[r] (separate IEEE multiply and add).  The packed multiply reads an aligned SGPR pair and broadcasts its low
-        // or high half with op_sel, so one pair serves two output channels.  The instruction order is pinned (volatile asm): the four
-        // multiplies of channel pair k are followed by the four adds of pair k-1, so no add waits on the multiply right in front of it
-        // (left to itself the scheduler serialises "mul, add, mul, add" through one temporary in the second half of the loop body).
-        // mul4: the four products of ONE channel pair (VEC = 4: two column pairs x two channels) or of TWO channel pairs (VEC = 2: one column pair x
-        // four channels); add4 adds them to their running sums.  `r` is the first of the 2 (VEC = 4) or 4 (VEC = 2) channels a call covers.
-        auto mul4 = [&](const f32x2& xlo, const f32x2& xhi, const f32x2& a2, const f32x2& b2, f32x2 (&pr)[4]) {
-            if constexpr (VEC == 4) {
-                asm volatile("v_pk_mul_f32 %0, %1, %2 op_sel_hi:[1,0]" : "=v"(pr[0]) : "v"(xlo), "s"(a2));
-                asm volatile("v_pk_mul_f32 %0, %1, %2 op_sel_hi:[1,0]" : "=v"(pr[1]) : "v"(xhi), "s"(a2));
-                asm volatile("v_pk_mul_f32 %0, %1, %2 op_sel:[0,1] op_sel_hi:[1,1]" : "=v"(pr[2]) : "v"(xlo), "s"(a2));
-                asm volatile("v_pk_mul_f32 %0, %1, %2 op_sel:[0,1] op_sel_hi:[1,1]" : "=v"(pr[3]) : "v"(xhi), "s"(a2));
-            } else {
-                asm volatile("v_pk_mul_f32 %0, %1, %2 op_sel_hi:[1,0]" : "=v"(pr[0]) : "v"(xlo), "s"(a2));
-                asm volatile("v_pk_mul_f32 %0, %1, %2 op_sel:[0,1] op_sel_hi:[1,1]" : "=v"(pr[1]) : "v"(xlo), "s"(a2));
-                asm volatile("v_pk_mul_f32 %0, %1, %2 op_sel_hi:[1,0]" : "=v"(pr[2]) : "v"(xlo), "s"(b2));
-                asm volatile("v_pk_mul_f32 %0, %1, %2 op_sel:[0,1] op_sel_hi:[1,1]" : "=v"(pr[3]) : "v"(xlo), "s"(b2));
-            }
-        };
-        auto add4 = [&](int r, const f32x2 (&pr)[4]) {
-            if constexpr (VEC == 4) {
-                asm volatile("v_pk_add_f32 %0, %1, %0" : "+v"(acc[r][0]) : "v"(pr[0]));
-                asm volatile("v_pk_add_f32 %0, %1, %0" : "+v"(acc[r][NP - 1]) : "v"(pr[1]));
-                asm volatile("v_pk_add_f32 %0, %1, %0" : "+v"(acc[r + 1][0]) : "v"(pr[2]));
-                asm volatile("v_pk_add_f32 %0, %1, %0" : "+v"(acc[r + 1][NP - 1]) : "v"(pr[3]));
-            } else {
-                asm volatile("v_pk_add_f32 %0, %1, %0" : "+v"(acc[r][0]) : "v"(pr[0]));
-                asm volatile("v_pk_add_f32 %0, %1, %0" : "+v"(acc[r + 1][0]) : "v"(pr[1]));
-                asm volatile("v_pk_add_f32 %0, %1, %0" : "+v"(acc[r + 2][0]) : "v"(pr[2]));
-                asm volatile("v_pk_add_f32 %0, %1, %0" : "+v"(acc[r + 3][0]) : "v"(pr[3]));
-            }
-        };
-        // COEF (float keys whose entries carry a coefficient): the stored non-zero of the reference is fl(coef * tap) -- one more packed
-        // multiply per channel pair, tap pair (SGPR) x the step's coefficient (broadcast from a VGPR pair's low half), and the products
-        // are then formed from that VGPR pair.
-        auto mul4v = [&](const f32x2& xlo, const f32x2& xhi, const f32x2& a2, const f32x2& b2, f32x2 (&pr)[4]) {
-            if constexpr (VEC == 4) {
-                asm volatile("v_pk_mul_f32 %0, %1, %2 op_sel_hi:[1,0]" : "=v"(pr[0]) : "v"(xlo), "v"(a2));
-                asm volatile("v_pk_mul_f32 %0, %1, %2 op_sel_hi:[1,0]" : "=v"(pr[1]) : "v"(xhi), "v"(a2));
-                asm volatile("v_pk_mul_f32 %0, %1, %2 op_sel:[0,1] op_sel_hi:[1,1]" : "=v"(pr[2]) : "v"(xlo), "v"(a2));
-                asm volatile("v_pk_mul_f32 %0, %1, %2 op_sel:[0,1] op_sel_hi:[1,1]" : "=v"(pr[3]) : "v"(xhi), "v"(a2));
-            } else {
-                asm volatile("v_pk_mul_f32 %0, %1, %2 op_sel_hi:[1,0]" : "=v"(pr[0]) : "v"(xlo), "v"(a2));
-                asm volatile("v_pk_mul_f32 %0, %1, %2 op_sel:[0,1] op_sel_hi:[1,1]" : "=v"(pr[1]) : "v"(xlo), "v"(a2));
-                asm volatile("v_pk_mul_f32 %0, %1, %2 op_sel_hi:[1,0]" : "=v"(pr[2]) : "v"(xlo), "v"(b2));
-                asm volatile("v_pk_mul_f32 %0, %1, %2 op_sel:[0,1] op_sel_hi:[1,1]" : "=v"(pr[3]) : "v"(xlo), "v"(b2));
-            }
-        };
-        auto mac = [&](const xrow_t& xv, const taps_t& av, const float cf) {
-            const f32x2 xlo = {xv[0], xv[1]}, xhi = {xv[VEC - 2], xv[VEC - 1]};
-            f32x2 pa[4], pb[4];
-            constexpr int CH = (VEC == 4) ? 2 : 4;                       // channels per mul4 / add4
-            if constexpr (COEF) {
-                const f32x2 cf2 = {cf, cf};
-                f32x2 sa, sb, sc, sd;
-#pragma unroll
-                for (int r = 0; r < RBX; r += 2 * CH) {
-                    asm volatile("v_pk_mul_f32 %0, %1, %2 op_sel_hi:[1,0]" : "=v"(sa) : "s"(f32x2{av[r], av[r + 1]}), "v"(cf2));
-                    asm volatile("v_pk_mul_f32 %0, %1, %2 op_sel_hi:[1,0]" : "=v"(sb) : "s"(f32x2{av[r + 2], av[r + 3]}), "v"(cf2));
-                    if constexpr (VEC == 2) {
-                        asm volatile("v_pk_mul_f32 %0, %1, %2 op_sel_hi:[1,0]" : "=v"(sc) : "s"(f32x2{av[r + 4], av[r + 5]}), "v"(cf2));
-                        asm volatile("v_pk_mul_f32 %0, %1, %2 op_sel_hi:[1,0]" : "=v"(sd) : "s"(f32x2{av[r + 6], av[r + 7]}), "v"(cf2));
-                    }
-                    if (r > 0) add4(r - CH, pb);
-                    if constexpr (VEC == 4) {
-                        mul4v(xlo, xhi, sa, sa, pa);
-                        mul4v(xlo, xhi, sb, sb, pb);
-                    } else {
-                        mul4v(xlo, xhi, sa, sb, pa);
-                        mul4v(xlo, xhi, sc, sd, pb);
-                    }
-                    add4(r, pa);
-                }
-                add4(RBX - CH, pb);
-                return;
-            }
-#pragma unroll
-            for (int r = 0; r < RBX; r += 2 * CH) {
-                if constexpr (VEC == 4) mul4(xlo, xhi, f32x2{av[r], av[r + 1]}, f32x2{av[r], av[r + 1]}, pa);
-                else mul4(xlo, xhi, f32x2{av[r], av[r + 1]}, f32x2{av[r + 2], av[r + 3]}, pa);
-                if (r > 0) add4(r - CH, pb);
-                if constexpr (VEC == 4) mul4(xlo, xhi, f32x2{av[r + 2], av[r + 3]}, f32x2{av[r + 2], av[r + 3]}, pb);
-                else mul4(xlo, xhi, f32x2{av[r + 4], av[r + 5]}, f32x2{av[r + 6], av[r + 7]}, pb);
-                add4(r, pa);
-            }
-            add4(RBX - CH, pb);
-        };
-        // Two steps per trip, operands double-buffered.  Step q+1's tap load is issued right after step q's taps have landed (scalar
-        // loads return out of order, so lgkmcnt can only be waited to zero) and its activation row right after that; both have step q's
-        // 2*RBX packed multiplies / adds to land.  kn_order() keeps the compiler from moving the arithmetic across the fetches.
-        if constexpr (XD == 4) {
-            // FOUR activation rows in flight (wide batches: a gathered row of a [D, 4096] block misses L2 -- the grouped CSR pipeline's finding),
-            // tap values one step ahead as before.  One step: this step's taps have landed -> request the next step's -> wait for this step's
-            // row (three younger rows stay in flight) -> arithmetic -> request the row four steps ahead into the register just released.
-            xrow_t x0, x1, x2, x3;
-            taps_t a0, a1;
-            float c0 = 1.0f, c1 = 1.0f;
-            fetch_x(x0);
-            fetch_x(x1);
-            fetch_x(x2);
-            fetch_x(x3);
-            fetch_a(a0, c0);
-            auto step4 = [&](const int q, xrow_t& xq, taps_t& aq, float& cq, taps_t& an, float& cn) {
-                taps_landed(aq);
-                fetch_a(an, cn);
-                row_landed(xq, std::integral_constant<int, 3>());
-                kn_order();
-                if (q < n_q) mac(xq, aq, cq);
-                kn_order();
-                fetch_x(xq);
-            };
-            for (int q = 0; q < n_q; q += 4) {
-                step4(q, x0, a0, c0, a1, c1);
-                step4(q + 1, x1, a1, c1, a0, c0);
-                step4(q + 2, x2, a0, c0, a1, c1);
-                step4(q + 3, x3, a1, c1, a0, c0);
-            }
-            asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)" : "+v"(x0), "+v"(x1), "+v"(x2), "+v"(x3), "+s"(a0));
-        } else {
-        xrow_t x0, x1;
-        taps_t a0, a1;
-        float c0 = 1.0f, c1 = 1.0f;
-        fetch_x(x0);
-        fetch_a(a0, c0);
-        advance();
-        int q = 0;
-        for (; q + 1 < n_q; q += 2) {
-            taps_landed(a0);
-            fetch_x(x1);
-            fetch_a(a1, c1);
-            advance();
-            row_landed(x0, std::integral_constant<int, 1>());
-            kn_order();
-            mac(x0, a0, c0);
-            kn_order();
-            taps_landed(a1);
-            fetch_x(x0);
-            fetch_a(a0, c0);
-            advance();
-            row_landed(x1, std::integral_constant<int, 1>());
-            kn_order();
-            mac(x1, a1, c1);
-            kn_order();
-        }
-        taps_landed(a0);
-        row_landed(x0, std::integral_constant<int, 0>());
-        if (q < n_q) mac(x0, a0, c0);
-        }
-    }
-    if (!active) return;
-    const float* xlast = p.lastcol ? (p.X + p.last_in_row * p.ldx + c) : nullptr;
-    xrow_t xl4;
-#pragma unroll
-    for (int v = 0; v < VEC; v++) xl4[v] = 0.f;
-    if (xlast) xl4 = *reinterpret_cast<const xrow_t*>(xlast);
-#pragma unroll
-    for (int r = 0; r < RBX; r++) {
-        const int m = co0 + r;
-        if (m >= p.Cout) continue;
-        const int64_t row = (int64_t)m * p.HoWo + o;
-        xrow_t t;
-#pragma unroll
-        for (int v = 0; v < VEC; v++) t[v] = acc[r][v / 2][v % 2];
-        if (xlast) {
-            const float lc = p.lastcol[row];
-            if (lc != 0.0f) {
-                const xrow_t bp = xl4 * lc;
-                t = t + bp;
-            }
-        }
-        if (p.relu) {
-#pragma unroll
-            for (int v = 0; v < VEC; v++) t[v] = (t[v] < 0.0f) ? 0.0f : t[v];
-        }
-        __builtin_nontemporal_store(t, reinterpret_cast<xrow_t*>(p.Y + row * p.ldy + c));      // the output is not re-read by this launch (conv1_1: 1.33 -> 1.11 ms)
-    }
+// The pipeline at VEC = 1 (33 .. 64 columns, KN_FLAG_NARROW64): the same body under an entry point of its own -- its row loads are single dwords, where every
+// instantiation of the kernel above loads two or four per lane (which is what tests/test_isa_lint.py looks for under that name).
+template <int RBX, bool COEF = false, int XD = 2, int VEC = 1>
+__global__ __launch_bounds__(256) void convtaps_exact_pipe64_kernel(ConvArgs p, int n_cob, int64_t n_rb) {
+    static_assert(VEC == 1 && XD == 2, "one batch column per lane, two activation rows in flight");
+#include "kn_conv_exact_pipe.inc"
 }
 
 // (KN_FLAG_EXACT with the multiplies on the matrix pipe -- convtaps_exact_mfma_kernel, round 4 -- was bit-exact but measured 4-8 % SLOWER than the pipeline
@@ -2603,13 +2356,14 @@ struct ExactChoice {
     enum Kernel { TABLE, PIPE, FILL, PLAIN } kernel = PLAIN;
     int rbx = 8;              // PIPE: output channels per wavefront (16 | 8); the channel bundles n_cob / n_rb of PIPE and PLAIN follow from it
     int xd = 2;               // PIPE: activation rows in flight (2 | 4)
-    int vec = 1;              // PIPE: batch columns per lane (4 | 2); PLAIN: 4 | 1
+    int vec = 1;              // PIPE: batch columns per lane (4 | 2; 1: the NARROW64 regime); PLAIN: 4 | 1
     int64_t n_ct = 0;         // PIPE / PLAIN: column tiles of 64 * vec columns
     bool wide = false;        // FILL: 64 output channels per wavefront instead of 32
     bool tiles2 = false;      // FILL: two 64-column tiles per wavefront
 };
 
-static ExactChoice exact_choice(const ConvTapsDev& A, const ConvArgs& a) {
+// `narrow64`: the call's regime is NARROW64 (33 .. 64 columns) -- the pipeline with one column per lane where the operator has the pipeline's shape, else what EXACT takes
+static ExactChoice exact_choice(const ConvTapsDev& A, const ConvArgs& a, bool narrow64) {
     const int64_t n_vecs = a.n_vecs, ldx = a.ldx, ldy = a.ldy;
     const uintptr_t x = (uintptr_t)a.X, y = (uintptr_t)a.Y;
     ExactChoice c;
@@ -2622,7 +2376,8 @@ static ExactChoice exact_choice(const ConvTapsDev& A, const ConvArgs& a) {
     // tiles better than 256-column ones (384 images).  Tuning::exact_vec = 2 | 4 forces either where both apply (diagnostic build).
     const bool pipe2_ok = pipe_shape && n_vecs >= 128 && n_vecs % 2 == 0 && ldx % 2 == 0 && ldy % 2 == 0 && x % 8 == 0 && y % 8 == 0;
     const bool pipe2 = pipe2_ok && (A.tune.exact_vec == 2 || (A.tune.exact_vec != 4 && (!pipe4 || (n_vecs + 127) / 128 * 128 < (n_vecs + 255) / 256 * 256)));
-    const bool pipe = pipe4 || pipe2;
+    const bool pipe1 = pipe_shape && narrow64;                    // one 64-column tile, any width 33 .. 64, no condition on alignment or leading dimensions
+    const bool pipe = pipe4 || pipe2 || pipe1;
     c.vec = pipe2 ? 2 : (v4 ? 4 : 1);
     c.n_ct = (n_vecs + 64 * c.vec - 1) / (64 * c.vec);
     // 16 output channels per wavefront when that still leaves every SIMD several wavefronts, else 8
@@ -2770,6 +2525,11 @@ static ExactPipeKernel exact_pipe_kernel(bool coef) {
     return coef ? convtaps_exact_pipe_kernel<RBX, true, XD, VEC> : convtaps_exact_pipe_kernel<RBX, false, XD, VEC>;
 }
 
+template <int RBX>
+static ExactPipeKernel exact_pipe64_kernel(bool coef) {
+    return coef ? convtaps_exact_pipe64_kernel<RBX, true> : convtaps_exact_pipe64_kernel<RBX, false>;
+}
+
 typedef void (*NarrowKernel)(ConvArgs, int, int64_t);
 template <int NV, bool FULL>
 static NarrowKernel narrow_kernel_of(bool dups, bool coef) {
@@ -2907,8 +2667,8 @@ static int launch_narrow(const ConvTapsDev& A, const ConvArgs& a, const NarrowCh
     return exact_tail(A, a, s);
 }
 
-static int spmm_exact(const ConvTapsDev& A, ConvArgs& a, hipStream_t s) {
-    const ExactChoice c = exact_choice(A, a);
+static int spmm_exact(const ConvTapsDev& A, ConvArgs& a, bool narrow64, hipStream_t s) {
+    const ExactChoice c = exact_choice(A, a, narrow64);
     const int64_t n_vecs = a.n_vecs;
     const int n_cob = (int)((A.Cout + c.rbx - 1) / c.rbx);
     const int64_t n_rb = ((int64_t)a.n_pix * n_cob + 3) / 4;
@@ -2930,12 +2690,15 @@ static int spmm_exact(const ConvTapsDev& A, ConvArgs& a, hipStream_t s) {
         int rc = convtaps_exact_table_spmm(A, a.X, a.ldx, n_vecs, a.Y, a.ldy, a.relu, s);
         if (rc) return rc;
     } else if (c.kernel == ExactChoice::PIPE) {
-        // the ten instantiations: 16 | 8 channels x coefficients or not, on 128-column tiles or 256-column ones, the latter with four rows in flight for 16 channels only
+        // the ten instantiations: 16 | 8 channels x coefficients or not, on 128-column tiles or 256-column ones, the latter with four rows in flight for 16 channels only;
+        // and the four of convtaps_exact_pipe64_kernel (one 64-column tile: NARROW64)
         const bool coef = !A.unit_coef;
-        const ExactPipeKernel k = c.vec == 2 ? (c.rbx == 16 ? exact_pipe_kernel<16, 2, 2>(coef) : exact_pipe_kernel<8, 2, 2>(coef))
+        const ExactPipeKernel k = c.vec == 1 ? (c.rbx == 16 ? exact_pipe64_kernel<16>(coef) : exact_pipe64_kernel<8>(coef))
+                                  : c.vec == 2 ? (c.rbx == 16 ? exact_pipe_kernel<16, 2, 2>(coef) : exact_pipe_kernel<8, 2, 2>(coef))
                                   : c.rbx == 8 ? exact_pipe_kernel<8, 2, 4>(coef)
                                                : (c.xd == 4 ? exact_pipe_kernel<16, 4, 4>(coef) : exact_pipe_kernel<16, 2, 4>(coef));
-        KN_LAUNCH("convtaps_exact_pipe_kernel<" + std::to_string(c.rbx) + (coef ? ",coef" : "") + (c.vec == 2 ? ",128-column tiles" : (c.xd == 4 ? ",rows in flight=4" : "")) + ">", k, grid,
+        KN_LAUNCH("convtaps_exact_pipe_kernel<" + std::to_string(c.rbx) + (coef ? ",coef" : "") + (c.vec == 1 ? ",64-column tiles" : c.vec == 2 ? ",128-column tiles" : (c.xd == 4 ? ",rows in flight=4" : "")) + ">" +
+                      (c.vec == 1 ? " (convtaps_exact_pipe64_kernel: one column per lane, packed over channel pairs)" : ""), k, grid,
                   dim3(256), 0, s, a, n_cob, n_rb);
     } else if (c.kernel == ExactChoice::FILL) {
         const bool regs = A.ntaps <= 16;                         // taps held in registers (else one value-row load per slot: 32 channels x one tile only)
@@ -3070,7 +2833,8 @@ int convtaps_spmm(const ConvTapsDev& A, const float* x, int64_t ldx, int64_t n_v
         case NARROW_MFMA:
         case NARROW:
         case NARROW32: rc = launch_narrow(A, a, narrow_choice(A, a, regime), s); break;
-        case EXACT: rc = spmm_exact(A, a, s); break;
+        case NARROW64:
+        case EXACT: rc = spmm_exact(A, a, regime == NARROW64, s); break;
         default: {
             const MfmaChoice c = mfma_choice(A, a, regime == BF16X3);
             // every matrix-core kernel streams its tiles out through kn_store_tile: where the choice says so, max |Y| rides in the epilogues (tiles + conv_lastrow_kernel

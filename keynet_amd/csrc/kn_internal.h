@@ -394,8 +394,15 @@ static constexpr int64_t NARROW_MAX_VECS = 8;
 // KN_FLAG_NARROW32, a modifier of the two flags above: their column range is 1 .. NARROW32_MAX_VECS instead (9 .. 32 columns: convtaps_narrow32_kernel, and the matrix-core
 // kernel at NV = 16 | 32).  Alone, and on every handle kind but conv-taps, it changes nothing.  narrow_max is the one place that reads it.
 static constexpr int64_t NARROW32_MAX_VECS = 32;
-static inline int64_t narrow_max(uint32_t flags) { return (flags & KN_FLAG_NARROW32) ? NARROW32_MAX_VECS : NARROW_MAX_VECS; }
-static inline bool narrow_call(uint32_t flags, int64_t n_vecs) { return (flags & (KN_FLAG_NARROW | KN_FLAG_NARROW_MFMA)) && n_vecs <= narrow_max(flags); }
+// KN_FLAG_NARROW64, a second modifier of the two flags: it opens the range NARROW32_MAX_VECS + 1 .. NARROW64_MAX_VECS (33 .. 64 columns: the order-preserving pipeline with one
+// column per lane, ConvRegime NARROW64) and that range ALONE -- at 32 columns and fewer a call is what its other flags make it, KN_FLAG_NARROW32 included.  There is no
+// matrix-core form at that width: KN_FLAG_NARROW_MFMA means KN_FLAG_NARROW there (narrow_mfma_call).  Read in narrow_max only: the widest batch a call of n_vecs columns may have.
+static constexpr int64_t NARROW64_MAX_VECS = 64;
+static inline int64_t narrow_max(uint32_t flags, int64_t n_vecs) {
+    if ((flags & KN_FLAG_NARROW64) && n_vecs > NARROW32_MAX_VECS) return NARROW64_MAX_VECS;
+    return (flags & KN_FLAG_NARROW32) ? NARROW32_MAX_VECS : NARROW_MAX_VECS;
+}
+static inline bool narrow_call(uint32_t flags, int64_t n_vecs) { return (flags & (KN_FLAG_NARROW | KN_FLAG_NARROW_MFMA)) && n_vecs <= narrow_max(flags, n_vecs); }
 // The width a narrow launcher instantiates its kernel for: the next of 1 | 2 | 4 | 8 (| 16 | 32: KN_FLAG_NARROW32 calls only) columns, its log2, and whether the batch fills it
 // (else the columns beyond n_vecs are masked)
 struct NarrowWidth { int nv, log2; bool full; };
@@ -416,14 +423,17 @@ static inline bool narrow_mfma_loses(const ConvTapsDev& A, int64_t n_vecs) {
     return A.Cin <= 4 && n_vecs > 4 && A.Hout * A.Wout * ((A.Cout + 63) / 64) >= 4 * 1024;
 }
 static inline bool narrow_mfma_call(const ConvTapsDev& A, uint32_t flags, int64_t n_vecs) {
-    return (flags & KN_FLAG_NARROW_MFMA) && !(flags & KN_FLAG_EXACT) && n_vecs <= narrow_max(flags) && A.pt_ok && !narrow_mfma_loses(A, n_vecs);
+    return (flags & KN_FLAG_NARROW_MFMA) && !(flags & KN_FLAG_EXACT) && n_vecs <= narrow_max(flags, n_vecs) && n_vecs <= NARROW32_MAX_VECS && A.pt_ok && !narrow_mfma_loses(A, n_vecs);
 }
 // The regime a call on a conv-taps handle takes: the one place that turns the flag word into one.  convtaps_spmm switches on it, kn_spmm asks it which side table
 // the call reads.  BF16X3 is the REQUEST (its planes are built for it): operands that do not qualify run as MFMA (mfma_choice, kn_conv.hip).
-enum ConvRegime { NARROW_MFMA, NARROW, NARROW32, EXACT, BF16X3, MFMA };
+// NARROW64 is the order-preserving product under every contract flag, launched by the order-preserving launcher (spmm_exact): an operator without the pipeline's shape
+// runs what EXACT runs at that width, so the regime never refuses.
+enum ConvRegime { NARROW_MFMA, NARROW, NARROW32, NARROW64, EXACT, BF16X3, MFMA };
 static inline ConvRegime conv_regime(const ConvTapsDev& A, uint32_t flags, int64_t n_vecs) {
     if (narrow_mfma_call(A, flags, n_vecs)) return NARROW_MFMA;
-    if (narrow_call(flags, n_vecs)) return n_vecs > NARROW_MAX_VECS ? NARROW32 : NARROW;      // (beyond 8 columns: KN_FLAG_NARROW32 is in force)
+    if (narrow_call(flags, n_vecs))                                                            // (beyond 8 columns KN_FLAG_NARROW32 is in force, beyond 32 KN_FLAG_NARROW64)
+        return n_vecs > NARROW32_MAX_VECS ? NARROW64 : (n_vecs > NARROW_MAX_VECS ? NARROW32 : NARROW);
     if (flags & KN_FLAG_EXACT) return EXACT;
     return (flags & KN_FLAG_BF16X3) ? BF16X3 : MFMA;
 }

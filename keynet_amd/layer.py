@@ -209,7 +209,7 @@ class KeyedLayer(nn.Module):
     def iskeyedrelu(self):
         return 'ReLU' in self._layertype
 
-    def forward(self, x_affine, fuse_relu=False, absmax=None, narrow=False, narrow_rows=False, narrow32=False):
+    def forward(self, x_affine, fuse_relu=False, absmax=None, narrow=False, narrow_rows=False, narrow32=False, narrow64=False):
         """[N, Din+1] -> [N, Dout+1] (keynet/layer.py:88-93).  The result is a transposed view of the feature-major
         [Dout+1, N] block the kernel wrote, so the next layer's x.t() is free.  `fuse_relu` folds the unkeyed nn.ReLU
         that follows this layer in the key-net (keynet/system.py:92) into the kernel epilogue.  `absmax`: a one-element device
@@ -223,14 +223,16 @@ class KeyedLayer(nn.Module):
         `narrow_rows` (with `narrow`): a layer whose operator is a float32 CSR handle (W.rows_capable()) runs its stored-order product on the row-lane kernel
         (KN_FLAG_NARROW_ROWS, kernel()) -- the same bits; conv-taps layers and everything else are what `narrow` alone makes them.  Nothing is decided or recorded.
         `narrow32` (with `narrow`): at most KeyedModel.NARROW32_MAX images; a conv-taps layer gets KN_FLAG_NARROW32 next to its narrow flag (kernel()), every other
-        layer runs as without it."""
+        layer runs as without it.
+        `narrow64` (with `narrow`; implies `narrow32`): at most KeyedModel.NARROW64_MAX images; a conv-taps layer gets KN_FLAG_NARROW64 as well (kernel()) and runs, beyond
+        NARROW32_MAX images, the order-preserving pipeline with one column per lane; every other layer runs as without it, at the unpadded width."""
         if verbose():
             print('[keynet_amd.layer]: forward %s' % str(self))
         exact = getattr(self, '_exact', True)
         relu = fuse_relu or self.iskeyedrelu()
         form = {}                            # what `narrow` / `narrow_rows` make of this layer: the keyword its operator's torchdot takes, if any
         if narrow and self.W.narrow_capable():
-            form = dict(narrow=self.narrow_mode(narrow, x_affine.t(), relu) if narrow == 'mfma' else True, narrow32=bool(narrow32))
+            form = dict(narrow=self.narrow_mode(narrow, x_affine.t(), relu) if narrow == 'mfma' else True, narrow32=bool(narrow32 or narrow64), narrow64=bool(narrow64))
         elif narrow:
             if exact == 'auto':
                 exact = True                 # an undecided layer without a narrow form: the reference's order for this call, nothing decided or recorded
@@ -247,7 +249,7 @@ class KeyedLayer(nn.Module):
         return self.W.torchdot(x_affine.t(), relu=relu, exact=exact, absmax=absmax, **form).t()
 
     @staticmethod
-    def kernel(W, contract, relu, device=None, narrow=False, narrow_rows=False, narrow32=False):
+    def kernel(W, contract, relu, device=None, narrow=False, narrow_rows=False, narrow32=False, narrow64=False):
         """The one place that turns a decided contract into an operator handle and flags: (get_op, flags) of the kn_spmm launch that applies operator `W`
         under `contract`, get_op(device) -> the handle resident there.  None when that is not one launch: 'auto' (still to calibrate), 'split' on an operator that has a split form (Conv2dTiledMatrix._torchdot_split).
         The rules: 'split' forced on an operator without a split form, and 'bf16x3' on a non-conv operator, are the f32 matrix cores (False); a conv operator
@@ -264,7 +266,9 @@ class KeyedLayer(nn.Module):
         without a dense handle in play -- gets KN_FLAG_NARROW_ROWS (the row-lane kernel, the same bits) next to the flags it has without the keyword.  A float64
         operator, a plain SparseMatrix that a re-ordering contract put on its dense handle, and conv-taps operators keep what they have.
         `narrow32` (with `narrow`; a batch of at most KeyedModel.NARROW32_MAX columns): a narrow-capable operator gets KN_FLAG_NARROW32 next to the flags it has
-        without the keyword (the library then honours its narrow flag up to 32 columns); every other operator keeps its flags."""
+        without the keyword (the library then honours its narrow flag up to 32 columns); every other operator keeps its flags.
+        `narrow64` (with `narrow`; a batch of at most KeyedModel.NARROW64_MAX columns): a narrow-capable operator gets KN_FLAG_NARROW32 | KN_FLAG_NARROW64 next to its narrow
+        flag (at 33 .. 64 columns the library then runs the order-preserving pipeline with one column per lane, under every contract); every other operator keeps its flags."""
         conv = isinstance(W, ksp.Conv2dTiledMatrix)
         lane = bool(narrow) and W.narrow_capable()          # one launch of a narrow conv kernel, whatever the contract
         mfma = lane and narrow == 'mfma' and conv and contract in (False, 'bf16x3', 'split')      # (the library falls back to the channel-lane kernel on an ineligible operator)
@@ -280,18 +284,18 @@ class KeyedLayer(nn.Module):
         if mfma:
             (exact, bf16x3) = (False, False)
         return (get_op, (_capi.KN_FLAG_RELU if relu else 0) | (_capi.KN_FLAG_EXACT if exact else 0) | (_capi.KN_FLAG_BF16X3 if bf16x3 else 0) |
-                (_capi.KN_FLAG_NARROW_MFMA if mfma else _capi.KN_FLAG_NARROW if lane else 0) | (_capi.KN_FLAG_NARROW32 if lane and narrow32 else 0) |
+                (_capi.KN_FLAG_NARROW_MFMA if mfma else _capi.KN_FLAG_NARROW if lane else 0) | (_capi.KN_FLAG_NARROW32 if lane and (narrow32 or narrow64) else 0) | (_capi.KN_FLAG_NARROW64 if lane and narrow64 else 0) |
                 (_capi.KN_FLAG_NARROW_ROWS if rows else 0))
 
-    def launch(self, device, relu=False, narrow=False, narrow_rows=False, narrow32=False):
+    def launch(self, device, relu=False, narrow=False, narrow_rows=False, narrow32=False, narrow64=False):
         """This layer under its contract in force as one launch on `device` (`relu`: the unkeyed nn.ReLU behind it is fused in), or None when it is not one
         kn_spmm launch: see kernel(); a float64 operator (its own kernel and a float64 result: kn_spmm_f64).  What the key-net's planners read
-        (KeyedModel._chain_op / _overlap_plan); forward() -> W.torchdot() runs the same rule.  `narrow`, `narrow_rows`, `narrow32`: see kernel(); 'mfma' goes through narrow_mode() first, without a batch."""
+        (KeyedModel._chain_op / _overlap_plan); forward() -> W.torchdot() runs the same rule.  `narrow`, `narrow_rows`, `narrow32`, `narrow64`: see kernel(); 'mfma' goes through narrow_mode() first, without a batch."""
         W = self.W
         if narrow == 'mfma':
             narrow = self.narrow_mode(narrow)                 # (a calibrated layer without a narrow record yet: the channel-lane kernel -- forward() measures, a planner does not)
         kernel = None if W.is_float64() else self.kernel(W, getattr(self, '_exact', True), relu or self.iskeyedrelu(), device, narrow=narrow, narrow_rows=bool(narrow and narrow_rows),
-                                                               narrow32=bool(narrow and narrow32))
+                                                               narrow32=bool(narrow and narrow32), narrow64=bool(narrow and narrow64))
         if kernel is None:
             return None
         return Launch(kernel[0](device), kernel[1], int(W.shape[0]), int(W.shape[1]), isinstance(W, ksp.Conv2dTiledMatrix), 'Linear' in self._layertype,

@@ -80,20 +80,21 @@ def _device_block(x):
     return xd if xd.is_contiguous() else xd.contiguous()
 
 
-def _run_torchdot(W, x, relu=False, exact=True, absmax=None, narrow=False, narrow_rows=False, narrow32=False):
+def _run_torchdot(W, x, relu=False, exact=True, absmax=None, narrow=False, narrow_rows=False, narrow32=False, narrow64=False):
     """Y = W.X on the GPU under the contract `exact`, on the handle and flags of KeyedLayer.kernel.  x: [cols, N], torch tensor (any device / strides) or ndarray.
     Returns [rows, N] on x's device: float32, or for a float64 operator the float64 block scipy returns for it (kn_spmm_f64; the activations are
     float32 either way).  `narrow`: at most NARROW_MAX columns on the channel-lane kernel where W owns a conv-taps handle (KeyedLayer.kernel); 'mfma': on the
     matrix-core narrow kernel (KN_FLAG_NARROW_MFMA) where `exact` is a re-ordering contract, else exactly narrow=True.  `narrow_rows`: at most NARROW_MAX columns
     on the row-lane kernel (KN_FLAG_NARROW_ROWS) where W's device form is a float32 CSR handle run in the stored order (W.rows_capable(), KeyedLayer.kernel): the
-    same bits; every other operator is what it is without the keyword.  `narrow32` (with `narrow`): at most NARROW32_MAX columns (KN_FLAG_NARROW32)."""
+    same bits; every other operator is what it is without the keyword.  `narrow32` (with `narrow`): at most NARROW32_MAX columns (KN_FLAG_NARROW32).
+    `narrow64` (with `narrow`; implies `narrow32`): at most NARROW64_MAX columns (KN_FLAG_NARROW64: beyond NARROW32_MAX the order-preserving pipeline, one column per lane)."""
     from .layer import KeyedLayer            # (layer.py imports this module)
     x = torch.as_tensor(x)
     assert W.shape[1] == x.shape[0], 'Non-conformal shape for W=%s, x=%s' % (str(W.shape), str(tuple(x.shape)))
     xd = _device_block(x)
     n = xd.shape[1]
-    _narrow_args(n, narrow, narrow_rows, 'batch columns', alone=True, narrow32=narrow32)
-    kernel = KeyedLayer.kernel(W, exact, relu, xd.device, narrow=narrow, narrow_rows=narrow_rows, narrow32=narrow32)
+    _narrow_args(n, narrow, narrow_rows, 'batch columns', alone=True, narrow32=narrow32, narrow64=narrow64)
+    kernel = KeyedLayer.kernel(W, exact, relu, xd.device, narrow=narrow, narrow_rows=narrow_rows, narrow32=narrow32, narrow64=narrow64)
     if kernel is None:
         y = W._torchdot_split(xd, relu=relu, absmax=absmax)
     else:
@@ -112,20 +113,29 @@ def _run_torchdot(W, x, relu=False, exact=True, absmax=None, narrow=False, narro
 
 NARROW_MAX = 8        # widest batch of the channel-lane conv-taps kernel (KN_FLAG_NARROW; KeyedModel.NARROW_MAX)
 NARROW32_MAX = 32     # ... with narrow32=True (KN_FLAG_NARROW32: convtaps_narrow32_kernel, the matrix-core narrow kernel at NV = 16 | 32; KeyedModel.NARROW32_MAX)
+NARROW64_MAX = 64     # ... with narrow64=True (KN_FLAG_NARROW64: beyond NARROW32_MAX columns convtaps_exact_pipe64_kernel, no matrix-core form; KeyedModel.NARROW64_MAX)
 
 
-def _narrow_args(n, narrow, narrow_rows, what='images', alone=False, narrow32=False):
+def _narrow_args(n, narrow, narrow_rows, what='images', alone=False, narrow32=False, narrow64=False):
     """The argument rule of the narrow forms, for a batch of `n`: `narrow_rows` only together with `narrow` (`alone`: a container's torchdot, which takes one
     keyword or the other), at most NARROW_MAX columns; `narrow32` only together with `narrow`, whose limit it lifts to NARROW32_MAX -- not that of `narrow_rows`
-    (the row-lane kernel is an 8-column kernel).  ValueError, or the normalised (mode, rows): mode False | True | 'mfma', rows a bool."""
+    (the row-lane kernel is an 8-column kernel); `narrow64` only together with `narrow` as well: it implies `narrow32` (at most NARROW32_MAX columns the call is exactly
+    narrow32=True) and lifts the limit to NARROW64_MAX, where narrow='mfma' is refused beyond NARROW32_MAX (no matrix-core form at that width).
+    ValueError, or the normalised (mode, rows): mode False | True | 'mfma', rows a bool."""
     if narrow_rows and not narrow and not alone:
         raise ValueError('narrow_rows=True is a form of the narrow forward: pass narrow=True or narrow=\'mfma\' with it')
     if narrow32 and not narrow:
         raise ValueError('narrow32=True widens the narrow forward: pass narrow=True or narrow=\'mfma\' with it')
+    if narrow64 and not narrow:
+        raise ValueError('narrow64=True widens the narrow forward: pass narrow=True with it')
     if narrow_rows and n > NARROW_MAX:
         raise ValueError('narrow_rows=True takes at most %d %s, got %d' % (NARROW_MAX, what, n))
-    if narrow and n > (NARROW32_MAX if narrow32 else NARROW_MAX):
-        raise ValueError('narrow=%r%s takes at most %d %s, got %d' % (narrow, ', narrow32=True' if narrow32 else '', NARROW32_MAX if narrow32 else NARROW_MAX, what, n))
+    limit = NARROW64_MAX if narrow64 else (NARROW32_MAX if narrow32 else NARROW_MAX)
+    if narrow and n > limit:
+        raise ValueError('narrow=%r%s takes at most %d %s, got %d' % (narrow, ', narrow64=True' if narrow64 else (', narrow32=True' if narrow32 else ''), limit, what, n))
+    if narrow == 'mfma' and n > NARROW32_MAX:
+        raise ValueError('narrow=\'mfma\', narrow64=True: there is no matrix-core form at %d .. %d %s (got %d); the padded forward is the matrix-core path there, '
+                         'narrow=True the order-preserving one' % (NARROW32_MAX + 1, NARROW64_MAX, what, n))
     return (narrow if narrow == 'mfma' else bool(narrow), bool(narrow_rows))
 
 
@@ -305,10 +315,11 @@ class FactoredSparseMatrix(SparseMatrix):
     def rows_capable(self):
         return False                     # (a conv-taps handle on the device)
 
-    def torchdot(self, x_torch, relu=False, exact=True, absmax=None, narrow=False, narrow32=False):
+    def torchdot(self, x_torch, relu=False, exact=True, absmax=None, narrow=False, narrow32=False, narrow64=False):
         """SparseMatrix.torchdot; `narrow` (True or 'mfma': the same here, the operator is under the bit-exact contract): at most NARROW_MAX columns on the channel-lane kernel of the factored device form (KN_FLAG_NARROW) -- the
-        same bits as without it (the order-preserving product, which IS scipy's on the stored CSR); `narrow32` (with `narrow`): at most NARROW32_MAX columns (KN_FLAG_NARROW32)."""
-        return _run_torchdot(self, x_torch, relu=relu, exact=exact, absmax=absmax, narrow=narrow, narrow32=narrow32)
+        same bits as without it (the order-preserving product, which IS scipy's on the stored CSR); `narrow32` (with `narrow`): at most NARROW32_MAX columns (KN_FLAG_NARROW32);
+        `narrow64` (with `narrow`): at most NARROW64_MAX (KN_FLAG_NARROW64)."""
+        return _run_torchdot(self, x_torch, relu=relu, exact=exact, absmax=absmax, narrow=narrow, narrow32=narrow32, narrow64=narrow64)
 
     @staticmethod
     def proven(M, factored, max_zero_fraction=0.01):
@@ -624,7 +635,7 @@ class Conv2dTiledMatrix(TiledMatrix):
     def rows_capable(self):
         return False                     # (a conv-taps handle on the device)
 
-    def torchdot(self, x, relu=False, exact=False, absmax=None, narrow=False, narrow32=False):
+    def torchdot(self, x, relu=False, exact=False, absmax=None, narrow=False, narrow32=False, narrow64=False):
         """[cols, N] -> [rows, N].  exact=False: f32 MFMA path (f32-input matrix instructions, exact f32 products); exact=True: the
         reference's accumulation order and rounding (order-preserving kernel on the factored operator); exact='split': a filled-in factored
         operator applied as spatial mixing per tap, then channel mixing (see _split_ops: another association of the sum, tolerance contract only); exact='bf16x3': f32 products
@@ -634,9 +645,11 @@ class Conv2dTiledMatrix(TiledMatrix):
         (KN_FLAG_NARROW_MFMA: an implicit GEMM over output pixels x images, another association of the sum) when `exact` is False / 'bf16x3' / 'split' and the
         operator is eligible (no (pixel, tap) pair with more than two slots); under True / 'auto', and on an ineligible operator, exactly narrow=True.
         narrow32=True (with `narrow`): N <= NARROW32_MAX -- beyond NARROW_MAX columns convtaps_narrow32_kernel (the bits of exact=True), or the matrix-core narrow
-        kernel at NV = 16 | 32 (per column the bits of narrow='mfma' on that column)."""
+        kernel at NV = 16 | 32 (per column the bits of narrow='mfma' on that column).
+        narrow64=True (with `narrow`; implies narrow32): N <= NARROW64_MAX -- beyond NARROW32_MAX columns the order-preserving pipeline with one column per lane
+        (KN_FLAG_NARROW64, convtaps_exact_pipe64_kernel; a filled-in operator: what exact=True runs at that width), the bits of exact=True; narrow='mfma' is refused there."""
         assert not isinstance(exact, str) or exact in ('bf16x3', 'split') or (narrow and exact == 'auto'), "exact must be True, False, 'bf16x3' or 'split'"
-        return _run_torchdot(self, x, relu=relu, exact=exact, absmax=absmax, narrow=narrow, narrow32=narrow32)
+        return _run_torchdot(self, x, relu=relu, exact=exact, absmax=absmax, narrow=narrow, narrow32=narrow32, narrow64=narrow64)
 
     # ---- the SPLIT application of a filled-in operator (tolerance contract only) -----------------------------------------------------
     # A factored keyed conv is  sum_t F_t (x) K_t  with F_t the Cout x Cin matrix of tap t and K_t = a_out S_t a_in^-1 the HoWo x HiWi spatial

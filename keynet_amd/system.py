@@ -177,8 +177,9 @@ class KeyedModel(object):
 
     NARROW_MAX = ksp.NARROW_MAX    # forward_linear(narrow=True) takes at most this many images (the channel-lane conv-taps kernel keeps one running sum per image and lane)
     NARROW32_MAX = ksp.NARROW32_MAX    # ... with narrow32=True (convtaps_narrow32_kernel: the columns in blocks of 8 | 16 | 32 running sums per lane)
+    NARROW64_MAX = ksp.NARROW64_MAX    # ... with narrow64=True (beyond NARROW32_MAX images convtaps_exact_pipe64_kernel: one column per lane, packed over output-channel pairs)
 
-    def forward_linear(self, img_cipher, overlap=None, narrow=False, narrow_rows=False, narrow32=False):
+    def forward_linear(self, img_cipher, overlap=None, narrow=False, narrow_rows=False, narrow32=False, narrow64=False):
         """[N, D0+1] -> [N, classes+1]: the nn.Sequential of keynet/system.py:132 with the unkeyed ReLUs fused into the
         producing layer's kernel epilogue.  Stream-ordered on torch's current HIP stream.  Host synchronisation: none for key-nets whose
         layers all run under a DECLARED contract (exact=True: the permutation key-nets; exact=False: forced); a key-net with layers on the
@@ -220,10 +221,16 @@ class KeyedModel(object):
         `narrow32=True` (only together with `narrow`, ValueError otherwise): the same forward for up to NARROW32_MAX images (ValueError beyond; `narrow_rows` stays
         at NARROW_MAX).  Beyond NARROW_MAX images the conv-taps layers run convtaps_narrow32_kernel (narrow=True: the bits of exact=True, as at 1 .. 8) or the
         matrix-core narrow kernel at 16 | 32 columns per pixel (narrow='mfma': per image the bits of narrow='mfma' on that image; a calibrated layer is measured on the
-        8 images that hold the batch's largest |x| and screened as at 1 .. 8); every other layer runs as it does without the keyword, at the unpadded width."""
-        (mode, rows) = ksp._narrow_args(img_cipher.shape[0], narrow, narrow_rows, narrow32=narrow32)
+        8 images that hold the batch's largest |x| and screened as at 1 .. 8); every other layer runs as it does without the keyword, at the unpadded width.
+        `narrow64=True` (only together with `narrow`, ValueError otherwise): the same forward for up to NARROW64_MAX images (ValueError beyond; `narrow_rows` stays at
+        NARROW_MAX).  It implies `narrow32`: a service passes one set of keywords for any batch of at most 64 images, and at NARROW32_MAX images and fewer the call is
+        exactly narrow32=True.  Beyond, the conv-taps layers run the order-preserving pipeline with one image per lane (KN_FLAG_NARROW64: convtaps_exact_pipe64_kernel, half
+        the packed instructions per step of the padded 128-image tile; a filled-in operator runs what exact=True runs at that width) -- the bits of exact=True under every
+        contract, so the forward of a key-net under the bit-exact contract equals the padded one bit for bit.  Nothing is padded, calibrated, screened, decided or recorded.
+        There is no matrix-core form at 33 .. 64 images: narrow='mfma' is a ValueError there (the padded forward is the matrix-core path)."""
+        (mode, rows) = ksp._narrow_args(img_cipher.shape[0], narrow, narrow_rows, narrow32=narrow32, narrow64=narrow64)
         (x, windows) = self._prepare(img_cipher, mode)
-        y = self._forward_passes(x, windows, False if mode else overlap, mode, rows, bool(narrow32))[0][:img_cipher.shape[0]]
+        y = self._forward_passes(x, windows, False if mode else overlap, mode, rows, bool(narrow32), bool(narrow64))[0][:img_cipher.shape[0]]
         return y if img_cipher.is_cuda else y.to(img_cipher.device)
 
     def _prepare(self, x, narrow=False):
@@ -258,11 +265,11 @@ class KeyedModel(object):
             x = x.detach().t().contiguous().t()
         return (x, windows)
 
-    def _forward_passes(self, x, windows, overlap, narrow=False, rows=False, narrow32=False):
+    def _forward_passes(self, x, windows, overlap, narrow=False, rows=False, narrow32=False, narrow64=False):
         """The screened forward of a prepared batch: (y, screens).  A pass whose screen re-calibrates a layer runs again (calibrating on its own images),
         then every other pass again: the batch comes out of ONE set of contracts.  At most RESCREEN_MAX_PASSES runs of a pass; then only the last pass is
         re-screened (the next forward decides).  Under a HIP-graph capture nothing is read: `screens` = (slots, screened) per pass, for capture's replay.
-        `narrow` / `rows` / `narrow32` (the normalised keywords narrow, narrow_rows, narrow32 of forward_linear): the screened layers are those a MEASUREMENT put on the matrix-core narrow kernel (none under
+        `narrow` / `rows` / `narrow32` / `narrow64` (the normalised keywords narrow, narrow_rows, narrow32, narrow64 of forward_linear): the screened layers are those a MEASUREMENT put on the matrix-core narrow kernel (none under
         narrow=True; an 'auto' layer does not switch the screen off: it runs in the reference's order for this call), screened against their narrow records; layers
         measured during a pass were measured on this very batch, so only the records that existed before it are screened."""
         keyed = self._keyed()
@@ -278,7 +285,7 @@ class KeyedModel(object):
             slots = torch.zeros(len(keyed) + 1, dtype=torch.float32, device=x.device) if screened else None
             (lo, hi) = windows[k]
             # (a window of a wider block: its own feature-major block, so that the pass can take the overlapped form)
-            ys[k] = self._forward_once(x if len(windows) == 1 else x[lo:hi].t().contiguous().t(), keyed, overlap, slots, screened, narrow, rows, narrow32)
+            ys[k] = self._forward_once(x if len(windows) == 1 else x[lo:hi].t().contiguous().t(), keyed, overlap, slots, screened, narrow, rows, narrow32, narrow64)
             if slots is None:
                 continue
             screens.append((slots, screened))
@@ -308,10 +315,10 @@ class KeyedModel(object):
     BATCH_TILE = 128           # _prepare pads a device batch of a tiled-conv key-net to whole multiples of this many images
     MAX_BLOCK_ELEMENTS = 1 << 31   # ... and splits a batch whose largest layer would hold this many activations or more into passes
 
-    def _forward_once(self, img_cipher, keyed, overlap, slots, screened, narrow=False, rows=False, narrow32=False):
+    def _forward_once(self, img_cipher, keyed, overlap, slots, screened, narrow=False, rows=False, narrow32=False, narrow64=False):
         """One pass over the keyed layers `keyed` (_keyed()).  `slots` (device f32 [L + 1], zeroed) / `screened` (indices of the keyed layers whose contract
         is re-screened): slot k receives max |x| of keyed layer k -- slot 0 by one pass over the input, slot k + 1 by the kernel that
-        produces layer k's output.  `narrow` / `rows` / `narrow32`: every layer in its narrow form (KeyedLayer.forward); the whole-net kernel only where no layer has one."""
+        produces layer k's output.  `narrow` / `rows` / `narrow32` / `narrow64`: every layer in its narrow form (KeyedLayer.forward); the whole-net kernel only where no layer has one."""
         forced = overlap is True
         if overlap is None and not self.OVERLAP_AUTO:
             overlap = False
@@ -335,7 +342,7 @@ class KeyedModel(object):
             if k is None:
                 y = _relu_block(y)
             else:
-                y = c.forward(y, fuse_relu=relu, absmax=slots[k + 1:k + 2] if (slots is not None and (k + 1) in screened) else None, narrow=narrow, narrow_rows=rows, narrow32=narrow32)
+                y = c.forward(y, fuse_relu=relu, absmax=slots[k + 1:k + 2] if (slots is not None and (k + 1) in screened) else None, narrow=narrow, narrow_rows=rows, narrow32=narrow32, narrow64=narrow64)
         return y
 
     # -- whole-net kernel: every operator of a small untiled key-net in ONE launch, activations in LDS (csrc/kn_chain.hip) --------
@@ -585,7 +592,7 @@ class KeyedModel(object):
             self._drop_plans()
         return changed
 
-    def capture(self, img_cipher, narrow=False, narrow_rows=False, narrow32=False):
+    def capture(self, img_cipher, narrow=False, narrow_rows=False, narrow32=False, narrow64=False):
         """Capture forward_linear for this input shape into a HIP graph (torch.cuda.CUDAGraph on ROCm) and return a callable
         `replay(x) -> [N, classes+1]`.  Small key-nets are launch-bound (LeNet at N=1024: 7 kernels in 0.25 ms); one graph
         launch replaces them.  The graph runs the passes of the eager forward on the block _prepare made; replay(x) copies x into its first N images.
@@ -599,29 +606,30 @@ class KeyedModel(object):
         matrix-core narrow kernel by a measurement the graph gathers their max |x|, replay() reads the slots after the launch and on a trip runs the batch eagerly
         (measuring again) and captures a new graph, as the wide capture does; with no such layer it reads nothing.
         `narrow_rows=True` (only with `narrow`): the graph of forward_linear(narrow=..., narrow_rows=True): the same straight line of launches.
-        `narrow32=True` (only with `narrow`): the graph of forward_linear(narrow=..., narrow32=True), up to NARROW32_MAX images."""
+        `narrow32=True` (only with `narrow`): the graph of forward_linear(narrow=..., narrow32=True), up to NARROW32_MAX images.
+        `narrow64=True` (only with `narrow`): the graph of forward_linear(narrow=True, narrow64=True), up to NARROW64_MAX images -- the same straight line of launches on one stream."""
         assert img_cipher.is_cuda, 'capture() needs a device tensor'
         n = img_cipher.shape[0]
-        (mode, rows) = ksp._narrow_args(n, narrow, narrow_rows, narrow32=narrow32)
-        narrow32 = bool(narrow32)
+        (mode, rows) = ksp._narrow_args(n, narrow, narrow_rows, narrow32=narrow32, narrow64=narrow64)
+        (narrow32, narrow64) = (bool(narrow32), bool(narrow64))
         src = img_cipher.detach().float() if mode else img_cipher.detach()
         (static_in, windows) = self._prepare(src.t().clone(memory_format=torch.contiguous_format).t(), mode)     # the graph's own input block
         keyed = self._keyed()
         state = {}
 
         def build():
-            self._forward_passes(static_in, windows, False, mode, rows, narrow32)       # uploads operators, sizes workspaces, calibrates (not capturable)
+            self._forward_passes(static_in, windows, False, mode, rows, narrow32, narrow64)       # uploads operators, sizes workspaces, calibrates (not capturable)
             torch.cuda.synchronize()
             side = torch.cuda.Stream()
             side.wait_stream(torch.cuda.current_stream())
             with torch.cuda.stream(side):
-                self._forward_passes(static_in, windows, False, mode, rows, narrow32)   # warm-up on the capture stream
+                self._forward_passes(static_in, windows, False, mode, rows, narrow32, narrow64)   # warm-up on the capture stream
             torch.cuda.current_stream().wait_stream(side)
             graph = torch.cuda.CUDAGraph()
             # capture ON THE WARMED STREAM: per-stream state of the operators (the split-K workspace of a dense layer, kn_api.hip) was sized
             # by the warm-up forward above; torch's default capture stream would be a fresh one, and a hipMalloc inside a capture is refused
             with torch.cuda.graph(graph, stream=side):
-                (out, screens) = self._forward_passes(static_in, windows, False, mode, rows, narrow32)
+                (out, screens) = self._forward_passes(static_in, windows, False, mode, rows, narrow32, narrow64)
             state.update(graph=graph, out=out[:n], screens=screens)
 
         build()
@@ -637,12 +645,12 @@ class KeyedModel(object):
         replay.graph = state['graph']
         return replay
 
-    def forward(self, img_cipher, outkey=None, narrow=False, narrow_rows=False, narrow32=False):
+    def forward(self, img_cipher, outkey=None, narrow=False, narrow_rows=False, narrow32=False, narrow64=False):
         """Encrypted image(s) [N, D0+1] -> logits.  N == 1 returns the reference's shape `outshape` = (C,1,1)
         (keynet/system.py:130-133); N > 1 (an extension: the reference cannot) returns (N, C, 1, 1).  `narrow`: forward_linear(narrow=True | 'mfma'), the
-        low-latency forms of this very call for 1 .. NARROW_MAX images; `narrow_rows`: with them, the CSR layers on the row-lane kernel (forward_linear); `narrow32`: with them, up to NARROW32_MAX images."""
+        low-latency forms of this very call for 1 .. NARROW_MAX images; `narrow_rows`: with them, the CSR layers on the row-lane kernel (forward_linear); `narrow32`: with them, up to NARROW32_MAX images; `narrow64`: up to NARROW64_MAX."""
         outkey = outkey if outkey is not None else self.embeddingkey()
-        y = self.forward_linear(img_cipher, narrow=narrow, narrow_rows=narrow_rows, narrow32=narrow32)
+        y = self.forward_linear(img_cipher, narrow=narrow, narrow_rows=narrow_rows, narrow32=narrow32, narrow64=narrow64)
         if outkey is not None:
             y = self.decrypt(y, outkey)
         n = y.shape[0]

@@ -40,7 +40,15 @@ its kn_spmm with and without KN_FLAG_NARROW_ROWS on the same block (HIP events, 
 default contract -- logits torch.equal before any time is printed --, then under exact_mode('auto') after one calibrating wide forward the padded forward and
 narrow='mfma', narrow32=True (inside the float-key gate against narrow=True, narrow32=True); at 8 images the plain narrow forwards are the yardstick.  The bars of
 the file are computed from the table.  --blocks: convtaps_narrow32_kernel on a 14 x 14 pixel, 512 -> 512 channel 3 x 3 operator at 32 columns with the block
-width forced by KN_NARROW32_NV (read at create by the diagnostic build only: keynet_amd.build.build(out=..., defines=('KN_ABLATION',))) against the launcher's rule."""
+width forced by KN_NARROW32_NV (read at create by the diagnostic build only: keynet_amd.build.build(out=..., defines=('KN_ABLATION',))) against the launcher's rule.
+
+    python tools/narrow_latency.py --narrow64 [--workload vgg16|allconv] [--out profiles/r11_narrow64.txt]
+    python tools/narrow_latency.py --narrow64 --one-forward      # at 64 images ONE forward without the keyword (padded to 128), then ONE narrow=True, narrow64=True forward
+    python tools/narrow_latency.py --narrow64 --from-trace DIR/.../*_kernel_trace.csv          # no GPU: the 13 conv launches of those two forwards
+
+--narrow64: under the default contract, in one process with the forms alternating: the forward without the keyword (a tiled key-net: padded to 128 images) against
+narrow=True, narrow64=True at 33, 48 and 64 images (`--workload allconv`: at 48) -- logits torch.equal before any time is printed --, and the narrow32 forward at 32
+images for the ladder.  The bars of the file are computed from the table."""
 import argparse
 import os
 import statistics
@@ -194,6 +202,90 @@ def narrow32_table(args, knet, xc, desc):
     text = '\n'.join(lines) + '\n'
     print(text)
     with open(args.out or os.path.join(ROOT, 'profiles', 'r10_narrow32.txt'), 'a') as f:
+        f.write(text)
+
+
+N64_IMAGES = (33, 48, 64)
+
+
+def narrow64_table(args, knet, xc, desc):
+    """--narrow64: see the module docstring."""
+    blk = lambda n: xc[:n].t().contiguous().t()
+    kw = dict(narrow=True, narrow64=True)
+    if args.one_forward:
+        for _ in range(2):                        # operators resident, workspaces sized
+            knet.forward_linear(blk(64))
+            knet.forward_linear(blk(64), **kw)
+        torch.cuda.synchronize()
+        print('TRACE-FROM-HERE: at 64 images one forward without the keyword (padded to 128), then one narrow=True, narrow64=True forward', flush=True)
+        knet.forward_linear(blk(64))
+        torch.cuda.synchronize()
+        knet.forward_linear(blk(64), **kw)
+        torch.cuda.synchronize()
+        return
+    cell = lambda v: '%8.3f (%.3f .. %.3f)' % (statistics.median(v), min(v), max(v))
+    images = (48,) if args.workload == 'allconv' else N64_IMAGES
+    lines = ['', '== tools/narrow_latency.py --narrow64%s: %s' % ('' if args.workload == 'vgg16' else ' --workload %s' % args.workload, desc),
+             '   %s, torch %s; HIP events, %d warm-up + median of %d forwards (min .. max), the forms of a row alternating in quarters; default contract, logits torch.equal: yes'
+             % (torch.cuda.get_device_name(0), torch.__version__, args.warmup, args.forwards),
+             '   %6s | %-28s | %-28s | %-9s | %s' % ('images', 'no keyword [ms]', 'narrow=True, narrow64=True [ms]', 'speed-up', 'ms per image, narrow64')]
+    med = {}
+    pads0 = getattr(knet, '_padded_forwards', 0)
+    for n in images:
+        x = blk(n)
+        (y0, y1) = (knet.forward_linear(x), knet.forward_linear(x, **kw))
+        torch.cuda.synchronize()
+        assert torch.equal(y0, y1), 'narrow64 logits differ from the forward without the keyword at %d images: max %g' % (n, float((y0 - y1).abs().max()))
+        forms = [lambda: knet.forward_linear(x), lambda: knet.forward_linear(x, **kw)]
+        t = [[] for _ in forms]
+        for _ in range(4):                        # alternate in quarters
+            for (u, f) in zip(t, forms):
+                u += timed(f, args.forwards // 4, args.warmup)
+        med[n] = [statistics.median(u) for u in t]
+        lines.append('   %6d | %-28s | %-28s | %8.2fx | %.3f' % (n, cell(t[0]), cell(t[1]), med[n][0] / med[n][1], med[n][1] / n))
+        print('n = %d done' % n, flush=True)
+    padded = getattr(knet, '_padded_forwards', 0) > pads0
+    lines.append('   the forward without the keyword is %s' % ('padded to 128 images' if padded else 'NOT padded (an untiled key-net runs at the width it is given)'))
+    if args.workload == 'vgg16':
+        x = blk(32)
+        t32 = timed(lambda: knet.forward_linear(x, narrow=True, narrow32=True), args.forwards, args.warmup)
+        m32 = statistics.median(t32)
+        lines.append('   %6d | %-28s | %-28s |           | %.3f   (narrow=True, narrow32=True: the ladder)' % (32, '', cell(t32), m32 / 32))
+        lines.append('   (a) no keyword / narrow64 at 64 images = %.2fx (the instruction count says up to 2x; below 1.3x the form is not worth merging)' % (med[64][0] / med[64][1]))
+        lines.append('   (b) narrow64 at 33 / 48 / 64 images: %.3f / %.3f / %.3f ms (one form, masked: 33 and 48 must not cost more than 64); per image at 64: %.3f ms against %.3f ms of narrow32 at 32'
+                     % (med[33][1], med[48][1], med[64][1], med[64][1] / 64, m32 / 32))
+    text = '\n'.join(lines) + '\n'
+    print(text)
+    with open(args.out or os.path.join(ROOT, 'profiles', 'r11_narrow64.txt'), 'a') as f:
+        f.write(text)
+
+
+def narrow64_trace_table(args):
+    """--narrow64 --from-trace: the conv launches of the last two forwards of a `--narrow64 --one-forward` run (device timestamps)."""
+    import csv
+    with open(args.from_trace, newline='') as f:
+        rows = [r for r in csv.DictReader(f) if 'convtaps_' in r['Kernel_Name'] and 'zero_guard' not in r['Kernel_Name']]
+    rows.sort(key=lambda r: int(r['Start_Timestamp']))
+    k = args.convs
+    assert len(rows) >= 2 * k, 'the trace holds %d conv launches, fewer than 2 forwards of %d' % (len(rows), k)
+    (wide, new) = (rows[-2 * k:-k], rows[-k:])
+    us = lambda r: (int(r['End_Timestamp']) - int(r['Start_Timestamp'])) / 1e3
+    wgs = lambda r: int(r.get('Grid_Size_X') or 0) // max(1, int(r.get('Workgroup_Size_X') or 1))
+    short = lambda r: r['Kernel_Name'].replace('void kn::', '').split('(')[0]
+    lines = ['', '== tools/narrow_latency.py --narrow64 --from-trace: the conv launches of one forward without the keyword (64 images padded to 128) and one narrow=True, narrow64=True forward',
+             '   of the same 64 images (rocprofv3 --kernel-trace, device timestamps)', '',
+             '   conv launch | workgroups, padded | padded [us] | workgroups, narrow64 | narrow64 [us] | ratio | kernels']
+    slower = []
+    for (j, (a, b)) in enumerate(zip(wide, new)):
+        lines.append('     %2d | %7d | %9.1f | %7d | %9.1f | %5.2fx | %s / %s' % (j + 1, wgs(a), us(a), wgs(b), us(b), us(a) / us(b), short(a), short(b)))
+        if us(b) > us(a):
+            slower.append(j + 1)
+    (sa, sb) = (sum(us(r) for r in wide), sum(us(r) for r in new))
+    lines.append('     sum of the %d conv launches: %9.1f | %9.1f | %5.2fx' % (k, sa, sb, sa / sb))
+    lines.append('     conv launches slower on the new form than on the padded 128-column form: %s' % (', '.join(str(j) for j in slower) or 'none'))
+    text = '\n'.join(lines) + '\n'
+    print(text)
+    with open(args.out or os.path.join(ROOT, 'profiles', 'r11_narrow64.txt'), 'a') as f:
         f.write(text)
 
 
@@ -417,11 +509,12 @@ def main():
     ap.add_argument('--rows', action='store_true', help='whole forwards and single layers with and without narrow_rows=True (profiles/r09_narrow_rows.txt)')
     ap.add_argument('--mfma', action='store_true', help="exact_mode('auto') after one calibrating wide forward: padded, narrow=True, narrow='mfma'")
     ap.add_argument('--narrow32', action='store_true', help='9 .. 32 images: no keyword against narrow32=True, both contracts (profiles/r10_narrow32.txt)')
+    ap.add_argument('--narrow64', action='store_true', help='33 .. 64 images: no keyword against narrow=True, narrow64=True under the default contract (profiles/r11_narrow64.txt)')
     ap.add_argument('--images', type=lambda v: tuple(int(k) for k in v.split(',')), default=N32_IMAGES, help='image counts of --narrow32')
     ap.add_argument('--blocks', action='store_true', help='with --narrow32: one conv5_x-shaped operator per column-block width (diagnostic build)')
     args = ap.parse_args()
     if args.from_trace:
-        return narrow32_trace_table(args) if args.narrow32 else rows_trace_table(args) if args.rows else trace_table(args)
+        return narrow64_trace_table(args) if args.narrow64 else narrow32_trace_table(args) if args.narrow32 else rows_trace_table(args) if args.rows else trace_table(args)
     if args.narrow32 and args.blocks:
         return narrow32_blocks(args)
     assert args.forwards >= 20 or args.one_forward, 'the median of at least 20 forwards'
@@ -429,10 +522,12 @@ def main():
     (sensor, knet, inshape, _, desc, _) = workloads.build_workload(args.workload, 0, fanout=True)
     dev = torch.device('cuda:0')
     torch.manual_seed(1)
-    imgs = torch.randn((max(args.images) if args.narrow32 else 8,) + tuple(inshape))
+    imgs = torch.randn((64 if args.narrow64 else max(args.images) if args.narrow32 else 8,) + tuple(inshape))
     xc = sensor.fromtensor(imgs.to(dev)).encrypt().astensor()
     xc = xc.t().contiguous().t()                  # feature-major, as the layers hand blocks on
     print('keyed %s in %.0f s' % (desc, time.time() - t0), flush=True)
+    if args.narrow64:
+        return narrow64_table(args, knet, xc, desc)
     if args.narrow32:
         return narrow32_table(args, knet, xc, desc)
     if args.mfma:
