@@ -105,7 +105,7 @@ enum kn_status {
                               There the call is the order-preserving product -- bit for bit the result of KN_FLAG_EXACT, and of the same columns inside a wider batch -- on the
                               software-pipelined kernel with ONE column per lane (convtaps_exact_pipe64_kernel: one wavefront = one output pixel x 16 | 8 output channels x one
                               64-column tile, the packed multiplies and adds run over output-channel pairs, half the vector-ALU work per step of a 128-column tile, lanes beyond
-                              n_vecs masked).  No condition on the alignment of x and y or on ldx, ldy.  There is no matrix-core form at this width: KN_FLAG_NARROW_MFMA means
+                              n_vecs masked).  No condition on the alignment of x and y or on ldx, ldy.  Without KN_FLAG_NARROW64_MFMA (below) KN_FLAG_NARROW_MFMA means
                               KN_FLAG_NARROW here, and KN_FLAG_EXACT / KN_FLAG_BF16X3 next to the flags change nothing.
                               Unlike KN_FLAG_NARROW / KN_FLAG_NARROW32 the range NEVER REFUSES: an operator without the pipeline's shape (filled-in operators: more than 64 slots
                               per output pixel or a pixel pair hit twice) and a block beyond (D + 1) * ldx < 2^31 run what KN_FLAG_EXACT runs at that width -- same plan string,
@@ -113,6 +113,18 @@ enum kn_status {
                               Where it changes NOTHING (same kernels, same plan string, same bits as without it): without one of the two flags; at n_vecs <= 32 (the call is what its
                               other flags make it, KN_FLAG_NARROW32 included); at n_vecs > 64; on CSR, dense, float64 and chain handles; in kn_spmm_planes.  In particular KN_FLAG_EXACT
                               alone at 64 columns keeps the generic kernel.  kn_spmm_plan names the form ("64-column tiles").  No reference counterpart. */
+
+#define KN_FLAG_NARROW64_MFMA (0x100u)  /* = 256.  The matrix-core form of the range KN_FLAG_NARROW64 opens, for callers that accept the float-key tolerance.  It takes effect ONLY next to
+                              KN_FLAG_NARROW_MFMA | KN_FLAG_NARROW64, without KN_FLAG_EXACT, on a conv-taps handle at 33 <= n_vecs <= 64.  There the call is the f32 matrix-core
+                              product of a plain kn_spmm (v_mfma_f32_32x32x2_f32, exact f32 products, re-ordered f32 sums) on ONE 64-column tile per (output pixel, channel tile):
+                              convtaps_mfma_kernel<MT = 128 | 64, NB = 64>: 128 output channels per tile where that divides the padded channel count and leaves 1 024 workgroups, else 64.  Every column
+                              has the bits that a plain kn_spmm gives it inside the same batch zero-padded to 128 aligned columns (same K order per output element), so a tolerance
+                              decision made on the wide kernel covers it.  With KN_FLAG_EXACT the call is the order-preserving pipeline of KN_FLAG_NARROW64, bit for bit;
+                              KN_FLAG_BF16X3 next to it changes nothing (there is no bf16 form at this width).  The range never refuses: a width, leading dimension or alignment the
+                              straight-line loaders do not take (anything but 64 aligned columns) runs the generic loader.
+                              Where it changes NOTHING (same kernels, same plan string, same bits as without it): alone, or with only one of the two flags; at n_vecs <= 32 and at
+                              n_vecs > 64; on CSR, dense, float64 and chain handles; in kn_spmm_planes.  kn_spmm_plan names the launch
+                              ("convtaps_mfma_kernel<MT=..,NB=64,KC=..> loader=..").  No reference counterpart. */
 
 typedef struct kn_operator* kn_handle_t;   /* opaque keyed operator resident in HBM */
 
@@ -236,6 +248,7 @@ int kn_export_csr_f64(kn_handle_t h, int32_t* indptr, int32_t* indices, double* 
  *   conv-taps, KN_FLAG_EXACT, pipelined kernel          (D + 1) * ldx < 2^31                               else the plain order-preserving kernel
  *   conv-taps, KN_FLAG_EXACT, filled-in operators       4 * ldx < 2^24, 4 * HiWi * ldx < 2^32, HiWi < 2^24  else the plain order-preserving kernel
  *   conv-taps, KN_FLAG_NARROW64 (33 <= n_vecs <= 64)    (D + 1) * ldx < 2^31                               else the plain order-preserving kernel
+ *   conv-taps, KN_FLAG_NARROW64_MFMA (33 .. 64)         the matrix-core rules above at NB = 64 (T = 16), on n_vecs = 64 aligned columns; else the generic loader
  *   CSR, KN_FLAG_NARROW_ROWS (n_vecs <= 8)               cols * ldx + 8 < 2^30                              else the kernels the call takes without the flag
  * The small-K matrix-core kernels of first-layer operators (slots * Cin + bias <= 28 contraction rows) form row * ldx in 64 bits and take any ldx.
  * KN_FLAG_NARROW / KN_FLAG_NARROW_MFMA (n_vecs <= 8 on a conv-taps operator) do NOT fall back: they return KN_ERR_UNSUPPORTED, Y untouched, unless (D + 1) * ldx + 8 < 2^31

@@ -20,6 +20,7 @@ KN_FLAG_NARROW = 8
 KN_FLAG_NARROW_MFMA = 16      # KN_FLAG_NARROW on the matrix cores where operator and contract allow (include/keynet_hip.h); else KN_FLAG_NARROW
 KN_FLAG_NARROW32 = 64         # modifier: KN_FLAG_NARROW / KN_FLAG_NARROW_MFMA on up to 32 columns instead of 8 (include/keynet_hip.h); alone, and on every other handle kind, it changes nothing
 KN_FLAG_NARROW64 = 128        # modifier: KN_FLAG_NARROW / KN_FLAG_NARROW_MFMA open 33 .. 64 columns (the order-preserving pipeline, one column per lane; include/keynet_hip.h); everywhere else it changes nothing
+KN_FLAG_NARROW64_MFMA = 256   # with KN_FLAG_NARROW_MFMA | KN_FLAG_NARROW64, without KN_FLAG_EXACT, on a conv-taps handle at 33 .. 64 columns: the f32 matrix-core product on 64-column tiles (include/keynet_hip.h); everywhere else it changes nothing
 KN_FLAG_NARROW_ROWS = 32      # f32 CSR operators on the row-lane kernel for 1 .. 8 columns (include/keynet_hip.h); ignored by every other handle and beyond 8 columns
 KN_ABI_VERSION = 5
 

@@ -111,6 +111,7 @@ struct ConvArgs {
     int32_t n_mt, n_bt, n_pix, max_slots, ntaps, wide_store;
     int64_t last_in_row;   // Cin*HiWi (row of X holding the homogeneous coordinate)
     int32_t tail_main;     // work items per XCD chunk computed as full tiles; the rest of the chunk runs as 4 quarter tiles each
+    int32_t k_order;       // 64-column tiles, generic loader only (mfma64_choice): 1 = walk K as the straight-line loaders do (slot groups outermost, channel chunk outer, slot inner); 0 = slot outer
     int64_t* stamps;          // diagnostic build only (KN_STAMPS): per-workgroup {start, end} of s_memrealtime, XCC id, kind; null otherwise
     const int32_t* sk_desc;   // small-K pipeline: per-pixel descriptors in processing order (ConvTapsDev::sk_desc), or null
     int32_t sk_stride, sk_tab_rows;
@@ -147,7 +148,9 @@ __device__ __forceinline__ void decode_conv_item(const ConvArgs& p, const int64_
 // discarded): every register-destination dwordx4 load costs the matrix pipe of its SIMD ~29 cycles, the per-lane pointer walk 1.6 %
 // of the launch; the same tiles fetched by global_load_lds_dwordx4 (no VGPR destination, no ds_write pass, two stages with a
 // vmcnt(0) in front of each chunk's barrier) ran 3.5 % SLOWER than register staging and was dropped.
-template <int MT, int NB, int KC, int WM, int WN, int MODE>
+// WHOLE64: the body as a 64-column launch of its own (convtaps_mfma_kernel<MT, 64, ...>, ConvRegime MFMA64).  It only names a separate instantiation: the quarter tiles of
+// the tail split keep theirs, and with it their code, instruction for instruction.
+template <int MT, int NB, int KC, int WM, int WN, int MODE, bool WHOLE64 = false>
 __device__ __forceinline__ void convtaps_mfma_tile(const ConvArgs& p, const int o, const int m0, const int b0, float* lds) {
     constexpr bool FAST = MODE >= 1;
     constexpr bool SPTR = MODE >= 2;
@@ -191,8 +194,18 @@ __device__ __forceinline__ void convtaps_mfma_tile(const ConvArgs& p, const int 
     f32x4 ra[AL], rb[BL];
 
     auto gload = [&](int q) {
-        const int s = s_beg + q / cpk;
-        const int ci0 = (q % cpk) * KC;
+        int s = s_beg + q / cpk;
+        int ci0 = (q % cpk) * KC;
+        if constexpr (WHOLE64 && !FAST) {
+            // A 64-column launch (KN_FLAG_NARROW64_MFMA) owes every column the bits of the wide launch on the padded batch, whose loaders are the straight-line ones
+            // wherever the operator admits them: same walk here -- groups of <= 64 slots outermost, channel chunk outer, slot inner (sptr_group / gload_fast below)
+            if (p.k_order) {
+                const int g = q / (MAX_FAST_SLOTS * cpk), r = q - g * (MAX_FAST_SLOTS * cpk);
+                const int gn = (n_slots - g * MAX_FAST_SLOTS) < MAX_FAST_SLOTS ? (n_slots - g * MAX_FAST_SLOTS) : MAX_FAST_SLOTS;
+                s = s_beg + g * MAX_FAST_SLOTS + r % gn;
+                ci0 = (r / gn) * KC;
+            }
+        }
         const int tap = p.slot_tap[s];
         const int in = p.slot_in[s];
         const float coef = (FAST || p.unit_coef) ? 1.0f : p.slot_coef[s];
@@ -408,6 +421,8 @@ __device__ __forceinline__ void convtaps_mfma_tile(const ConvArgs& p, const int 
             if constexpr (AL == 2 && BL == 2) asm volatile("s_waitcnt vmcnt(0)" : "+v"(ra[0]), "+v"(ra[1]), "+v"(rb[0]), "+v"(rb[1]));
             else if constexpr (AL == 1 && BL == 4) asm volatile("s_waitcnt vmcnt(0)" : "+v"(ra[0]), "+v"(rb[0]), "+v"(rb[1]), "+v"(rb[2]), "+v"(rb[3]));
             else if constexpr (AL == 1 && BL == 1) asm volatile("s_waitcnt vmcnt(0)" : "+v"(ra[0]), "+v"(rb[0]));
+            else if constexpr (AL == 2 && BL == 1) asm volatile("s_waitcnt vmcnt(0)" : "+v"(ra[0]), "+v"(ra[1]), "+v"(rb[0]));                                  // 128 x 64
+            else if constexpr (AL == 4 && BL == 1) asm volatile("s_waitcnt vmcnt(0)" : "+v"(ra[0]), "+v"(ra[1]), "+v"(ra[2]), "+v"(ra[3]), "+v"(rb[0]));        // 256 x 64 (diagnostic build)
             else static_assert(!SPTR, "tile shape without a wait statement");
         }
     };
@@ -420,7 +435,7 @@ __device__ __forceinline__ void convtaps_mfma_tile(const ConvArgs& p, const int 
     // lives at t*(W*32) + w*32 + l.  A wavefront's T sub-tile fragments are then W*32 dwords apart and consecutive k-steps a
     // whole row apart -- both multiples of 64 dwords when W = 2 -- so every fragment read of a chunk is ONE base register plus
     // immediate offsets (ds_read2st64_b32) instead of a v_add per read: 16 fewer VALU instructions per chunk and wavefront
-    // (+2.3 % on the 128x128 tile, same-call A/B).
+    // (+2.3 % on the 128x128 tile, same-call A/B).  (W = 1, the A side of the 64 x 256 tile: 32 dwords apart, one base register plus ds_read2_b32 immediates.)
     uint32_t a_lds[AL], b_lds[BL];
 #pragma unroll
     for (int i = 0; i < AL; i++) {
@@ -638,7 +653,7 @@ __global__ __launch_bounds__(256, 2) void convtaps_mfma_kernel(ConvArgs p) {
             done = true;
         }
     }
-    if (!done) convtaps_mfma_tile<MT, NB, KC, WM, WN, FAST>(p, o, mt * MT, bt * NB, lds);
+    if (!done) convtaps_mfma_tile<MT, NB, KC, WM, WN, FAST, NB == 64>(p, o, mt * MT, bt * NB, lds);
 #ifdef KN_ABLATION
     if (p.stamps && threadIdx.x == 0) p.stamps[4 * (int64_t)blockIdx.x + 1] = (int64_t)__builtin_amdgcn_s_memrealtime();
 #endif
@@ -2519,6 +2534,45 @@ static MfmaChoice mfma_choice(const ConvTapsDev& A, const ConvArgs& a, bool bf16
     return c;
 }
 
+// ConvRegime MFMA64 (KN_FLAG_NARROW_MFMA | KN_FLAG_NARROW64 | KN_FLAG_NARROW64_MFMA at 33 .. 64 columns): the f32 tile product on ONE 64-column tile per (pixel, channel tile).
+// Tile height: 128 output channels where that divides cout_pad and still leaves 1 024 workgroups (four per CU: narrow_choice's threshold for its two-block tiles), else 64.
+// Measured on VGG-16-shaped operators at 64 columns (profiles/r12_narrow64_mfma.txt; us at 256 / 128 / 64 channels): conv3_2 (3 136 / 6 272 / 12 544 workgroups) 1 815 / 1 720 /
+// 1 775, conv4_2 (1 568 / 3 136 / 6 272) 1 985 / 1 833 / 1 850, conv5_1 (392 / 784 / 1 568) 614 / 598 / 573: the threshold holds on both sides (conv5_x is the layer below it), and
+// a 256-channel tile (4 x 1 wavefronts of 64 x 64, 44.5 KB of LDS) loses to 128 everywhere, so the product library has none.  Tuning::mfma64_mt forces 64 | 128 (| 256: diagnostic
+// build, KC = 16, not with per-thread pointers).  No tail split, no occupancy cap.
+// The contract is the K ORDER: every column gets the bits the wide launch gives it inside the batch zero-padded to 128 columns, whose loaders (`wide`) are the
+// straight-line ones wherever operator and block admit them (chunk outer, slot inner, slot groups outermost) and the generic one (slot outer) elsewhere -- 64-channel
+// operators, whose wide tile is 256 columns, among them.  Where the two orders differ (more than one channel chunk per slot) the 64-column launch follows the wide
+// launch's: its generic loader walks either order (ConvArgs::k_order); its straight-line loaders walk the first only and are taken where that is the wide order.
+// The loaders never refuse: any width, leading dimension or alignment that tile_loaders turns down runs the generic loader.
+static MfmaChoice mfma64_choice(const ConvTapsDev& A, ConvArgs& a) {
+    MfmaChoice c;
+    c.kernel = MfmaChoice::TILE;
+    c.nb = 64;
+    c.kc = A.cin_pad % 16 == 0 ? 16 : 4;
+    c.mt = (A.cout_pad % 128 == 0 && (int64_t)a.n_pix * (A.cout_pad / 128) >= 1024) ? 128 : 64;
+    if ((A.tune.mfma64_mt == 64 || A.tune.mfma64_mt == 128) && A.cout_pad % A.tune.mfma64_mt == 0) c.mt = A.tune.mfma64_mt;
+    ConvArgs padded = a;                                                     // the same block as the padded forward lays it out: whole 128-column tiles, aligned
+    padded.n_vecs = 128;
+    padded.vec_ok = 1;
+    const bool big_m = A.cout_pad % 128 == 0 && A.Cout > 64;                // (mfma_choice's tile rule)
+    const int wide = tile_loaders(A, padded, big_m ? 128 : 256, c.kc);
+    const bool one_order = A.cin_pad / c.kc == 1;                            // one channel chunk per slot and at most 64 slots: both walks are the same sequence
+    a.k_order = wide != 0 ? 1 : 0;
+    c.mode = tile_loaders(A, a, 64, c.kc);
+    if (c.mode != 0 && wide == 0 && !(one_order && A.max_slots <= MAX_FAST_SLOTS)) c.mode = 0;
+#ifdef KN_ABLATION
+    if (A.tune.mfma64_mt == 256 && A.cout_pad % 256 == 0 && c.kc == 16 && c.mode != 1) c.mt = 256;      // (the instantiations mfma_kernel has)
+#endif
+    c.n_mt = (int32_t)(A.cout_pad / c.mt);
+    c.n_bt = 1;
+    c.absmax_rides = a.wide_store && a.n_vecs % c.nb == 0;
+    const int64_t chunk = ((int64_t)a.n_pix * c.n_mt + 7) / 8;
+    c.grid = 8 * chunk;
+    c.tail_main = (int32_t)chunk;
+    return c;
+}
+
 typedef void (*ExactPipeKernel)(ConvArgs, int, int64_t);
 template <int RBX, int XD, int VEC>
 static ExactPipeKernel exact_pipe_kernel(bool coef) {
@@ -2754,8 +2808,19 @@ static ConvKernel mfma_kernel(const MfmaChoice& c) {
         case MfmaChoice::SMALLK: return convtaps_smallk_kernel;
         default: break;
     }
-    if (c.mt == 128) return c.kc == 16 ? tile_kernel<128, 128, 16, 2, 2>(c.mode, c.tail) : tile_kernel<128, 128, 4, 2, 2>(c.mode, c.tail);
-    return c.kc == 16 ? tile_kernel<64, 256, 16, 1, 4>(c.mode, c.tail) : tile_kernel<64, 256, 4, 1, 4>(c.mode, c.tail);
+    if (c.nb != 64) {
+        if (c.mt == 128) return c.kc == 16 ? tile_kernel<128, 128, 16, 2, 2>(c.mode, c.tail) : tile_kernel<128, 128, 4, 2, 2>(c.mode, c.tail);
+        return c.kc == 16 ? tile_kernel<64, 256, 16, 1, 4>(c.mode, c.tail) : tile_kernel<64, 256, 4, 1, 4>(c.mode, c.tail);
+    }
+    // 64-column tiles (mfma64_choice): whole launches of the quarter tile, and of two of them stacked over the output channels
+#ifdef KN_ABLATION
+    // DIAGNOSTIC BUILD ONLY (Tuning::mfma64_mt = 256): four stacked, 4 x 1 wavefronts of 64 x 64 -- measured 5 - 9 % slower than 128 x 64 on conv3_x / conv4_x-shaped
+    // operators (profiles/r12_narrow64_mfma.txt) and left out of the product library.  No per-thread-pointer form (four 64-bit tap pointers per lane: 132 registers).
+    if (c.mt == 256)
+        return c.mode == 3 ? convtaps_mfma_kernel<256, 64, 16, 4, 1, 3, false> : (c.mode == 2 ? convtaps_mfma_kernel<256, 64, 16, 4, 1, 2, false> : convtaps_mfma_kernel<256, 64, 16, 4, 1, 0, false>);
+#endif
+    if (c.mt == 128) return c.kc == 16 ? tile_kernel<128, 64, 16, 2, 2>(c.mode, false) : tile_kernel<128, 64, 4, 2, 2>(c.mode, false);
+    return c.kc == 16 ? tile_kernel<64, 64, 16, 2, 2>(c.mode, false) : tile_kernel<64, 64, 4, 2, 2>(c.mode, false);
 }
 
 // (the two loader modes may differ in registers)
@@ -2836,7 +2901,7 @@ int convtaps_spmm(const ConvTapsDev& A, const float* x, int64_t ldx, int64_t n_v
         case NARROW64:
         case EXACT: rc = spmm_exact(A, a, regime == NARROW64, s); break;
         default: {
-            const MfmaChoice c = mfma_choice(A, a, regime == BF16X3);
+            const MfmaChoice c = regime == MFMA64 ? mfma64_choice(A, a) : mfma_choice(A, a, regime == BF16X3);
             // every matrix-core kernel streams its tiles out through kn_store_tile: where the choice says so, max |Y| rides in the epilogues (tiles + conv_lastrow_kernel
             // for the homogeneous row)
             if (absmax && c.absmax_rides) {

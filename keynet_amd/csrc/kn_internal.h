@@ -196,6 +196,7 @@ PlanSink*& plan_sink();   // thread-local; null outside kn_spmm_plan
     X(chain_no_seq, "KN_CHAIN_NO_SEQ", 0, true)      /* whole-net kernel: thin layers read their columns from the staged pool instead of walking a re-ordered input sequentially */ \
     X(chain_no_share, "KN_CHAIN_NO_SHARE", 0, true)  /* whole-net kernel: every lane streams its own copy of its row's values (no shared value blocks) */ \
     X(narrow32_nv, "KN_NARROW32_NV", 0, true)        /* convtaps_narrow32_kernel: 8 | 16 | 32 columns per block (0: the rule, narrow_choice) */ \
+    X(mfma64_mt, "KN_MFMA64_MT", 0, true)            /* 64-column f32 tiles (KN_FLAG_NARROW64_MFMA): 64 | 128 (| 256: no product form) output channels per tile (0: the rule, mfma64_choice) */ \
     X(fill_form, "KN_FILL_FORM", 0, true)            /* filled-in order-preserving kernel: 0 = the dispatch rule, 1 / 2 = 32 / 64 channels x one column tile, 3 / 4 = 32 / 64 channels x two tiles */ \
     X(abl, "KN_ABL", 0, true)                        /* kernel ablation mask (kn_conv.hip, KN_ABLATION code paths) */
 struct Tuning {
@@ -395,8 +396,8 @@ static constexpr int64_t NARROW_MAX_VECS = 8;
 // kernel at NV = 16 | 32).  Alone, and on every handle kind but conv-taps, it changes nothing.  narrow_max is the one place that reads it.
 static constexpr int64_t NARROW32_MAX_VECS = 32;
 // KN_FLAG_NARROW64, a second modifier of the two flags: it opens the range NARROW32_MAX_VECS + 1 .. NARROW64_MAX_VECS (33 .. 64 columns: the order-preserving pipeline with one
-// column per lane, ConvRegime NARROW64) and that range ALONE -- at 32 columns and fewer a call is what its other flags make it, KN_FLAG_NARROW32 included.  There is no
-// matrix-core form at that width: KN_FLAG_NARROW_MFMA means KN_FLAG_NARROW there (narrow_mfma_call).  Read in narrow_max only: the widest batch a call of n_vecs columns may have.
+// column per lane, ConvRegime NARROW64) and that range ALONE -- at 32 columns and fewer a call is what its other flags make it, KN_FLAG_NARROW32 included.  Without
+// KN_FLAG_NARROW64_MFMA (narrow64_mfma_call below) KN_FLAG_NARROW_MFMA means KN_FLAG_NARROW at that width (narrow_mfma_call).  Read in narrow_max only: the widest batch a call of n_vecs columns may have.
 static constexpr int64_t NARROW64_MAX_VECS = 64;
 static inline int64_t narrow_max(uint32_t flags, int64_t n_vecs) {
     if ((flags & KN_FLAG_NARROW64) && n_vecs > NARROW32_MAX_VECS) return NARROW64_MAX_VECS;
@@ -429,9 +430,16 @@ static inline bool narrow_mfma_call(const ConvTapsDev& A, uint32_t flags, int64_
 // the call reads.  BF16X3 is the REQUEST (its planes are built for it): operands that do not qualify run as MFMA (mfma_choice, kn_conv.hip).
 // NARROW64 is the order-preserving product under every contract flag, launched by the order-preserving launcher (spmm_exact): an operator without the pipeline's shape
 // runs what EXACT runs at that width, so the regime never refuses.
-enum ConvRegime { NARROW_MFMA, NARROW, NARROW32, NARROW64, EXACT, BF16X3, MFMA };
+// MFMA64 (KN_FLAG_NARROW64_MFMA next to KN_FLAG_NARROW_MFMA | KN_FLAG_NARROW64, without KN_FLAG_EXACT, at 33 .. 64 columns and there alone): the f32 tile product of MFMA on
+// 64-column tiles (mfma64_choice, kn_conv.hip); KN_FLAG_BF16X3 next to it changes nothing.  In every other situation the bit is not read.
+enum ConvRegime { NARROW_MFMA, NARROW, NARROW32, NARROW64, EXACT, BF16X3, MFMA, MFMA64 };
+static inline bool narrow64_mfma_call(uint32_t flags, int64_t n_vecs) {
+    const uint32_t all = KN_FLAG_NARROW_MFMA | KN_FLAG_NARROW64 | KN_FLAG_NARROW64_MFMA;
+    return (flags & all) == all && !(flags & KN_FLAG_EXACT) && n_vecs > NARROW32_MAX_VECS && n_vecs <= NARROW64_MAX_VECS;
+}
 static inline ConvRegime conv_regime(const ConvTapsDev& A, uint32_t flags, int64_t n_vecs) {
     if (narrow_mfma_call(A, flags, n_vecs)) return NARROW_MFMA;
+    if (narrow64_mfma_call(flags, n_vecs)) return MFMA64;
     if (narrow_call(flags, n_vecs))                                                            // (beyond 8 columns KN_FLAG_NARROW32 is in force, beyond 32 KN_FLAG_NARROW64)
         return n_vecs > NARROW32_MAX_VECS ? NARROW64 : (n_vecs > NARROW_MAX_VECS ? NARROW32 : NARROW);
     if (flags & KN_FLAG_EXACT) return EXACT;

@@ -225,13 +225,20 @@ class KeyedLayer(nn.Module):
         `narrow32` (with `narrow`): at most KeyedModel.NARROW32_MAX images; a conv-taps layer gets KN_FLAG_NARROW32 next to its narrow flag (kernel()), every other
         layer runs as without it.
         `narrow64` (with `narrow`; implies `narrow32`): at most KeyedModel.NARROW64_MAX images; a conv-taps layer gets KN_FLAG_NARROW64 as well (kernel()) and runs, beyond
-        NARROW32_MAX images, the order-preserving pipeline with one column per lane; every other layer runs as without it, at the unpadded width."""
+        NARROW32_MAX images, the order-preserving pipeline with one column per lane; every other layer runs as without it, at the unpadded width.
+        `narrow64='mfma'` (with narrow='mfma'): at NARROW32_MAX images and fewer exactly narrow='mfma', narrow32=True.  Beyond, a conv-taps layer whose contract in force is
+        False or 'bf16x3' -- declared or decided by calibration -- runs the f32 matrix-core product on 64-column tiles (KN_FLAG_NARROW64_MFMA): the WIDE kernel's association,
+        covered by the layer's wide decision, so narrow_mode() and the narrow record are not consulted and nothing is measured or recorded (KeyedModel.forward_linear
+        re-screens a calibrated layer against its wide record).  Under True, 'auto' or 'split' the layer is what narrow=True, narrow64=True makes it."""
         if verbose():
             print('[keynet_amd.layer]: forward %s' % str(self))
         exact = getattr(self, '_exact', True)
         relu = fuse_relu or self.iskeyedrelu()
         form = {}                            # what `narrow` / `narrow_rows` make of this layer: the keyword its operator's torchdot takes, if any
-        if narrow and self.W.narrow_capable():
+        if narrow == 'mfma' and narrow64 == 'mfma' and x_affine.shape[0] > ksp.NARROW32_MAX and self.W.narrow_capable():
+            tile = isinstance(self.W, ksp.Conv2dTiledMatrix) and exact in (False, 'bf16x3')      # the wide decision covers the 64-column tile: same kernel, same K order
+            form = dict(narrow='mfma' if tile else True, narrow32=True, narrow64='mfma' if tile else True)
+        elif narrow and self.W.narrow_capable():
             form = dict(narrow=self.narrow_mode(narrow, x_affine.t(), relu) if narrow == 'mfma' else True, narrow32=bool(narrow32 or narrow64), narrow64=bool(narrow64))
         elif narrow:
             if exact == 'auto':
@@ -268,7 +275,10 @@ class KeyedLayer(nn.Module):
         `narrow32` (with `narrow`; a batch of at most KeyedModel.NARROW32_MAX columns): a narrow-capable operator gets KN_FLAG_NARROW32 next to the flags it has
         without the keyword (the library then honours its narrow flag up to 32 columns); every other operator keeps its flags.
         `narrow64` (with `narrow`; a batch of at most KeyedModel.NARROW64_MAX columns): a narrow-capable operator gets KN_FLAG_NARROW32 | KN_FLAG_NARROW64 next to its narrow
-        flag (at 33 .. 64 columns the library then runs the order-preserving pipeline with one column per lane, under every contract); every other operator keeps its flags."""
+        flag (at 33 .. 64 columns the library then runs the order-preserving pipeline with one column per lane, under every contract); every other operator keeps its flags.
+        `narrow64='mfma'` (with narrow='mfma'): a conv operator under False or 'bf16x3' gets KN_FLAG_NARROW_MFMA | KN_FLAG_NARROW32 | KN_FLAG_NARROW64 | KN_FLAG_NARROW64_MFMA and no
+        other contract flag: at 33 .. 64 columns the f32 tile kernel on 64-column tiles (there is no bf16 form at that width), at 32 and fewer the library ignores the new bit.
+        Under 'split' it keeps the flags of narrow='mfma', narrow64=True (the pipeline at 33 .. 64 columns), under True / 'auto' those of narrow=True, narrow64=True."""
         conv = isinstance(W, ksp.Conv2dTiledMatrix)
         lane = bool(narrow) and W.narrow_capable()          # one launch of a narrow conv kernel, whatever the contract
         mfma = lane and narrow == 'mfma' and conv and contract in (False, 'bf16x3', 'split')      # (the library falls back to the channel-lane kernel on an ineligible operator)
@@ -285,17 +295,21 @@ class KeyedLayer(nn.Module):
             (exact, bf16x3) = (False, False)
         return (get_op, (_capi.KN_FLAG_RELU if relu else 0) | (_capi.KN_FLAG_EXACT if exact else 0) | (_capi.KN_FLAG_BF16X3 if bf16x3 else 0) |
                 (_capi.KN_FLAG_NARROW_MFMA if mfma else _capi.KN_FLAG_NARROW if lane else 0) | (_capi.KN_FLAG_NARROW32 if lane and (narrow32 or narrow64) else 0) | (_capi.KN_FLAG_NARROW64 if lane and narrow64 else 0) |
-                (_capi.KN_FLAG_NARROW_ROWS if rows else 0))
+                (_capi.KN_FLAG_NARROW64_MFMA if mfma and narrow64 == 'mfma' and contract in (False, 'bf16x3') else 0) | (_capi.KN_FLAG_NARROW_ROWS if rows else 0))
 
     def launch(self, device, relu=False, narrow=False, narrow_rows=False, narrow32=False, narrow64=False):
         """This layer under its contract in force as one launch on `device` (`relu`: the unkeyed nn.ReLU behind it is fused in), or None when it is not one
         kn_spmm launch: see kernel(); a float64 operator (its own kernel and a float64 result: kn_spmm_f64).  What the key-net's planners read
-        (KeyedModel._chain_op / _overlap_plan); forward() -> W.torchdot() runs the same rule.  `narrow`, `narrow_rows`, `narrow32`, `narrow64`: see kernel(); 'mfma' goes through narrow_mode() first, without a batch."""
+        (KeyedModel._chain_op / _overlap_plan); forward() -> W.torchdot() runs the same rule.  `narrow`, `narrow_rows`, `narrow32`, `narrow64`: see kernel(); 'mfma' goes through narrow_mode() first, without a batch.
+        narrow64='mfma' (with narrow='mfma') asks for the launch of a batch of 33 .. 64 columns: the layer's wide decision holds there (forward()), narrow_mode() is not consulted."""
         W = self.W
-        if narrow == 'mfma':
+        if narrow == 'mfma' and narrow64 == 'mfma':
+            tile = isinstance(W, ksp.Conv2dTiledMatrix) and getattr(self, '_exact', True) in (False, 'bf16x3')
+            (narrow, narrow64) = ('mfma' if tile else True, 'mfma' if tile else True)
+        elif narrow == 'mfma':
             narrow = self.narrow_mode(narrow)                 # (a calibrated layer without a narrow record yet: the channel-lane kernel -- forward() measures, a planner does not)
         kernel = None if W.is_float64() else self.kernel(W, getattr(self, '_exact', True), relu or self.iskeyedrelu(), device, narrow=narrow, narrow_rows=bool(narrow and narrow_rows),
-                                                               narrow32=bool(narrow and narrow32), narrow64=bool(narrow and narrow64))
+                                                               narrow32=bool(narrow and narrow32), narrow64=narrow64 if (narrow and narrow64 == 'mfma') else bool(narrow and narrow64))
         if kernel is None:
             return None
         return Launch(kernel[0](device), kernel[1], int(W.shape[0]), int(W.shape[1]), isinstance(W, ksp.Conv2dTiledMatrix), 'Linear' in self._layertype,

@@ -87,7 +87,9 @@ def _run_torchdot(W, x, relu=False, exact=True, absmax=None, narrow=False, narro
     matrix-core narrow kernel (KN_FLAG_NARROW_MFMA) where `exact` is a re-ordering contract, else exactly narrow=True.  `narrow_rows`: at most NARROW_MAX columns
     on the row-lane kernel (KN_FLAG_NARROW_ROWS) where W's device form is a float32 CSR handle run in the stored order (W.rows_capable(), KeyedLayer.kernel): the
     same bits; every other operator is what it is without the keyword.  `narrow32` (with `narrow`): at most NARROW32_MAX columns (KN_FLAG_NARROW32).
-    `narrow64` (with `narrow`; implies `narrow32`): at most NARROW64_MAX columns (KN_FLAG_NARROW64: beyond NARROW32_MAX the order-preserving pipeline, one column per lane)."""
+    `narrow64` (with `narrow`; implies `narrow32`): at most NARROW64_MAX columns (KN_FLAG_NARROW64: beyond NARROW32_MAX the order-preserving pipeline, one column per lane).
+    `narrow64='mfma'` (with narrow='mfma'): beyond NARROW32_MAX columns a conv operator under False / 'bf16x3' runs the f32 matrix-core product on 64-column tiles
+    (KN_FLAG_NARROW64_MFMA, KeyedLayer.kernel); every other contract and operator is what narrow64=True makes it."""
     from .layer import KeyedLayer            # (layer.py imports this module)
     x = torch.as_tensor(x)
     assert W.shape[1] == x.shape[0], 'Non-conformal shape for W=%s, x=%s' % (str(W.shape), str(tuple(x.shape)))
@@ -113,15 +115,19 @@ def _run_torchdot(W, x, relu=False, exact=True, absmax=None, narrow=False, narro
 
 NARROW_MAX = 8        # widest batch of the channel-lane conv-taps kernel (KN_FLAG_NARROW; KeyedModel.NARROW_MAX)
 NARROW32_MAX = 32     # ... with narrow32=True (KN_FLAG_NARROW32: convtaps_narrow32_kernel, the matrix-core narrow kernel at NV = 16 | 32; KeyedModel.NARROW32_MAX)
-NARROW64_MAX = 64     # ... with narrow64=True (KN_FLAG_NARROW64: beyond NARROW32_MAX columns convtaps_exact_pipe64_kernel, no matrix-core form; KeyedModel.NARROW64_MAX)
+NARROW64_MAX = 64     # ... with narrow64=True (KN_FLAG_NARROW64: beyond NARROW32_MAX columns convtaps_exact_pipe64_kernel; narrow64='mfma': the f32 tile kernel on 64-column tiles; KeyedModel.NARROW64_MAX)
 
 
 def _narrow_args(n, narrow, narrow_rows, what='images', alone=False, narrow32=False, narrow64=False):
     """The argument rule of the narrow forms, for a batch of `n`: `narrow_rows` only together with `narrow` (`alone`: a container's torchdot, which takes one
     keyword or the other), at most NARROW_MAX columns; `narrow32` only together with `narrow`, whose limit it lifts to NARROW32_MAX -- not that of `narrow_rows`
     (the row-lane kernel is an 8-column kernel); `narrow64` only together with `narrow` as well: it implies `narrow32` (at most NARROW32_MAX columns the call is exactly
-    narrow32=True) and lifts the limit to NARROW64_MAX, where narrow='mfma' is refused beyond NARROW32_MAX (no matrix-core form at that width).
+    narrow32=True) and lifts the limit to NARROW64_MAX, where narrow='mfma' with narrow64=True is refused beyond NARROW32_MAX (True asks for the order-preserving form
+    of that width); `narrow64='mfma'` only together with narrow='mfma': the matrix-core form of NARROW32_MAX + 1 .. NARROW64_MAX columns (KN_FLAG_NARROW64_MFMA), and at
+    NARROW32_MAX columns and fewer exactly narrow='mfma', narrow32=True.
     ValueError, or the normalised (mode, rows): mode False | True | 'mfma', rows a bool."""
+    if narrow64 == 'mfma' and narrow != 'mfma':
+        raise ValueError('narrow64=\'mfma\' is the matrix-core form of %d .. %d %s: pass narrow=\'mfma\' with it (got narrow=%r)' % (NARROW32_MAX + 1, NARROW64_MAX, what, narrow))
     if narrow_rows and not narrow and not alone:
         raise ValueError('narrow_rows=True is a form of the narrow forward: pass narrow=True or narrow=\'mfma\' with it')
     if narrow32 and not narrow:
@@ -133,7 +139,7 @@ def _narrow_args(n, narrow, narrow_rows, what='images', alone=False, narrow32=Fa
     limit = NARROW64_MAX if narrow64 else (NARROW32_MAX if narrow32 else NARROW_MAX)
     if narrow and n > limit:
         raise ValueError('narrow=%r%s takes at most %d %s, got %d' % (narrow, ', narrow64=True' if narrow64 else (', narrow32=True' if narrow32 else ''), limit, what, n))
-    if narrow == 'mfma' and n > NARROW32_MAX:
+    if narrow == 'mfma' and n > NARROW32_MAX and narrow64 != 'mfma':
         raise ValueError('narrow=\'mfma\', narrow64=True: there is no matrix-core form at %d .. %d %s (got %d); the padded forward is the matrix-core path there, '
                          'narrow=True the order-preserving one' % (NARROW32_MAX + 1, NARROW64_MAX, what, n))
     return (narrow if narrow == 'mfma' else bool(narrow), bool(narrow_rows))
@@ -646,6 +652,9 @@ class Conv2dTiledMatrix(TiledMatrix):
         operator is eligible (no (pixel, tap) pair with more than two slots); under True / 'auto', and on an ineligible operator, exactly narrow=True.
         narrow32=True (with `narrow`): N <= NARROW32_MAX -- beyond NARROW_MAX columns convtaps_narrow32_kernel (the bits of exact=True), or the matrix-core narrow
         kernel at NV = 16 | 32 (per column the bits of narrow='mfma' on that column).
+        narrow64='mfma' (with narrow='mfma'): N <= NARROW64_MAX -- beyond NARROW32_MAX columns, under exact=False / 'bf16x3', the f32 matrix-core product on 64-column
+        tiles (KN_FLAG_NARROW64_MFMA: per column the bits of the plain matrix-core call on the batch zero-padded to 128 columns); under every other contract
+        narrow64=True; at NARROW32_MAX columns and fewer exactly narrow='mfma', narrow32=True.
         narrow64=True (with `narrow`; implies narrow32): N <= NARROW64_MAX -- beyond NARROW32_MAX columns the order-preserving pipeline with one column per lane
         (KN_FLAG_NARROW64, convtaps_exact_pipe64_kernel; a filled-in operator: what exact=True runs at that width), the bits of exact=True; narrow='mfma' is refused there."""
         assert not isinstance(exact, str) or exact in ('bf16x3', 'split') or (narrow and exact == 'auto'), "exact must be True, False, 'bf16x3' or 'split'"

@@ -227,11 +227,39 @@ class KeyedModel(object):
         exactly narrow32=True.  Beyond, the conv-taps layers run the order-preserving pipeline with one image per lane (KN_FLAG_NARROW64: convtaps_exact_pipe64_kernel, half
         the packed instructions per step of the padded 128-image tile; a filled-in operator runs what exact=True runs at that width) -- the bits of exact=True under every
         contract, so the forward of a key-net under the bit-exact contract equals the padded one bit for bit.  Nothing is padded, calibrated, screened, decided or recorded.
-        There is no matrix-core form at 33 .. 64 images: narrow='mfma' is a ValueError there (the padded forward is the matrix-core path)."""
-        (mode, rows) = ksp._narrow_args(img_cipher.shape[0], narrow, narrow_rows, narrow32=narrow32, narrow64=narrow64)
-        (x, windows) = self._prepare(img_cipher, mode)
-        y = self._forward_passes(x, windows, False if mode else overlap, mode, rows, bool(narrow32), bool(narrow64))[0][:img_cipher.shape[0]]
+        narrow='mfma' with narrow64=True is a ValueError at 33 .. 64 images (True asks for the order-preserving form of that width).
+        `narrow64='mfma'` (only together with narrow='mfma', ValueError otherwise; at most NARROW64_MAX images): the matrix-core forward of 33 .. 64 images.  At NARROW32_MAX
+        images and fewer the call is exactly narrow='mfma', narrow32=True, bit for bit.  Beyond, the batch is laid out feature-major and zero-padded to 64 columns (the
+        argument of _prepare's padding: an image's logits are the same in any batch, zero images raise no layer's max |x|), and a conv-taps layer whose contract in force is
+        False or 'bf16x3' runs the f32 tile kernel on 64-column tiles (KN_FLAG_NARROW64_MFMA: convtaps_mfma_kernel<MT, NB=64>; there is no bf16 form at this width) -- per
+        image the bits the padded forward's f32 tiles give it, half the matrix work of the 128-column tile the padded forward runs half empty.  A conv-taps layer under True,
+        still 'auto', or decided 'split' runs what narrow64=True runs (the order-preserving pipeline, which satisfies every contract: nothing is decided or recorded); the
+        other layers run as they do without the keyword, at 64 columns.  A key-net with no layer on a re-ordering contract therefore returns the bits of narrow=True,
+        narrow64=True.  The screen: the 64-column tile is the WIDE kernel's association, so a declared layer is unscreened and a layer calibration put there (screened()) is
+        re-screened against its WIDE record (not the narrow one, which belongs to the other kernel), through the same slots and RESCREEN_FACTOR.  A tripped layer goes back
+        to 'auto' as on the wide path (launch lists dropped), this pass runs again with that layer in the stored order, and the next padded forward calibrates it: nothing
+        calibrates inside this path."""
+        n = img_cipher.shape[0]
+        (mode, rows) = ksp._narrow_args(n, narrow, narrow_rows, narrow32=narrow32, narrow64=narrow64)
+        narrow64 = self._narrow64_form(n, narrow64)
+        (x, windows) = self._prepare64(img_cipher) if narrow64 == 'mfma' else self._prepare(img_cipher, mode)
+        y = self._forward_passes(x, windows, False if mode else overlap, mode, rows, bool(narrow32), narrow64)[0][:n]
         return y if img_cipher.is_cuda else y.to(img_cipher.device)
+
+    @staticmethod
+    def _narrow64_form(n, narrow64):
+        """The normalised `narrow64` of a batch of n images: 'mfma' beyond NARROW32_MAX images only (at fewer, narrow64='mfma' is exactly narrow64=True, i.e. narrow32), else a bool."""
+        return 'mfma' if (narrow64 == 'mfma' and n > ksp.NARROW32_MAX) else bool(narrow64)
+
+    def _prepare64(self, x):
+        """(x, windows) of a narrow64='mfma' forward of 33 .. 64 images: one feature-major float32 device block of NARROW64_MAX columns, the images beyond the batch zero
+        (the straight-line loaders of the 64-column tile take whole aligned tiles, and the stores are wide).  _prepare is not involved."""
+        x = x.detach().float()
+        if not x.is_cuda:
+            x = x.cuda()
+        xp = torch.zeros((x.shape[1], self.NARROW64_MAX), dtype=torch.float32, device=x.device).t()
+        xp[:x.shape[0]] = x
+        return (xp, [(0, self.NARROW64_MAX)])
 
     def _prepare(self, x, narrow=False):
         """What the kernels get to see: (x, windows), the image ranges of the passes.  A host batch goes to the device ONCE (the layers chain
@@ -271,7 +299,10 @@ class KeyedModel(object):
         re-screened (the next forward decides).  Under a HIP-graph capture nothing is read: `screens` = (slots, screened) per pass, for capture's replay.
         `narrow` / `rows` / `narrow32` / `narrow64` (the normalised keywords narrow, narrow_rows, narrow32, narrow64 of forward_linear): the screened layers are those a MEASUREMENT put on the matrix-core narrow kernel (none under
         narrow=True; an 'auto' layer does not switch the screen off: it runs in the reference's order for this call), screened against their narrow records; layers
-        measured during a pass were measured on this very batch, so only the records that existed before it are screened."""
+        measured during a pass were measured on this very batch, so only the records that existed before it are screened.
+        narrow64 == 'mfma' (33 .. 64 images, _prepare64's block): the screened layers are the conv-taps layers a CALIBRATION put on the f32 / bf16x3 matrix-core kernels -- they
+        run the wide kernel's association on 64-column tiles -- screened against their WIDE records; a trip sends the layer back to 'auto' (stored order in the re-run)."""
+        wide64 = narrow == 'mfma' and narrow64 == 'mfma'
         keyed = self._keyed()
         on_dev = x.is_cuda and x.dim() == 2
         read = on_dev and not torch.cuda.is_current_stream_capturing() and self.RESCREEN_READ
@@ -281,7 +312,10 @@ class KeyedModel(object):
             k = todo.pop(0)
             screened = set()
             if on_dev and self.RESCREEN and (narrow == 'mfma' if narrow else not any(getattr(c, '_exact', True) == 'auto' for c in keyed)):
-                screened = set(j for (j, c) in enumerate(keyed) if (c.narrow_screened() if narrow else c.screened()))
+                if wide64:
+                    screened = set(j for (j, c) in enumerate(keyed) if c.screened() and isinstance(c.W, ksp.Conv2dTiledMatrix) and c.W.narrow_capable() and c._exact in (False, 'bf16x3'))
+                else:
+                    screened = set(j for (j, c) in enumerate(keyed) if (c.narrow_screened() if narrow else c.screened()))
             slots = torch.zeros(len(keyed) + 1, dtype=torch.float32, device=x.device) if screened else None
             (lo, hi) = windows[k]
             # (a window of a wider block: its own feature-major block, so that the pass can take the overlapped form)
@@ -291,7 +325,7 @@ class KeyedModel(object):
             screens.append((slots, screened))
             if not read or (todo and redos + 1 == self.RESCREEN_MAX_PASSES):
                 continue
-            if self._rescreen(slots.tolist(), keyed, screened, bool(narrow)) and redos + 1 < self.RESCREEN_MAX_PASSES:
+            if self._rescreen(slots.tolist(), keyed, screened, bool(narrow) and not wide64) and redos + 1 < self.RESCREEN_MAX_PASSES:
                 redos += 1
                 todo = [k] + [j for j in range(len(windows)) if j != k]
         return (ys[0] if len(ys) == 1 else torch.cat([y.t() for y in ys], dim=1).t(), screens)
@@ -607,13 +641,17 @@ class KeyedModel(object):
         (measuring again) and captures a new graph, as the wide capture does; with no such layer it reads nothing.
         `narrow_rows=True` (only with `narrow`): the graph of forward_linear(narrow=..., narrow_rows=True): the same straight line of launches.
         `narrow32=True` (only with `narrow`): the graph of forward_linear(narrow=..., narrow32=True), up to NARROW32_MAX images.
-        `narrow64=True` (only with `narrow`): the graph of forward_linear(narrow=True, narrow64=True), up to NARROW64_MAX images -- the same straight line of launches on one stream."""
+        `narrow64=True` (only with `narrow`): the graph of forward_linear(narrow=True, narrow64=True), up to NARROW64_MAX images -- the same straight line of launches on one stream.
+        `narrow64='mfma'` (only with narrow='mfma'): the graph of forward_linear(narrow='mfma', narrow64='mfma') -- at 33 .. 64 images the 64-column block of that forward, still a
+        straight line of launches on one stream.  With layers on the matrix-core kernels by calibration the graph gathers their max |x|; replay() reads the slots against the
+        WIDE records and on a trip runs the batch eagerly (the tripped layer back to 'auto', in the stored order) and captures a new graph, as the wide capture does."""
         assert img_cipher.is_cuda, 'capture() needs a device tensor'
         n = img_cipher.shape[0]
         (mode, rows) = ksp._narrow_args(n, narrow, narrow_rows, narrow32=narrow32, narrow64=narrow64)
-        (narrow32, narrow64) = (bool(narrow32), bool(narrow64))
+        (narrow32, narrow64) = (bool(narrow32), self._narrow64_form(n, narrow64))
+        wide64 = narrow64 == 'mfma'
         src = img_cipher.detach().float() if mode else img_cipher.detach()
-        (static_in, windows) = self._prepare(src.t().clone(memory_format=torch.contiguous_format).t(), mode)     # the graph's own input block
+        (static_in, windows) = self._prepare64(src) if wide64 else self._prepare(src.t().clone(memory_format=torch.contiguous_format).t(), mode)     # the graph's own input block
         keyed = self._keyed()
         state = {}
 
@@ -637,7 +675,7 @@ class KeyedModel(object):
         def replay(x):
             static_in[:n].copy_(x)
             state['graph'].replay()
-            if any(self._rescreen(slots.tolist(), keyed, screened, bool(mode)) for (slots, screened) in state['screens']):
+            if any(self._rescreen(slots.tolist(), keyed, screened, bool(mode) and not wide64) for (slots, screened) in state['screens']):
                 build()                                          # eager forward on this batch re-calibrates (narrow: measures again); then a fresh graph
                 state['graph'].replay()
             replay.graph = state['graph']
@@ -648,7 +686,8 @@ class KeyedModel(object):
     def forward(self, img_cipher, outkey=None, narrow=False, narrow_rows=False, narrow32=False, narrow64=False):
         """Encrypted image(s) [N, D0+1] -> logits.  N == 1 returns the reference's shape `outshape` = (C,1,1)
         (keynet/system.py:130-133); N > 1 (an extension: the reference cannot) returns (N, C, 1, 1).  `narrow`: forward_linear(narrow=True | 'mfma'), the
-        low-latency forms of this very call for 1 .. NARROW_MAX images; `narrow_rows`: with them, the CSR layers on the row-lane kernel (forward_linear); `narrow32`: with them, up to NARROW32_MAX images; `narrow64`: up to NARROW64_MAX."""
+        low-latency forms of this very call for 1 .. NARROW_MAX images; `narrow_rows`: with them, the CSR layers on the row-lane kernel (forward_linear); `narrow32`: with them, up to NARROW32_MAX images; `narrow64`: up to NARROW64_MAX
+        (narrow64=True: the order-preserving form of 33 .. 64 images; narrow64='mfma', with narrow='mfma': the matrix-core form on 64-column tiles, forward_linear)."""
         outkey = outkey if outkey is not None else self.embeddingkey()
         y = self.forward_linear(img_cipher, narrow=narrow, narrow_rows=narrow_rows, narrow32=narrow32, narrow64=narrow64)
         if outkey is not None:

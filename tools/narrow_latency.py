@@ -46,6 +46,10 @@ width forced by KN_NARROW32_NV (read at create by the diagnostic build only: key
     python tools/narrow_latency.py --narrow64 --one-forward      # at 64 images ONE forward without the keyword (padded to 128), then ONE narrow=True, narrow64=True forward
     python tools/narrow_latency.py --narrow64 --from-trace DIR/.../*_kernel_trace.csv          # no GPU: the 13 conv launches of those two forwards
 
+--mfma64 (profiles/r12_narrow64_mfma.txt): under exact_mode('auto') after one calibrating padded forward, in one process with the forms alternating, at 33, 48 and 64
+images: (a) the forward without the keyword (padded to 128 images), (b) narrow='mfma', narrow64='mfma' (the f32 tile kernel on 64-column tiles; logits torch.equal to (a)
+before any time is printed), (c) the same images as two narrow='mfma', narrow32=True forwards.  `--mfma64 --one-forward` / `--mfma64 --from-trace`: the conv launches of one
+(a) and one (b) forward at 64 images, layer by layer.
 --narrow64: under the default contract, in one process with the forms alternating: the forward without the keyword (a tiled key-net: padded to 128 images) against
 narrow=True, narrow64=True at 33, 48 and 64 images (`--workload allconv`: at 48) -- logits torch.equal before any time is printed --, and the narrow32 forward at 32
 images for the ladder.  The bars of the file are computed from the table."""
@@ -260,32 +264,88 @@ def narrow64_table(args, knet, xc, desc):
         f.write(text)
 
 
+def mfma64_table(args, knet, xc, desc):
+    """--mfma64: see the module docstring."""
+    from keynet_amd import sparse as ksp
+    blk = lambda lo, hi: xc[lo:hi].t().contiguous().t()
+    kw = dict(narrow='mfma', narrow64='mfma')
+    kw32 = dict(narrow='mfma', narrow32=True)
+    knet.exact_mode('auto')
+    knet.forward_linear(blk(0, 64))               # the calibrating padded forward
+    convs = [(name, c) for (name, c) in knet._keyed(named=True) if isinstance(c.W, ksp.Conv2dTiledMatrix)]
+    if args.one_forward:
+        for _ in range(2):                        # operators resident, workspaces sized
+            knet.forward_linear(blk(0, 64))
+            knet.forward_linear(blk(0, 64), **kw)
+        torch.cuda.synchronize()
+        print("TRACE-FROM-HERE: at 64 images one forward without the keyword (padded to 128), then one narrow='mfma', narrow64='mfma' forward", flush=True)
+        knet.forward_linear(blk(0, 64))
+        torch.cuda.synchronize()
+        knet.forward_linear(blk(0, 64), **kw)
+        torch.cuda.synchronize()
+        return
+    cell = lambda v: '%8.3f (%.3f .. %.3f)' % (statistics.median(v), min(v), max(v))
+    lines = ['', "== tools/narrow_latency.py --mfma64: %s under exact_mode('auto') after one calibrating padded forward" % desc,
+             '   %s, torch %s; HIP events, %d warm-up + median of %d forwards (min .. max), the forms of a row alternating in quarters; logits of (b) torch.equal to (a): yes'
+             % (torch.cuda.get_device_name(0), torch.__version__, args.warmup, args.forwards),
+             '   conv layers on the f32 / bf16x3 matrix-core kernels by calibration: %d of %d' % (sum(1 for (_, c) in convs if c._exact in (False, 'bf16x3')), len(convs)),
+             "   %6s | %-28s | %-28s | %-28s | %s" % ('images', '(a) no keyword, padded [ms]', "(b) narrow64='mfma' [ms]", "(c) two narrow32 'mfma' [ms]", '(a) / (b), (c) / (b)')]
+    med = {}
+    for n in N64_IMAGES:
+        (x, xa, xb) = (blk(0, n), blk(0, 32), blk(32, n))
+        (y0, y1) = (knet.forward_linear(x), knet.forward_linear(x, **kw))
+        knet.forward_linear(xa, **kw32)           # (measures the narrow records of calibrated layers once)
+        knet.forward_linear(xb, **kw32)
+        torch.cuda.synchronize()
+        assert torch.equal(y0, y1), "narrow64='mfma' logits differ from the padded forward at %d images: max %g" % (n, float((y0 - y1).abs().max()))
+        forms = [lambda: knet.forward_linear(x), lambda: knet.forward_linear(x, **kw), lambda: (knet.forward_linear(xa, **kw32), knet.forward_linear(xb, **kw32))]
+        t = [[] for _ in forms]
+        for _ in range(4):                        # alternate in quarters
+            for (u, f) in zip(t, forms):
+                u += timed(f, args.forwards // 4, args.warmup)
+        med[n] = [statistics.median(u) for u in t]
+        lines.append('   %6d | %-28s | %-28s | %-28s | %.2fx, %.2fx' % (n, cell(t[0]), cell(t[1]), cell(t[2]), med[n][0] / med[n][1], med[n][2] / med[n][1]))
+        print('n = %d done' % n, flush=True)
+    lines.append('   bars at 64 images: (a) / (b) = %.2fx (>= 1.3x asked, 2x is the ceiling: half the matrix work); (c) / (b) = %.2fx (must exceed 1)' % (med[64][0] / med[64][1], med[64][2] / med[64][1]))
+    lines.append('   the 64-column launch of each conv layer (kn_spmm_plan at 64 aligned columns):')
+    for (name, c) in convs:
+        la = c.launch(xc.device, relu=False, **kw)
+        with torch.cuda.device(xc.device):
+            lines.append('     %-10s %s' % (name, la.op.plan(64, la.flags).split(';')[0]))
+    text = '\n'.join(lines) + '\n'
+    print(text)
+    with open(args.out or os.path.join(ROOT, 'profiles', 'r12_narrow64_mfma.txt'), 'a') as f:
+        f.write(text)
+
+
 def narrow64_trace_table(args):
-    """--narrow64 --from-trace: the conv launches of the last two forwards of a `--narrow64 --one-forward` run (device timestamps)."""
+    """--narrow64 --from-trace: the conv launches of the last two forwards of a `--narrow64 --one-forward` run (device timestamps).  With --mfma64: of a `--mfma64 --one-forward` run."""
     import csv
     with open(args.from_trace, newline='') as f:
         rows = [r for r in csv.DictReader(f) if 'convtaps_' in r['Kernel_Name'] and 'zero_guard' not in r['Kernel_Name']]
     rows.sort(key=lambda r: int(r['Start_Timestamp']))
-    k = args.convs
+    k = args.convs + args.linears                 # (a keyed nn.Linear on the matrix cores is a split-K launch of the same kernel family, behind the convs of its forward)
     assert len(rows) >= 2 * k, 'the trace holds %d conv launches, fewer than 2 forwards of %d' % (len(rows), k)
     (wide, new) = (rows[-2 * k:-k], rows[-k:])
     us = lambda r: (int(r['End_Timestamp']) - int(r['Start_Timestamp'])) / 1e3
     wgs = lambda r: int(r.get('Grid_Size_X') or 0) // max(1, int(r.get('Workgroup_Size_X') or 1))
     short = lambda r: r['Kernel_Name'].replace('void kn::', '').split('(')[0]
-    lines = ['', '== tools/narrow_latency.py --narrow64 --from-trace: the conv launches of one forward without the keyword (64 images padded to 128) and one narrow=True, narrow64=True forward',
+    (flag, form, out) = ('--mfma64', "narrow='mfma', narrow64='mfma'", 'r12_narrow64_mfma.txt') if args.mfma64 else ('--narrow64', 'narrow=True, narrow64=True', 'r11_narrow64.txt')
+    lines = ['', '== tools/narrow_latency.py %s --from-trace: the conv launches of one forward without the keyword (64 images padded to 128) and one %s forward' % (flag, form),
              '   of the same 64 images (rocprofv3 --kernel-trace, device timestamps)', '',
              '   conv launch | workgroups, padded | padded [us] | workgroups, narrow64 | narrow64 [us] | ratio | kernels']
     slower = []
     for (j, (a, b)) in enumerate(zip(wide, new)):
-        lines.append('     %2d | %7d | %9.1f | %7d | %9.1f | %5.2fx | %s / %s' % (j + 1, wgs(a), us(a), wgs(b), us(b), us(a) / us(b), short(a), short(b)))
-        if us(b) > us(a):
+        lines.append('     %2s | %7d | %9.1f | %7d | %9.1f | %5.2fx | %s / %s' % (j + 1 if j < args.convs else 'fc', wgs(a), us(a), wgs(b), us(b), us(a) / us(b), short(a), short(b)))
+        if us(b) > us(a) and j < args.convs:
             slower.append(j + 1)
-    (sa, sb) = (sum(us(r) for r in wide), sum(us(r) for r in new))
+    (sa, sb) = (sum(us(r) for r in wide[:args.convs]), sum(us(r) for r in new[:args.convs]))
+    k = args.convs
     lines.append('     sum of the %d conv launches: %9.1f | %9.1f | %5.2fx' % (k, sa, sb, sa / sb))
     lines.append('     conv launches slower on the new form than on the padded 128-column form: %s' % (', '.join(str(j) for j in slower) or 'none'))
     text = '\n'.join(lines) + '\n'
     print(text)
-    with open(args.out or os.path.join(ROOT, 'profiles', 'r11_narrow64.txt'), 'a') as f:
+    with open(args.out or os.path.join(ROOT, 'profiles', out), 'a') as f:
         f.write(text)
 
 
@@ -504,17 +564,19 @@ def main():
     ap.add_argument('--out', default=None, help='the file the table is appended to (default: profiles/r07_narrow_forward.txt, with --mfma or --from-trace profiles/r08_narrow_mfma.txt)')
     ap.add_argument('--from-trace', default=None, help='a *_kernel_trace.csv of a --mfma --one-forward run: print its conv launches, layer by layer (no GPU)')
     ap.add_argument('--convs', type=int, default=13, help='conv layers per forward in --from-trace')
+    ap.add_argument('--linears', type=int, default=0, help='with --from-trace: keyed nn.Linear layers per forward that launch the conv-taps tile kernel as split-K (VGG-16 under the tolerance contract: 3)')
     ap.add_argument('--one-forward', action='store_true', help='key, warm up, run one narrow forward and exit (for a kernel trace)')
     ap.add_argument('-n', type=int, default=1, help='images of --one-forward')
     ap.add_argument('--rows', action='store_true', help='whole forwards and single layers with and without narrow_rows=True (profiles/r09_narrow_rows.txt)')
     ap.add_argument('--mfma', action='store_true', help="exact_mode('auto') after one calibrating wide forward: padded, narrow=True, narrow='mfma'")
     ap.add_argument('--narrow32', action='store_true', help='9 .. 32 images: no keyword against narrow32=True, both contracts (profiles/r10_narrow32.txt)')
     ap.add_argument('--narrow64', action='store_true', help='33 .. 64 images: no keyword against narrow=True, narrow64=True under the default contract (profiles/r11_narrow64.txt)')
+    ap.add_argument('--mfma64', action='store_true', help="33 .. 64 images under exact_mode('auto'): padded forward, narrow='mfma' narrow64='mfma', two narrow32 forwards (profiles/r12_narrow64_mfma.txt)")
     ap.add_argument('--images', type=lambda v: tuple(int(k) for k in v.split(',')), default=N32_IMAGES, help='image counts of --narrow32')
     ap.add_argument('--blocks', action='store_true', help='with --narrow32: one conv5_x-shaped operator per column-block width (diagnostic build)')
     args = ap.parse_args()
     if args.from_trace:
-        return narrow64_trace_table(args) if args.narrow64 else narrow32_trace_table(args) if args.narrow32 else rows_trace_table(args) if args.rows else trace_table(args)
+        return narrow64_trace_table(args) if (args.narrow64 or args.mfma64) else narrow32_trace_table(args) if args.narrow32 else rows_trace_table(args) if args.rows else trace_table(args)
     if args.narrow32 and args.blocks:
         return narrow32_blocks(args)
     assert args.forwards >= 20 or args.one_forward, 'the median of at least 20 forwards'
@@ -522,10 +584,12 @@ def main():
     (sensor, knet, inshape, _, desc, _) = workloads.build_workload(args.workload, 0, fanout=True)
     dev = torch.device('cuda:0')
     torch.manual_seed(1)
-    imgs = torch.randn((64 if args.narrow64 else max(args.images) if args.narrow32 else 8,) + tuple(inshape))
+    imgs = torch.randn((64 if (args.narrow64 or args.mfma64) else max(args.images) if args.narrow32 else 8,) + tuple(inshape))
     xc = sensor.fromtensor(imgs.to(dev)).encrypt().astensor()
     xc = xc.t().contiguous().t()                  # feature-major, as the layers hand blocks on
     print('keyed %s in %.0f s' % (desc, time.time() - t0), flush=True)
+    if args.mfma64:
+        return mfma64_table(args, knet, xc, desc)
     if args.narrow64:
         return narrow64_table(args, knet, xc, desc)
     if args.narrow32:
