@@ -126,6 +126,25 @@ enum kn_status {
                               n_vecs > 64; on CSR, dense, float64 and chain handles; in kn_spmm_planes.  kn_spmm_plan names the launch
                               ("convtaps_mfma_kernel<MT=..,NB=64,KC=..> loader=..").  No reference counterpart. */
 
+#define KN_FLAG_NARROW_LINEAR (0x200u)  /* = 512.  Low-latency form of a keyed Linear under the bit-exact contract, for 1 .. 64 batch columns.  An opt-in of its own, like KN_FLAG_NARROW_ROWS:
+                              the conv flags neither imply nor exclude it.
+                              What runs.  For n_vecs <= 32 (see below for 33 .. 64) a float32 CSR handle (kn_csr_create, kn_tiled_create) that holds BIG pattern groups (>= 256 rows over >= 2 048 shared
+                              columns: a keyed nn.Linear) runs csr_stream_group_kernel on those groups.  A workgroup owns 64 member rows times all n_vecs columns: the lane is
+                              the OUTPUT ROW, W = 1 | 2 | 4 | 8 wavefronts carry NV = 1 | 2 | 4 columns each as running sums (W * NV >= n_vecs), and the values reach them
+                              through a ring in LDS that all wavefronts fill ahead of the walk -- the 256-byte value segments, and the activations of each step next to them --, so a value leaves HBM once per call.  The walk over a
+                              row's stored columns is serial, in stored order, with separate multiply and add: bit for bit the result without the flag.  Everything else
+                              the operator holds -- loose rows, the homogeneous row, long loose rows, small groups, the patched-row guard -- runs exactly what the call's other
+                              flags make it; with KN_FLAG_NARROW_ROWS next to it at n_vecs <= 8 those parts take csr_narrow_kernel, and the big groups take
+                              csr_stream_group_kernel at every width 1 .. 8 (KN_FLAG_NARROW_ROWS alone keeps its own rule, big-group operators at 1 and 2 columns only).
+                              Where it changes NOTHING (same kernels, same plan string, same bits as without it; the call falls back, it does not refuse):
+                                - on an operator without a big pattern group;
+                                - at n_vecs > 64, and at 33 <= n_vecs <= 64: the form built for that range (8 wavefronts x 8 columns) measured 0.69x of csr_big_group_kernel on
+                                  VGG-16's fc6 - fc8, so a handle with big groups keeps the kernel it has there (narrow_linear_loses; profiles/r13_narrow_linear.txt);
+                                - on conv-taps, dense, float64 and chain handles, and in kn_spmm_planes.
+                              The kernel forms every address into X in 64 bits: it takes any ldx (KN_FLAG_NARROW_ROWS next to it keeps its own rule for the parts it runs).
+                              Honoured by kn_spmm, by kn_spmm_screen (max |Y| by the library's reduction pass over Y) and by kn_spmm_plan, which names the kernel, W, NV, the
+                              number of 64-row chunks and the ring.  No reference counterpart. */
+
 typedef struct kn_operator* kn_handle_t;   /* opaque keyed operator resident in HBM */
 
 int         kn_abi_version(void);
@@ -250,6 +269,7 @@ int kn_export_csr_f64(kn_handle_t h, int32_t* indptr, int32_t* indices, double* 
  *   conv-taps, KN_FLAG_NARROW64 (33 <= n_vecs <= 64)    (D + 1) * ldx < 2^31                               else the plain order-preserving kernel
  *   conv-taps, KN_FLAG_NARROW64_MFMA (33 .. 64)         the matrix-core rules above at NB = 64 (T = 16), on n_vecs = 64 aligned columns; else the generic loader
  *   CSR, KN_FLAG_NARROW_ROWS (n_vecs <= 8)               cols * ldx + 8 < 2^30                              else the kernels the call takes without the flag
+ *   CSR, KN_FLAG_NARROW_LINEAR (n_vecs <= 32)            none: 64-bit addresses, any ldx
  * The small-K matrix-core kernels of first-layer operators (slots * Cin + bias <= 28 contraction rows) form row * ldx in 64 bits and take any ldx.
  * KN_FLAG_NARROW / KN_FLAG_NARROW_MFMA (n_vecs <= 8 on a conv-taps operator) do NOT fall back: they return KN_ERR_UNSUPPORTED, Y untouched, unless (D + 1) * ldx + 8 < 2^31
  * (with KN_FLAG_NARROW32 at 9 <= n_vecs <= 32: unless (D + 1) * ldx + 32 < 2^31).

@@ -524,7 +524,7 @@ void csr_free(CsrDev& c) {
                     c.loose_rows, c.long_rows, c.patch_rows, c.patch_ptr, c.patch_cols};
     for (void* p : ptrs)
         if (p) (void)hipFree(p);
-    for (WorkList* w : {&c.work, &c.big, &c.ws, &c.mf[0], &c.mf[1], &c.mf[2], &c.mf16, &c.nr}) {
+    for (WorkList* w : {&c.work, &c.big, &c.ws, &c.mf[0], &c.mf[1], &c.mf[2], &c.mf16, &c.nr, &c.sg, &c.nrs}) {
         if (w->grp) (void)hipFree(w->grp);
         if (w->r0) (void)hipFree(w->r0);
     }
@@ -683,7 +683,7 @@ struct HostList {
     }
 };
 struct HostLists {
-    HostList work, big, ws, mf[3], mf16, nr;
+    HostList work, big, ws, mf[3], mf16, nr, sg, nrs;
     int64_t mf_rows = 0, mf_nnz = 0;
 };
 // Each kernel's chunk rule, one line per list: which groups, what chunk height.  Every list is in group order, a group's chunks in member order.
@@ -694,6 +694,7 @@ static HostLists csr_cut_work_lists(const GroupTables& T, const Tuning& tune) {
         const bool big = n_mem >= 256 && ncol >= 2048 && !tune.no_big_groups;      // a keyed nn.Linear
         const bool mf = !big && n_mem >= MF_MIN_MEMBERS;
         L.nr.cut(g, n_mem, 64);                        // every group in 64-row chunks for the row-lane kernel (1 .. 8 batch columns)
+        (big ? L.sg : L.nrs).cut(g, n_mem, 64);        // the same chunks in two lists: the big groups for the value-stream kernel (1 .. 32 columns), the others for the row-lane kernel next to it
         if (big) L.big.cut(g, n_mem, BIG_ROWS);        // LDS-staged kernel, 32 rows per workgroup
         if (big) L.mf16.cut(g, n_mem, 16);             // the same group for the 16-row matrix-pipe kernel (narrow batches)
         if (!big) L.work.cut(g, n_mem, RB);            // the vector-ALU grouped kernels: bundles of RB rows
@@ -762,6 +763,7 @@ static int csr_upload(CsrDev& A, const GroupTables& T, const HostLists& L, const
     for (const auto& l : lists)
         if ((rc = work_list(*l.first, *l.second))) return rc;
     if ((rc = arrays({{&A.long_rows, &U.longrows}, {&A.loose_rows, &U.loose}}))) return rc;
+    if ((rc = work_list(A.sg, L.sg)) || (rc = work_list(A.nrs, L.nrs))) return rc;      // (behind everything else: the older arrays land where they always have)
     A.n_groups = T.n_groups();
     A.grouped_nnz = T.grouped_nnz;
     A.n_patch = (int64_t)T.patch_rows.size();
@@ -1134,6 +1136,7 @@ struct CsrChoice {
     int64_t n_loose = 0;
     VecRows t = {1, 1};              // PLAIN: launch_csr<vec, rbk>; PIPE: rbk = 16 | 8
     bool absmax_rides = false;       // max |Y| (kn_spmm_screen) in the epilogue of the row kernel
+    bool stream = false;             // KN_FLAG_NARROW_LINEAR: the big groups on csr_stream_group_kernel (then `big` is BIG_NONE and a ROW_LANES launch takes CsrDev::nrs)
 };
 
 static CsrChoice csr_choice(const CsrDev& A, const float* x, int64_t ldx, const float* y, int64_t ldy, int64_t n_vecs, uint32_t flags) {
@@ -1142,10 +1145,12 @@ static CsrChoice csr_choice(const CsrDev& A, const float* x, int64_t ldx, const 
     // KN_FLAG_NARROW_ROWS on 1 .. 8 columns: the long loose rows in the deep-queue role of the big-group launch, as without the flag; loose rows too long for a lane
     // (narrow_rows_loose) on csr_rows_kernel, as without the flag; everything else in one launch of the row-lane kernel.  max |Y| comes from the caller's reduction
     // pass, as behind the other narrow kernels.
+    // KN_FLAG_NARROW_LINEAR where narrow_linear_call takes it (big groups, 1 .. 32 columns): those groups on the value-stream kernel; everything else is what the call is without them
+    c.stream = narrow_linear_call(A, flags, n_vecs);
     if (narrow_rows_call(A, flags, n_vecs, ldx)) {
         if (A.n_long > 0) c.long_rows = CsrChoice::LONG_DEEP;
         c.kernel = CsrChoice::ROW_LANES;
-        c.groups = A.nr;
+        c.groups = c.stream ? A.nrs : A.nr;
         c.loose_first = !narrow_rows_loose(A) && A.n_loose > 0;
         c.n_loose = narrow_rows_loose(A) ? A.n_loose : 0;
         return c;
@@ -1163,7 +1168,7 @@ static CsrChoice csr_choice(const CsrDev& A, const float* x, int64_t ldx, const 
     // 1024 / 2048 columns: 3.38 / 5.85 / 11.17 against 2.68 / 4.37 / 8.17; 4096 x 4096 at 512 / 1024: 0.59 / 1.02 against 0.49 / 0.77); with ONE wavefront per
     // SIMD (VGG-16 fc6 at 256 images: 1 024 chunks) it loses -- 2.16 against 1.74 ms, a lone wavefront pays ~9 cycles per instruction -- and the LDS-staged
     // kernel stays.  Tuning::big_mfma16 (KN_BIG_MFMA16=0|1 when the operator is created) forces either.
-    if (A.big.n > 0) {
+    if (A.big.n > 0 && !c.stream) {
         const bool mfma16 = A.mf16.n > 0 && n_vecs >= 64 && (A.tune.big_mfma16 < 0 ? A.mf16.n * ((n_vecs + 63) / 64) >= ENOUGH : A.tune.big_mfma16 > 0);
         c.big = mfma16 ? CsrChoice::BIG_MFMA16 : CsrChoice::BIG_LDS;
     }
@@ -1224,13 +1229,14 @@ int csr_spmm(const CsrDev& A, const float* x, int64_t ldx, int64_t n_vecs, float
                   A.data, x, ldx, y, ldy, n_vecs, relu, n_rb);
         KN_HIP(hipGetLastError());
     }
+    if (c.stream && (rc = csr_stream_group_spmm(A, x, ldx, n_vecs, y, ldy, relu, s))) return rc;
     if (c.big == CsrChoice::BIG_MFMA16 && (rc = csr_group_mfma16_spmm(A, A.mf16, x, ldx, n_vecs, y, ldy, relu, s))) return rc;
     if (c.big == CsrChoice::BIG_LDS || c.long_rows == CsrChoice::LONG_DEEP) {
         const int64_t n_ct = (n_vecs + 63) / 64;
         const int64_t n_big = c.big == CsrChoice::BIG_LDS ? A.big.n : 0, n_long_deep = c.long_rows == CsrChoice::LONG_DEEP ? A.n_long : 0;
         const int64_t grid_big = ((n_ct * n_big + 7) / 8) * 8;
         const int64_t grid_long = n_long_deep * ((n_ct + 3) / 4);
-        KN_LAUNCH(c.kernel == CsrChoice::ROW_LANES ? "csr_big_group_kernel (long rows)" : "csr_big_group_kernel", csr_big_group_kernel, dim3((unsigned)(grid_big + grid_long)), dim3(256), 0, s, n_big,
+        KN_LAUNCH(c.kernel == CsrChoice::ROW_LANES || c.stream ? "csr_big_group_kernel (long rows)" : "csr_big_group_kernel", csr_big_group_kernel, dim3((unsigned)(grid_big + grid_long)), dim3(256), 0, s, n_big,
                   A.big.grp, A.big.r0, KN_GROUP_TABLES(A), x, ldx, y, ldy, n_vecs, relu, grid_big, A.long_rows, n_long_deep, A.indptr, A.indices, A.data);
         KN_HIP(hipGetLastError());
     }

@@ -251,6 +251,9 @@ struct CsrDev {
     // the row-lane kernel for 1 .. 8 batch columns (kn_csr_narrow.hip, KN_FLAG_NARROW_ROWS): EVERY pattern group, the big ones included, in chunks of 64
     // member rows (a last chunk may be partly filled); grp_cols carries NARROW_ROWS_COL_PAD entries of padding for its look-ahead
     WorkList nr;
+    // the value-stream kernel for 1 .. 32 batch columns (kn_csr_stream.hip: KN_FLAG_NARROW_LINEAR, narrow_linear_call): sg = the 64-row chunks of the BIG groups, nrs = those of every other
+    // group (nr = both, in group order): what the row-lane kernel keeps next to it
+    WorkList sg, nrs;
     // matrix-pipe products (kn_csr_mfma.hip): pattern groups with >= MF_MIN_MEMBERS members cut into chunks of 32 * (k + 1) member rows, k = 0..2
     // (list k holds the chunks of k + 1 row blocks); ws = the 16-row bundles of the REMAINING (small) groups for the vector-ALU kernels
     WorkList mf[3];
@@ -465,6 +468,36 @@ static constexpr int64_t NARROW_ROWS_LOOSE_MAX = 64;
 static inline bool narrow_rows_loose(const CsrDev& A) { return A.loose_max <= NARROW_ROWS_LOOSE_MAX; }
 int csr_narrow_rows_spmm(const CsrDev& A, const WorkList& groups, const int32_t* loose_rows, int64_t n_loose, const float* x, int64_t ldx, int64_t n_vecs, float* y, int64_t ldy, int relu,
                          hipStream_t s);      // kn_csr_narrow.hip
+// KN_FLAG_NARROW_LINEAR: an f32 CSR operator's BIG pattern groups (a keyed Linear) on the value-stream kernel (kn_csr_stream.hip) for at most NARROW64_MAX_VECS columns,
+// where the handle rule below does not keep the kernel they have; else the flag is ignored (the other kernels give the same bits).  Everything else the operator holds runs what the call's other flags make it.  The kernel forms
+// every address in 64 bits: no condition on ldx.  The one place that reads the flag.
+// The form of a width (at most STREAM_MAX_VECS columns): W wavefronts x NV running sums per lane, W * NV >= n_vecs, the fewest sums per lane that 8 wavefronts allow (a keyed Linear puts one workgroup
+// on a CU -- VGG-16 fc6: 65 chunks on 256 CUs -- so a further wavefront costs nothing but its share of the issue slots, it takes its share of the fills, and every
+// wavefront pays two LDS reads per step whatever its NV).  Chosen on the instruction counts of the compiled loop; the neighbouring forms of a width were not measured
+// against it.
+struct StreamForm { int w, nv; bool full; };
+static inline StreamForm stream_form(int64_t n_vecs) {
+    const int nv = n_vecs <= 8 ? 1 : (n_vecs <= 16 ? 2 : 4);
+    const int64_t per = (n_vecs + nv - 1) / nv;
+    const int w = per <= 1 ? 1 : (per <= 2 ? 2 : (per <= 4 ? 4 : 8));
+    return {w, nv, n_vecs == (int64_t)w * nv};
+}
+// Its ring: slots of one 16-step slab -- 16 x 256 bytes of values, 16 x cw activations (cw = W * NV; at least 256 bytes), 64 column indices -- as many as 64 KB of static
+// LDS hold, at most 11; all but STREAM_SPARE_SLOTS of them in flight: 32 KB of values up to 16 columns, 28 KB (next to 14 KB of activations) at 32.
+static constexpr int STREAM_SLAB_STEPS = 16, STREAM_SPARE_SLOTS = 3, STREAM_MAX_SLOTS = 11;
+static constexpr int stream_slot_bytes(int cw) { return STREAM_SLAB_STEPS * 256 + (STREAM_SLAB_STEPS * cw * 4 < 256 ? 256 : STREAM_SLAB_STEPS * cw * 4) + 256; }
+static constexpr int stream_ring_slots(int cw) { return 64 * 1024 / stream_slot_bytes(cw) < STREAM_MAX_SLOTS ? 64 * 1024 / stream_slot_bytes(cw) : STREAM_MAX_SLOTS; }
+// The WIDTHS that stay on the kernels they have (measured, profiles/r13_narrow_linear.txt): a big-group operator beyond 32 columns.  The form built for them -- W = 8,
+// NV = 8, where 64 KB of LDS hold 7 slots: 16 KB of values in flight next to 16 KB of activations -- issued 8 packed multiplies and adds and five LDS reads per step and
+// wavefront, two wavefronts to a SIMD, and measured 0.69x of csr_big_group_kernel (which carries 64 columns per lane for the price of one) on VGG-16's fc6 at 33 and at 64
+// columns (2 412 us against 1 671, values cold), 0.70x on fc7 and fc8 (407 / 402 us against 285 / 282); up to 32 columns the kernel measured 1.27x .. 3.59x on all three
+// (fc6: 489 us at 1 column, 599 at 8, 880 at 16, 1 300 at 32, against 1 670 .. 1 684).  That form is not instantiated.
+static constexpr int64_t STREAM_MAX_VECS = 32;
+static inline bool narrow_linear_loses(const CsrDev& A, int64_t n_vecs) { return A.big.n > 0 && n_vecs > STREAM_MAX_VECS; }
+static inline bool narrow_linear_call(const CsrDev& A, uint32_t flags, int64_t n_vecs) {
+    return (flags & KN_FLAG_NARROW_LINEAR) && A.big.n > 0 && n_vecs <= NARROW64_MAX_VECS && !narrow_linear_loses(A, n_vecs);
+}
+int csr_stream_group_spmm(const CsrDev& A, const float* x, int64_t ldx, int64_t n_vecs, float* y, int64_t ldy, int relu, hipStream_t s);      // kn_csr_stream.hip
 int convtaps_spmm(const ConvTapsDev& A, const float* x, int64_t ldx, int64_t n_vecs, float* y, int64_t ldy,
                   uint32_t flags, hipStream_t s, float* absmax = nullptr, bool* absmax_fused = nullptr);
 int absmax_pass(const float* y, int64_t rows, int64_t ld, int64_t n_vecs, float* absmax, hipStream_t s);

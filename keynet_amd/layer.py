@@ -209,7 +209,7 @@ class KeyedLayer(nn.Module):
     def iskeyedrelu(self):
         return 'ReLU' in self._layertype
 
-    def forward(self, x_affine, fuse_relu=False, absmax=None, narrow=False, narrow_rows=False, narrow32=False, narrow64=False):
+    def forward(self, x_affine, fuse_relu=False, absmax=None, narrow=False, narrow_rows=False, narrow32=False, narrow64=False, narrow_linear=False):
         """[N, Din+1] -> [N, Dout+1] (keynet/layer.py:88-93).  The result is a transposed view of the feature-major
         [Dout+1, N] block the kernel wrote, so the next layer's x.t() is free.  `fuse_relu` folds the unkeyed nn.ReLU
         that follows this layer in the key-net (keynet/system.py:92) into the kernel epilogue.  `absmax`: a one-element device
@@ -229,7 +229,9 @@ class KeyedLayer(nn.Module):
         `narrow64='mfma'` (with narrow='mfma'): at NARROW32_MAX images and fewer exactly narrow='mfma', narrow32=True.  Beyond, a conv-taps layer whose contract in force is
         False or 'bf16x3' -- declared or decided by calibration -- runs the f32 matrix-core product on 64-column tiles (KN_FLAG_NARROW64_MFMA): the WIDE kernel's association,
         covered by the layer's wide decision, so narrow_mode() and the narrow record are not consulted and nothing is measured or recorded (KeyedModel.forward_linear
-        re-screens a calibrated layer against its wide record).  Under True, 'auto' or 'split' the layer is what narrow=True, narrow64=True makes it."""
+        re-screens a calibrated layer against its wide record).  Under True, 'auto' or 'split' the layer is what narrow=True, narrow64=True makes it.
+        `narrow_linear` (with `narrow`, at every width its keywords allow): a layer that `narrow_rows` would put on the row-lane kernel carries KN_FLAG_NARROW_LINEAR
+        (kernel()): where its operator holds big pattern groups -- a keyed Linear -- they run the LDS value-stream kernel, the same bits.  Nothing is decided or recorded."""
         if verbose():
             print('[keynet_amd.layer]: forward %s' % str(self))
         exact = getattr(self, '_exact', True)
@@ -245,6 +247,8 @@ class KeyedLayer(nn.Module):
                 exact = True                 # an undecided layer without a narrow form: the reference's order for this call, nothing decided or recorded
             if narrow_rows and self.W.rows_capable():
                 form = dict(narrow_rows=True)
+            if narrow_linear and self.W.rows_capable():
+                form['narrow_linear'] = True
         elif exact == 'auto':
             if x_affine.is_cuda and torch.cuda.is_current_stream_capturing():
                 raise _capi.KeynetHipError('keynet_amd: %s has not decided its arithmetic contract yet (exact=\'auto\' calibrates on the first batch, with host reads): '
@@ -256,7 +260,7 @@ class KeyedLayer(nn.Module):
         return self.W.torchdot(x_affine.t(), relu=relu, exact=exact, absmax=absmax, **form).t()
 
     @staticmethod
-    def kernel(W, contract, relu, device=None, narrow=False, narrow_rows=False, narrow32=False, narrow64=False):
+    def kernel(W, contract, relu, device=None, narrow=False, narrow_rows=False, narrow32=False, narrow64=False, narrow_linear=False):
         """The one place that turns a decided contract into an operator handle and flags: (get_op, flags) of the kn_spmm launch that applies operator `W`
         under `contract`, get_op(device) -> the handle resident there.  None when that is not one launch: 'auto' (still to calibrate), 'split' on an operator that has a split form (Conv2dTiledMatrix._torchdot_split).
         The rules: 'split' forced on an operator without a split form, and 'bf16x3' on a non-conv operator, are the f32 matrix cores (False); a conv operator
@@ -278,7 +282,9 @@ class KeyedLayer(nn.Module):
         flag (at 33 .. 64 columns the library then runs the order-preserving pipeline with one column per lane, under every contract); every other operator keeps its flags.
         `narrow64='mfma'` (with narrow='mfma'): a conv operator under False or 'bf16x3' gets KN_FLAG_NARROW_MFMA | KN_FLAG_NARROW32 | KN_FLAG_NARROW64 | KN_FLAG_NARROW64_MFMA and no
         other contract flag: at 33 .. 64 columns the f32 tile kernel on 64-column tiles (there is no bf16 form at that width), at 32 and fewer the library ignores the new bit.
-        Under 'split' it keeps the flags of narrow='mfma', narrow64=True (the pipeline at 33 .. 64 columns), under True / 'auto' those of narrow=True, narrow64=True."""
+        Under 'split' it keeps the flags of narrow='mfma', narrow64=True (the pipeline at 33 .. 64 columns), under True / 'auto' those of narrow=True, narrow64=True.
+        `narrow_linear` (a batch of at most KeyedModel.NARROW64_MAX columns): KN_FLAG_NARROW_LINEAR under exactly the condition of `narrow_rows` -- an operator run in the
+        stored order on its own float32 CSR handle; the library honours it where that handle holds big pattern groups (a keyed Linear) and ignores it elsewhere."""
         conv = isinstance(W, ksp.Conv2dTiledMatrix)
         lane = bool(narrow) and W.narrow_capable()          # one launch of a narrow conv kernel, whatever the contract
         mfma = lane and narrow == 'mfma' and conv and contract in (False, 'bf16x3', 'split')      # (the library falls back to the channel-lane kernel on an ineligible operator)
@@ -290,17 +296,18 @@ class KeyedLayer(nn.Module):
         (get_op, exact, bf16x3) = (W._device_op, contract is True or not conv, contract == 'bf16x3')
         if not conv and not contract and type(W) is SparseMatrix and not W.is_float64() and W._dense_device_op(device) is not None:
             (get_op, exact) = (W._dense_device_op, False)
-        rows = narrow_rows and not lane and not conv and get_op == W._device_op and W.rows_capable()
+        stored = not lane and not conv and get_op == W._device_op and W.rows_capable()      # the stored order on the operator's own float32 CSR handle
+        (rows, linear) = (narrow_rows and stored, narrow_linear and stored)
         if mfma:
             (exact, bf16x3) = (False, False)
         return (get_op, (_capi.KN_FLAG_RELU if relu else 0) | (_capi.KN_FLAG_EXACT if exact else 0) | (_capi.KN_FLAG_BF16X3 if bf16x3 else 0) |
                 (_capi.KN_FLAG_NARROW_MFMA if mfma else _capi.KN_FLAG_NARROW if lane else 0) | (_capi.KN_FLAG_NARROW32 if lane and (narrow32 or narrow64) else 0) | (_capi.KN_FLAG_NARROW64 if lane and narrow64 else 0) |
-                (_capi.KN_FLAG_NARROW64_MFMA if mfma and narrow64 == 'mfma' and contract in (False, 'bf16x3') else 0) | (_capi.KN_FLAG_NARROW_ROWS if rows else 0))
+                (_capi.KN_FLAG_NARROW64_MFMA if mfma and narrow64 == 'mfma' and contract in (False, 'bf16x3') else 0) | (_capi.KN_FLAG_NARROW_ROWS if rows else 0) | (_capi.KN_FLAG_NARROW_LINEAR if linear else 0))
 
-    def launch(self, device, relu=False, narrow=False, narrow_rows=False, narrow32=False, narrow64=False):
+    def launch(self, device, relu=False, narrow=False, narrow_rows=False, narrow32=False, narrow64=False, narrow_linear=False):
         """This layer under its contract in force as one launch on `device` (`relu`: the unkeyed nn.ReLU behind it is fused in), or None when it is not one
         kn_spmm launch: see kernel(); a float64 operator (its own kernel and a float64 result: kn_spmm_f64).  What the key-net's planners read
-        (KeyedModel._chain_op / _overlap_plan); forward() -> W.torchdot() runs the same rule.  `narrow`, `narrow_rows`, `narrow32`, `narrow64`: see kernel(); 'mfma' goes through narrow_mode() first, without a batch.
+        (KeyedModel._chain_op / _overlap_plan); forward() -> W.torchdot() runs the same rule.  `narrow`, `narrow_rows`, `narrow32`, `narrow64`, `narrow_linear`: see kernel(); 'mfma' goes through narrow_mode() first, without a batch.
         narrow64='mfma' (with narrow='mfma') asks for the launch of a batch of 33 .. 64 columns: the layer's wide decision holds there (forward()), narrow_mode() is not consulted."""
         W = self.W
         if narrow == 'mfma' and narrow64 == 'mfma':
@@ -309,7 +316,7 @@ class KeyedLayer(nn.Module):
         elif narrow == 'mfma':
             narrow = self.narrow_mode(narrow)                 # (a calibrated layer without a narrow record yet: the channel-lane kernel -- forward() measures, a planner does not)
         kernel = None if W.is_float64() else self.kernel(W, getattr(self, '_exact', True), relu or self.iskeyedrelu(), device, narrow=narrow, narrow_rows=bool(narrow and narrow_rows),
-                                                               narrow32=bool(narrow and narrow32), narrow64=narrow64 if (narrow and narrow64 == 'mfma') else bool(narrow and narrow64))
+                                                               narrow32=bool(narrow and narrow32), narrow64=narrow64 if (narrow and narrow64 == 'mfma') else bool(narrow and narrow64), narrow_linear=bool(narrow and narrow_linear))
         if kernel is None:
             return None
         return Launch(kernel[0](device), kernel[1], int(W.shape[0]), int(W.shape[1]), isinstance(W, ksp.Conv2dTiledMatrix), 'Linear' in self._layertype,

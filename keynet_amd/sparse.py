@@ -80,7 +80,7 @@ def _device_block(x):
     return xd if xd.is_contiguous() else xd.contiguous()
 
 
-def _run_torchdot(W, x, relu=False, exact=True, absmax=None, narrow=False, narrow_rows=False, narrow32=False, narrow64=False):
+def _run_torchdot(W, x, relu=False, exact=True, absmax=None, narrow=False, narrow_rows=False, narrow32=False, narrow64=False, narrow_linear=False):
     """Y = W.X on the GPU under the contract `exact`, on the handle and flags of KeyedLayer.kernel.  x: [cols, N], torch tensor (any device / strides) or ndarray.
     Returns [rows, N] on x's device: float32, or for a float64 operator the float64 block scipy returns for it (kn_spmm_f64; the activations are
     float32 either way).  `narrow`: at most NARROW_MAX columns on the channel-lane kernel where W owns a conv-taps handle (KeyedLayer.kernel); 'mfma': on the
@@ -89,14 +89,16 @@ def _run_torchdot(W, x, relu=False, exact=True, absmax=None, narrow=False, narro
     same bits; every other operator is what it is without the keyword.  `narrow32` (with `narrow`): at most NARROW32_MAX columns (KN_FLAG_NARROW32).
     `narrow64` (with `narrow`; implies `narrow32`): at most NARROW64_MAX columns (KN_FLAG_NARROW64: beyond NARROW32_MAX the order-preserving pipeline, one column per lane).
     `narrow64='mfma'` (with narrow='mfma'): beyond NARROW32_MAX columns a conv operator under False / 'bf16x3' runs the f32 matrix-core product on 64-column tiles
-    (KN_FLAG_NARROW64_MFMA, KeyedLayer.kernel); every other contract and operator is what narrow64=True makes it."""
+    (KN_FLAG_NARROW64_MFMA, KeyedLayer.kernel); every other contract and operator is what narrow64=True makes it.  `narrow_linear`: at most NARROW64_MAX columns (with
+    `narrow`: its limit) with KN_FLAG_NARROW_LINEAR where `narrow_rows` would set its flag: a keyed Linear's big pattern groups on the LDS value-stream kernel, the
+    same bits; every other operator is what it is without the keyword."""
     from .layer import KeyedLayer            # (layer.py imports this module)
     x = torch.as_tensor(x)
     assert W.shape[1] == x.shape[0], 'Non-conformal shape for W=%s, x=%s' % (str(W.shape), str(tuple(x.shape)))
     xd = _device_block(x)
     n = xd.shape[1]
-    _narrow_args(n, narrow, narrow_rows, 'batch columns', alone=True, narrow32=narrow32, narrow64=narrow64)
-    kernel = KeyedLayer.kernel(W, exact, relu, xd.device, narrow=narrow, narrow_rows=narrow_rows, narrow32=narrow32, narrow64=narrow64)
+    _narrow_args(n, narrow, narrow_rows, 'batch columns', alone=True, narrow32=narrow32, narrow64=narrow64, narrow_linear=narrow_linear)
+    kernel = KeyedLayer.kernel(W, exact, relu, xd.device, narrow=narrow, narrow_rows=narrow_rows, narrow32=narrow32, narrow64=narrow64, narrow_linear=narrow_linear)
     if kernel is None:
         y = W._torchdot_split(xd, relu=relu, absmax=absmax)
     else:
@@ -118,18 +120,23 @@ NARROW32_MAX = 32     # ... with narrow32=True (KN_FLAG_NARROW32: convtaps_narro
 NARROW64_MAX = 64     # ... with narrow64=True (KN_FLAG_NARROW64: beyond NARROW32_MAX columns convtaps_exact_pipe64_kernel; narrow64='mfma': the f32 tile kernel on 64-column tiles; KeyedModel.NARROW64_MAX)
 
 
-def _narrow_args(n, narrow, narrow_rows, what='images', alone=False, narrow32=False, narrow64=False):
+def _narrow_args(n, narrow, narrow_rows, what='images', alone=False, narrow32=False, narrow64=False, narrow_linear=False):
     """The argument rule of the narrow forms, for a batch of `n`: `narrow_rows` only together with `narrow` (`alone`: a container's torchdot, which takes one
     keyword or the other), at most NARROW_MAX columns; `narrow32` only together with `narrow`, whose limit it lifts to NARROW32_MAX -- not that of `narrow_rows`
     (the row-lane kernel is an 8-column kernel); `narrow64` only together with `narrow` as well: it implies `narrow32` (at most NARROW32_MAX columns the call is exactly
     narrow32=True) and lifts the limit to NARROW64_MAX, where narrow='mfma' with narrow64=True is refused beyond NARROW32_MAX (True asks for the order-preserving form
     of that width); `narrow64='mfma'` only together with narrow='mfma': the matrix-core form of NARROW32_MAX + 1 .. NARROW64_MAX columns (KN_FLAG_NARROW64_MFMA), and at
-    NARROW32_MAX columns and fewer exactly narrow='mfma', narrow32=True.
+    NARROW32_MAX columns and fewer exactly narrow='mfma', narrow32=True; `narrow_linear` only together with `narrow` (or `alone`), up to the limit the `narrow`
+    keywords passed give -- NARROW_MAX, NARROW32_MAX with `narrow32`, NARROW64_MAX with `narrow64` -- and alone up to NARROW64_MAX, the kernel's own range.
     ValueError, or the normalised (mode, rows): mode False | True | 'mfma', rows a bool."""
     if narrow64 == 'mfma' and narrow != 'mfma':
         raise ValueError('narrow64=\'mfma\' is the matrix-core form of %d .. %d %s: pass narrow=\'mfma\' with it (got narrow=%r)' % (NARROW32_MAX + 1, NARROW64_MAX, what, narrow))
     if narrow_rows and not narrow and not alone:
         raise ValueError('narrow_rows=True is a form of the narrow forward: pass narrow=True or narrow=\'mfma\' with it')
+    if narrow_linear and not narrow and not alone:
+        raise ValueError('narrow_linear=True is a form of the narrow forward: pass narrow=True or narrow=\'mfma\' with it')
+    if narrow_linear and not narrow and n > NARROW64_MAX:
+        raise ValueError('narrow_linear=True takes at most %d %s, got %d' % (NARROW64_MAX, what, n))
     if narrow32 and not narrow:
         raise ValueError('narrow32=True widens the narrow forward: pass narrow=True or narrow=\'mfma\' with it')
     if narrow64 and not narrow:
@@ -219,14 +226,16 @@ class SparseMatrix(object):
             return False
         return _on_device(self, '_op_dense', make, device) or None
 
-    def torchdot(self, x_torch, relu=False, exact=True, absmax=None, narrow_rows=False):
+    def torchdot(self, x_torch, relu=False, exact=True, absmax=None, narrow_rows=False, narrow_linear=False):
         """W . x for x of shape [W.shape[1], N]: the hot path (keynet/sparse.py:488-492).  exact=True (default): bit-exact
         with scipy (order-preserving CSR kernels).  exact=False: a large dense operator (keyed nn.Linear) may run as a
         split-K f32-MFMA GEMM instead (within 1e-5; used by the tiled key-nets whose conv layers are on MFMA anyway).
         `absmax`: one-element device f32 tensor raised to max |W . x| (kn_spmm_screen).
         `narrow_rows` (N <= NARROW_MAX, ValueError beyond): the stored-order product on the row-lane kernel (KN_FLAG_NARROW_ROWS), the same bits; an operator
-        on its dense handle (exact=False) or in float64 is what it is without the keyword."""
-        return _run_torchdot(self, x_torch, relu=relu, exact=exact, absmax=absmax, narrow_rows=narrow_rows)
+        on its dense handle (exact=False) or in float64 is what it is without the keyword.
+        `narrow_linear` (N <= NARROW64_MAX, ValueError beyond): the big pattern groups of a keyed Linear on the LDS value-stream kernel (KN_FLAG_NARROW_LINEAR), the
+        same bits, under the same conditions; an operator without such a group is what it is without the keyword."""
+        return _run_torchdot(self, x_torch, relu=relu, exact=exact, absmax=absmax, narrow_rows=narrow_rows, narrow_linear=narrow_linear)
 
     def dot(self, x_numpy):
         assert isinstance(x_numpy, np.ndarray)
@@ -407,10 +416,11 @@ class TiledMatrix(SparseMatrix):
             return _capi.Operator.tiled(self.shape, np.array(list(self), dtype=np.int64).reshape(-1, 3), ptr, tr, tc, tv)
         return _on_device(self, '_op', make, device)
 
-    def torchdot(self, x, relu=False, exact=True, absmax=None, narrow_rows=False):
+    def torchdot(self, x, relu=False, exact=True, absmax=None, narrow_rows=False, narrow_linear=False):
         """[cols, N] -> [rows, N] (keynet/sparse.py:603-612); always the order-preserving path (bit-exact).  `narrow_rows` (N <= NARROW_MAX, ValueError beyond):
-        on the row-lane kernel (KN_FLAG_NARROW_ROWS), the same bits."""
-        return _run_torchdot(self, x, relu=relu, exact=True, absmax=absmax, narrow_rows=narrow_rows)
+        on the row-lane kernel (KN_FLAG_NARROW_ROWS), the same bits.  `narrow_linear` (N <= NARROW64_MAX, ValueError beyond): big pattern groups of the expanded
+        operator on the LDS value-stream kernel (KN_FLAG_NARROW_LINEAR), the same bits; without such a group the call is what it is without the keyword."""
+        return _run_torchdot(self, x, relu=relu, exact=True, absmax=absmax, narrow_rows=narrow_rows, narrow_linear=narrow_linear)
 
     def dot(self, x):
         assert isinstance(x, np.ndarray)

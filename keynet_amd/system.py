@@ -179,7 +179,7 @@ class KeyedModel(object):
     NARROW32_MAX = ksp.NARROW32_MAX    # ... with narrow32=True (convtaps_narrow32_kernel: the columns in blocks of 8 | 16 | 32 running sums per lane)
     NARROW64_MAX = ksp.NARROW64_MAX    # ... with narrow64=True (beyond NARROW32_MAX images convtaps_exact_pipe64_kernel: one column per lane, packed over output-channel pairs)
 
-    def forward_linear(self, img_cipher, overlap=None, narrow=False, narrow_rows=False, narrow32=False, narrow64=False):
+    def forward_linear(self, img_cipher, overlap=None, narrow=False, narrow_rows=False, narrow32=False, narrow64=False, narrow_linear=False):
         """[N, D0+1] -> [N, classes+1]: the nn.Sequential of keynet/system.py:132 with the unkeyed ReLUs fused into the
         producing layer's kernel epilogue.  Stream-ordered on torch's current HIP stream.  Host synchronisation: none for key-nets whose
         layers all run under a DECLARED contract (exact=True: the permutation key-nets; exact=False: forced); a key-net with layers on the
@@ -238,12 +238,18 @@ class KeyedModel(object):
         narrow64=True.  The screen: the 64-column tile is the WIDE kernel's association, so a declared layer is unscreened and a layer calibration put there (screened()) is
         re-screened against its WIDE record (not the narrow one, which belongs to the other kernel), through the same slots and RESCREEN_FACTOR.  A tripped layer goes back
         to 'auto' as on the wide path (launch lists dropped), this pass runs again with that layer in the stored order, and the next padded forward calibrates it: nothing
-        calibrates inside this path."""
+        calibrates inside this path.
+        `narrow_linear=True` (only together with `narrow`, ValueError otherwise; at every width the `narrow` keywords passed allow: NARROW_MAX, NARROW32_MAX with
+        `narrow32`, NARROW64_MAX with `narrow64`): the keyed Linear layers under the bit-exact contract -- float32 CSR operators in the stored order that hold big
+        pattern groups -- run csr_stream_group_kernel (KN_FLAG_NARROW_LINEAR: a workgroup owns 64 output rows times all images, the values reach it through a ring in
+        LDS and leave HBM once per call) instead of the wide-batch kernel, which costs 64 images at every width.  The same bits layer by layer; next to `narrow_rows` the
+        other CSR layers and the remaining rows of a Linear keep the row-lane kernel.  Nothing is calibrated, screened, decided, recorded or saved, and the cached launch
+        lists and the whole-net kernel are left alone."""
         n = img_cipher.shape[0]
-        (mode, rows) = ksp._narrow_args(n, narrow, narrow_rows, narrow32=narrow32, narrow64=narrow64)
+        (mode, rows) = ksp._narrow_args(n, narrow, narrow_rows, narrow32=narrow32, narrow64=narrow64, narrow_linear=narrow_linear)
         narrow64 = self._narrow64_form(n, narrow64)
         (x, windows) = self._prepare64(img_cipher) if narrow64 == 'mfma' else self._prepare(img_cipher, mode)
-        y = self._forward_passes(x, windows, False if mode else overlap, mode, rows, bool(narrow32), narrow64)[0][:n]
+        y = self._forward_passes(x, windows, False if mode else overlap, mode, rows, bool(narrow32), narrow64, bool(narrow_linear))[0][:n]
         return y if img_cipher.is_cuda else y.to(img_cipher.device)
 
     @staticmethod
@@ -293,11 +299,11 @@ class KeyedModel(object):
             x = x.detach().t().contiguous().t()
         return (x, windows)
 
-    def _forward_passes(self, x, windows, overlap, narrow=False, rows=False, narrow32=False, narrow64=False):
+    def _forward_passes(self, x, windows, overlap, narrow=False, rows=False, narrow32=False, narrow64=False, linear=False):
         """The screened forward of a prepared batch: (y, screens).  A pass whose screen re-calibrates a layer runs again (calibrating on its own images),
         then every other pass again: the batch comes out of ONE set of contracts.  At most RESCREEN_MAX_PASSES runs of a pass; then only the last pass is
         re-screened (the next forward decides).  Under a HIP-graph capture nothing is read: `screens` = (slots, screened) per pass, for capture's replay.
-        `narrow` / `rows` / `narrow32` / `narrow64` (the normalised keywords narrow, narrow_rows, narrow32, narrow64 of forward_linear): the screened layers are those a MEASUREMENT put on the matrix-core narrow kernel (none under
+        `narrow` / `rows` / `narrow32` / `narrow64` / `linear` (the normalised keywords narrow, narrow_rows, narrow32, narrow64, narrow_linear of forward_linear): the screened layers are those a MEASUREMENT put on the matrix-core narrow kernel (none under
         narrow=True; an 'auto' layer does not switch the screen off: it runs in the reference's order for this call), screened against their narrow records; layers
         measured during a pass were measured on this very batch, so only the records that existed before it are screened.
         narrow64 == 'mfma' (33 .. 64 images, _prepare64's block): the screened layers are the conv-taps layers a CALIBRATION put on the f32 / bf16x3 matrix-core kernels -- they
@@ -319,7 +325,7 @@ class KeyedModel(object):
             slots = torch.zeros(len(keyed) + 1, dtype=torch.float32, device=x.device) if screened else None
             (lo, hi) = windows[k]
             # (a window of a wider block: its own feature-major block, so that the pass can take the overlapped form)
-            ys[k] = self._forward_once(x if len(windows) == 1 else x[lo:hi].t().contiguous().t(), keyed, overlap, slots, screened, narrow, rows, narrow32, narrow64)
+            ys[k] = self._forward_once(x if len(windows) == 1 else x[lo:hi].t().contiguous().t(), keyed, overlap, slots, screened, narrow, rows, narrow32, narrow64, linear)
             if slots is None:
                 continue
             screens.append((slots, screened))
@@ -349,10 +355,10 @@ class KeyedModel(object):
     BATCH_TILE = 128           # _prepare pads a device batch of a tiled-conv key-net to whole multiples of this many images
     MAX_BLOCK_ELEMENTS = 1 << 31   # ... and splits a batch whose largest layer would hold this many activations or more into passes
 
-    def _forward_once(self, img_cipher, keyed, overlap, slots, screened, narrow=False, rows=False, narrow32=False, narrow64=False):
+    def _forward_once(self, img_cipher, keyed, overlap, slots, screened, narrow=False, rows=False, narrow32=False, narrow64=False, linear=False):
         """One pass over the keyed layers `keyed` (_keyed()).  `slots` (device f32 [L + 1], zeroed) / `screened` (indices of the keyed layers whose contract
         is re-screened): slot k receives max |x| of keyed layer k -- slot 0 by one pass over the input, slot k + 1 by the kernel that
-        produces layer k's output.  `narrow` / `rows` / `narrow32` / `narrow64`: every layer in its narrow form (KeyedLayer.forward); the whole-net kernel only where no layer has one."""
+        produces layer k's output.  `narrow` / `rows` / `narrow32` / `narrow64` / `linear`: every layer in its narrow form (KeyedLayer.forward); the whole-net kernel only where no layer has one."""
         forced = overlap is True
         if overlap is None and not self.OVERLAP_AUTO:
             overlap = False
@@ -376,7 +382,7 @@ class KeyedModel(object):
             if k is None:
                 y = _relu_block(y)
             else:
-                y = c.forward(y, fuse_relu=relu, absmax=slots[k + 1:k + 2] if (slots is not None and (k + 1) in screened) else None, narrow=narrow, narrow_rows=rows, narrow32=narrow32, narrow64=narrow64)
+                y = c.forward(y, fuse_relu=relu, absmax=slots[k + 1:k + 2] if (slots is not None and (k + 1) in screened) else None, narrow=narrow, narrow_rows=rows, narrow32=narrow32, narrow64=narrow64, narrow_linear=linear)
         return y
 
     # -- whole-net kernel: every operator of a small untiled key-net in ONE launch, activations in LDS (csrc/kn_chain.hip) --------
@@ -626,7 +632,7 @@ class KeyedModel(object):
             self._drop_plans()
         return changed
 
-    def capture(self, img_cipher, narrow=False, narrow_rows=False, narrow32=False, narrow64=False):
+    def capture(self, img_cipher, narrow=False, narrow_rows=False, narrow32=False, narrow64=False, narrow_linear=False):
         """Capture forward_linear for this input shape into a HIP graph (torch.cuda.CUDAGraph on ROCm) and return a callable
         `replay(x) -> [N, classes+1]`.  Small key-nets are launch-bound (LeNet at N=1024: 7 kernels in 0.25 ms); one graph
         launch replaces them.  The graph runs the passes of the eager forward on the block _prepare made; replay(x) copies x into its first N images.
@@ -644,10 +650,12 @@ class KeyedModel(object):
         `narrow64=True` (only with `narrow`): the graph of forward_linear(narrow=True, narrow64=True), up to NARROW64_MAX images -- the same straight line of launches on one stream.
         `narrow64='mfma'` (only with narrow='mfma'): the graph of forward_linear(narrow='mfma', narrow64='mfma') -- at 33 .. 64 images the 64-column block of that forward, still a
         straight line of launches on one stream.  With layers on the matrix-core kernels by calibration the graph gathers their max |x|; replay() reads the slots against the
-        WIDE records and on a trip runs the batch eagerly (the tripped layer back to 'auto', in the stored order) and captures a new graph, as the wide capture does."""
+        WIDE records and on a trip runs the batch eagerly (the tripped layer back to 'auto', in the stored order) and captures a new graph, as the wide capture does.
+        `narrow_linear=True` (only with `narrow`): the graph of forward_linear(narrow=..., narrow_linear=True): the same straight line of launches."""
         assert img_cipher.is_cuda, 'capture() needs a device tensor'
         n = img_cipher.shape[0]
-        (mode, rows) = ksp._narrow_args(n, narrow, narrow_rows, narrow32=narrow32, narrow64=narrow64)
+        (mode, rows) = ksp._narrow_args(n, narrow, narrow_rows, narrow32=narrow32, narrow64=narrow64, narrow_linear=narrow_linear)
+        linear = bool(narrow_linear)
         (narrow32, narrow64) = (bool(narrow32), self._narrow64_form(n, narrow64))
         wide64 = narrow64 == 'mfma'
         src = img_cipher.detach().float() if mode else img_cipher.detach()
@@ -656,18 +664,18 @@ class KeyedModel(object):
         state = {}
 
         def build():
-            self._forward_passes(static_in, windows, False, mode, rows, narrow32, narrow64)       # uploads operators, sizes workspaces, calibrates (not capturable)
+            self._forward_passes(static_in, windows, False, mode, rows, narrow32, narrow64, linear)       # uploads operators, sizes workspaces, calibrates (not capturable)
             torch.cuda.synchronize()
             side = torch.cuda.Stream()
             side.wait_stream(torch.cuda.current_stream())
             with torch.cuda.stream(side):
-                self._forward_passes(static_in, windows, False, mode, rows, narrow32, narrow64)   # warm-up on the capture stream
+                self._forward_passes(static_in, windows, False, mode, rows, narrow32, narrow64, linear)   # warm-up on the capture stream
             torch.cuda.current_stream().wait_stream(side)
             graph = torch.cuda.CUDAGraph()
             # capture ON THE WARMED STREAM: per-stream state of the operators (the split-K workspace of a dense layer, kn_api.hip) was sized
             # by the warm-up forward above; torch's default capture stream would be a fresh one, and a hipMalloc inside a capture is refused
             with torch.cuda.graph(graph, stream=side):
-                (out, screens) = self._forward_passes(static_in, windows, False, mode, rows, narrow32, narrow64)
+                (out, screens) = self._forward_passes(static_in, windows, False, mode, rows, narrow32, narrow64, linear)
             state.update(graph=graph, out=out[:n], screens=screens)
 
         build()
@@ -683,13 +691,13 @@ class KeyedModel(object):
         replay.graph = state['graph']
         return replay
 
-    def forward(self, img_cipher, outkey=None, narrow=False, narrow_rows=False, narrow32=False, narrow64=False):
+    def forward(self, img_cipher, outkey=None, narrow=False, narrow_rows=False, narrow32=False, narrow64=False, narrow_linear=False):
         """Encrypted image(s) [N, D0+1] -> logits.  N == 1 returns the reference's shape `outshape` = (C,1,1)
         (keynet/system.py:130-133); N > 1 (an extension: the reference cannot) returns (N, C, 1, 1).  `narrow`: forward_linear(narrow=True | 'mfma'), the
         low-latency forms of this very call for 1 .. NARROW_MAX images; `narrow_rows`: with them, the CSR layers on the row-lane kernel (forward_linear); `narrow32`: with them, up to NARROW32_MAX images; `narrow64`: up to NARROW64_MAX
-        (narrow64=True: the order-preserving form of 33 .. 64 images; narrow64='mfma', with narrow='mfma': the matrix-core form on 64-column tiles, forward_linear)."""
+        (narrow64=True: the order-preserving form of 33 .. 64 images; narrow64='mfma', with narrow='mfma': the matrix-core form on 64-column tiles, forward_linear); `narrow_linear`: with them, the keyed Linear layers on the LDS value-stream kernel (forward_linear)."""
         outkey = outkey if outkey is not None else self.embeddingkey()
-        y = self.forward_linear(img_cipher, narrow=narrow, narrow_rows=narrow_rows, narrow32=narrow32, narrow64=narrow64)
+        y = self.forward_linear(img_cipher, narrow=narrow, narrow_rows=narrow_rows, narrow32=narrow32, narrow64=narrow64, narrow_linear=narrow_linear)
         if outkey is not None:
             y = self.decrypt(y, outkey)
         n = y.shape[0]

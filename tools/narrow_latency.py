@@ -52,7 +52,16 @@ before any time is printed), (c) the same images as two narrow='mfma', narrow32=
 (a) and one (b) forward at 64 images, layer by layer.
 --narrow64: under the default contract, in one process with the forms alternating: the forward without the keyword (a tiled key-net: padded to 128 images) against
 narrow=True, narrow64=True at 33, 48 and 64 images (`--workload allconv`: at 48) -- logits torch.equal before any time is printed --, and the narrow32 forward at 32
-images for the ladder.  The bars of the file are computed from the table."""
+images for the ladder.  The bars of the file are computed from the table.
+
+    python tools/narrow_latency.py --linear [--out profiles/r13_narrow_linear.txt]
+    python tools/narrow_latency.py --linear --one-forward        # for n in (1, 8, 16, 64) ONE narrow forward, then ONE with narrow_linear=True (for a kernel trace)
+    python tools/narrow_latency.py --linear --from-trace DIR/.../*_kernel_trace.csv [--convs 13]     # no GPU: the CSR launches of those forwards side by side
+
+--linear: keyed VGG-16 under the default contract, everything in one process with the forms alternating.  fc6, fc7 and fc8 alone: kn_spmm without and with
+KN_FLAG_NARROW_LINEAR at 1, 2, 3, 4, 8, 16, 32, 33 and 64 columns, up to 8 columns also next to KN_FLAG_NARROW_ROWS -- back to back on one block (values as warm as
+the layer's size lets them be) and behind a pass over a 512 MB buffer that leaves nothing of the operator on chip (what a forward sees) -- with the plan strings; then
+whole forwards at 1, 8, 16 and 64 images, narrow=True with the width's keywords, without and with narrow_linear=True, the logits torch.equal before any time is printed."""
 import argparse
 import os
 import statistics
@@ -495,6 +504,140 @@ def rows_table(args, knet, xc, desc):
         f.write(text)
 
 
+LINEAR_WIDTHS = (1, 2, 3, 4, 8, 16, 32, 33, 64)
+LINEAR_IMAGES = (1, 8, 16, 64)
+
+
+def _width_keywords(n):
+    return dict(narrow=True, narrow32=n > 8, narrow64=n > 32)
+
+
+def linear_table(args, knet, xc, desc):
+    """--linear: see the module docstring."""
+    from keynet_amd import _capi
+    dev = xc.device
+    (ROWS, LINEAR) = (_capi.KN_FLAG_NARROW_ROWS, _capi.KN_FLAG_NARROW_LINEAR)
+    if args.one_forward:
+        for n in LINEAR_IMAGES:                   # operators resident
+            knet.forward_linear(xc[:n].t().contiguous().t(), narrow_linear=True, **_width_keywords(n))
+        torch.cuda.synchronize()
+        print('TRACE-FROM-HERE: for n in (1, 8, 16, 64) one narrow=True forward with the width\'s keywords, then one with narrow_linear=True', flush=True)
+        for n in LINEAR_IMAGES:
+            x = xc[:n].t().contiguous().t()
+            knet.forward_linear(x, **_width_keywords(n))
+            knet.forward_linear(x, narrow_linear=True, **_width_keywords(n))
+            torch.cuda.synchronize()
+        return
+    med = lambda v: '%8.3f (%.3f .. %.3f)' % (statistics.median(v), min(v), max(v))
+    lines = ['', '== tools/narrow_latency.py --linear: %s' % desc,
+             '   %s, torch %s; HIP events, %d warm-up + median of %d calls (min .. max), the forms alternating; logits torch.equal: yes'
+             % (torch.cuda.get_device_name(0), torch.__version__, args.warmup, args.forwards)]
+    st = torch.cuda.current_stream().cuda_stream
+    flush = torch.empty(128 << 20, dtype=torch.float32, device=dev)     # 512 MB: twice the Infinity Cache
+
+    def cold(fn, calls):
+        out = []
+        for _ in range(calls):
+            flush.zero_()
+            (a, b) = (torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True))
+            a.record()
+            fn()
+            b.record()
+            b.synchronize()
+            out.append(a.elapsed_time(b))
+        return out
+
+    linears = []
+    for (name, c) in knet._keyed(named=True):
+        (la0, la1) = (c.launch(dev, narrow=True), c.launch(dev, narrow=True, narrow_linear=True))
+        if la1 is not None and la1.flags != la0.flags and 'csr_stream_group_kernel' in la1.op.plan(1, la1.flags):
+            linears.append((name, la0))
+    lines.append('   the layers with big pattern groups, alone: kn_spmm [us] without the flag | with KN_FLAG_NARROW_LINEAR (ratio) and, up to 8 columns, with KN_FLAG_NARROW_ROWS |')
+    lines.append('   with both (ratio to KN_FLAG_NARROW_ROWS alone); first line back to back on one block, second line behind a pass over 512 MB (cold values)')
+    for (name, la) in linears:
+        lines.append('   %s  %d x %d' % (name, la.rows, la.cols))
+        for n in LINEAR_WIDTHS:
+            x = torch.randn((la.cols, n), device=dev)
+            ys = [torch.empty((la.rows, n), device=dev) for _ in range(2)]
+            forms = [la.flags, la.flags | LINEAR] + ([la.flags | ROWS, la.flags | ROWS | LINEAR] if n <= 8 else [])
+            calls = [(lambda f=f, y=ys[i & 1]: la.op.spmm(x.data_ptr(), n, n, y.data_ptr(), n, f, st)) for (i, f) in enumerate(forms)]
+            for k in range(0, len(forms), 2):
+                calls[k]()
+                calls[k + 1]()
+                torch.cuda.synchronize()
+                assert torch.equal(ys[0], ys[1]), 'KN_FLAG_NARROW_LINEAR changed the bits of %s at %d column(s)' % (name, n)
+            (warm, cool) = ([[] for _ in forms], [[] for _ in forms])
+            for _ in range(2):
+                for (k, fn) in enumerate(calls):
+                    warm[k] += timed(fn, args.forwards // 2, args.warmup)
+                    cool[k] += cold(fn, args.forwards // 2)
+            for (tag, t) in (('warm', warm), ('cold', cool)):
+                m = [statistics.median(v) * 1e3 for v in t]
+                cell = '%8.1f | %8.1f (%4.2fx)' % (m[0], m[1], m[0] / m[1])
+                if n <= 8:
+                    cell += ' | %8.1f | %8.1f (%4.2fx)' % (m[2], m[3], m[2] / m[3])
+                lines.append('     %2d column(s) %s: %s' % (n, tag, cell))
+            lines.append('        %s' % la.op.plan(n, la.flags | LINEAR))
+            if n <= 8:
+                lines.append('        %s' % la.op.plan(n, la.flags | ROWS | LINEAR))
+        print('%s done' % name, flush=True)
+    lines.append('')
+    lines.append('   whole forwards, default contract, narrow=True with the width\'s keywords')
+    lines.append('   %6s | %-28s | %-28s | %s' % ('images', 'without [ms]', '+ narrow_linear=True [ms]', 'without / with'))
+    for n in LINEAR_IMAGES:
+        x = xc[:n].t().contiguous().t()
+        kw = _width_keywords(n)
+        (y0, y1) = (knet.forward_linear(x, **kw), knet.forward_linear(x, narrow_linear=True, **kw))
+        torch.cuda.synchronize()
+        assert torch.equal(y0, y1), 'narrow_linear changed the logits at %d image(s)' % n
+        (a, b) = ([], [])
+        for _ in range(4):                        # alternate in quarters
+            a += timed(lambda: knet.forward_linear(x, **kw), args.forwards // 4, args.warmup)
+            b += timed(lambda: knet.forward_linear(x, narrow_linear=True, **kw), args.forwards // 4, args.warmup)
+        lines.append('   %6d | %-28s | %-28s | %.2fx' % (n, med(a), med(b), statistics.median(a) / statistics.median(b)))
+        print('n = %d done' % n, flush=True)
+    text = '\n'.join(lines) + '\n'
+    print(text)
+    with open(args.out or os.path.join(ROOT, 'profiles', 'r13_narrow_linear.txt'), 'a') as f:
+        f.write(text)
+
+
+def linear_trace_table(args):
+    """--linear --from-trace: the CSR launches (fc6 - fc8 and the pools, with their helpers) of the last eight forwards of a `--linear --one-forward` run."""
+    import csv
+    with open(args.from_trace, newline='') as f:
+        rows = sorted(csv.DictReader(f), key=lambda r: int(r['Start_Timestamp']))
+    first = next(i for (i, r) in enumerate(rows) if 'convtaps' in r['Kernel_Name'])
+    (fw, seen) = ([[]], 0)
+    for r in rows[first:]:                        # a forward = its k conv launches and the launches between and behind them, up to the next conv launch
+        conv = 'convtaps' in r['Kernel_Name']
+        if conv and seen == args.convs:
+            fw.append([])
+            seen = 0
+        seen += conv
+        fw[-1].append(r)
+    fw = fw[-8:]
+    assert len(fw) == 8, 'the trace holds %d forwards, fewer than 8' % len(fw)
+    us = lambda r: (int(r['End_Timestamp']) - int(r['Start_Timestamp'])) / 1e3
+    big = lambda r: any(k in r['Kernel_Name'] for k in ('csr_big_group', 'csr_stream_group', 'mfma16'))
+    lines = ['', '== tools/narrow_latency.py --linear --from-trace: the launches of fc6 - fc8 and the pools (with their helpers) in one narrow=True forward and one with narrow_linear=True (rocprofv3 --kernel-trace)']
+    for (i, n) in enumerate(LINEAR_IMAGES):
+        (a, b) = [[r for r in f if 'kn::' in r['Kernel_Name'] and 'conv' not in r['Kernel_Name']] for f in (fw[2 * i], fw[2 * i + 1])]
+        lines.append('')
+        lines.append('   %d image(s) [us]: without narrow_linear | with narrow_linear' % n)
+        for j in range(max(len(a), len(b))):
+            cell = lambda L: ('%9.1f %-60s' % (us(L[j]), L[j]['Kernel_Name'][:60])) if j < len(L) else ' ' * 70
+            lines.append('     %s | %s' % (cell(a), cell(b)))
+        (sa, sb) = (sum(us(r) for r in a if big(r)), sum(us(r) for r in b if big(r)))
+        lines.append('     sum of the big-group launches (fc6 - fc8): %9.1f | %9.1f | %5.2fx' % (sa, sb, sa / max(sb, 1e-9)))
+        (wa, wb) = [(int(f[-1]['End_Timestamp']) - int(f[0]['Start_Timestamp'])) / 1e3 for f in (fw[2 * i], fw[2 * i + 1])]
+        lines.append('     first launch to last launch of the forward:  %9.1f | %9.1f | %5.2fx' % (wa, wb, wa / max(wb, 1e-9)))
+    text = '\n'.join(lines) + '\n'
+    print(text)
+    with open(args.out or os.path.join(ROOT, 'profiles', 'r13_narrow_linear.txt'), 'a') as f:
+        f.write(text)
+
+
 def rows_trace_table(args):
     """--rows --from-trace: the NON-conv launches of the last eight forwards of a `--rows --one-forward` run (device timestamps), forward by forward."""
     import csv
@@ -568,6 +711,7 @@ def main():
     ap.add_argument('--one-forward', action='store_true', help='key, warm up, run one narrow forward and exit (for a kernel trace)')
     ap.add_argument('-n', type=int, default=1, help='images of --one-forward')
     ap.add_argument('--rows', action='store_true', help='whole forwards and single layers with and without narrow_rows=True (profiles/r09_narrow_rows.txt)')
+    ap.add_argument('--linear', action='store_true', help='fc6 - fc8 alone and whole forwards with and without narrow_linear=True (profiles/r13_narrow_linear.txt)')
     ap.add_argument('--mfma', action='store_true', help="exact_mode('auto') after one calibrating wide forward: padded, narrow=True, narrow='mfma'")
     ap.add_argument('--narrow32', action='store_true', help='9 .. 32 images: no keyword against narrow32=True, both contracts (profiles/r10_narrow32.txt)')
     ap.add_argument('--narrow64', action='store_true', help='33 .. 64 images: no keyword against narrow=True, narrow64=True under the default contract (profiles/r11_narrow64.txt)')
@@ -576,7 +720,7 @@ def main():
     ap.add_argument('--blocks', action='store_true', help='with --narrow32: one conv5_x-shaped operator per column-block width (diagnostic build)')
     args = ap.parse_args()
     if args.from_trace:
-        return narrow64_trace_table(args) if (args.narrow64 or args.mfma64) else narrow32_trace_table(args) if args.narrow32 else rows_trace_table(args) if args.rows else trace_table(args)
+        return narrow64_trace_table(args) if (args.narrow64 or args.mfma64) else narrow32_trace_table(args) if args.narrow32 else rows_trace_table(args) if args.rows else linear_trace_table(args) if args.linear else trace_table(args)
     if args.narrow32 and args.blocks:
         return narrow32_blocks(args)
     assert args.forwards >= 20 or args.one_forward, 'the median of at least 20 forwards'
@@ -584,7 +728,7 @@ def main():
     (sensor, knet, inshape, _, desc, _) = workloads.build_workload(args.workload, 0, fanout=True)
     dev = torch.device('cuda:0')
     torch.manual_seed(1)
-    imgs = torch.randn((64 if (args.narrow64 or args.mfma64) else max(args.images) if args.narrow32 else 8,) + tuple(inshape))
+    imgs = torch.randn((64 if (args.narrow64 or args.mfma64 or args.linear) else max(args.images) if args.narrow32 else 8,) + tuple(inshape))
     xc = sensor.fromtensor(imgs.to(dev)).encrypt().astensor()
     xc = xc.t().contiguous().t()                  # feature-major, as the layers hand blocks on
     print('keyed %s in %.0f s' % (desc, time.time() - t0), flush=True)
@@ -598,6 +742,8 @@ def main():
         return mfma_table(args, knet, xc, desc)
     if args.rows:
         return rows_table(args, knet, xc, desc)
+    if args.linear:
+        return linear_table(args, knet, xc, desc)
     if args.one_forward:
         x = xc[:args.n].t().contiguous().t()
         knet.forward_linear(x, narrow=True)       # operators resident
