@@ -216,40 +216,13 @@ class KeyedLayer(nn.Module):
         f32 tensor raised to max |y| of this call (kn_spmm_screen; KeyedModel.forward_linear re-screens the next layer's contract with it).
         A layer whose contract is still 'auto' decides it here, on this batch (blocking host reads, an extra order-preserving launch:
         not capturable into a HIP graph -- KeyedModel.capture runs an eager forward first).
-        `narrow` (at most KeyedModel.NARROW_MAX images): a conv-taps layer runs the channel-lane order-preserving kernel (KN_FLAG_NARROW) whatever its
-        contract is -- the reference's own arithmetic, which satisfies every contract: nothing is calibrated, screened or decided; other layers run as usual.
-        `narrow='mfma'`: the matrix-core narrow kernel (KN_FLAG_NARROW_MFMA) where this layer's contract in force allows re-ordered sums (narrow_mode():
-        declared -> always; decided by calibration -> measured once on the first such batch, recorded under _contract_record['narrow']); else narrow=True.
-        `narrow_rows` (with `narrow`): a layer whose operator is a float32 CSR handle (W.rows_capable()) runs its stored-order product on the row-lane kernel
-        (KN_FLAG_NARROW_ROWS, kernel()) -- the same bits; conv-taps layers and everything else are what `narrow` alone makes them.  Nothing is decided or recorded.
-        `narrow32` (with `narrow`): at most KeyedModel.NARROW32_MAX images; a conv-taps layer gets KN_FLAG_NARROW32 next to its narrow flag (kernel()), every other
-        layer runs as without it.
-        `narrow64` (with `narrow`; implies `narrow32`): at most KeyedModel.NARROW64_MAX images; a conv-taps layer gets KN_FLAG_NARROW64 as well (kernel()) and runs, beyond
-        NARROW32_MAX images, the order-preserving pipeline with one column per lane; every other layer runs as without it, at the unpadded width.
-        `narrow64='mfma'` (with narrow='mfma'): at NARROW32_MAX images and fewer exactly narrow='mfma', narrow32=True.  Beyond, a conv-taps layer whose contract in force is
-        False or 'bf16x3' -- declared or decided by calibration -- runs the f32 matrix-core product on 64-column tiles (KN_FLAG_NARROW64_MFMA): the WIDE kernel's association,
-        covered by the layer's wide decision, so narrow_mode() and the narrow record are not consulted and nothing is measured or recorded (KeyedModel.forward_linear
-        re-screens a calibrated layer against its wide record).  Under True, 'auto' or 'split' the layer is what narrow=True, narrow64=True makes it.
-        `narrow_linear` (with `narrow`, at every width its keywords allow): a layer that `narrow_rows` would put on the row-lane kernel carries KN_FLAG_NARROW_LINEAR
-        (kernel()): where its operator holds big pattern groups -- a keyed Linear -- they run the LDS value-stream kernel, the same bits.  Nothing is decided or recorded."""
+        `narrow`, `narrow_rows`, `narrow32`, `narrow64`, `narrow_linear` (narrow='mfma', narrow64='mfma' included): this layer of KeyedModel.forward_linear's narrow forms, as
+        narrowed() decides it on this batch -- with `narrow` nothing is calibrated, and only narrow='mfma' on a calibrated layer measures and records (narrow_mode())."""
         if verbose():
             print('[keynet_amd.layer]: forward %s' % str(self))
-        exact = getattr(self, '_exact', True)
-        relu = fuse_relu or self.iskeyedrelu()
-        form = {}                            # what `narrow` / `narrow_rows` make of this layer: the keyword its operator's torchdot takes, if any
-        if narrow == 'mfma' and narrow64 == 'mfma' and x_affine.shape[0] > ksp.NARROW32_MAX and self.W.narrow_capable():
-            tile = isinstance(self.W, ksp.Conv2dTiledMatrix) and exact in (False, 'bf16x3')      # the wide decision covers the 64-column tile: same kernel, same K order
-            form = dict(narrow='mfma' if tile else True, narrow32=True, narrow64='mfma' if tile else True)
-        elif narrow and self.W.narrow_capable():
-            form = dict(narrow=self.narrow_mode(narrow, x_affine.t(), relu) if narrow == 'mfma' else True, narrow32=bool(narrow32 or narrow64), narrow64=bool(narrow64))
-        elif narrow:
-            if exact == 'auto':
-                exact = True                 # an undecided layer without a narrow form: the reference's order for this call, nothing decided or recorded
-            if narrow_rows and self.W.rows_capable():
-                form = dict(narrow_rows=True)
-            if narrow_linear and self.W.rows_capable():
-                form['narrow_linear'] = True
-        elif exact == 'auto':
+        (xt, relu) = (x_affine.t(), fuse_relu or self.iskeyedrelu())
+        (exact, keywords) = self.narrowed(ksp.NarrowForm.of(None, narrow, narrow_rows, narrow32, narrow64, narrow_linear), xt, relu)
+        if exact == 'auto' and not narrow:
             if x_affine.is_cuda and torch.cuda.is_current_stream_capturing():
                 raise _capi.KeynetHipError('keynet_amd: %s has not decided its arithmetic contract yet (exact=\'auto\' calibrates on the first batch, with host reads): '
                                            'run one eager forward before capturing a HIP graph (KeyedModel.capture does), or declare exact=True / False' % self._repr)
@@ -257,7 +230,27 @@ class KeyedLayer(nn.Module):
             if absmax is not None:
                 _absmax_into(y.t(), absmax)
             return y
-        return self.W.torchdot(x_affine.t(), relu=relu, exact=exact, absmax=absmax, **form).t()
+        return self.W.torchdot(xt, relu=relu, exact=exact, absmax=absmax, **keywords).t()
+
+    def narrowed(self, form, xt=None, relu=False):
+        """What this layer makes of the ksp.NarrowForm `form`: (contract, keywords) -- the contract its operator runs under and the keywords that operator's torchdot /
+        kernel() take (none on the wide forward).  `xt` ([cols, N]): the batch of a forward; None: a planner asking (launch()), which decides and measures nothing.
+        An operator with a conv-taps handle (W.narrow_capable()): where the 64-column tile is asked for (narrow64='mfma'; with a batch: of more than NARROW32_MAX columns) a
+        conv operator under False / 'bf16x3' takes it -- the wide kernel's association, covered by the wide decision: narrow_mode() is not consulted -- and everything else is what
+        narrow=True, narrow64=True makes it; otherwise narrow='mfma' is narrow_mode()'s answer for this layer, measured on `xt` where a calibrated layer has no narrow record yet
+        (a planner gets the channel-lane kernel).  Any other operator: `narrow_rows` / `narrow_linear` where it is a float32 CSR handle (W.rows_capable()), and a layer still
+        'auto' runs in the reference's order for this call (to a planner it stays 'auto': not one launch)."""
+        (W, exact) = (self.W, getattr(self, '_exact', True))
+        if not form.mode:
+            return (exact, {})
+        if W.narrow_capable():
+            if form.tile64 and (xt is None or xt.shape[1] > ksp.NARROW32_MAX):
+                mode = 'mfma' if isinstance(W, ksp.Conv2dTiledMatrix) and exact in (False, 'bf16x3') else True
+                return (exact, dict(narrow=mode, narrow32=True, narrow64=mode))
+            return (exact, dict(narrow=self.narrow_mode('mfma', xt, relu) if form.mode == 'mfma' else True, narrow32=form.narrow32, narrow64=form.narrow64))
+        if exact == 'auto' and xt is not None:
+            exact = True
+        return (exact, dict(narrow_rows=form.rows, narrow_linear=form.linear) if (form.rows or form.linear) and W.rows_capable() else {})
 
     @staticmethod
     def kernel(W, contract, relu, device=None, narrow=False, narrow_rows=False, narrow32=False, narrow64=False, narrow_linear=False):
@@ -267,27 +260,20 @@ class KeyedLayer(nn.Module):
         runs the order-preserving kernel under True, else the matrix cores (bf16x3: the emulation where operator and batch qualify); a plain SparseMatrix
         off the exact contract runs as a dense GEMM when it has such a handle (a large keyed nn.Linear); everything else -- tiled / factored CSR
         containers, float64 operators, small or sparse matrices -- has the reference's order only.
-        `narrow` (a batch of at most KeyedModel.NARROW_MAX columns): an operator that owns a conv-taps handle (W.narrow_capable()) is ONE launch of the
-        channel-lane order-preserving kernel under EVERY contract, the undecided and the two-step ones included -- KN_FLAG_NARROW next to the flags the
-        contract sets anyway (the library ignores them below 9 columns); every other operator is what it is without the keyword.
-        `narrow='mfma'`: a CONV operator under a re-ordering contract (False, 'bf16x3', 'split') is one launch with KN_FLAG_NARROW_MFMA (the matrix-core narrow
-        kernel) and no other contract flag; under True / 'auto', and for every other operator, exactly narrow=True.  (Whether a CALIBRATED layer may pass 'mfma'
-        here is KeyedLayer.narrow_mode's decision.)
-        `narrow_rows` (the same batches): an operator with W.rows_capable() that runs in the stored order on its CSR handle -- contract True, or any non-conv operator
-        without a dense handle in play -- gets KN_FLAG_NARROW_ROWS (the row-lane kernel, the same bits) next to the flags it has without the keyword.  A float64
-        operator, a plain SparseMatrix that a re-ordering contract put on its dense handle, and conv-taps operators keep what they have.
-        `narrow32` (with `narrow`; a batch of at most KeyedModel.NARROW32_MAX columns): a narrow-capable operator gets KN_FLAG_NARROW32 next to the flags it has
-        without the keyword (the library then honours its narrow flag up to 32 columns); every other operator keeps its flags.
-        `narrow64` (with `narrow`; a batch of at most KeyedModel.NARROW64_MAX columns): a narrow-capable operator gets KN_FLAG_NARROW32 | KN_FLAG_NARROW64 next to its narrow
-        flag (at 33 .. 64 columns the library then runs the order-preserving pipeline with one column per lane, under every contract); every other operator keeps its flags.
-        `narrow64='mfma'` (with narrow='mfma'): a conv operator under False or 'bf16x3' gets KN_FLAG_NARROW_MFMA | KN_FLAG_NARROW32 | KN_FLAG_NARROW64 | KN_FLAG_NARROW64_MFMA and no
-        other contract flag: at 33 .. 64 columns the f32 tile kernel on 64-column tiles (there is no bf16 form at that width), at 32 and fewer the library ignores the new bit.
-        Under 'split' it keeps the flags of narrow='mfma', narrow64=True (the pipeline at 33 .. 64 columns), under True / 'auto' those of narrow=True, narrow64=True.
-        `narrow_linear` (a batch of at most KeyedModel.NARROW64_MAX columns): KN_FLAG_NARROW_LINEAR under exactly the condition of `narrow_rows` -- an operator run in the
-        stored order on its own float32 CSR handle; the library honours it where that handle holds big pattern groups (a keyed Linear) and ignores it elsewhere."""
+        The flags of the narrow forms (`narrow`, `narrow_rows`, `narrow32`, `narrow64`, `narrow_linear`: KeyedModel.forward_linear says what they select; no batch here, so
+        nothing is refused and a keyword that needs `narrow` adds nothing without it):
+        `narrow`: an operator that owns a conv-taps handle (W.narrow_capable()) is ONE launch under EVERY contract, the undecided and the two-step ones included --
+        KN_FLAG_NARROW next to the flags the contract sets anyway (the library ignores them at these widths); with `narrow32` also KN_FLAG_NARROW32, with `narrow64`
+        KN_FLAG_NARROW32 | KN_FLAG_NARROW64.  Every other operator keeps the flags it has without these three.
+        narrow='mfma': a CONV operator under a re-ordering contract (False, 'bf16x3', 'split') carries KN_FLAG_NARROW_MFMA instead and no contract flag; under True / 'auto',
+        and for every other operator, exactly narrow=True.  (Whether a CALIBRATED layer may pass 'mfma' here is narrow_mode()'s decision.)  With narrow64='mfma' a conv
+        operator under False / 'bf16x3' adds KN_FLAG_NARROW64_MFMA (the 64-column tile at 33 .. 64 columns; the library ignores the bit below); every other case is narrow64=True.
+        `narrow_rows`, `narrow_linear`: KN_FLAG_NARROW_ROWS, KN_FLAG_NARROW_LINEAR on an operator that runs in the stored order on its own float32 CSR handle
+        (W.rows_capable(); not a float64 operator, not a SparseMatrix a re-ordering contract put on its dense handle, not a conv-taps operator), `narrow` or not."""
+        form = ksp.NarrowForm.of(None, narrow, narrow_rows, narrow32, narrow64, narrow_linear)
         conv = isinstance(W, ksp.Conv2dTiledMatrix)
-        lane = bool(narrow) and W.narrow_capable()          # one launch of a narrow conv kernel, whatever the contract
-        mfma = lane and narrow == 'mfma' and conv and contract in (False, 'bf16x3', 'split')      # (the library falls back to the channel-lane kernel on an ineligible operator)
+        lane = bool(form.mode) and W.narrow_capable()       # one launch of a narrow conv kernel, whatever the contract
+        mfma = lane and form.mode == 'mfma' and conv and contract in (False, 'bf16x3', 'split')      # (the library falls back to the channel-lane kernel on an ineligible operator)
         if not lane:
             if contract == 'auto' or (contract == 'split' and conv and W._taps is not None):
                 return None
@@ -297,26 +283,22 @@ class KeyedLayer(nn.Module):
         if not conv and not contract and type(W) is SparseMatrix and not W.is_float64() and W._dense_device_op(device) is not None:
             (get_op, exact) = (W._dense_device_op, False)
         stored = not lane and not conv and get_op == W._device_op and W.rows_capable()      # the stored order on the operator's own float32 CSR handle
-        (rows, linear) = (narrow_rows and stored, narrow_linear and stored)
         if mfma:
             (exact, bf16x3) = (False, False)
         return (get_op, (_capi.KN_FLAG_RELU if relu else 0) | (_capi.KN_FLAG_EXACT if exact else 0) | (_capi.KN_FLAG_BF16X3 if bf16x3 else 0) |
-                (_capi.KN_FLAG_NARROW_MFMA if mfma else _capi.KN_FLAG_NARROW if lane else 0) | (_capi.KN_FLAG_NARROW32 if lane and (narrow32 or narrow64) else 0) | (_capi.KN_FLAG_NARROW64 if lane and narrow64 else 0) |
-                (_capi.KN_FLAG_NARROW64_MFMA if mfma and narrow64 == 'mfma' and contract in (False, 'bf16x3') else 0) | (_capi.KN_FLAG_NARROW_ROWS if rows else 0) | (_capi.KN_FLAG_NARROW_LINEAR if linear else 0))
+                (_capi.KN_FLAG_NARROW_MFMA if mfma else _capi.KN_FLAG_NARROW if lane else 0) | (_capi.KN_FLAG_NARROW32 if lane and form.narrow32 else 0) | (_capi.KN_FLAG_NARROW64 if lane and form.narrow64 else 0) |
+                (_capi.KN_FLAG_NARROW64_MFMA if mfma and form.tile64 and contract in (False, 'bf16x3') else 0) |
+                (_capi.KN_FLAG_NARROW_ROWS if form.rows and stored else 0) | (_capi.KN_FLAG_NARROW_LINEAR if form.linear and stored else 0))
 
     def launch(self, device, relu=False, narrow=False, narrow_rows=False, narrow32=False, narrow64=False, narrow_linear=False):
         """This layer under its contract in force as one launch on `device` (`relu`: the unkeyed nn.ReLU behind it is fused in), or None when it is not one
         kn_spmm launch: see kernel(); a float64 operator (its own kernel and a float64 result: kn_spmm_f64).  What the key-net's planners read
-        (KeyedModel._chain_op / _overlap_plan); forward() -> W.torchdot() runs the same rule.  `narrow`, `narrow_rows`, `narrow32`, `narrow64`, `narrow_linear`: see kernel(); 'mfma' goes through narrow_mode() first, without a batch.
-        narrow64='mfma' (with narrow='mfma') asks for the launch of a batch of 33 .. 64 columns: the layer's wide decision holds there (forward()), narrow_mode() is not consulted."""
+        (KeyedModel._chain_op / _overlap_plan); forward() -> W.torchdot() runs the same rule.  `narrow`, `narrow_rows`, `narrow32`, `narrow64`, `narrow_linear`: the launch
+        forward() issues under them (narrowed(); without `narrow` the others say nothing), except that a planner has no batch: a layer still 'auto' is not one launch,
+        narrow='mfma' on a calibrated layer without a narrow record answers the channel-lane kernel, and narrow64='mfma' asks for the launch of 33 .. 64 columns."""
         W = self.W
-        if narrow == 'mfma' and narrow64 == 'mfma':
-            tile = isinstance(W, ksp.Conv2dTiledMatrix) and getattr(self, '_exact', True) in (False, 'bf16x3')
-            (narrow, narrow64) = ('mfma' if tile else True, 'mfma' if tile else True)
-        elif narrow == 'mfma':
-            narrow = self.narrow_mode(narrow)                 # (a calibrated layer without a narrow record yet: the channel-lane kernel -- forward() measures, a planner does not)
-        kernel = None if W.is_float64() else self.kernel(W, getattr(self, '_exact', True), relu or self.iskeyedrelu(), device, narrow=narrow, narrow_rows=bool(narrow and narrow_rows),
-                                                               narrow32=bool(narrow and narrow32), narrow64=narrow64 if (narrow and narrow64 == 'mfma') else bool(narrow and narrow64), narrow_linear=bool(narrow and narrow_linear))
+        (exact, keywords) = self.narrowed(ksp.NarrowForm.of(None, narrow, narrow_rows, narrow32, narrow64, narrow_linear))
+        kernel = None if W.is_float64() else self.kernel(W, exact, relu or self.iskeyedrelu(), device, **keywords)
         if kernel is None:
             return None
         return Launch(kernel[0](device), kernel[1], int(W.shape[0]), int(W.shape[1]), isinstance(W, ksp.Conv2dTiledMatrix), 'Linear' in self._layertype,

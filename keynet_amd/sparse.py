@@ -8,7 +8,9 @@ in libkeynet_hip.so on an MI355X (there is no CPU route: a missing library or de
 Build-time (host, offline) constructors live here too, restated and vectorised: Toeplitz matrices of conv / avgpool
 layers (keynet/sparse.py:122-212) and the tilers (keynet/sparse.py:519-571, 692-776).
 """
+import collections
 import copy
+import functools
 import numpy as np
 import scipy.sparse
 import torch
@@ -83,22 +85,16 @@ def _device_block(x):
 def _run_torchdot(W, x, relu=False, exact=True, absmax=None, narrow=False, narrow_rows=False, narrow32=False, narrow64=False, narrow_linear=False):
     """Y = W.X on the GPU under the contract `exact`, on the handle and flags of KeyedLayer.kernel.  x: [cols, N], torch tensor (any device / strides) or ndarray.
     Returns [rows, N] on x's device: float32, or for a float64 operator the float64 block scipy returns for it (kn_spmm_f64; the activations are
-    float32 either way).  `narrow`: at most NARROW_MAX columns on the channel-lane kernel where W owns a conv-taps handle (KeyedLayer.kernel); 'mfma': on the
-    matrix-core narrow kernel (KN_FLAG_NARROW_MFMA) where `exact` is a re-ordering contract, else exactly narrow=True.  `narrow_rows`: at most NARROW_MAX columns
-    on the row-lane kernel (KN_FLAG_NARROW_ROWS) where W's device form is a float32 CSR handle run in the stored order (W.rows_capable(), KeyedLayer.kernel): the
-    same bits; every other operator is what it is without the keyword.  `narrow32` (with `narrow`): at most NARROW32_MAX columns (KN_FLAG_NARROW32).
-    `narrow64` (with `narrow`; implies `narrow32`): at most NARROW64_MAX columns (KN_FLAG_NARROW64: beyond NARROW32_MAX the order-preserving pipeline, one column per lane).
-    `narrow64='mfma'` (with narrow='mfma'): beyond NARROW32_MAX columns a conv operator under False / 'bf16x3' runs the f32 matrix-core product on 64-column tiles
-    (KN_FLAG_NARROW64_MFMA, KeyedLayer.kernel); every other contract and operator is what narrow64=True makes it.  `narrow_linear`: at most NARROW64_MAX columns (with
-    `narrow`: its limit) with KN_FLAG_NARROW_LINEAR where `narrow_rows` would set its flag: a keyed Linear's big pattern groups on the LDS value-stream kernel, the
-    same bits; every other operator is what it is without the keyword."""
+    float32 either way).  `narrow`, `narrow_rows`, `narrow32`, `narrow64`, `narrow_linear` (narrow64='mfma' included): the narrow forms of the product
+    (KeyedModel.forward_linear), each allowed on its own here (_narrow_args with `alone`: a container's torchdot takes the ones its operator has a form for);
+    which flag each one sets on which operator is KeyedLayer.kernel's rule."""
     from .layer import KeyedLayer            # (layer.py imports this module)
     x = torch.as_tensor(x)
     assert W.shape[1] == x.shape[0], 'Non-conformal shape for W=%s, x=%s' % (str(W.shape), str(tuple(x.shape)))
     xd = _device_block(x)
     n = xd.shape[1]
-    _narrow_args(n, narrow, narrow_rows, 'batch columns', alone=True, narrow32=narrow32, narrow64=narrow64, narrow_linear=narrow_linear)
-    kernel = KeyedLayer.kernel(W, exact, relu, xd.device, narrow=narrow, narrow_rows=narrow_rows, narrow32=narrow32, narrow64=narrow64, narrow_linear=narrow_linear)
+    _narrow_args(n, narrow, narrow_rows, 'batch columns', True, narrow32, narrow64, narrow_linear)
+    kernel = KeyedLayer.kernel(W, exact, relu, xd.device, narrow, narrow_rows, narrow32, narrow64, narrow_linear)
     if kernel is None:
         y = W._torchdot_split(xd, relu=relu, absmax=absmax)
     else:
@@ -150,6 +146,30 @@ def _narrow_args(n, narrow, narrow_rows, what='images', alone=False, narrow32=Fa
         raise ValueError('narrow=\'mfma\', narrow64=True: there is no matrix-core form at %d .. %d %s (got %d); the padded forward is the matrix-core path there, '
                          'narrow=True the order-preserving one' % (NARROW32_MAX + 1, NARROW64_MAX, what, n))
     return (narrow if narrow == 'mfma' else bool(narrow), bool(narrow_rows))
+
+
+class NarrowForm(collections.namedtuple('NarrowForm', 'mode rows narrow32 narrow64 tile64 linear')):
+    """The five keywords narrow, narrow_rows, narrow32, narrow64, narrow_linear of one call, resolved once: what KeyedModel.forward_linear documents, as a value.
+    `mode`: False (the wide forward) | True (the order-preserving conv kernels) | 'mfma' (the matrix-core narrow kernel where a layer's contract allows it);
+    `narrow32`, `narrow64`: the width the keywords allow is lifted to NARROW32_MAX, to NARROW64_MAX (narrow64 implies narrow32); `tile64`: narrow64='mfma' at a
+    width that takes the 64-column matrix-core tile; `rows`, `linear`: narrow_rows, narrow_linear.  Built by of() at the surfaces that take the keywords: once per
+    call in KeyedModel, which hands the value down to _forward_once; there keywords() hands the keywords back to each KeyedLayer.forward, and that surface and
+    KeyedLayer.kernel behind the operator's torchdot each build the value again from them (the keyword surfaces are what a layer and an operator are called by)."""
+    __slots__ = ()
+
+    @classmethod
+    @functools.lru_cache(maxsize=256)        # (asked per layer and launch, on the shortest forwards, for the same few keyword sets)
+    def of(cls, n, narrow=False, narrow_rows=False, narrow32=False, narrow64=False, narrow_linear=False, what='images', alone=False):
+        """The form of a batch of `n` under the keywords: _narrow_args refuses what the argument rule refuses (`what`, `alone`: its own).  n = None: no batch
+        (KeyedLayer.kernel / launch) -- nothing is refused, a keyword without `narrow` means what the rules of kernel() make of it, and the tile is asked for."""
+        mode = narrow if narrow == 'mfma' else bool(narrow)
+        if n is not None:
+            _narrow_args(n, narrow, narrow_rows, what, alone, narrow32=narrow32, narrow64=narrow64, narrow_linear=narrow_linear)
+        return cls(mode, bool(narrow_rows), bool(narrow32 or narrow64), bool(narrow64), mode == 'mfma' and narrow64 == 'mfma' and (n is None or n > NARROW32_MAX), bool(narrow_linear))
+
+    def keywords(self):
+        """The keywords of this form, normalised, as KeyedLayer.forward and the surfaces below it take them (narrow64: 'mfma' only where the tile is asked for)."""
+        return dict(narrow=self.mode, narrow_rows=self.rows, narrow32=self.narrow32, narrow64='mfma' if self.tile64 else self.narrow64, narrow_linear=self.linear)
 
 
 # ------------------------------------------------------------------------------------------------------------------
@@ -656,17 +676,11 @@ class Conv2dTiledMatrix(TiledMatrix):
         reference's accumulation order and rounding (order-preserving kernel on the factored operator); exact='split': a filled-in factored
         operator applied as spatial mixing per tap, then channel mixing (see _split_ops: another association of the sum, tolerance contract only); exact='bf16x3': f32 products
         emulated on the bf16 matrix pipe (three-way exact split, six of nine cross products, f32 accumulate: KN_FLAG_BF16X3) where the
-        operator and batch qualify, else the f32 MFMA path.  narrow=True (N <= NARROW_MAX, ValueError beyond): the channel-lane order-preserving kernel
-        (KN_FLAG_NARROW) whatever `exact` says -- always the reference's own arithmetic, the bits of exact=True.  narrow='mfma': the matrix-core narrow kernel
-        (KN_FLAG_NARROW_MFMA: an implicit GEMM over output pixels x images, another association of the sum) when `exact` is False / 'bf16x3' / 'split' and the
-        operator is eligible (no (pixel, tap) pair with more than two slots); under True / 'auto', and on an ineligible operator, exactly narrow=True.
-        narrow32=True (with `narrow`): N <= NARROW32_MAX -- beyond NARROW_MAX columns convtaps_narrow32_kernel (the bits of exact=True), or the matrix-core narrow
-        kernel at NV = 16 | 32 (per column the bits of narrow='mfma' on that column).
-        narrow64='mfma' (with narrow='mfma'): N <= NARROW64_MAX -- beyond NARROW32_MAX columns, under exact=False / 'bf16x3', the f32 matrix-core product on 64-column
-        tiles (KN_FLAG_NARROW64_MFMA: per column the bits of the plain matrix-core call on the batch zero-padded to 128 columns); under every other contract
-        narrow64=True; at NARROW32_MAX columns and fewer exactly narrow='mfma', narrow32=True.
-        narrow64=True (with `narrow`; implies narrow32): N <= NARROW64_MAX -- beyond NARROW32_MAX columns the order-preserving pipeline with one column per lane
-        (KN_FLAG_NARROW64, convtaps_exact_pipe64_kernel; a filled-in operator: what exact=True runs at that width), the bits of exact=True; narrow='mfma' is refused there."""
+        operator and batch qualify, else the f32 MFMA path.  `narrow`, `narrow32`, `narrow64`: the narrow forms of KeyedModel.forward_linear on this one operator, N within
+        their limits (ValueError beyond) -- narrow=True the order-preserving narrow kernels whatever `exact` says (the bits of exact=True); narrow='mfma' the matrix-core
+        narrow kernel when `exact` is False / 'bf16x3' / 'split' and the operator is eligible (no (pixel, tap) pair with more than two slots), else exactly narrow=True;
+        narrow64='mfma' (with narrow='mfma') beyond NARROW32_MAX columns under False / 'bf16x3' the f32 product on 64-column tiles (per column the bits of the plain
+        matrix-core call on the batch zero-padded to 128 columns), else narrow64=True.  The flag word is KeyedLayer.kernel's."""
         assert not isinstance(exact, str) or exact in ('bf16x3', 'split') or (narrow and exact == 'auto'), "exact must be True, False, 'bf16x3' or 'split'"
         return _run_torchdot(self, x, relu=relu, exact=exact, absmax=absmax, narrow=narrow, narrow32=narrow32, narrow64=narrow64)
 

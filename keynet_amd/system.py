@@ -199,62 +199,63 @@ class KeyedModel(object):
         Memory: the overlapped forward keeps two ping-pong workspaces of max_rows x N floats per (device, N) plan (VGG-16 at N = 256:
         2 x 3.3 GB) plus two side streams; at most OVERLAP_PLANS_KEPT plans are cached (least recently used dropped),
         release_workspace() drops them all.
-        `narrow=True`: the low-latency forward of 1 .. NARROW_MAX images (ValueError beyond).  Nothing is padded: the batch is laid out feature-major once
-        and every conv-taps layer runs the channel-lane order-preserving kernel (KN_FLAG_NARROW), WHATEVER its contract is.  A narrow forward is therefore
-        always the reference's own arithmetic on the conv layers -- stored order, separate multiply and add, the bits exact=True gives -- which satisfies
-        every contract: it calibrates nothing, screens nothing, changes no layer's decision or record and leaves the cached launch lists alone.  The other
-        layers run as they do without the keyword, at the unpadded width (a layer still undecided: in the reference's order, for this call; a non-conv layer a calibration
-        put on the matrix cores stays there and is NOT re-screened by this forward); a key-net that
-        qualifies for the whole-net kernel still takes it; the overlapped form is never taken.
+        THE NARROW FORMS (low latency, at most 64 images; this is the one place that says what their five keywords mean -- they are resolved once per call into a
+        ksp.NarrowForm, ValueError where ksp._narrow_args refuses them: every other keyword only together with `narrow`, no batch beyond the width they allow).  Common to
+        all: nothing is padded (but the 64-column tile, below) -- the batch is laid out feature-major once and every layer runs at that width; the overlapped form is never
+        taken, the whole-net kernel only where no layer has a narrow form; no layer's wide decision changes, nothing is saved, the cached launch lists are left alone.
+        `narrow=True` (1 .. NARROW_MAX images): every conv-taps layer runs the channel-lane order-preserving kernel (KN_FLAG_NARROW), WHATEVER its contract is: the
+        reference's own arithmetic on the conv layers -- stored order, separate multiply and add, the bits exact=True gives -- which satisfies every contract, so nothing
+        is calibrated, screened, decided or recorded.  The other layers run as they do without the keyword (a layer still undecided: in the reference's order, for this
+        call; a non-conv layer a calibration put on the matrix cores stays there and is NOT re-screened by this forward).
         `narrow='mfma'`: the same forward with the conv-taps layers on the matrix-core narrow kernel (KN_FLAG_NARROW_MFMA: an implicit GEMM whose N dimension is
         output pixels x images) WHERE THE LAYER'S CONTRACT IN FORCE ALLOWS RE-ORDERED SUMS (KeyedLayer.narrow_mode): a declared exact=False / 'bf16x3' layer always,
         unscreened; a layer calibration put on a re-ordering kernel after ITS OWN measurement on the first such batch (channel-lane against matrix-core kernel on these
-        columns, the rule of _calibrate; recorded under the layer's calibration record as 'narrow', the wide decision untouched); a layer under True, or still
-        undecided, exactly as narrow=True -- nothing is decided for it.  Layers accepted by measurement are re-screened on every narrow='mfma' forward like their
-        wide counterparts: max |x| of each comes from kn_spmm_screen on its producer (behind the narrow kernels that is one kn_absmax-style reduction launch per
-        screened layer, one more for the input when the first layer is screened), is read back once at the end of the forward, and a layer whose input exceeds
-        RESCREEN_FACTOR x its narrow record's max_abs_x drops that record, is measured again on this batch, and the batch runs again (_rescreen).
-        `narrow_rows=True` (only together with `narrow`, ValueError otherwise): the layers that are float32 CSR operators in the stored order -- keyed Linear layers
-        under the bit-exact contract, pools, every layer of an untiled key-net -- run the row-lane kernel (KN_FLAG_NARROW_ROWS: the lane is the output row, the images
-        its running sums) instead of the wide-batch CSR kernels at the unpadded width.  The same bits layer by layer; orthogonal to which conv kernel `narrow` selects;
-        nothing is calibrated, decided, recorded or saved, and the cached launch lists and the whole-net kernel are left alone.
-        `narrow32=True` (only together with `narrow`, ValueError otherwise): the same forward for up to NARROW32_MAX images (ValueError beyond; `narrow_rows` stays
-        at NARROW_MAX).  Beyond NARROW_MAX images the conv-taps layers run convtaps_narrow32_kernel (narrow=True: the bits of exact=True, as at 1 .. 8) or the
-        matrix-core narrow kernel at 16 | 32 columns per pixel (narrow='mfma': per image the bits of narrow='mfma' on that image; a calibrated layer is measured on the
-        8 images that hold the batch's largest |x| and screened as at 1 .. 8); every other layer runs as it does without the keyword, at the unpadded width.
-        `narrow64=True` (only together with `narrow`, ValueError otherwise): the same forward for up to NARROW64_MAX images (ValueError beyond; `narrow_rows` stays at
-        NARROW_MAX).  It implies `narrow32`: a service passes one set of keywords for any batch of at most 64 images, and at NARROW32_MAX images and fewer the call is
-        exactly narrow32=True.  Beyond, the conv-taps layers run the order-preserving pipeline with one image per lane (KN_FLAG_NARROW64: convtaps_exact_pipe64_kernel, half
-        the packed instructions per step of the padded 128-image tile; a filled-in operator runs what exact=True runs at that width) -- the bits of exact=True under every
-        contract, so the forward of a key-net under the bit-exact contract equals the padded one bit for bit.  Nothing is padded, calibrated, screened, decided or recorded.
-        narrow='mfma' with narrow64=True is a ValueError at 33 .. 64 images (True asks for the order-preserving form of that width).
-        `narrow64='mfma'` (only together with narrow='mfma', ValueError otherwise; at most NARROW64_MAX images): the matrix-core forward of 33 .. 64 images.  At NARROW32_MAX
-        images and fewer the call is exactly narrow='mfma', narrow32=True, bit for bit.  Beyond, the batch is laid out feature-major and zero-padded to 64 columns (the
-        argument of _prepare's padding: an image's logits are the same in any batch, zero images raise no layer's max |x|), and a conv-taps layer whose contract in force is
-        False or 'bf16x3' runs the f32 tile kernel on 64-column tiles (KN_FLAG_NARROW64_MFMA: convtaps_mfma_kernel<MT, NB=64>; there is no bf16 form at this width) -- per
-        image the bits the padded forward's f32 tiles give it, half the matrix work of the 128-column tile the padded forward runs half empty.  A conv-taps layer under True,
-        still 'auto', or decided 'split' runs what narrow64=True runs (the order-preserving pipeline, which satisfies every contract: nothing is decided or recorded); the
-        other layers run as they do without the keyword, at 64 columns.  A key-net with no layer on a re-ordering contract therefore returns the bits of narrow=True,
-        narrow64=True.  The screen: the 64-column tile is the WIDE kernel's association, so a declared layer is unscreened and a layer calibration put there (screened()) is
-        re-screened against its WIDE record (not the narrow one, which belongs to the other kernel), through the same slots and RESCREEN_FACTOR.  A tripped layer goes back
-        to 'auto' as on the wide path (launch lists dropped), this pass runs again with that layer in the stored order, and the next padded forward calibrates it: nothing
-        calibrates inside this path.
-        `narrow_linear=True` (only together with `narrow`, ValueError otherwise; at every width the `narrow` keywords passed allow: NARROW_MAX, NARROW32_MAX with
-        `narrow32`, NARROW64_MAX with `narrow64`): the keyed Linear layers under the bit-exact contract -- float32 CSR operators in the stored order that hold big
-        pattern groups -- run csr_stream_group_kernel (KN_FLAG_NARROW_LINEAR: a workgroup owns 64 output rows times all images, the values reach it through a ring in
-        LDS and leave HBM once per call) instead of the wide-batch kernel, which costs 64 images at every width.  The same bits layer by layer; next to `narrow_rows` the
-        other CSR layers and the remaining rows of a Linear keep the row-lane kernel.  Nothing is calibrated, screened, decided, recorded or saved, and the cached launch
-        lists and the whole-net kernel are left alone."""
-        n = img_cipher.shape[0]
-        (mode, rows) = ksp._narrow_args(n, narrow, narrow_rows, narrow32=narrow32, narrow64=narrow64, narrow_linear=narrow_linear)
-        narrow64 = self._narrow64_form(n, narrow64)
-        (x, windows) = self._prepare64(img_cipher) if narrow64 == 'mfma' else self._prepare(img_cipher, mode)
-        y = self._forward_passes(x, windows, False if mode else overlap, mode, rows, bool(narrow32), narrow64, bool(narrow_linear))[0][:n]
+        columns, the rule of _calibrate; recorded under the layer's calibration record as 'narrow'); a layer under True, or still undecided, exactly as narrow=True --
+        nothing is decided for it.  Layers accepted by measurement are re-screened on every narrow='mfma' forward like their wide counterparts: max |x| of each comes
+        from kn_spmm_screen on its producer (behind the narrow kernels one kn_absmax-style reduction launch per screened layer, one more for the input when the first
+        layer is screened), is read back once at the end of the forward, and a layer whose input exceeds RESCREEN_FACTOR x its narrow record's max_abs_x drops that
+        record, is measured again on this batch, and the batch runs again (_screen, _rescreen).
+        `narrow32=True`: up to NARROW32_MAX images.  Beyond NARROW_MAX the conv-taps layers run convtaps_narrow32_kernel (narrow=True: the bits of exact=True, as at
+        1 .. 8) or the matrix-core narrow kernel at 16 | 32 columns per pixel (narrow='mfma': per image the bits of narrow='mfma' on that image; a calibrated layer is
+        measured on the 8 images that hold the batch's largest |x| and screened as at 1 .. 8).
+        `narrow64=True`: up to NARROW64_MAX images.  It implies `narrow32` -- a service passes one set of keywords for any batch of at most 64 images, and at NARROW32_MAX
+        images and fewer the call is exactly narrow32=True.  Beyond, the conv-taps layers run the order-preserving pipeline with one image per lane (KN_FLAG_NARROW64:
+        convtaps_exact_pipe64_kernel, half the packed instructions per step of the padded 128-image tile; a filled-in operator runs what exact=True runs at that width) --
+        the bits of exact=True under every contract, so the forward of a key-net under the bit-exact contract equals the padded one bit for bit; nothing is calibrated,
+        screened, decided or recorded.  narrow='mfma' with narrow64=True is a ValueError at 33 .. 64 images (True asks for the order-preserving form of that width).
+        `narrow64='mfma'` (only together with narrow='mfma'): the matrix-core forward of 33 .. 64 images; at NARROW32_MAX images and fewer exactly narrow='mfma',
+        narrow32=True, bit for bit.  Beyond, the batch is zero-padded to 64 columns (_prepare64; the argument of _prepare's padding: an image's logits are the same in any
+        batch, zero images raise no layer's max |x|), and a conv-taps layer whose contract in force is False or 'bf16x3' runs the f32 tile kernel on 64-column tiles
+        (KN_FLAG_NARROW64_MFMA: convtaps_mfma_kernel<MT, NB=64>; there is no bf16 form at this width) -- per image the bits the padded forward's f32 tiles give it, half
+        the matrix work of the 128-column tile the padded forward runs half empty.  A conv-taps layer under True, still 'auto', or decided 'split' runs what narrow64=True
+        runs, so a key-net with no layer on a re-ordering contract returns the bits of narrow=True, narrow64=True.  The screen: the 64-column tile is the WIDE kernel's
+        association, so a declared layer is unscreened and a layer calibration put there is re-screened against its WIDE record (not the narrow one, which belongs to
+        the other kernel), through the same slots and RESCREEN_FACTOR.  A tripped layer goes back to 'auto' as on the wide path (launch lists dropped), this pass runs
+        again with that layer in the stored order, and the next padded forward calibrates it: nothing calibrates inside this path.
+        `narrow_rows=True` (at most NARROW_MAX images, whatever `narrow32` / `narrow64` allow): the layers that are float32 CSR operators in the stored order -- keyed
+        Linear layers under the bit-exact contract, pools, every layer of an untiled key-net -- run the row-lane kernel (KN_FLAG_NARROW_ROWS: the lane is the output row,
+        the images its running sums) instead of the wide-batch CSR kernels.  The same bits layer by layer; orthogonal to which conv kernel `narrow` selects.
+        `narrow_linear=True` (at every width the other keywords allow): the keyed Linear layers under the bit-exact contract -- float32 CSR operators in the stored order
+        that hold big pattern groups -- run csr_stream_group_kernel (KN_FLAG_NARROW_LINEAR: a workgroup owns 64 output rows times all images, the values reach it through
+        a ring in LDS and leave HBM once per call) instead of the wide-batch kernel, which costs 64 images at every width.  The same bits layer by layer; next to
+        `narrow_rows` the other CSR layers and the remaining rows of a Linear keep the row-lane kernel."""
+        (form, x, windows) = self._resolve(img_cipher, (narrow, narrow_rows, narrow32, narrow64, narrow_linear))
+        y = self._forward_passes(x, windows, False if form.mode else overlap, form)[0][:img_cipher.shape[0]]
         return y if img_cipher.is_cuda else y.to(img_cipher.device)
+
+    def _resolve(self, x, keywords, own=False):
+        """The narrow keywords of forward_linear / capture (in the order of their signatures) on the batch x, once per call: (form, block, windows) -- the ksp.NarrowForm
+        everything below reads (ValueError where the argument rule refuses the keywords) and the block the passes run on, _prepare64's where the form takes the 64-column
+        tile, else _prepare's.  `own` (capture): a block of the call's own, never x's memory -- the graph's input."""
+        form = ksp.NarrowForm.of(x.shape[0], *keywords)
+        if own:
+            x = x.detach().float() if form.mode else x.detach()
+            x = x if form.tile64 else x.t().clone(memory_format=torch.contiguous_format).t()
+        return (form,) + (self._prepare64(x) if form.tile64 else self._prepare(x, form.mode))
 
     @staticmethod
     def _narrow64_form(n, narrow64):
-        """The normalised `narrow64` of a batch of n images: 'mfma' beyond NARROW32_MAX images only (at fewer, narrow64='mfma' is exactly narrow64=True, i.e. narrow32), else a bool."""
+        """The normalised `narrow64` of a batch of n images, as NarrowForm.keywords() hands it on: 'mfma' beyond NARROW32_MAX images only (at fewer, narrow64='mfma' is exactly narrow64=True, i.e. narrow32), else a bool."""
         return 'mfma' if (narrow64 == 'mfma' and n > ksp.NARROW32_MAX) else bool(narrow64)
 
     def _prepare64(self, x):
@@ -299,16 +300,11 @@ class KeyedModel(object):
             x = x.detach().t().contiguous().t()
         return (x, windows)
 
-    def _forward_passes(self, x, windows, overlap, narrow=False, rows=False, narrow32=False, narrow64=False, linear=False):
-        """The screened forward of a prepared batch: (y, screens).  A pass whose screen re-calibrates a layer runs again (calibrating on its own images),
-        then every other pass again: the batch comes out of ONE set of contracts.  At most RESCREEN_MAX_PASSES runs of a pass; then only the last pass is
-        re-screened (the next forward decides).  Under a HIP-graph capture nothing is read: `screens` = (slots, screened) per pass, for capture's replay.
-        `narrow` / `rows` / `narrow32` / `narrow64` / `linear` (the normalised keywords narrow, narrow_rows, narrow32, narrow64, narrow_linear of forward_linear): the screened layers are those a MEASUREMENT put on the matrix-core narrow kernel (none under
-        narrow=True; an 'auto' layer does not switch the screen off: it runs in the reference's order for this call), screened against their narrow records; layers
-        measured during a pass were measured on this very batch, so only the records that existed before it are screened.
-        narrow64 == 'mfma' (33 .. 64 images, _prepare64's block): the screened layers are the conv-taps layers a CALIBRATION put on the f32 / bf16x3 matrix-core kernels -- they
-        run the wide kernel's association on 64-column tiles -- screened against their WIDE records; a trip sends the layer back to 'auto' (stored order in the re-run)."""
-        wide64 = narrow == 'mfma' and narrow64 == 'mfma'
+    def _forward_passes(self, x, windows, overlap, form):
+        """The screened forward of a prepared batch under the ksp.NarrowForm `form`: (y, screens).  A pass whose screen re-calibrates a layer runs again (calibrating on its
+        own images), then every other pass again: the batch comes out of ONE set of contracts.  At most RESCREEN_MAX_PASSES runs of a pass; then only the last pass is
+        re-screened (the next forward decides).  Under a HIP-graph capture nothing is read: `screens` = the arguments of _rescreen per pass, for capture's replay.
+        Which layers are screened, and against what: _screen; records made during a pass were measured on this very batch, so only those that existed before it are screened."""
         keyed = self._keyed()
         on_dev = x.is_cuda and x.dim() == 2
         read = on_dev and not torch.cuda.is_current_stream_capturing() and self.RESCREEN_READ
@@ -316,25 +312,36 @@ class KeyedModel(object):
         (todo, screens, redos) = (list(range(len(windows))), [], 0)
         while todo:
             k = todo.pop(0)
-            screened = set()
-            if on_dev and self.RESCREEN and (narrow == 'mfma' if narrow else not any(getattr(c, '_exact', True) == 'auto' for c in keyed)):
-                if wide64:
-                    screened = set(j for (j, c) in enumerate(keyed) if c.screened() and isinstance(c.W, ksp.Conv2dTiledMatrix) and c.W.narrow_capable() and c._exact in (False, 'bf16x3'))
-                else:
-                    screened = set(j for (j, c) in enumerate(keyed) if (c.narrow_screened() if narrow else c.screened()))
+            (screened, narrow) = self._screen(form, keyed) if on_dev and self.RESCREEN else (set(), False)
             slots = torch.zeros(len(keyed) + 1, dtype=torch.float32, device=x.device) if screened else None
             (lo, hi) = windows[k]
             # (a window of a wider block: its own feature-major block, so that the pass can take the overlapped form)
-            ys[k] = self._forward_once(x if len(windows) == 1 else x[lo:hi].t().contiguous().t(), keyed, overlap, slots, screened, narrow, rows, narrow32, narrow64, linear)
+            ys[k] = self._forward_once(x if len(windows) == 1 else x[lo:hi].t().contiguous().t(), keyed, overlap, slots, screened, form)
             if slots is None:
                 continue
-            screens.append((slots, screened))
+            screens.append((slots, screened, narrow))
             if not read or (todo and redos + 1 == self.RESCREEN_MAX_PASSES):
                 continue
-            if self._rescreen(slots.tolist(), keyed, screened, bool(narrow) and not wide64) and redos + 1 < self.RESCREEN_MAX_PASSES:
+            if self._rescreen(slots.tolist(), keyed, screened, narrow) and redos + 1 < self.RESCREEN_MAX_PASSES:
                 redos += 1
                 todo = [k] + [j for j in range(len(windows)) if j != k]
         return (ys[0] if len(ys) == 1 else torch.cat([y.t() for y in ys], dim=1).t(), screens)
+
+    @staticmethod
+    def _screen(form, keyed):
+        """The per-forward screen under `form`: (screened, narrow) -- the indices of the keyed layers whose input this forward checks, and the record it checks them against
+        with what a trip does (_rescreen).  narrow=True: the conv layers run the reference's own arithmetic -- nobody, whatever the other layers are.  narrow='mfma': the
+        layers a MEASUREMENT put on the matrix-core narrow kernel, against their narrow records (`narrow`: a trip drops that record, the layer is measured again on this
+        batch; an 'auto' layer does not switch the screen off, it runs in the reference's order for this call).  The 64-column tile: the conv-taps layers a CALIBRATION put
+        on the f32 / bf16x3 matrix-core kernels -- the wide kernel's association -- against their WIDE records, a trip as on the wide forward.  The wide forward: every layer
+        on a re-ordering kernel by calibration, once no layer is 'auto' any more; a trip sends the layer back to 'auto' and drops the launch lists."""
+        if form.tile64:
+            return (set(j for (j, c) in enumerate(keyed) if c.screened() and isinstance(c.W, ksp.Conv2dTiledMatrix) and c.W.narrow_capable() and c._exact in (False, 'bf16x3')), False)
+        if form.mode:
+            return (set(j for (j, c) in enumerate(keyed) if c.narrow_screened()) if form.mode == 'mfma' else set(), True)
+        if any(getattr(c, '_exact', True) == 'auto' for c in keyed):
+            return (set(), False)
+        return (set(j for (j, c) in enumerate(keyed) if c.screened()), False)
 
     def _rescreen(self, xmax, keyed, screened, narrow=False):
         """Host side of the per-forward screen: layers whose input magnitude has outgrown their calibration go back to 'auto' (decided
@@ -355,10 +362,10 @@ class KeyedModel(object):
     BATCH_TILE = 128           # _prepare pads a device batch of a tiled-conv key-net to whole multiples of this many images
     MAX_BLOCK_ELEMENTS = 1 << 31   # ... and splits a batch whose largest layer would hold this many activations or more into passes
 
-    def _forward_once(self, img_cipher, keyed, overlap, slots, screened, narrow=False, rows=False, narrow32=False, narrow64=False, linear=False):
+    def _forward_once(self, img_cipher, keyed, overlap, slots, screened, form):
         """One pass over the keyed layers `keyed` (_keyed()).  `slots` (device f32 [L + 1], zeroed) / `screened` (indices of the keyed layers whose contract
         is re-screened): slot k receives max |x| of keyed layer k -- slot 0 by one pass over the input, slot k + 1 by the kernel that
-        produces layer k's output.  `narrow` / `rows` / `narrow32` / `narrow64` / `linear`: every layer in its narrow form (KeyedLayer.forward); the whole-net kernel only where no layer has one."""
+        produces layer k's output.  `form` (ksp.NarrowForm): narrow, every layer in its narrow form (KeyedLayer.forward) and the whole-net kernel only where no layer has one."""
         forced = overlap is True
         if overlap is None and not self.OVERLAP_AUTO:
             overlap = False
@@ -367,7 +374,7 @@ class KeyedModel(object):
         if overlap is None:
             overlap = (img_cipher.is_cuda and img_cipher.dtype == torch.float32 and img_cipher.dim() == 2 and img_cipher.shape[0] >= 256 and
                        img_cipher.shape[0] % 256 == 0 and img_cipher.t().is_contiguous() and not torch.cuda.is_current_stream_capturing())
-        if not forced and img_cipher.is_cuda and img_cipher.dim() == 2 and not screened and not (narrow and any(c.W.narrow_capable() for c in keyed)):
+        if not forced and img_cipher.is_cuda and img_cipher.dim() == 2 and not screened and not (form.mode and any(c.W.narrow_capable() for c in keyed)):
             chain = self._chain_op(img_cipher.device)
             if chain is not None:
                 return self._forward_chain(img_cipher, chain)
@@ -377,12 +384,12 @@ class KeyedModel(object):
             plan = self._overlap_plan(img_cipher.device, img_cipher.shape[0], force=forced)
             if plan is not None and img_cipher.is_cuda and img_cipher.dtype == torch.float32 and img_cipher.t().is_contiguous():
                 return self._forward_overlapped(img_cipher.detach(), plan, slots, screened)
-        y = img_cipher
+        (y, keywords) = (img_cipher, form.keywords())
         for (k, c, relu) in self._steps():
             if k is None:
                 y = _relu_block(y)
             else:
-                y = c.forward(y, fuse_relu=relu, absmax=slots[k + 1:k + 2] if (slots is not None and (k + 1) in screened) else None, narrow=narrow, narrow_rows=rows, narrow32=narrow32, narrow64=narrow64, narrow_linear=linear)
+                y = c.forward(y, fuse_relu=relu, absmax=slots[k + 1:k + 2] if (slots is not None and (k + 1) in screened) else None, **keywords)
         return y
 
     # -- whole-net kernel: every operator of a small untiled key-net in ONE launch, activations in LDS (csrc/kn_chain.hip) --------
@@ -640,42 +647,29 @@ class KeyedModel(object):
         rows of the graph's static output buffer (clone it to keep a result across replays).  A key-net with calibrated layers keeps its per-forward
         screen: the graph gathers max |x| per layer like the eager forward, replay() reads it back after the launch and, when a layer's input has
         outgrown its calibration, re-runs the batch eagerly (re-calibrating) and captures a new graph.
-        `narrow=True` (at most NARROW_MAX images): the graph of forward_linear(narrow=True) -- a straight line of launches on one stream, no parallel
-        branches; nothing is screened (the conv layers run the reference's own arithmetic), so replay() reads nothing back.
-        `narrow='mfma'`: the graph of forward_linear(narrow='mfma'), decided by one eager forward first; still one stream, no parallel branches.  With layers on the
-        matrix-core narrow kernel by a measurement the graph gathers their max |x|, replay() reads the slots after the launch and on a trip runs the batch eagerly
-        (measuring again) and captures a new graph, as the wide capture does; with no such layer it reads nothing.
-        `narrow_rows=True` (only with `narrow`): the graph of forward_linear(narrow=..., narrow_rows=True): the same straight line of launches.
-        `narrow32=True` (only with `narrow`): the graph of forward_linear(narrow=..., narrow32=True), up to NARROW32_MAX images.
-        `narrow64=True` (only with `narrow`): the graph of forward_linear(narrow=True, narrow64=True), up to NARROW64_MAX images -- the same straight line of launches on one stream.
-        `narrow64='mfma'` (only with narrow='mfma'): the graph of forward_linear(narrow='mfma', narrow64='mfma') -- at 33 .. 64 images the 64-column block of that forward, still a
-        straight line of launches on one stream.  With layers on the matrix-core kernels by calibration the graph gathers their max |x|; replay() reads the slots against the
-        WIDE records and on a trip runs the batch eagerly (the tripped layer back to 'auto', in the stored order) and captures a new graph, as the wide capture does.
-        `narrow_linear=True` (only with `narrow`): the graph of forward_linear(narrow=..., narrow_linear=True): the same straight line of launches."""
+        `narrow`, `narrow_rows`, `narrow32`, `narrow64`, `narrow_linear` (narrow='mfma', narrow64='mfma' included): the graph of forward_linear under the same keywords, up to
+        the same widths -- a straight line of launches on one stream, no parallel branches, decided by the eager forward first.  Where that forward screens layers
+        (narrow='mfma': against their narrow records; the 64-column tile: against their wide records; narrow=True: none, replay() reads nothing back) the graph gathers
+        their max |x|, replay() reads the slots after the launch and on a trip runs the batch eagerly (measuring or calibrating again) and captures a new graph."""
         assert img_cipher.is_cuda, 'capture() needs a device tensor'
         n = img_cipher.shape[0]
-        (mode, rows) = ksp._narrow_args(n, narrow, narrow_rows, narrow32=narrow32, narrow64=narrow64, narrow_linear=narrow_linear)
-        linear = bool(narrow_linear)
-        (narrow32, narrow64) = (bool(narrow32), self._narrow64_form(n, narrow64))
-        wide64 = narrow64 == 'mfma'
-        src = img_cipher.detach().float() if mode else img_cipher.detach()
-        (static_in, windows) = self._prepare64(src) if wide64 else self._prepare(src.t().clone(memory_format=torch.contiguous_format).t(), mode)     # the graph's own input block
+        (form, static_in, windows) = self._resolve(img_cipher, (narrow, narrow_rows, narrow32, narrow64, narrow_linear), own=True)
         keyed = self._keyed()
         state = {}
 
         def build():
-            self._forward_passes(static_in, windows, False, mode, rows, narrow32, narrow64, linear)       # uploads operators, sizes workspaces, calibrates (not capturable)
+            self._forward_passes(static_in, windows, False, form)       # uploads operators, sizes workspaces, calibrates (not capturable)
             torch.cuda.synchronize()
             side = torch.cuda.Stream()
             side.wait_stream(torch.cuda.current_stream())
             with torch.cuda.stream(side):
-                self._forward_passes(static_in, windows, False, mode, rows, narrow32, narrow64, linear)   # warm-up on the capture stream
+                self._forward_passes(static_in, windows, False, form)   # warm-up on the capture stream
             torch.cuda.current_stream().wait_stream(side)
             graph = torch.cuda.CUDAGraph()
             # capture ON THE WARMED STREAM: per-stream state of the operators (the split-K workspace of a dense layer, kn_api.hip) was sized
             # by the warm-up forward above; torch's default capture stream would be a fresh one, and a hipMalloc inside a capture is refused
             with torch.cuda.graph(graph, stream=side):
-                (out, screens) = self._forward_passes(static_in, windows, False, mode, rows, narrow32, narrow64, linear)
+                (out, screens) = self._forward_passes(static_in, windows, False, form)
             state.update(graph=graph, out=out[:n], screens=screens)
 
         build()
@@ -683,7 +677,7 @@ class KeyedModel(object):
         def replay(x):
             static_in[:n].copy_(x)
             state['graph'].replay()
-            if any(self._rescreen(slots.tolist(), keyed, screened, bool(mode) and not wide64) for (slots, screened) in state['screens']):
+            if any(self._rescreen(slots.tolist(), keyed, screened, narrow) for (slots, screened, narrow) in state['screens']):
                 build()                                          # eager forward on this batch re-calibrates (narrow: measures again); then a fresh graph
                 state['graph'].replay()
             replay.graph = state['graph']
@@ -693,9 +687,8 @@ class KeyedModel(object):
 
     def forward(self, img_cipher, outkey=None, narrow=False, narrow_rows=False, narrow32=False, narrow64=False, narrow_linear=False):
         """Encrypted image(s) [N, D0+1] -> logits.  N == 1 returns the reference's shape `outshape` = (C,1,1)
-        (keynet/system.py:130-133); N > 1 (an extension: the reference cannot) returns (N, C, 1, 1).  `narrow`: forward_linear(narrow=True | 'mfma'), the
-        low-latency forms of this very call for 1 .. NARROW_MAX images; `narrow_rows`: with them, the CSR layers on the row-lane kernel (forward_linear); `narrow32`: with them, up to NARROW32_MAX images; `narrow64`: up to NARROW64_MAX
-        (narrow64=True: the order-preserving form of 33 .. 64 images; narrow64='mfma', with narrow='mfma': the matrix-core form on 64-column tiles, forward_linear); `narrow_linear`: with them, the keyed Linear layers on the LDS value-stream kernel (forward_linear)."""
+        (keynet/system.py:130-133); N > 1 (an extension: the reference cannot) returns (N, C, 1, 1).  `narrow`, `narrow_rows`, `narrow32`, `narrow64`,
+        `narrow_linear` (narrow='mfma', narrow64='mfma' included): the low-latency forms of this very call, handed to forward_linear, which says what each selects."""
         outkey = outkey if outkey is not None else self.embeddingkey()
         y = self.forward_linear(img_cipher, narrow=narrow, narrow_rows=narrow_rows, narrow32=narrow32, narrow64=narrow64, narrow_linear=narrow_linear)
         if outkey is not None:
