@@ -1,6 +1,7 @@
 // kn_api.hip -- extern "C" surface of libkeynet_hip.so (see include/keynet_hip.h for the reference interface each
 // entry point replaces).  Host-side conversion of the reference's operator containers into HBM-resident formats.
 #include "kn_internal.h"
+#include "kn_deal.h"
 #include <algorithm>
 #include <cstring>
 #include <map>
@@ -396,6 +397,20 @@ static int convtaps_create_impl(ConvBuild& b, kn_operator** out) {
         for (int64_t o = 0; o < HoWo; o++) ids[(size_t)o] = (int32_t)o;
         h->h_pix_order = locality_order(ids, pix_ptr.data(), slot_in.data(), HiWi, std::max(1, c.tune.conv_ball), 1 << 30);
     }
+    // ... and the same order dealt to the 8 XCDs (kn_deal.h) for the kernels that cut it into one contiguous chunk per XCD: a work item's K loop is as long as its
+    // pixel's slot list, so equal counts of the ball order are unequal work where the border pixels gather in some XCD's chunk (VGG-16 conv5_x: 27 % border pixels, slot
+    // weight per XCD 1.07 - 1.10 x the mean).  Equal slot weight per eighth, heavy pixels first, ball order kept inside a weight class.  Every output element keeps its
+    // K order: the result does not depend on which order is walked.  Tuning::no_deal keeps the ball order (parity tests' side-by-side, A/B timing).
+    std::vector<int32_t> pix_deal = h->h_pix_order;
+    if (!c.tune.no_deal) {
+        std::vector<int32_t> weight((size_t)HoWo);
+        for (int64_t o = 0; o < HoWo; o++) weight[(size_t)o] = pix_ptr[(size_t)o + 1] - pix_ptr[(size_t)o];
+        pix_deal = deal_order(h->h_pix_order, weight);
+#ifdef KN_ABLATION
+        if (getenv("KN_STAMPS"))       // diagnostic build, next to the workgroup timeline: what the dealing changed for this operator
+            fprintf(stderr, "[kn_deal] %lld pixels, slot weight per XCD segment max/mean %.4f -> %.4f\n", (long long)HoWo, deal_imbalance(h->h_pix_order, weight), deal_imbalance(pix_deal, weight));
+#endif
+    }
     std::vector<float> lastcol;
     if (c.has_last) {
         lastcol.assign((size_t)rows, 0.0f);
@@ -407,7 +422,7 @@ static int convtaps_create_impl(ConvBuild& b, kn_operator** out) {
     if ((!sk_desc.empty() && (rc = upload(&c.sk_desc, sk_desc.data(), sk_desc.size()))) || (rc = upload(&c.tapsT, tapsT.data(), tapsT.size())) || (rc = upload(&c.pix_ptr, pix_ptr.data(), pix_ptr.size())) ||
         (rc = upload(&c.slot_in, slot_in.data(), slot_in.size())) || (rc = upload(&c.slot_tap, slot_tap.data(), slot_tap.size())) ||
         (rc = upload(&c.slot_coef, slot_coef.data(), slot_coef.size())) || (rc = upload(&c.pix_order, h->h_pix_order.data(), h->h_pix_order.size())) ||
-        (rc = upload(&c.lastcol, lastcol.data(), lastcol.size())) || (!fill_ptr.empty() && (rc = upload(&c.fill_ptr, fill_ptr.data(), fill_ptr.size()))))
+        (rc = upload(&c.pix_deal, pix_deal.data(), pix_deal.size())) || (rc = upload(&c.lastcol, lastcol.data(), lastcol.size())) || (!fill_ptr.empty() && (rc = upload(&c.fill_ptr, fill_ptr.data(), fill_ptr.size()))))
         return rc;
     *out = h.release();
     return KN_OK;

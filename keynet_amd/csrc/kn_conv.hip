@@ -2236,7 +2236,7 @@ __global__ __launch_bounds__(256) void conv_lastrow_kernel(const float* __restri
 }
 
 void convtaps_free(ConvTapsDev& c) {
-    void* ptrs[] = {c.tapsT, c.pix_ptr, c.slot_in, c.slot_tap, c.slot_coef, c.pix_order, c.lastcol, c.sk_desc, c.tapsB, c.zero_ent, c.ex_ptr, c.ex_tab, c.ex_order, c.fill_ptr, c.fill_rec, c.pt_rec};
+    void* ptrs[] = {c.tapsT, c.pix_ptr, c.slot_in, c.slot_tap, c.slot_coef, c.pix_order, c.pix_deal, c.lastcol, c.sk_desc, c.tapsB, c.zero_ent, c.ex_ptr, c.ex_tab, c.ex_order, c.fill_ptr, c.fill_rec, c.pt_rec};
     for (void* q : ptrs)
         if (q) (void)hipFree(q);
     c = ConvTapsDev();
@@ -2875,6 +2875,9 @@ static int spmm_mfma(const ConvTapsDev& A, ConvArgs& a, const MfmaChoice& c, hip
     a.n_mt = c.n_mt;
     a.n_bt = c.n_bt;
     a.tail_main = c.tail_main;
+    // the two kernels that cut the item list into one contiguous chunk per XCD walk the order dealt for that (ConvTapsDev::pix_deal, kn_deal.h); the small-K kernels keep
+    // the locality order their descriptors were laid out in
+    if (c.kernel == MfmaChoice::TILE || c.kernel == MfmaChoice::BF16X3) a.pix_order = A.pix_deal;
     if (c.kernel == MfmaChoice::BF16X3) {
         a.tapsB = A.tapsB;
         a.tapsB_plane = A.tapsB_plane;

@@ -176,6 +176,7 @@ PlanSink*& plan_sink();   // thread-local; null outside kn_spmm_plan
     X(table_nrb, "KN_TABLE_NRB", 0, false)           /* =1|2|3     32-channel blocks per workgroup of the table kernel (0: the rule) */ \
     X(no_fill_exact, "KN_NO_FILL_EXACT", 0, false)   /* =1         filled-in conv operators (> 64 slots per pixel, or several slots on one (output, input) pixel pair) under KN_FLAG_EXACT: the generic kernel instead of convtaps_exact_fill_kernel */ \
     X(no_fill_tiles2, "KN_NO_FILL_TILES2", 0, false) /* =1         ... on batches of whole 128-column tiles: one 64-column tile per wavefront instead of two */ \
+    X(no_deal, "KN_NO_DEAL", 0, false)               /* =1         conv-taps matrix-core kernels: the XCD chunks cut from the locality order itself instead of the slot-balanced, heavy-first dealing order (kn_deal.h) */ \
     /* ---- diagnostic build only ---- */ \
     X(occ, "KN_OCC", 0, true)                        /* workgroups per CU cap of the 128 x 128 conv-taps launch (0: the rule) */ \
     X(no_tail_split, "KN_NO_TAIL_SPLIT", 0, true) \
@@ -307,6 +308,7 @@ struct ConvTapsDev {
     int32_t* slot_tap = nullptr;        // [nslots]
     float* slot_coef = nullptr;         // [nslots]
     int32_t* pix_order = nullptr;       // [HoWo] processing order of output pixels (locality)
+    int32_t* pix_deal = nullptr;        // [HoWo] the same order dealt to the 8 XCDs by slot weight, heavy pixels first (kn_deal.h): what the kernels that cut per-XCD chunks walk
     float* lastcol = nullptr;           // [Cout*HoWo+1] or null
     bool has_last = false;
     bool unit_coef = true;
