@@ -333,6 +333,22 @@ int kn_affine_to_linear(const float* x_dev, int64_t n, int64_t d, float* out_dev
  * *maxdev_dev (device float, may be NULL) receives max_b |y[d, b] - 1| so the host can raise ValueError when > 1e-3. */
 int kn_linear_to_affine(const float* y_dev, int64_t ldy, int64_t n, int64_t d, float* out_dev, float* maxdev_dev, void* stream);
 
+/* Planes <-> columns of a narrow batch.  No reference counterpart: the reference applies the fused operator (keynet/sparse.py:603-612), at one image
+ * (keynet/system.py:130-133).  They serve the narrow split route of a FILLED-IN conv (keynet_amd/sparse.py, Conv2dTiledMatrix._torchdot_split_narrow; the opt-in keyword
+ * narrow_split=True of the low-latency forward at 1 .. 32 images): with so few images the input-channel planes ARE the batch of the spatial matrix, so the activation block
+ * X [Cin x HiWi, n] is laid out as Xt [HiWi, Cin x n], ONE kn_spmm of the spatial CSR runs at n_vecs = Cin x n (64 .. 16 384 columns, the width the CSR kernels are built
+ * for, where kn_spmm_planes at n columns uses n lanes in 64), and its result goes back to planes for the channel-mixing conv-taps operator.
+ *   kn_planes_to_columns:  in[p][r][b]  at in_dev + p * plane_stride + r * ld + b     ->   out[r][(p, b)] at out_dev + r * ld_out + p * n_vecs + b
+ *   kn_columns_to_planes:  in[r][(p, b)] at in_dev + r * ld_in + p * n_vecs + b        ->   out[p][r][b]  at out_dev + p * plane_stride + r * ld + b
+ * for p < n_planes, r < rows, b < n_vecs.  Pure data movement (no arithmetic: NaN payloads and -0 pass through); elements outside the written windows are untouched;
+ * every address is formed in 64 bits (a plane may begin beyond 2^31 elements).  1 <= n_vecs <= 32 (KN_ERR_UNSUPPORTED beyond: not a narrow batch), any n_planes and rows,
+ * any ld >= n_vecs, ld_in / ld_out >= n_planes * n_vecs, plane_stride >= (rows - 1) * ld + n_vecs (KN_ERR_SHAPE otherwise).  Tiled through LDS: 16 bytes per lane on a side
+ * whose base and strides are multiples of four floats (the planes side also needs ld == n_vecs or n_vecs % 4 == 0), one float per lane otherwise.
+ * ABI: entry points ADDED to the library leave KN_ABI_VERSION where it is -- the number moves when something a caller of the previous version relies on changes (a
+ * signature, the meaning of a flag or of an argument); a binding that needs a newer entry point than a stale library has fails to resolve the symbol when it loads it. */
+int kn_planes_to_columns(const float* in_dev, int64_t plane_stride, int64_t ld, int64_t n_planes, int64_t rows, int64_t n_vecs, float* out_dev, int64_t ld_out, void* stream);
+int kn_columns_to_planes(const float* in_dev, int64_t ld_in, int64_t n_planes, int64_t rows, int64_t n_vecs, float* out_dev, int64_t plane_stride, int64_t ld, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

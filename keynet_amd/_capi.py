@@ -28,7 +28,7 @@ KN_ABI_VERSION = 5
 # every symbol include/keynet_hip.h declares (tests/test_capi.py checks the header against this list)
 SYMBOLS = ['kn_abi_version', 'kn_last_error', 'kn_device_info', 'kn_csr_create', 'kn_csr_create_f64', 'kn_dtype_bits', 'kn_export_csr_f64', 'kn_spmm_f64', 'kn_tiled_create', 'kn_conv2dtiled_create',
            'kn_convtaps_create', 'kn_convtaps_drop_zero_entries', 'kn_dense_create', 'kn_chain_create', 'kn_destroy', 'kn_nnz', 'kn_nnz_expanded', 'kn_shape', 'kn_export_csr', 'kn_spmm', 'kn_spmm_planes', 'kn_spmm_screen', 'kn_absmax', 'kn_reserve_workspace', 'kn_release_side_tables', 'kn_spmm_plan', 'kn_relu',
-           'kn_affine_to_linear', 'kn_linear_to_affine']
+           'kn_affine_to_linear', 'kn_linear_to_affine', 'kn_planes_to_columns', 'kn_columns_to_planes']
 
 
 class KeynetHipError(RuntimeError):
@@ -85,6 +85,8 @@ def lib():
         L.kn_relu.argtypes = [p, i64, i64, i64, p]
         L.kn_affine_to_linear.argtypes = [p, i64, i64, p, i64, p]
         L.kn_linear_to_affine.argtypes = [p, i64, i64, i64, p, p, p]
+        L.kn_planes_to_columns.argtypes = [p, i64, i64, i64, i64, i64, p, i64, p]
+        L.kn_columns_to_planes.argtypes = [p, i64, i64, i64, i64, p, i64, i64, p]
         for s in SYMBOLS:
             if s not in ('kn_last_error',):
                 getattr(L, s).restype = ci
@@ -289,3 +291,13 @@ def affine_to_linear(x_ptr, n, d, out_ptr, ldo, stream):
 
 def linear_to_affine(y_ptr, ldy, n, d, out_ptr, maxdev_ptr, stream):
     check(lib().kn_linear_to_affine(y_ptr, int(ldy), int(n), int(d), out_ptr, maxdev_ptr, stream))
+
+
+def planes_to_columns(in_ptr, plane_stride, ld, n_planes, rows, n_vecs, out_ptr, ld_out, stream):
+    """kn_planes_to_columns: in[p][r][b] (p * plane_stride + r * ld + b) -> out[r][(p, b)] (r * ld_out + p * n_vecs + b); n_vecs <= 32."""
+    check(lib().kn_planes_to_columns(in_ptr, int(plane_stride), int(ld), int(n_planes), int(rows), int(n_vecs), out_ptr, int(ld_out), stream))
+
+
+def columns_to_planes(in_ptr, ld_in, n_planes, rows, n_vecs, out_ptr, plane_stride, ld, stream):
+    """kn_columns_to_planes: in[r][(p, b)] (r * ld_in + p * n_vecs + b) -> out[p][r][b] (p * plane_stride + r * ld + b); the inverse of planes_to_columns."""
+    check(lib().kn_columns_to_planes(in_ptr, int(ld_in), int(n_planes), int(rows), int(n_vecs), out_ptr, int(plane_stride), int(ld), stream))

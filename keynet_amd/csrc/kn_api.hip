@@ -1131,4 +1131,31 @@ int kn_linear_to_affine(const float* y_dev, int64_t ldy, int64_t n, int64_t d, f
     });
 }
 
+// what both directions of the planes <-> columns permute require of their arguments (nothing is refused for its width or plane count inside 1 .. 32 columns)
+static int permute_args(const float* in_dev, const float* out_dev, int64_t plane_stride, int64_t ld, int64_t n_planes, int64_t rows, int64_t n_vecs, int64_t ld_cols) {
+    KN_REQUIRE(n_planes >= 0 && rows >= 0 && n_vecs >= 0, KN_ERR_INVALID, "negative size");
+    KN_REQUIRE(n_vecs <= 32, KN_ERR_UNSUPPORTED, "planes <-> columns is the layout change of a narrow batch: at most 32 columns per plane");
+    KN_REQUIRE((in_dev && out_dev) || n_planes * rows * n_vecs == 0, KN_ERR_INVALID, "NULL pointer");
+    KN_REQUIRE(ld >= n_vecs, KN_ERR_SHAPE, "leading dimension smaller than n_vecs");
+    KN_REQUIRE(n_planes == 0 || ld_cols / n_planes >= n_vecs, KN_ERR_SHAPE, "leading dimension of the column block smaller than n_planes * n_vecs");
+    KN_REQUIRE(n_planes <= 1 || rows == 0 || n_vecs == 0 || (plane_stride - n_vecs) / ld >= rows - 1, KN_ERR_SHAPE, "planes overlap: plane_stride smaller than (rows - 1) * ld + n_vecs");
+    return KN_OK;
+}
+
+int kn_planes_to_columns(const float* in_dev, int64_t plane_stride, int64_t ld, int64_t n_planes, int64_t rows, int64_t n_vecs, float* out_dev, int64_t ld_out, void* stream) {
+    return guarded([&]() -> int {
+    KN_HOST_ONLY_GUARD();
+    if (int rc = permute_args(in_dev, out_dev, plane_stride, ld, n_planes, rows, n_vecs, ld_out)) return rc;
+    return planes_to_columns(in_dev, plane_stride, ld, n_planes, rows, n_vecs, out_dev, ld_out, reinterpret_cast<hipStream_t>(stream));
+    });
+}
+
+int kn_columns_to_planes(const float* in_dev, int64_t ld_in, int64_t n_planes, int64_t rows, int64_t n_vecs, float* out_dev, int64_t plane_stride, int64_t ld, void* stream) {
+    return guarded([&]() -> int {
+    KN_HOST_ONLY_GUARD();
+    if (int rc = permute_args(in_dev, out_dev, plane_stride, ld, n_planes, rows, n_vecs, ld_in)) return rc;
+    return columns_to_planes(in_dev, ld_in, n_planes, rows, n_vecs, out_dev, plane_stride, ld, reinterpret_cast<hipStream_t>(stream));
+    });
+}
+
 }  // extern "C"

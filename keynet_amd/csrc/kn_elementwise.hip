@@ -2,6 +2,7 @@
 //   relu_inplace        nn.ReLU over [rows, n_vecs] incl. the homogeneous row (keynet/system.py:92) when it cannot be fused
 //   affine_to_linear    keynet/torch.py:65-68 + the x.t() of keynet/layer.py:92: [n, d] images -> [d+1, n] feature-major
 //   linear_to_affine    keynet/torch.py:71-77: [d+1, n] -> [n, d], plus max |last row - 1| for the host-side ValueError
+//   planes_to_columns / columns_to_planes   the two layout changes around the spatial CSR of the narrow split route (no reference counterpart)
 // Transposes go through a padded 64x65 LDS tile so both the global read and the global write are coalesced.
 #include "kn_internal.h"
 
@@ -183,6 +184,113 @@ int absmax_pass(const float* y, int64_t rows, int64_t ld, int64_t n_vecs, float*
     }
     KN_HIP(hipGetLastError());
     return KN_OK;
+}
+
+// Planes <-> columns of a narrow batch (kn_planes_to_columns / kn_columns_to_planes; the narrow split route of keynet_amd/sparse.py).
+//   planes side   Pl[p][r][b] at pl + p * ps + r * ldp + b      (p < planes, r < rows, b < nv <= 32)
+//   columns side  Co[r][(p, b)] at co + r * ldc + p * nv + b
+// A transpose of the planes x rows matrix of nv-float elements: one workgroup moves a tile of T planes x T rows through LDS, so that it walks the planes side along
+// r (contiguous where ldp == nv) and the columns side along (p, b) (always contiguous).  T = 64 | 32 | 16 for nv <= 2 | 8 | 32: segments of 64 .. 512 floats on either
+// side.  In LDS plane pl of the tile starts at pl * sp with sp = T * nv + pad = nv (mod 64): the columns side, whose consecutive lanes step to the next plane every nv
+// elements, then reads bank (element index mod 64) -- without the pad every plane would start in the same bank (nv = 1: all 64 lanes in one).  A lane moves 16 bytes
+// of global memory per access where its side is aligned (`vec`: the host's rule below) and one float otherwise; LDS is accessed float by float (a 16-byte lane's four
+// accesses meet those of three other lanes in a bank: LDS at a quarter of its rate is still ahead of HBM).  No arithmetic: bits pass through.
+constexpr int PERMUTE_LDS_FLOATS = 10240;      // >= T * sp for every nv (T = 32, nv = 8: 32 * (256 + 63))
+
+// one side of the tile: GLOBAL -> LDS (LOAD) or LDS -> GLOBAL.  `segs` segments of `len` valid floats; element e of segment s lives in global memory at
+// g + s * gseg + (e / run) * grun + e % run (runs of `run` contiguous floats `grun` apart; run == len-or-more: one contiguous segment) and in LDS at
+// tile[lds_of(s, e)].  G = 4: 16-byte global accesses on whole quads (the caller guarantees their alignment and that a quad never straddles a run), floats on a ragged tail.
+template <bool LOAD, int G, typename LdsOf>
+__device__ __forceinline__ void permute_side(float* __restrict__ tile, const float* __restrict__ gsrc, float* __restrict__ gdst, int64_t gseg, int64_t grun, int run, int segs,
+                                             int len, LdsOf lds_of) {
+    const int per = (len + G - 1) / G;
+    for (int i = (int)threadIdx.x; i < segs * per; i += 256) {
+        const int sg = i / per;
+        const int e = (i - sg * per) * G;
+        const int k = e / run;
+        const int64_t at = (int64_t)sg * gseg + (int64_t)k * grun + (e - k * run);
+        if (G == 4 && e + 4 <= len) {
+            if (LOAD) {
+                const float4 v = *reinterpret_cast<const float4*>(gsrc + at);
+                tile[lds_of(sg, e)] = v.x;
+                tile[lds_of(sg, e + 1)] = v.y;
+                tile[lds_of(sg, e + 2)] = v.z;
+                tile[lds_of(sg, e + 3)] = v.w;
+            } else {
+                float4 v;
+                v.x = tile[lds_of(sg, e)];
+                v.y = tile[lds_of(sg, e + 1)];
+                v.z = tile[lds_of(sg, e + 2)];
+                v.w = tile[lds_of(sg, e + 3)];
+                *reinterpret_cast<float4*>(gdst + at) = v;
+            }
+        } else {
+            for (int j = 0; j < G && e + j < len; j++) {
+                const int kj = (e + j) / run;
+                const int64_t aj = (int64_t)sg * gseg + (int64_t)kj * grun + (e + j - kj * run);
+                if (LOAD) tile[lds_of(sg, e + j)] = gsrc[aj];
+                else gdst[aj] = tile[lds_of(sg, e + j)];
+            }
+        }
+    }
+}
+
+template <bool TO_COLUMNS, int GP, int GC>
+__global__ __launch_bounds__(256) void planes_columns_kernel(const float* __restrict__ src, float* __restrict__ dst, int64_t planes, int64_t rows, int nv, int64_t ps,
+                                                             int64_t ldp, int64_t ldc, int T, int sp) {
+    __shared__ float tile[PERMUTE_LDS_FLOATS];
+    const int64_t r0 = (int64_t)blockIdx.x * T, p0 = (int64_t)blockIdx.y * T;
+    const int tr = (rows - r0 < T) ? (int)(rows - r0) : T, tp = (planes - p0 < T) ? (int)(planes - p0) : T;
+    const int64_t pl_at = p0 * ps + r0 * ldp;            // the tile's corner on either side (64 bits: a plane may begin beyond 2^31 elements)
+    const int64_t co_at = r0 * ldc + p0 * nv;
+    // planes side: segment = a plane of the tile, tr rows of nv floats, ldp apart (one contiguous run where ldp == nv); LDS: pl * sp + e
+    auto lds_pl = [sp](int pl, int e) { return pl * sp + e; };
+    // columns side: segment = a row of the tile, tp * nv contiguous floats; LDS: element o = (pl, b) of row rl at pl * sp + rl * nv + b
+    auto lds_co = [sp, nv](int rl, int o) { const int pl = o / nv; return pl * sp + rl * nv + (o - pl * nv); };
+    const int prun = (ldp == nv) ? tr * nv : nv;
+    if (TO_COLUMNS) {
+        permute_side<true, GP>(tile, src + pl_at, nullptr, ps, ldp, prun, tp, tr * nv, lds_pl);
+        __syncthreads();
+        permute_side<false, GC>(tile, nullptr, dst + co_at, ldc, 0, tp * nv, tr, tp * nv, lds_co);
+    } else {
+        permute_side<true, GC>(tile, src + co_at, nullptr, ldc, 0, tp * nv, tr, tp * nv, lds_co);
+        __syncthreads();
+        permute_side<false, GP>(tile, nullptr, dst + pl_at, ps, ldp, prun, tp, tr * nv, lds_pl);
+    }
+}
+
+template <bool TO_COLUMNS>
+static int planes_columns(const float* src, float* dst, const float* pl, const float* co, int64_t planes, int64_t rows, int64_t nv, int64_t ps, int64_t ldp, int64_t ldc,
+                          hipStream_t s) {
+    if (planes <= 0 || rows <= 0 || nv <= 0) return KN_OK;
+    const int T = nv <= 2 ? 64 : (nv <= 8 ? 32 : 16);
+    const int sp = T * (int)nv + (int)((((nv - T * nv) % 64) + 64) % 64);
+    if ((int64_t)T * sp > PERMUTE_LDS_FLOATS) return fail(KN_ERR_UNSUPPORTED, "planes <-> columns: the tile does not fit the LDS array");
+    // 16 bytes per lane on a side: its base and every stride a multiple of four floats (tile corners are: T % 4 == 0), and quads that stay inside a contiguous run --
+    // the planes side where rows follow each other without a gap (ldp == nv) or a row is whole quads; the columns side always (a ragged end moves float by float)
+    const bool vp = ((uintptr_t)pl) % 16 == 0 && (ps % 4 == 0 || planes == 1) && (ldp == nv || (nv % 4 == 0 && ldp % 4 == 0));
+    const bool vc = ((uintptr_t)co) % 16 == 0 && ldc % 4 == 0;
+    const int64_t ymax = 65535;                          // planes beyond 65 535 tiles: further launches
+    for (int64_t pt = 0; pt * T < planes; pt += ymax) {
+        const int64_t np = std::min<int64_t>(planes - pt * T, ymax * T);
+        const dim3 grid((unsigned)((rows + T - 1) / T), (unsigned)((np + T - 1) / T));
+        const float* sp_ = src + (TO_COLUMNS ? pt * T * ps : pt * T * nv);
+        float* dp_ = dst + (TO_COLUMNS ? pt * T * nv : pt * T * ps);
+        if (vp && vc) hipLaunchKernelGGL((planes_columns_kernel<TO_COLUMNS, 4, 4>), grid, dim3(256), 0, s, sp_, dp_, np, rows, (int)nv, ps, ldp, ldc, T, sp);
+        else if (vp) hipLaunchKernelGGL((planes_columns_kernel<TO_COLUMNS, 4, 1>), grid, dim3(256), 0, s, sp_, dp_, np, rows, (int)nv, ps, ldp, ldc, T, sp);
+        else if (vc) hipLaunchKernelGGL((planes_columns_kernel<TO_COLUMNS, 1, 4>), grid, dim3(256), 0, s, sp_, dp_, np, rows, (int)nv, ps, ldp, ldc, T, sp);
+        else hipLaunchKernelGGL((planes_columns_kernel<TO_COLUMNS, 1, 1>), grid, dim3(256), 0, s, sp_, dp_, np, rows, (int)nv, ps, ldp, ldc, T, sp);
+    }
+    KN_HIP(hipGetLastError());
+    return KN_OK;
+}
+
+int planes_to_columns(const float* in, int64_t plane_stride, int64_t ld, int64_t planes, int64_t rows, int64_t n_vecs, float* out, int64_t ld_out, hipStream_t s) {
+    return planes_columns<true>(in, out, in, out, planes, rows, n_vecs, plane_stride, ld, ld_out, s);
+}
+
+int columns_to_planes(const float* in, int64_t ld_in, int64_t planes, int64_t rows, int64_t n_vecs, float* out, int64_t plane_stride, int64_t ld, hipStream_t s) {
+    return planes_columns<false>(in, out, out, in, planes, rows, n_vecs, plane_stride, ld, ld_in, s);
 }
 
 int linear_to_affine(const float* y, int64_t ldy, int64_t n, int64_t d, float* out, float* maxdev, hipStream_t s) {

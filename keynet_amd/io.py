@@ -17,7 +17,8 @@ Schema (also the schema of tests/golden/*.npz, written by tests/golden/make_gold
     L.<name>.contract_record         (save_keynet only) JSON of the calibration record behind a decided 'auto' layer (measured difference,
                                      tolerance, the max |x| the decision covers): a loaded key-net keeps re-screening against it.  The record of a
                                      layer's narrow='mfma' measurement rides inside it (key 'narrow': KeyedLayer.narrow_mode), so a loaded key-net
-                                     keeps that decision and its screen too
+                                     keeps that decision and its screen too; likewise the record of a narrow_split=True measurement (key
+                                     'narrow_split': KeyedLayer.narrow_split_mode)
     outshape                         (C,1,1) of the logits
     sensor.*                         (optional) the image key pair as stored-order CSR + 'sensor.inshape'
 

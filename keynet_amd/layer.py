@@ -209,7 +209,7 @@ class KeyedLayer(nn.Module):
     def iskeyedrelu(self):
         return 'ReLU' in self._layertype
 
-    def forward(self, x_affine, fuse_relu=False, absmax=None, narrow=False, narrow_rows=False, narrow32=False, narrow64=False, narrow_linear=False):
+    def forward(self, x_affine, fuse_relu=False, absmax=None, narrow=False, narrow_rows=False, narrow32=False, narrow64=False, narrow_linear=False, narrow_split=False):
         """[N, Din+1] -> [N, Dout+1] (keynet/layer.py:88-93).  The result is a transposed view of the feature-major
         [Dout+1, N] block the kernel wrote, so the next layer's x.t() is free.  `fuse_relu` folds the unkeyed nn.ReLU
         that follows this layer in the key-net (keynet/system.py:92) into the kernel epilogue.  `absmax`: a one-element device
@@ -217,11 +217,13 @@ class KeyedLayer(nn.Module):
         A layer whose contract is still 'auto' decides it here, on this batch (blocking host reads, an extra order-preserving launch:
         not capturable into a HIP graph -- KeyedModel.capture runs an eager forward first).
         `narrow`, `narrow_rows`, `narrow32`, `narrow64`, `narrow_linear` (narrow='mfma', narrow64='mfma' included): this layer of KeyedModel.forward_linear's narrow forms, as
-        narrowed() decides it on this batch -- with `narrow` nothing is calibrated, and only narrow='mfma' on a calibrated layer measures and records (narrow_mode())."""
+        narrowed() decides it on this batch -- with `narrow` nothing is calibrated, and only narrow='mfma' on a calibrated layer measures and records (narrow_mode()).
+        `narrow_split` (only with narrow='mfma'): a filled-in conv layer under 'split' runs the narrow split route where narrow_split_mode() allows it; a calibrated one measures
+        and records that under its own key first.  Every other layer, and this one beyond NARROW32_MAX images, is what it is without the keyword."""
         if verbose():
             print('[keynet_amd.layer]: forward %s' % str(self))
         (xt, relu) = (x_affine.t(), fuse_relu or self.iskeyedrelu())
-        (exact, keywords) = self.narrowed(ksp.NarrowForm.of(None, narrow, narrow_rows, narrow32, narrow64, narrow_linear), xt, relu)
+        (exact, keywords) = self.narrowed(ksp.NarrowForm.of(None, narrow, narrow_rows, narrow32, narrow64, narrow_linear, narrow_split=narrow_split), xt, relu)
         if exact == 'auto' and not narrow:
             if x_affine.is_cuda and torch.cuda.is_current_stream_capturing():
                 raise _capi.KeynetHipError('keynet_amd: %s has not decided its arithmetic contract yet (exact=\'auto\' calibrates on the first batch, with host reads): '
@@ -239,7 +241,8 @@ class KeyedLayer(nn.Module):
         conv operator under False / 'bf16x3' takes it -- the wide kernel's association, covered by the wide decision: narrow_mode() is not consulted -- and everything else is what
         narrow=True, narrow64=True makes it; otherwise narrow='mfma' is narrow_mode()'s answer for this layer, measured on `xt` where a calibrated layer has no narrow record yet
         (a planner gets the channel-lane kernel).  Any other operator: `narrow_rows` / `narrow_linear` where it is a float32 CSR handle (W.rows_capable()), and a layer still
-        'auto' runs in the reference's order for this call (to a planner it stays 'auto': not one launch)."""
+        'auto' runs in the reference's order for this call (to a planner it stays 'auto': not one launch).  `form.split` (narrow_split=True): ahead of narrow_mode(), a layer
+        narrow_split_mode() puts on the narrow split route gets narrow='mfma', narrow_split=True (to a planner: not one launch); any other layer is what it is without it."""
         (W, exact) = (self.W, getattr(self, '_exact', True))
         if not form.mode:
             return (exact, {})
@@ -247,13 +250,15 @@ class KeyedLayer(nn.Module):
             if form.tile64 and (xt is None or xt.shape[1] > ksp.NARROW32_MAX):
                 mode = 'mfma' if isinstance(W, ksp.Conv2dTiledMatrix) and exact in (False, 'bf16x3') else True
                 return (exact, dict(narrow=mode, narrow32=True, narrow64=mode))
+            if form.split and self.narrow_split_mode(xt, relu):
+                return (exact, dict(narrow='mfma', narrow32=form.narrow32, narrow64=form.narrow64, narrow_split=True))
             return (exact, dict(narrow=self.narrow_mode('mfma', xt, relu) if form.mode == 'mfma' else True, narrow32=form.narrow32, narrow64=form.narrow64))
         if exact == 'auto' and xt is not None:
             exact = True
         return (exact, dict(narrow_rows=form.rows, narrow_linear=form.linear) if (form.rows or form.linear) and W.rows_capable() else {})
 
     @staticmethod
-    def kernel(W, contract, relu, device=None, narrow=False, narrow_rows=False, narrow32=False, narrow64=False, narrow_linear=False):
+    def kernel(W, contract, relu, device=None, narrow=False, narrow_rows=False, narrow32=False, narrow64=False, narrow_linear=False, narrow_split=False):
         """The one place that turns a decided contract into an operator handle and flags: (get_op, flags) of the kn_spmm launch that applies operator `W`
         under `contract`, get_op(device) -> the handle resident there.  None when that is not one launch: 'auto' (still to calibrate), 'split' on an operator that has a split form (Conv2dTiledMatrix._torchdot_split).
         The rules: 'split' forced on an operator without a split form, and 'bf16x3' on a non-conv operator, are the f32 matrix cores (False); a conv operator
@@ -269,9 +274,14 @@ class KeyedLayer(nn.Module):
         and for every other operator, exactly narrow=True.  (Whether a CALIBRATED layer may pass 'mfma' here is narrow_mode()'s decision.)  With narrow64='mfma' a conv
         operator under False / 'bf16x3' adds KN_FLAG_NARROW64_MFMA (the 64-column tile at 33 .. 64 columns; the library ignores the bit below); every other case is narrow64=True.
         `narrow_rows`, `narrow_linear`: KN_FLAG_NARROW_ROWS, KN_FLAG_NARROW_LINEAR on an operator that runs in the stored order on its own float32 CSR handle
-        (W.rows_capable(); not a float64 operator, not a SparseMatrix a re-ordering contract put on its dense handle, not a conv-taps operator), `narrow` or not."""
-        form = ksp.NarrowForm.of(None, narrow, narrow_rows, narrow32, narrow64, narrow_linear)
+        (W.rows_capable(); not a float64 operator, not a SparseMatrix a re-ordering contract put on its dense handle, not a conv-taps operator), `narrow` or not.
+        `narrow_split` (with narrow='mfma'): a conv operator with a split form under 'split' is NOT one launch (None) -- the narrow split route of up to NARROW32_MAX columns,
+        Conv2dTiledMatrix._torchdot_split_narrow, which the operator's torchdot takes where narrow_split_route() offers it at the batch's width, asking again without the
+        keyword where not; on every other operator and contract the keyword adds nothing."""
+        form = ksp.NarrowForm.of(None, narrow, narrow_rows, narrow32, narrow64, narrow_linear, narrow_split=narrow_split)
         conv = isinstance(W, ksp.Conv2dTiledMatrix)
+        if form.split and conv and contract == 'split' and W.narrow_capable() and W.split_capable():
+            return None
         lane = bool(form.mode) and W.narrow_capable()       # one launch of a narrow conv kernel, whatever the contract
         mfma = lane and form.mode == 'mfma' and conv and contract in (False, 'bf16x3', 'split')      # (the library falls back to the channel-lane kernel on an ineligible operator)
         if not lane:
@@ -290,14 +300,15 @@ class KeyedLayer(nn.Module):
                 (_capi.KN_FLAG_NARROW64_MFMA if mfma and form.tile64 and contract in (False, 'bf16x3') else 0) |
                 (_capi.KN_FLAG_NARROW_ROWS if form.rows and stored else 0) | (_capi.KN_FLAG_NARROW_LINEAR if form.linear and stored else 0))
 
-    def launch(self, device, relu=False, narrow=False, narrow_rows=False, narrow32=False, narrow64=False, narrow_linear=False):
+    def launch(self, device, relu=False, narrow=False, narrow_rows=False, narrow32=False, narrow64=False, narrow_linear=False, narrow_split=False):
         """This layer under its contract in force as one launch on `device` (`relu`: the unkeyed nn.ReLU behind it is fused in), or None when it is not one
         kn_spmm launch: see kernel(); a float64 operator (its own kernel and a float64 result: kn_spmm_f64).  What the key-net's planners read
         (KeyedModel._chain_op / _overlap_plan); forward() -> W.torchdot() runs the same rule.  `narrow`, `narrow_rows`, `narrow32`, `narrow64`, `narrow_linear`: the launch
         forward() issues under them (narrowed(); without `narrow` the others say nothing), except that a planner has no batch: a layer still 'auto' is not one launch,
-        narrow='mfma' on a calibrated layer without a narrow record answers the channel-lane kernel, and narrow64='mfma' asks for the launch of 33 .. 64 columns."""
+        narrow='mfma' on a calibrated layer without a narrow record answers the channel-lane kernel, and narrow64='mfma' asks for the launch of 33 .. 64 columns.  `narrow_split`: a layer
+        on the narrow split route (declared 'split', or an accepted narrow_split record) is not one launch; one still to measure answers what it answers without the keyword."""
         W = self.W
-        (exact, keywords) = self.narrowed(ksp.NarrowForm.of(None, narrow, narrow_rows, narrow32, narrow64, narrow_linear))
+        (exact, keywords) = self.narrowed(ksp.NarrowForm.of(None, narrow, narrow_rows, narrow32, narrow64, narrow_linear, narrow_split=narrow_split))
         kernel = None if W.is_float64() else self.kernel(W, exact, relu or self.iskeyedrelu(), device, **keywords)
         if kernel is None:
             return None
@@ -314,9 +325,14 @@ class KeyedLayer(nn.Module):
         rec = getattr(self, '_contract_record', None)
         return getattr(self, '_exact', True) in (False, 'bf16x3', 'split') and rec is not None and rec.get('max_abs_x') is not None
 
+    def _screen_key(self, narrow):
+        """Where the record a narrow forward screens sits inside the calibration record: 'narrow', or under narrow='split' (a narrow_split=True forward) 'narrow_split' for a layer
+        that forward runs on the narrow split route by a measurement (narrow_split_screened(): narrowed() asks for the route first)."""
+        return 'narrow_split' if narrow == 'split' and self.narrow_split_screened() else 'narrow'
+
     def screen_record(self, narrow=False):
-        """The record whose max_abs_x a forward screens: the calibration record, or under `narrow` the narrow record inside it (narrow_record())."""
-        return self._contract_record['narrow'] if narrow else self._contract_record
+        """The record whose max_abs_x a forward screens: the calibration record, or under `narrow` the narrow record inside it (narrow_record(); narrow='split': _screen_key)."""
+        return self._contract_record[self._screen_key(narrow)] if narrow else self._contract_record
 
     def rescreen(self, xmax, narrow=False):
         """max |x| of a later batch against the calibrated one: True = the decision does not cover this batch (re-calibrate).  The measured
@@ -332,7 +348,7 @@ class KeyedLayer(nn.Module):
         """Drop the record a screen has outgrown: the layer is 'auto' again (decided by the next forward, on that batch); under `narrow` only the narrow
         record goes (measured again by the next narrow='mfma' pass) and the wide decision stays."""
         if narrow:
-            self._contract_record.pop('narrow', None)
+            self._contract_record.pop(self._screen_key(narrow), None)       # (narrow='split': only the narrow_split record of a layer on that route)
         else:
             self._exact = 'auto'
             self.__dict__.pop('_contract_record', None)
@@ -408,6 +424,72 @@ class KeyedLayer(nn.Module):
         if not ok:
             _log.warning('keynet_amd: %s keeps the channel-lane kernel on narrow forwards: matrix-core narrow result off by %.3g where the tolerance is %.3g', self._repr, measured, tol)
         return dict(layer=self._repr, decided='mfma' if ok else 'exact', measured_narrow_mfma_vs_exact=measured, tol=tol, bound=bound, gate_ratio=ratio, max_abs_diff=dmax,
+                    max_abs_x=xmax, measured_on_columns=n)
+
+    # -- narrow_split=True: the narrow split route of a filled-in conv layer under 'split' ---------------------------------------------------
+    def narrow_split_record(self):
+        """The record of this layer's narrow_split measurement (a layer calibration decided 'split' only), or None."""
+        rec = getattr(self, '_contract_record', None)
+        return None if rec is None else rec.get('narrow_split')
+
+    def narrow_split_screened(self):
+        """Does a narrow_split=True forward run this layer on the narrow split route BY A MEASUREMENT (then it re-screens max |x| against that record)?"""
+        rec = self.narrow_split_record()
+        return self.screened() and rec is not None and rec.get('decided') == 'split' and rec.get('max_abs_x') is not None
+
+    def narrow_split_mode(self, xt=None, relu=False):
+        """Does a narrow='mfma', narrow_split=True forward run this layer on the narrow split route (Conv2dTiledMatrix._torchdot_split_narrow) now?  Only a conv-taps operator
+        with a split form whose contract in force is 'split', at a width the operator offers the route for (narrow_split_route: the cost rule, and the channel-mixing operator on
+        the matrix-core narrow kernel; a planner, without a batch, is not asked about a width).  DECLARED 'split' (exact_mode('split')): yes, unscreened, as every declared
+        re-ordering contract.  DECIDED 'split' by calibration (screened()): the route is one more association of the sum that the wide record does not cover, so the first eager
+        call with a batch measures it the way narrow_mode() measures the matrix-core narrow kernel -- the channel-lane kernel against the route on these very columns (of a
+        wider batch the 8-column window with the largest |x|: per image neither side's bits depend on the width), gate(), accepted by _calibrate's rule -- into a record of its
+        OWN, _contract_record['narrow_split'] = {decided: 'split' | 'exact', gate_ratio, max_abs_x, measured_on_columns, ...}.  The 'narrow' record, the wide fields and what
+        narrow='mfma' without the keyword does are never touched.  A layer calibration sent to 'exact' is out of reach: it stays on the channel-lane kernel."""
+        W = self.W
+        if not isinstance(W, ksp.Conv2dTiledMatrix) or not W.narrow_capable() or getattr(self, '_exact', True) != 'split' or not W.split_capable():
+            return False
+        if xt is not None and not W.narrow_split_route(int(xt.shape[1]), relu, xt.device if xt.is_cuda else None):
+            return False
+        if not self.screened():
+            return True
+        rec = self.narrow_split_record()
+        if rec is None:
+            if xt is None:
+                return False
+            if xt.is_cuda and torch.cuda.is_current_stream_capturing():
+                raise _capi.KeynetHipError('keynet_amd: %s has not measured the narrow split route yet (host reads): run one eager narrow=\'mfma\', narrow_split=True forward '
+                                           'before capturing a HIP graph (KeyedModel.capture does)' % self._repr)
+            rec = self._contract_record['narrow_split'] = self._measure_narrow_split(xt, relu)
+        return rec['decided'] == 'split'
+
+    def _measure_narrow_split(self, xt, relu):
+        """The narrow_split record of a layer calibration decided 'split', measured on the batch xt ([cols, N]): see narrow_split_mode().  Of more than NARROW_MAX columns the
+        window of NARROW_MAX that holds the largest |x| is measured, placed as _measure_narrow places its window."""
+        W = self.W
+        xt = ksp._device_block(xt)
+        n = int(xt.shape[1])
+        if n > ksp.NARROW_MAX:
+            c0 = min((int(torch.argmax(xt.detach().abs().amax(dim=0))) // ksp.NARROW_MAX) * ksp.NARROW_MAX, n - ksp.NARROW_MAX)
+            (xt, n) = (xt[:, c0:c0 + ksp.NARROW_MAX].contiguous(), ksp.NARROW_MAX)
+        if n == 0 or not W.narrow_split_route(n, relu, xt.device):
+            return dict(layer=self._repr, decided='exact', reason='an empty batch' if n == 0 else 'the operator does not offer the narrow split route on the measured columns',
+                        gate_ratio=None, max_abs_x=None, measured_on_columns=n)
+        xmax = float(xt.detach().abs().max())
+        asum = getattr(self, '_abs_rowsum', None)
+        if asum is None:
+            asum = self._abs_rowsum = W.max_abs_rowsum()
+        bound = 2.0 * EPS32 * asum * xmax
+        ye = W.torchdot(xt, relu=relu, exact=True, narrow=True)
+        ys = W._torchdot_split_narrow(xt, relu=relu)
+        (ratio, measured, tol, dmax) = gate(ys, ye)
+        ok = ratio <= 0.5 and (bound <= FLOAT_KEY_ATOL or ratio <= 0.25)
+        if not ok:
+            _log.warning('keynet_amd: %s keeps the channel-lane kernel on narrow_split forwards: narrow split result off by %.3g where the tolerance is %.3g', self._repr, measured, tol)
+        else:
+            with torch.cuda.device(xt.device):                 # the slot records the channel-lane side of the measurement built again (_calibrate released them for a 'split' layer)
+                W._device_op(xt.device).release_side_tables()
+        return dict(layer=self._repr, decided='split' if ok else 'exact', measured_narrow_split_vs_exact=measured, tol=tol, bound=bound, gate_ratio=ratio, max_abs_diff=dmax,
                     max_abs_x=xmax, measured_on_columns=n)
 
     def mfma_capable(self, device=None):

@@ -82,20 +82,26 @@ def _device_block(x):
     return xd if xd.is_contiguous() else xd.contiguous()
 
 
-def _run_torchdot(W, x, relu=False, exact=True, absmax=None, narrow=False, narrow_rows=False, narrow32=False, narrow64=False, narrow_linear=False):
+def _run_torchdot(W, x, relu=False, exact=True, absmax=None, narrow=False, narrow_rows=False, narrow32=False, narrow64=False, narrow_linear=False, narrow_split=False):
     """Y = W.X on the GPU under the contract `exact`, on the handle and flags of KeyedLayer.kernel.  x: [cols, N], torch tensor (any device / strides) or ndarray.
     Returns [rows, N] on x's device: float32, or for a float64 operator the float64 block scipy returns for it (kn_spmm_f64; the activations are
     float32 either way).  `narrow`, `narrow_rows`, `narrow32`, `narrow64`, `narrow_linear` (narrow64='mfma' included): the narrow forms of the product
     (KeyedModel.forward_linear), each allowed on its own here (_narrow_args with `alone`: a container's torchdot takes the ones its operator has a form for);
-    which flag each one sets on which operator is KeyedLayer.kernel's rule."""
+    which flag each one sets on which operator is KeyedLayer.kernel's rule.  `narrow_split` (only with narrow='mfma'): a filled-in conv operator under 'split' runs the
+    narrow split route where it has one at this width (Conv2dTiledMatrix.narrow_split_route), else exactly the call without the keyword."""
     from .layer import KeyedLayer            # (layer.py imports this module)
     x = torch.as_tensor(x)
     assert W.shape[1] == x.shape[0], 'Non-conformal shape for W=%s, x=%s' % (str(W.shape), str(tuple(x.shape)))
     xd = _device_block(x)
     n = xd.shape[1]
-    _narrow_args(n, narrow, narrow_rows, 'batch columns', True, narrow32, narrow64, narrow_linear)
-    kernel = KeyedLayer.kernel(W, exact, relu, xd.device, narrow, narrow_rows, narrow32, narrow64, narrow_linear)
-    if kernel is None:
+    _narrow_args(n, narrow, narrow_rows, 'batch columns', True, narrow32, narrow64, narrow_linear, narrow_split)
+    kernel = KeyedLayer.kernel(W, exact, relu, xd.device, narrow, narrow_rows, narrow32, narrow64, narrow_linear, narrow_split)
+    split_narrow = kernel is None and bool(narrow_split) and isinstance(W, Conv2dTiledMatrix) and W.narrow_capable()      # (kernel()'s one "not one launch" among the narrow conv calls)
+    if split_narrow and not W.narrow_split_route(n, relu, xd.device):
+        (kernel, split_narrow) = (KeyedLayer.kernel(W, exact, relu, xd.device, narrow, narrow_rows, narrow32, narrow64, narrow_linear), False)
+    if split_narrow:
+        y = W._torchdot_split_narrow(xd, relu=relu, absmax=absmax)
+    elif kernel is None:
         y = W._torchdot_split(xd, relu=relu, absmax=absmax)
     else:
         (get_op, flags) = kernel
@@ -116,15 +122,19 @@ NARROW32_MAX = 32     # ... with narrow32=True (KN_FLAG_NARROW32: convtaps_narro
 NARROW64_MAX = 64     # ... with narrow64=True (KN_FLAG_NARROW64: beyond NARROW32_MAX columns convtaps_exact_pipe64_kernel; narrow64='mfma': the f32 tile kernel on 64-column tiles; KeyedModel.NARROW64_MAX)
 
 
-def _narrow_args(n, narrow, narrow_rows, what='images', alone=False, narrow32=False, narrow64=False, narrow_linear=False):
+def _narrow_args(n, narrow, narrow_rows, what='images', alone=False, narrow32=False, narrow64=False, narrow_linear=False, narrow_split=False):
     """The argument rule of the narrow forms, for a batch of `n`: `narrow_rows` only together with `narrow` (`alone`: a container's torchdot, which takes one
     keyword or the other), at most NARROW_MAX columns; `narrow32` only together with `narrow`, whose limit it lifts to NARROW32_MAX -- not that of `narrow_rows`
     (the row-lane kernel is an 8-column kernel); `narrow64` only together with `narrow` as well: it implies `narrow32` (at most NARROW32_MAX columns the call is exactly
     narrow32=True) and lifts the limit to NARROW64_MAX, where narrow='mfma' with narrow64=True is refused beyond NARROW32_MAX (True asks for the order-preserving form
     of that width); `narrow64='mfma'` only together with narrow='mfma': the matrix-core form of NARROW32_MAX + 1 .. NARROW64_MAX columns (KN_FLAG_NARROW64_MFMA), and at
     NARROW32_MAX columns and fewer exactly narrow='mfma', narrow32=True; `narrow_linear` only together with `narrow` (or `alone`), up to the limit the `narrow`
-    keywords passed give -- NARROW_MAX, NARROW32_MAX with `narrow32`, NARROW64_MAX with `narrow64` -- and alone up to NARROW64_MAX, the kernel's own range.
+    keywords passed give -- NARROW_MAX, NARROW32_MAX with `narrow32`, NARROW64_MAX with `narrow64` -- and alone up to NARROW64_MAX, the kernel's own range;
+    `narrow_split` only together with narrow='mfma' (`alone` or not: the route ends on the matrix-core narrow kernel), at the widths the other keywords allow -- it takes effect up
+    to NARROW32_MAX columns and changes nothing beyond.
     ValueError, or the normalised (mode, rows): mode False | True | 'mfma', rows a bool."""
+    if narrow_split and narrow != 'mfma':
+        raise ValueError('narrow_split=True is the split application of a filled-in conv layer on the matrix-core narrow kernel: pass narrow=\'mfma\' with it (got narrow=%r)' % (narrow,))
     if narrow64 == 'mfma' and narrow != 'mfma':
         raise ValueError('narrow64=\'mfma\' is the matrix-core form of %d .. %d %s: pass narrow=\'mfma\' with it (got narrow=%r)' % (NARROW32_MAX + 1, NARROW64_MAX, what, narrow))
     if narrow_rows and not narrow and not alone:
@@ -154,22 +164,45 @@ class NarrowForm(collections.namedtuple('NarrowForm', 'mode rows narrow32 narrow
     `narrow32`, `narrow64`: the width the keywords allow is lifted to NARROW32_MAX, to NARROW64_MAX (narrow64 implies narrow32); `tile64`: narrow64='mfma' at a
     width that takes the 64-column matrix-core tile; `rows`, `linear`: narrow_rows, narrow_linear.  Built by of() at the surfaces that take the keywords: once per
     call in KeyedModel, which hands the value down to _forward_once; there keywords() hands the keywords back to each KeyedLayer.forward, and that surface and
-    KeyedLayer.kernel behind the operator's torchdot each build the value again from them (the keyword surfaces are what a layer and an operator are called by)."""
+    KeyedLayer.kernel behind the operator's torchdot each build the value again from them (the keyword surfaces are what a layer and an operator are called by).
+    `split`: the opt-in sixth keyword narrow_split=True (only with narrow='mfma': the narrow split route of a filled-in conv layer, KeyedModel.forward_linear).  The six fields
+    above ARE the value of every call without it; a call with it gets the same six fields as a NarrowSplitForm, which equals no plain form and hands the keyword back."""
     __slots__ = ()
+    split = False
 
     @classmethod
     @functools.lru_cache(maxsize=256)        # (asked per layer and launch, on the shortest forwards, for the same few keyword sets)
-    def of(cls, n, narrow=False, narrow_rows=False, narrow32=False, narrow64=False, narrow_linear=False, what='images', alone=False):
+    def of(cls, n, narrow=False, narrow_rows=False, narrow32=False, narrow64=False, narrow_linear=False, what='images', alone=False, narrow_split=False):
         """The form of a batch of `n` under the keywords: _narrow_args refuses what the argument rule refuses (`what`, `alone`: its own).  n = None: no batch
         (KeyedLayer.kernel / launch) -- nothing is refused, a keyword without `narrow` means what the rules of kernel() make of it, and the tile is asked for."""
         mode = narrow if narrow == 'mfma' else bool(narrow)
         if n is not None:
-            _narrow_args(n, narrow, narrow_rows, what, alone, narrow32=narrow32, narrow64=narrow64, narrow_linear=narrow_linear)
-        return cls(mode, bool(narrow_rows), bool(narrow32 or narrow64), bool(narrow64), mode == 'mfma' and narrow64 == 'mfma' and (n is None or n > NARROW32_MAX), bool(narrow_linear))
+            _narrow_args(n, narrow, narrow_rows, what, alone, narrow32=narrow32, narrow64=narrow64, narrow_linear=narrow_linear, narrow_split=narrow_split)
+        kind = NarrowSplitForm if (narrow_split and mode == 'mfma') else NarrowForm
+        return kind(mode, bool(narrow_rows), bool(narrow32 or narrow64), bool(narrow64), mode == 'mfma' and narrow64 == 'mfma' and (n is None or n > NARROW32_MAX), bool(narrow_linear))
 
     def keywords(self):
-        """The keywords of this form, normalised, as KeyedLayer.forward and the surfaces below it take them (narrow64: 'mfma' only where the tile is asked for)."""
-        return dict(narrow=self.mode, narrow_rows=self.rows, narrow32=self.narrow32, narrow64='mfma' if self.tile64 else self.narrow64, narrow_linear=self.linear)
+        """The keywords of this form, normalised, as KeyedLayer.forward and the surfaces below it take them (narrow64: 'mfma' only where the tile is asked for;
+        narrow_split: only where it was passed)."""
+        kw = dict(narrow=self.mode, narrow_rows=self.rows, narrow32=self.narrow32, narrow64='mfma' if self.tile64 else self.narrow64, narrow_linear=self.linear)
+        if self.split:
+            kw['narrow_split'] = True
+        return kw
+
+
+class NarrowSplitForm(NarrowForm):
+    """A NarrowForm of a call that passed narrow_split=True (with narrow='mfma'): the same six fields, `split` True."""
+    __slots__ = ()
+    split = True
+
+    def __eq__(self, other):
+        return type(other) is NarrowSplitForm and tuple.__eq__(self, other)
+
+    def __ne__(self, other):
+        return not self.__eq__(other)
+
+    def __hash__(self):
+        return hash((NarrowSplitForm, tuple(self)))
 
 
 # ------------------------------------------------------------------------------------------------------------------
@@ -671,8 +704,9 @@ class Conv2dTiledMatrix(TiledMatrix):
     def rows_capable(self):
         return False                     # (a conv-taps handle on the device)
 
-    def torchdot(self, x, relu=False, exact=False, absmax=None, narrow=False, narrow32=False, narrow64=False):
-        """[cols, N] -> [rows, N].  exact=False: f32 MFMA path (f32-input matrix instructions, exact f32 products); exact=True: the
+    def torchdot(self, x, relu=False, exact=False, absmax=None, narrow=False, narrow32=False, narrow64=False, narrow_split=False):
+        """[cols, N] -> [rows, N].  `narrow_split` (only with narrow='mfma', ValueError otherwise): under exact='split', at most NARROW32_MAX columns, a filled-in operator runs
+        the narrow split route (_torchdot_split_narrow) where narrow_split_route() offers it; everywhere else the call is what it is without the keyword.  exact=False: f32 MFMA path (f32-input matrix instructions, exact f32 products); exact=True: the
         reference's accumulation order and rounding (order-preserving kernel on the factored operator); exact='split': a filled-in factored
         operator applied as spatial mixing per tap, then channel mixing (see _split_ops: another association of the sum, tolerance contract only); exact='bf16x3': f32 products
         emulated on the bf16 matrix pipe (three-way exact split, six of nine cross products, f32 accumulate: KN_FLAG_BF16X3) where the
@@ -682,7 +716,13 @@ class Conv2dTiledMatrix(TiledMatrix):
         narrow64='mfma' (with narrow='mfma') beyond NARROW32_MAX columns under False / 'bf16x3' the f32 product on 64-column tiles (per column the bits of the plain
         matrix-core call on the batch zero-padded to 128 columns), else narrow64=True.  The flag word is KeyedLayer.kernel's."""
         assert not isinstance(exact, str) or exact in ('bf16x3', 'split') or (narrow and exact == 'auto'), "exact must be True, False, 'bf16x3' or 'split'"
-        return _run_torchdot(self, x, relu=relu, exact=exact, absmax=absmax, narrow=narrow, narrow32=narrow32, narrow64=narrow64)
+        return _run_torchdot(self, x, relu=relu, exact=exact, absmax=absmax, narrow=narrow, narrow32=narrow32, narrow64=narrow64, narrow_split=narrow_split)
+
+    def __getstate__(self):
+        d = super(Conv2dTiledMatrix, self).__getstate__()
+        d.pop('_narrow_split_ws', None)           # device workspaces and plan answers of the narrow split route: rebuilt at first use
+        d.pop('_narrow_split_plans', None)
+        return d
 
     # ---- the SPLIT application of a filled-in operator (tolerance contract only) -----------------------------------------------------
     # A factored keyed conv is  sum_t F_t (x) K_t  with F_t the Cout x Cin matrix of tap t and K_t = a_out S_t a_in^-1 the HoWo x HiWi spatial
@@ -779,6 +819,107 @@ class Conv2dTiledMatrix(TiledMatrix):
                 if has_last:
                     z[-1, :w].copy_(xd[-1, c0:c0 + w])
                 op2.spmm(z.data_ptr(), ldz, w, y.data_ptr() + 4 * c0, n, flags, st, absmax_ptr=None if absmax is None else absmax.data_ptr())
+        return y
+
+    # ---- the NARROW split route (narrow='mfma', narrow_split=True; 1 .. NARROW32_MAX columns) ---------------------------------------------------
+    # kn_spmm_planes puts the input-channel planes on grid dimension y and the batch columns on lanes: at one image one lane in 64 works.  For a narrow batch the
+    # planes ARE the batch of the spatial matrix: on Xt[in][(ci, b)] it is an ordinary CSR product with N = Cin x n = 64 .. 16 384 columns, the width the CSR kernels
+    # are built for.  Four steps:  X -> Xt (kn_planes_to_columns);  Z' = K Xt (ONE kn_spmm, stored order);  Z' -> Z (kn_columns_to_planes; the homogeneous row copied
+    # as on the wide route);  Y = op2 Z on the matrix-core narrow kernel (op2 has one slot per (pixel, tap): eligible, where the fused filled-in operator is not).
+    # Z of an image is bit-equal to the wide route's (the same stored-order sums, whatever the width), and an image's Y does not depend on the launch width (the narrow
+    # matrix-core kernel's property), so ONE measurement on 8 columns covers every width (KeyedLayer.narrow_split_mode).
+    NARROW_SPLIT_Z_BYTES = 4 << 30      # Z' is produced in windows of whole images of at most this size (VGG-16 conv1_2 at 32 images: 3.7 GB, one window); a window is the three
+                                        # first steps on a column range of X -- other columns, the same sums: windows change no bit
+    NARROW_SPLIT_MIN_GAIN = 1.3         # the route is offered where the estimate of the fused channel-lane launch is at least this many times the route's (the margin every narrow regime was held to)
+    # the constants of narrow_split_capable's estimate (seconds; DESIGN section 5 says which are measured):
+    # (set from profiles/r14_narrow_split.txt, each on the slow side of what was measured so that the estimate of the route errs high and that of the fused launch low)
+    NARROW_SPLIT_STEP_RATE = 1.2e10     # wavefront steps per second of the channel-lane kernel in its summed-stored-values form (measured 1.15 - 1.35e10 at one image; the 9-slot form: 2.1e10)
+    NARROW_SPLIT_CSR_RATE = 2.0e12      # multiply-adds per second of the CSR kernels at Cin x n columns (measured 2.0e12 on conv1_2 .. 8.1e12 on conv4_2)
+    NARROW_SPLIT_BYTE_RATE = 3.0e12     # bytes per second of the two permutes and of Xt / Z' through the CSR kernel (the permutes measured 4.3 - 5.3e12 on the large layers, 0.6 - 3e12 on the small)
+    NARROW_SPLIT_MMA_RATE = 2.0e13      # multiply-adds per second of the matrix-core narrow kernel on the 9-slot operator (measured 0.8 - 3.2e13)
+    NARROW_SPLIT_FIXED = 6.0e-5         # three more launches and the narrow kernel's floor (reasoning: its smallest measured launch is 33 us, a launch about 9 us)
+
+    def narrow_split_capable(self, n_vecs=None):
+        """Is the narrow split route worth offering to this operator at `n_vecs` columns?  split_capable()'s question for the narrow forward: the fused launch it replaces is the
+        channel-lane kernel in its summed-stored-values form -- entries x Cin x ceil(Cout / 64) wavefront steps per block of up to 16 columns -- and the route costs
+        entries x Cin x n multiply-adds on the CSR kernels, the activations moved five times (X read, Xt written and read, Z' written and read, Z written: two permutes around
+        one product) and the 9-slot narrow launch."""
+        if not self.split_capable():
+            return False
+        if n_vecs is None:
+            return True
+        if not 0 < n_vecs <= NARROW32_MAX:
+            return False
+        (Cin, Cout, HoWo, HiWi) = (self._inshape[0], self._outshape[0], self._outshape[1] * self._outshape[2], self._inshape[1] * self._inshape[2])
+        (ent, nt, n) = (float(len(self._taps['ent_out'])), float(len(self._taps['taps'])), float(n_vecs))
+        fused = ent * Cin * -(-Cout // 64) * -(-n_vecs // 16) / self.NARROW_SPLIT_STEP_RATE
+        split = (ent * Cin * n / self.NARROW_SPLIT_CSR_RATE + 4.0 * Cin * n * (3.0 * HiWi + 3.0 * nt * HoWo) / self.NARROW_SPLIT_BYTE_RATE +
+                 nt * HoWo * Cin * Cout * n / self.NARROW_SPLIT_MMA_RATE + self.NARROW_SPLIT_FIXED)
+        return fused >= self.NARROW_SPLIT_MIN_GAIN * split
+
+    def narrow_split_route(self, n_vecs, relu=False, device=None):
+        """Does a narrow_split call of `n_vecs` columns take the route here?  A split form (split_capable()), the cost rule (narrow_split_capable), and the channel-mixing
+        operator's narrow launch at this width on the matrix-core narrow kernel (kn_spmm_plan names it; asked once per (device, width, relu))."""
+        if not 0 < n_vecs <= NARROW32_MAX or not self.narrow_split_capable(n_vecs):
+            return False
+        idx = torch.cuda.current_device() if (device is None or device.index is None) else device.index
+        plans = self.__dict__.setdefault('_narrow_split_plans', {})
+        key = (idx, int(n_vecs), bool(relu))
+        if key not in plans:
+            with torch.cuda.device(idx):
+                plans[key] = 'convtaps_narrow_mfma_kernel' in self._split_ops(device)[1].plan(n_vecs, self._narrow_split_flags(n_vecs, relu))
+        return plans[key]
+
+    @staticmethod
+    def _narrow_split_flags(n_vecs, relu):
+        return _capi.KN_FLAG_NARROW_MFMA | (_capi.KN_FLAG_NARROW32 if n_vecs > NARROW_MAX else 0) | (_capi.KN_FLAG_RELU if relu else 0)
+
+    def _narrow_split_window(self, n_vecs):
+        """Images per window of the route's first three steps: whole images, Z' within NARROW_SPLIT_Z_BYTES."""
+        (Cin, nt, HoWo) = (self._inshape[0], len(self._taps['taps']), self._outshape[1] * self._outshape[2])
+        return max(1, min(int(n_vecs), int(self.NARROW_SPLIT_Z_BYTES // (4 * nt * HoWo * Cin))))
+
+    def _narrow_split_workspace(self, device, n_vecs):
+        """(Xt, Z', Z) flat float32 device buffers of the route, per (device, width class 8 | 32, window): allocated at the first call of a class (an eager one: KeyedModel.capture
+        runs it before capturing) and reused by every later one on the stream order of the calls; nothing asks the allocator or the device per forward.  Dropped by
+        release_narrow_split_workspace() (KeyedModel.release_workspace) and by pickling."""
+        (Cin, Hin, Win) = self._inshape
+        (HoWo, HiWi, nt) = (self._outshape[1] * self._outshape[2], Hin * Win, len(self._taps['taps']))
+        wc = NARROW_MAX if n_vecs <= NARROW_MAX else NARROW32_MAX
+        win = self._narrow_split_window(wc)
+        ws = self.__dict__.setdefault('_narrow_split_ws', {})
+        key = (torch.cuda.current_device() if device.index is None else device.index, wc, win)
+        if key not in ws:
+            zrows = Cin * nt * HoWo + (1 if self._taps['lastcol'] is not None else 0)
+            ws[key] = tuple(torch.empty(k, dtype=torch.float32, device=device) for k in (HiWi * Cin * win, nt * HoWo * Cin * win, zrows * wc))
+        return ws[key]
+
+    def release_narrow_split_workspace(self):
+        self.__dict__.pop('_narrow_split_ws', None)
+
+    def _torchdot_split_narrow(self, xd, relu=False, absmax=None):
+        """xd: the device block (_device_block) [cols, n], n <= NARROW32_MAX -> [rows, n] on its device: the narrow split route (above)."""
+        (Cin, Hin, Win) = self._inshape
+        (HoWo, HiWi, nt) = (self._outshape[1] * self._outshape[2], Hin * Win, len(self._taps['taps']))
+        has_last = self._taps['lastcol'] is not None
+        n = int(xd.shape[1])
+        assert 0 < n <= NARROW32_MAX, 'the narrow split route takes 1 .. %d columns, got %d' % (NARROW32_MAX, n)
+        y = torch.empty((self.shape[0], n), dtype=torch.float32, device=xd.device)
+        with torch.cuda.device(xd.device):
+            (opK, op2) = self._split_ops(xd.device)
+            (xt, zc, z) = self._narrow_split_workspace(xd.device, n)
+            win = self._narrow_split_window(NARROW_MAX if n <= NARROW_MAX else NARROW32_MAX)
+            st = _stream_ptr()
+            for c0 in range(0, n, win):
+                w = min(win, n - c0)
+                N = Cin * w
+                _capi.planes_to_columns(xd.data_ptr() + 4 * c0, HiWi * n, n, Cin, HiWi, w, xt.data_ptr(), N, st)
+                opK.spmm(xt.data_ptr(), N, N, zc.data_ptr(), N, _capi.KN_FLAG_EXACT | (_capi.KN_FLAG_NARROW_ROWS if N <= NARROW_MAX else 0), st)
+                _capi.columns_to_planes(zc.data_ptr(), N, Cin, nt * HoWo, w, z.data_ptr() + 4 * c0, nt * HoWo * n, n, st)
+            zv = z[:(Cin * nt * HoWo + (1 if has_last else 0)) * n].view(-1, n)
+            if has_last:
+                zv[-1].copy_(xd[-1])
+            op2.spmm(z.data_ptr(), n, n, y.data_ptr(), n, self._narrow_split_flags(n, relu), st, absmax_ptr=None if absmax is None else absmax.data_ptr())
         return y
 
     def _expand_taps_host(self, pixels=None, channels=None):

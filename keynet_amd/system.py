@@ -179,7 +179,7 @@ class KeyedModel(object):
     NARROW32_MAX = ksp.NARROW32_MAX    # ... with narrow32=True (convtaps_narrow32_kernel: the columns in blocks of 8 | 16 | 32 running sums per lane)
     NARROW64_MAX = ksp.NARROW64_MAX    # ... with narrow64=True (beyond NARROW32_MAX images convtaps_exact_pipe64_kernel: one column per lane, packed over output-channel pairs)
 
-    def forward_linear(self, img_cipher, overlap=None, narrow=False, narrow_rows=False, narrow32=False, narrow64=False, narrow_linear=False):
+    def forward_linear(self, img_cipher, overlap=None, narrow=False, narrow_rows=False, narrow32=False, narrow64=False, narrow_linear=False, narrow_split=False):
         """[N, D0+1] -> [N, classes+1]: the nn.Sequential of keynet/system.py:132 with the unkeyed ReLUs fused into the
         producing layer's kernel epilogue.  Stream-ordered on torch's current HIP stream.  Host synchronisation: none for key-nets whose
         layers all run under a DECLARED contract (exact=True: the permutation key-nets; exact=False: forced); a key-net with layers on the
@@ -238,16 +238,28 @@ class KeyedModel(object):
         `narrow_linear=True` (at every width the other keywords allow): the keyed Linear layers under the bit-exact contract -- float32 CSR operators in the stored order
         that hold big pattern groups -- run csr_stream_group_kernel (KN_FLAG_NARROW_LINEAR: a workgroup owns 64 output rows times all images, the values reach it through
         a ring in LDS and leave HBM once per call) instead of the wide-batch kernel, which costs 64 images at every width.  The same bits layer by layer; next to
-        `narrow_rows` the other CSR layers and the remaining rows of a Linear keep the row-lane kernel."""
-        (form, x, windows) = self._resolve(img_cipher, (narrow, narrow_rows, narrow32, narrow64, narrow_linear))
+        `narrow_rows` the other CSR layers and the remaining rows of a Linear keep the row-lane kernel.
+        `narrow_split=True` (opt-in; only together with narrow='mfma', ValueError otherwise; 1 .. NARROW_MAX images, to NARROW32_MAX with `narrow32`): the FILLED-IN conv layers
+        whose contract in force is 'split' (doubly-stochastic keys: 500 - 5 400 slots per output pixel) run the narrow split route instead of the fused operator on the
+        channel-lane kernel, which is all narrow='mfma' has for them (more than two slots on a (pixel, tap) pair: no matrix-core narrow form).  The route
+        (Conv2dTiledMatrix._torchdot_split_narrow): X [Cin x HiWi, n] -> Xt [HiWi, Cin x n] (kn_planes_to_columns), ONE stored-order product of the spatial CSR at Cin x n
+        columns, back to planes (kn_columns_to_planes), then the 9-slot channel-mixing operator on the matrix-core narrow kernel.  Taken where the operator's cost rule offers it at
+        this width (narrow_split_capable) and the second step plans the matrix-core narrow kernel; a layer declared 'split' runs it unscreened, a layer CALIBRATION decided
+        'split' after its own measurement on the first such batch (KeyedLayer.narrow_split_mode: channel-lane kernel against the route on these columns, _calibrate's rule),
+        recorded under the calibration record's own key 'narrow_split' and re-screened on every narrow_split forward like a narrow record (a trip drops only that record).
+        Every other layer -- and a layer calibration sent to 'exact', which stays on the channel-lane kernel -- is what narrow='mfma' makes it, bit for bit; at 33 .. 64
+        images (narrow64) the keyword changes nothing.  Workspaces: Xt, Z' and Z per (layer, device, width class 8 | 32), allocated by the first forward of a class
+        and kept (release_workspace() drops them); calls that share a layer are ordered by their stream."""
+        (form, x, windows) = self._resolve(img_cipher, (narrow, narrow_rows, narrow32, narrow64, narrow_linear), narrow_split=narrow_split)
         y = self._forward_passes(x, windows, False if form.mode else overlap, form)[0][:img_cipher.shape[0]]
         return y if img_cipher.is_cuda else y.to(img_cipher.device)
 
-    def _resolve(self, x, keywords, own=False):
+    def _resolve(self, x, keywords, own=False, narrow_split=False):
         """The narrow keywords of forward_linear / capture (in the order of their signatures) on the batch x, once per call: (form, block, windows) -- the ksp.NarrowForm
         everything below reads (ValueError where the argument rule refuses the keywords) and the block the passes run on, _prepare64's where the form takes the 64-column
-        tile, else _prepare's.  `own` (capture): a block of the call's own, never x's memory -- the graph's input."""
-        form = ksp.NarrowForm.of(x.shape[0], *keywords)
+        tile, else _prepare's.  `own` (capture): a block of the call's own, never x's memory -- the graph's input.
+        `narrow_split`: the opt-in sixth keyword, carried by the form (NarrowForm.split)."""
+        form = ksp.NarrowForm.of(x.shape[0], *keywords, narrow_split=narrow_split)
         if own:
             x = x.detach().float() if form.mode else x.detach()
             x = x if form.tile64 else x.t().clone(memory_format=torch.contiguous_format).t()
@@ -338,6 +350,8 @@ class KeyedModel(object):
         if form.tile64:
             return (set(j for (j, c) in enumerate(keyed) if c.screened() and isinstance(c.W, ksp.Conv2dTiledMatrix) and c.W.narrow_capable() and c._exact in (False, 'bf16x3')), False)
         if form.mode:
+            if form.split:      # narrow_split=True: also the layers a measurement put on the narrow split route, against THAT record ('split': KeyedLayer._screen_key)
+                return (set(j for (j, c) in enumerate(keyed) if c.narrow_screened() or c.narrow_split_screened()), 'split')
             return (set(j for (j, c) in enumerate(keyed) if c.narrow_screened()) if form.mode == 'mfma' else set(), True)
         if any(getattr(c, '_exact', True) == 'auto' for c in keyed):
             return (set(), False)
@@ -346,11 +360,12 @@ class KeyedModel(object):
     def _rescreen(self, xmax, keyed, screened, narrow=False):
         """Host side of the per-forward screen: layers whose input magnitude has outgrown their calibration go back to 'auto' (decided
         again by the next forward, on that batch).  Returns their indices.  `narrow`: the screen of a narrow='mfma' forward -- against the layers' NARROW
-        records; an outgrown one is dropped (measured again by the next narrow='mfma' pass, on that batch), the wide decision and the launch lists stay."""
+        records; an outgrown one is dropped (measured again by the next narrow='mfma' pass, on that batch), the wide decision and the launch lists stay.  narrow='split' (a
+        narrow_split=True forward): a layer on the narrow split route is checked against its narrow_split record, and a trip drops that record alone."""
         redo = [k for k in sorted(screened) if keyed[k].rescreen(xmax[k], narrow=narrow)]
         for k in redo:
             klayer._log.info('keynet_amd: %s: max |x| = %.3g against %.3g at %s: re-calibrating on this batch', keyed[k]._repr, xmax[k], keyed[k].screen_record(narrow)['max_abs_x'],
-                             'its narrow measurement' if narrow else 'calibration')
+                             ('its narrow split measurement' if keyed[k]._screen_key(narrow) == 'narrow_split' else 'its narrow measurement') if narrow else 'calibration')
             keyed[k].unscreen(narrow)
         if redo:
             count = '_narrow_remeasurements' if narrow else '_recalibrations'
@@ -518,8 +533,12 @@ class KeyedModel(object):
         return total
 
     def release_workspace(self):
-        """Drop the activation workspaces and side streams of the overlapped forward (two ping-pong blocks per batch size)."""
+        """Drop the activation workspaces and side streams of the overlapped forward (two ping-pong blocks per batch size), and the Xt / Z' / Z workspaces of the narrow
+        split route (per layer, device and width class)."""
         self._drop_plans()
+        for c in self._keyed():
+            if isinstance(c.W, ksp.Conv2dTiledMatrix):
+                c.W.release_narrow_split_workspace()
 
     def _forward_overlapped(self, x, plan, slots=None, screened=()):
         """x: [N, D0+1] whose transpose is a contiguous feature-major block.  Layers ping-pong between two flat workspaces with the
@@ -595,9 +614,13 @@ class KeyedModel(object):
         record of that decision (bound, measured difference, tolerance, max |x| it covers).  `switched` lists the layers calibration moved
         off the matrix cores; `rescreen` says whether every forward re-checks the decisions; `recalibrations` counts the layers a later,
         larger batch sent back to calibration.  `narrow` per layer: the record of its narrow='mfma' measurement (KeyedLayer.narrow_mode; also inside
-        `calibration`), None for layers that have none."""
+        `calibration`), None for layers that have none.  `narrow_split`: the record of a layer's narrow_split measurement (KeyedLayer.narrow_split_mode; also inside `calibration`)
+        -- present only on the layers that have one, so the rows of a key-net that never ran a narrow_split forward are what they were."""
         rows = [dict(name=n, exact=getattr(c, '_exact', True), declared=getattr(c, '_exact_decl', getattr(c, '_exact', True)),
                      calibration=getattr(c, '_contract_record', None), screened=c.screened(), narrow=c.narrow_record()) for (n, c) in self._keyed(named=True)]
+        for (r, (_, c)) in zip(rows, self._keyed(named=True)):
+            if c.narrow_split_record() is not None:
+                r['narrow_split'] = c.narrow_split_record()
         return dict(layers=rows, switched=[r['name'] for r in rows if r['calibration'] is not None and r['calibration'].get('decided') == 'exact' and 'bound' in r['calibration']],
                     undecided=[r['name'] for r in rows if r['exact'] == 'auto'],
                     rescreen=bool(self.RESCREEN and any(r['screened'] for r in rows)),
@@ -639,7 +662,7 @@ class KeyedModel(object):
             self._drop_plans()
         return changed
 
-    def capture(self, img_cipher, narrow=False, narrow_rows=False, narrow32=False, narrow64=False, narrow_linear=False):
+    def capture(self, img_cipher, narrow=False, narrow_rows=False, narrow32=False, narrow64=False, narrow_linear=False, narrow_split=False):
         """Capture forward_linear for this input shape into a HIP graph (torch.cuda.CUDAGraph on ROCm) and return a callable
         `replay(x) -> [N, classes+1]`.  Small key-nets are launch-bound (LeNet at N=1024: 7 kernels in 0.25 ms); one graph
         launch replaces them.  The graph runs the passes of the eager forward on the block _prepare made; replay(x) copies x into its first N images.
@@ -650,10 +673,12 @@ class KeyedModel(object):
         `narrow`, `narrow_rows`, `narrow32`, `narrow64`, `narrow_linear` (narrow='mfma', narrow64='mfma' included): the graph of forward_linear under the same keywords, up to
         the same widths -- a straight line of launches on one stream, no parallel branches, decided by the eager forward first.  Where that forward screens layers
         (narrow='mfma': against their narrow records; the 64-column tile: against their wide records; narrow=True: none, replay() reads nothing back) the graph gathers
-        their max |x|, replay() reads the slots after the launch and on a trip runs the batch eagerly (measuring or calibrating again) and captures a new graph."""
+        their max |x|, replay() reads the slots after the launch and on a trip runs the batch eagerly (measuring or calibrating again) and captures a new graph.
+        `narrow_split` (with narrow='mfma'): the graph of that forward -- the eager forward first measures the narrow split route where a calibrated layer has no record of it and
+        allocates the route's workspaces, so the capture finds both; replay equals the eager forward bit for bit."""
         assert img_cipher.is_cuda, 'capture() needs a device tensor'
         n = img_cipher.shape[0]
-        (form, static_in, windows) = self._resolve(img_cipher, (narrow, narrow_rows, narrow32, narrow64, narrow_linear), own=True)
+        (form, static_in, windows) = self._resolve(img_cipher, (narrow, narrow_rows, narrow32, narrow64, narrow_linear), own=True, narrow_split=narrow_split)
         keyed = self._keyed()
         state = {}
 
@@ -685,12 +710,12 @@ class KeyedModel(object):
         replay.graph = state['graph']
         return replay
 
-    def forward(self, img_cipher, outkey=None, narrow=False, narrow_rows=False, narrow32=False, narrow64=False, narrow_linear=False):
+    def forward(self, img_cipher, outkey=None, narrow=False, narrow_rows=False, narrow32=False, narrow64=False, narrow_linear=False, narrow_split=False):
         """Encrypted image(s) [N, D0+1] -> logits.  N == 1 returns the reference's shape `outshape` = (C,1,1)
         (keynet/system.py:130-133); N > 1 (an extension: the reference cannot) returns (N, C, 1, 1).  `narrow`, `narrow_rows`, `narrow32`, `narrow64`,
-        `narrow_linear` (narrow='mfma', narrow64='mfma' included): the low-latency forms of this very call, handed to forward_linear, which says what each selects."""
+        `narrow_linear`, `narrow_split` (narrow='mfma', narrow64='mfma' included): the low-latency forms of this very call, handed to forward_linear, which says what each selects."""
         outkey = outkey if outkey is not None else self.embeddingkey()
-        y = self.forward_linear(img_cipher, narrow=narrow, narrow_rows=narrow_rows, narrow32=narrow32, narrow64=narrow64, narrow_linear=narrow_linear)
+        y = self.forward_linear(img_cipher, narrow=narrow, narrow_rows=narrow_rows, narrow32=narrow32, narrow64=narrow64, narrow_linear=narrow_linear, narrow_split=narrow_split)
         if outkey is not None:
             y = self.decrypt(y, outkey)
         n = y.shape[0]

@@ -58,6 +58,11 @@ images for the ladder.  The bars of the file are computed from the table.
     python tools/narrow_latency.py --linear --one-forward        # for n in (1, 8, 16, 64) ONE narrow forward, then ONE with narrow_linear=True (for a kernel trace)
     python tools/narrow_latency.py --linear --from-trace DIR/.../*_kernel_trace.csv [--convs 13]     # no GPU: the CSR launches of those forwards side by side
 
+    python tools/narrow_latency.py --split [--layers conv1_2,conv5_x]     # no key-net: filled-in synthetic operators of the VGG-16 conv shapes, narrow='mfma' without and with
+                                                                          # narrow_split=True at 1, 8 and 32 images in one process (profiles/r14_narrow_split.txt)
+    python tools/narrow_latency.py --split --one-forward                  # ONE narrow split call per layer and width behind a warm-up call (for a kernel trace)
+    python tools/narrow_latency.py --split --from-trace DIR/.../*_kernel_trace.csv    # no GPU: the four steps of those calls
+
 --linear: keyed VGG-16 under the default contract, everything in one process with the forms alternating.  fc6, fc7 and fc8 alone: kn_spmm without and with
 KN_FLAG_NARROW_LINEAR at 1, 2, 3, 4, 8, 16, 32, 33 and 64 columns, up to 8 columns also next to KN_FLAG_NARROW_ROWS -- back to back on one block (values as warm as
 the layer's size lets them be) and behind a pass over a 512 MB buffer that leaves nothing of the operator on chip (what a forward sees) -- with the plan strings; then
@@ -404,6 +409,137 @@ def narrow32_blocks(args):
         f.write(text)
 
 
+# (name, Cin, Cout, H, entries per (output pixel, tap)): the conv shapes of VGG-16 with fill factors across what Conv2dTiledMatrix.fill_factor() documents for doubly-stochastic
+# keys (55 - 600; a 14 x 14 layer has 196 pixels to fill)
+SPLIT_LAYERS = [('conv1_1', 3, 64, 224, 55), ('conv1_2', 64, 64, 224, 55), ('conv2_1', 64, 128, 112, 150), ('conv2_2', 128, 128, 112, 150), ('conv3_1', 128, 256, 56, 300),
+                ('conv3_2', 256, 256, 56, 300), ('conv4_1', 256, 512, 28, 600), ('conv4_2', 512, 512, 28, 600), ('conv5_x', 512, 512, 14, 196)]
+SPLIT_IMAGES = (1, 8, 32)
+
+
+def _split_operator(rng, Cin, Cout, H, fill):
+    """A filled-in factored conv of a VGG-16 layer shape, built the way tests/test_parity_gpu.py's _filled_in_convtaps builds one (every output pixel reads `fill` input pixels
+    through each of the nine taps, each entry with its own coefficient; an averaging key), vectorised: tap t reads the pixels o + off_t[k] (mod H x H), off_t distinct."""
+    import numpy as np
+    from keynet_amd import sparse as ksp
+    HW = H * H
+    taps = (rng.randn(9, Cout, Cin) / np.sqrt(9 * Cin)).astype(np.float32)
+    o = np.arange(HW, dtype=np.int64)
+    (eo, ei, et) = ([], [], [])
+    for t in range(9):
+        off = np.sort(rng.choice(HW, size=fill, replace=False))
+        eo.append(np.repeat(o, fill))
+        ei.append(((o[:, None] + off[None, :]) % HW).reshape(-1))
+        et.append(np.full(HW * fill, t))
+    coef = (rng.rand(9 * HW * fill) / fill).astype(np.float32)
+    lastcol = np.concatenate((rng.randn(Cout * HW), [1.0])).astype(np.float32)
+    return ksp.Conv2dTiledMatrix.fromtaps((Cin, H, H), (Cout, H, H), taps, np.concatenate(eo), np.concatenate(ei), np.concatenate(et), coef, lastcol)
+
+
+def split_table(args):
+    """--split: per layer shape, in ONE process, narrow='mfma' without the keyword (the fused operator on the channel-lane kernel: what a narrow forward ran before) and with
+    narrow_split=True (the narrow split route, offered whatever the cost rule says: NARROW_SPLIT_MIN_GAIN = 0 for the measurement) at 1, 8 and 32 images, ReLU fused; next to
+    each pair the gate() ratio of the route against the fused kernel's bits, and what narrow_split_capable() says with the constants in the tree.  --one-forward: after one
+    warm-up call per width, ONE route call per layer and width and nothing else (the program for a kernel trace; --split --from-trace sums its four steps)."""
+    import numpy as np
+    from keynet_amd import sparse as ksp
+    from keynet_amd.layer import gate
+    dev = torch.device('cuda:0')
+    layers = [l for l in SPLIT_LAYERS if not args.layers or l[0] in args.layers]
+    lines = ['', '== tools/narrow_latency.py --split: filled-in synthetic operators of the VGG-16 conv shapes, contract \'split\', ReLU fused; %s, torch %s' % (torch.cuda.get_device_name(0), torch.__version__),
+             "   fused = torchdot(narrow='mfma') (the channel-lane kernel, summed stored values): %d warm-up + median of %d calls;  route = the same call with narrow_split=True: %d + %d calls; HIP events"
+             % (1, args.fused_calls, args.warmup, args.forwards),
+             '   %-8s %4s %4s %4s %5s %9s | %6s | %12s | %12s | %7s | %10s | %s' % ('layer', 'Cin', 'Cout', 'H', 'fill', 'entries', 'images', 'fused [ms]', 'route [ms]', 'gain', 'gate ratio', 'narrow_split_capable')]
+    for (name, Cin, Cout, H, fill) in layers:
+        rng = np.random.RandomState(H + Cin)
+        t0 = time.time()
+        W = _split_operator(rng, Cin, Cout, H, fill)
+        x32 = torch.randn(W.shape[1], 32, device=dev)
+        x32[-1] = 1.0
+        print('%s built in %.0f s (fill factor %.0f)' % (name, time.time() - t0, W.fill_factor()), flush=True)
+        for n in SPLIT_IMAGES:
+            x = x32[:, :n].contiguous()
+            kw = dict(relu=True, exact='split', narrow='mfma', narrow32=n > ksp.NARROW_MAX)
+            rule = W.narrow_split_capable(n)
+            W.NARROW_SPLIT_MIN_GAIN = 0.0
+            try:
+                if not W.narrow_split_route(n, True, dev):
+                    # (conv1_1 at 5 .. 32 images: Cin <= 4 keeps a large layer on the channel-lane kernel, narrow_mfma_loses in csrc/kn_internal.h -- no route, the call is the fused one)
+                    lines.append('   %-8s %4d %4d %4d %5d %9d | %6d | the channel-mixing operator does not plan the matrix-core narrow kernel at this width: no route, the keyword changes nothing'
+                                 % (name, Cin, Cout, H, fill, len(W._taps['ent_out']), n))
+                    print(lines[-1], flush=True)
+                    continue
+                if args.one_forward:
+                    W.torchdot(x, narrow_split=True, **kw)
+                    torch.cuda.synchronize()
+                    print('TRACE: %s n=%d' % (name, n), flush=True)
+                    W.torchdot(x, narrow_split=True, **kw)
+                    torch.cuda.synchronize()
+                    continue
+                ys = W.torchdot(x, narrow_split=True, **kw)
+                tr = timed(lambda: W.torchdot(x, narrow_split=True, **kw), args.forwards, args.warmup)
+            finally:
+                del W.NARROW_SPLIT_MIN_GAIN
+            yf = W.torchdot(x, **kw)
+            tf = timed(lambda: W.torchdot(x, **kw), args.fused_calls, 1)
+            (ratio, _, _, _) = gate(ys, yf)
+            (mf, mr) = (statistics.median(tf), statistics.median(tr))
+            lines.append('   %-8s %4d %4d %4d %5d %9d | %6d | %12.3f | %12.3f | %6.1fx | %10.3g | %s' % (name, Cin, Cout, H, fill, len(W._taps['ent_out']), n, mf, mr, mf / mr, ratio, rule))
+            print(lines[-1], flush=True)
+            del ys, yf
+        del W, x32
+        torch.cuda.empty_cache()
+    if args.one_forward:
+        return
+    text = '\n'.join(lines) + '\n'
+    print(text)
+    with open(args.out or os.path.join(ROOT, 'profiles', 'r14_narrow_split.txt'), 'a') as f:
+        f.write(text)
+
+
+def split_trace_table(args):
+    """--split --from-trace: the four steps of the route, per layer and width, from the kernel trace of a `--split --one-forward` run (device timestamps).  Every (layer, width)
+    ran the route twice (a warm-up call, then the traced one) and a call ends with its matrix-core narrow launch: the second of each pair is reported."""
+    import csv
+    with open(args.from_trace, newline='') as f:
+        rows = sorted(csv.DictReader(f), key=lambda r: int(r['Start_Timestamp']))
+    (calls, cur) = ([], [])
+    for r in rows:
+        cur.append((r['Kernel_Name'], (int(r['End_Timestamp']) - int(r['Start_Timestamp'])) / 1e3))
+        if 'convtaps_narrow_mfma_kernel' in r['Kernel_Name']:
+            calls.append(cur)
+            cur = []
+    layers = [l for l in SPLIT_LAYERS if not args.layers or l[0] in args.layers]
+    routed = lambda Cin, Cout, H, n: not (Cin <= 4 and n > 4 and H * H * ((Cout + 63) // 64) >= 4096)      # (narrow_mfma_loses, csrc/kn_internal.h: those widths have no route and ran nothing)
+    want = 2 * sum(1 for (_, Cin, Cout, H, _) in layers for n in SPLIT_IMAGES if routed(Cin, Cout, H, n))
+    assert len(calls) == want, 'expected %d route calls in the trace, found %d' % (want, len(calls))
+    lines = ['', '== tools/narrow_latency.py --split --from-trace: the steps of ONE narrow split call per layer and width (rocprofv3 --kernel-trace, device timestamps, us)',
+             '   %-8s %6s | %12s | %12s | %12s | %12s | %8s | %9s | %s' % ('layer', 'images', '1 X -> Xt', "2 Z' = K Xt", "3 Z' -> Z", '4 Y = op2 Z', 'others', 'sum', 'permute GB/s (steps 1 + 3: bytes read + written)')]
+    k = 1
+    for (name, Cin, Cout, H, fill) in layers:
+        for n in SPLIT_IMAGES:
+            if not routed(Cin, Cout, H, n):
+                continue
+            step = [0.0] * 5
+            for (kn, us) in calls[k]:
+                if 'planes_columns_kernel<true' in kn or 'planes_columns_kernelILb1' in kn:
+                    step[0] += us
+                elif 'planes_columns_kernel' in kn:
+                    step[2] += us
+                elif 'convtaps_narrow_mfma_kernel' in kn:
+                    step[3] += us
+                elif 'csr' in kn:
+                    step[1] += us
+                else:
+                    step[4] += us
+            moved = 2.0 * 4 * Cin * n * (H * H + 9 * H * H)
+            lines.append('   %-8s %6d | %12.1f | %12.1f | %12.1f | %12.1f | %8.1f | %9.1f | %.0f' % (name, n, step[0], step[1], step[2], step[3], step[4], sum(step), moved / ((step[0] + step[2]) * 1e-6) / 1e9))
+            k += 2
+    text = '\n'.join(lines) + '\n'
+    print(text)
+    with open(args.out or os.path.join(ROOT, 'profiles', 'r14_narrow_split.txt'), 'a') as f:
+        f.write(text)
+
+
 def narrow32_trace_table(args):
     """--narrow32 --from-trace: the conv launches of the last four forwards of a `--narrow32 --one-forward` run (device timestamps)."""
     import csv
@@ -718,7 +854,12 @@ def main():
     ap.add_argument('--mfma64', action='store_true', help="33 .. 64 images under exact_mode('auto'): padded forward, narrow='mfma' narrow64='mfma', two narrow32 forwards (profiles/r12_narrow64_mfma.txt)")
     ap.add_argument('--images', type=lambda v: tuple(int(k) for k in v.split(',')), default=N32_IMAGES, help='image counts of --narrow32')
     ap.add_argument('--blocks', action='store_true', help='with --narrow32: one conv5_x-shaped operator per column-block width (diagnostic build)')
+    ap.add_argument('--split', action='store_true', help="filled-in synthetic operators of the VGG-16 conv shapes: narrow='mfma' without and with narrow_split=True at 1, 8, 32 images (profiles/r14_narrow_split.txt)")
+    ap.add_argument('--layers', type=lambda v: tuple(v.split(',')), default=(), help='with --split: only these layer shapes (conv1_1, conv1_2, conv2_1, ..., conv5_x)')
+    ap.add_argument('--fused-calls', type=int, default=3, help='with --split: timed calls of the fused channel-lane launch (hundreds of ms each on the larger layers)')
     args = ap.parse_args()
+    if args.split:
+        return split_trace_table(args) if args.from_trace else split_table(args)
     if args.from_trace:
         return narrow64_trace_table(args) if (args.narrow64 or args.mfma64) else narrow32_trace_table(args) if args.narrow32 else rows_trace_table(args) if args.rows else linear_trace_table(args) if args.linear else trace_table(args)
     if args.narrow32 and args.blocks:
