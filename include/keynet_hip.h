@@ -144,6 +144,22 @@ enum kn_status {
                               The kernel forms every address into X in 64 bits: it takes any ldx (KN_FLAG_NARROW_ROWS next to it keeps its own rule for the parts it runs).
                               Honoured by kn_spmm, by kn_spmm_screen (max |Y| by the library's reduction pass over Y) and by kn_spmm_plan, which names the kernel, W, NV, the
                               number of 64-row chunks and the ring.  No reference counterpart. */
+#define KN_FLAG_NARROW_TAPS (0x400u)  /* = 1024.  A MODIFIER of the channel-lane form of KN_FLAG_NARROW: the same product, bit for bit, with the taps resident in registers.
+                              It takes effect ONLY where the call would run convtaps_narrow_kernel: on a conv-taps handle at n_vecs <= 8 with KN_FLAG_NARROW, or with
+                              KN_FLAG_NARROW_MFMA where that flag means KN_FLAG_NARROW (with KN_FLAG_EXACT, on an operator without a matrix-core form, on the Cin <= 4 rule).
+                              There an ELIGIBLE operator runs convtaps_narrow_taps_kernel: a wavefront owns P = 1 | 2 output pixels x 64 output channels x NV = 1 | 2 | 4 | 8
+                              running sums; the pixels' slot lists (activation offsets, packed tap indices, coefficients) stay in scalar registers for the whole walk, an
+                              input channel's value rows of all taps are loaded once into 16 vector registers, one channel ahead, and a step is one scalar activation load,
+                              one indexed register read and NV multiply / add pairs.  Same order (input channel outer, slots by ascending input pixel inner), same separate
+                              roundings, same bias entry, ReLU, homogeneous row and zero guard as KN_FLAG_NARROW: the result equals KN_FLAG_NARROW's and KN_FLAG_EXACT's.
+                              Eligible: no summed stored values (filled-in operators are not), at most 9 slots per output pixel, at most 16 taps, with
+                              coefficients or without, value rows in whole 64-channel blocks -- every conv layer of the tiled permutation / identity key-nets and the factored
+                              untiled convs.  Per call: 4 * Hin * Win * ldx < 2^32 (the kernel's byte offsets inside one channel's plane).  An operator with coefficients runs 5 .. 8
+                              columns as two launches, columns 0 .. 3 and the rest (its 8-column forms are not built), the same bits.
+                              Where it changes NOTHING (same kernels, same plan string, same bits; it never refuses what KN_FLAG_NARROW does not refuse): alone; on an
+                              ineligible operator or call; at n_vecs > 8 (the KN_FLAG_NARROW32 / KN_FLAG_NARROW64 ranges); where KN_FLAG_NARROW_MFMA runs the matrix-core
+                              kernel; on CSR, dense, float64 and chain handles; in kn_spmm_planes.  kn_spmm_plan names the kernel, P, NV, the masked width and `coef`.
+                              No reference counterpart. */
 
 typedef struct kn_operator* kn_handle_t;   /* opaque keyed operator resident in HBM */
 

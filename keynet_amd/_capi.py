@@ -22,6 +22,7 @@ KN_FLAG_NARROW32 = 64         # modifier: KN_FLAG_NARROW / KN_FLAG_NARROW_MFMA o
 KN_FLAG_NARROW64 = 128        # modifier: KN_FLAG_NARROW / KN_FLAG_NARROW_MFMA open 33 .. 64 columns (the order-preserving pipeline, one column per lane; include/keynet_hip.h); everywhere else it changes nothing
 KN_FLAG_NARROW64_MFMA = 256   # with KN_FLAG_NARROW_MFMA | KN_FLAG_NARROW64, without KN_FLAG_EXACT, on a conv-taps handle at 33 .. 64 columns: the f32 matrix-core product on 64-column tiles (include/keynet_hip.h); everywhere else it changes nothing
 KN_FLAG_NARROW_LINEAR = 512  # f32 CSR operators with big pattern groups (a keyed Linear) on the LDS value-stream kernel for 1 .. 32 columns (include/keynet_hip.h); everywhere else, 33 .. 64 columns included, it changes nothing
+KN_FLAG_NARROW_TAPS = 1024   # modifier of KN_FLAG_NARROW's channel-lane form at 1 .. 8 columns: an eligible conv-taps operator runs convtaps_narrow_taps_kernel, same bits (include/keynet_hip.h); everywhere else it changes nothing
 KN_FLAG_NARROW_ROWS = 32      # f32 CSR operators on the row-lane kernel for 1 .. 8 columns (include/keynet_hip.h); ignored by every other handle and beyond 8 columns
 KN_ABI_VERSION = 5
 

@@ -1439,6 +1439,8 @@ __global__ __launch_bounds__(256) void convtaps_narrow_kernel(ConvArgs p, int n_
     }
 }
 
+#include "kn_conv_narrow_taps.inc"
+
 // ---- order-preserving path for 9 .. 32 batch columns (KN_FLAG_NARROW32 next to KN_FLAG_NARROW): lanes are OUTPUT CHANNELS, columns come in blocks ---
 // convtaps_narrow_kernel's work item and arithmetic, statement for statement (input channel outer, the pixel's slots by ascending input pixel inner, DUPS committed
 // when the walk reaches the next pixel pair, separate multiply and add, the bias entry where it is stored, ReLU), with three differences of FORM:
@@ -2647,6 +2649,31 @@ static NarrowMfmaKernel narrow_mfma_kernel(bool two, bool coef) {
                : (coef ? convtaps_narrow_mfma_kernel<TM, false, true> : convtaps_narrow_mfma_kernel<TM, false, false>);
 }
 
+// NARROW with KN_FLAG_NARROW_TAPS on an eligible operator (narrow_taps_call): convtaps_narrow_taps_kernel (kn_conv_narrow_taps.inc).  The shipped forms: NT = 9 | 16 value
+// rows per channel (the next that holds the operator's taps; 16 without coefficients only), NV as the width, and P = 2 pixels per wavefront for NV = 1 | 2 without
+// coefficients -- every other two-pixel form, and every four-pixel form, compiled with scalar registers spilled into vector lanes and is not instantiated.  Nor are, for
+// the same reason, the forms with coefficients at NV = 8: an operator with coefficients runs 5 .. 8 columns as TWO column blocks, columns 0 .. 3 on the full NV = 4 form
+// and the other 1 .. 4 on the form of their width, each a launch of its own on a window of the caller's blocks (columns are independent sums: the same bits).
+// P = 2 only where the pixel pairs still give every SIMD its four wavefronts (4 096 items: VGG-16 conv5_x, 196 pixels x 8 channel blocks, stays at P = 1).
+typedef void (*NarrowTapsKernel)(ConvArgs, int, int, int64_t);
+template <int NT, int NV, bool FULL>
+static NarrowTapsKernel narrow_taps_kernel_of(int pix, bool coef) {
+    if constexpr (NV <= 2) {
+        if (pix == 2 && !coef) return convtaps_narrow_taps_kernel<NT, 2, NV, true, false>;
+    }
+    if constexpr (NV == 8) return coef ? nullptr : convtaps_narrow_taps_kernel<NT, 1, NV, FULL, false>;      // (no such form: narrow_choice cuts the columns into two blocks)
+    else return coef ? convtaps_narrow_taps_kernel<NT, 1, NV, FULL, true> : convtaps_narrow_taps_kernel<NT, 1, NV, FULL, false>;
+}
+template <int NT>
+static NarrowTapsKernel narrow_taps_kernel(int nv, bool full, int pix, bool coef) {
+    switch (nv) {                                        // (a width of 1 or 2 columns always fills its form)
+        case 1: return narrow_taps_kernel_of<NT, 1, true>(pix, coef);
+        case 2: return narrow_taps_kernel_of<NT, 2, true>(pix, coef);
+        case 4: return full ? narrow_taps_kernel_of<NT, 4, true>(pix, coef) : narrow_taps_kernel_of<NT, 4, false>(pix, coef);
+        default: return full ? narrow_taps_kernel_of<NT, 8, true>(pix, coef) : narrow_taps_kernel_of<NT, 8, false>(pix, coef);
+    }
+}
+
 struct NarrowChoice {
     ConvRegime regime = NARROW;
     NarrowWidth w = {1, 0, true};   // columns per lane (NARROW32: per column block) and whether the batch fills them, else the last ones are masked
@@ -2655,14 +2682,20 @@ struct NarrowChoice {
     int n_cb = 0;                   // 64-channel blocks
     int64_t n_nt = 0;               // NARROW_MFMA: tiles of 32 (pixel, image) columns
     int64_t n_wg = 0;               // work items (channel-lane kernels: of four wavefronts each)
+    int taps_pix = 0;               // NARROW: 0 = convtaps_narrow_kernel, else convtaps_narrow_taps_kernel with this many pixels per wavefront (1 | 2) ...
+    int taps_nt = 0;                // ... and this many value rows per channel (9 | 16)
+    int n_grp = 0;                  // ... over this many pixel groups
+    NarrowTapsKernel taps_b = nullptr;      // ... and, where the columns run as two blocks (coefficients at 5 .. 8 columns), the kernel of columns 4 .. and their width
+    NarrowWidth w_b = {1, 0, true};
     union {                         // the instantiation, by regime
         NarrowKernel lanes;
+        NarrowTapsKernel taps;
         Narrow32Kernel lanes32;
         NarrowMfmaKernel mfma;
     } kernel = {nullptr};
 };
 
-static NarrowChoice narrow_choice(const ConvTapsDev& A, const ConvArgs& a, ConvRegime regime) {
+static NarrowChoice narrow_choice(const ConvTapsDev& A, const ConvArgs& a, ConvRegime regime, uint32_t flags) {
     NarrowChoice c;
     c.regime = regime;
     c.w = narrow_width(a.n_vecs);
@@ -2672,6 +2705,23 @@ static NarrowChoice narrow_choice(const ConvTapsDev& A, const ConvArgs& a, ConvR
     if (regime == NARROW) {
         c.n_wg = (items + 3) / 4;
         c.kernel.lanes = narrow_kernel(c.w.nv, c.w.full, A.has_dups, coef);
+        // KN_FLAG_NARROW_TAPS: the tap-resident kernel where the operator is eligible and a channel's plane of this block stays inside its 32-bit byte offsets
+        if (narrow_taps_call(A, flags, a.n_vecs) && 4 * ((int64_t)a.HiWi * a.ldx + NARROW_MAX_VECS) < ((int64_t)1 << 32)) {
+            const int64_t pairs = (int64_t)((a.n_pix + 1) / 2) * c.n_cb;
+            const int pix = (!coef && c.w.nv <= 2 && pairs >= 4096) ? 2 : 1;
+            const bool nine = A.ntaps <= 9;
+            auto form = [&](const NarrowWidth& w) { return nine ? narrow_taps_kernel<9>(w.nv, w.full, pix, coef) : narrow_taps_kernel<16>(w.nv, w.full, pix, coef); };
+            if (coef && c.w.nv == 8) {              // two column blocks: 4 + (n_vecs - 4)
+                c.w = {4, 2, true};
+                c.w_b = narrow_width(a.n_vecs - 4);
+                c.taps_b = form(c.w_b);
+            }
+            c.taps_pix = pix;
+            c.taps_nt = nine ? 9 : 16;
+            c.n_grp = (a.n_pix + pix - 1) / pix;
+            c.n_wg = ((int64_t)c.n_grp * c.n_cb + 3) / 4;
+            c.kernel.taps = form(c.w);
+        }
     } else if (regime == NARROW32) {
         int nv = A.has_dups ? 16 : c.w.nv;
         if (4 * A.ntaps * A.cin_pad * A.cout_pad <= (2 << 20))
@@ -2714,7 +2764,23 @@ static int launch_narrow(const ConvTapsDev& A, const ConvArgs& a, const NarrowCh
         KN_LAUNCH("convtaps_narrow32_kernel<NV=" + std::to_string(w.nv) + (w.full ? "" : ", masked to " + std::to_string(a.n_vecs)) + ", " + std::to_string(c.n_colb) +
                       (c.n_colb == 1 ? " column block" : " column blocks") + (A.has_dups ? ", stored values summed" : "") + (coef ? ", coef" : "") + "> (lane = output channel)",
                   c.kernel.lanes32, grid, dim3(256), 0, s, a, c.n_cb, c.n_colb, n_wg);
-    else
+    else if (c.taps_pix > 0) {
+        auto name = [&](const NarrowWidth& wk, int64_t cols, const char* block) {
+            return "convtaps_narrow_taps_kernel<" + std::to_string(c.taps_nt) + " value rows, P=" + std::to_string(c.taps_pix) + ", NV=" + std::to_string(wk.nv) +
+                   (wk.full ? "" : ", masked to " + std::to_string(cols)) + (coef ? ", coef" : "") + std::string(block) + "> (lane = output channel, taps resident)";
+        };
+        if (c.taps_b) {                              // columns 0 .. 3, then columns 4 .. n_vecs - 1: each block a window of X and Y
+            ConvArgs a0 = a, a1 = a;
+            a0.n_vecs = 4;
+            a1.n_vecs = a.n_vecs - 4;
+            a1.X = a.X + 4;
+            a1.Y = a.Y + 4;
+            KN_LAUNCH(name(w, 4, ", columns 0 .. 3"), c.kernel.taps, grid, dim3(256), 0, s, a0, c.n_cb, c.n_grp, n_wg);
+            KN_LAUNCH(name(c.w_b, a1.n_vecs, ", columns 4 .."), c.taps_b, grid, dim3(256), 0, s, a1, c.n_cb, c.n_grp, n_wg);
+        } else {
+            KN_LAUNCH(name(w, a.n_vecs, ""), c.kernel.taps, grid, dim3(256), 0, s, a, c.n_cb, c.n_grp, n_wg);
+        }
+    } else
         KN_LAUNCH("convtaps_narrow_kernel<" + std::to_string(w.nv) + (w.full ? "" : ",masked to " + std::to_string(a.n_vecs)) + (A.has_dups ? ",stored values summed" : "") + (coef ? ",coef" : "") +
                       "> (lane = output channel)",
                   c.kernel.lanes, grid, dim3(256), 0, s, a, c.n_cb, n_wg);
@@ -2900,7 +2966,7 @@ int convtaps_spmm(const ConvTapsDev& A, const float* x, int64_t ldx, int64_t n_v
     switch (regime) {
         case NARROW_MFMA:
         case NARROW:
-        case NARROW32: rc = launch_narrow(A, a, narrow_choice(A, a, regime), s); break;
+        case NARROW32: rc = launch_narrow(A, a, narrow_choice(A, a, regime, flags), s); break;
         case NARROW64:
         case EXACT: rc = spmm_exact(A, a, regime == NARROW64, s); break;
         default: {

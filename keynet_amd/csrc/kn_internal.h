@@ -431,6 +431,22 @@ static inline bool narrow_mfma_loses(const ConvTapsDev& A, int64_t n_vecs) {
 static inline bool narrow_mfma_call(const ConvTapsDev& A, uint32_t flags, int64_t n_vecs) {
     return (flags & KN_FLAG_NARROW_MFMA) && !(flags & KN_FLAG_EXACT) && n_vecs <= narrow_max(flags, n_vecs) && n_vecs <= NARROW32_MAX_VECS && A.pt_ok && !narrow_mfma_loses(A, n_vecs);
 }
+// KN_FLAG_NARROW_TAPS, a modifier of regime NARROW (conv_regime below: KN_FLAG_NARROW at 1 .. 8 columns, or KN_FLAG_NARROW_MFMA where that flag means KN_FLAG_NARROW): an
+// ELIGIBLE operator runs convtaps_narrow_taps_kernel (kn_conv_narrow_taps.inc), bit for bit the channel-lane kernel's result.  Eligible, by what create recorded: no
+// summed stored values, at most NARROW_TAPS_MAX_SLOTS slots per output pixel (a 3 x 3 window), 1 .. NARROW_TAPS_MAX_TAPS taps, with coefficients or without,
+// value rows in whole 64-channel blocks.  Everywhere else -- alone, in every other regime, on an
+// ineligible operator, on other handle kinds, in kn_spmm_planes -- the bit is not read.  narrow_taps_call is the one place that reads it; narrow_choice (kn_conv.hip)
+// asks it and adds the per-call condition of the kernel's 32-bit byte offsets.
+static constexpr int NARROW_TAPS_MAX_SLOTS = 9;
+static constexpr int NARROW_TAPS_MAX_TAPS = 16;
+static inline bool narrow_taps_ok(const ConvTapsDev& A) {
+    return !A.has_dups && A.nslots > 0 && A.max_slots <= NARROW_TAPS_MAX_SLOTS && A.ntaps >= 1 && A.ntaps <= NARROW_TAPS_MAX_TAPS && A.cout_pad % 64 == 0;
+}
+// No shape or width is known to be slower than convtaps_narrow_kernel (profiles/r15_narrow_taps.txt); a measured one goes here, next to narrow_mfma_loses, from the kernel trace only
+static inline bool narrow_taps_loses(const ConvTapsDev& A, int64_t n_vecs) { return false; }
+static inline bool narrow_taps_call(const ConvTapsDev& A, uint32_t flags, int64_t n_vecs) {
+    return (flags & KN_FLAG_NARROW_TAPS) && n_vecs <= NARROW_MAX_VECS && narrow_taps_ok(A) && !narrow_taps_loses(A, n_vecs);
+}
 // The regime a call on a conv-taps handle takes: the one place that turns the flag word into one.  convtaps_spmm switches on it, kn_spmm asks it which side table
 // the call reads.  BF16X3 is the REQUEST (its planes are built for it): operands that do not qualify run as MFMA (mfma_choice, kn_conv.hip).
 // NARROW64 is the order-preserving product under every contract flag, launched by the order-preserving launcher (spmm_exact): an operator without the pipeline's shape

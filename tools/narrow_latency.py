@@ -63,6 +63,13 @@ images for the ladder.  The bars of the file are computed from the table.
     python tools/narrow_latency.py --split --one-forward                  # ONE narrow split call per layer and width behind a warm-up call (for a kernel trace)
     python tools/narrow_latency.py --split --from-trace DIR/.../*_kernel_trace.csv    # no GPU: the four steps of those calls
 
+    python tools/narrow_latency.py --taps [--out profiles/r15_narrow_taps.txt]
+    python tools/narrow_latency.py --taps --one-forward          # for n in (1, 2, 4, 8) ONE narrow forward, then ONE with narrow_taps=True (for a kernel trace)
+    python tools/narrow_latency.py --taps --from-trace DIR/.../*_kernel_trace.csv [--convs 13]       # no GPU: the conv launches of those forwards side by side
+
+--taps: keyed VGG-16 under the default contract, whole forwards narrow=True, narrow_rows=True, narrow_linear=True without and with narrow_taps=True at 1, 2, 4 and 8
+images in one process, the forms alternating, the logits torch.equal before any time is printed.
+
 --linear: keyed VGG-16 under the default contract, everything in one process with the forms alternating.  fc6, fc7 and fc8 alone: kn_spmm without and with
 KN_FLAG_NARROW_LINEAR at 1, 2, 3, 4, 8, 16, 32, 33 and 64 columns, up to 8 columns also next to KN_FLAG_NARROW_ROWS -- back to back on one block (values as warm as
 the layer's size lets them be) and behind a pass over a 512 MB buffer that leaves nothing of the operator on chip (what a forward sees) -- with the plan strings; then
@@ -808,6 +815,78 @@ def rows_trace_table(args):
         f.write(text)
 
 
+TAPS_FORM = dict(narrow=True, narrow_rows=True, narrow_linear=True)
+
+
+def taps_table(args, knet, xc, desc):
+    """--taps: see the module docstring."""
+    if args.one_forward:
+        for n in (1, 2, 4, 8):
+            x = xc[:n].t().contiguous().t()
+            for kw in (dict(), dict(narrow_taps=True)):
+                knet.forward_linear(x, **TAPS_FORM, **kw)      # (operators resident, kernels loaded)
+            torch.cuda.synchronize()
+        print('TRACE-FROM-HERE: for n in (1, 2, 4, 8) one narrow forward, then one with narrow_taps=True', flush=True)
+        for n in (1, 2, 4, 8):
+            x = xc[:n].t().contiguous().t()
+            for kw in (dict(), dict(narrow_taps=True)):
+                knet.forward_linear(x, **TAPS_FORM, **kw)
+                torch.cuda.synchronize()
+        return
+    rows = []
+    for n in (1, 2, 4, 8):
+        x = xc[:n].t().contiguous().t()
+        (plain, taps) = (knet.forward_linear(x, **TAPS_FORM), knet.forward_linear(x, narrow_taps=True, **TAPS_FORM))
+        torch.cuda.synchronize()
+        assert torch.equal(plain, taps), 'narrow_taps logits differ at %d image(s): max %g' % (n, float((plain - taps).abs().max()))
+        t = ([], [])
+        for _ in range(2):                        # the forms alternating, two rounds of --forwards / 2 each
+            t[0].extend(timed(lambda: knet.forward_linear(x, **TAPS_FORM), args.forwards // 2, args.warmup))
+            t[1].extend(timed(lambda: knet.forward_linear(x, narrow_taps=True, **TAPS_FORM), args.forwards // 2, args.warmup))
+        rows.append((n, [(statistics.median(v), min(v), max(v)) for v in t]))
+        print('n = %d done' % n, flush=True)
+    lines = ['', '== tools/narrow_latency.py --taps --workload %s: %s' % (args.workload, desc),
+             '   %s, torch %s; HIP events, %d warm-up + median of %d forwards (min .. max), forms alternating; logits torch.equal: yes'
+             % (torch.cuda.get_device_name(0), torch.__version__, args.warmup, args.forwards),
+             '   %6s | %-34s | %-34s | %s' % ('images', 'narrow, narrow_rows, narrow_linear [ms]', '... and narrow_taps=True [ms]', 'ratio')]
+    for (n, t) in rows:
+        cell = ['%8.3f (%.3f .. %.3f)' % v for v in t]
+        lines.append('   %6d | %-34s | %-34s | %.2fx' % (n, cell[0], cell[1], t[0][0] / t[1][0]))
+    text = '\n'.join(lines) + '\n'
+    print(text)
+    with open(args.out or os.path.join(ROOT, 'profiles', 'r15_narrow_taps.txt'), 'a') as f:
+        f.write(text)
+
+
+def taps_trace_table(args):
+    """--taps --from-trace: the conv launches of the last eight forwards of a `--taps --one-forward` run under rocprofv3 --kernel-trace (device timestamps)."""
+    import csv
+    with open(args.from_trace, newline='') as f:
+        rows = [r for r in csv.DictReader(f) if 'convtaps_narrow' in r['Kernel_Name']]
+    rows.sort(key=lambda r: int(r['Start_Timestamp']))
+    k = args.convs
+    assert len(rows) >= 8 * k, 'the trace holds %d narrow conv launches, fewer than 8 forwards of %d' % (len(rows), k)
+    rows = rows[-8 * k:]
+    us = lambda r: (int(r['End_Timestamp']) - int(r['Start_Timestamp'])) / 1e3
+    lines = ['', '== tools/narrow_latency.py --taps --from-trace: the conv launches of one narrow forward and one with narrow_taps=True (rocprofv3 --kernel-trace, device timestamps)']
+    for (i, n) in enumerate((1, 2, 4, 8)):
+        (old, new) = (rows[(2 * i) * k:(2 * i + 1) * k], rows[(2 * i + 1) * k:(2 * i + 2) * k])
+        assert all('narrow_taps' not in r['Kernel_Name'] for r in old), 'the forward without the keyword launched the tap-resident kernel'
+        lines.append('')
+        lines.append('   %d image(s) [us]: conv launch | workgroups | convtaps_narrow_kernel | with narrow_taps | ratio | kernel of the narrow_taps forward' % n)
+        for (j, (a, b)) in enumerate(zip(old, new)):
+            name = b['Kernel_Name']
+            form = name[name.index('<'):name.index('>') + 1] if ('narrow_taps' in name and '<' in name and '>' in name) else ''
+            lines.append('     %2d | %6d | %9.1f | %9.1f | %5.2fx | %s' % (j + 1, int(b.get('Grid_Size_X') or 0) // max(1, int(b.get('Workgroup_Size_X') or 1)), us(a), us(b), us(a) / us(b),
+                                                                  ('taps resident <NT, P, NV, FULL, COEF> = ' + form) if 'narrow_taps' in name else 'channel-lane'))
+        (sa, sb) = (sum(us(r) for r in old), sum(us(r) for r in new))
+        lines.append('     sum of the %d conv launches: %9.1f | %9.1f | %5.2fx' % (k, sa, sb, sa / sb))
+    text = '\n'.join(lines) + '\n'
+    print(text)
+    with open(args.out or os.path.join(ROOT, 'profiles', 'r15_narrow_taps.txt'), 'a') as f:
+        f.write(text)
+
+
 def trace_table(args):
     """--from-trace: the conv launches of the last eight forwards of a `--mfma --one-forward` run under rocprofv3 --kernel-trace (device timestamps)."""
     import csv
@@ -855,11 +934,14 @@ def main():
     ap.add_argument('--images', type=lambda v: tuple(int(k) for k in v.split(',')), default=N32_IMAGES, help='image counts of --narrow32')
     ap.add_argument('--blocks', action='store_true', help='with --narrow32: one conv5_x-shaped operator per column-block width (diagnostic build)')
     ap.add_argument('--split', action='store_true', help="filled-in synthetic operators of the VGG-16 conv shapes: narrow='mfma' without and with narrow_split=True at 1, 8, 32 images (profiles/r14_narrow_split.txt)")
+    ap.add_argument('--taps', action='store_true', help='whole forwards with and without narrow_taps=True at 1, 2, 4, 8 images (profiles/r15_narrow_taps.txt)')
     ap.add_argument('--layers', type=lambda v: tuple(v.split(',')), default=(), help='with --split: only these layer shapes (conv1_1, conv1_2, conv2_1, ..., conv5_x)')
     ap.add_argument('--fused-calls', type=int, default=3, help='with --split: timed calls of the fused channel-lane launch (hundreds of ms each on the larger layers)')
     args = ap.parse_args()
     if args.split:
         return split_trace_table(args) if args.from_trace else split_table(args)
+    if args.from_trace and args.taps:
+        return taps_trace_table(args)
     if args.from_trace:
         return narrow64_trace_table(args) if (args.narrow64 or args.mfma64) else narrow32_trace_table(args) if args.narrow32 else rows_trace_table(args) if args.rows else linear_trace_table(args) if args.linear else trace_table(args)
     if args.narrow32 and args.blocks:
@@ -873,6 +955,8 @@ def main():
     xc = sensor.fromtensor(imgs.to(dev)).encrypt().astensor()
     xc = xc.t().contiguous().t()                  # feature-major, as the layers hand blocks on
     print('keyed %s in %.0f s' % (desc, time.time() - t0), flush=True)
+    if args.taps:
+        return taps_table(args, knet, xc, desc)
     if args.mfma64:
         return mfma64_table(args, knet, xc, desc)
     if args.narrow64:
