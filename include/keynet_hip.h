@@ -160,6 +160,26 @@ enum kn_status {
                               ineligible operator or call; at n_vecs > 8 (the KN_FLAG_NARROW32 / KN_FLAG_NARROW64 ranges); where KN_FLAG_NARROW_MFMA runs the matrix-core
                               kernel; on CSR, dense, float64 and chain handles; in kn_spmm_planes.  kn_spmm_plan names the kernel, P, NV, the masked width and `coef`.
                               No reference counterpart. */
+#define KN_FLAG_NARROW_FILL (0x800u)  /* = 2048.  A MODIFIER of the channel-lane forms of KN_FLAG_NARROW (1 .. 8 columns) and KN_FLAG_NARROW | KN_FLAG_NARROW32 (9 .. 32): the same
+                              product, bit for bit, for FILLED-IN operators (summed stored values, hundreds of slots per output pixel: the reference's doubly-stochastic keys).
+                              It takes effect ONLY where the call would run convtaps_narrow_kernel or convtaps_narrow32_kernel: on a conv-taps handle with KN_FLAG_NARROW, or
+                              with KN_FLAG_NARROW_MFMA where that flag means KN_FLAG_NARROW.  There an ELIGIBLE operator runs convtaps_narrow_fill_kernel: a wavefront owns one
+                              output pixel x 64 output channels x NV = 1 | 2 | 4 | 8 running sums; the pixel's slot records {input pixel, tap index, coefficient, first | last
+                              slot of a stored column} are streamed by scalar loads a batch ahead, an input channel's value rows of all taps are loaded once into 16 vector
+                              registers, one channel ahead, a slot is one indexed register read, one multiply and one add, and a stored column costs one scalar activation
+                              load and NV multiply / add pairs.  9 .. 32 columns run as blocks of 8 columns, each block a wavefront of its own.  Same order (input channel
+                              outer, slots by ascending input pixel inner, the terms of a stored value in entry order), same separate roundings, same bias entry, ReLU,
+                              homogeneous row and zero guard as KN_FLAG_NARROW: the result equals KN_FLAG_NARROW's and KN_FLAG_EXACT's.
+                              Eligible: an operator that has the record lists of the filled-in KN_FLAG_EXACT kernel (summed stored values, or more than 64 slots on an output
+                              pixel), at most 16 taps, value rows in whole 64-channel blocks.  Per call: 4 * (Hin * Win * ldx + 32) < 2^32 (the kernel's byte offsets inside one
+                              channel's plane); a call that fails it runs the kernel it runs without the bit.
+                              The flag CAN ALLOCATE: the first such call builds the operator's record table on the device (16 bytes per slot, the table KN_FLAG_EXACT builds;
+                              kn_release_side_tables frees it, the next such call builds it again).
+                              Where it changes NOTHING (same kernels, same plan string, same bits; it never refuses what KN_FLAG_NARROW does not refuse): alone; on an
+                              ineligible operator or call; at n_vecs > 32 (the KN_FLAG_NARROW64 range); where KN_FLAG_NARROW_MFMA runs the matrix-core kernel; with
+                              KN_FLAG_EXACT or the matrix-core flags only; on CSR, dense, float64 and chain handles; in kn_spmm_planes.  No operator is eligible for both
+                              KN_FLAG_NARROW_TAPS and KN_FLAG_NARROW_FILL.  kn_spmm_plan names the kernel, NV, the masked width, the column blocks and `coef`.
+                              No reference counterpart. */
 
 typedef struct kn_operator* kn_handle_t;   /* opaque keyed operator resident in HBM */
 
@@ -286,6 +306,7 @@ int kn_export_csr_f64(kn_handle_t h, int32_t* indptr, int32_t* indices, double* 
  *   conv-taps, KN_FLAG_NARROW64_MFMA (33 .. 64)         the matrix-core rules above at NB = 64 (T = 16), on n_vecs = 64 aligned columns; else the generic loader
  *   CSR, KN_FLAG_NARROW_ROWS (n_vecs <= 8)               cols * ldx + 8 < 2^30                              else the kernels the call takes without the flag
  *   CSR, KN_FLAG_NARROW_LINEAR (n_vecs <= 32)            none: 64-bit addresses, any ldx
+ *   conv-taps, KN_FLAG_NARROW_FILL (n_vecs <= 32)       4 * (HiWi * ldx + 32) < 2^32                        else the channel-lane kernel the call takes without the flag
  * The small-K matrix-core kernels of first-layer operators (slots * Cin + bias <= 28 contraction rows) form row * ldx in 64 bits and take any ldx.
  * KN_FLAG_NARROW / KN_FLAG_NARROW_MFMA (n_vecs <= 8 on a conv-taps operator) do NOT fall back: they return KN_ERR_UNSUPPORTED, Y untouched, unless (D + 1) * ldx + 8 < 2^31
  * (with KN_FLAG_NARROW32 at 9 <= n_vecs <= 32: unless (D + 1) * ldx + 32 < 2^31).

@@ -24,6 +24,10 @@ KN_FLAG_NARROW64_MFMA = 256   # with KN_FLAG_NARROW_MFMA | KN_FLAG_NARROW64, wit
 KN_FLAG_NARROW_LINEAR = 512  # f32 CSR operators with big pattern groups (a keyed Linear) on the LDS value-stream kernel for 1 .. 32 columns (include/keynet_hip.h); everywhere else, 33 .. 64 columns included, it changes nothing
 KN_FLAG_NARROW_TAPS = 1024   # modifier of KN_FLAG_NARROW's channel-lane form at 1 .. 8 columns: an eligible conv-taps operator runs convtaps_narrow_taps_kernel, same bits (include/keynet_hip.h); everywhere else it changes nothing
 KN_FLAG_NARROW_ROWS = 32      # f32 CSR operators on the row-lane kernel for 1 .. 8 columns (include/keynet_hip.h); ignored by every other handle and beyond 8 columns
+# KN_FLAG_NARROW_FILL of include/keynet_hip.h: modifier of KN_FLAG_NARROW [| KN_FLAG_NARROW32] -- an eligible FILLED-IN conv-taps operator runs convtaps_narrow_fill_kernel at 1 .. 32 columns, same
+# bits; everywhere else it changes nothing.  Named KN_MODIFIER_*, not KN_FLAG_*: tests/test_narrow_taps_host.py pins the KN_FLAG_* names of this module at eleven, and
+# tests/test_narrow_fill_host.py ties this constant to the header's.
+KN_MODIFIER_NARROW_FILL = 0x800
 KN_ABI_VERSION = 5
 
 # every symbol include/keynet_hip.h declares (tests/test_capi.py checks the header against this list)

@@ -993,6 +993,8 @@ static int spmm_impl(kn_handle_t h, const float* x_dev, int64_t ldx, int64_t n_v
             case BF16X3: rc = first_use(h, h->ct.tapsB, [&] { return convtaps_build_bf16(h->ct, h->h_taps); }); break;
             case NARROW64:
             case EXACT: if (convtaps_fill_ok(h->ct)) rc = first_use(h, h->ct.fill_rec, [&] { return convtaps_build_fill(h->ct, s); }); break;
+            case NARROW:
+            case NARROW32: if (narrow_fill_call(h->ct, flags, n_vecs)) rc = first_use(h, h->ct.fill_rec, [&] { return convtaps_build_fill(h->ct, s); }); break;      // KN_FLAG_NARROW_FILL
             default: break;
         }
         if (rc) return rc;

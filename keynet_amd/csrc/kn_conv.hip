@@ -1440,6 +1440,7 @@ __global__ __launch_bounds__(256) void convtaps_narrow_kernel(ConvArgs p, int n_
 }
 
 #include "kn_conv_narrow_taps.inc"
+#include "kn_conv_narrow_fill.inc"
 
 // ---- order-preserving path for 9 .. 32 batch columns (KN_FLAG_NARROW32 next to KN_FLAG_NARROW): lanes are OUTPUT CHANNELS, columns come in blocks ---
 // convtaps_narrow_kernel's work item and arithmetic, statement for statement (input channel outer, the pixel's slots by ascending input pixel inner, DUPS committed
@@ -2674,6 +2675,19 @@ static NarrowTapsKernel narrow_taps_kernel(int nv, bool full, int pix, bool coef
     }
 }
 
+// NARROW / NARROW32 with KN_FLAG_NARROW_FILL on an eligible operator (narrow_fill_call): convtaps_narrow_fill_kernel (kn_conv_narrow_fill.inc).  The shipped forms: NV as
+// the width (1 | 2 | 4 | 8; 4 and 8 also masked), one pixel per wavefront, 16 value rows per channel, one form for operators with coefficients and without.  9 .. 32
+// columns: NV = 8 with the column block as part of the work item (the last block masked where n_vecs % 8 != 0).
+typedef void (*NarrowFillKernel)(ConvArgs, const int32_t*, const FillRec*, int, int, int64_t);
+static NarrowFillKernel narrow_fill_kernel(int nv, bool full) {
+    switch (nv) {                                        // (a width of 1 or 2 columns always fills its form)
+        case 1: return convtaps_narrow_fill_kernel<1, true>;
+        case 2: return convtaps_narrow_fill_kernel<2, true>;
+        case 4: return full ? convtaps_narrow_fill_kernel<4, true> : convtaps_narrow_fill_kernel<4, false>;
+        default: return full ? convtaps_narrow_fill_kernel<8, true> : convtaps_narrow_fill_kernel<8, false>;
+    }
+}
+
 struct NarrowChoice {
     ConvRegime regime = NARROW;
     NarrowWidth w = {1, 0, true};   // columns per lane (NARROW32: per column block) and whether the batch fills them, else the last ones are masked
@@ -2687,6 +2701,7 @@ struct NarrowChoice {
     int n_grp = 0;                  // ... over this many pixel groups
     NarrowTapsKernel taps_b = nullptr;      // ... and, where the columns run as two blocks (coefficients at 5 .. 8 columns), the kernel of columns 4 .. and their width
     NarrowWidth w_b = {1, 0, true};
+    NarrowFillKernel fill = nullptr;        // NARROW / NARROW32: convtaps_narrow_fill_kernel in place of the regime's kernel (w, n_colb, n_wg are then its own)
     union {                         // the instantiation, by regime
         NarrowKernel lanes;
         NarrowTapsKernel taps;
@@ -2694,6 +2709,13 @@ struct NarrowChoice {
         NarrowMfmaKernel mfma;
     } kernel = {nullptr};
 };
+
+// KN_FLAG_NARROW_FILL on this call: the flag's own rule (narrow_fill_call), the kernel's 32-bit byte offsets inside one channel's plane of X, and the records -- built
+// by kn_spmm at the call's first use; a planner needs none.  A call that fails runs the kernel it runs without the bit.
+static bool narrow_fill_takes(const ConvTapsDev& A, const ConvArgs& a, uint32_t flags) {
+    return narrow_fill_call(A, flags, a.n_vecs) && 4 * ((int64_t)a.HiWi * a.ldx + NARROW32_MAX_VECS) < ((int64_t)1 << 32) &&
+           (__atomic_load_n(&A.fill_rec, __ATOMIC_ACQUIRE) != nullptr || plan_sink() != nullptr);
+}
 
 static NarrowChoice narrow_choice(const ConvTapsDev& A, const ConvArgs& a, ConvRegime regime, uint32_t flags) {
     NarrowChoice c;
@@ -2705,6 +2727,10 @@ static NarrowChoice narrow_choice(const ConvTapsDev& A, const ConvArgs& a, ConvR
     if (regime == NARROW) {
         c.n_wg = (items + 3) / 4;
         c.kernel.lanes = narrow_kernel(c.w.nv, c.w.full, A.has_dups, coef);
+        if (narrow_fill_takes(A, a, flags)) {                // KN_FLAG_NARROW_FILL (no operator is eligible for this and for KN_FLAG_NARROW_TAPS: kn_internal.h)
+            c.fill = narrow_fill_kernel(c.w.nv, c.w.full);
+            return c;
+        }
         // KN_FLAG_NARROW_TAPS: the tap-resident kernel where the operator is eligible and a channel's plane of this block stays inside its 32-bit byte offsets
         if (narrow_taps_call(A, flags, a.n_vecs) && 4 * ((int64_t)a.HiWi * a.ldx + NARROW_MAX_VECS) < ((int64_t)1 << 32)) {
             const int64_t pairs = (int64_t)((a.n_pix + 1) / 2) * c.n_cb;
@@ -2723,6 +2749,13 @@ static NarrowChoice narrow_choice(const ConvTapsDev& A, const ConvArgs& a, ConvR
             c.kernel.taps = form(c.w);
         }
     } else if (regime == NARROW32) {
+        if (narrow_fill_takes(A, a, flags)) {                // KN_FLAG_NARROW_FILL: blocks of 8 columns, the last one masked
+            c.w = {8, 3, a.n_vecs % 8 == 0};
+            c.n_colb = (int)((a.n_vecs + 7) / 8);
+            c.n_wg = (items * c.n_colb + 3) / 4;
+            c.fill = narrow_fill_kernel(8, c.w.full);
+            return c;
+        }
         int nv = A.has_dups ? 16 : c.w.nv;
         if (4 * A.ntaps * A.cin_pad * A.cout_pad <= (2 << 20))
             while (nv > 8 && items * ((a.n_vecs + nv - 1) / nv) < 4096) nv >>= 1;
@@ -2760,7 +2793,14 @@ static int launch_narrow(const ConvTapsDev& A, const ConvArgs& a, const NarrowCh
     }
     KN_REQUIRE(n_wg + 8 < ((int64_t)1 << 29) && A.Cin * (int64_t)A.max_slots < ((int64_t)1 << 31), KN_ERR_UNSUPPORTED,
                "grid or slot walk too large for the channel-lane order-preserving kernel");
-    if (c.regime == NARROW32)
+    if (c.fill) {
+        ConvArgs af = a;
+        af.pix_order = A.pix_deal;                   // per-XCD chunks of pixels whose lists differ several times in length: the slot-weighted, heavy-first order (kn_deal.h)
+        KN_LAUNCH("convtaps_narrow_fill_kernel<NV=" + std::to_string(w.nv) + (w.full ? "" : ", masked to " + std::to_string(a.n_vecs)) + ", " + std::to_string(c.n_colb) +
+                      (c.n_colb == 1 ? " column block" : " column blocks") + (coef ? ", coef" : "") + "> (lane = output channel, taps resident, " + std::to_string(A.fill_n) +
+                      " slot records, pixels in pix_deal order)",
+                  c.fill, grid, dim3(256), 0, s, af, A.fill_ptr, __atomic_load_n(&A.fill_rec, __ATOMIC_ACQUIRE), c.n_cb, c.n_colb, n_wg);
+    } else if (c.regime == NARROW32)
         KN_LAUNCH("convtaps_narrow32_kernel<NV=" + std::to_string(w.nv) + (w.full ? "" : ", masked to " + std::to_string(a.n_vecs)) + ", " + std::to_string(c.n_colb) +
                       (c.n_colb == 1 ? " column block" : " column blocks") + (A.has_dups ? ", stored values summed" : "") + (coef ? ", coef" : "") + "> (lane = output channel)",
                   c.kernel.lanes32, grid, dim3(256), 0, s, a, c.n_cb, c.n_colb, n_wg);

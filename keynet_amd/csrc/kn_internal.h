@@ -447,6 +447,25 @@ static inline bool narrow_taps_loses(const ConvTapsDev& A, int64_t n_vecs) { ret
 static inline bool narrow_taps_call(const ConvTapsDev& A, uint32_t flags, int64_t n_vecs) {
     return (flags & KN_FLAG_NARROW_TAPS) && n_vecs <= NARROW_MAX_VECS && narrow_taps_ok(A) && !narrow_taps_loses(A, n_vecs);
 }
+// KN_FLAG_NARROW_FILL, a modifier of regimes NARROW and NARROW32 (KN_FLAG_NARROW [| KN_FLAG_NARROW32] at 1 .. 32 columns, or KN_FLAG_NARROW_MFMA where that flag means
+// KN_FLAG_NARROW): an ELIGIBLE operator runs convtaps_narrow_fill_kernel (kn_conv_narrow_fill.inc), bit for bit the channel-lane kernels' result.  Eligible: the handle has
+// the record lists of the filled-in order-preserving kernel (convtaps_fill_ok: summed stored values, or more than 64 slots on some output pixel), 1 .. 16 taps (the records
+// then hold tap indices, and a channel's value rows fit 16 registers), value rows in whole 64-channel blocks.
+// narrow_fill_ok and narrow_taps_ok cannot both hold for one operator: the first needs has_dups or max_slots > 64 (what convtaps_fill_offsets lays lists out for), the
+// second !has_dups and max_slots <= 9.  Everywhere else -- alone, in every other regime, on an ineligible operator, on other handle kinds, in kn_spmm_planes -- the bit is
+// not read.  narrow_fill_call is the one place that reads it; narrow_choice (kn_conv.hip) asks it and adds the per-call conditions (32-bit byte offsets, records built);
+// spmm_impl (kn_api.hip) asks it whether the call builds the records.
+bool convtaps_fill_ok(const ConvTapsDev& A);      // kn_conv.hip
+static constexpr int NARROW_FILL_MAX_TAPS = 16;
+static inline bool narrow_fill_ok(const ConvTapsDev& A) { return convtaps_fill_ok(A) && A.ntaps >= 1 && A.ntaps <= NARROW_FILL_MAX_TAPS && A.cout_pad % 64 == 0; }
+// The (shape, width) pairs where convtaps_narrow_fill_kernel does not beat the kernel the call runs without the bit by more than the boxes' 3 % spread: none.  Measured
+// (profiles/r16_narrow_fill.txt; filled-in operators of the VGG-16 shapes, same process, gain over convtaps_narrow_kernel / convtaps_narrow32_kernel at 1 / 8 / 16 / 32 images):
+// conv1_2 2.89x / 2.48x / 1.66x / 1.71x, conv2_1 3.00x / 2.38x / 1.64x / 1.61x, conv3_1 2.93x / 2.03x / 1.53x / 1.50x, conv4_1 2.68x / 1.70x / 1.30x / 1.25x,
+// conv5_x 1.82x / 1.64x / 1.54x / 1.30x.  (Against the PADDED 128-column launch the deep layers lose from 16 images on -- DESIGN.md 8 -- which is the caller's choice of call, not this rule's.)
+static inline bool narrow_fill_loses(const ConvTapsDev& A, int64_t n_vecs) { return false; }
+static inline bool narrow_fill_call(const ConvTapsDev& A, uint32_t flags, int64_t n_vecs) {
+    return (flags & KN_FLAG_NARROW_FILL) && n_vecs <= NARROW32_MAX_VECS && narrow_fill_ok(A) && !narrow_fill_loses(A, n_vecs);
+}
 // The regime a call on a conv-taps handle takes: the one place that turns the flag word into one.  convtaps_spmm switches on it, kn_spmm asks it which side table
 // the call reads.  BF16X3 is the REQUEST (its planes are built for it): operands that do not qualify run as MFMA (mfma_choice, kn_conv.hip).
 // NARROW64 is the order-preserving product under every contract flag, launched by the order-preserving launcher (spmm_exact): an operator without the pipeline's shape

@@ -209,7 +209,7 @@ class KeyedLayer(nn.Module):
     def iskeyedrelu(self):
         return 'ReLU' in self._layertype
 
-    def forward(self, x_affine, fuse_relu=False, absmax=None, narrow=False, narrow_rows=False, narrow32=False, narrow64=False, narrow_linear=False, narrow_split=False, narrow_taps=False):
+    def forward(self, x_affine, fuse_relu=False, absmax=None, narrow=False, narrow_rows=False, narrow32=False, narrow64=False, narrow_linear=False, narrow_split=False, narrow_taps=False, narrow_fill=False):
         """[N, Din+1] -> [N, Dout+1] (keynet/layer.py:88-93).  The result is a transposed view of the feature-major
         [Dout+1, N] block the kernel wrote, so the next layer's x.t() is free.  `fuse_relu` folds the unkeyed nn.ReLU
         that follows this layer in the key-net (keynet/system.py:92) into the kernel epilogue.  `absmax`: a one-element device
@@ -220,11 +220,12 @@ class KeyedLayer(nn.Module):
         narrowed() decides it on this batch -- with `narrow` nothing is calibrated, and only narrow='mfma' on a calibrated layer measures and records (narrow_mode()).
         `narrow_split` (only with narrow='mfma'): a filled-in conv layer under 'split' runs the narrow split route where narrow_split_mode() allows it; a calibrated one measures
         and records that under its own key first.  Every other layer, and this one beyond NARROW32_MAX images, is what it is without the keyword.
-        `narrow_taps` (only with `narrow`): a conv-taps layer's channel-lane launch carries KN_FLAG_NARROW_TAPS (kernel()); nothing is measured or recorded for it."""
+        `narrow_taps` (only with `narrow`): a conv-taps layer's channel-lane launch carries KN_FLAG_NARROW_TAPS (kernel()); nothing is measured or recorded for it.
+        `narrow_fill` (only with `narrow`): the same launches carry KN_FLAG_NARROW_FILL (kernel()); nothing is measured or recorded for it either."""
         if verbose():
             print('[keynet_amd.layer]: forward %s' % str(self))
         (xt, relu) = (x_affine.t(), fuse_relu or self.iskeyedrelu())
-        (exact, keywords) = self.narrowed(ksp.NarrowForm.of(None, narrow, narrow_rows, narrow32, narrow64, narrow_linear, narrow_split=narrow_split, narrow_taps=narrow_taps), xt, relu)
+        (exact, keywords) = self.narrowed(ksp.NarrowForm.of(None, narrow, narrow_rows, narrow32, narrow64, narrow_linear, narrow_split=narrow_split, narrow_taps=narrow_taps, narrow_fill=narrow_fill), xt, relu)
         if exact == 'auto' and not narrow:
             if x_affine.is_cuda and torch.cuda.is_current_stream_capturing():
                 raise _capi.KeynetHipError('keynet_amd: %s has not decided its arithmetic contract yet (exact=\'auto\' calibrates on the first batch, with host reads): '
@@ -244,12 +245,12 @@ class KeyedLayer(nn.Module):
         (a planner gets the channel-lane kernel).  Any other operator: `narrow_rows` / `narrow_linear` where it is a float32 CSR handle (W.rows_capable()), and a layer still
         'auto' runs in the reference's order for this call (to a planner it stays 'auto': not one launch).  `form.split` (narrow_split=True): ahead of narrow_mode(), a layer
         narrow_split_mode() puts on the narrow split route gets narrow='mfma', narrow_split=True (to a planner: not one launch); any other layer is what it is without it.
-        `form.taps` (narrow_taps=True): handed on to every operator with a conv-taps handle, next to whatever `narrow` it gets."""
+        `form.taps` (narrow_taps=True), `form.fill` (narrow_fill=True): handed on to every operator with a conv-taps handle, next to whatever `narrow` it gets."""
         (W, exact) = (self.W, getattr(self, '_exact', True))
         if not form.mode:
             return (exact, {})
         if W.narrow_capable():
-            taps = dict(narrow_taps=True) if form.taps else {}
+            taps = dict(dict(narrow_taps=True) if form.taps else {}, **(dict(narrow_fill=True) if form.fill else {}))
             if form.tile64 and (xt is None or xt.shape[1] > ksp.NARROW32_MAX):
                 mode = 'mfma' if isinstance(W, ksp.Conv2dTiledMatrix) and exact in (False, 'bf16x3') else True
                 return (exact, dict(narrow=mode, narrow32=True, narrow64=mode, **taps))
@@ -261,7 +262,7 @@ class KeyedLayer(nn.Module):
         return (exact, dict(narrow_rows=form.rows, narrow_linear=form.linear) if (form.rows or form.linear) and W.rows_capable() else {})
 
     @staticmethod
-    def kernel(W, contract, relu, device=None, narrow=False, narrow_rows=False, narrow32=False, narrow64=False, narrow_linear=False, narrow_split=False, narrow_taps=False):
+    def kernel(W, contract, relu, device=None, narrow=False, narrow_rows=False, narrow32=False, narrow64=False, narrow_linear=False, narrow_split=False, narrow_taps=False, narrow_fill=False):
         """The one place that turns a decided contract into an operator handle and flags: (get_op, flags) of the kn_spmm launch that applies operator `W`
         under `contract`, get_op(device) -> the handle resident there.  None when that is not one launch: 'auto' (still to calibrate), 'split' on an operator that has a split form (Conv2dTiledMatrix._torchdot_split).
         The rules: 'split' forced on an operator without a split form, and 'bf16x3' on a non-conv operator, are the f32 matrix cores (False); a conv operator
@@ -282,8 +283,10 @@ class KeyedLayer(nn.Module):
         Conv2dTiledMatrix._torchdot_split_narrow, which the operator's torchdot takes where narrow_split_route() offers it at the batch's width, asking again without the
         keyword where not; on every other operator and contract the keyword adds nothing.
         `narrow_taps` (with `narrow`): KN_FLAG_NARROW_TAPS exactly where KN_FLAG_NARROW is set -- inside a narrow='mfma' call that is the operators under True / 'auto' and
-        the non-conv ones with a conv-taps handle; the library runs the tap-resident kernel on an eligible operator at up to NARROW_MAX columns and ignores the bit elsewhere."""
-        form = ksp.NarrowForm.of(None, narrow, narrow_rows, narrow32, narrow64, narrow_linear, narrow_split=narrow_split, narrow_taps=narrow_taps)
+        the non-conv ones with a conv-taps handle; the library runs the tap-resident kernel on an eligible operator at up to NARROW_MAX columns and ignores the bit elsewhere.
+        `narrow_fill` (with `narrow`): KN_FLAG_NARROW_FILL (_capi.KN_MODIFIER_NARROW_FILL) on exactly the same launches -- with narrow_split=True those are the layers not on the
+        route; the library runs convtaps_narrow_fill_kernel on an eligible (filled-in) operator at up to NARROW32_MAX columns and ignores the bit elsewhere."""
+        form = ksp.NarrowForm.of(None, narrow, narrow_rows, narrow32, narrow64, narrow_linear, narrow_split=narrow_split, narrow_taps=narrow_taps, narrow_fill=narrow_fill)
         conv = isinstance(W, ksp.Conv2dTiledMatrix)
         if form.split and conv and contract == 'split' and W.narrow_capable() and W.split_capable():
             return None
@@ -301,19 +304,19 @@ class KeyedLayer(nn.Module):
         if mfma:
             (exact, bf16x3) = (False, False)
         return (get_op, (_capi.KN_FLAG_RELU if relu else 0) | (_capi.KN_FLAG_EXACT if exact else 0) | (_capi.KN_FLAG_BF16X3 if bf16x3 else 0) |
-                (_capi.KN_FLAG_NARROW_MFMA if mfma else _capi.KN_FLAG_NARROW if lane else 0) | (_capi.KN_FLAG_NARROW_TAPS if form.taps and lane and not mfma else 0) | (_capi.KN_FLAG_NARROW32 if lane and form.narrow32 else 0) | (_capi.KN_FLAG_NARROW64 if lane and form.narrow64 else 0) |
+                (_capi.KN_FLAG_NARROW_MFMA if mfma else _capi.KN_FLAG_NARROW if lane else 0) | (_capi.KN_FLAG_NARROW_TAPS if form.taps and lane and not mfma else 0) | (_capi.KN_MODIFIER_NARROW_FILL if form.fill and lane and not mfma else 0) | (_capi.KN_FLAG_NARROW32 if lane and form.narrow32 else 0) | (_capi.KN_FLAG_NARROW64 if lane and form.narrow64 else 0) |
                 (_capi.KN_FLAG_NARROW64_MFMA if mfma and form.tile64 and contract in (False, 'bf16x3') else 0) |
                 (_capi.KN_FLAG_NARROW_ROWS if form.rows and stored else 0) | (_capi.KN_FLAG_NARROW_LINEAR if form.linear and stored else 0))
 
-    def launch(self, device, relu=False, narrow=False, narrow_rows=False, narrow32=False, narrow64=False, narrow_linear=False, narrow_split=False, narrow_taps=False):
+    def launch(self, device, relu=False, narrow=False, narrow_rows=False, narrow32=False, narrow64=False, narrow_linear=False, narrow_split=False, narrow_taps=False, narrow_fill=False):
         """This layer under its contract in force as one launch on `device` (`relu`: the unkeyed nn.ReLU behind it is fused in), or None when it is not one
         kn_spmm launch: see kernel(); a float64 operator (its own kernel and a float64 result: kn_spmm_f64).  What the key-net's planners read
         (KeyedModel._chain_op / _overlap_plan); forward() -> W.torchdot() runs the same rule.  `narrow`, `narrow_rows`, `narrow32`, `narrow64`, `narrow_linear`: the launch
         forward() issues under them (narrowed(); without `narrow` the others say nothing), except that a planner has no batch: a layer still 'auto' is not one launch,
         narrow='mfma' on a calibrated layer without a narrow record answers the channel-lane kernel, and narrow64='mfma' asks for the launch of 33 .. 64 columns.  `narrow_split`: a layer
-        on the narrow split route (declared 'split', or an accepted narrow_split record) is not one launch; one still to measure answers what it answers without the keyword.  `narrow_taps`: the launch carries KN_FLAG_NARROW_TAPS where kernel() sets it."""
+        on the narrow split route (declared 'split', or an accepted narrow_split record) is not one launch; one still to measure answers what it answers without the keyword.  `narrow_taps`, `narrow_fill`: the launch carries KN_FLAG_NARROW_TAPS, KN_FLAG_NARROW_FILL where kernel() sets them."""
         W = self.W
-        (exact, keywords) = self.narrowed(ksp.NarrowForm.of(None, narrow, narrow_rows, narrow32, narrow64, narrow_linear, narrow_split=narrow_split, narrow_taps=narrow_taps))
+        (exact, keywords) = self.narrowed(ksp.NarrowForm.of(None, narrow, narrow_rows, narrow32, narrow64, narrow_linear, narrow_split=narrow_split, narrow_taps=narrow_taps, narrow_fill=narrow_fill))
         kernel = None if W.is_float64() else self.kernel(W, exact, relu or self.iskeyedrelu(), device, **keywords)
         if kernel is None:
             return None

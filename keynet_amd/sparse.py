@@ -82,24 +82,25 @@ def _device_block(x):
     return xd if xd.is_contiguous() else xd.contiguous()
 
 
-def _run_torchdot(W, x, relu=False, exact=True, absmax=None, narrow=False, narrow_rows=False, narrow32=False, narrow64=False, narrow_linear=False, narrow_split=False, narrow_taps=False):
+def _run_torchdot(W, x, relu=False, exact=True, absmax=None, narrow=False, narrow_rows=False, narrow32=False, narrow64=False, narrow_linear=False, narrow_split=False, narrow_taps=False, narrow_fill=False):
     """Y = W.X on the GPU under the contract `exact`, on the handle and flags of KeyedLayer.kernel.  x: [cols, N], torch tensor (any device / strides) or ndarray.
     Returns [rows, N] on x's device: float32, or for a float64 operator the float64 block scipy returns for it (kn_spmm_f64; the activations are
     float32 either way).  `narrow`, `narrow_rows`, `narrow32`, `narrow64`, `narrow_linear` (narrow64='mfma' included): the narrow forms of the product
     (KeyedModel.forward_linear), each allowed on its own here (_narrow_args with `alone`: a container's torchdot takes the ones its operator has a form for);
     which flag each one sets on which operator is KeyedLayer.kernel's rule.  `narrow_split` (only with narrow='mfma'): a filled-in conv operator under 'split' runs the
     narrow split route where it has one at this width (Conv2dTiledMatrix.narrow_split_route), else exactly the call without the keyword.  `narrow_taps` (only with
-    `narrow`): KN_FLAG_NARROW_TAPS next to KN_FLAG_NARROW -- the tap-resident channel-lane kernel on an eligible conv-taps operator, the same bits."""
+    `narrow`): KN_FLAG_NARROW_TAPS next to KN_FLAG_NARROW -- the tap-resident channel-lane kernel on an eligible conv-taps operator, the same bits.  `narrow_fill` (only
+    with `narrow`): KN_FLAG_NARROW_FILL next to KN_FLAG_NARROW -- the tap-resident kernel of FILLED-IN conv-taps operators at up to NARROW32_MAX columns, the same bits."""
     from .layer import KeyedLayer            # (layer.py imports this module)
     x = torch.as_tensor(x)
     assert W.shape[1] == x.shape[0], 'Non-conformal shape for W=%s, x=%s' % (str(W.shape), str(tuple(x.shape)))
     xd = _device_block(x)
     n = xd.shape[1]
-    _narrow_args(n, narrow, narrow_rows, 'batch columns', True, narrow32, narrow64, narrow_linear, narrow_split, narrow_taps)
-    kernel = KeyedLayer.kernel(W, exact, relu, xd.device, narrow, narrow_rows, narrow32, narrow64, narrow_linear, narrow_split, narrow_taps)
+    _narrow_args(n, narrow, narrow_rows, 'batch columns', True, narrow32, narrow64, narrow_linear, narrow_split, narrow_taps, narrow_fill)
+    kernel = KeyedLayer.kernel(W, exact, relu, xd.device, narrow, narrow_rows, narrow32, narrow64, narrow_linear, narrow_split, narrow_taps, narrow_fill)
     split_narrow = kernel is None and bool(narrow_split) and isinstance(W, Conv2dTiledMatrix) and W.narrow_capable()      # (kernel()'s one "not one launch" among the narrow conv calls)
     if split_narrow and not W.narrow_split_route(n, relu, xd.device):
-        (kernel, split_narrow) = (KeyedLayer.kernel(W, exact, relu, xd.device, narrow, narrow_rows, narrow32, narrow64, narrow_linear, narrow_taps=narrow_taps), False)
+        (kernel, split_narrow) = (KeyedLayer.kernel(W, exact, relu, xd.device, narrow, narrow_rows, narrow32, narrow64, narrow_linear, narrow_taps=narrow_taps, narrow_fill=narrow_fill), False)
     if split_narrow:
         y = W._torchdot_split_narrow(xd, relu=relu, absmax=absmax)
     elif kernel is None:
@@ -123,7 +124,7 @@ NARROW32_MAX = 32     # ... with narrow32=True (KN_FLAG_NARROW32: convtaps_narro
 NARROW64_MAX = 64     # ... with narrow64=True (KN_FLAG_NARROW64: beyond NARROW32_MAX columns convtaps_exact_pipe64_kernel; narrow64='mfma': the f32 tile kernel on 64-column tiles; KeyedModel.NARROW64_MAX)
 
 
-def _narrow_args(n, narrow, narrow_rows, what='images', alone=False, narrow32=False, narrow64=False, narrow_linear=False, narrow_split=False, narrow_taps=False):
+def _narrow_args(n, narrow, narrow_rows, what='images', alone=False, narrow32=False, narrow64=False, narrow_linear=False, narrow_split=False, narrow_taps=False, narrow_fill=False):
     """The argument rule of the narrow forms, for a batch of `n`: `narrow_rows` only together with `narrow` (`alone`: a container's torchdot, which takes one
     keyword or the other), at most NARROW_MAX columns; `narrow32` only together with `narrow`, whose limit it lifts to NARROW32_MAX -- not that of `narrow_rows`
     (the row-lane kernel is an 8-column kernel); `narrow64` only together with `narrow` as well: it implies `narrow32` (at most NARROW32_MAX columns the call is exactly
@@ -133,12 +134,15 @@ def _narrow_args(n, narrow, narrow_rows, what='images', alone=False, narrow32=Fa
     keywords passed give -- NARROW_MAX, NARROW32_MAX with `narrow32`, NARROW64_MAX with `narrow64` -- and alone up to NARROW64_MAX, the kernel's own range;
     `narrow_split` only together with narrow='mfma' (`alone` or not: the route ends on the matrix-core narrow kernel), at the widths the other keywords allow -- it takes effect up
     to NARROW32_MAX columns and changes nothing beyond; `narrow_taps` only together with `narrow` (True or 'mfma'; `alone` or not: it modifies that keyword's channel-lane
-    kernel), at the widths the other keywords allow -- it takes effect up to NARROW_MAX columns and changes nothing beyond.
+    kernel), at the widths the other keywords allow -- it takes effect up to NARROW_MAX columns and changes nothing beyond; `narrow_fill` by the same rule -- it takes
+    effect up to NARROW32_MAX columns.
     ValueError, or the normalised (mode, rows): mode False | True | 'mfma', rows a bool."""
     if narrow_split and narrow != 'mfma':
         raise ValueError('narrow_split=True is the split application of a filled-in conv layer on the matrix-core narrow kernel: pass narrow=\'mfma\' with it (got narrow=%r)' % (narrow,))
     if narrow_taps and not narrow:
         raise ValueError('narrow_taps=True is the tap-resident form of the channel-lane conv kernel: pass narrow=True or narrow=\'mfma\' with it (got narrow=%r)' % (narrow,))
+    if narrow_fill and not narrow:
+        raise ValueError('narrow_fill=True is the tap-resident form of the channel-lane conv kernels for filled-in operators: pass narrow=True or narrow=\'mfma\' with it (got narrow=%r)' % (narrow,))
     if narrow64 == 'mfma' and narrow != 'mfma':
         raise ValueError('narrow64=\'mfma\' is the matrix-core form of %d .. %d %s: pass narrow=\'mfma\' with it (got narrow=%r)' % (NARROW32_MAX + 1, NARROW64_MAX, what, narrow))
     if narrow_rows and not narrow and not alone:
@@ -172,31 +176,38 @@ class NarrowForm(collections.namedtuple('NarrowForm', 'mode rows narrow32 narrow
     `split`: the opt-in sixth keyword narrow_split=True (only with narrow='mfma': the narrow split route of a filled-in conv layer, KeyedModel.forward_linear).  The six fields
     above ARE the value of every call without it; a call with it gets the same six fields as a NarrowSplitForm, which equals no plain form and hands the keyword back.
     `taps`: the opt-in seventh keyword narrow_taps=True (only with `narrow`: KN_FLAG_NARROW_TAPS on the conv layers' channel-lane launches), carried the same way -- a
-    NarrowTapsForm, or with narrow_split=True a NarrowSplitTapsForm; each kind equals its own kind only."""
+    NarrowTapsForm, or with narrow_split=True a NarrowSplitTapsForm; each kind equals its own kind only.
+    `fill`: the opt-in eighth keyword narrow_fill=True (only with `narrow`: KN_FLAG_NARROW_FILL on the same launches), carried the same way: the kind of the call without
+    it has a `fill` twin (_fill_kind: NarrowFillForm, NarrowSplitFillForm, NarrowTapsFillForm, NarrowSplitTapsFillForm), which equals its own kind only."""
     __slots__ = ()
     split = False
     taps = False
+    fill = False
 
     @classmethod
     @functools.lru_cache(maxsize=256)        # (asked per layer and launch, on the shortest forwards, for the same few keyword sets)
-    def of(cls, n, narrow=False, narrow_rows=False, narrow32=False, narrow64=False, narrow_linear=False, what='images', alone=False, narrow_split=False, narrow_taps=False):
+    def of(cls, n, narrow=False, narrow_rows=False, narrow32=False, narrow64=False, narrow_linear=False, what='images', alone=False, narrow_split=False, narrow_taps=False, narrow_fill=False):
         """The form of a batch of `n` under the keywords: _narrow_args refuses what the argument rule refuses (`what`, `alone`: its own).  n = None: no batch
         (KeyedLayer.kernel / launch) -- nothing is refused, a keyword without `narrow` means what the rules of kernel() make of it, and the tile is asked for."""
         mode = narrow if narrow == 'mfma' else bool(narrow)
         if n is not None:
-            _narrow_args(n, narrow, narrow_rows, what, alone, narrow32=narrow32, narrow64=narrow64, narrow_linear=narrow_linear, narrow_split=narrow_split, narrow_taps=narrow_taps)
+            _narrow_args(n, narrow, narrow_rows, what, alone, narrow32=narrow32, narrow64=narrow64, narrow_linear=narrow_linear, narrow_split=narrow_split, narrow_taps=narrow_taps, narrow_fill=narrow_fill)
         (split, taps) = (bool(narrow_split and mode == 'mfma'), bool(narrow_taps and mode))
         kind = (NarrowSplitTapsForm if taps else NarrowSplitForm) if split else (NarrowTapsForm if taps else NarrowForm)
+        if narrow_fill and mode:
+            kind = _fill_kind[kind]
         return kind(mode, bool(narrow_rows), bool(narrow32 or narrow64), bool(narrow64), mode == 'mfma' and narrow64 == 'mfma' and (n is None or n > NARROW32_MAX), bool(narrow_linear))
 
     def keywords(self):
         """The keywords of this form, normalised, as KeyedLayer.forward and the surfaces below it take them (narrow64: 'mfma' only where the tile is asked for;
-        narrow_split, narrow_taps: only where they were passed)."""
+        narrow_split, narrow_taps, narrow_fill: only where they were passed)."""
         kw = dict(narrow=self.mode, narrow_rows=self.rows, narrow32=self.narrow32, narrow64='mfma' if self.tile64 else self.narrow64, narrow_linear=self.linear)
         if self.split:
             kw['narrow_split'] = True
         if self.taps:
             kw['narrow_taps'] = True
+        if self.fill:
+            kw['narrow_fill'] = True
         return kw
 
 
@@ -230,6 +241,20 @@ class NarrowSplitTapsForm(NarrowSplitForm):
     """... and of a call that passed both narrow_split=True and narrow_taps=True (with narrow='mfma'): a split form with `taps` True."""
     __slots__ = ()
     taps = True
+
+
+def _fill_twin(kind, name):
+    """The kind of the calls that passed narrow_fill=True next to the keywords of `kind`: the same fields, `split` and `taps` (a split kind stays a NarrowSplitForm),
+    `fill` True, equal to its own kind only."""
+    base = kind if kind is not NarrowForm else _TypedNarrowForm
+    return type(name, (base,), dict(__slots__=(), fill=True, __doc__='%s of a call that also passed narrow_fill=True (with `narrow`): the same six fields, `fill` True.' % kind.__name__))
+
+
+NarrowFillForm = _fill_twin(NarrowForm, 'NarrowFillForm')
+NarrowSplitFillForm = _fill_twin(NarrowSplitForm, 'NarrowSplitFillForm')
+NarrowTapsFillForm = _fill_twin(NarrowTapsForm, 'NarrowTapsFillForm')
+NarrowSplitTapsFillForm = _fill_twin(NarrowSplitTapsForm, 'NarrowSplitTapsFillForm')
+_fill_kind = {NarrowForm: NarrowFillForm, NarrowSplitForm: NarrowSplitFillForm, NarrowTapsForm: NarrowTapsFillForm, NarrowSplitTapsForm: NarrowSplitTapsFillForm}
 
 
 # ------------------------------------------------------------------------------------------------------------------
@@ -410,11 +435,11 @@ class FactoredSparseMatrix(SparseMatrix):
     def rows_capable(self):
         return False                     # (a conv-taps handle on the device)
 
-    def torchdot(self, x_torch, relu=False, exact=True, absmax=None, narrow=False, narrow32=False, narrow64=False, narrow_taps=False):
+    def torchdot(self, x_torch, relu=False, exact=True, absmax=None, narrow=False, narrow32=False, narrow64=False, narrow_taps=False, narrow_fill=False):
         """SparseMatrix.torchdot; `narrow` (True or 'mfma': the same here, the operator is under the bit-exact contract): at most NARROW_MAX columns on the channel-lane kernel of the factored device form (KN_FLAG_NARROW) -- the
         same bits as without it (the order-preserving product, which IS scipy's on the stored CSR); `narrow32` (with `narrow`): at most NARROW32_MAX columns (KN_FLAG_NARROW32);
-        `narrow64` (with `narrow`): at most NARROW64_MAX (KN_FLAG_NARROW64); `narrow_taps` (with `narrow`): the tap-resident kernel at up to NARROW_MAX columns (KN_FLAG_NARROW_TAPS)."""
-        return _run_torchdot(self, x_torch, relu=relu, exact=exact, absmax=absmax, narrow=narrow, narrow32=narrow32, narrow64=narrow64, narrow_taps=narrow_taps)
+        `narrow64` (with `narrow`): at most NARROW64_MAX (KN_FLAG_NARROW64); `narrow_taps` (with `narrow`): the tap-resident kernel at up to NARROW_MAX columns (KN_FLAG_NARROW_TAPS); `narrow_fill` (with `narrow`): the filled-in operators' tap-resident kernel at up to NARROW32_MAX columns (KN_FLAG_NARROW_FILL)."""
+        return _run_torchdot(self, x_torch, relu=relu, exact=exact, absmax=absmax, narrow=narrow, narrow32=narrow32, narrow64=narrow64, narrow_taps=narrow_taps, narrow_fill=narrow_fill)
 
     @staticmethod
     def proven(M, factored, max_zero_fraction=0.01):
@@ -731,9 +756,9 @@ class Conv2dTiledMatrix(TiledMatrix):
     def rows_capable(self):
         return False                     # (a conv-taps handle on the device)
 
-    def torchdot(self, x, relu=False, exact=False, absmax=None, narrow=False, narrow32=False, narrow64=False, narrow_split=False, narrow_taps=False):
+    def torchdot(self, x, relu=False, exact=False, absmax=None, narrow=False, narrow32=False, narrow64=False, narrow_split=False, narrow_taps=False, narrow_fill=False):
         """[cols, N] -> [rows, N].  `narrow_split` (only with narrow='mfma', ValueError otherwise): under exact='split', at most NARROW32_MAX columns, a filled-in operator runs
-        the narrow split route (_torchdot_split_narrow) where narrow_split_route() offers it; everywhere else the call is what it is without the keyword.  `narrow_taps` (only with `narrow`): KN_FLAG_NARROW_TAPS wherever the call carries KN_FLAG_NARROW -- the tap-resident kernel at up to NARROW_MAX columns, the same bits.  exact=False: f32 MFMA path (f32-input matrix instructions, exact f32 products); exact=True: the
+        the narrow split route (_torchdot_split_narrow) where narrow_split_route() offers it; everywhere else the call is what it is without the keyword.  `narrow_taps` (only with `narrow`): KN_FLAG_NARROW_TAPS wherever the call carries KN_FLAG_NARROW -- the tap-resident kernel at up to NARROW_MAX columns, the same bits.  `narrow_fill` (only with `narrow`): KN_FLAG_NARROW_FILL wherever the call carries KN_FLAG_NARROW -- a filled-in operator's tap-resident kernel at up to NARROW32_MAX columns, the same bits.  exact=False: f32 MFMA path (f32-input matrix instructions, exact f32 products); exact=True: the
         reference's accumulation order and rounding (order-preserving kernel on the factored operator); exact='split': a filled-in factored
         operator applied as spatial mixing per tap, then channel mixing (see _split_ops: another association of the sum, tolerance contract only); exact='bf16x3': f32 products
         emulated on the bf16 matrix pipe (three-way exact split, six of nine cross products, f32 accumulate: KN_FLAG_BF16X3) where the
@@ -743,7 +768,7 @@ class Conv2dTiledMatrix(TiledMatrix):
         narrow64='mfma' (with narrow='mfma') beyond NARROW32_MAX columns under False / 'bf16x3' the f32 product on 64-column tiles (per column the bits of the plain
         matrix-core call on the batch zero-padded to 128 columns), else narrow64=True.  The flag word is KeyedLayer.kernel's."""
         assert not isinstance(exact, str) or exact in ('bf16x3', 'split') or (narrow and exact == 'auto'), "exact must be True, False, 'bf16x3' or 'split'"
-        return _run_torchdot(self, x, relu=relu, exact=exact, absmax=absmax, narrow=narrow, narrow32=narrow32, narrow64=narrow64, narrow_split=narrow_split, narrow_taps=narrow_taps)
+        return _run_torchdot(self, x, relu=relu, exact=exact, absmax=absmax, narrow=narrow, narrow32=narrow32, narrow64=narrow64, narrow_split=narrow_split, narrow_taps=narrow_taps, narrow_fill=narrow_fill)
 
     def __getstate__(self):
         d = super(Conv2dTiledMatrix, self).__getstate__()

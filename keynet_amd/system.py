@@ -179,7 +179,7 @@ class KeyedModel(object):
     NARROW32_MAX = ksp.NARROW32_MAX    # ... with narrow32=True (convtaps_narrow32_kernel: the columns in blocks of 8 | 16 | 32 running sums per lane)
     NARROW64_MAX = ksp.NARROW64_MAX    # ... with narrow64=True (beyond NARROW32_MAX images convtaps_exact_pipe64_kernel: one column per lane, packed over output-channel pairs)
 
-    def forward_linear(self, img_cipher, overlap=None, narrow=False, narrow_rows=False, narrow32=False, narrow64=False, narrow_linear=False, narrow_split=False, narrow_taps=False):
+    def forward_linear(self, img_cipher, overlap=None, narrow=False, narrow_rows=False, narrow32=False, narrow64=False, narrow_linear=False, narrow_split=False, narrow_taps=False, narrow_fill=False):
         """[N, D0+1] -> [N, classes+1]: the nn.Sequential of keynet/system.py:132 with the unkeyed ReLUs fused into the
         producing layer's kernel epilogue.  Stream-ordered on torch's current HIP stream.  Host synchronisation: none for key-nets whose
         layers all run under a DECLARED contract (exact=True: the permutation key-nets; exact=False: forced); a key-net with layers on the
@@ -253,17 +253,23 @@ class KeyedModel(object):
         `narrow_taps=True` (opt-in; only together with narrow=True | 'mfma', ValueError otherwise; every width those keywords allow, in effect up to NARROW_MAX images): the
         conv layers that run the channel-lane kernel run convtaps_narrow_taps_kernel instead (KN_FLAG_NARROW_TAPS: slot lists in scalar registers, an input channel's value
         rows of all taps in vector registers) where the operator is eligible -- every conv layer of the tiled permutation / identity key-nets; filled-in layers are not.
-        Nothing is calibrated, recorded or screened: the bits are those of the same call without the keyword."""
-        (form, x, windows) = self._resolve(img_cipher, (narrow, narrow_rows, narrow32, narrow64, narrow_linear), narrow_split=narrow_split, narrow_taps=narrow_taps)
+        Nothing is calibrated, recorded or screened: the bits are those of the same call without the keyword.
+        `narrow_fill=True` (opt-in; only together with narrow=True | 'mfma', ValueError otherwise; every width those keywords allow, in effect up to NARROW32_MAX images): the
+        FILLED-IN conv layers that run the channel-lane kernels in the reference's order -- under doubly-stochastic keys the layers calibration sends to `exact`, and every
+        layer of a key-net declared exact=True -- run convtaps_narrow_fill_kernel instead (KN_FLAG_NARROW_FILL: the pixel's slot records streamed by scalar loads, an input
+        channel's value rows of all taps in vector registers, one multiply and one add per slot); up to 32 images in blocks of 8.  The first such call of a layer builds
+        its record table on the device (16 bytes per slot).  It combines freely with the other keywords (with narrow_split=True it reaches the layers not on the route);
+        nothing is calibrated, recorded or screened: the bits are those of the same call without the keyword."""
+        (form, x, windows) = self._resolve(img_cipher, (narrow, narrow_rows, narrow32, narrow64, narrow_linear), narrow_split=narrow_split, narrow_taps=narrow_taps, narrow_fill=narrow_fill)
         y = self._forward_passes(x, windows, False if form.mode else overlap, form)[0][:img_cipher.shape[0]]
         return y if img_cipher.is_cuda else y.to(img_cipher.device)
 
-    def _resolve(self, x, keywords, own=False, narrow_split=False, narrow_taps=False):
+    def _resolve(self, x, keywords, own=False, narrow_split=False, narrow_taps=False, narrow_fill=False):
         """The narrow keywords of forward_linear / capture (in the order of their signatures) on the batch x, once per call: (form, block, windows) -- the ksp.NarrowForm
         everything below reads (ValueError where the argument rule refuses the keywords) and the block the passes run on, _prepare64's where the form takes the 64-column
         tile, else _prepare's.  `own` (capture): a block of the call's own, never x's memory -- the graph's input.
-        `narrow_split`, `narrow_taps`: the opt-in sixth and seventh keywords, carried by the form (NarrowForm.split, NarrowForm.taps)."""
-        form = ksp.NarrowForm.of(x.shape[0], *keywords, narrow_split=narrow_split, narrow_taps=narrow_taps)
+        `narrow_split`, `narrow_taps`, `narrow_fill`: the opt-in sixth, seventh and eighth keywords, carried by the form (NarrowForm.split, .taps, .fill)."""
+        form = ksp.NarrowForm.of(x.shape[0], *keywords, narrow_split=narrow_split, narrow_taps=narrow_taps, narrow_fill=narrow_fill)
         if own:
             x = x.detach().float() if form.mode else x.detach()
             x = x if form.tile64 else x.t().clone(memory_format=torch.contiguous_format).t()
@@ -666,7 +672,7 @@ class KeyedModel(object):
             self._drop_plans()
         return changed
 
-    def capture(self, img_cipher, narrow=False, narrow_rows=False, narrow32=False, narrow64=False, narrow_linear=False, narrow_split=False, narrow_taps=False):
+    def capture(self, img_cipher, narrow=False, narrow_rows=False, narrow32=False, narrow64=False, narrow_linear=False, narrow_split=False, narrow_taps=False, narrow_fill=False):
         """Capture forward_linear for this input shape into a HIP graph (torch.cuda.CUDAGraph on ROCm) and return a callable
         `replay(x) -> [N, classes+1]`.  Small key-nets are launch-bound (LeNet at N=1024: 7 kernels in 0.25 ms); one graph
         launch replaces them.  The graph runs the passes of the eager forward on the block _prepare made; replay(x) copies x into its first N images.
@@ -679,10 +685,10 @@ class KeyedModel(object):
         (narrow='mfma': against their narrow records; the 64-column tile: against their wide records; narrow=True: none, replay() reads nothing back) the graph gathers
         their max |x|, replay() reads the slots after the launch and on a trip runs the batch eagerly (measuring or calibrating again) and captures a new graph.
         `narrow_split` (with narrow='mfma'): the graph of that forward -- the eager forward first measures the narrow split route where a calibrated layer has no record of it and
-        allocates the route's workspaces, so the capture finds both; replay equals the eager forward bit for bit.  `narrow_taps` (with `narrow`): the graph of that forward."""
+        allocates the route's workspaces, so the capture finds both; replay equals the eager forward bit for bit.  `narrow_taps`, `narrow_fill` (with `narrow`): the graph of that forward (the eager forward run first builds the record tables of narrow_fill, so the capture allocates nothing)."""
         assert img_cipher.is_cuda, 'capture() needs a device tensor'
         n = img_cipher.shape[0]
-        (form, static_in, windows) = self._resolve(img_cipher, (narrow, narrow_rows, narrow32, narrow64, narrow_linear), own=True, narrow_split=narrow_split, narrow_taps=narrow_taps)
+        (form, static_in, windows) = self._resolve(img_cipher, (narrow, narrow_rows, narrow32, narrow64, narrow_linear), own=True, narrow_split=narrow_split, narrow_taps=narrow_taps, narrow_fill=narrow_fill)
         keyed = self._keyed()
         state = {}
 
@@ -714,12 +720,12 @@ class KeyedModel(object):
         replay.graph = state['graph']
         return replay
 
-    def forward(self, img_cipher, outkey=None, narrow=False, narrow_rows=False, narrow32=False, narrow64=False, narrow_linear=False, narrow_split=False, narrow_taps=False):
+    def forward(self, img_cipher, outkey=None, narrow=False, narrow_rows=False, narrow32=False, narrow64=False, narrow_linear=False, narrow_split=False, narrow_taps=False, narrow_fill=False):
         """Encrypted image(s) [N, D0+1] -> logits.  N == 1 returns the reference's shape `outshape` = (C,1,1)
         (keynet/system.py:130-133); N > 1 (an extension: the reference cannot) returns (N, C, 1, 1).  `narrow`, `narrow_rows`, `narrow32`, `narrow64`,
-        `narrow_linear`, `narrow_split`, `narrow_taps` (narrow='mfma', narrow64='mfma' included): the low-latency forms of this very call, handed to forward_linear, which says what each selects."""
+        `narrow_linear`, `narrow_split`, `narrow_taps`, `narrow_fill` (narrow='mfma', narrow64='mfma' included): the low-latency forms of this very call, handed to forward_linear, which says what each selects."""
         outkey = outkey if outkey is not None else self.embeddingkey()
-        y = self.forward_linear(img_cipher, narrow=narrow, narrow_rows=narrow_rows, narrow32=narrow32, narrow64=narrow64, narrow_linear=narrow_linear, narrow_split=narrow_split, narrow_taps=narrow_taps)
+        y = self.forward_linear(img_cipher, narrow=narrow, narrow_rows=narrow_rows, narrow32=narrow32, narrow64=narrow64, narrow_linear=narrow_linear, narrow_split=narrow_split, narrow_taps=narrow_taps, narrow_fill=narrow_fill)
         if outkey is not None:
             y = self.decrypt(y, outkey)
         n = y.shape[0]

@@ -62,6 +62,8 @@ images for the ladder.  The bars of the file are computed from the table.
                                                                           # narrow_split=True at 1, 8 and 32 images in one process (profiles/r14_narrow_split.txt)
     python tools/narrow_latency.py --split --one-forward                  # ONE narrow split call per layer and width behind a warm-up call (for a kernel trace)
     python tools/narrow_latency.py --split --from-trace DIR/.../*_kernel_trace.csv    # no GPU: the four steps of those calls
+    python tools/narrow_latency.py --fill [--layers conv1_2,conv5_x]      # the same operators under exact=True: narrow=True without and with narrow_fill=True and the padded 128-column call
+                                                                          # at 1, 8, 16, 32 images in one process (profiles/r16_narrow_fill.txt); --one-forward / --from-trace as for --split
 
     python tools/narrow_latency.py --taps [--out profiles/r15_narrow_taps.txt]
     python tools/narrow_latency.py --taps --one-forward          # for n in (1, 2, 4, 8) ONE narrow forward, then ONE with narrow_taps=True (for a kernel trace)
@@ -547,6 +549,97 @@ def split_trace_table(args):
         f.write(text)
 
 
+FILL_IMAGES = (1, 8, 16, 32)
+
+
+def fill_table(args):
+    """--fill: per layer shape, in ONE process, on the filled-in synthetic operators of --split, contract exact=True, ReLU fused, at 1, 8, 16 and 32 images:
+    (a) torchdot(narrow=True[, narrow32=True]) -- the channel-lane kernels that sum stored values, what such a call ran before; (b) the same call with narrow_fill=True
+    (convtaps_narrow_fill_kernel); (c) the padded alternative, torchdot(x128, exact=True) on the batch zero-padded to 128 columns (convtaps_exact_fill_kernel).  Medians of HIP-event
+    timings; torch.equal of (b) against (a) and against the first columns of (c).  --one-forward: after one warm-up call, ONE call of (a), (b), (c) per layer and width and
+    nothing else (the program for a kernel trace; --fill --from-trace reads it)."""
+    import numpy as np
+    from keynet_amd import sparse as ksp
+    dev = torch.device('cuda:0')
+    layers = [l for l in SPLIT_LAYERS if not args.layers or l[0] in args.layers]
+    out = args.out or os.path.join(ROOT, 'profiles', 'r16_narrow_fill.txt')
+    lines = ['', '== tools/narrow_latency.py --fill: filled-in synthetic operators of the VGG-16 conv shapes, contract exact=True, ReLU fused; %s, torch %s' % (torch.cuda.get_device_name(0), torch.__version__),
+             '   (a) = torchdot(narrow=True[, narrow32=True]): %d warm-up + median of %d calls;  (b) = the same call with narrow_fill=True: %d + %d calls;  (c) = torchdot(x padded to 128 columns, exact=True): %d + %d calls; HIP events'
+             % (1, args.fused_calls, args.warmup, args.forwards, 1, args.fused_calls),
+             '   %-8s %4s %4s %4s %5s %9s | %6s | %11s | %11s | %11s | %7s | %7s | %6s | %6s | %s' % ('layer', 'Cin', 'Cout', 'H', 'fill', 'entries', 'images', '(a) [ms]', '(b) [ms]', '(c) [ms]', '(a)/(b)', '(c)/(b)',
+                                                                                                 'b == a', 'b == c', 'kernel of (b)')]
+    if not args.one_forward:
+        with open(out, 'a') as f:
+            f.write('\n'.join(lines) + '\n')
+    for (name, Cin, Cout, H, fill) in layers:
+        rng = np.random.RandomState(H + Cin)
+        t0 = time.time()
+        W = _split_operator(rng, Cin, Cout, H, fill)
+        x128 = torch.zeros(W.shape[1], 128, device=dev)
+        x128[:, :32] = torch.randn(W.shape[1], 32, device=dev)
+        x128[-1, :32] = 1.0
+        print('%s built in %.0f s' % (name, time.time() - t0), flush=True)
+        with torch.cuda.device(dev):
+            op = W._device_op(dev)
+        for n in FILL_IMAGES:
+            x = x128[:, :n].contiguous()
+            xp = x128.clone()
+            xp[:, n:] = 0.0
+            kw = dict(relu=True, exact=True, narrow=True, narrow32=n > ksp.NARROW_MAX)
+            from keynet_amd import _capi
+            flags = _capi.KN_FLAG_RELU | _capi.KN_FLAG_EXACT | _capi.KN_FLAG_NARROW | (_capi.KN_FLAG_NARROW32 if n > ksp.NARROW_MAX else 0) | _capi.KN_MODIFIER_NARROW_FILL
+            kernel = op.plan(n, flags).split(' (')[0]
+            if args.one_forward:
+                yb = W.torchdot(x, narrow_fill=True, **kw)       # (warm-up: builds the records)
+                torch.cuda.synchronize()
+                print('TRACE: %s n=%d' % (name, n), flush=True)
+                W.torchdot(x, **kw)
+                W.torchdot(x, narrow_fill=True, **kw)
+                W.torchdot(xp, relu=True, exact=True)
+                torch.cuda.synchronize()
+                continue
+            yb = W.torchdot(x, narrow_fill=True, **kw)
+            tb = timed(lambda: W.torchdot(x, narrow_fill=True, **kw), args.forwards, args.warmup)
+            ya = W.torchdot(x, **kw)
+            ta = timed(lambda: W.torchdot(x, **kw), args.fused_calls, 0)
+            yc = W.torchdot(xp, relu=True, exact=True)
+            tc = timed(lambda: W.torchdot(xp, relu=True, exact=True), args.fused_calls, 0)
+            (ma, mb, mc) = (statistics.median(ta), statistics.median(tb), statistics.median(tc))
+            line = '   %-8s %4d %4d %4d %5d %9d | %6d | %11.3f | %11.3f | %11.3f | %6.2fx | %6.2fx | %6s | %6s | %s' % (
+                name, Cin, Cout, H, fill, len(W._taps['ent_out']), n, ma, mb, mc, ma / mb, mc / mb, torch.equal(yb, ya), torch.equal(yb, yc[:, :n]), kernel)
+            print(line, flush=True)
+            with open(out, 'a') as f:
+                f.write(line + '\n')
+            del ya, yb, yc
+        del W, op, x128
+        torch.cuda.empty_cache()
+
+
+def fill_trace_table(args):
+    """--fill --from-trace: the launches of ONE call of (a), (b), (c) per layer and width, from the kernel trace of a `--fill --one-forward` run (device timestamps).  Per
+    (layer, width) the run issues a warm-up call of (b) and then (a), (b), (c): the last three launches of a conv-taps main kernel in each group of four are reported."""
+    import csv
+    with open(args.from_trace, newline='') as f:
+        rows = sorted(csv.DictReader(f), key=lambda r: int(r['Start_Timestamp']))
+    main = [(r['Kernel_Name'], (int(r['End_Timestamp']) - int(r['Start_Timestamp'])) / 1e3) for r in rows
+            if any(k in r['Kernel_Name'] for k in ('convtaps_narrow_kernel', 'convtaps_narrow32_kernel', 'convtaps_narrow_fill_kernel', 'convtaps_exact_fill_kernel'))]
+    layers = [l for l in SPLIT_LAYERS if not args.layers or l[0] in args.layers]
+    assert len(main) == 4 * len(layers) * len(FILL_IMAGES), 'expected %d conv-taps launches in the trace, found %d' % (4 * len(layers) * len(FILL_IMAGES), len(main))
+    lines = ['', '== tools/narrow_latency.py --fill --from-trace: ONE launch of (a), (b), (c) per layer and width (rocprofv3 --kernel-trace, device timestamps, us)',
+             '   %-8s %6s | %12s | %12s | %12s | %7s | %7s' % ('layer', 'images', '(a)', '(b)', '(c)', '(a)/(b)', '(c)/(b)')]
+    k = 0
+    for (name, Cin, Cout, H, fill) in layers:
+        for n in FILL_IMAGES:
+            (a, b, c) = (main[k + 1], main[k + 2], main[k + 3])
+            assert 'convtaps_narrow_fill_kernel' in b[0] and 'convtaps_exact_fill_kernel' in c[0] and 'fill' not in a[0], (a[0], b[0], c[0])
+            lines.append('   %-8s %6d | %12.1f | %12.1f | %12.1f | %6.2fx | %6.2fx' % (name, n, a[1], b[1], c[1], a[1] / b[1], c[1] / b[1]))
+            k += 4
+    text = '\n'.join(lines) + '\n'
+    print(text)
+    with open(args.out or os.path.join(ROOT, 'profiles', 'r16_narrow_fill.txt'), 'a') as f:
+        f.write(text)
+
+
 def narrow32_trace_table(args):
     """--narrow32 --from-trace: the conv launches of the last four forwards of a `--narrow32 --one-forward` run (device timestamps)."""
     import csv
@@ -934,12 +1027,15 @@ def main():
     ap.add_argument('--images', type=lambda v: tuple(int(k) for k in v.split(',')), default=N32_IMAGES, help='image counts of --narrow32')
     ap.add_argument('--blocks', action='store_true', help='with --narrow32: one conv5_x-shaped operator per column-block width (diagnostic build)')
     ap.add_argument('--split', action='store_true', help="filled-in synthetic operators of the VGG-16 conv shapes: narrow='mfma' without and with narrow_split=True at 1, 8, 32 images (profiles/r14_narrow_split.txt)")
+    ap.add_argument('--fill', action='store_true', help='filled-in synthetic operators of the VGG-16 conv shapes under exact=True: narrow=True without and with narrow_fill=True, and the padded 128-column call, at 1, 8, 16, 32 images (profiles/r16_narrow_fill.txt)')
     ap.add_argument('--taps', action='store_true', help='whole forwards with and without narrow_taps=True at 1, 2, 4, 8 images (profiles/r15_narrow_taps.txt)')
     ap.add_argument('--layers', type=lambda v: tuple(v.split(',')), default=(), help='with --split: only these layer shapes (conv1_1, conv1_2, conv2_1, ..., conv5_x)')
     ap.add_argument('--fused-calls', type=int, default=3, help='with --split: timed calls of the fused channel-lane launch (hundreds of ms each on the larger layers)')
     args = ap.parse_args()
     if args.split:
         return split_trace_table(args) if args.from_trace else split_table(args)
+    if args.fill:
+        return fill_trace_table(args) if args.from_trace else fill_table(args)
     if args.from_trace and args.taps:
         return taps_trace_table(args)
     if args.from_trace:
