@@ -160,6 +160,21 @@ enum kn_status {
                               ineligible operator or call; at n_vecs > 8 (the KN_FLAG_NARROW32 / KN_FLAG_NARROW64 ranges); where KN_FLAG_NARROW_MFMA runs the matrix-core
                               kernel; on CSR, dense, float64 and chain handles; in kn_spmm_planes.  kn_spmm_plan names the kernel, P, NV, the masked width and `coef`.
                               No reference counterpart. */
+#define KN_MODIFIER_NARROW_TAPS32 (0x1000u)  /* = 4096.  A MODIFIER of KN_FLAG_NARROW_TAPS: with BOTH bits, the channel-lane form of KN_FLAG_NARROW | KN_FLAG_NARROW32 at
+                              9 <= n_vecs <= 32 computes the same product, bit for bit, with the taps resident in registers and packed f32 arithmetic.
+                              It takes effect ONLY where the call would run convtaps_narrow32_kernel on an operator ELIGIBLE for KN_FLAG_NARROW_TAPS (the rule above).
+                              There the call runs convtaps_narrow_taps32_kernel: a wavefront owns one output pixel x 64 output channels x one block of NV = 8 | 16 | 32
+                              columns (the block width and count KN_FLAG_NARROW32 chooses); the pixel's slot list stays in scalar registers, an input channel's value rows
+                              of all taps are loaded once into 16 vector registers, one channel ahead, and a step is one or two scalar activation segment loads of 16
+                              floats (the next one in flight behind the current arithmetic), one indexed register read and NV / 2 v_pk_mul_f32 + NV / 2 v_pk_add_f32 --
+                              each element its own IEEE multiply and its own IEEE add.  Same order, same separate roundings, same bias entry, ReLU, homogeneous row and
+                              zero guard as KN_FLAG_NARROW32: the result equals KN_FLAG_NARROW32's and KN_FLAG_EXACT's.
+                              Per call: 4 * (Hin * Win * ldx + 32) < 2^32 (the kernel's byte offsets inside one channel's plane); a call that fails it runs
+                              convtaps_narrow32_kernel.
+                              Where it changes NOTHING (same kernels, same plan string, same bits): without KN_FLAG_NARROW_TAPS; at n_vecs <= 8 (KN_FLAG_NARROW_TAPS
+                              alone decides there) and at n_vecs > 32; in every other regime; on an ineligible operator; where KN_FLAG_NARROW_FILL takes the launch; on
+                              CSR, dense, float64 and chain handles; in kn_spmm_planes.  KN_FLAG_NARROW_TAPS without this bit stays a no-op at n_vecs > 8.
+                              kn_spmm_plan names the kernel, the value rows, NV, the masked width, the column blocks and `coef`.  No reference counterpart. */
 #define KN_FLAG_NARROW_FILL (0x800u)  /* = 2048.  A MODIFIER of the channel-lane forms of KN_FLAG_NARROW (1 .. 8 columns) and KN_FLAG_NARROW | KN_FLAG_NARROW32 (9 .. 32): the same
                               product, bit for bit, for FILLED-IN operators (summed stored values, hundreds of slots per output pixel: the reference's doubly-stochastic keys).
                               It takes effect ONLY where the call would run convtaps_narrow_kernel or convtaps_narrow32_kernel: on a conv-taps handle with KN_FLAG_NARROW, or

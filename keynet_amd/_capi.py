@@ -28,6 +28,9 @@ KN_FLAG_NARROW_ROWS = 32      # f32 CSR operators on the row-lane kernel for 1 .
 # bits; everywhere else it changes nothing.  Named KN_MODIFIER_*, not KN_FLAG_*: tests/test_narrow_taps_host.py pins the KN_FLAG_* names of this module at eleven, and
 # tests/test_narrow_fill_host.py ties this constant to the header's.
 KN_MODIFIER_NARROW_FILL = 0x800
+# KN_MODIFIER_NARROW_TAPS32 of include/keynet_hip.h: modifier of KN_FLAG_NARROW_TAPS -- with both bits an eligible conv-taps operator runs convtaps_narrow_taps32_kernel (taps
+# resident, packed f32 multiplies and adds) at 9 .. 32 columns under KN_FLAG_NARROW | KN_FLAG_NARROW32, same bits; everywhere else it changes nothing
+KN_MODIFIER_NARROW_TAPS32 = 0x1000
 KN_ABI_VERSION = 5
 
 # every symbol include/keynet_hip.h declares (tests/test_capi.py checks the header against this list)

@@ -1440,6 +1440,7 @@ __global__ __launch_bounds__(256) void convtaps_narrow_kernel(ConvArgs p, int n_
 }
 
 #include "kn_conv_narrow_taps.inc"
+#include "kn_conv_narrow_taps32.inc"
 #include "kn_conv_narrow_fill.inc"
 
 // ---- order-preserving path for 9 .. 32 batch columns (KN_FLAG_NARROW32 next to KN_FLAG_NARROW): lanes are OUTPUT CHANNELS, columns come in blocks ---
@@ -2675,6 +2676,27 @@ static NarrowTapsKernel narrow_taps_kernel(int nv, bool full, int pix, bool coef
     }
 }
 
+// NARROW32 with KN_FLAG_NARROW_TAPS | KN_MODIFIER_NARROW_TAPS32 on an eligible operator (narrow_taps32_call): convtaps_narrow_taps32_kernel (kn_conv_narrow_taps32.inc) behind
+// the block width and count of the regime's rule.  The shipped forms: NT = 9 | 16 value rows per channel (the next that holds the operator's taps), NV = 8 | 16 | 32, full and
+// masked; with coefficients NV = 8 only -- the forms with coefficients at NV = 16 | 32 (nine more resident scalar registers next to 32 of activations) compiled with scalar
+// registers spilled into vector lanes and are not instantiated: nullptr, and the call keeps convtaps_narrow32_kernel.
+template <int NT, int NV>
+static Narrow32Kernel narrow_taps32_kernel_of(bool full, bool coef) {
+    if constexpr (NV == 8) {
+        if (coef) return full ? convtaps_narrow_taps32_kernel<NT, NV, true, true> : convtaps_narrow_taps32_kernel<NT, NV, false, true>;
+    }
+    if (coef) return nullptr;                            // (no such form)
+    return full ? convtaps_narrow_taps32_kernel<NT, NV, true, false> : convtaps_narrow_taps32_kernel<NT, NV, false, false>;
+}
+template <int NT>
+static Narrow32Kernel narrow_taps32_kernel(int nv, bool full, bool coef) {
+    switch (nv) {
+        case 8: return narrow_taps32_kernel_of<NT, 8>(full, coef);
+        case 16: return narrow_taps32_kernel_of<NT, 16>(full, coef);
+        default: return narrow_taps32_kernel_of<NT, 32>(full, coef);
+    }
+}
+
 // NARROW / NARROW32 with KN_FLAG_NARROW_FILL on an eligible operator (narrow_fill_call): convtaps_narrow_fill_kernel (kn_conv_narrow_fill.inc).  The shipped forms: NV as
 // the width (1 | 2 | 4 | 8; 4 and 8 also masked), one pixel per wavefront, 16 value rows per channel, one form for operators with coefficients and without.  9 .. 32
 // columns: NV = 8 with the column block as part of the work item (the last block masked where n_vecs % 8 != 0).
@@ -2699,6 +2721,7 @@ struct NarrowChoice {
     int taps_pix = 0;               // NARROW: 0 = convtaps_narrow_kernel, else convtaps_narrow_taps_kernel with this many pixels per wavefront (1 | 2) ...
     int taps_nt = 0;                // ... and this many value rows per channel (9 | 16)
     int n_grp = 0;                  // ... over this many pixel groups
+    bool taps32 = false;            // NARROW32: kernel.lanes32 is convtaps_narrow_taps32_kernel (taps_nt value rows per channel), on the regime's own w, n_colb and n_wg
     NarrowTapsKernel taps_b = nullptr;      // ... and, where the columns run as two blocks (coefficients at 5 .. 8 columns), the kernel of columns 4 .. and their width
     NarrowWidth w_b = {1, 0, true};
     NarrowFillKernel fill = nullptr;        // NARROW / NARROW32: convtaps_narrow_fill_kernel in place of the regime's kernel (w, n_colb, n_wg are then its own)
@@ -2765,6 +2788,16 @@ static NarrowChoice narrow_choice(const ConvTapsDev& A, const ConvArgs& a, ConvR
         c.n_wg = (items * c.n_colb + 3) / 4;
         c.kernel.lanes32 = nv == 8 ? narrow32_kernel_of<8>(A.has_dups, coef) : nv == 16 ? narrow32_kernel_of<16>(A.has_dups, coef)
                                    : (coef ? convtaps_narrow32_kernel<32, false, true> : convtaps_narrow32_kernel<32, false, false>);
+        // KN_FLAG_NARROW_TAPS | KN_MODIFIER_NARROW_TAPS32: the packed tap-resident kernel behind the same choice, where the operator is eligible, a channel's plane of this
+        // block stays inside the kernel's 32-bit byte offsets and the form is built
+        if (narrow_taps32_call(A, flags, a.n_vecs) && 4 * ((int64_t)a.HiWi * a.ldx + NARROW32_MAX_VECS) < ((int64_t)1 << 32)) {
+            const bool nine = A.ntaps <= 9;
+            if (Narrow32Kernel k = nine ? narrow_taps32_kernel<9>(nv, c.w.full, coef) : narrow_taps32_kernel<16>(nv, c.w.full, coef)) {
+                c.kernel.lanes32 = k;
+                c.taps32 = true;
+                c.taps_nt = nine ? 9 : 16;
+            }
+        }
     } else {
         c.n_nt = (((int64_t)a.n_pix << c.w.log2) + 31) / 32;
         c.tm = c.n_cb * c.n_nt >= 1024 ? 2 : 1;
@@ -2800,7 +2833,11 @@ static int launch_narrow(const ConvTapsDev& A, const ConvArgs& a, const NarrowCh
                       (c.n_colb == 1 ? " column block" : " column blocks") + (coef ? ", coef" : "") + "> (lane = output channel, taps resident, " + std::to_string(A.fill_n) +
                       " slot records, pixels in pix_deal order)",
                   c.fill, grid, dim3(256), 0, s, af, A.fill_ptr, __atomic_load_n(&A.fill_rec, __ATOMIC_ACQUIRE), c.n_cb, c.n_colb, n_wg);
-    } else if (c.regime == NARROW32)
+    } else if (c.regime == NARROW32 && c.taps32)
+        KN_LAUNCH("convtaps_narrow_taps32_kernel<" + std::to_string(c.taps_nt) + " value rows, NV=" + std::to_string(w.nv) + (w.full ? "" : ", masked to " + std::to_string(a.n_vecs)) + ", " +
+                      std::to_string(c.n_colb) + (c.n_colb == 1 ? " column block" : " column blocks") + (coef ? ", coef" : "") + "> (lane = output channel, taps resident, packed f32)",
+                  c.kernel.lanes32, grid, dim3(256), 0, s, a, c.n_cb, c.n_colb, n_wg);
+    else if (c.regime == NARROW32)
         KN_LAUNCH("convtaps_narrow32_kernel<NV=" + std::to_string(w.nv) + (w.full ? "" : ", masked to " + std::to_string(a.n_vecs)) + ", " + std::to_string(c.n_colb) +
                       (c.n_colb == 1 ? " column block" : " column blocks") + (A.has_dups ? ", stored values summed" : "") + (coef ? ", coef" : "") + "> (lane = output channel)",
                   c.kernel.lanes32, grid, dim3(256), 0, s, a, c.n_cb, c.n_colb, n_wg);

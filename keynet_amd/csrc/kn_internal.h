@@ -447,6 +447,18 @@ static inline bool narrow_taps_loses(const ConvTapsDev& A, int64_t n_vecs) { ret
 static inline bool narrow_taps_call(const ConvTapsDev& A, uint32_t flags, int64_t n_vecs) {
     return (flags & KN_FLAG_NARROW_TAPS) && n_vecs <= NARROW_MAX_VECS && narrow_taps_ok(A) && !narrow_taps_loses(A, n_vecs);
 }
+// KN_MODIFIER_NARROW_TAPS32, a modifier of KN_FLAG_NARROW_TAPS in regime NARROW32 (KN_FLAG_NARROW | KN_FLAG_NARROW32 at 9 .. 32 columns, or KN_FLAG_NARROW_MFMA where that
+// flag means KN_FLAG_NARROW): an operator eligible for KN_FLAG_NARROW_TAPS (narrow_taps_ok) runs convtaps_narrow_taps32_kernel (kn_conv_narrow_taps32.inc) when the call
+// carries BOTH bits, bit for bit convtaps_narrow32_kernel's result.  Everywhere else -- without KN_FLAG_NARROW_TAPS, in every other regime, at 8 columns or fewer, beyond
+// 32, on an ineligible operator, on other handle kinds, in kn_spmm_planes, where KN_FLAG_NARROW_FILL takes the launch -- the bit is not read.  narrow_taps32_call is the one
+// place that reads it; narrow_choice (kn_conv.hip) asks it and adds the per-call condition of the kernel's 32-bit byte offsets and whether the form is built.
+// narrow_taps32_loses: the (shape, width) pairs whose launch is slower than convtaps_narrow32_kernel's in a kernel trace, each with its trace line.  None: of the 13 conv
+// launches of keyed VGG-16 the slowest ratios are conv1_1 1.59x at 16 images and conv4_3 1.01x (3 468.4 -> 3 422.7 us) at 32 (profiles/r17_narrow_taps32.txt).
+static inline bool narrow_taps32_loses(const ConvTapsDev& A, int64_t n_vecs) { return false; }
+static inline bool narrow_taps32_call(const ConvTapsDev& A, uint32_t flags, int64_t n_vecs) {
+    return (flags & KN_FLAG_NARROW_TAPS) && (flags & KN_MODIFIER_NARROW_TAPS32) && n_vecs > NARROW_MAX_VECS && n_vecs <= NARROW32_MAX_VECS && narrow_taps_ok(A) &&
+           !narrow_taps32_loses(A, n_vecs);
+}
 // KN_FLAG_NARROW_FILL, a modifier of regimes NARROW and NARROW32 (KN_FLAG_NARROW [| KN_FLAG_NARROW32] at 1 .. 32 columns, or KN_FLAG_NARROW_MFMA where that flag means
 // KN_FLAG_NARROW): an ELIGIBLE operator runs convtaps_narrow_fill_kernel (kn_conv_narrow_fill.inc), bit for bit the channel-lane kernels' result.  Eligible: the handle has
 // the record lists of the filled-in order-preserving kernel (convtaps_fill_ok: summed stored values, or more than 64 slots on some output pixel), 1 .. 16 taps (the records

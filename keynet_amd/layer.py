@@ -245,12 +245,12 @@ class KeyedLayer(nn.Module):
         (a planner gets the channel-lane kernel).  Any other operator: `narrow_rows` / `narrow_linear` where it is a float32 CSR handle (W.rows_capable()), and a layer still
         'auto' runs in the reference's order for this call (to a planner it stays 'auto': not one launch).  `form.split` (narrow_split=True): ahead of narrow_mode(), a layer
         narrow_split_mode() puts on the narrow split route gets narrow='mfma', narrow_split=True (to a planner: not one launch); any other layer is what it is without it.
-        `form.taps` (narrow_taps=True), `form.fill` (narrow_fill=True): handed on to every operator with a conv-taps handle, next to whatever `narrow` it gets."""
+        `form.taps` (narrow_taps=True | 'packed'), `form.fill` (narrow_fill=True): handed on to every operator with a conv-taps handle, next to whatever `narrow` it gets."""
         (W, exact) = (self.W, getattr(self, '_exact', True))
         if not form.mode:
             return (exact, {})
         if W.narrow_capable():
-            taps = dict(dict(narrow_taps=True) if form.taps else {}, **(dict(narrow_fill=True) if form.fill else {}))
+            taps = dict(dict(narrow_taps=form.taps) if form.taps else {}, **(dict(narrow_fill=True) if form.fill else {}))
             if form.tile64 and (xt is None or xt.shape[1] > ksp.NARROW32_MAX):
                 mode = 'mfma' if isinstance(W, ksp.Conv2dTiledMatrix) and exact in (False, 'bf16x3') else True
                 return (exact, dict(narrow=mode, narrow32=True, narrow64=mode, **taps))
@@ -284,6 +284,8 @@ class KeyedLayer(nn.Module):
         keyword where not; on every other operator and contract the keyword adds nothing.
         `narrow_taps` (with `narrow`): KN_FLAG_NARROW_TAPS exactly where KN_FLAG_NARROW is set -- inside a narrow='mfma' call that is the operators under True / 'auto' and
         the non-conv ones with a conv-taps handle; the library runs the tap-resident kernel on an eligible operator at up to NARROW_MAX columns and ignores the bit elsewhere.
+        narrow_taps='packed': KN_MODIFIER_NARROW_TAPS32 next to it, on exactly the same launches -- with KN_FLAG_NARROW32 the library runs convtaps_narrow_taps32_kernel on an
+        eligible operator at NARROW_MAX + 1 .. NARROW32_MAX columns; up to NARROW_MAX columns the call is narrow_taps=True.
         `narrow_fill` (with `narrow`): KN_FLAG_NARROW_FILL (_capi.KN_MODIFIER_NARROW_FILL) on exactly the same launches -- with narrow_split=True those are the layers not on the
         route; the library runs convtaps_narrow_fill_kernel on an eligible (filled-in) operator at up to NARROW32_MAX columns and ignores the bit elsewhere."""
         form = ksp.NarrowForm.of(None, narrow, narrow_rows, narrow32, narrow64, narrow_linear, narrow_split=narrow_split, narrow_taps=narrow_taps, narrow_fill=narrow_fill)
@@ -304,7 +306,7 @@ class KeyedLayer(nn.Module):
         if mfma:
             (exact, bf16x3) = (False, False)
         return (get_op, (_capi.KN_FLAG_RELU if relu else 0) | (_capi.KN_FLAG_EXACT if exact else 0) | (_capi.KN_FLAG_BF16X3 if bf16x3 else 0) |
-                (_capi.KN_FLAG_NARROW_MFMA if mfma else _capi.KN_FLAG_NARROW if lane else 0) | (_capi.KN_FLAG_NARROW_TAPS if form.taps and lane and not mfma else 0) | (_capi.KN_MODIFIER_NARROW_FILL if form.fill and lane and not mfma else 0) | (_capi.KN_FLAG_NARROW32 if lane and form.narrow32 else 0) | (_capi.KN_FLAG_NARROW64 if lane and form.narrow64 else 0) |
+                (_capi.KN_FLAG_NARROW_MFMA if mfma else _capi.KN_FLAG_NARROW if lane else 0) | (_capi.KN_FLAG_NARROW_TAPS if form.taps and lane and not mfma else 0) | (_capi.KN_MODIFIER_NARROW_TAPS32 if form.taps == 'packed' and lane and not mfma else 0) | (_capi.KN_MODIFIER_NARROW_FILL if form.fill and lane and not mfma else 0) | (_capi.KN_FLAG_NARROW32 if lane and form.narrow32 else 0) | (_capi.KN_FLAG_NARROW64 if lane and form.narrow64 else 0) |
                 (_capi.KN_FLAG_NARROW64_MFMA if mfma and form.tile64 and contract in (False, 'bf16x3') else 0) |
                 (_capi.KN_FLAG_NARROW_ROWS if form.rows and stored else 0) | (_capi.KN_FLAG_NARROW_LINEAR if form.linear and stored else 0))
 

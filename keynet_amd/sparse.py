@@ -140,7 +140,7 @@ def _narrow_args(n, narrow, narrow_rows, what='images', alone=False, narrow32=Fa
     if narrow_split and narrow != 'mfma':
         raise ValueError('narrow_split=True is the split application of a filled-in conv layer on the matrix-core narrow kernel: pass narrow=\'mfma\' with it (got narrow=%r)' % (narrow,))
     if narrow_taps and not narrow:
-        raise ValueError('narrow_taps=True is the tap-resident form of the channel-lane conv kernel: pass narrow=True or narrow=\'mfma\' with it (got narrow=%r)' % (narrow,))
+        raise ValueError('narrow_taps=%r is the tap-resident form of the channel-lane conv kernel: pass narrow=True or narrow=\'mfma\' with it (got narrow=%r)' % (narrow_taps, narrow))
     if narrow_fill and not narrow:
         raise ValueError('narrow_fill=True is the tap-resident form of the channel-lane conv kernels for filled-in operators: pass narrow=True or narrow=\'mfma\' with it (got narrow=%r)' % (narrow,))
     if narrow64 == 'mfma' and narrow != 'mfma':
@@ -177,6 +177,8 @@ class NarrowForm(collections.namedtuple('NarrowForm', 'mode rows narrow32 narrow
     above ARE the value of every call without it; a call with it gets the same six fields as a NarrowSplitForm, which equals no plain form and hands the keyword back.
     `taps`: the opt-in seventh keyword narrow_taps=True (only with `narrow`: KN_FLAG_NARROW_TAPS on the conv layers' channel-lane launches), carried the same way -- a
     NarrowTapsForm, or with narrow_split=True a NarrowSplitTapsForm; each kind equals its own kind only.
+    narrow_taps='packed' (KN_MODIFIER_NARROW_TAPS32 next to KN_FLAG_NARROW_TAPS: the packed tap-resident kernel at NARROW_MAX + 1 .. NARROW32_MAX columns) is a kind of its
+    own again, the `packed` twin of the kind narrow_taps=True gives (_packed_kind), with `taps` == 'packed'.
     `fill`: the opt-in eighth keyword narrow_fill=True (only with `narrow`: KN_FLAG_NARROW_FILL on the same launches), carried the same way: the kind of the call without
     it has a `fill` twin (_fill_kind: NarrowFillForm, NarrowSplitFillForm, NarrowTapsFillForm, NarrowSplitTapsFillForm), which equals its own kind only."""
     __slots__ = ()
@@ -196,6 +198,8 @@ class NarrowForm(collections.namedtuple('NarrowForm', 'mode rows narrow32 narrow
         kind = (NarrowSplitTapsForm if taps else NarrowSplitForm) if split else (NarrowTapsForm if taps else NarrowForm)
         if narrow_fill and mode:
             kind = _fill_kind[kind]
+        if taps and narrow_taps == 'packed':
+            kind = _packed_kind[kind]
         return kind(mode, bool(narrow_rows), bool(narrow32 or narrow64), bool(narrow64), mode == 'mfma' and narrow64 == 'mfma' and (n is None or n > NARROW32_MAX), bool(narrow_linear))
 
     def keywords(self):
@@ -205,7 +209,7 @@ class NarrowForm(collections.namedtuple('NarrowForm', 'mode rows narrow32 narrow
         if self.split:
             kw['narrow_split'] = True
         if self.taps:
-            kw['narrow_taps'] = True
+            kw['narrow_taps'] = self.taps         # True | 'packed'
         if self.fill:
             kw['narrow_fill'] = True
         return kw
@@ -255,6 +259,19 @@ NarrowSplitFillForm = _fill_twin(NarrowSplitForm, 'NarrowSplitFillForm')
 NarrowTapsFillForm = _fill_twin(NarrowTapsForm, 'NarrowTapsFillForm')
 NarrowSplitTapsFillForm = _fill_twin(NarrowSplitTapsForm, 'NarrowSplitTapsFillForm')
 _fill_kind = {NarrowForm: NarrowFillForm, NarrowSplitForm: NarrowSplitFillForm, NarrowTapsForm: NarrowTapsFillForm, NarrowSplitTapsForm: NarrowSplitTapsFillForm}
+
+
+def _packed_twin(kind, name):
+    """The kind of the calls that passed narrow_taps='packed' where the calls of `kind` passed narrow_taps=True: the same fields, `split` and `fill`, `taps` the string
+    'packed' (true where `taps` is tested, and what keywords() hands back), equal to its own kind only."""
+    return type(name, (kind,), dict(__slots__=(), taps='packed', __doc__='%s of a call that passed narrow_taps=\'packed\' in place of narrow_taps=True: the same six fields, `taps` \'packed\'.' % kind.__name__))
+
+
+NarrowPackedForm = _packed_twin(NarrowTapsForm, 'NarrowPackedForm')
+NarrowSplitPackedForm = _packed_twin(NarrowSplitTapsForm, 'NarrowSplitPackedForm')
+NarrowPackedFillForm = _packed_twin(NarrowTapsFillForm, 'NarrowPackedFillForm')
+NarrowSplitPackedFillForm = _packed_twin(NarrowSplitTapsFillForm, 'NarrowSplitPackedFillForm')
+_packed_kind = {NarrowTapsForm: NarrowPackedForm, NarrowSplitTapsForm: NarrowSplitPackedForm, NarrowTapsFillForm: NarrowPackedFillForm, NarrowSplitTapsFillForm: NarrowSplitPackedFillForm}
 
 
 # ------------------------------------------------------------------------------------------------------------------

@@ -254,6 +254,10 @@ class KeyedModel(object):
         conv layers that run the channel-lane kernel run convtaps_narrow_taps_kernel instead (KN_FLAG_NARROW_TAPS: slot lists in scalar registers, an input channel's value
         rows of all taps in vector registers) where the operator is eligible -- every conv layer of the tiled permutation / identity key-nets; filled-in layers are not.
         Nothing is calibrated, recorded or screened: the bits are those of the same call without the keyword.
+        `narrow_taps='packed'` (opt-in, the same argument rule): up to NARROW_MAX images exactly narrow_taps=True; with narrow32=True (or narrow64=True) at NARROW_MAX + 1 ..
+        NARROW32_MAX images the eligible conv layers run convtaps_narrow_taps32_kernel in place of convtaps_narrow32_kernel (KN_MODIFIER_NARROW_TAPS32: the same resident
+        slot lists and value rows, a step's activations as 16-float scalar segments, packed f32 multiplies and adds, each element rounded as before) -- the same bits;
+        beyond NARROW32_MAX images it changes nothing.  Operators with coefficients have the 8-column-block forms only and keep convtaps_narrow32_kernel elsewhere.
         `narrow_fill=True` (opt-in; only together with narrow=True | 'mfma', ValueError otherwise; every width those keywords allow, in effect up to NARROW32_MAX images): the
         FILLED-IN conv layers that run the channel-lane kernels in the reference's order -- under doubly-stochastic keys the layers calibration sends to `exact`, and every
         layer of a key-net declared exact=True -- run convtaps_narrow_fill_kernel instead (KN_FLAG_NARROW_FILL: the pixel's slot records streamed by scalar loads, an input

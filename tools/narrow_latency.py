@@ -66,9 +66,15 @@ images for the ladder.  The bars of the file are computed from the table.
                                                                           # at 1, 8, 16, 32 images in one process (profiles/r16_narrow_fill.txt); --one-forward / --from-trace as for --split
 
     python tools/narrow_latency.py --taps [--out profiles/r15_narrow_taps.txt]
+    python tools/narrow_latency.py --taps32 [--workload allconv] [--one-forward | --from-trace DIR/.../*_kernel_trace.csv]
     python tools/narrow_latency.py --taps --one-forward          # for n in (1, 2, 4, 8) ONE narrow forward, then ONE with narrow_taps=True (for a kernel trace)
     python tools/narrow_latency.py --taps --from-trace DIR/.../*_kernel_trace.csv [--convs 13]       # no GPU: the conv launches of those forwards side by side
 
+--taps32: keyed VGG-16 under the default contract, whole forwards narrow=True, narrow32=True, narrow_linear=True without and with narrow_taps='packed' at 9, 12, 16, 24
+and 32 images (HIP events, median of 20 with min .. max, the two forms alternating, logits torch.equal), and in the same process the 8-image forward narrow=True,
+narrow_rows=True, narrow_linear=True, narrow_taps=True; the two bars of the table: at 16 and 32 images the gain exceeds the two spreads added, and 16 images cost no more
+than twice the 8-image forward.  --workload allconv: 16 images (blocks of 8 columns).  --one-forward / --from-trace: as --taps, at 16 and 32 images, against
+convtaps_narrow32_kernel in the same trace.  Appends to profiles/r17_narrow_taps32.txt.
 --taps: keyed VGG-16 under the default contract, whole forwards narrow=True, narrow_rows=True, narrow_linear=True without and with narrow_taps=True at 1, 2, 4 and 8
 images in one process, the forms alternating, the logits torch.equal before any time is printed.
 
@@ -980,6 +986,91 @@ def taps_trace_table(args):
         f.write(text)
 
 
+TAPS32_FORM = dict(narrow=True, narrow32=True, narrow_linear=True)
+TAPS32_IMAGES = (9, 12, 16, 24, 32)
+TAPS32_TRACED = (16, 32)
+
+
+def taps32_table(args, knet, xc, desc):
+    """--taps32: see the module docstring."""
+    images = TAPS32_IMAGES if args.workload == 'vgg16' else (16,)
+    if args.one_forward:
+        for n in TAPS32_TRACED:
+            x = xc[:n].t().contiguous().t()
+            for kw in (dict(), dict(narrow_taps='packed')):
+                knet.forward_linear(x, **TAPS32_FORM, **kw)      # (operators resident, kernels loaded)
+            torch.cuda.synchronize()
+        print('TRACE-FROM-HERE: for n in (16, 32) one narrow32 forward, then one with narrow_taps=\'packed\'', flush=True)
+        for n in TAPS32_TRACED:
+            x = xc[:n].t().contiguous().t()
+            for kw in (dict(), dict(narrow_taps='packed')):
+                knet.forward_linear(x, **TAPS32_FORM, **kw)
+                torch.cuda.synchronize()
+        return
+    rows = []
+    for n in images:
+        x = xc[:n].t().contiguous().t()
+        (plain, packed) = (knet.forward_linear(x, **TAPS32_FORM), knet.forward_linear(x, narrow_taps='packed', **TAPS32_FORM))
+        torch.cuda.synchronize()
+        assert torch.equal(plain, packed), 'narrow_taps=\'packed\' logits differ at %d images: max %g' % (n, float((plain - packed).abs().max()))
+        t = ([], [])
+        for _ in range(2):                        # the forms alternating, two rounds of --forwards / 2 each
+            t[0].extend(timed(lambda: knet.forward_linear(x, **TAPS32_FORM), args.forwards // 2, args.warmup))
+            t[1].extend(timed(lambda: knet.forward_linear(x, narrow_taps='packed', **TAPS32_FORM), args.forwards // 2, args.warmup))
+        rows.append((n, [(statistics.median(v), min(v), max(v)) for v in t]))
+        print('n = %d done' % n, flush=True)
+    x8 = xc[:8].t().contiguous().t()              # the best bit-exact 8-image forward, in this process
+    v8 = timed(lambda: knet.forward_linear(x8, narrow_taps=True, **TAPS_FORM), args.forwards, args.warmup)
+    t8 = (statistics.median(v8), min(v8), max(v8))
+    lines = ['', '== tools/narrow_latency.py --taps32 --workload %s: %s' % (args.workload, desc),
+             '   %s, torch %s; HIP events, %d warm-up + median of %d forwards (min .. max), forms alternating; logits torch.equal: yes'
+             % (torch.cuda.get_device_name(0), torch.__version__, args.warmup, args.forwards),
+             '   %6s | %-34s | %-34s | %s' % ('images', 'narrow, narrow32, narrow_linear [ms]', '... and narrow_taps=\'packed\' [ms]', 'ratio | gain [ms] against the two spreads added [ms]')]
+    for (n, t) in rows:
+        cell = ['%8.3f (%.3f .. %.3f)' % v for v in t]
+        (gain, spreads) = (t[0][0] - t[1][0], (t[0][2] - t[0][1]) + (t[1][2] - t[1][1]))
+        lines.append('   %6d | %-34s | %-34s | %.2fx | %.3f against %.3f%s' % (n, cell[0], cell[1], t[0][0] / t[1][0], gain, spreads,
+                                                                             '' if (n not in TAPS32_TRACED or args.workload != 'vgg16') else (': bar MET' if gain > spreads else ': bar MISSED')))
+    lines.append('   %6d | narrow, narrow_rows, narrow_linear, narrow_taps=True [ms]: %8.3f (%.3f .. %.3f)' % ((8,) + t8))
+    for (n, t) in rows:
+        if n == 16 and args.workload == 'vgg16':
+            lines.append('   16 images packed %.3f ms against twice the 8-image forward %.3f ms: bar %s' % (t[1][0], 2 * t8[0], 'MET' if t[1][0] <= 2 * t8[0] else 'MISSED'))
+    text = '\n'.join(lines) + '\n'
+    print(text)
+    with open(args.out or os.path.join(ROOT, 'profiles', 'r17_narrow_taps32.txt'), 'a') as f:
+        f.write(text)
+
+
+def taps32_trace_table(args):
+    """--taps32 --from-trace: the conv launches of the last four forwards of a `--taps32 --one-forward` run under rocprofv3 --kernel-trace (device timestamps)."""
+    import csv
+    with open(args.from_trace, newline='') as f:
+        rows = [r for r in csv.DictReader(f) if 'convtaps_narrow' in r['Kernel_Name']]
+    rows.sort(key=lambda r: int(r['Start_Timestamp']))
+    k = args.convs
+    assert len(rows) >= 4 * k, 'the trace holds %d narrow conv launches, fewer than 4 forwards of %d' % (len(rows), k)
+    rows = rows[-4 * k:]
+    us = lambda r: (int(r['End_Timestamp']) - int(r['Start_Timestamp'])) / 1e3
+    lines = ['', '== tools/narrow_latency.py --taps32 --from-trace: the conv launches of one narrow32 forward and one with narrow_taps=\'packed\' (rocprofv3 --kernel-trace, device timestamps)']
+    for (i, n) in enumerate(TAPS32_TRACED):
+        (old, new) = (rows[(2 * i) * k:(2 * i + 1) * k], rows[(2 * i + 1) * k:(2 * i + 2) * k])
+        assert all('narrow_taps32' not in r['Kernel_Name'] for r in old), 'the forward without the keyword launched the packed tap-resident kernel'
+        lines.append('')
+        lines.append('   %d images [us]: conv launch | workgroups | convtaps_narrow32_kernel | with narrow_taps=\'packed\' | ratio | kernel of the packed forward' % n)
+        for (j, (a, b)) in enumerate(zip(old, new)):
+            name = b['Kernel_Name']
+            form = name[name.index('<'):name.index('>') + 1] if ('narrow_taps32' in name and '<' in name and '>' in name) else ''
+            lines.append('     %2d | %6d | %9.1f | %9.1f | %5.2fx | %s%s' % (j + 1, int(b.get('Grid_Size_X') or 0) // max(1, int(b.get('Workgroup_Size_X') or 1)), us(a), us(b), us(a) / us(b),
+                                                                    ('taps resident, packed <NT, NV, FULL, COEF> = ' + form) if 'narrow_taps32' in name else 'convtaps_narrow32_kernel',
+                                                                    ' -- SLOWER' if 'narrow_taps32' in name and us(b) > us(a) else ''))
+        (sa, sb) = (sum(us(r) for r in old), sum(us(r) for r in new))
+        lines.append('     sum of the %d conv launches: %9.1f | %9.1f | %5.2fx' % (k, sa, sb, sa / sb))
+    text = '\n'.join(lines) + '\n'
+    print(text)
+    with open(args.out or os.path.join(ROOT, 'profiles', 'r17_narrow_taps32.txt'), 'a') as f:
+        f.write(text)
+
+
 def trace_table(args):
     """--from-trace: the conv launches of the last eight forwards of a `--mfma --one-forward` run under rocprofv3 --kernel-trace (device timestamps)."""
     import csv
@@ -1029,6 +1120,7 @@ def main():
     ap.add_argument('--split', action='store_true', help="filled-in synthetic operators of the VGG-16 conv shapes: narrow='mfma' without and with narrow_split=True at 1, 8, 32 images (profiles/r14_narrow_split.txt)")
     ap.add_argument('--fill', action='store_true', help='filled-in synthetic operators of the VGG-16 conv shapes under exact=True: narrow=True without and with narrow_fill=True, and the padded 128-column call, at 1, 8, 16, 32 images (profiles/r16_narrow_fill.txt)')
     ap.add_argument('--taps', action='store_true', help='whole forwards with and without narrow_taps=True at 1, 2, 4, 8 images (profiles/r15_narrow_taps.txt)')
+    ap.add_argument('--taps32', action='store_true', help="whole forwards narrow32=True without and with narrow_taps='packed' at 9, 12, 16, 24, 32 images, and the 8-image narrow_taps=True forward (profiles/r17_narrow_taps32.txt)")
     ap.add_argument('--layers', type=lambda v: tuple(v.split(',')), default=(), help='with --split: only these layer shapes (conv1_1, conv1_2, conv2_1, ..., conv5_x)')
     ap.add_argument('--fused-calls', type=int, default=3, help='with --split: timed calls of the fused channel-lane launch (hundreds of ms each on the larger layers)')
     args = ap.parse_args()
@@ -1038,6 +1130,8 @@ def main():
         return fill_trace_table(args) if args.from_trace else fill_table(args)
     if args.from_trace and args.taps:
         return taps_trace_table(args)
+    if args.from_trace and args.taps32:
+        return taps32_trace_table(args)
     if args.from_trace:
         return narrow64_trace_table(args) if (args.narrow64 or args.mfma64) else narrow32_trace_table(args) if args.narrow32 else rows_trace_table(args) if args.rows else linear_trace_table(args) if args.linear else trace_table(args)
     if args.narrow32 and args.blocks:
@@ -1047,12 +1141,14 @@ def main():
     (sensor, knet, inshape, _, desc, _) = workloads.build_workload(args.workload, 0, fanout=True)
     dev = torch.device('cuda:0')
     torch.manual_seed(1)
-    imgs = torch.randn((64 if (args.narrow64 or args.mfma64 or args.linear) else max(args.images) if args.narrow32 else 8,) + tuple(inshape))
+    imgs = torch.randn((64 if (args.narrow64 or args.mfma64 or args.linear) else max(args.images) if args.narrow32 else 32 if args.taps32 else 8,) + tuple(inshape))
     xc = sensor.fromtensor(imgs.to(dev)).encrypt().astensor()
     xc = xc.t().contiguous().t()                  # feature-major, as the layers hand blocks on
     print('keyed %s in %.0f s' % (desc, time.time() - t0), flush=True)
     if args.taps:
         return taps_table(args, knet, xc, desc)
+    if args.taps32:
+        return taps32_table(args, knet, xc, desc)
     if args.mfma64:
         return mfma64_table(args, knet, xc, desc)
     if args.narrow64:
