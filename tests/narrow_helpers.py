@@ -1,5 +1,5 @@
-"""Helpers shared by the GPU tests of the three narrow kernels (test_narrow_gpu.py, test_narrow_mfma_gpu.py, test_narrow_rows_gpu.py): one kn_spmm on a column window
-with its plan, and the recorder of the kn_spmm calls a forward issues."""
+"""Helpers shared by the GPU tests of the narrow kernels (test_narrow_gpu.py, test_narrow_mfma_gpu.py, test_narrow_rows_gpu.py and the later test_narrow*_gpu.py; the
+seeded fuzzers of test_fuzz_narrow_gpu.py): one kn_spmm on a column window with its plan, and the recorder of the kn_spmm calls a forward issues."""
 import torch
 
 from keynet_amd import _capi
