@@ -8,6 +8,9 @@
 // (one product per output element, one rounding; verified bit for bit against v_mul_f32 on 33.5 M products incl. denormal operands and
 // results, overflow, Inf and NaN by tools/micro/mfma_product.hip -- the only difference is the SIGN OF A ZERO product, +0 from the matrix pipe
 // where v_mul_f32 gives -0, and a running sum that starts at +0.0 is never -0.0, so adding either zero leaves it unchanged bit for bit).
+// The test tier holds both claims on the uint32 patterns: tests/test_value_classes_gpu.py runs this kernel (CSR and TAPS forms), csr_group_mfma16_kernel and
+// convtaps_exact_fill_kernel on subnormal operands and results, underflowing and overflowing products and integer data full of -0.0 against the oracle, the sign
+// of every zero included; tests/test_value_classes_host.py holds the premise that the reference's sums are never -0.0.
 // So the 32 x 64 products of one stored column -- 32 member rows of a pattern group x 64 batch columns -- come out of ONE matrix instruction
 // (64 cycles of the matrix pipe), and the vector ALU only adds them to the running sums, in stored order: 16 v_pk_add_f32 (64 cycles).
 // MEASURED (tools/micro/mfma_add_rate.hip, profiles/r05_micro_*.txt): on gfx950 the f32 matrix instruction and the packed f32 adds do NOT

@@ -12,6 +12,7 @@ import numpy as np
 import pytest
 import torch
 
+import value_classes
 from keynet_amd import _capi
 from narrow_helpers import _spmm
 from test_parity_gpu import close_conditioned, dev
@@ -96,9 +97,10 @@ _ops = {}
 _refs = {}
 
 
-def _operator(name, switch):
-    """(handle, (shape, indptr, indices, data) of its expansion), created once per (operator, switch): the environment is read when a handle is created."""
-    if (name, switch) not in _ops:
+def _operator(name, switch, values=None):
+    """(handle, (shape, indptr, indices, data) of its expansion), created once per (operator, switch): the environment is read when a handle is created.
+    `values`: a variant of value_classes.conv_values -- the same operator with its values scaled by powers of two (tests/test_value_classes_gpu.py)."""
+    if (name, switch, values) not in _ops:
         (cin, cout, hw, per_pixel, coef, dup) = OPS[name]
         rng = np.random.RandomState(len(name) + 7 * cin)
         HW = hw * hw
@@ -108,6 +110,7 @@ def _operator(name, switch):
         taps = rng.randn(9, cout, cin).astype(np.float32)
         ec = (rng.rand(len(eo)).astype(np.float32) + 0.5) if coef else None
         lc = np.concatenate((rng.randn(cout * HW), [1.0])).astype(np.float32)
+        (taps, ec, lc) = value_classes.conv_values(values, taps, ec, lc, per_pixel * cin)
         if switch:
             os.environ[switch] = '1'
         try:
@@ -117,8 +120,8 @@ def _operator(name, switch):
             if switch:
                 del os.environ[switch]
         (ip, ix, dt) = op.export_csr()
-        _ops[(name, switch)] = (op, (op.shape(), ip, ix, dt))
-    return _ops[(name, switch)]
+        _ops[(name, switch, values)] = (op, (op.shape(), ip, ix, dt))
+    return _ops[(name, switch, values)]
 
 
 def _reference(name, n):

@@ -10,6 +10,7 @@ from torch import nn
 
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import oracle                                    # noqa: E402  (checker)
+from value_classes import bits_equal            # noqa: E402  (the uint32 patterns: the sign of a zero and a flushed subnormal count)
 from keynet_amd import _capi, sparse as ksp      # noqa: E402
 from keynet_amd.layer import KeyedLayer          # noqa: E402
 
@@ -79,7 +80,7 @@ def fuzz_chain(n_cases, seed=12345, verbose=False):
                 if m[4]:
                     ref = np.where(ref < 0, np.float32(0), ref)               # torch relu: NaN stays NaN
         got = yd.cpu().numpy()
-        if not np.array_equal(got, ref, equal_nan=True):
+        if not bits_equal(got, ref):
             bad += 1
             print('case', case, 'MISMATCH dims', dims, 'n', n, 'max', np.nanmax(np.abs(got - ref)))
         if rng.rand() < 0.3:
@@ -92,7 +93,7 @@ def fuzz_chain(n_cases, seed=12345, verbose=False):
             yw = torch.full((dims[-1], wide), -7.0, dtype=torch.float32, device=dev)
             chain.spmm(xw.data_ptr() + 4 * w0, wide, n, yw.data_ptr() + 4 * w0, wide, 2, S)
             yw = yw.cpu().numpy()
-            if not (np.array_equal(yw[:, w0:w0 + n], ref, equal_nan=True) and np.all(yw[:, :w0] == -7.0) and np.all(yw[:, w0 + n:] == -7.0)):
+            if not (bits_equal(yw[:, w0:w0 + n], ref) and np.all(yw[:, :w0] == -7.0) and np.all(yw[:, w0 + n:] == -7.0)):
                 bad += 1
                 print('case', case, 'WINDOW MISMATCH dims', dims, 'n', n, 'w0', w0, 'wide', wide)
     return (n_cases, refused, bad)
@@ -196,7 +197,7 @@ def fuzz_csr(n_cases, seed=4242, verbose=False):
                 W._device_op(dev).spmm(xw.data_ptr() + 4 * w0, wide, n_vecs, yw.data_ptr() + 4 * w0, wide, _capi.KN_FLAG_EXACT | (_capi.KN_FLAG_RELU if relu else 0),
                                        torch.cuda.current_stream().cuda_stream)
             yw = yw.cpu().numpy()
-            if not (np.array_equal(yw[:, w0:w0 + n_vecs], ref, equal_nan=True) and np.all(yw[:, :w0] == -7.0) and np.all(yw[:, w0 + n_vecs:] == -7.0)):
+            if not (bits_equal(yw[:, w0:w0 + n_vecs], ref) and np.all(yw[:, :w0] == -7.0) and np.all(yw[:, w0 + n_vecs:] == -7.0)):
                 bad += 1
                 print('case', case, 'WINDOW MISMATCH shape', (m, n), 'n_vecs', n_vecs, 'w0', w0, 'wide', wide)
         if not f64 and m * n_vecs < 4e6 and rng.rand() < 0.3:
@@ -223,13 +224,13 @@ def fuzz_csr(n_cases, seed=4242, verbose=False):
             with np.errstate(all='ignore'):
                 r0 = oracle.csr_matvecs((m, n), indptr, indices, data, np.ascontiguousarray(Xp[:n * ld].reshape(n, ld)[:, :n_vecs]))
                 r0 = np.where(r0 < 0, np.float32(0), r0) if relu else r0
-            if not np.array_equal(yb.cpu().numpy()[:m * ld].reshape(m, ld)[:, :n_vecs], r0, equal_nan=True):
+            if not bits_equal(yb.cpu().numpy()[:m * ld].reshape(m, ld)[:, :n_vecs], r0):
                 bad += 1
                 print('case', case, 'PLANE 0 differs from the oracle', (m, n), n_vecs)
         with torch.cuda.device(dev):
             import re
             fuzz_csr.kernels |= set(re.findall(r'(csr_\w+_kernel)', W._device_op(dev).plan(n_vecs, _capi.KN_FLAG_EXACT)))
-        if not np.array_equal(got, ref, equal_nan=True):
+        if not bits_equal(got, ref):
             bad += 1
             print('case', case, 'MISMATCH shape', (m, n), 'n_vecs', n_vecs, 'relu', relu, 'max', np.nanmax(np.abs(got - ref)))
     return (n_cases, bad)
@@ -330,10 +331,10 @@ def fuzz_convtaps(n_cases, seed=2024, verbose=False, only=None, hook=None):
                 W._device_op(dev).spmm(xw.data_ptr() + 4 * w0, wide, n_vecs, yw.data_ptr() + 4 * w0, wide, _capi.KN_FLAG_EXACT | (_capi.KN_FLAG_RELU if relu else 0),
                                        torch.cuda.current_stream().cuda_stream)
             yw = yw.cpu().numpy()
-            if not (np.array_equal(yw[:, w0:w0 + n_vecs], ref, equal_nan=True) and np.all(yw[:, :w0] == -7.0) and np.all(yw[:, w0 + n_vecs:] == -7.0)):
+            if not (bits_equal(yw[:, w0:w0 + n_vecs], ref) and np.all(yw[:, :w0] == -7.0) and np.all(yw[:, w0 + n_vecs:] == -7.0)):
                 bad += 1
                 print('case', case, 'WINDOW MISMATCH n_vecs', n_vecs, 'w0', w0, 'wide', wide, '|', plan[:120])
-        if not np.array_equal(got, ref, equal_nan=True):
+        if not bits_equal(got, ref):
             bad += 1
             print('case', case, 'MISMATCH', 'Cin', Cin, 'Cout', Cout, 'pixels', (Pin, Pout), 'taps', ntaps, 'entries', len(eo), 'filled', filled, 'coef', coef, 'last', has_last,
                   'n_vecs', n_vecs, 'relu', relu, 'max', np.nanmax(np.abs(got - ref)), '|', plan[:160])
@@ -385,7 +386,7 @@ def fuzz_tiled(n_cases, seed=99, verbose=False):
             if relu:
                 ref = np.where(ref < 0, np.float32(0), ref)
         got = W.torchdot(torch.as_tensor(X).to(dev), relu=relu).cpu().numpy()
-        if not np.array_equal(got, ref, equal_nan=True):
+        if not bits_equal(got, ref):
             bad += 1
             print('case', case, 'MISMATCH kind', kind, 'shape', (m, n), 'tile', W.tileshape(), 'n_vecs', n_vecs, 'max', np.nanmax(np.abs(got - ref)))
     return (n_cases, bad)
@@ -422,7 +423,7 @@ def fuzz_models(n_cases, seed=31337, verbose=False):
             z = np.load(os.path.join(d, 'k.npz'), allow_pickle=False)
             with np.errstate(all='ignore'):
                 ref = oracle.keynet_forward(oracle.load_golden_layers(z), xc.cpu().numpy())
-        ok_bits = np.array_equal(y, ref)
+        ok_bits = bits_equal(y, ref)
         ok_plain = bool(np.allclose(y[:, :plain.shape[1]], plain, atol=1e-4, rtol=1e-4))
         if not (ok_bits and ok_plain):
             bad += 1
@@ -459,7 +460,7 @@ def fuzz_dense(n_cases, seed=555, verbose=False):
         if relu:
             ref = np.where(ref < 0, np.float32(0), ref)
         xd = torch.as_tensor(X).to(dev)
-        if not np.array_equal(W.torchdot(xd, relu=relu).cpu().numpy(), ref):
+        if not bits_equal(W.torchdot(xd, relu=relu).cpu().numpy(), ref):
             bad += 1
             print('case', case, 'MISMATCH (stored order) outs', outs, 'ins', ins, 'n_vecs', n_vecs)
         ym = W.torchdot(xd, relu=relu, exact=False).cpu().numpy()
@@ -565,7 +566,7 @@ def fuzz_factored(n_cases, seed=777, verbose=False):
             with np.errstate(all='ignore'):
                 r = np.where(ref < 0, np.float32(0), ref) if relu else ref
             y = W.torchdot(torch.as_tensor(X).to(dev), relu=relu).cpu().numpy()
-            ok = np.array_equal(y, r, equal_nan=True)
+            ok = bits_equal(y, r)
             with torch.cuda.device(dev):
                 plan = W._device_op(dev).plan(n_vecs, 2 | (1 if relu else 0)).split(' ')[0]
             total += 1
@@ -588,7 +589,7 @@ def fuzz_factored(n_cases, seed=777, verbose=False):
             X = rng.randn(cols + 3, n_vecs).astype(np.float32)
             ref = oracle.csr_matvecs(M.shape, indptr, indices, data, X)
             y = W.torchdot(torch.as_tensor(X).to(dev), relu=False).cpu().numpy()
-            ok = np.array_equal(y, ref)
+            ok = bits_equal(y, ref)
             total += 1
             if verbose:
                 print('big  %3d rows %d cols %d n_vecs %d %s' % (case, rows, cols, n_vecs, 'ok' if ok else 'MISMATCH'), flush=True)

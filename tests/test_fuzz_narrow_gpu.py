@@ -18,6 +18,7 @@ import torch
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 import oracle                                    # noqa: E402  (checker)
+from value_classes import bits_equal            # noqa: E402  (the uint32 patterns: the sign of a zero and a flushed subnormal count)
 from keynet_amd import _capi                     # noqa: E402
 import fuzz_narrow_cases as fc                   # noqa: E402
 from fuzz_narrow_cases import RELU, EXACT, NARROW, MFMA, ROWS, N32, N64, N64M, LINEAR, TAPS, TAPS32, FILL      # noqa: E402
@@ -138,7 +139,7 @@ def fuzz_convtaps_narrow(n_cases, seed=CONV_SEED, verbose=False, only=None):
             ref = fc.oracle_product(fc.conv_reference(d), X[:, :n], relu=bool(relu))
             got = win.cpu().numpy()
         if not matrix_core:
-            if not np.array_equal(got, ref, equal_nan=True):
+            if not bits_equal(got, ref):
                 bad(d, 'differs from the oracle, max %r' % float(np.nanmax(np.abs(got - ref))), plan)
             y128 = _spmm(op, torch.as_tensor(X).to(dev), 128, EXACT | relu)[0][:, :n]
             keep = ~torch.isnan(y128)
@@ -220,7 +221,7 @@ def fuzz_csr_narrow(n_cases, seed=CSR_SEED, verbose=False, only=None):
                 ref = np.where(ref < 0, ref.dtype.type(0), ref)
             ref32 = ref.astype(np.float32)
         got = win.cpu().numpy()
-        if not np.array_equal(got, ref32, equal_nan=True):
+        if not bits_equal(got, ref32):
             bad(d, 'differs from the oracle, max %r' % float(np.nanmax(np.abs(got - ref32))), plan)
         if not _outside_intact(whole, n, start):
             bad(d, 'wrote outside the window', plan)
@@ -243,7 +244,7 @@ def fuzz_csr_narrow(n_cases, seed=CSR_SEED, verbose=False, only=None):
             y64 = torch.empty((d['shape'][0], n), dtype=torch.float64, device=dev)
             with torch.cuda.device(dev):
                 op.spmm_f64(xc.data_ptr(), n, n, y64.data_ptr(), n, flags, torch.cuda.current_stream().cuda_stream)
-            if not np.array_equal(y64.cpu().numpy(), ref, equal_nan=True):
+            if not bits_equal(y64.cpu().numpy(), ref):
                 bad(d, 'kn_spmm_f64 differs from the float64 oracle', plan)
     return counts
 
@@ -314,7 +315,7 @@ def fuzz_models_narrow(n_cases, seed=MODEL_SEED, verbose=False, only=None):
                       inshape, n, d['names'], kw, flush=True)
             continue
         ok_plain = bool(torch.equal(y, y0))
-        ok_bits = np.array_equal(yn, ref)
+        ok_bits = bits_equal(yn, ref)
         xc2 = sensor.fromtensor(x2.to(dev)).encrypt().astensor()
         replay = knet.capture(xc, **kw)
         r1 = replay(xc).clone()

@@ -69,6 +69,7 @@ import scipy.sparse
 import torch
 
 import oracle
+import value_classes
 from keynet_amd import sparse as ksp
 from keynet_amd import _capi
 from test_parity_gpu import _random_convtaps, close, close_conditioned, dev
@@ -133,12 +134,16 @@ def _env(env, make):
                 os.environ[k] = v
 
 
-def _csr_case(shape, ip, ix, dt, env=()):
+def _csr_case(shape, ip, ix, dt, env=(), values=None, has_last=False):
+    """`values`: a variant of value_classes.csr_values -- the builder's values by powers of two (tests/test_value_classes_gpu.py); None: as they are."""
     (ip, ix) = (np.asarray(ip, np.int32), np.asarray(ix, np.int32))
+    dt = value_classes.csr_values(values, shape, ip, ix, dt, has_last)
     return Case(_env(dict(env), lambda: _capi.Operator.csr(shape, ip, ix, dt)), shape, ip, ix, dt)
 
 
-def _conv_case(W, has_last, M=None, env=()):
+def _conv_case(W, has_last, M=None, env=(), values=None):
+    if values is not None:
+        (W, M) = value_classes.revalued_convtaps(W, values)
     op = _env(dict(env), lambda: W._device_op(dev()))
     if M is None:
         M = W.tosparse('csr')
@@ -147,7 +152,7 @@ def _conv_case(W, has_last, M=None, env=()):
 
 
 @functools.lru_cache(maxsize=None)
-def conv(Cin, Cout, H, k, stride, unit, has_last, gain=False, env=(), big_bias=False):
+def conv(Cin, Cout, H, k, stride, unit, has_last, gain=False, env=(), big_bias=False, values=None):
     rng = np.random.RandomState(1000 * Cin + 10 * Cout + H + k)
     assert unit or not gain
     W = _random_convtaps(rng, Cin, Cout, H, k, stride, unit, has_last)
@@ -159,24 +164,24 @@ def conv(Cin, Cout, H, k, stride, unit, has_last, gain=False, env=(), big_bias=F
         lastcol = t['lastcol'].copy()
         lastcol[-2] = 1e6
         W = ksp.Conv2dTiledMatrix.fromtaps(W._inshape, W._outshape, t['taps'], t['ent_out'], t['ent_in'], t['ent_tap'], t['ent_coef'], lastcol)
-    return _conv_case(W, has_last, env=env)
+    return _conv_case(W, has_last, env=env, values=values)
 
 
 @functools.lru_cache(maxsize=None)
-def dropped_zero_conv():
+def dropped_zero_conv(values=None):
     (W, M) = _dropped_zero_operator(np.random.RandomState(5), 16, 32, 8)        # (32 output channels: the operator carries the stored-column table too)
-    return _conv_case(W, True, M=M)
+    return _conv_case(W, True, M=M, values=values)
 
 
 @functools.lru_cache(maxsize=None)
-def grouped_csr(members=16, n_groups=1100, n=1024, env=()):
+def grouped_csr(members=16, n_groups=1100, n=1024, env=(), values=None):
     rng = np.random.RandomState(members + n_groups)
     (m, ip, ix, dt) = grouped_operator(rng, n, members, n_groups, lambda g: 1 + (g * 7) % 70)
-    return _csr_case((m, n), ip, ix, dt, env=env)
+    return _csr_case((m, n), ip, ix, dt, env=env, values=values)
 
 
 @functools.lru_cache(maxsize=None)
-def loose_csr(big_last=False):
+def loose_csr(big_last=False, values=None):
     rng = np.random.RandomState(3)
     (m, n) = (6000, 2048)
     lens = rng.randint(6, 12, m)
@@ -188,46 +193,46 @@ def loose_csr(big_last=False):
     if big_last:              # the last row's values scaled by 1e6: max |Y| then lies in a row whose offset is beyond 2^31 (kn_spmm_screen)
         assert ip[-1] - ip[-2] >= 6
         dt[ip[-2]:] *= np.float32(1e6)
-    return _csr_case((m, n), ip, ix, dt)
+    return _csr_case((m, n), ip, ix, dt, values=values)
 
 
 @functools.lru_cache(maxsize=None)
-def long_rows_csr():
+def long_rows_csr(long_rows=1100, values=None):
     """1 100 unrelated rows of 1 024 .. 1 100 stored entries each (duplicates, unsorted) and a few short ones."""
     rng = np.random.RandomState(4)
-    (m, n) = (1120, 1500)
-    lens = np.concatenate((rng.randint(1024, 1101, 1100), rng.randint(0, 9, 20)))
+    (m, n) = (long_rows + 20, 1500)
+    lens = np.concatenate((rng.randint(1024, 1101, long_rows), rng.randint(0, 9, 20)))
     ip = np.concatenate(([0], np.cumsum(lens))).astype(np.int32)
     ix = rng.randint(0, n, int(ip[-1])).astype(np.int32)
-    return _csr_case((m, n), ip, ix, (rng.randn(len(ix)) / 32).astype(np.float32))
+    return _csr_case((m, n), ip, ix, (rng.randn(len(ix)) / 32).astype(np.float32), values=values)
 
 
 @functools.lru_cache(maxsize=None)
-def linear_csr(outs=300, ins=2500, env=()):
+def linear_csr(outs=300, ins=2500, env=(), values=None):
     """A keyed nn.Linear in the stored order: every row the same unsorted column sequence (one big pattern group) and the loose homogeneous row."""
     rng = np.random.RandomState(outs + ins)
     perm = rng.permutation(ins + 1).astype(np.int32)
     ix = np.concatenate([perm] * outs + [np.array([ins], np.int32)])
     ip = np.concatenate((np.arange(outs + 1) * (ins + 1), [outs * (ins + 1) + 1])).astype(np.int32)
     dt = np.concatenate(((rng.randn(outs * (ins + 1)) / np.sqrt(ins)).astype(np.float32), [np.float32(1.0)]))
-    c = _csr_case((outs + 1, ins + 1), ip, ix, dt, env=env)
+    c = _csr_case((outs + 1, ins + 1), ip, ix, dt, env=env, values=values, has_last=True)
     c.has_last = True
     return c
 
 
 @functools.lru_cache(maxsize=None)
-def f64_csr():
+def f64_csr(values=None):
     rng = np.random.RandomState(100)
     (m, n) = (301, 157)
     rows = [np.zeros(0, np.int32) if r % 17 == 0 else rng.randint(0, n, 3000 if r == 5 else rng.randint(1, 90)).astype(np.int32) for r in range(m)]
     ip = np.concatenate(([0], np.cumsum([len(r) for r in rows]))).astype(np.int32)
     ix = np.concatenate(rows)
     dt = rng.randn(len(ix)) * np.exp(rng.uniform(-30, 30, len(ix)))
-    return _csr_case((m, n), ip, ix, dt)
+    return _csr_case((m, n), ip, ix, dt, values=values)
 
 
 @functools.lru_cache(maxsize=None)
-def patched_csr():
+def patched_csr(values=None):
     """test_patched_group_members_vs_oracle's operator: group members that lost entries; returns (case, (row, missing columns) of the patched rows)."""
     rng = np.random.RandomState(11)
     (n_cols, n_groups, members, seq_len) = (700, 9, 21, 70)
@@ -251,7 +256,7 @@ def patched_csr():
         ix.extend(int(v) for v in c)
         dt.extend(rng.randn(len(c)).astype(np.float32))
         ip.append(len(ix))
-    return (_csr_case((len(ip) - 1, n_cols), ip, ix, np.array(dt, np.float32)), missing)
+    return (_csr_case((len(ip) - 1, n_cols), ip, ix, np.array(dt, np.float32), values=values), missing)
 
 
 @functools.lru_cache(maxsize=None)

@@ -12,6 +12,7 @@ import numpy as np
 import pytest
 import torch
 
+import value_classes
 from keynet_amd import io as kio
 from keynet_amd import sparse as ksp
 from keynet_amd import _capi
@@ -47,18 +48,21 @@ INELIGIBLE = [
 _built = {}
 
 
-def _build(case, seed=7):
-    """(W, sorted CSR, X [cols, 128], oracle product at 32 columns): built once per case and shared, never modified."""
-    if case[0] not in _built:
+def _build(case, seed=7, values=None):
+    """(W, sorted CSR, X [cols, 128], oracle product at 32 columns): built once per case and shared, never modified.  `values`: a variant of
+    value_classes.conv_values (tests/test_value_classes_gpu.py): the same operator with its values scaled by powers of two."""
+    if (case[0], values) not in _built:
         (tag, gen, args) = case
         rng = np.random.RandomState(seed)
         W = _filled_in_convtaps(rng, *args) if gen == 'filled' else _random_convtaps(rng, *args)
+        if values is not None:
+            W = value_classes.revalued_convtaps(W, values)[0]
         M = _sorted_csr(W)
         X = rng.randn(W.shape[1], 128).astype(np.float32)
         if args[-1]:
             X[-1] = 1.0
-        _built[case[0]] = (W, M, X, _oracle(M, X[:, :32]))
-    return _built[case[0]]
+        _built[(case[0], values)] = (W, M, X, _oracle(M, X[:, :32]))
+    return _built[(case[0], values)]
 
 
 def _op(W):

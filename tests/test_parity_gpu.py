@@ -1,5 +1,7 @@
 """Parity of the HIP path (through the C ABI) against the reference's vectors and the CPU oracle.  Needs an MI355X."""
 import copy
+import functools
+
 import numpy as np
 import pytest
 import torch
@@ -1099,35 +1101,51 @@ def test_explicit_tile_loop_on_device(golden):
         TorchTiled._torchdot(torch.zeros(3, 2, device=dev()), (2, 2), (4, 4), [np.zeros((0, 3))], [])
 
 
+# the layer builders of the whole-net kernel's tests (below, and tests/test_value_classes_gpu.py): (indptr, indices, data) drawn from `rng`
+def _chain_grouped(rng, rows, cols, group, nnz, tail_loose):
+    (ip, ix, dt) = ([0], [], [])
+    shared = None
+    for r in range(rows):
+        if r >= rows - tail_loose:
+            c = rng.randint(0, cols, size=rng.randint(1, 6))         # the odd rows at the end: patterns of their own (e.g. the homogeneous row)
+        else:
+            if r % group == 0:
+                shared = rng.randint(0, cols, size=nnz)
+            c = shared
+        ix.extend(int(v) for v in c)
+        dt.extend(rng.randn(len(c)).astype(np.float32))
+        ip.append(len(ix))
+    return (np.array(ip, np.int32), np.array(ix, np.int32), np.array(dt, np.float32))
+
+
+def _chain_dense(rng, rows, cols, seq_len=None):
+    perm = rng.permutation(cols)[:seq_len]
+    (ip, ix, dt) = ([0], [], [])
+    for r in range(rows):
+        ix.extend(int(v) for v in perm)
+        dt.extend(rng.randn(len(perm)).astype(np.float32))
+        ip.append(len(ix))
+    return (np.array(ip, np.int32), np.array(ix, np.int32), np.array(dt, np.float32))
+
+
+def _chain_dense_plus(rng, rows, cols, n_other):
+    """A keyed Linear as the reference stores it: `rows - n_other` rows sharing one permuted column sequence + n_other rows of their own (the homogeneous row ...)."""
+    (ip, ix, dt) = _chain_dense(rng, rows - n_other, cols)
+    (ip, ix, dt) = (list(ip), list(ix), list(dt))
+    for _ in range(n_other):
+        c = rng.choice(cols, size=rng.randint(1, 4), replace=False)
+        ix.extend(int(v) for v in c)
+        dt.extend(rng.randn(len(c)).astype(np.float32))
+        ip.append(len(ix))
+    return (np.array(ip, np.int32), np.array(ix, np.int32), np.array(dt, np.float32))
+
+
 def test_whole_net_kernel_layout_choices_vs_oracle():
     """The whole-net kernel's per-layer layout choices, each against the CPU oracle bit for bit: conv-like layers (groups of rows sharing an
     unsorted column sequence) with their pattern pool in LDS -- including a last slice of unrelated rows that is stored the same way --, a
     conv-like layer whose pool does NOT fit beside the activations (columns from memory), and a Linear on the thin walk behind them."""
     rng = np.random.RandomState(7)
-
-    def grouped(rows, cols, group, nnz, tail_loose):
-        (ip, ix, dt) = ([0], [], [])
-        shared = None
-        for r in range(rows):
-            if r >= rows - tail_loose:
-                c = rng.randint(0, cols, size=rng.randint(1, 6))         # the odd rows at the end: patterns of their own (e.g. the homogeneous row)
-            else:
-                if r % group == 0:
-                    shared = rng.randint(0, cols, size=nnz)
-                c = shared
-            ix.extend(int(v) for v in c)
-            dt.extend(rng.randn(len(c)).astype(np.float32))
-            ip.append(len(ix))
-        return (np.array(ip, np.int32), np.array(ix, np.int32), np.array(dt, np.float32))
-
-    def dense(rows, cols, seq_len=None):
-        perm = rng.permutation(cols)[:seq_len]
-        (ip, ix, dt) = ([0], [], [])
-        for r in range(rows):
-            ix.extend(int(v) for v in perm)
-            dt.extend(rng.randn(len(perm)).astype(np.float32))
-            ip.append(len(ix))
-        return (np.array(ip, np.int32), np.array(ix, np.int32), np.array(dt, np.float32))
+    (grouped, dense, dense_plus) = (functools.partial(_chain_grouped, rng), functools.partial(_chain_dense, rng), functools.partial(_chain_dense_plus, rng))
 
     def run(layers, want):
         (ops, mats) = ([], [])
@@ -1150,17 +1168,6 @@ def test_whole_net_kernel_layout_choices_vs_oracle():
                 if relu:
                     ref = np.where(ref < 0, np.float32(0), ref)              # torch relu: NaN stays NaN
         assert np.array_equal(yd.cpu().numpy(), ref, equal_nan=True)
-
-    def dense_plus(rows, cols, n_other):
-        """A keyed Linear as the reference stores it: `rows - n_other` rows sharing one permuted column sequence + n_other rows of their own (the homogeneous row ...)."""
-        (ip, ix, dt) = dense(rows - n_other, cols)
-        (ip, ix, dt) = (list(ip), list(ix), list(dt))
-        for _ in range(n_other):
-            c = rng.choice(cols, size=rng.randint(1, 4), replace=False)
-            ix.extend(int(v) for v in c)
-            dt.extend(rng.randn(len(c)).astype(np.float32))
-            ip.append(len(ix))
-        return (np.array(ip, np.int32), np.array(ix, np.int32), np.array(dt, np.float32))
 
     # (round 6: a thin layer BEHIND another layer is walked sequentially -- the layer before it writes its output in the thin layer's stored column order)
     run([((645, 200), grouped(645, 200, 6, 11, 5), 1), ((130, 645), grouped(130, 645, 16, 50, 2), 0), ((70, 130), dense(70, 130), 1), ((10, 70), dense(10, 70), 0)],
