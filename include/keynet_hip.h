@@ -175,6 +175,23 @@ enum kn_status {
                               alone decides there) and at n_vecs > 32; in every other regime; on an ineligible operator; where KN_FLAG_NARROW_FILL takes the launch; on
                               CSR, dense, float64 and chain handles; in kn_spmm_planes.  KN_FLAG_NARROW_TAPS without this bit stays a no-op at n_vecs > 8.
                               kn_spmm_plan names the kernel, the value rows, NV, the masked width, the column blocks and `coef`.  No reference counterpart. */
+#define KN_MODIFIER_NARROW_TAPS_PAIRS (0x2000u)  /* = 8192.  A MODIFIER of KN_FLAG_NARROW_TAPS: with BOTH bits, the tap-resident form of KN_FLAG_NARROW at 1 <= n_vecs <= 8
+                              computes the same product, bit for bit, with TWO output channels per lane and packed f32 arithmetic.
+                              It takes effect ONLY where the call would run convtaps_narrow_taps_kernel (the rule of KN_FLAG_NARROW_TAPS above) on an operator of more than
+                              64 output channels.  There the call runs convtaps_narrow_taps_pairs_kernel: a wavefront owns one output pixel x 128 output channels (lane l:
+                              channels 128 b + l and 128 b + 64 + l, the two halves of a register pair) x NV = 1 | 2 | 4 | 8 running sums per channel; the pixel's slot
+                              list stays in scalar registers, an input channel's value rows of all taps are loaded once into 16 vector register pairs, one channel ahead,
+                              and a step is one scalar activation load, one indexed read of a register pair and NV v_pk_mul_f32 + NV v_pk_add_f32 -- each element its own
+                              IEEE multiply and its own IEEE add, the step's scalar half paid once for 128 channels.  A trailing block of 64 padded channels re-reads its
+                              first half's value rows and stores nothing for the second.  Same order, same separate roundings, same bias entry, ReLU, homogeneous row
+                              and zero guard as KN_FLAG_NARROW: the result equals KN_FLAG_NARROW's and KN_FLAG_EXACT's.  An operator with coefficients runs 5 .. 8 columns
+                              as two launches of this kernel, columns 0 .. 3 and the rest, as it does on convtaps_narrow_taps_kernel.
+                              A launch has half the wavefronts of convtaps_narrow_taps_kernel's: the (shape, width) pairs whose launch was not faster in a kernel
+                              trace (deep layers of few pixels: fewer than 1 024 wavefronts at every width, fewer than 4 096 up to 4 columns) keep that kernel.
+                              Where it changes NOTHING (same kernels, same plan string, same bits; it never refuses): without KN_FLAG_NARROW_TAPS; at n_vecs > 8; where
+                              KN_FLAG_NARROW_MFMA runs the matrix-core kernel; where KN_FLAG_NARROW_FILL takes the launch; on operators of 64 output channels or fewer;
+                              on an ineligible operator or call; on CSR, dense, float64 and chain handles; in kn_spmm_planes.
+                              kn_spmm_plan names the kernel, the value rows, NV, the masked width and `coef`.  No reference counterpart. */
 #define KN_FLAG_NARROW_FILL (0x800u)  /* = 2048.  A MODIFIER of the channel-lane forms of KN_FLAG_NARROW (1 .. 8 columns) and KN_FLAG_NARROW | KN_FLAG_NARROW32 (9 .. 32): the same
                               product, bit for bit, for FILLED-IN operators (summed stored values, hundreds of slots per output pixel: the reference's doubly-stochastic keys).
                               It takes effect ONLY where the call would run convtaps_narrow_kernel or convtaps_narrow32_kernel: on a conv-taps handle with KN_FLAG_NARROW, or

@@ -31,6 +31,10 @@ KN_MODIFIER_NARROW_FILL = 0x800
 # KN_MODIFIER_NARROW_TAPS32 of include/keynet_hip.h: modifier of KN_FLAG_NARROW_TAPS -- with both bits an eligible conv-taps operator runs convtaps_narrow_taps32_kernel (taps
 # resident, packed f32 multiplies and adds) at 9 .. 32 columns under KN_FLAG_NARROW | KN_FLAG_NARROW32, same bits; everywhere else it changes nothing
 KN_MODIFIER_NARROW_TAPS32 = 0x1000
+# KN_MODIFIER_NARROW_TAPS_PAIRS of include/keynet_hip.h: modifier of KN_FLAG_NARROW_TAPS -- with both bits an eligible conv-taps operator of more than 64 output channels
+# runs convtaps_narrow_taps_pairs_kernel (two output channels per lane, packed f32 multiplies and adds) at 1 .. 8 columns under KN_FLAG_NARROW, same bits; everywhere
+# else it changes nothing
+KN_MODIFIER_NARROW_TAPS_PAIRS = 0x2000
 KN_ABI_VERSION = 5
 
 # every symbol include/keynet_hip.h declares (tests/test_capi.py checks the header against this list)

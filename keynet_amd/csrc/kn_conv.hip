@@ -1441,6 +1441,7 @@ __global__ __launch_bounds__(256) void convtaps_narrow_kernel(ConvArgs p, int n_
 
 #include "kn_conv_narrow_taps.inc"
 #include "kn_conv_narrow_taps32.inc"
+#include "kn_conv_narrow_taps_pairs.inc"
 #include "kn_conv_narrow_fill.inc"
 
 // ---- order-preserving path for 9 .. 32 batch columns (KN_FLAG_NARROW32 next to KN_FLAG_NARROW): lanes are OUTPUT CHANNELS, columns come in blocks ---
@@ -2676,6 +2677,26 @@ static NarrowTapsKernel narrow_taps_kernel(int nv, bool full, int pix, bool coef
     }
 }
 
+// NARROW with KN_FLAG_NARROW_TAPS | KN_MODIFIER_NARROW_TAPS_PAIRS on an eligible operator of more than 64 output channels (narrow_taps_pairs_call):
+// convtaps_narrow_taps_pairs_kernel (kn_conv_narrow_taps_pairs.inc), one pixel and 128 output channels per wavefront.  The shipped forms: NT = 9 | 16 value rows per
+// channel (the next that holds the operator's taps), NV as the width (4 and 8 also masked), with coefficients for NV <= 4 -- an operator with
+// coefficients runs 5 .. 8 columns as the same two column blocks it runs on convtaps_narrow_taps_kernel, both on this kernel.  A form that is not built is nullptr, and
+// the call keeps convtaps_narrow_taps_kernel.
+template <int NT, int NV, bool FULL>
+static NarrowTapsKernel narrow_taps_pairs_kernel_of(bool coef) {
+    if constexpr (NV == 8) return coef ? nullptr : convtaps_narrow_taps_pairs_kernel<NT, NV, FULL, false>;      // (no such form with coefficients)
+    else return coef ? convtaps_narrow_taps_pairs_kernel<NT, NV, FULL, true> : convtaps_narrow_taps_pairs_kernel<NT, NV, FULL, false>;
+}
+template <int NT>
+static NarrowTapsKernel narrow_taps_pairs_kernel(int nv, bool full, bool coef) {
+    switch (nv) {                                        // (a width of 1 or 2 columns always fills its form)
+        case 1: return narrow_taps_pairs_kernel_of<NT, 1, true>(coef);
+        case 2: return narrow_taps_pairs_kernel_of<NT, 2, true>(coef);
+        case 4: return full ? narrow_taps_pairs_kernel_of<NT, 4, true>(coef) : narrow_taps_pairs_kernel_of<NT, 4, false>(coef);
+        default: return full ? narrow_taps_pairs_kernel_of<NT, 8, true>(coef) : narrow_taps_pairs_kernel_of<NT, 8, false>(coef);
+    }
+}
+
 // NARROW32 with KN_FLAG_NARROW_TAPS | KN_MODIFIER_NARROW_TAPS32 on an eligible operator (narrow_taps32_call): convtaps_narrow_taps32_kernel (kn_conv_narrow_taps32.inc) behind
 // the block width and count of the regime's rule.  The shipped forms: NT = 9 | 16 value rows per channel (the next that holds the operator's taps), NV = 8 | 16 | 32, full and
 // masked; with coefficients NV = 8 only -- the forms with coefficients at NV = 16 | 32 (nine more resident scalar registers next to 32 of activations) compiled with scalar
@@ -2721,6 +2742,8 @@ struct NarrowChoice {
     int taps_pix = 0;               // NARROW: 0 = convtaps_narrow_kernel, else convtaps_narrow_taps_kernel with this many pixels per wavefront (1 | 2) ...
     int taps_nt = 0;                // ... and this many value rows per channel (9 | 16)
     int n_grp = 0;                  // ... over this many pixel groups
+    bool taps_pairs = false;        // ... kernel.taps (and taps_b) is convtaps_narrow_taps_pairs_kernel: one pixel per wavefront (taps_pix = 1, n_grp = n_pix) ...
+    int n_cb2 = 0;                  // ... x this many 128-channel blocks
     bool taps32 = false;            // NARROW32: kernel.lanes32 is convtaps_narrow_taps32_kernel (taps_nt value rows per channel), on the regime's own w, n_colb and n_wg
     NarrowTapsKernel taps_b = nullptr;      // ... and, where the columns run as two blocks (coefficients at 5 .. 8 columns), the kernel of columns 4 .. and their width
     NarrowWidth w_b = {1, 0, true};
@@ -2770,6 +2793,20 @@ static NarrowChoice narrow_choice(const ConvTapsDev& A, const ConvArgs& a, ConvR
             c.n_grp = (a.n_pix + pix - 1) / pix;
             c.n_wg = ((int64_t)c.n_grp * c.n_cb + 3) / 4;
             c.kernel.taps = form(c.w);
+            // KN_MODIFIER_NARROW_TAPS_PAIRS: the channel-pair kernel on the same widths and column blocks, where every form the call needs is built
+            if (narrow_taps_pairs_call(A, flags, a.n_vecs)) {
+                auto form2 = [&](const NarrowWidth& w) { return nine ? narrow_taps_pairs_kernel<9>(w.nv, w.full, coef) : narrow_taps_pairs_kernel<16>(w.nv, w.full, coef); };
+                const NarrowTapsKernel k = form2(c.w), k_b = c.taps_b ? form2(c.w_b) : nullptr;
+                if (k && (!c.taps_b || k_b)) {
+                    c.taps_pairs = true;
+                    c.taps_pix = 1;
+                    c.n_grp = a.n_pix;
+                    c.n_cb2 = (int)((A.Cout + 127) / 128);
+                    c.n_wg = ((int64_t)a.n_pix * c.n_cb2 + 3) / 4;
+                    c.kernel.taps = k;
+                    if (c.taps_b) c.taps_b = k_b;
+                }
+            }
         }
     } else if (regime == NARROW32) {
         if (narrow_fill_takes(A, a, flags)) {                // KN_FLAG_NARROW_FILL: blocks of 8 columns, the last one masked
@@ -2843,19 +2880,23 @@ static int launch_narrow(const ConvTapsDev& A, const ConvArgs& a, const NarrowCh
                   c.kernel.lanes32, grid, dim3(256), 0, s, a, c.n_cb, c.n_colb, n_wg);
     else if (c.taps_pix > 0) {
         auto name = [&](const NarrowWidth& wk, int64_t cols, const char* block) {
+            if (c.taps_pairs)
+                return "convtaps_narrow_taps_pairs_kernel<" + std::to_string(c.taps_nt) + " value rows, NV=" + std::to_string(wk.nv) + (wk.full ? "" : ", masked to " + std::to_string(cols)) +
+                       (coef ? ", coef" : "") + std::string(block) + "> (lane = two output channels, taps resident, packed f32)";
             return "convtaps_narrow_taps_kernel<" + std::to_string(c.taps_nt) + " value rows, P=" + std::to_string(c.taps_pix) + ", NV=" + std::to_string(wk.nv) +
                    (wk.full ? "" : ", masked to " + std::to_string(cols)) + (coef ? ", coef" : "") + std::string(block) + "> (lane = output channel, taps resident)";
         };
+        const int n_blk = c.taps_pairs ? c.n_cb2 : c.n_cb;      // channel blocks of the kernel: 128 channels each, or 64
         if (c.taps_b) {                              // columns 0 .. 3, then columns 4 .. n_vecs - 1: each block a window of X and Y
             ConvArgs a0 = a, a1 = a;
             a0.n_vecs = 4;
             a1.n_vecs = a.n_vecs - 4;
             a1.X = a.X + 4;
             a1.Y = a.Y + 4;
-            KN_LAUNCH(name(w, 4, ", columns 0 .. 3"), c.kernel.taps, grid, dim3(256), 0, s, a0, c.n_cb, c.n_grp, n_wg);
-            KN_LAUNCH(name(c.w_b, a1.n_vecs, ", columns 4 .."), c.taps_b, grid, dim3(256), 0, s, a1, c.n_cb, c.n_grp, n_wg);
+            KN_LAUNCH(name(w, 4, ", columns 0 .. 3"), c.kernel.taps, grid, dim3(256), 0, s, a0, n_blk, c.n_grp, n_wg);
+            KN_LAUNCH(name(c.w_b, a1.n_vecs, ", columns 4 .."), c.taps_b, grid, dim3(256), 0, s, a1, n_blk, c.n_grp, n_wg);
         } else {
-            KN_LAUNCH(name(w, a.n_vecs, ""), c.kernel.taps, grid, dim3(256), 0, s, a, c.n_cb, c.n_grp, n_wg);
+            KN_LAUNCH(name(w, a.n_vecs, ""), c.kernel.taps, grid, dim3(256), 0, s, a, n_blk, c.n_grp, n_wg);
         }
     } else
         KN_LAUNCH("convtaps_narrow_kernel<" + std::to_string(w.nv) + (w.full ? "" : ",masked to " + std::to_string(a.n_vecs)) + (A.has_dups ? ",stored values summed" : "") + (coef ? ",coef" : "") +

@@ -459,6 +459,34 @@ static inline bool narrow_taps32_call(const ConvTapsDev& A, uint32_t flags, int6
     return (flags & KN_FLAG_NARROW_TAPS) && (flags & KN_MODIFIER_NARROW_TAPS32) && n_vecs > NARROW_MAX_VECS && n_vecs <= NARROW32_MAX_VECS && narrow_taps_ok(A) &&
            !narrow_taps32_loses(A, n_vecs);
 }
+// KN_MODIFIER_NARROW_TAPS_PAIRS, a modifier of KN_FLAG_NARROW_TAPS in regime NARROW (1 .. 8 columns): an operator eligible for KN_FLAG_NARROW_TAPS (narrow_taps_ok) with more
+// than 64 output channels runs convtaps_narrow_taps_pairs_kernel (kn_conv_narrow_taps_pairs.inc: two output channels per lane, packed f32) when the call carries BOTH
+// bits, bit for bit convtaps_narrow_taps_kernel's result.  Everywhere else -- without KN_FLAG_NARROW_TAPS, beyond 8 columns, in regime NARROW_MFMA, where
+// KN_FLAG_NARROW_FILL takes the launch, on operators of 64 output channels or fewer, on an ineligible operator, on other handle kinds, in kn_spmm_planes -- the bit is not
+// read.  narrow_taps_pairs_call is the one place that reads it; narrow_choice (kn_conv.hip) asks it behind narrow_taps_call and the per-call offset condition, and adds
+// whether the form is built.
+// narrow_taps_pairs_loses: the (shape, width) pairs whose launch is not faster than convtaps_narrow_taps_kernel's in a kernel trace by more than the two min .. max
+// spreads added (profiles/r18_narrow_taps_pairs.txt: keyed VGG-16, three launches a side, medians in us).  The kernel halves the instructions per channel AND the
+// wavefronts of a launch; what it loses is shapes whose 128-channel blocks x pixels leave the 1 024 SIMDs few wavefronts each, the more so the shorter a step (NV):
+//   conv5_x (512 -> 512 channels, 196 pixels: 784 wavefronts), every width:    1 image 207.1 -> 309.9, 2: 221.5 -> 337.8, 4: 277.8 -> 387.2, 8: 494.6 -> 568.2
+//   conv4_x (256 | 512 -> 512, 784 pixels: 3 136 wavefronts), NV <= 4:         1 image 406.9 -> 428.1 (conv4_1 211.3 -> 219.2), 2: 410.4 -> 465.5, 4: 545.4 -> 651.9;
+//                                                                              NV = 8 wins (1 214.9 -> 974.7)
+//   conv3_x (128 | 256 -> 256, 3 136 pixels: 6 272 wavefronts), NV = 4:        278.7 -> 282.5, 567.2 -> 559.2, 572.1 -> 553.8 (gains inside the spreads);
+//                                                                              NV = 1 | 2 | 8 win (1.07 - 1.32x)
+//   conv2_x (64 | 128 -> 128, 12 544 pixels: 12 544 wavefronts) wins at every width (1.18 - 1.43x).
+// The thresholds are the next powers of two above the measured counts.  Only operators of 128 input channels and more are listed: every measured shape has them, and
+// a shorter channel loop (the operators of the tests, first layers) is not measured -- it stays on the kernel the caller asked for.  Widths 3, 5, 6, 7 take the row
+// of the form they run (NV = 4, NV = 8, masked); not traced.
+static inline bool narrow_taps_pairs_loses(const ConvTapsDev& A, int64_t n_vecs) {
+    if (A.Cin < 128) return false;
+    const int64_t waves = A.Hout * A.Wout * ((A.Cout + 127) / 128);
+    const int nv = n_vecs <= 1 ? 1 : (n_vecs <= 2 ? 2 : (n_vecs <= 4 ? 4 : 8));
+    return waves < 1024 || (waves < 4096 && nv <= 4) || (waves < 8192 && nv == 4);
+}
+static inline bool narrow_taps_pairs_call(const ConvTapsDev& A, uint32_t flags, int64_t n_vecs) {
+    return (flags & KN_FLAG_NARROW_TAPS) && (flags & KN_MODIFIER_NARROW_TAPS_PAIRS) && n_vecs <= NARROW_MAX_VECS && narrow_taps_ok(A) && A.Cout > 64 &&
+           !narrow_taps_pairs_loses(A, n_vecs);
+}
 // KN_FLAG_NARROW_FILL, a modifier of regimes NARROW and NARROW32 (KN_FLAG_NARROW [| KN_FLAG_NARROW32] at 1 .. 32 columns, or KN_FLAG_NARROW_MFMA where that flag means
 // KN_FLAG_NARROW): an ELIGIBLE operator runs convtaps_narrow_fill_kernel (kn_conv_narrow_fill.inc), bit for bit the channel-lane kernels' result.  Eligible: the handle has
 // the record lists of the filled-in order-preserving kernel (convtaps_fill_ok: summed stored values, or more than 64 slots on some output pixel), 1 .. 16 taps (the records

@@ -286,6 +286,8 @@ class KeyedLayer(nn.Module):
         the non-conv ones with a conv-taps handle; the library runs the tap-resident kernel on an eligible operator at up to NARROW_MAX columns and ignores the bit elsewhere.
         narrow_taps='packed': KN_MODIFIER_NARROW_TAPS32 next to it, on exactly the same launches -- with KN_FLAG_NARROW32 the library runs convtaps_narrow_taps32_kernel on an
         eligible operator at NARROW_MAX + 1 .. NARROW32_MAX columns; up to NARROW_MAX columns the call is narrow_taps=True.
+        narrow_taps='pairs': KN_MODIFIER_NARROW_TAPS_PAIRS next to both bits, on exactly the same launches -- at up to NARROW_MAX columns the library runs
+        convtaps_narrow_taps_pairs_kernel on an eligible operator of more than 64 output channels; beyond, the call is narrow_taps='packed'.
         `narrow_fill` (with `narrow`): KN_FLAG_NARROW_FILL (_capi.KN_MODIFIER_NARROW_FILL) on exactly the same launches -- with narrow_split=True those are the layers not on the
         route; the library runs convtaps_narrow_fill_kernel on an eligible (filled-in) operator at up to NARROW32_MAX columns and ignores the bit elsewhere."""
         form = ksp.NarrowForm.of(None, narrow, narrow_rows, narrow32, narrow64, narrow_linear, narrow_split=narrow_split, narrow_taps=narrow_taps, narrow_fill=narrow_fill)
@@ -306,7 +308,7 @@ class KeyedLayer(nn.Module):
         if mfma:
             (exact, bf16x3) = (False, False)
         return (get_op, (_capi.KN_FLAG_RELU if relu else 0) | (_capi.KN_FLAG_EXACT if exact else 0) | (_capi.KN_FLAG_BF16X3 if bf16x3 else 0) |
-                (_capi.KN_FLAG_NARROW_MFMA if mfma else _capi.KN_FLAG_NARROW if lane else 0) | (_capi.KN_FLAG_NARROW_TAPS if form.taps and lane and not mfma else 0) | (_capi.KN_MODIFIER_NARROW_TAPS32 if form.taps == 'packed' and lane and not mfma else 0) | (_capi.KN_MODIFIER_NARROW_FILL if form.fill and lane and not mfma else 0) | (_capi.KN_FLAG_NARROW32 if lane and form.narrow32 else 0) | (_capi.KN_FLAG_NARROW64 if lane and form.narrow64 else 0) |
+                (_capi.KN_FLAG_NARROW_MFMA if mfma else _capi.KN_FLAG_NARROW if lane else 0) | (_capi.KN_FLAG_NARROW_TAPS if form.taps and lane and not mfma else 0) | (_capi.KN_MODIFIER_NARROW_TAPS32 if form.taps in ('packed', 'pairs') and lane and not mfma else 0) | (_capi.KN_MODIFIER_NARROW_TAPS_PAIRS if form.taps == 'pairs' and lane and not mfma else 0) | (_capi.KN_MODIFIER_NARROW_FILL if form.fill and lane and not mfma else 0) | (_capi.KN_FLAG_NARROW32 if lane and form.narrow32 else 0) | (_capi.KN_FLAG_NARROW64 if lane and form.narrow64 else 0) |
                 (_capi.KN_FLAG_NARROW64_MFMA if mfma and form.tile64 and contract in (False, 'bf16x3') else 0) |
                 (_capi.KN_FLAG_NARROW_ROWS if form.rows and stored else 0) | (_capi.KN_FLAG_NARROW_LINEAR if form.linear and stored else 0))
 

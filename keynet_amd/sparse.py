@@ -179,6 +179,8 @@ class NarrowForm(collections.namedtuple('NarrowForm', 'mode rows narrow32 narrow
     NarrowTapsForm, or with narrow_split=True a NarrowSplitTapsForm; each kind equals its own kind only.
     narrow_taps='packed' (KN_MODIFIER_NARROW_TAPS32 next to KN_FLAG_NARROW_TAPS: the packed tap-resident kernel at NARROW_MAX + 1 .. NARROW32_MAX columns) is a kind of its
     own again, the `packed` twin of the kind narrow_taps=True gives (_packed_kind), with `taps` == 'packed'.
+    narrow_taps='pairs' (KN_MODIFIER_NARROW_TAPS_PAIRS next to both: the channel-pair tap-resident kernel at 1 .. NARROW_MAX columns, 'packed' beyond) likewise: the
+    `pairs` twin (_pairs_kind), with `taps` == 'pairs'.
     `fill`: the opt-in eighth keyword narrow_fill=True (only with `narrow`: KN_FLAG_NARROW_FILL on the same launches), carried the same way: the kind of the call without
     it has a `fill` twin (_fill_kind: NarrowFillForm, NarrowSplitFillForm, NarrowTapsFillForm, NarrowSplitTapsFillForm), which equals its own kind only."""
     __slots__ = ()
@@ -200,6 +202,8 @@ class NarrowForm(collections.namedtuple('NarrowForm', 'mode rows narrow32 narrow
             kind = _fill_kind[kind]
         if taps and narrow_taps == 'packed':
             kind = _packed_kind[kind]
+        elif taps and narrow_taps == 'pairs':
+            kind = _pairs_kind[kind]
         return kind(mode, bool(narrow_rows), bool(narrow32 or narrow64), bool(narrow64), mode == 'mfma' and narrow64 == 'mfma' and (n is None or n > NARROW32_MAX), bool(narrow_linear))
 
     def keywords(self):
@@ -209,7 +213,7 @@ class NarrowForm(collections.namedtuple('NarrowForm', 'mode rows narrow32 narrow
         if self.split:
             kw['narrow_split'] = True
         if self.taps:
-            kw['narrow_taps'] = self.taps         # True | 'packed'
+            kw['narrow_taps'] = self.taps         # True | 'packed' | 'pairs'
         if self.fill:
             kw['narrow_fill'] = True
         return kw
@@ -272,6 +276,19 @@ NarrowSplitPackedForm = _packed_twin(NarrowSplitTapsForm, 'NarrowSplitPackedForm
 NarrowPackedFillForm = _packed_twin(NarrowTapsFillForm, 'NarrowPackedFillForm')
 NarrowSplitPackedFillForm = _packed_twin(NarrowSplitTapsFillForm, 'NarrowSplitPackedFillForm')
 _packed_kind = {NarrowTapsForm: NarrowPackedForm, NarrowSplitTapsForm: NarrowSplitPackedForm, NarrowTapsFillForm: NarrowPackedFillForm, NarrowSplitTapsFillForm: NarrowSplitPackedFillForm}
+
+
+def _pairs_twin(kind, name):
+    """The kind of the calls that passed narrow_taps='pairs' where the calls of `kind` passed narrow_taps=True: the same fields, `split` and `fill`, `taps` the string
+    'pairs', equal to its own kind only."""
+    return type(name, (kind,), dict(__slots__=(), taps='pairs', __doc__='%s of a call that passed narrow_taps=\'pairs\' in place of narrow_taps=True: the same six fields, `taps` \'pairs\'.' % kind.__name__))
+
+
+NarrowPairsForm = _pairs_twin(NarrowTapsForm, 'NarrowPairsForm')
+NarrowSplitPairsForm = _pairs_twin(NarrowSplitTapsForm, 'NarrowSplitPairsForm')
+NarrowPairsFillForm = _pairs_twin(NarrowTapsFillForm, 'NarrowPairsFillForm')
+NarrowSplitPairsFillForm = _pairs_twin(NarrowSplitTapsFillForm, 'NarrowSplitPairsFillForm')
+_pairs_kind = {NarrowTapsForm: NarrowPairsForm, NarrowSplitTapsForm: NarrowSplitPairsForm, NarrowTapsFillForm: NarrowPairsFillForm, NarrowSplitTapsFillForm: NarrowSplitPairsFillForm}
 
 
 # ------------------------------------------------------------------------------------------------------------------

@@ -258,6 +258,10 @@ class KeyedModel(object):
         NARROW32_MAX images the eligible conv layers run convtaps_narrow_taps32_kernel in place of convtaps_narrow32_kernel (KN_MODIFIER_NARROW_TAPS32: the same resident
         slot lists and value rows, a step's activations as 16-float scalar segments, packed f32 multiplies and adds, each element rounded as before) -- the same bits;
         beyond NARROW32_MAX images it changes nothing.  Operators with coefficients have the 8-column-block forms only and keep convtaps_narrow32_kernel elsewhere.
+        `narrow_taps='pairs'` (opt-in, the same argument rule): beyond NARROW_MAX images exactly narrow_taps='packed', so one set of keywords serves any batch; up to
+        NARROW_MAX images the eligible conv layers of more than 64 output channels run convtaps_narrow_taps_pairs_kernel in place of convtaps_narrow_taps_kernel
+        (KN_MODIFIER_NARROW_TAPS_PAIRS: a lane holds two output channels as the halves of a register pair, a step's scalar half is paid once for 128 channels, packed
+        f32 multiplies and adds, each element rounded as before) -- the same bits.  Nothing is calibrated, recorded or screened for it.
         `narrow_fill=True` (opt-in; only together with narrow=True | 'mfma', ValueError otherwise; every width those keywords allow, in effect up to NARROW32_MAX images): the
         FILLED-IN conv layers that run the channel-lane kernels in the reference's order -- under doubly-stochastic keys the layers calibration sends to `exact`, and every
         layer of a key-net declared exact=True -- run convtaps_narrow_fill_kernel instead (KN_FLAG_NARROW_FILL: the pixel's slot records streamed by scalar loads, an input

@@ -67,6 +67,7 @@ images for the ladder.  The bars of the file are computed from the table.
 
     python tools/narrow_latency.py --taps [--out profiles/r15_narrow_taps.txt]
     python tools/narrow_latency.py --taps32 [--workload allconv] [--one-forward | --from-trace DIR/.../*_kernel_trace.csv]
+    python tools/narrow_latency.py --pairs [--one-forward | --from-trace DIR/.../*_kernel_trace.csv]
     python tools/narrow_latency.py --taps --one-forward          # for n in (1, 2, 4, 8) ONE narrow forward, then ONE with narrow_taps=True (for a kernel trace)
     python tools/narrow_latency.py --taps --from-trace DIR/.../*_kernel_trace.csv [--convs 13]       # no GPU: the conv launches of those forwards side by side
 
@@ -75,6 +76,11 @@ and 32 images (HIP events, median of 20 with min .. max, the two forms alternati
 narrow_rows=True, narrow_linear=True, narrow_taps=True; the two bars of the table: at 16 and 32 images the gain exceeds the two spreads added, and 16 images cost no more
 than twice the 8-image forward.  --workload allconv: 16 images (blocks of 8 columns).  --one-forward / --from-trace: as --taps, at 16 and 32 images, against
 convtaps_narrow32_kernel in the same trace.  Appends to profiles/r17_narrow_taps32.txt.
+--pairs: keyed VGG-16 under the default contract, whole forwards narrow=True, narrow_rows=True, narrow_linear=True, narrow_taps=True against the same with
+narrow_taps='pairs' at 1, 2, 4 and 8 images in one process (HIP events, median of 20 with min .. max, the two forms alternating, logits torch.equal before any time
+is printed), and whether the one-image forward meets 4 ms.  --one-forward / --from-trace: as --taps, the 13 conv launches of convtaps_narrow_taps_kernel against
+those of the narrow_taps='pairs' forward in one trace, three forwards of each form alternating per width: per launch the medians with min .. max, and WINS where
+the gain exceeds the two spreads added, else LOSES (the rule of narrow_taps_pairs_loses).  Appends to profiles/r18_narrow_taps_pairs.txt.
 --taps: keyed VGG-16 under the default contract, whole forwards narrow=True, narrow_rows=True, narrow_linear=True without and with narrow_taps=True at 1, 2, 4 and 8
 images in one process, the forms alternating, the logits torch.equal before any time is printed.
 
@@ -986,6 +992,97 @@ def taps_trace_table(args):
         f.write(text)
 
 
+PAIRS_FORM = dict(narrow=True, narrow_rows=True, narrow_linear=True)
+PAIRS_IMAGES = (1, 2, 4, 8)
+PAIRS_REPEATS = 3                                 # traced forwards per form and width: a launch's min .. max spread
+
+
+def pairs_table(args, knet, xc, desc):
+    """--pairs: see the module docstring."""
+    forms = (dict(narrow_taps=True), dict(narrow_taps='pairs'))
+    if args.one_forward:
+        for n in PAIRS_IMAGES:
+            x = xc[:n].t().contiguous().t()
+            for kw in forms:
+                knet.forward_linear(x, **PAIRS_FORM, **kw)      # (operators resident, kernels loaded)
+            torch.cuda.synchronize()
+        print('TRACE-FROM-HERE: for n in (1, 2, 4, 8) %d times one forward with narrow_taps=True, then one with narrow_taps=\'pairs\'' % PAIRS_REPEATS, flush=True)
+        for n in PAIRS_IMAGES:
+            x = xc[:n].t().contiguous().t()
+            for _ in range(PAIRS_REPEATS):
+                for kw in forms:
+                    knet.forward_linear(x, **PAIRS_FORM, **kw)
+                    torch.cuda.synchronize()
+        return
+    rows = []
+    for n in PAIRS_IMAGES:
+        x = xc[:n].t().contiguous().t()
+        (taps, pairs) = (knet.forward_linear(x, **PAIRS_FORM, **forms[0]), knet.forward_linear(x, **PAIRS_FORM, **forms[1]))
+        torch.cuda.synchronize()
+        assert torch.equal(taps, pairs), 'narrow_taps=\'pairs\' logits differ at %d image(s): max %g' % (n, float((taps - pairs).abs().max()))
+        t = ([], [])
+        for _ in range(2):                        # the forms alternating, two rounds of --forwards / 2 each
+            t[0].extend(timed(lambda: knet.forward_linear(x, **PAIRS_FORM, **forms[0]), args.forwards // 2, args.warmup))
+            t[1].extend(timed(lambda: knet.forward_linear(x, **PAIRS_FORM, **forms[1]), args.forwards // 2, args.warmup))
+        rows.append((n, [(statistics.median(v), min(v), max(v)) for v in t]))
+        print('n = %d done' % n, flush=True)
+    lines = ['', '== tools/narrow_latency.py --pairs --workload %s: %s' % (args.workload, desc),
+             '   %s, torch %s; HIP events, %d warm-up + median of %d forwards (min .. max), forms alternating; logits torch.equal: yes'
+             % (torch.cuda.get_device_name(0), torch.__version__, args.warmup, args.forwards),
+             '   %6s | %-34s | %-34s | %s' % ('images', '... narrow_taps=True [ms]', '... narrow_taps=\'pairs\' [ms]', 'ratio | gain [ms] against the two spreads added [ms]')]
+    for (n, t) in rows:
+        cell = ['%8.3f (%.3f .. %.3f)' % v for v in t]
+        (gain, spreads) = (t[0][0] - t[1][0], (t[0][2] - t[0][1]) + (t[1][2] - t[1][1]))
+        lines.append('   %6d | %-34s | %-34s | %.2fx | %.3f against %.3f' % (n, cell[0], cell[1], t[0][0] / t[1][0], gain, spreads))
+    if args.workload == 'vgg16':
+        one = rows[0][1][1][0]
+        lines.append('   one image with narrow_taps=\'pairs\': %.3f ms against the 4 ms target: %s' % (one, 'MET' if one <= 4.0 else 'MISSED'))
+    text = '\n'.join(lines) + '\n'
+    print(text)
+    with open(args.out or os.path.join(ROOT, 'profiles', 'r18_narrow_taps_pairs.txt'), 'a') as f:
+        f.write(text)
+
+
+def pairs_trace_table(args):
+    """--pairs --from-trace: the conv launches of the last 8 x PAIRS_REPEATS forwards of a `--pairs --one-forward` run under rocprofv3 --kernel-trace (device
+    timestamps): per launch the median of the repeats with min .. max on both sides, and the rule of narrow_taps_pairs_loses -- a (layer, width) stays on the new
+    kernel only where the gain exceeds the two spreads added."""
+    import csv
+    with open(args.from_trace, newline='') as f:
+        rows = [r for r in csv.DictReader(f) if 'convtaps_narrow' in r['Kernel_Name']]
+    rows.sort(key=lambda r: int(r['Start_Timestamp']))
+    (k, reps) = (args.convs, PAIRS_REPEATS)
+    assert len(rows) >= 8 * reps * k, 'the trace holds %d narrow conv launches, fewer than %d forwards of %d' % (len(rows), 8 * reps, k)
+    rows = rows[-8 * reps * k:]
+    us = lambda r: (int(r['End_Timestamp']) - int(r['Start_Timestamp'])) / 1e3
+    stat = lambda v: (statistics.median(v), min(v), max(v))
+    lines = ['', '== tools/narrow_latency.py --pairs --from-trace: the conv launches of %d forwards with narrow_taps=True and %d with narrow_taps=\'pairs\', alternating (rocprofv3 --kernel-trace, device timestamps)' % (reps, reps)]
+    for (i, n) in enumerate(PAIRS_IMAGES):
+        fw = [rows[(2 * reps * i + j) * k:(2 * reps * i + j + 1) * k] for j in range(2 * reps)]
+        (old, new) = (fw[0::2], fw[1::2])
+        assert all('taps_pairs' not in r['Kernel_Name'] for f_ in old for r in f_), 'the narrow_taps=True forward launched the channel-pair kernel'
+        lines.append('')
+        lines.append('   %d image(s) [us, median (min .. max) of %d]: conv launch | workgroups | convtaps_narrow_taps_kernel | with narrow_taps=\'pairs\' | ratio | gain against the two spreads added | kernel of the pairs forward' % (n, reps))
+        (sa, sb) = (0.0, 0.0)
+        for j in range(k):
+            (a, b) = (stat([us(f_[j]) for f_ in old]), stat([us(f_[j]) for f_ in new]))
+            r = new[0][j]
+            name = r['Kernel_Name']
+            mine = 'taps_pairs' in name
+            form = name[name.index('<'):name.index('>') + 1] if ('<' in name and '>' in name) else ''
+            (gain, spreads) = (a[0] - b[0], (a[2] - a[1]) + (b[2] - b[1]))
+            lines.append('     %2d | %6d | %8.1f (%.1f .. %.1f) | %8.1f (%.1f .. %.1f) | %5.2fx | %7.1f against %6.1f%s | %s' % (
+                (j + 1, int(r.get('Grid_Size_X') or 0) // max(1, int(r.get('Workgroup_Size_X') or 1))) + a + b + (a[0] / b[0], gain, spreads, ('' if not mine else ': WINS' if gain > spreads else ': LOSES'),
+                                                                                                                    ('two channels per lane <NT, NV, FULL, COEF> = ' if mine else 'convtaps_narrow_taps_kernel <NT, P, NV, FULL, COEF> = ') + form)))
+            sa += a[0]
+            sb += b[0]
+        lines.append('     sum of the %d conv launches (medians): %9.1f | %9.1f | %5.2fx' % (k, sa, sb, sa / sb))
+    text = '\n'.join(lines) + '\n'
+    print(text)
+    with open(args.out or os.path.join(ROOT, 'profiles', 'r18_narrow_taps_pairs.txt'), 'a') as f:
+        f.write(text)
+
+
 TAPS32_FORM = dict(narrow=True, narrow32=True, narrow_linear=True)
 TAPS32_IMAGES = (9, 12, 16, 24, 32)
 TAPS32_TRACED = (16, 32)
@@ -1121,6 +1218,7 @@ def main():
     ap.add_argument('--fill', action='store_true', help='filled-in synthetic operators of the VGG-16 conv shapes under exact=True: narrow=True without and with narrow_fill=True, and the padded 128-column call, at 1, 8, 16, 32 images (profiles/r16_narrow_fill.txt)')
     ap.add_argument('--taps', action='store_true', help='whole forwards with and without narrow_taps=True at 1, 2, 4, 8 images (profiles/r15_narrow_taps.txt)')
     ap.add_argument('--taps32', action='store_true', help="whole forwards narrow32=True without and with narrow_taps='packed' at 9, 12, 16, 24, 32 images, and the 8-image narrow_taps=True forward (profiles/r17_narrow_taps32.txt)")
+    ap.add_argument('--pairs', action='store_true', help="whole forwards with narrow_taps=True against narrow_taps='pairs' at 1, 2, 4, 8 images (profiles/r18_narrow_taps_pairs.txt)")
     ap.add_argument('--layers', type=lambda v: tuple(v.split(',')), default=(), help='with --split: only these layer shapes (conv1_1, conv1_2, conv2_1, ..., conv5_x)')
     ap.add_argument('--fused-calls', type=int, default=3, help='with --split: timed calls of the fused channel-lane launch (hundreds of ms each on the larger layers)')
     args = ap.parse_args()
@@ -1130,6 +1228,8 @@ def main():
         return fill_trace_table(args) if args.from_trace else fill_table(args)
     if args.from_trace and args.taps:
         return taps_trace_table(args)
+    if args.from_trace and args.pairs:
+        return pairs_trace_table(args)
     if args.from_trace and args.taps32:
         return taps32_trace_table(args)
     if args.from_trace:
@@ -1147,6 +1247,8 @@ def main():
     print('keyed %s in %.0f s' % (desc, time.time() - t0), flush=True)
     if args.taps:
         return taps_table(args, knet, xc, desc)
+    if args.pairs:
+        return pairs_table(args, knet, xc, desc)
     if args.taps32:
         return taps32_table(args, knet, xc, desc)
     if args.mfma64:
