@@ -398,6 +398,19 @@ int kn_relu(float* y_dev, int64_t rows, int64_t ld, int64_t n_vecs, void* stream
  * x_dev [n, d] row-major images  ->  out_dev [d+1, n] feature-major with the ones row appended. */
 int kn_affine_to_linear(const float* x_dev, int64_t n, int64_t d, float* out_dev, int64_t ldo, void* stream);
 
+/* The sensor's ingest of raw frames (keynet/system.py:183-201, 250-255 with keynet/torch.py:65-68): the reference's sensor loads an image as [0, 255] values, homogenises
+ * it and hands it to the image key, on the host; this is the load and the homogenisation for n uint8 frames that are already on the device, in one launch.
+ *   img_dev   n frames of c * h * w bytes; layout 0: img[b][ch][y][x] (NCHW), layout 1: img[b][y][x][ch] (NHWC: a camera's or PIL's order)
+ *   out_dev   the feature-major block, D = c * h * w:  out[((ch * h + y) * w + x) * ldo + b] = (float)img[b][..]   for b < n
+ *                                                      out[D * ldo + b] = 1.0f                                  for b < n   (the ones row)
+ *             every row, the ones row included, is +0.0f for n <= b < n_cols (zero images: the padding of a batch to whole tiles, written in the same launch);
+ *             columns n_cols <= b < ldo are not touched.
+ * uint8 -> float32 is exact: the block is bit-equal to kn_affine_to_linear on the frames converted to float32 NCHW, followed by that padding.  1 <= n <= n_cols <= ldo and
+ * c, h, w >= 1 (KN_ERR_SHAPE otherwise; nothing is launched); every address is formed in 64 bits.  Tiled through LDS (256 frame positions x 64 images): contiguous bytes
+ * along a frame on the way in, contiguous floats along the batch on the way out -- 16-byte stores where ldo and out_dev are multiples of four floats, scalar stores otherwise;
+ * the (y, x, ch) -> (ch, y, x) permutation of layout 1 is index arithmetic of the same pass.  An added entry point: KN_ABI_VERSION stays (the rule below). */
+int kn_u8_to_linear(const uint8_t* img_dev, int64_t n, int64_t c, int64_t h, int64_t w, int layout, float* out_dev, int64_t ldo, int64_t n_cols, void* stream);
+
 /* keynet.torch.linear_to_affine (keynet/torch.py:71-77): y_dev [d+1, n] feature-major -> out_dev [n, d] row-major;
  * *maxdev_dev (device float, may be NULL) receives max_b |y[d, b] - 1| so the host can raise ValueError when > 1e-3. */
 int kn_linear_to_affine(const float* y_dev, int64_t ldy, int64_t n, int64_t d, float* out_dev, float* maxdev_dev, void* stream);

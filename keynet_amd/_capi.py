@@ -40,7 +40,7 @@ KN_ABI_VERSION = 5
 # every symbol include/keynet_hip.h declares (tests/test_capi.py checks the header against this list)
 SYMBOLS = ['kn_abi_version', 'kn_last_error', 'kn_device_info', 'kn_csr_create', 'kn_csr_create_f64', 'kn_dtype_bits', 'kn_export_csr_f64', 'kn_spmm_f64', 'kn_tiled_create', 'kn_conv2dtiled_create',
            'kn_convtaps_create', 'kn_convtaps_drop_zero_entries', 'kn_dense_create', 'kn_chain_create', 'kn_destroy', 'kn_nnz', 'kn_nnz_expanded', 'kn_shape', 'kn_export_csr', 'kn_spmm', 'kn_spmm_planes', 'kn_spmm_screen', 'kn_absmax', 'kn_reserve_workspace', 'kn_release_side_tables', 'kn_spmm_plan', 'kn_relu',
-           'kn_affine_to_linear', 'kn_linear_to_affine', 'kn_planes_to_columns', 'kn_columns_to_planes']
+           'kn_affine_to_linear', 'kn_u8_to_linear', 'kn_linear_to_affine', 'kn_planes_to_columns', 'kn_columns_to_planes']
 
 
 class KeynetHipError(RuntimeError):
@@ -96,6 +96,7 @@ def lib():
         L.kn_reserve_workspace.argtypes = [p, i64, p]
         L.kn_relu.argtypes = [p, i64, i64, i64, p]
         L.kn_affine_to_linear.argtypes = [p, i64, i64, p, i64, p]
+        L.kn_u8_to_linear.argtypes = [p, i64, i64, i64, i64, ci, p, i64, i64, p]
         L.kn_linear_to_affine.argtypes = [p, i64, i64, i64, p, p, p]
         L.kn_planes_to_columns.argtypes = [p, i64, i64, i64, i64, i64, p, i64, p]
         L.kn_columns_to_planes.argtypes = [p, i64, i64, i64, i64, p, i64, i64, p]
@@ -299,6 +300,11 @@ def relu(y_ptr, rows, ld, n_vecs, stream):
 
 def affine_to_linear(x_ptr, n, d, out_ptr, ldo, stream):
     check(lib().kn_affine_to_linear(x_ptr, int(n), int(d), out_ptr, int(ldo), stream))
+
+
+def u8_to_linear(img_ptr, n, c, h, w, layout, out_ptr, ldo, n_cols, stream):
+    """kn_u8_to_linear: n uint8 frames (layout 0: NCHW, 1: NHWC) -> the feature-major [c * h * w + 1, n_cols] block at ldo, ones row appended, columns n .. n_cols - 1 zero images."""
+    check(lib().kn_u8_to_linear(img_ptr, int(n), int(c), int(h), int(w), int(layout), out_ptr, int(ldo), int(n_cols), stream))
 
 
 def linear_to_affine(y_ptr, ldy, n, d, out_ptr, maxdev_ptr, stream):

@@ -1123,6 +1123,18 @@ int kn_affine_to_linear(const float* x_dev, int64_t n, int64_t d, float* out_dev
     });
 }
 
+int kn_u8_to_linear(const uint8_t* img_dev, int64_t n, int64_t c, int64_t h, int64_t w, int layout, float* out_dev, int64_t ldo, int64_t n_cols, void* stream) {
+    return guarded([&]() -> int {
+    KN_HOST_ONLY_GUARD();
+    KN_REQUIRE(n >= 1 && n <= n_cols && n_cols <= ldo, KN_ERR_SHAPE, "1 <= n <= n_cols <= ldo");
+    KN_REQUIRE(c >= 1 && h >= 1 && w >= 1, KN_ERR_SHAPE, "empty frame");
+    KN_REQUIRE(c <= INT32_MAX && h <= INT32_MAX && w <= INT32_MAX && h * w <= INT64_MAX / c, KN_ERR_INVALID, "frame size out of range");
+    KN_REQUIRE(layout == 0 || layout == 1, KN_ERR_INVALID, "layout is 0 (NCHW) or 1 (NHWC)");
+    KN_REQUIRE(img_dev && out_dev, KN_ERR_INVALID, "NULL pointer");
+    return u8_to_linear(img_dev, n, c, h, w, layout, out_dev, ldo, n_cols, reinterpret_cast<hipStream_t>(stream));
+    });
+}
+
 int kn_linear_to_affine(const float* y_dev, int64_t ldy, int64_t n, int64_t d, float* out_dev, float* maxdev_dev, void* stream) {
     return guarded([&]() -> int {
     KN_HOST_ONLY_GUARD();

@@ -2,6 +2,7 @@
 //   relu_inplace        nn.ReLU over [rows, n_vecs] incl. the homogeneous row (keynet/system.py:92) when it cannot be fused
 //   affine_to_linear    keynet/torch.py:65-68 + the x.t() of keynet/layer.py:92: [n, d] images -> [d+1, n] feature-major
 //   linear_to_affine    keynet/torch.py:71-77: [d+1, n] -> [n, d], plus max |last row - 1| for the host-side ValueError
+//   u8_to_linear        the sensor's ingest of raw frames (keynet/system.py:183-201 + keynet/torch.py:65-68): n uint8 frames, NCHW or NHWC -> [d+1, n_cols] feature-major, padded
 //   planes_to_columns / columns_to_planes   the two layout changes around the spatial CSR of the narrow split route (no reference counterpart)
 // Transposes go through a padded 64x65 LDS tile so both the global read and the global write are coalesced.
 #include "kn_internal.h"
@@ -101,6 +102,116 @@ int affine_to_linear(const float* x, int64_t n, int64_t d, float* out, int64_t l
         hipLaunchKernelGGL(transpose_kernel, grid, dim3(256), 0, s, x, n, d, d, out, ldo);
     }
     hipLaunchKernelGGL(fill_row_kernel, dim3((unsigned)std::min<int64_t>((n + 255) / 256, 1024)), dim3(256), 0, s, out + d * ldo, n, 1.0f);
+    KN_HIP(hipGetLastError());
+    return KN_OK;
+}
+
+// kn_u8_to_linear: n uint8 frames of D = c * h * w bytes each -> the feature-major block [D + 1, n_cols] (ones row appended, columns n .. n_cols - 1 zero images).
+// The byte at position p of a frame belongs to row r(p): p itself for NCHW; for NHWC p = (y * w + x) * c + ch and r = ch * (h * w) + (y * w + x).
+// One workgroup moves a tile of U8_POS = 256 frame positions x U8_COLS = 64 images through LDS, kept as BYTES (16.6 KB, nine workgroups on a CU):
+//   in    a wavefront reads 256 contiguous bytes of one frame per instruction -- one dword per lane where the frames are dword-aligned (D % 4 == 0 and the
+//         base), one byte per lane otherwise -- and stores them at tile[image][position].  An image's row is 260 bytes = 65 dwords, so image i starts in bank
+//         i (mod 32): the dword stores of a wavefront fall on consecutive banks, conflict-free.
+//   out   lane (g = lane / 4, q = lane % 4) owns images 4g .. 4g + 3 at position 4 * (pass, wave) + q: four byte reads from dwords (4g + k) * 65 + position / 4
+//         -- in a half-wave (g = 0 .. 7) 8 distinct banks per k, the four q of one g on ONE dword (a broadcast) -- converted (v_cvt_f32_ubyte: exact) and stored as one
+//         float4, 16 lanes x 16 bytes = 256 contiguous bytes of an output row per wavefront.  The row permutation of NHWC is this side's index arithmetic: the
+//         row changes, the 256-byte run along the batch does not.  V4 = false (ldo or the base not a multiple of four floats): four scalar stores; a quad that
+//         crosses n_cols stores scalars up to it either way, so columns n_cols .. ldo - 1 are never touched.
+// Position tile 0 of every column tile also writes the ones row.  No arithmetic but the conversion; every address is formed in 64 bits.
+constexpr int U8_POS = 256, U8_COLS = 64, U8_STRIDE = U8_POS + 4;
+
+template <bool V4>
+__device__ __forceinline__ void u8_store_quad(float* __restrict__ row, int64_t b, int64_t n_cols, float4 v) {
+    if (V4 && b + 4 <= n_cols) {
+        *reinterpret_cast<float4*>(row + b) = v;
+    } else {
+        if (b < n_cols) row[b] = v.x;
+        if (b + 1 < n_cols) row[b + 1] = v.y;
+        if (b + 2 < n_cols) row[b + 2] = v.z;
+        if (b + 3 < n_cols) row[b + 3] = v.w;
+    }
+}
+
+template <bool NHWC, bool L4, bool V4>
+__global__ __launch_bounds__(256) void u8_to_linear_kernel(const uint8_t* __restrict__ img, int64_t n, int64_t D, int c, int64_t hw, float* __restrict__ out, int64_t ldo,
+                                                           int64_t n_cols) {
+    __shared__ __attribute__((aligned(16))) uint8_t tile[U8_COLS * U8_STRIDE];
+    const int64_t p0 = (int64_t)blockIdx.x * U8_POS;
+    const int64_t b0 = (int64_t)blockIdx.y * U8_COLS;
+    const int lane = (int)threadIdx.x & 63, wave = (int)threadIdx.x >> 6;
+    const int cols = (n_cols - b0 < U8_COLS) ? (int)(n_cols - b0) : U8_COLS;        // columns of this tile that exist: >= 1
+    // in: images beyond n (the pad columns) are zero bytes
+    if (L4) {
+        const int64_t p = p0 + 4 * lane;
+        for (int i = wave; i < cols; i += 4) {
+            uint32_t v = 0;
+            if (b0 + i < n && p < D) v = *reinterpret_cast<const uint32_t*>(img + (b0 + i) * D + p);      // D % 4 == 0: a dword is inside the frame or outside it
+            *reinterpret_cast<uint32_t*>(tile + i * U8_STRIDE + 4 * lane) = v;
+        }
+    } else {
+        const int64_t p = p0 + (int)threadIdx.x;
+        for (int i = 0; i < cols; i++) {
+            uint8_t v = 0;
+            if (b0 + i < n && p < D) v = img[(b0 + i) * D + p];
+            tile[i * U8_STRIDE + (int)threadIdx.x] = v;
+        }
+    }
+    __syncthreads();
+    // out
+    const int g = lane >> 2, q = lane & 3;
+    const int64_t b = b0 + 4 * g;
+    if (4 * g < cols) {
+        for (int pass = 0; pass < U8_POS / 16; pass++) {
+            const int pl = pass * 16 + wave * 4 + q;
+            const int64_t p = p0 + pl;
+            if (p >= D) break;                              // positions ascend with the pass
+            int64_t r = p;
+            if (NHWC) {
+                const int64_t pix = p / c;
+                r = (p - pix * c) * hw + pix;
+            }
+            const uint8_t* t = tile + (4 * g) * U8_STRIDE + pl;
+            float4 v;
+            v.x = (float)t[0];
+            v.y = (4 * g + 1 < cols) ? (float)t[U8_STRIDE] : 0.0f;
+            v.z = (4 * g + 2 < cols) ? (float)t[2 * U8_STRIDE] : 0.0f;
+            v.w = (4 * g + 3 < cols) ? (float)t[3 * U8_STRIDE] : 0.0f;
+            u8_store_quad<V4>(out + r * ldo, b, n_cols, v);
+        }
+    }
+    if (blockIdx.x == 0 && (int)threadIdx.x < 16 && 4 * (int)threadIdx.x < cols) {       // the ones row: 1.0 under an image, 0.0 under a pad column
+        const int64_t bq = b0 + 4 * (int)threadIdx.x;
+        float4 v;
+        v.x = (bq < n) ? 1.0f : 0.0f;
+        v.y = (bq + 1 < n) ? 1.0f : 0.0f;
+        v.z = (bq + 2 < n) ? 1.0f : 0.0f;
+        v.w = (bq + 3 < n) ? 1.0f : 0.0f;
+        u8_store_quad<V4>(out + D * ldo, bq, n_cols, v);
+    }
+}
+
+int u8_to_linear(const uint8_t* img, int64_t n, int64_t c, int64_t h, int64_t w, int layout, float* out, int64_t ldo, int64_t n_cols, hipStream_t s) {
+    const int64_t D = c * h * w;
+    const int64_t ptiles = (D + U8_POS - 1) / U8_POS, ctiles = (n_cols + U8_COLS - 1) / U8_COLS;
+    if (ptiles > INT32_MAX || ctiles > 65535) return fail(KN_ERR_UNSUPPORTED, "kn_u8_to_linear: more tiles than one launch grid holds");
+    const bool nhwc = layout == 1 && c > 1;                // one channel: the two layouts are the same bytes
+    const bool l4 = D % 4 == 0 && ((uintptr_t)img) % 4 == 0;
+    const bool v4 = ldo % 4 == 0 && ((uintptr_t)out) % 16 == 0;
+    const dim3 grid((unsigned)ptiles, (unsigned)ctiles);
+#define KN_U8_LAUNCH(NHWC, L4, V4) \
+    KN_LAUNCH("u8_to_linear_kernel<" #NHWC "," #L4 "," #V4 ">", (u8_to_linear_kernel<NHWC, L4, V4>), grid, dim3(256), 0, s, img, n, D, (int)c, h * w, out, ldo, n_cols)
+    if (nhwc) {
+        if (l4 && v4) KN_U8_LAUNCH(true, true, true);
+        else if (l4) KN_U8_LAUNCH(true, true, false);
+        else if (v4) KN_U8_LAUNCH(true, false, true);
+        else KN_U8_LAUNCH(true, false, false);
+    } else {
+        if (l4 && v4) KN_U8_LAUNCH(false, true, true);
+        else if (l4) KN_U8_LAUNCH(false, true, false);
+        else if (v4) KN_U8_LAUNCH(false, false, true);
+        else KN_U8_LAUNCH(false, false, false);
+    }
+#undef KN_U8_LAUNCH
     KN_HIP(hipGetLastError());
     return KN_OK;
 }

@@ -839,6 +839,21 @@ class KeyedSensor(klayer.KeyedLayer):
             self._tensor = self.forward(ktorch.affine_to_linear(self._tensor))
         return self
 
+    def check_frames(self, frames, layout='NHWC', dtype=torch.uint8):
+        """n of a batch of frames that has this sensor's shape ([n, H, W, C] under 'NHWC', [n, C, H, W] under 'NCHW'); ValueError otherwise.  No GPU call."""
+        (n, chw) = ktorch.frame_shape(frames, layout, dtype)
+        if chw != tuple(self._inshape[1:]):
+            raise ValueError('frames of shape (C, H, W) = %s do not fit the sensor %s' % (str(chw), str(tuple(self._inshape[1:]))))
+        return n
+
+    def encrypt_frames(self, frames, layout='NHWC', pad_to=1):
+        """uint8 frames on the device ([n, H, W, C], or [n, C, H, W] with layout='NCHW') -> the encrypted block [n_cols, C*H*W+1] on the device: the load, homogenise,
+        encrypt of keynet/system.py:183-201, 250-255 for a batch of raw camera frames, as kn_u8_to_linear (ktorch.frames_to_linear) and this sensor's own keyed product.
+        Its first n rows equal fromtensor(frames as float NCHW).encrypt().astensor() bit for bit; rows n .. n_cols - 1 (n_cols = n rounded up to `pad_to`) stay zero
+        images.  Stateless: the loaded tensor of this sensor is neither read nor changed.  ValueError for frames that are not the sensor's shape, before any GPU call."""
+        self.check_frames(frames, layout)
+        return self.forward(ktorch.frames_to_linear(frames, layout=layout, pad_to=pad_to))
+
     def decrypt(self):
         assert self.isloaded(), 'Load image first'
         if self.isencrypted():

@@ -31,6 +31,45 @@ def affine_to_linear(x):
     return torch.cat((x.reshape(N, D), torch.ones(N, 1, dtype=x.dtype)), dim=1)
 
 
+LAYOUTS = ('NCHW', 'NHWC')      # the `layout` strings of frames_to_linear, in the order of kn_u8_to_linear's codes
+
+
+def frame_shape(frames, layout='NHWC', dtype=torch.uint8):
+    """(n, (C, H, W)) of a batch of frames [n, H, W, C] (layout 'NHWC') or [n, C, H, W] ('NCHW'); ValueError for another layout string, rank or dtype, or an empty batch.
+    Touches no GPU (what frames_to_linear, KeyedSensor.encrypt_frames and StreamedForward check their arguments with)."""
+    if layout not in LAYOUTS:
+        raise ValueError('invalid layout "%s": one of %s' % (str(layout), ', '.join(LAYOUTS)))
+    if not isinstance(frames, torch.Tensor):
+        raise ValueError('frames must be a torch tensor, not %s' % type(frames).__name__)
+    if frames.dtype != dtype:
+        raise ValueError('frames must be %s, not %s' % (dtype, frames.dtype))
+    if frames.dim() != 4:
+        raise ValueError('frames must be [n, %s], not a tensor of rank %d' % ('H, W, C' if layout == 'NHWC' else 'C, H, W', frames.dim()))
+    if min(frames.shape) < 1:
+        raise ValueError('empty batch of frames: shape %s' % str(tuple(frames.shape)))
+    (n, a, b, c) = (int(v) for v in frames.shape)
+    return (n, (c, a, b) if layout == 'NHWC' else (a, b, c))
+
+
+def frames_to_linear(frames, layout='NHWC', pad_to=1):
+    """uint8 frames on the device, [n, H, W, C] (layout 'NHWC': a camera's order) or [n, C, H, W] ('NCHW') -> [n_cols, C*H*W+1] float32 with a trailing ones
+    column, n_cols = n rounded up to a multiple of `pad_to`; the rows beyond n are zero images (all zero, the ones column included: what KeyedModel._prepare
+    pads a batch with).  Like the device branch of affine_to_linear the result is the transposed VIEW of a fresh feature-major [D+1, n_cols] block; its first n
+    rows are bit-equal to affine_to_linear(frames.permute(0, 3, 1, 2).float()).  One launch of kn_u8_to_linear on the current stream.  ValueError for a wrong
+    dtype, rank or layout string, before any GPU call."""
+    (n, (C, H, W)) = frame_shape(frames, layout)
+    if int(pad_to) < 1:
+        raise ValueError('pad_to must be a positive number of images, not %s' % str(pad_to))
+    if not frames.is_cuda:
+        raise ValueError('frames_to_linear takes frames that are on the device (StreamedForward brings host frames there)')
+    n_cols = -(-n // int(pad_to)) * int(pad_to)
+    fc = frames.contiguous()
+    out = torch.empty((C * H * W + 1, n_cols), dtype=torch.float32, device=frames.device)
+    with torch.cuda.device(frames.device):
+        _capi.u8_to_linear(fc.data_ptr(), n, C, H, W, LAYOUTS.index(layout), out.data_ptr(), n_cols, n_cols, _stream_ptr())
+    return out.t()
+
+
 def linear_to_affine(x, outshape=None):
     """Nx(K+1) -> NxK, checking that the homogeneous column is 1 within 1e-3 (ValueError otherwise), then reshaping to
     `outshape` (keynet/torch.py:71-77)."""
