@@ -7,13 +7,15 @@ fuzzers re-runs one case of a longer run exactly as that run draws it.
 The kernels behind the flags take their forms by rules on the operator and the width (narrow_choice, kn_conv.hip): a form such as P = 2 or the two-launch column split
 needs an operator class, a width range and a set of flag bits at once, and independent draws would meet it a few times in a thousand cases.  So a case first draws
 its class (evenly, the wide one in ten: conv_plan), then an AIM among those of the class -- a width range and the flag bits a form needs -- and everything the
-aim leaves open at random.  'free' aims leave everything open.  conv_props / conv_classes / csr_classes compute the HOST-VISIBLE classes of an operator from W._taps and the CSR alone: the
+aim leaves open at random.  'free' aims leave everything open.  About one conv case in four (never a dropped-zero one, whose CSR is given) is then turned into its
+exact-sum twin (exact_sum_twin: same shape, flags and window, integer values and activations whose sums are exact in every order).  conv_props / conv_classes / csr_classes compute the HOST-VISIBLE classes of an operator from W._taps and the CSR alone: the
 create-time facts the library decides eligibility by (kn_internal.h: narrow_taps_ok, narrow_fill_ok, convtaps_pt_eligibility), restated, never read from a plan."""
 import numpy as np
 import scipy.sparse
 import torch
 from torch import nn
 
+import exact_sum
 import oracle
 from keynet_amd import _capi
 from keynet_amd import sparse as ksp
@@ -231,7 +233,7 @@ def conv_plan(n_cases, seed):
 
 def conv_cases(n_cases, seed, only=None):
     """Yields one dict per case: `skipped` (a reason) or the whole case -- cls, aim, W, M (None: the sorted expansion), props, n, flags, ld, start, X [cols, 128] (the
-    case's batch is its first n columns; non-finite values already in), nonfinite, screen.  Class and aim come from conv_plan, everything else from a stream of the
+    case's batch is its first n columns; non-finite values already in), nonfinite, screen, twin (an exact-sum twin: exact_sum_twin).  Class and aim come from conv_plan, everything else from a stream of the
     case's own (seed, case): `only` yields that one case of the run, exactly as the whole run draws it."""
     for (case, (cls, (aim, widths, regime, on, off))) in enumerate(conv_plan(n_cases, seed)):
         if only is not None and case != only:
@@ -251,13 +253,31 @@ def conv_cases(n_cases, seed, only=None):
         if _taps_of(W)['lastcol'] is not None:
             X[-1] = 1.0
         screen = bool(rng.rand() < 0.25)
+        twin = bool(cls != 'dropped' and rng.rand() < 0.25)              # (the last draw of the case's stream: everything above is what it was before there were twins)
+        if twin:
+            (W, X, nonfinite) = (exact_sum_twin(W, X.shape[1], case) + ([],))
         p = conv_props(W)
-        d = dict(case=case, cls=cls, aim=aim, props=p, n=n, flags=flags, ld=ld, start=start, nonfinite=nonfinite, screen=screen, skipped=None)
+        d = dict(case=case, cls=cls, aim=aim, props=p, n=n, flags=flags, ld=ld, start=start, nonfinite=nonfinite, screen=screen, skipped=None, twin=twin)
         if p['Cout'] * p['Cin'] * len(_taps_of(W)['ent_out']) > ORACLE_BUDGET:
             d['skipped'] = 'oracle budget'
         else:
             d.update(W=W, M=M, X=X)
         yield d
+
+
+def exact_sum_twin(W, n_cols, case):
+    """(W, X [cols, n_cols]): the exact-sum twin of a conv case (tests/exact_sum.py) -- the operator's shape and entry lists as drawn, integer taps, coefficients 1 | 2, integer
+    biases and activations, the split of the bit budget walking with the case number; sum |tap| |coef| |x| over the terms of every output element <= 2^24, asserted.  On such a
+    case every order of the sum gives the oracle's bits, so the fuzzer holds a matrix-core plan to bits_equal instead of its bound.  No non-finite activations."""
+    split = exact_sum.SPLITS[case % 3]
+    t = W._taps
+    per_row = exact_sum.longest_row(W)
+    (taps, coef, lastcol) = exact_sum.conv_values(split, t['taps'], t['ent_coef'], t['lastcol'], per_row, seed=case)
+    W2 = ksp.Conv2dTiledMatrix.fromtaps(W._inshape, W._outshape, taps, t['ent_out'], t['ent_in'], t['ent_tap'], coef, lastcol)
+    (p_bits, _) = exact_sum.split_bits(exact_sum.budget(per_row + (1 if lastcol is not None else 0)), split)
+    X = exact_sum.activations(W2.shape[1], n_cols, W2._taps['lastcol'] is not None, p_bits, seed=case + 1, cin=int(W2._inshape[0]))
+    exact_sum.condition_factored(W2, X, 'exact-sum twin of conv case %d' % case)
+    return (W2, X)
 
 
 def conv_reference(d):
@@ -287,7 +307,7 @@ def oracle_product(M, X, relu=False):
 
 def describe(d):
     """One line that pins a case: the determinism check compares these."""
-    keys = [k for k in ('case', 'cls', 'aim', 'kind', 'n', 'flags', 'ld', 'start', 'nonfinite', 'screen', 'skipped', 'relu', 'f64', 'big', 'family', 'tile', 'inshape', 'names', 'keywords', 'float_keys') if k in d]
+    keys = [k for k in ('case', 'cls', 'aim', 'twin', 'kind', 'n', 'flags', 'ld', 'start', 'nonfinite', 'screen', 'skipped', 'relu', 'f64', 'big', 'family', 'tile', 'inshape', 'names', 'keywords', 'float_keys') if k in d]
     s = ' '.join('%s=%s' % (k, d[k]) for k in keys)
     if d.get('props'):
         s += ' ' + ' '.join('%s=%s' % kv for kv in sorted(d['props'].items()))

@@ -97,25 +97,31 @@ _ops = {}
 _refs = {}
 
 
+def _factored(name, values=None):
+    """The arguments of kn_convtaps_create for the operator `name` (host arrays: tests/test_exact_sum_host.py expands them without a device)."""
+    (cin, cout, hw, per_pixel, coef, dup) = OPS[name]
+    rng = np.random.RandomState(len(name) + 7 * cin)
+    HW = hw * hw
+    eo = np.repeat(np.arange(HW), per_pixel)
+    k = np.tile(np.arange(per_pixel), HW)
+    ei = (eo % 3) if dup else (eo + 7 * k) % HW
+    taps = rng.randn(9, cout, cin).astype(np.float32)
+    ec = (rng.rand(len(eo)).astype(np.float32) + 0.5) if coef else None
+    lc = np.concatenate((rng.randn(cout * HW), [1.0])).astype(np.float32)
+    (taps, ec, lc) = value_classes.conv_values(values, taps, ec, lc, per_pixel * cin)
+    return ((cin, hw, hw), (cout, hw, hw), taps, eo.astype(np.int32), ei.astype(np.int32), (k % 9).astype(np.int32), ec, lc)
+
+
 def _operator(name, switch, values=None):
     """(handle, (shape, indptr, indices, data) of its expansion), created once per (operator, switch): the environment is read when a handle is created.
     `values`: a variant of value_classes.conv_values -- the same operator with its values scaled by powers of two (tests/test_value_classes_gpu.py)."""
     if (name, switch, values) not in _ops:
-        (cin, cout, hw, per_pixel, coef, dup) = OPS[name]
-        rng = np.random.RandomState(len(name) + 7 * cin)
-        HW = hw * hw
-        eo = np.repeat(np.arange(HW), per_pixel)
-        k = np.tile(np.arange(per_pixel), HW)
-        ei = (eo % 3) if dup else (eo + 7 * k) % HW
-        taps = rng.randn(9, cout, cin).astype(np.float32)
-        ec = (rng.rand(len(eo)).astype(np.float32) + 0.5) if coef else None
-        lc = np.concatenate((rng.randn(cout * HW), [1.0])).astype(np.float32)
-        (taps, ec, lc) = value_classes.conv_values(values, taps, ec, lc, per_pixel * cin)
+        (inshape, outshape, taps, eo, ei, et, ec, lc) = _factored(name, values)
         if switch:
             os.environ[switch] = '1'
         try:
             with torch.cuda.device(dev()):
-                op = _capi.Operator.convtaps((cin, hw, hw), (cout, hw, hw), taps, eo.astype(np.int32), ei.astype(np.int32), (k % 9).astype(np.int32), ec, lc)
+                op = _capi.Operator.convtaps(inshape, outshape, taps, eo, ei, et, ec, lc)
         finally:
             if switch:
                 del os.environ[switch]

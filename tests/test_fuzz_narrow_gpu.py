@@ -37,6 +37,7 @@ CONV_REACH = ['convtaps_narrow_kernel', 'convtaps_narrow32_kernel', 'convtaps_ex
               TAPS_KERNEL + ' P=1', TAPS_KERNEL + ' P=2', TAPS_KERNEL + ' 16 value rows', TAPS_KERNEL + ' coef', TAPS_KERNEL + ' columns 4 ..',
               TAPS32_KERNEL + ' NV=8', TAPS32_KERNEL + ' NV=16', TAPS32_KERNEL + ' NV=32', TAPS32_KERNEL + ' masked',
               FILL_KERNEL + ' <= 8 columns', FILL_KERNEL + ' column blocks']
+TWIN_REACH = 'exact-sum twin on a matrix-core plan'
 CSR_REACH = ['csr_narrow_kernel', 'csr_stream_group_kernel']
 MODEL_REACH = ['tap-resident kernel', 'csr_narrow_kernel', 'csr_stream_group_kernel', 'convtaps_exact_pipe64_kernel', NMFMA_KERNEL]
 
@@ -100,7 +101,8 @@ def fuzz_convtaps_narrow(n_cases, seed=CONV_SEED, verbose=False, only=None):
     with non-finite activations and with the screen slot.  A call whose plan names no matrix-core kernel: the window equals the oracle on the operator's sorted
     canonical CSR bit for bit, NaN positions included, and its int32 view equals that of the first columns of the KN_FLAG_EXACT product at 128 columns where that is
     no NaN (the sign of zero).  A matrix-core call (finite X): inside fuzz_convtaps' bound element-wise, the same bits twice, per image the bits of the call on
-    that image's chunk of at most 8 columns (9 .. 32 columns), the bits of the plain matrix-core call on the batch zero-padded to 128 columns (the 64-column tile).
+    that image's chunk of at most 8 columns (9 .. 32 columns), the bits of the plain matrix-core call on the batch zero-padded to 128 columns (the 64-column tile);
+    on an exact-sum twin (about one case in four, fuzz_narrow_cases.exact_sum_twin) the oracle's bits in place of the bound.
     Every call: the sentinel outside the window, the slot == max |Y|.  A modifier that the operator's host-visible class or the width rules out, NARROW_ROWS |
     NARROW_LINEAR, and KN_FLAG_NARROW32 alone: the plan and the bits of the call without it.  Returns dict(cases, checked, skipped, bad); .reach counts the forms."""
     dev = torch.device('cuda:0')
@@ -146,8 +148,11 @@ def fuzz_convtaps_narrow(n_cases, seed=CONV_SEED, verbose=False, only=None):
             if not bool(torch.equal(win.contiguous().view(torch.int32)[keep], y128.contiguous().view(torch.int32)[keep])):
                 bad(d, 'int32 view differs from the 128-column KN_FLAG_EXACT product', plan)
         elif finite:
-            S = fc.conv_abs_sum(d)
-            if not np.all(np.abs(got.astype(np.float64) - ref) <= 1e-5 * np.maximum(1.0, np.abs(ref)) + 8 * 2.0 ** -24 * S):      # (fuzz_convtaps' bound of the matrix-core path)
+            if d['twin']:                                               # an exact-sum twin: every order of the sum gives the oracle's bits
+                reach[TWIN_REACH] += 1
+                if not bits_equal(got, ref):
+                    bad(d, 'matrix-core call on an exact-sum twin differs from the oracle, max %r' % float(np.abs(got - ref).max()), plan)
+            elif not np.all(np.abs(got.astype(np.float64) - ref) <= 1e-5 * np.maximum(1.0, np.abs(ref)) + 8 * 2.0 ** -24 * fc.conv_abs_sum(d)):      # (fuzz_convtaps' bound of the matrix-core path)
                 bad(d, 'matrix-core call off by %r' % float(np.abs(got - ref).max()), plan)
             if not _same_bits(_spmm(op, xw, n, flags, ld=ld, start=start)[0], win):
                 bad(d, 'matrix-core call not deterministic', plan)
@@ -343,6 +348,7 @@ def _check(counts, reach, wanted, at_least):
 def test_fuzz_narrow_conv_operators():
     counts = fuzz_convtaps_narrow(CONV_CASES)
     _check(counts, fuzz_convtaps_narrow.reach, CONV_REACH, 3)
+    assert fuzz_convtaps_narrow.reach[TWIN_REACH] >= 1, dict(fuzz_convtaps_narrow.reach)
 
 
 def test_fuzz_narrow_csr_operators():

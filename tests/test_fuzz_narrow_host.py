@@ -6,6 +6,7 @@ import pytest
 import scipy.sparse
 
 import keynet_amd.sparse as ksp
+import exact_sum
 import fuzz_narrow_cases as fc
 
 # the tier of tests/test_fuzz_narrow_gpu.py (that module needs no device to import, but it is the GPU tier's: the numbers are restated and compared there)
@@ -22,7 +23,7 @@ def _conv_tier():
     """The conv cases of the tier, generated once: (descriptions, class counts, skipped, the worst ratio of the oracle's distance from the float64 product to its bound)."""
     if 'conv' not in _tier:
         (lines, counts, skipped, worst) = ([], dict.fromkeys(CONV_CLASSES, 0), 0, 0.0)
-        aims = {}
+        (aims, twins) = ({}, [])
         for d in fc.conv_cases(CONV_CASES, CONV_SEED):
             lines.append(fc.describe(d))
             if d['skipped']:
@@ -32,8 +33,15 @@ def _conv_tier():
                 counts[c] += 1
             aims[(d['cls'], d['aim'])] = aims.get((d['cls'], d['aim']), 0) + 1
             if not d['nonfinite']:
-                worst = max(worst, _judge_ratio(fc.conv_reference(d), d['X'][:, :d['n']]))
+                ratio = _judge_ratio(fc.conv_reference(d), d['X'][:, :d['n']])
+                worst = max(worst, ratio)
+            if d['twin']:
+                t = fc._taps_of(d['W'])
+                integer = all(np.array_equal(a, np.rint(a)) for a in (t['taps'], d['X']) + tuple(a for a in (t['ent_coef'], t['lastcol']) if a is not None))
+                twins.append(dict(case=d['case'], cls=d['cls'], ratio=ratio, integer=integer, nonfinite=d['nonfinite'], sums=exact_sum.condition_factored(d['W'], d['X'][:, :d['n']]),
+                                  matrix_core=bool(d['flags'] & fc.MFMA and not d['flags'] & fc.EXACT and ((d['props']['mfma_ok'] and d['n'] <= 32) or (d['n'] > 32 and d['flags'] & fc.N64M)))))
         _tier['conv'] = (lines, counts, skipped, worst, aims)
+        _tier['twins'] = twins
     return _tier['conv']
 
 
@@ -87,6 +95,18 @@ def test_conv_cases_reach_every_host_visible_class():
     for (cls, forms) in fc.CONV_AIMS.items():                          # every aim of every class is drawn at least 3 times: what the GPU tier's reach condition stands on
         for f in forms:
             assert aims.get((cls, f[0]), 0) >= 3, (cls, f[0], sorted(aims.items()))
+
+
+def test_exact_sum_twins_of_the_conv_tier():
+    """About one conv case in four is an exact-sum twin: integer operands, no non-finite activation, sum |a| |x| over the terms <= 2^24 (exact_sum.condition_factored
+    asserts it), so the oracle's float32 product IS the float64 product; and enough of them carry KN_FLAG_NARROW_MFMA on an operator the matrix-core narrow kernel takes (or, beyond 32 columns, the bit of the 64-column tile)
+    that the GPU tier's reach condition (one twin on a matrix-core plan) does not hang on one draw."""
+    _conv_tier()
+    twins = _tier['twins']
+    print(len(twins), 'twins;', sum(t['matrix_core'] for t in twins), 'aimed at the matrix-core narrow kernel; largest sum %.0f' % max(t['sums'] for t in twins))
+    assert CONV_CASES // 8 <= len(twins) <= 3 * CONV_CASES // 8, len(twins)
+    assert all(t['integer'] and not t['nonfinite'] and t['ratio'] == 0.0 and t['sums'] <= exact_sum.LIMIT and t['cls'] != 'dropped' for t in twins), [t for t in twins if t['ratio'] != 0.0][:3]
+    assert sum(t['matrix_core'] for t in twins) >= 3
 
 
 def test_csr_cases_reach_every_host_visible_class():

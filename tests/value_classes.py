@@ -13,6 +13,8 @@ values(variant, ...)     the operator side: every variant scales the builder's v
                          `overflow`  4 x `unit`: magnitude ~ 4 / sqrt(entries per row)
                          `wide`      `unit` and a per-entry factor 2^e, e uniform in -40 .. 40
                          `small-int` sign(v) * (1 or 2): integer products and sums, exact zeros in the sums, -0 products under a -0.0 activation
+conv_values(variant ...) a variant ('exact-sum', (split, cap)) hands the operator to tests/exact_sum.py: integer taps, coefficients and biases under a bit budget (the
+                         inputs on which the kernels that may re-order a sum must give the oracle's bits; tests/test_exact_sum_gpu.py)
 """
 import collections
 
@@ -246,6 +248,9 @@ def conv_values(variant, taps, coef, lastcol, per_row, seed=0):
     if variant is None:
         return (taps, coef, lastcol)
     (kind, bias_exp) = variant
+    if kind == 'exact-sum':                               # (tests/exact_sum.py: integer operands under a bit budget; the variant's second field is (split, cap))
+        import exact_sum
+        return exact_sum.conv_values(bias_exp[0], taps, coef, lastcol, per_row, seed, cap=bias_exp[1])
     rng = np.random.RandomState(seed)
     rms = _rms(taps) * (_rms(coef) if coef is not None else 1.0)
     t = values(kind, taps, per_row, rng, rms=rms)
