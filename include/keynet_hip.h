@@ -411,6 +411,32 @@ int kn_affine_to_linear(const float* x_dev, int64_t n, int64_t d, float* out_dev
  * the (y, x, ch) -> (ch, y, x) permutation of layout 1 is index arithmetic of the same pass.  An added entry point: KN_ABI_VERSION stays (the rule below). */
 int kn_u8_to_linear(const uint8_t* img_dev, int64_t n, int64_t c, int64_t h, int64_t w, int layout, float* out_dev, int64_t ldo, int64_t n_cols, void* stream);
 
+/* The per-image range of a feature-major block, on the device: the minimum and maximum the reference's mat2gray takes of an image on the host (keynet/sparse.py:25-33,
+ * behind keynet/system.py:173-181 and 223-228), for every column of a batch at once.
+ *   lo_dev[b] = min, hi_dev[b] = max of x[r * ld + b] over r < rows, for b < n_vecs <= ld (KN_ERR_SHAPE otherwise).  The caller passes rows = D: the ones row stays out.
+ * NaN elements are skipped; a column with no other element gives lo = +Inf, hi = -Inf (so does rows == 0).  Minimum and maximum are exact and commute, so the result does
+ * not depend on the launch geometry; only the sign of a zero is open (-0.0 and +0.0 compare equal).  The call initialises lo / hi itself (elements n_vecs and beyond are not
+ * touched), allocates nothing and does not wait for the device: it can be captured into a HIP graph.  Row chunks meet in the outputs through ordinary vector integer atomics
+ * on the floats' bits.  Every address is formed in 64 bits.  An added entry point: KN_ABI_VERSION stays (the rule below). */
+int kn_column_range(const float* x_dev, int64_t rows, int64_t ld, int64_t n_vecs, float* lo_dev, float* hi_dev, void* stream);
+
+/* The sensor's egress of frames, the inverse of kn_u8_to_linear in one launch: the reference turns a loaded tensor into a viewable 8-bit image on the host -- linear_to_affine
+ * (keynet/torch.py:71-77), the gray mapping of mat2gray (keynet/sparse.py:25-33) and the conversion to bytes (keynet/system.py:173-181, 223-228; decrypt at 257-263 stops
+ * at the float tensor) -- this is the affine, the rounding and the layout change for n columns of a feature-major block that is already on the device.
+ *   x_dev     the feature-major block, D = c * h * w rows of ldx floats; row D (the ones row) is not read, nor are columns n <= b < ldx
+ *   img_dev   n frames of D bytes; layout as kn_u8_to_linear's: 0: img[b][ch][y][x] (NCHW), 1: img[b][y][x][ch] (NHWC).  For b < n:
+ *                 t = gain[b] * x[((ch * h + y) * w + x) * ldx + b]        one IEEE f32 multiply
+ *                 t = t + bias[b]                                          one IEEE f32 add: never fused with the multiply
+ *                 img[b][..] = 0 if t is NaN, else min(255, max(0, rint(t)))    round to nearest, ties to even; -Inf -> 0, +Inf -> 255
+ *             bytes outside the n * D of the frames are not touched.
+ *   gain_dev, bias_dev   n device floats each; gain_dev == NULL means 1.0f, bias_dev == NULL means 0.0f (with both NULL t is x itself)
+ * 1 <= n <= ldx and c, h, w >= 1 (KN_ERR_SHAPE otherwise; nothing is launched); NULL x_dev or img_dev is KN_ERR_INVALID; every address is formed in 64 bits.  Tiled through
+ * LDS as bytes (256 frame positions x 64 images): contiguous floats along the batch on the way in -- 16-byte loads where ldx and x_dev are multiples of four floats, scalar
+ * loads otherwise -- contiguous bytes along a frame on the way out -- a dword per lane where D and img_dev are multiples of four bytes, bytes otherwise; the
+ * (ch, y, x) -> (y, x, ch) permutation of layout 1 is index arithmetic of the same pass.  No workspace.  An added entry point: KN_ABI_VERSION stays (the rule below). */
+int kn_linear_to_u8(const float* x_dev, int64_t ldx, int64_t n, int64_t c, int64_t h, int64_t w, int layout,
+                    const float* gain_dev, const float* bias_dev, uint8_t* img_dev, void* stream);
+
 /* keynet.torch.linear_to_affine (keynet/torch.py:71-77): y_dev [d+1, n] feature-major -> out_dev [n, d] row-major;
  * *maxdev_dev (device float, may be NULL) receives max_b |y[d, b] - 1| so the host can raise ValueError when > 1e-3. */
 int kn_linear_to_affine(const float* y_dev, int64_t ldy, int64_t n, int64_t d, float* out_dev, float* maxdev_dev, void* stream);

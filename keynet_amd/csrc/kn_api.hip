@@ -1135,6 +1135,29 @@ int kn_u8_to_linear(const uint8_t* img_dev, int64_t n, int64_t c, int64_t h, int
     });
 }
 
+int kn_column_range(const float* x_dev, int64_t rows, int64_t ld, int64_t n_vecs, float* lo_dev, float* hi_dev, void* stream) {
+    return guarded([&]() -> int {
+    KN_HOST_ONLY_GUARD();
+    KN_REQUIRE(rows >= 0 && n_vecs >= 0, KN_ERR_INVALID, "negative size");
+    KN_REQUIRE(ld >= n_vecs, KN_ERR_SHAPE, "leading dimension smaller than n_vecs");
+    KN_REQUIRE(((lo_dev && hi_dev) || n_vecs == 0) && (x_dev || rows * n_vecs == 0), KN_ERR_INVALID, "NULL pointer");
+    return column_range(x_dev, rows, ld, n_vecs, lo_dev, hi_dev, reinterpret_cast<hipStream_t>(stream));
+    });
+}
+
+int kn_linear_to_u8(const float* x_dev, int64_t ldx, int64_t n, int64_t c, int64_t h, int64_t w, int layout, const float* gain_dev, const float* bias_dev, uint8_t* img_dev,
+                    void* stream) {
+    return guarded([&]() -> int {
+    KN_HOST_ONLY_GUARD();
+    KN_REQUIRE(n >= 1 && n <= ldx, KN_ERR_SHAPE, "1 <= n <= ldx");
+    KN_REQUIRE(c >= 1 && h >= 1 && w >= 1, KN_ERR_SHAPE, "empty frame");
+    KN_REQUIRE(c <= INT32_MAX && h <= INT32_MAX && w <= INT32_MAX && h * w <= INT64_MAX / c, KN_ERR_INVALID, "frame size out of range");
+    KN_REQUIRE(layout == 0 || layout == 1, KN_ERR_INVALID, "layout is 0 (NCHW) or 1 (NHWC)");
+    KN_REQUIRE(x_dev && img_dev, KN_ERR_INVALID, "NULL pointer");
+    return linear_to_u8(x_dev, ldx, n, c, h, w, layout, gain_dev, bias_dev, img_dev, reinterpret_cast<hipStream_t>(stream));
+    });
+}
+
 int kn_linear_to_affine(const float* y_dev, int64_t ldy, int64_t n, int64_t d, float* out_dev, float* maxdev_dev, void* stream) {
     return guarded([&]() -> int {
     KN_HOST_ONLY_GUARD();

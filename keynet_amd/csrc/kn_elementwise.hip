@@ -3,6 +3,8 @@
 //   affine_to_linear    keynet/torch.py:65-68 + the x.t() of keynet/layer.py:92: [n, d] images -> [d+1, n] feature-major
 //   linear_to_affine    keynet/torch.py:71-77: [d+1, n] -> [n, d], plus max |last row - 1| for the host-side ValueError
 //   u8_to_linear        the sensor's ingest of raw frames (keynet/system.py:183-201 + keynet/torch.py:65-68): n uint8 frames, NCHW or NHWC -> [d+1, n_cols] feature-major, padded
+//   linear_to_u8        the sensor's egress (keynet/system.py:173-181, 223-228 + keynet/torch.py:71-77): n columns of a [d+1, ldx] block -> n uint8 frames, NCHW or NHWC, saturate(rint(gain * x + bias))
+//   column_range        the per-image minimum and maximum mat2gray takes (keynet/sparse.py:27), NaN skipped
 //   planes_to_columns / columns_to_planes   the two layout changes around the spatial CSR of the narrow split route (no reference counterpart)
 // Transposes go through a padded 64x65 LDS tile so both the global read and the global write are coalesced.
 #include "kn_internal.h"
@@ -212,6 +214,238 @@ int u8_to_linear(const uint8_t* img, int64_t n, int64_t c, int64_t h, int64_t w,
         else KN_U8_LAUNCH(false, false, false);
     }
 #undef KN_U8_LAUNCH
+    KN_HIP(hipGetLastError());
+    return KN_OK;
+}
+
+// kn_linear_to_u8: kn_u8_to_linear run backwards -- the first n columns of a feature-major block [D (+ the ones row, not read), ldx] -> n uint8 frames of D bytes,
+// img = saturate(rint(gain[b] * x + bias[b])).  The same tile: U8_POS = 256 OUTPUT byte positions x U8_COLS = 64 images, parked in LDS as BYTES, tile[image][position],
+// an image's row 260 bytes = 65 dwords.
+//   in    lane (g = lane / 4, q = lane % 4) owns images 4g .. 4g + 3 at the four positions of quad j = 16 * pass + 4 * wave + q: four loads, one per position, each a
+//         float4 along the batch -- 16 lanes x 16 bytes = 256 contiguous bytes of one feature row, four rows per wave instruction (V4 = false, ldx or the base not a
+//         multiple of four floats: scalar loads; a quad that crosses n loads scalars up to it either way, so columns n .. ldx - 1 are never read).  Multiply, add
+//         (separate roundings: the build is -ffp-contract=off and the two are __fmul_rn / __fadd_rn), rint, saturate.  Storing each byte on its own would put the
+//         four q of one g -- four positions of one image that share a dword -- on ONE bank with four addresses, every store instruction 4-way conflicted, sixteen of
+//         them per lane and pass; instead the lane packs the four positions of an image into a dword and stores four dwords: dword (4g + k) * 65 + j is in bank
+//         4g + k + j (mod 32), and over a half-wave (g = 0 .. 7, q = 0 .. 3, k fixed) 4g + q + const takes every one of the 32 banks once -- conflict-free.
+//         Under NHWC the row of output position p = (y * w + x) * c + ch is ch * (h * w) + (y * w + x): one division per quad, then steps of one channel.
+//   out   a wavefront writes 256 contiguous bytes of one frame, one dword per lane from consecutive banks (S4: D % 4 == 0 and a dword-aligned base, so a dword is
+//         inside the frame or outside it), one byte per lane otherwise (the four lanes of a dword read it as a broadcast).
+// Each lane loads the gain and bias of its four images once, before the passes.  No workspace; every address is formed in 64 bits; bytes outside the n * D are not touched.
+__device__ __forceinline__ uint32_t u8_saturate(float t) {
+    const float r = rintf(t);                               // v_rndne_f32: ties to even
+    return (t != t) ? 0u : (uint32_t)(int)fminf(255.0f, fmaxf(0.0f, r));
+}
+
+template <bool NHWC, bool V4, bool S4>
+__global__ __launch_bounds__(256) void linear_to_u8_kernel(const float* __restrict__ x, int64_t ldx, int64_t n, int64_t D, int c, int64_t hw, const float* __restrict__ gain,
+                                                           const float* __restrict__ bias, uint8_t* __restrict__ img) {
+    __shared__ __attribute__((aligned(16))) uint8_t tile[U8_COLS * U8_STRIDE];
+    const int64_t p0 = (int64_t)blockIdx.x * U8_POS;
+    const int64_t b0 = (int64_t)blockIdx.y * U8_COLS;
+    const int lane = (int)threadIdx.x & 63, wave = (int)threadIdx.x >> 6;
+    const int cols = (n - b0 < U8_COLS) ? (int)(n - b0) : U8_COLS;                  // images of this tile: >= 1
+    // in
+    const int g = lane >> 2, q = lane & 3;
+    const int64_t b = b0 + 4 * g;
+    if (4 * g < cols) {
+        float gn[4], bs[4];
+#pragma unroll
+        for (int k = 0; k < 4; k++) {
+            gn[k] = (gain && b + k < n) ? gain[b + k] : 1.0f;
+            bs[k] = (bias && b + k < n) ? bias[b + k] : 0.0f;
+        }
+        for (int pass = 0; pass < U8_POS / 64; pass++) {
+            const int j = pass * 16 + wave * 4 + q;
+            const int64_t p = p0 + 4 * j;
+            if (p >= D) break;                              // positions ascend with the pass
+            int64_t pix = 0;
+            int ch = 0;
+            if (NHWC) {
+                if (D <= (int64_t)INT32_MAX) {
+                    const uint32_t px = (uint32_t)p / (uint32_t)c;
+                    pix = px;
+                    ch = (int)((uint32_t)p - px * (uint32_t)c);
+                } else {
+                    pix = p / c;
+                    ch = (int)(p - pix * c);
+                }
+            }
+            uint32_t word[4] = {0u, 0u, 0u, 0u};
+#pragma unroll
+            for (int i = 0; i < 4; i++) {
+                float4 v = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
+                if (p + i < D) {
+                    const int64_t r = NHWC ? (int64_t)ch * hw + pix : p + i;
+                    const float* row = x + r * ldx;
+                    if (V4 && b + 4 <= n) {
+                        v = *reinterpret_cast<const float4*>(row + b);
+                    } else {
+                        v.x = row[b];                                               // b < n: 4g < cols
+                        if (b + 1 < n) v.y = row[b + 1];
+                        if (b + 2 < n) v.z = row[b + 2];
+                        if (b + 3 < n) v.w = row[b + 3];
+                    }
+                }
+                word[0] |= u8_saturate(__fadd_rn(__fmul_rn(gn[0], v.x), bs[0])) << (8 * i);
+                word[1] |= u8_saturate(__fadd_rn(__fmul_rn(gn[1], v.y), bs[1])) << (8 * i);
+                word[2] |= u8_saturate(__fadd_rn(__fmul_rn(gn[2], v.z), bs[2])) << (8 * i);
+                word[3] |= u8_saturate(__fadd_rn(__fmul_rn(gn[3], v.w), bs[3])) << (8 * i);
+                if (NHWC && ++ch == c) {
+                    ch = 0;
+                    pix++;
+                }
+            }
+#pragma unroll
+            for (int k = 0; k < 4; k++) *reinterpret_cast<uint32_t*>(tile + (4 * g + k) * U8_STRIDE + 4 * j) = word[k];     // images cols .. 4g + 3: rows of the tile nothing reads
+        }
+    }
+    __syncthreads();
+    // out
+    if (S4) {
+        const int64_t p = p0 + 4 * lane;
+        if (p < D)
+            for (int i = wave; i < cols; i += 4) *reinterpret_cast<uint32_t*>(img + (b0 + i) * D + p) = *reinterpret_cast<const uint32_t*>(tile + i * U8_STRIDE + 4 * lane);
+    } else {
+        const int64_t p = p0 + (int)threadIdx.x;
+        if (p < D)
+            for (int i = 0; i < cols; i++) img[(b0 + i) * D + p] = tile[i * U8_STRIDE + (int)threadIdx.x];
+    }
+}
+
+int linear_to_u8(const float* x, int64_t ldx, int64_t n, int64_t c, int64_t h, int64_t w, int layout, const float* gain, const float* bias, uint8_t* img, hipStream_t s) {
+    const int64_t D = c * h * w;
+    const int64_t ptiles = (D + U8_POS - 1) / U8_POS, ctiles = (n + U8_COLS - 1) / U8_COLS;
+    if (ptiles > INT32_MAX || ctiles > 65535) return fail(KN_ERR_UNSUPPORTED, "kn_linear_to_u8: more tiles than one launch grid holds");
+    const bool nhwc = layout == 1 && c > 1;                // one channel: the two layouts are the same bytes
+    const bool v4 = ldx % 4 == 0 && ((uintptr_t)x) % 16 == 0;
+    const bool s4 = D % 4 == 0 && ((uintptr_t)img) % 4 == 0;
+    const dim3 grid((unsigned)ptiles, (unsigned)ctiles);
+#define KN_L8_LAUNCH(NHWC, V4, S4) \
+    KN_LAUNCH("linear_to_u8_kernel<" #NHWC "," #V4 "," #S4 ">", (linear_to_u8_kernel<NHWC, V4, S4>), grid, dim3(256), 0, s, x, ldx, n, D, (int)c, h * w, gain, bias, img)
+    if (nhwc) {
+        if (v4 && s4) KN_L8_LAUNCH(true, true, true);
+        else if (v4) KN_L8_LAUNCH(true, true, false);
+        else if (s4) KN_L8_LAUNCH(true, false, true);
+        else KN_L8_LAUNCH(true, false, false);
+    } else {
+        if (v4 && s4) KN_L8_LAUNCH(false, true, true);
+        else if (v4) KN_L8_LAUNCH(false, true, false);
+        else if (s4) KN_L8_LAUNCH(false, false, true);
+        else KN_L8_LAUNCH(false, false, false);
+    }
+#undef KN_L8_LAUNCH
+    KN_HIP(hipGetLastError());
+    return KN_OK;
+}
+
+// kn_column_range: lo[b] = min, hi[b] = max over r < rows of x[r * ld + b], NaN skipped (keynet/sparse.py:27 per image: the input of mat2gray).  Lanes sit on columns, so a
+// wavefront's load is contiguous along the batch: a column tile is cw = the power of two >= min(n_vecs, 64) columns wide, a lane owns VEC of them -- four, one 16-byte
+// load, where ld and the base are multiples of four floats and the tile has four columns; one otherwise, and scalars in the quad that crosses n_vecs -- and thread t the
+// rows t / (cw / VEC) (+ multiples of 256 * VEC / cw) of its row chunk: one image still fills its wavefronts, with 256 consecutive rows.  A thread's running pairs go to
+// LDS, the first cw threads fold the partials of their column, and the row chunks meet in lo / hi through integer atomics on the float's bits: for a value with the sign bit clear
+// signed-integer order is float order, and every negative float is a negative integer below it; for a value with the sign bit set unsigned order is reversed float order,
+// and every non-negative float is an unsigned below it.  So min = (sign clear ? signed min : unsigned max), max = (sign clear ? signed max : unsigned min), each correct
+// whatever the slot holds, +-Inf and the fill values included.  The slot is read first and the atomic issued only when it would change it (kn_wave_absmax_commit: why).
+// Minimum and maximum are exact and commute: the result does not depend on the chunking.  column_range_fill_kernel initialises the outputs in the same stream.
+__global__ __launch_bounds__(256) void column_range_fill_kernel(float* __restrict__ lo, float* __restrict__ hi, int64_t n) {
+    for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (int64_t)gridDim.x * blockDim.x) {
+        lo[i] = __builtin_huge_valf();
+        hi[i] = -__builtin_huge_valf();
+    }
+}
+
+__device__ __forceinline__ void atomic_min_f32(float* slot, float v) {
+    if (!(v < __builtin_bit_cast(float, __atomic_load_n(reinterpret_cast<unsigned*>(slot), __ATOMIC_RELAXED)))) return;
+    if ((int)__float_as_uint(v) >= 0) atomicMin(reinterpret_cast<int*>(slot), (int)__float_as_uint(v));
+    else atomicMax(reinterpret_cast<unsigned*>(slot), __float_as_uint(v));
+}
+
+__device__ __forceinline__ void atomic_max_f32(float* slot, float v) {
+    if (!(v > __builtin_bit_cast(float, __atomic_load_n(reinterpret_cast<unsigned*>(slot), __ATOMIC_RELAXED)))) return;
+    if ((int)__float_as_uint(v) >= 0) atomicMax(reinterpret_cast<int*>(slot), (int)__float_as_uint(v));
+    else atomicMin(reinterpret_cast<unsigned*>(slot), __float_as_uint(v));
+}
+
+template <int VEC>
+__global__ __launch_bounds__(256) void column_range_kernel(const float* __restrict__ x, int64_t rows, int64_t ld, int64_t n_vecs, int cw, int64_t chunk_rows,
+                                                           float* __restrict__ lo, float* __restrict__ hi) {
+    __shared__ float red_lo[256 * VEC], red_hi[256 * VEC];
+    const int t = (int)threadIdx.x;
+    const int lpr = cw / VEC;                               // lanes per row of the tile: a power of two
+    const int col = (t & (lpr - 1)) * VEC, rsub = t / lpr, step = 256 / lpr;
+    const int64_t b = (int64_t)blockIdx.y * cw + col;
+    const int64_t r0 = (int64_t)blockIdx.x * chunk_rows;
+    const int64_t r1 = (rows - r0 < chunk_rows) ? rows : r0 + chunk_rows;
+    float mn[VEC], mx[VEC];
+#pragma unroll
+    for (int k = 0; k < VEC; k++) {
+        mn[k] = __builtin_huge_valf();
+        mx[k] = -__builtin_huge_valf();
+    }
+    if (VEC == 4 && b + 4 <= n_vecs) {
+        const float* px = x + b;
+#pragma unroll 4
+        for (int64_t r = r0 + rsub; r < r1; r += step) {
+            const float4 q = *reinterpret_cast<const float4*>(px + r * ld);
+            const float v[4] = {q.x, q.y, q.z, q.w};
+#pragma unroll
+            for (int k = 0; k < 4; k++) {
+                mn[k] = (v[k] < mn[k]) ? v[k] : mn[k];      // a NaN compares false: skipped
+                mx[k] = (v[k] > mx[k]) ? v[k] : mx[k];
+            }
+        }
+    } else if (b < n_vecs) {                                // VEC == 1, or the quad that crosses n_vecs: scalars up to it
+        const float* px = x + b;
+#pragma unroll 4
+        for (int64_t r = r0 + rsub; r < r1; r += step) {
+#pragma unroll
+            for (int k = 0; k < VEC; k++) {
+                if (b + k < n_vecs) {
+                    const float v = px[r * ld + k];
+                    mn[k] = (v < mn[k]) ? v : mn[k];
+                    mx[k] = (v > mx[k]) ? v : mx[k];
+                }
+            }
+        }
+    }
+#pragma unroll
+    for (int k = 0; k < VEC; k++) {
+        red_lo[rsub * cw + col + k] = mn[k];                // [step][cw]: 256 * VEC floats
+        red_hi[rsub * cw + col + k] = mx[k];
+    }
+    __syncthreads();
+    const int64_t bt = (int64_t)blockIdx.y * cw + t;
+    if (t < cw && bt < n_vecs) {
+        float a = red_lo[t], z = red_hi[t];
+        for (int k = 1; k < step; k++) {
+            const float a2 = red_lo[k * cw + t], z2 = red_hi[k * cw + t];
+            a = (a2 < a) ? a2 : a;
+            z = (z2 > z) ? z2 : z;
+        }
+        atomic_min_f32(lo + bt, a);
+        atomic_max_f32(hi + bt, z);
+    }
+}
+
+int column_range(const float* x, int64_t rows, int64_t ld, int64_t n_vecs, float* lo, float* hi, hipStream_t s) {
+    if (n_vecs <= 0) return KN_OK;
+    KN_LAUNCH("column_range_fill_kernel", column_range_fill_kernel, dim3((unsigned)std::min<int64_t>((n_vecs + 255) / 256, 1024)), dim3(256), 0, s, lo, hi, n_vecs);
+    if (rows > 0) {
+        int cw = 1;
+        while (cw < n_vecs && cw < 64) cw <<= 1;
+        const int64_t ctiles = (n_vecs + cw - 1) / cw;
+        if (ctiles > 65535) return fail(KN_ERR_UNSUPPORTED, "kn_column_range: more column tiles than one launch grid holds");
+        const bool v4 = cw >= 4 && ld % 4 == 0 && ((uintptr_t)x) % 16 == 0;         // 16 bytes per lane: tile corners are multiples of four columns
+        const int64_t step = 256 / (cw / (v4 ? 4 : 1));
+        const int64_t want = std::max<int64_t>(1, 2048 / ctiles);                   // row chunks per column tile: ~2 048 workgroups in all
+        int64_t chunk_rows = std::max<int64_t>((rows + want - 1) / want, 16 * step);
+        chunk_rows = (chunk_rows + step - 1) / step * step;
+        const int64_t chunks = (rows + chunk_rows - 1) / chunk_rows;               // <= want
+        const dim3 grid((unsigned)chunks, (unsigned)ctiles);
+        if (v4) KN_LAUNCH("column_range_kernel<4>", column_range_kernel<4>, grid, dim3(256), 0, s, x, rows, ld, n_vecs, cw, chunk_rows, lo, hi);
+        else KN_LAUNCH("column_range_kernel<1>", column_range_kernel<1>, grid, dim3(256), 0, s, x, rows, ld, n_vecs, cw, chunk_rows, lo, hi);
+    }
     KN_HIP(hipGetLastError());
     return KN_OK;
 }

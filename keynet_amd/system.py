@@ -794,11 +794,25 @@ class KeyedSensor(klayer.KeyedLayer):
     def __repr__(self):
         return str('<KeyedSensor: height=%d, width=%d, channels=%d>' % (self._inshape[2], self._inshape[3], self._inshape[1]))
 
-    def load(self, imgfile):
+    def load(self, imgfile, imagekey=None):
         """Read + resize an image file to the sensor shape as a float tensor in [0,255] (keynet/system.py:183-201 via
-        vipy; here PIL bilinear -- the resize interpolation is parity-unpinned)."""
+        vipy; here PIL bilinear -- the resize interpolation is parity-unpinned).
+        With `imagekey` (what save() returned next to the file; keynet/system.py:185-194): the file is an encrypted 8-bit image, read as stored -- no resize, its shape
+        asserted -- scaled by 1/255, homogenised and multiplied by the key (a SparseMatrix.torchdot on the device); the tensor becomes the decrypted [1, C, H, W] image."""
         from PIL import Image
         (C, H, W) = self._inshape[1:]
+        if imagekey is not None:
+            im = Image.open(imgfile)
+            if im.mode != ('L' if C == 1 else 'RGB'):
+                im = im.getchannel(0) if C == 1 else im.convert('RGB')          # one channel only, no scaling (keynet/system.py:186-187)
+            a = np.asarray(im, dtype=np.float32)
+            a = a.reshape(a.shape[0], a.shape[1], 1) if a.ndim == 2 else a
+            assert (a.shape[2], a.shape[0], a.shape[1]) == (C, H, W), 'the stored image %s is not the sensor shape %s' % (str(a.shape), str((C, H, W)))
+            x = torch.as_tensor(np.ascontiguousarray(a.transpose(2, 0, 1))).unsqueeze(0)
+            x_linear = ktorch.affine_to_linear((1.0 / 255.0) * x)               # [0, 255] -> [0, 1], one f32 multiply as the reference's
+            key = ksp.SparseMatrix(imagekey) if scipy.sparse.issparse(imagekey) else imagekey
+            self._tensor = ktorch.linear_to_affine(key.torchdot(x_linear.t()).t().float(), (1, C, H, W))
+            return self
         im = Image.open(imgfile).convert('L' if C == 1 else 'RGB').resize((W, H), Image.BILINEAR)
         a = np.asarray(im, dtype=np.float32)
         a = a.reshape(H, W, 1) if a.ndim == 2 else a
@@ -861,6 +875,81 @@ class KeyedSensor(klayer.KeyedLayer):
             n = x_raw.shape[0]
             self._tensor = ktorch.linear_to_affine(x_raw, (n,) + tuple(self._inshape[1:]))
         return self
+
+    def _check_cipher(self, x_cipher, layout):
+        """n of an encrypted block [n, C*H*W+1] (float32, on the device) that has this sensor's shape; ValueError otherwise, also for a wrong layout string.  No GPU call."""
+        if layout not in ktorch.LAYOUTS:
+            raise ValueError('invalid layout "%s": one of %s' % (str(layout), ', '.join(ktorch.LAYOUTS)))
+        return ktorch._check_linear(x_cipher, 'decrypt_frames', int(np.prod(self._inshape)))[0]
+
+    def decrypt_frames(self, x_cipher, layout='NHWC'):
+        """The encrypted block [n, C*H*W+1] on the device (what encrypt_frames returns, its zero images included) -> uint8 frames on the device, [n, H, W, C] or
+        [n, C, H, W] with layout='NCHW': the decrypt of keynet/system.py:257-263 for a batch, as this sensor's own decrypt product and kn_linear_to_u8
+        (ktorch.linear_to_frames with unit gain: round to nearest, saturate).  Under a permutation image key the decrypted block is exact, so
+        decrypt_frames(encrypt_frames(f)) == f byte for byte; under a float key as long as the decrypt error stays below one half.  Stateless: the loaded tensor of this
+        sensor is neither read nor changed.  The homogeneous column is not checked (decrypt() does: a zero image has none).  ValueError for a block that is not the sensor's
+        shape, before any GPU call."""
+        self._check_cipher(x_cipher, layout)
+        x_raw = super(KeyedSensor, self).decrypt(self._decryptkey, x_cipher)
+        return ktorch.linear_to_frames(x_raw.float(), tuple(self._inshape[1:]), layout=layout)
+
+    def asframes(self, layout='NHWC'):
+        """The loaded tensor, encrypted or not, one image or a batch, as gray-scaled uint8 frames on the device: (frames, gain, bias), frames [N, H, W, C] (or
+        [N, C, H, W]), gain and bias device float32 [N] -- every image mapped by its own range onto [0, 255] (the mat2gray of keynet/system.py:223-228, per image):
+        kn_column_range, ktorch.gray_affine, kn_linear_to_u8, nothing read back to the host.  An un-encrypted tensor is homogenised first (affine_to_linear).  A constant
+        image is black (gray_affine).  ValueError for a wrong layout string, before any GPU call."""
+        if layout not in ktorch.LAYOUTS:
+            raise ValueError('invalid layout "%s": one of %s' % (str(layout), ', '.join(ktorch.LAYOUTS)))
+        assert self.isloaded(), 'Load image first'
+        x = ksp._device_block(self._tensor) if not self._tensor.is_cuda else self._tensor.detach().float()
+        if not self.isencrypted():
+            x = ktorch.affine_to_linear(x)
+        (lo, hi) = ktorch.column_range(x)
+        (gain, bias) = ktorch.gray_affine(lo, hi)
+        return (ktorch.linear_to_frames(x, tuple(self._inshape[1:]), layout=layout, gain=gain, bias=bias), gain, bias)
+
+    def _image_mode(self):
+        C = self._inshape[1]
+        if C not in (1, 3):
+            raise ValueError('an image has 1 or 3 channels, this sensor has %d (asframes gives the bytes)' % C)
+        return 'L' if C == 1 else 'RGB'
+
+    def _asimage(self):
+        """(PIL image, gain, bias) of the one loaded image."""
+        from PIL import Image
+        mode = self._image_mode()
+        assert self.isloaded(), 'Load image first'
+        assert self._tensor.ndim == 3 or self._tensor.shape[0] == 1, 'asimage is for one image (asframes takes a batch)'
+        (frames, gain, bias) = self.asframes('NHWC')
+        a = frames[0].cpu().numpy()
+        return (Image.fromarray(a[:, :, 0] if mode == 'L' else a, mode), gain, bias)
+
+    def asimage(self):
+        """The loaded image (N == 1), encrypted or not, gray-scaled to 8 bits as a PIL.Image, 'RGB' for three channels and 'L' for one (keynet/system.py:223-228, PIL
+        in place of vipy); ValueError for another channel count."""
+        return self._asimage()[0]
+
+    def toimage(self):
+        return self.asimage()
+
+    def gray_imagekey(self, gain, bias):
+        """decryptkey . G^-1 for the gray mapping G: y = (gain / 255) x + bias / 255 of one encrypted image onto [0, 1] -- the key that takes the stored 8-bit image,
+        scaled by 1/255 and homogenised, back to the decrypted image (keynet/system.py:181).  G^-1 = [[(255 / gain) I, -bias / gain], [0, 1]] in closed form in float64,
+        cast at the end (keys.diagonal_affine_to_linear).  Host algebra (scipy); ValueError for gain == 0: a constant image was stored as black and has no inverse."""
+        (g, b) = (float(gain) / 255.0, float(bias) / 255.0)
+        if not (np.isfinite(g) and np.isfinite(b)) or g == 0.0:
+            raise ValueError('the gray mapping of a constant or non-finite image has no inverse (gain %g, bias %g)' % (float(gain), float(bias)))
+        D = int(np.prod(self._inshape))
+        (_, Ginv) = diagonal_affine_to_linear(scipy.sparse.eye(D, dtype=np.float64).tocsr() * g, np.full((D, 1), b, dtype=np.float64), withinverse=True)
+        return scipy.sparse.csr_matrix(self._decryptkey).dot(Ginv.tocsr())
+
+    def save(self, outfile='/tmp/out.png'):
+        """Write the encrypted image (N == 1) as an 8-bit PNG and return (outfile, imagekey): load(outfile, imagekey) reads it back and decrypts it, to within half a
+        gray step of the encrypted image's range (keynet/system.py:173-181)."""
+        assert self.isencrypted(), 'save() stores the encrypted image: encrypt() first'
+        (im, gain, bias) = self._asimage()
+        im.save(outfile, format='PNG')
+        return (outfile, self.gray_imagekey(gain.cpu()[0], bias.cpu()[0]))
 
 
 class PublicKeyedSensor(KeyedSensor):

@@ -70,6 +70,93 @@ def frames_to_linear(frames, layout='NHWC', pad_to=1):
     return out.t()
 
 
+def _check_linear(x_linear, what, features=None):
+    """(n, D) of an [n, D+1] float32 device tensor; ValueError for another type, rank, dtype or feature count, an empty batch or a host tensor.  Touches no GPU."""
+    if not isinstance(x_linear, torch.Tensor):
+        raise ValueError('%s takes a torch tensor, not %s' % (what, type(x_linear).__name__))
+    if x_linear.dim() != 2:
+        raise ValueError('%s takes the homogeneous block [n, D+1], not a tensor of rank %d' % (what, x_linear.dim()))
+    if x_linear.dtype != torch.float32:
+        raise ValueError('%s takes a float32 block, not %s' % (what, x_linear.dtype))
+    (n, D) = (int(x_linear.shape[0]), int(x_linear.shape[1]) - 1)
+    if n < 1 or D < 1:
+        raise ValueError('%s: empty block of shape %s' % (what, str(tuple(x_linear.shape))))
+    if features is not None and D != int(features):
+        raise ValueError('%s: %d features per image do not fit the frame shape, which has %d' % (what, D, int(features)))
+    if not x_linear.is_cuda:
+        raise ValueError('%s takes a block that is on the device' % what)
+    return (n, D)
+
+
+def _feature_major(x_linear):
+    """The feature-major [D+1, n] block the kernels read: the transposed view of x_linear in place where that is contiguous (what the keyed layers and frames_to_linear
+    return), the block ksp._device_block makes of it otherwise."""
+    xt = x_linear.detach().t()
+    if xt.is_contiguous():
+        return xt
+    from . import sparse as ksp
+    return ksp._device_block(xt)
+
+
+def column_range(x_linear):
+    """[n, D+1] float32 on the device -> (lo, hi), device float32 [n]: each image's minimum and maximum over its D features, the homogeneous column left out -- the two
+    numbers the reference's mat2gray takes of an image on the host (keynet/sparse.py:27).  NaN features are skipped; an image with no other feature gives (+Inf, -Inf).
+    kn_column_range on the current stream: no host read, nothing waits.  ValueError as linear_to_frames, before any GPU call."""
+    (n, D) = _check_linear(x_linear, 'column_range')
+    xt = _feature_major(x_linear)
+    lo = torch.empty(n, dtype=torch.float32, device=xt.device)
+    hi = torch.empty(n, dtype=torch.float32, device=xt.device)
+    with torch.cuda.device(xt.device):
+        _capi.column_range(xt.data_ptr(), D, n, n, lo.data_ptr(), hi.data_ptr(), _stream_ptr())
+    return (lo, hi)
+
+
+def gray_affine(lo, hi):
+    """(gain, bias) of the gray mapping of images whose ranges are [lo, hi] onto [0, 255]: gain = 255 / (hi - lo), bias = -lo * gain, element-wise on the tensors' own
+    device without a host read (keynet/sparse.py:25-33 with the 255 of the 8-bit image folded in).  Where hi == lo or the range is not finite (an infinite feature, or the
+    (+Inf, -Inf) of an image with no feature to compare) gain = 0 and bias = 0: such an image becomes black.  The reference divides by zero there: its constant image is
+    all NaN."""
+    (lo, hi) = (lo.float(), hi.float())
+    span = hi - lo
+    ok = torch.isfinite(lo) & torch.isfinite(hi) & torch.isfinite(span) & (span > 0)
+    (zero, one) = (torch.zeros_like(span), torch.ones_like(span))
+    gain = 255.0 / torch.where(ok, span, one)
+    bias = -torch.where(ok, lo, zero) * gain
+    ok = ok & torch.isfinite(gain) & torch.isfinite(bias)                # (a span so small that 255 / span overflows: not a finite range to map either)
+    return (torch.where(ok, gain, zero), torch.where(ok, bias, zero))
+
+
+def _per_image(v, n, device, name):
+    if v is None:
+        return None
+    if not isinstance(v, torch.Tensor) or v.dtype != torch.float32 or tuple(v.shape) != (n,):
+        raise ValueError('%s must be None or a float32 tensor of shape [%d]' % (name, n))
+    if not v.is_cuda or v.device != device:
+        raise ValueError('%s must be on the device of the block' % name)
+    return v.detach().contiguous()
+
+
+def linear_to_frames(x_linear, inshape, layout='NHWC', gain=None, bias=None):
+    """[n, C*H*W+1] float32 on the device (`inshape` = (C, H, W)) -> uint8 frames on the device, [n, H, W, C] (layout 'NHWC': a viewer's or an encoder's order) or
+    [n, C, H, W] ('NCHW'): frame = min(255, max(0, rint(gain[b] * x + bias[b]))), NaN -> 0 -- an f32 multiply, an f32 add, round to nearest even.  `gain`, `bias`: None (1 and
+    0: the block's own values) or device float32 tensors [n], one pair per image (gray_affine's).  The inverse of frames_to_linear: linear_to_frames(frames_to_linear(f)) == f.
+    The homogeneous column is not read (linear_to_affine is the call that checks it).  One launch of kn_linear_to_u8 on the current stream; the transposed view of a
+    feature-major block is read in place.  ValueError for a wrong layout string, rank, dtype or feature count, or a host tensor, before any GPU call."""
+    if layout not in LAYOUTS:
+        raise ValueError('invalid layout "%s": one of %s' % (str(layout), ', '.join(LAYOUTS)))
+    if len(tuple(inshape)) != 3 or min(int(v) for v in inshape) < 1:
+        raise ValueError('inshape must be (C, H, W), not %s' % str(inshape))
+    (C, H, W) = (int(v) for v in inshape)
+    (n, D) = _check_linear(x_linear, 'linear_to_frames', C * H * W)
+    (gain, bias) = (_per_image(gain, n, x_linear.device, 'gain'), _per_image(bias, n, x_linear.device, 'bias'))
+    xt = _feature_major(x_linear)
+    out = torch.empty((n, H, W, C) if layout == 'NHWC' else (n, C, H, W), dtype=torch.uint8, device=xt.device)
+    with torch.cuda.device(xt.device):
+        _capi.linear_to_u8(xt.data_ptr(), n, n, C, H, W, LAYOUTS.index(layout), None if gain is None else gain.data_ptr(), None if bias is None else bias.data_ptr(),
+                           out.data_ptr(), _stream_ptr())
+    return out
+
+
 def linear_to_affine(x, outshape=None):
     """Nx(K+1) -> NxK, checking that the homogeneous column is 1 within 1e-3 (ValueError otherwise), then reshaping to
     `outshape` (keynet/torch.py:71-77)."""
