@@ -213,6 +213,26 @@ enum kn_status {
                               KN_FLAG_NARROW_TAPS and KN_FLAG_NARROW_FILL.  kn_spmm_plan names the kernel, NV, the masked width, the column blocks and `coef`.
                               No reference counterpart. */
 
+#define KN_MODIFIER_WINO (0x4000u)  /* = 16384 (the next free bit: 0x1000 and 0x2000 are the two modifiers above).  A MODIFIER of a plain kn_spmm on a conv-taps handle, for callers
+                              that accept the float-key tolerance: a keyed 3 x 3 convolution runs in its 1-D Winograd F(2,3) form along the image rows -- two neighbouring outputs of
+                              a 3-tap row from 4 products instead of 6, two thirds of the matrix instructions.  Three launches: wino_in_kernel forms V [Cin][HiWi / 2][4] (sums and
+                              differences of two activation rows, f32), convtaps_mfma_kernel applies the DERIVED conv-taps operator (2 * HoWo pseudo output pixels, at most 3 slots each,
+                              12 tap matrices U formed in double and rounded once, K = 3 * Cin) into M, wino_out_kernel forms y(2c) = M0 + M1 + M2 + bias, y(2c + 1) = M1 - M2 - M3 + bias in
+                              that order, applies ReLU and stores (nontemporal; max |Y| of kn_spmm_screen folded in); conv_lastrow_kernel keeps the homogeneous row.  Every
+                              product and sum is f32; the association is not the plain call's, so the result agrees with it to the float-key tolerance, never bit for bit,
+                              and a column's bits do not depend on the batch width.  Inf - Inf inside the transforms is NaN where the plain product is Inf: a caller that must
+                              reproduce non-finite activations keeps them away from the flag (the Python host's screen does).
+                              It takes effect ONLY on a conv-taps handle, without KN_FLAG_EXACT and outside the narrow ranges, at n_vecs a multiple of 128 with x, y 16-byte
+                              aligned and ldx, ldy multiples of 4, on an ELIGIBLE operator: 9 taps, unit coefficients, no (output pixel, input pixel) pair hit twice, equal
+                              image sizes, at most one entry per (pixel, tap), and an entry table that IS a 3 x 3 convolution with zero padding of an image of even width under
+                              some pixel permutation on either side (derived from the table itself at the first call that asks, verified against the whole table;
+                              kn_wino_status says why an operator is not).  KN_FLAG_BF16X3 next to it changes nothing.
+                              The flag CAN ALLOCATE: the first such call (kn_spmm_plan included) derives and packs the operator's form (kn_release_side_tables frees it), and a
+                              call takes 2 * (Cin * HiWi + Cout * HoWo) * n_vecs floats from ONE pool per (device, stream) shared by all handles, grown to the largest request
+                              (kn_reserve_workspace with the flag's handle sizes it ahead of a HIP-graph capture; an unreserved call under capture fails).
+                              Where it changes NOTHING (same kernels, same plan string, same bits): with KN_FLAG_EXACT; in the narrow ranges; at other widths or alignments; on an
+                              ineligible operator; on CSR, dense, float64 and chain handles; in kn_spmm_planes.  kn_spmm_plan lists the three launches.  No reference counterpart. */
+
 typedef struct kn_operator* kn_handle_t;   /* opaque keyed operator resident in HBM */
 
 int         kn_abi_version(void);
@@ -383,6 +403,13 @@ int kn_release_side_tables(kn_handle_t h);
  * kn_dense_create handle has any: its split-K partial sums), so that the first kn_spmm on that stream can be captured into a HIP graph.
  * A no-op for every other operator kind. */
 int kn_reserve_workspace(kn_handle_t h, int64_t n_vecs, void* stream);
+/* The same for a call that carries `flags`: with KN_MODIFIER_WINO on a conv-taps handle whose call at n_vecs columns would take the Winograd form (16-byte aligned blocks assumed) it
+ * derives the form if that has not happened yet and grows the (device, stream) pool to what the call needs; with any other flag word it is kn_reserve_workspace.  An added
+ * entry point: KN_ABI_VERSION stays. */
+int kn_reserve_workspace_flags(kn_handle_t h, int64_t n_vecs, uint32_t flags, void* stream);
+/* KN_MODIFIER_WINO: is the operator eligible?  Derives the form if no call has asked yet (it allocates, like the first such kn_spmm).  *eligible = 1 | 0; buf (may be NULL)
+ * receives "eligible" or the reason it is not, NUL-terminated.  KN_ERR_UNSUPPORTED on other handle kinds.  An added entry point: KN_ABI_VERSION stays. */
+int kn_wino_status(kn_handle_t h, int* eligible, char* buf, int64_t buf_len);
 
 /* Introspection: which kernels kn_spmm would launch for this operator, batch width, leading dimensions (16-byte aligned activations
  * assumed) and flags -- the SAME dispatch code runs, every launch site describes itself instead of launching.  No reference

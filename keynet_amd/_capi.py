@@ -35,11 +35,14 @@ KN_MODIFIER_NARROW_TAPS32 = 0x1000
 # runs convtaps_narrow_taps_pairs_kernel (two output channels per lane, packed f32 multiplies and adds) at 1 .. 8 columns under KN_FLAG_NARROW, same bits; everywhere
 # else it changes nothing
 KN_MODIFIER_NARROW_TAPS_PAIRS = 0x2000
+# KN_MODIFIER_WINO of include/keynet_hip.h: modifier of a plain kn_spmm on a conv-taps handle -- an eligible keyed 3 x 3 conv runs its 1-D Winograd F(2,3) form at whole 128-column
+# tiles (tolerance contract: another association of the f32 sum); everywhere else it changes nothing.  Named KN_MODIFIER_* like the three above
+KN_MODIFIER_WINO = 0x4000
 KN_ABI_VERSION = 5
 
 # every symbol include/keynet_hip.h declares (tests/test_capi.py checks the header against this list)
 SYMBOLS = ['kn_abi_version', 'kn_last_error', 'kn_device_info', 'kn_csr_create', 'kn_csr_create_f64', 'kn_dtype_bits', 'kn_export_csr_f64', 'kn_spmm_f64', 'kn_tiled_create', 'kn_conv2dtiled_create',
-           'kn_convtaps_create', 'kn_convtaps_drop_zero_entries', 'kn_dense_create', 'kn_chain_create', 'kn_destroy', 'kn_nnz', 'kn_nnz_expanded', 'kn_shape', 'kn_export_csr', 'kn_spmm', 'kn_spmm_planes', 'kn_spmm_screen', 'kn_absmax', 'kn_reserve_workspace', 'kn_release_side_tables', 'kn_spmm_plan', 'kn_relu',
+           'kn_convtaps_create', 'kn_convtaps_drop_zero_entries', 'kn_dense_create', 'kn_chain_create', 'kn_destroy', 'kn_nnz', 'kn_nnz_expanded', 'kn_shape', 'kn_export_csr', 'kn_spmm', 'kn_spmm_planes', 'kn_spmm_screen', 'kn_absmax', 'kn_reserve_workspace', 'kn_reserve_workspace_flags', 'kn_wino_status', 'kn_release_side_tables', 'kn_spmm_plan', 'kn_relu',
            'kn_affine_to_linear', 'kn_u8_to_linear', 'kn_column_range', 'kn_linear_to_u8', 'kn_linear_to_affine', 'kn_planes_to_columns', 'kn_columns_to_planes']
 
 
@@ -94,6 +97,8 @@ def lib():
         L.kn_release_side_tables.argtypes = [p]
         L.kn_absmax.argtypes = [p, i64, i64, i64, p, p]
         L.kn_reserve_workspace.argtypes = [p, i64, p]
+        L.kn_reserve_workspace_flags.argtypes = [p, i64, u32, p]
+        L.kn_wino_status.argtypes = [p, p, p, i64]
         L.kn_relu.argtypes = [p, i64, i64, i64, p]
         L.kn_affine_to_linear.argtypes = [p, i64, i64, p, i64, p]
         L.kn_u8_to_linear.argtypes = [p, i64, i64, i64, i64, ci, p, i64, i64, p]
@@ -270,8 +275,19 @@ class Operator(object):
         else:
             check(lib().kn_spmm(self._h, x_ptr, int(ldx), int(n_vecs), y_ptr, int(ldy), int(flags), stream))
 
-    def reserve_workspace(self, n_vecs, stream):
-        check(lib().kn_reserve_workspace(self._h, int(n_vecs), stream))
+    def reserve_workspace(self, n_vecs, stream, flags=0):
+        """kn_reserve_workspace; with `flags` kn_reserve_workspace_flags (KN_MODIFIER_WINO: the (device, stream) pool of the Winograd form's V and M blocks)."""
+        if flags:
+            check(lib().kn_reserve_workspace_flags(self._h, int(n_vecs), int(flags), stream))
+        else:
+            check(lib().kn_reserve_workspace(self._h, int(n_vecs), stream))
+
+    def wino_status(self):
+        """kn_wino_status: (eligible, 'eligible' or the reason the operator has no Winograd form); derives the form when no call has asked yet."""
+        ok = ctypes.c_int(0)
+        buf = ctypes.create_string_buffer(256)
+        check(lib().kn_wino_status(self._h, ctypes.byref(ok), buf, 256))
+        return (bool(ok.value), buf.value.decode())
 
     def spmm_planes(self, x_ptr, ldx, x_plane_stride, n_planes, n_vecs, y_ptr, ldy, y_plane_stride, flags, stream):
         """kn_spmm_planes: this CSR operator on n_planes activation blocks in one launch per kernel; False when the operator needs the per-plane loop (KN_ERR_UNSUPPORTED)."""

@@ -4,8 +4,8 @@ import subprocess
 
 HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(HERE, 'csrc')
-INCLUDED = ['kn_internal.h', 'kn_conv_exact_pipe.inc', 'kn_conv_narrow_taps.inc', 'kn_conv_narrow_taps32.inc', 'kn_conv_narrow_taps_pairs.inc', 'kn_conv_narrow_fill.inc', 'kn_deal.h']      # what the sources include from csrc/ (kn_conv_exact_pipe.inc: the body two kernels of kn_conv.hip share; kn_conv_narrow_taps.inc: convtaps_narrow_taps_kernel; kn_conv_narrow_taps32.inc: convtaps_narrow_taps32_kernel; kn_conv_narrow_taps_pairs.inc: convtaps_narrow_taps_pairs_kernel; kn_conv_narrow_fill.inc: convtaps_narrow_fill_kernel; kn_deal.h: kn_api.hip's dealing order)
-SOURCES = ['kn_api.hip', 'kn_csr.hip', 'kn_csr_narrow.hip', 'kn_csr_stream.hip', 'kn_csr_f64.hip', 'kn_csr_mfma.hip', 'kn_conv.hip', 'kn_elementwise.hip', 'kn_chain.hip']
+INCLUDED = ['kn_internal.h', 'kn_conv_exact_pipe.inc', 'kn_conv_narrow_taps.inc', 'kn_conv_narrow_taps32.inc', 'kn_conv_narrow_taps_pairs.inc', 'kn_conv_narrow_fill.inc', 'kn_deal.h', 'kn_wino.h']      # what the sources include from csrc/ (kn_conv_exact_pipe.inc: the body two kernels of kn_conv.hip share; kn_conv_narrow_taps.inc: convtaps_narrow_taps_kernel; kn_conv_narrow_taps32.inc: convtaps_narrow_taps32_kernel; kn_conv_narrow_taps_pairs.inc: convtaps_narrow_taps_pairs_kernel; kn_conv_narrow_fill.inc: convtaps_narrow_fill_kernel; kn_deal.h: kn_api.hip's dealing order; kn_wino.h: the host derivation of KN_MODIFIER_WINO)
+SOURCES = ['kn_api.hip', 'kn_csr.hip', 'kn_csr_narrow.hip', 'kn_csr_stream.hip', 'kn_csr_f64.hip', 'kn_csr_mfma.hip', 'kn_conv.hip', 'kn_conv_wino.hip', 'kn_elementwise.hip', 'kn_chain.hip']
 LIB = os.path.join(HERE, 'libkeynet_hip.so')
 
 

@@ -2,6 +2,7 @@
 // entry point replaces).  Host-side conversion of the reference's operator containers into HBM-resident formats.
 #include "kn_internal.h"
 #include "kn_deal.h"
+#include "kn_wino.h"
 #include <algorithm>
 #include <cstring>
 #include <map>
@@ -428,6 +429,51 @@ static int convtaps_create_impl(ConvBuild& b, kn_operator** out) {
     return KN_OK;
 }
 
+// KN_MODIFIER_WINO: the handle's 1-D Winograd form (kn_wino.h), derived from its host description at the first call that asks and packed by the conv-taps packer above; the
+// caller holds lazy_mu.  An operator that is not eligible is marked so (wino_why) and KN_OK is returned: the call then runs what it runs without the flag.
+void wino_free(kn_operator* h) {
+    if (h->wino_sub) (void)kn_destroy(h->wino_sub);
+    if (h->wino_in) (void)hipFree(h->wino_in);
+    if (h->wino_out) (void)hipFree(h->wino_out);
+    h->wino_sub = nullptr;
+    h->wino_in = h->wino_out = nullptr;
+}
+
+int convtaps_build_wino(kn_operator* h) {
+    if (__atomic_load_n(&h->wino_state, __ATOMIC_ACQUIRE) != 0) return KN_OK;
+    const ConvTapsDev& c = h->ct;
+    const int64_t HoWo = c.Hout * c.Wout, HiWi = c.Hin * c.Win, msz = c.Cout * c.Cin;
+    WinoTables t = h->dense_sub ? wino_refuse("not a conv-taps operator") : wino_derive(HoWo, HiWi, c.ntaps, c.unit_coef, c.has_dups, h->h_ent_out, h->h_ent_in, h->h_ent_tap);
+    if (t.ok && (2 * HoWo * c.Cout >= INT32_MAX || 2 * HiWi * c.Cin >= INT32_MAX)) t = wino_refuse("the form's blocks pass the int32 row range");
+    if (!t.ok) {
+        h->wino_why = t.why;
+        __atomic_store_n(&h->wino_state, 2, __ATOMIC_RELEASE);
+        return KN_OK;
+    }
+    ConvBuild b;
+    b.inshape[0] = c.Cin; b.inshape[1] = HiWi / 2; b.inshape[2] = 4;
+    b.outshape[0] = c.Cout; b.outshape[1] = HoWo / 2; b.outshape[2] = 4;
+    b.has_last = false;
+    const std::vector<double> u = wino_taps(h->h_taps, msz);
+    b.taps.resize(u.size());
+    for (size_t k = 0; k < u.size(); k++) b.taps[k] = (float)u[k];      // formed in double, rounded once
+    b.ent_out = std::move(t.ent_out);
+    b.ent_in = std::move(t.ent_in);
+    b.ent_tap = std::move(t.ent_tap);
+    b.ent_coef.assign(b.ent_out.size(), 1.0f);
+    kn_operator* sub = nullptr;
+    int rc = convtaps_create_impl(b, &sub);
+    if (rc) return rc;
+    h->wino_sub = sub;
+    if ((rc = upload(&h->wino_in, t.in_d.data(), t.in_d.size())) || (rc = upload(&h->wino_out, t.out_pair.data(), t.out_pair.size()))) {
+        wino_free(h);
+        return rc;
+    }
+    h->wino_why.clear();
+    __atomic_store_n(&h->wino_state, 1, __ATOMIC_RELEASE);      // upload() is a synchronous copy: the tables are in HBM before the state is visible
+    return KN_OK;
+}
+
 // Processing order of the pixels for the table kernel.  Its workgroups (one output pixel x 32 * NRB channels x 256 batch columns) sweep the
 // input channels in the same order but start as earlier ones retire, so the ~128 resident on an XCD sit at staggered phases of the sweep:
 // an activation row is found in that XCD's L2 again only when the workgroup sharing it was dispatched a few places earlier (measured:
@@ -846,6 +892,7 @@ int kn_destroy(kn_handle_t h) {
     if (h->chain) chain_free(h->chain);
     if (h->dense_sub) kn_destroy(h->dense_sub);
     if (h->dense_lastcol) (void)hipFree(h->dense_lastcol);
+    wino_free(h);
     for (auto& kv : h->dense_ws)
         if (kv.second.ptr) (void)hipFree(kv.second.ptr);
     for (auto& r : h->dense_ws_retired) {
@@ -955,6 +1002,16 @@ static int dense_workspace(kn_handle_t h, hipStream_t s, int64_t n_vecs, float**
     return KN_OK;
 }
 
+// KN_MODIFIER_WINO: the state of the handle's form, derived now if no call has asked yet (kn_spmm_plan included: the plan names the derived operator's launch).
+// 1 built, 2 not eligible, 0 the derivation failed (out of memory: the call runs what it runs without the flag).
+static int wino_ready(kn_handle_t h) {
+    int st = __atomic_load_n(&h->wino_state, __ATOMIC_ACQUIRE);
+    if (st != 0) return st;
+    std::lock_guard<std::mutex> g(h->lazy_mu);
+    if (convtaps_build_wino(h) != KN_OK) return 0;
+    return __atomic_load_n(&h->wino_state, __ATOMIC_ACQUIRE);
+}
+
 // kn_spmm / kn_spmm_screen.  `absmax` (device float or null): raised to max |Y| -- folded into the stores of the matrix-core kernels, one
 // extra pass over Y behind every other kernel family.
 static int spmm_impl(kn_handle_t h, const float* x_dev, int64_t ldx, int64_t n_vecs, float* y_dev, int64_t ldy, uint32_t flags, float* absmax, void* stream) {
@@ -986,6 +1043,9 @@ static int spmm_impl(kn_handle_t h, const float* x_dev, int64_t ldx, int64_t n_v
         rc = convtaps_spmm(h->dense_sub->ct, x_dev, ldx, n_vecs, ws, n_vecs, 0, s);
         if (rc) return rc;
         rc = dense_reduce(ws, n_vecs, outs, S, h->dense_lastcol, x_dev + (h->cols - 1) * ldx, y_dev, ldy, n_vecs, (flags & KN_FLAG_RELU) ? 1 : 0, s);
+    } else if (wino_call(h->ct, flags, n_vecs, x_dev, ldx, y_dev, ldy) && wino_ready(h) == 1) {
+        rc = wino_spmm(h, x_dev, ldx, n_vecs, y_dev, ldy, flags, s, absmax);      // KN_MODIFIER_WINO on an eligible operator; max |Y| rides in wino_out_kernel's stores
+        fused = true;
     } else {
         // the side table the call's regime reads, built at its first use (the channel-lane kernels read the slot lists themselves, the f32 matrix-core kernels the taps)
         switch (conv_regime(h->ct, flags, n_vecs)) {
@@ -1061,9 +1121,14 @@ int kn_release_side_tables(kn_handle_t h) {
     FillRec* rec = __atomic_load_n(&h->ct.fill_rec, __ATOMIC_ACQUIRE);
     uint16_t* tb = __atomic_load_n(&h->ct.tapsB, __ATOMIC_ACQUIRE);
     PtRec* pt = __atomic_load_n(&h->ct.pt_rec, __ATOMIC_ACQUIRE);
-    if (!rec && !tb && !pt) return KN_OK;
+    const bool wino = h->wino_sub != nullptr;
+    if (!rec && !tb && !pt && !wino) return KN_OK;
     if (int rc = check_device(h, "")) return rc;
     KN_HIP(hipDeviceSynchronize());                               // a launch on ANY stream may still be reading the tables (rare call: a layer changed its contract)
+    if (wino) {                                                   // the Winograd form: derived again by the next call that asks
+        __atomic_store_n(&h->wino_state, 0, __ATOMIC_RELEASE);
+        wino_free(h);
+    }
     __atomic_store_n(&h->ct.fill_rec, (FillRec*)nullptr, __ATOMIC_RELEASE);
     __atomic_store_n(&h->ct.tapsB, (uint16_t*)nullptr, __ATOMIC_RELEASE);
     __atomic_store_n(&h->ct.pt_rec, (PtRec*)nullptr, __ATOMIC_RELEASE);
@@ -1082,6 +1147,36 @@ int kn_reserve_workspace(kn_handle_t h, int64_t n_vecs, void* stream) {
     if (int rc = check_device(h, "")) return rc;
     float* ws = nullptr;
     return dense_workspace(h, reinterpret_cast<hipStream_t>(stream), n_vecs, &ws);
+    });
+}
+
+int kn_reserve_workspace_flags(kn_handle_t h, int64_t n_vecs, uint32_t flags, void* stream) {
+    return guarded([&]() -> int {
+    KN_REQUIRE(h != nullptr, KN_ERR_INVALID, "NULL handle");
+    KN_REQUIRE(n_vecs >= 0 && n_vecs < INT32_MAX, KN_ERR_INVALID, "n_vecs out of range");
+    const float* aligned = reinterpret_cast<const float*>((uintptr_t)4096);
+    if (h->kind != KIND_CONVTAPS || !wino_call(h->ct, flags, n_vecs, aligned, 4, aligned, 4)) return kn_reserve_workspace(h, n_vecs, stream);
+    KN_HOST_ONLY_GUARD();
+    if (int rc = check_device(h, "")) return rc;
+    if (wino_ready(h) != 1) return KN_OK;
+    float* ws = nullptr;
+    return wino_workspace(h->device, reinterpret_cast<hipStream_t>(stream), wino_workspace_floats(h, n_vecs), &ws);
+    });
+}
+
+int kn_wino_status(kn_handle_t h, int* eligible, char* buf, int64_t buf_len) {
+    return guarded([&]() -> int {
+    KN_REQUIRE(h != nullptr && eligible != nullptr, KN_ERR_INVALID, "NULL argument");
+    KN_REQUIRE(h->kind == KIND_CONVTAPS, KN_ERR_UNSUPPORTED, "kn_wino_status: not a conv-taps operator");
+    if (int rc = check_device(h, "")) return rc;
+    const int st = wino_ready(h);
+    KN_REQUIRE(st != 0, KN_ERR_NOMEM, "kn_wino_status: the form could not be built: " + std::string(kn_last_error()));
+    *eligible = st == 1 ? 1 : 0;
+    if (buf && buf_len > 0) {
+        std::strncpy(buf, st == 1 ? "eligible" : h->wino_why.c_str(), (size_t)buf_len - 1);
+        buf[buf_len - 1] = 0;
+    }
+    return KN_OK;
     });
 }
 

@@ -2371,6 +2371,14 @@ static void launch_lastrow(const ConvTapsDev& A, const ConvArgs& a, hipStream_t 
               a.X + a.last_in_row * a.ldx, a.Y + out_last * a.ldy, n_vecs, a.relu, a.absmax);
 }
 
+// ... and for a launcher outside this file (kn_conv_wino.hip)
+int convtaps_lastrow(const ConvTapsDev& A, const float* x, int64_t ldx, int64_t n_vecs, float* y, int64_t ldy, int relu, float* absmax, hipStream_t s) {
+    ConvArgs a = conv_args(A, x, ldx, n_vecs, y, ldy, relu ? KN_FLAG_RELU : 0);
+    a.absmax = absmax;
+    launch_lastrow(A, a, s);
+    return KN_OK;
+}
+
 // KN_FLAG_EXACT: which order-preserving kernel takes a call, decided before anything is launched
 struct ExactChoice {
     enum Kernel { TABLE, PIPE, FILL, PLAIN } kernel = PLAIN;

@@ -378,6 +378,15 @@ struct kn_operator {
     std::vector<Retired> dense_ws_retired;
     // a whole key-net of CSR operators as one launch (kn_chain.hip)
     kn::ChainDev* chain = nullptr;
+    // KN_MODIFIER_WINO (kn_wino.h, kn_conv_wino.hip): the 1-D Winograd F(2,3) form of a keyed 3 x 3 conv, derived from the handle's host description at the first call that
+    // asks (convtaps_build_wino under lazy_mu, kn_api.hip) and kept as a sub-operator like dense_sub: a conv-taps operator of 2 * HoWo pseudo output pixels over
+    // 2 * HiWi pseudo input pixels and 12 taps, packed by the ordinary conv-taps packer.  wino_state: 0 not asked yet, 1 built, 2 the operator is not eligible (wino_why
+    // says why; asked once).  kn_release_side_tables and kn_destroy free it.
+    int wino_state = 0;
+    std::string wino_why;
+    kn_operator* wino_sub = nullptr;
+    int32_t* wino_in = nullptr;       // [HiWi / 2][4] input pixels d0 .. d3 of an input pair (-1: outside the image): wino_in_kernel
+    int32_t* wino_out = nullptr;      // [HoWo / 2][2] output pixels of an output pair: wino_out_kernel
 };
 
 namespace kn {
@@ -578,6 +587,22 @@ int csr_stream_group_spmm(const CsrDev& A, const float* x, int64_t ldx, int64_t 
 int convtaps_spmm(const ConvTapsDev& A, const float* x, int64_t ldx, int64_t n_vecs, float* y, int64_t ldy,
                   uint32_t flags, hipStream_t s, float* absmax = nullptr, bool* absmax_fused = nullptr);
 int absmax_pass(const float* y, int64_t rows, int64_t ld, int64_t n_vecs, float* absmax, hipStream_t s);
+// the homogeneous row of a conv-taps operator's output on its own (kn_conv.hip, conv_lastrow_kernel), for a launcher outside that file
+int convtaps_lastrow(const ConvTapsDev& A, const float* x, int64_t ldx, int64_t n_vecs, float* y, int64_t ldy, int relu, float* absmax, hipStream_t s);
+// KN_MODIFIER_WINO, a modifier of a plain kn_spmm (regimes MFMA and BF16X3: without KN_FLAG_EXACT and outside the narrow ranges) on a conv-taps handle: whole 128-column
+// tiles of 16-byte aligned blocks on an eligible operator run the 1-D Winograd form -- wino_in_kernel, the derived operator's matrix-core launch, wino_out_kernel.  In
+// every other case the bit is not read.  wino_call is the one place that reads it (the operands' half; eligibility is the handle's wino_state).
+static inline bool wino_call(const ConvTapsDev& A, uint32_t flags, int64_t n_vecs, const float* x, int64_t ldx, const float* y, int64_t ldy) {
+    if (!(flags & KN_MODIFIER_WINO) || n_vecs <= 0 || n_vecs % 128 != 0 || ldx % 4 != 0 || ldy % 4 != 0 || ((uintptr_t)x) % 16 != 0 || ((uintptr_t)y) % 16 != 0) return false;
+    const ConvRegime r = conv_regime(A, flags, n_vecs);
+    return r == MFMA || r == BF16X3;
+}
+int convtaps_build_wino(kn_operator* h);      // kn_api.hip (it reads the host description of the handle); the caller holds lazy_mu
+void wino_free(kn_operator* h);               // kn_api.hip
+int wino_spmm(const kn_operator* h, const float* x, int64_t ldx, int64_t n_vecs, float* y, int64_t ldy, uint32_t flags, hipStream_t s, float* absmax);      // kn_conv_wino.hip
+// the V and M blocks of a call: 2 * (Cin * HiWi + Cout * HoWo) * n_vecs floats from ONE pool per (device, stream), shared by all handles and grown to the largest request
+int64_t wino_workspace_floats(const kn_operator* h, int64_t n_vecs);
+int wino_workspace(int device, hipStream_t s, int64_t floats, float** out);
 struct MfTaps;
 int convtaps_exact_table_spmm(const ConvTapsDev& A, const float* x, int64_t ldx, int64_t n_vecs, float* y, int64_t ldy, int relu, hipStream_t s);
 

@@ -248,7 +248,9 @@ class KeyedLayer(nn.Module):
         `form.taps` (narrow_taps=True | 'packed'), `form.fill` (narrow_fill=True): handed on to every operator with a conv-taps handle, next to whatever `narrow` it gets."""
         (W, exact) = (self.W, getattr(self, '_exact', True))
         if not form.mode:
-            return (exact, {})
+            # a layer calibration put on the Winograd form of its matrix-core launch (record: decided='mfma', form='wino'; the contract stays False)
+            rec = getattr(self, '_contract_record', None)
+            return ('wino' if exact is False and rec is not None and rec.get('form') == 'wino' else exact, {})
         if W.narrow_capable():
             taps = dict(dict(narrow_taps=form.taps) if form.taps else {}, **(dict(narrow_fill=True) if form.fill else {}))
             if form.tile64 and (xt is None or xt.shape[1] > ksp.NARROW32_MAX):
@@ -292,6 +294,9 @@ class KeyedLayer(nn.Module):
         route; the library runs convtaps_narrow_fill_kernel on an eligible (filled-in) operator at up to NARROW32_MAX columns and ignores the bit elsewhere."""
         form = ksp.NarrowForm.of(None, narrow, narrow_rows, narrow32, narrow64, narrow_linear, narrow_split=narrow_split, narrow_taps=narrow_taps, narrow_fill=narrow_fill)
         conv = isinstance(W, ksp.Conv2dTiledMatrix)
+        wino = contract == 'wino'          # the matrix cores (False) with KN_MODIFIER_WINO on a conv operator's wide launch: no contract of its own (narrowed() passes it for a layer whose record holds form='wino')
+        if wino:
+            contract = False
         if form.split and conv and contract == 'split' and W.narrow_capable() and W.split_capable():
             return None
         lane = bool(form.mode) and W.narrow_capable()       # one launch of a narrow conv kernel, whatever the contract
@@ -310,7 +315,8 @@ class KeyedLayer(nn.Module):
         return (get_op, (_capi.KN_FLAG_RELU if relu else 0) | (_capi.KN_FLAG_EXACT if exact else 0) | (_capi.KN_FLAG_BF16X3 if bf16x3 else 0) |
                 (_capi.KN_FLAG_NARROW_MFMA if mfma else _capi.KN_FLAG_NARROW if lane else 0) | (_capi.KN_FLAG_NARROW_TAPS if form.taps and lane and not mfma else 0) | (_capi.KN_MODIFIER_NARROW_TAPS32 if form.taps in ('packed', 'pairs') and lane and not mfma else 0) | (_capi.KN_MODIFIER_NARROW_TAPS_PAIRS if form.taps == 'pairs' and lane and not mfma else 0) | (_capi.KN_MODIFIER_NARROW_FILL if form.fill and lane and not mfma else 0) | (_capi.KN_FLAG_NARROW32 if lane and form.narrow32 else 0) | (_capi.KN_FLAG_NARROW64 if lane and form.narrow64 else 0) |
                 (_capi.KN_FLAG_NARROW64_MFMA if mfma and form.tile64 and contract in (False, 'bf16x3') else 0) |
-                (_capi.KN_FLAG_NARROW_ROWS if form.rows and stored else 0) | (_capi.KN_FLAG_NARROW_LINEAR if form.linear and stored else 0))
+                (_capi.KN_FLAG_NARROW_ROWS if form.rows and stored else 0) | (_capi.KN_FLAG_NARROW_LINEAR if form.linear and stored else 0) |
+                (_capi.KN_MODIFIER_WINO if wino and conv and not lane else 0))
 
     def launch(self, device, relu=False, narrow=False, narrow_rows=False, narrow32=False, narrow64=False, narrow_linear=False, narrow_split=False, narrow_taps=False, narrow_fill=False):
         """This layer under its contract in force as one launch on `device` (`relu`: the unkeyed nn.ReLU behind it is fused in), or None when it is not one
@@ -596,6 +602,21 @@ class KeyedLayer(nn.Module):
                     W._device_op(dev).release_side_tables()
                 return ys.t()
             del ys
+        # candidate for a keyed 3 x 3 conv whose plan takes it: the 1-D Winograd F(2,3) form of the matrix-core launch (Conv2dTiledMatrix.wino_offered: the cost rule;
+        # the plan: the library's eligibility).  The 2 eps rowsum bound does not describe this association (sums and differences of activations, halved tap sums), so it is
+        # held to the rule of the bf16x3 candidate: a quarter of the gate on the measured window.  The contract stays 'mfma'; the record says which form runs.
+        if isinstance(W, ksp.Conv2dTiledMatrix) and cols % 128 == 0 and W.wino_offered(cols) and W.wino_offered(n) and W.wino_planned(cols, relu, dev):
+            if ye_win is None:
+                ye_win = W.torchdot(xt[:, win], relu=relu, exact=True)
+            yw = W.torchdot(xt[:, win], relu=relu, exact='wino')
+            (ratio_w, meas_w, tol_w, dmax_w) = gate(yw, ye_win)
+            ymax_w = float(ye_win.abs().max())
+            del yw
+            if ratio_w <= 0.25:
+                self._exact = False
+                self._contract_record = dict(layer=self._repr, decided='mfma', form='wino', max_abs_rowsum=asum, max_abs_x=xmax, max_abs_y=ymax_w, tol=tol_w, bound=bound,
+                                             measured_mfma_vs_exact=meas_w, gate_ratio=ratio_w, max_abs_diff=dmax_w, measured_on_columns=cols, measured_from_column=c0)
+                return W.torchdot(xt, relu=relu, exact='wino').t()
         y = W.torchdot(xt, relu=relu, exact=False)
         ymax = float(y.abs().max())
         (ratio, measured, tol, dmax) = (None, None, FLOAT_KEY_ATOL, None)

@@ -801,8 +801,27 @@ class Conv2dTiledMatrix(TiledMatrix):
         narrow kernel when `exact` is False / 'bf16x3' / 'split' and the operator is eligible (no (pixel, tap) pair with more than two slots), else exactly narrow=True;
         narrow64='mfma' (with narrow='mfma') beyond NARROW32_MAX columns under False / 'bf16x3' the f32 product on 64-column tiles (per column the bits of the plain
         matrix-core call on the batch zero-padded to 128 columns), else narrow64=True.  The flag word is KeyedLayer.kernel's."""
-        assert not isinstance(exact, str) or exact in ('bf16x3', 'split') or (narrow and exact == 'auto'), "exact must be True, False, 'bf16x3' or 'split'"
+        assert not isinstance(exact, str) or exact in ('bf16x3', 'split', 'wino') or (narrow and exact == 'auto'), "exact must be True, False, 'bf16x3', 'split' or 'wino'"
         return _run_torchdot(self, x, relu=relu, exact=exact, absmax=absmax, narrow=narrow, narrow32=narrow32, narrow64=narrow64, narrow_split=narrow_split, narrow_taps=narrow_taps, narrow_fill=narrow_fill)
+
+    # ---- the 1-D Winograd F(2,3) form of a keyed 3 x 3 conv (tolerance contract only) ----------------------------------------------------
+    # exact='wino' is exact=False with KN_MODIFIER_WINO (include/keynet_hip.h): two neighbouring outputs of a 3-tap image row from 4 products instead of 6 -- two thirds
+    # of the matrix instructions, paid for with two memory-bound transforms over blocks twice the activations' size.  Whether an operator HAS the form is the
+    # library's answer (its entry table must be a 3 x 3 convolution of an image of even width under some pixel permutation; the plan names the launches); whether
+    # the form is worth OFFERING is the cost rule here, kept apart from that like split_capable.  Another association of the f32 sum: KeyedLayer._calibrate measures it
+    # against the order-preserving kernel and accepts it at a quarter of the gate.  Inf - Inf inside the input transform is NaN where the plain product is Inf:
+    # non-finite activations must not reach the form, and they do not -- the screen of the float-key contract sends such a layer to the stored order first.
+    WINO_MIN_CHANNELS = 128     # measured (profiles/wino_layer_ab.txt, VGG-16 shapes at 128 and 256 columns, A-B-A-B in one process): every shape from conv2_2 (128 -> 128
+                                # channels: 1.04 - 1.08x) to conv5_x (1.35 - 1.41x) won in every repetition; operators with a 64-channel side were not measured and are not offered
+
+    def wino_offered(self, n_vecs):
+        """The cost rule of exact='wino': whole 128-column tiles on an operator whose smaller channel count reaches WINO_MIN_CHANNELS."""
+        return n_vecs > 0 and n_vecs % 128 == 0 and min(self._inshape[0], self._outshape[0]) >= self.WINO_MIN_CHANNELS
+
+    def wino_planned(self, n_vecs, relu, device):
+        """Does a plain call of n_vecs columns with KN_MODIFIER_WINO take the form on this operator (the library's eligibility, read off the plan)?"""
+        with torch.cuda.device(device):
+            return 'wino_in_kernel' in self._device_op(device).plan(n_vecs, _capi.KN_MODIFIER_WINO | (_capi.KN_FLAG_RELU if relu else 0))
 
     def __getstate__(self):
         d = super(Conv2dTiledMatrix, self).__getstate__()
