@@ -464,6 +464,40 @@ int kn_column_range(const float* x_dev, int64_t rows, int64_t ld, int64_t n_vecs
 int kn_linear_to_u8(const float* x_dev, int64_t ldx, int64_t n, int64_t c, int64_t h, int64_t w, int layout,
                     const float* gain_dev, const float* bias_dev, uint8_t* img_dev, void* stream);
 
+/* The dequantising ingest of encrypted frames: kn_u8_to_linear for the wire between a sensor and the key-net.  The reference stores an encrypted image as an 8-bit picture
+ * (keynet/system.py:173-181) and reads it back on the host through a private image key (keynet/system.py:185-194); here n quantised frames that are already on the
+ * device become the feature-major block a keyed layer reads, and the inverse of the gray mapping -- public numbers, one pair per image -- is applied in the same launch.
+ *   img_dev   n frames of D = c * h * w elements: bytes for depth 8, uint16_t in host byte order for depth 16; layout codes as kn_u8_to_linear's (0: NCHW, 1: NHWC)
+ *   out_dev   the feature-major block.  For b < n and row r = (ch * h + y) * w + x:
+ *                 t = (float)img[b][..]                                    exact at both depths
+ *                 t = scale[b] * t                                         one IEEE f32 multiply
+ *                 t = t + offset[b]                                        one IEEE f32 add: never fused with the multiply
+ *                 out[r * ldo + b] = t
+ *             out[D * ldo + b] = 1.0f for b < n (the ones row); every row, the ones row included, is +0.0f for n <= b < n_cols: a zero image is a zero image, it is NOT
+ *             offset; columns n_cols <= b < ldo are not touched.
+ *   scale_dev, offset_dev   n device floats each; scale_dev == NULL means no multiply, offset_dev == NULL means no add.  With both NULL and depth == 8 the block is
+ *             bit-equal to kn_u8_to_linear's.
+ * Refusals as kn_u8_to_linear's -- 1 <= n <= n_cols <= ldo and c, h, w >= 1 (KN_ERR_SHAPE), layout 0 or 1 and non-NULL img_dev, out_dev (KN_ERR_INVALID) -- and: a depth other
+ * than 8 or 16 is KN_ERR_UNSUPPORTED, 16-bit frames at an address that is not a multiple of two KN_ERR_INVALID.  Nothing is launched on a refusal.  Every address is formed in
+ * 64 bits.  The call allocates nothing and does not wait for the device: it can be captured into a HIP graph.  Tiled through LDS as the stored integers (256 bytes of a frame
+ * x 64 images: 256 positions at 8 bits, 128 at 16): contiguous reads along a frame -- a dword per lane where the frame size in bytes and img_dev are multiples of four, one
+ * element per lane otherwise -- and one 16-byte store along the batch per lane where ldo and out_dev are multiples of four floats, scalar stores otherwise.  An added entry
+ * point: KN_ABI_VERSION stays (the rule below). */
+int kn_frames_to_linear(const void* img_dev, int depth, int64_t n, int64_t c, int64_t h, int64_t w, int layout,
+                        const float* scale_dev, const float* offset_dev,
+                        float* out_dev, int64_t ldo, int64_t n_cols, void* stream);
+
+/* kn_linear_to_u8 at 16 bits, the egress a float image key needs (half a gray step of an 8-bit encrypted image is 0.2 % of its range on every feature; 16 bits bring that down
+ * 257-fold).  Arguments, layouts and refusals are kn_linear_to_u8's, with n frames of D uint16_t in host byte order.  For b < n:
+ *                 t = gain[b] * x[((ch * h + y) * w + x) * ldx + b]        one IEEE f32 multiply
+ *                 t = t + bias[b]                                          one IEEE f32 add: never fused with the multiply
+ *                 img[b][..] = 0 if t is NaN, else min(65535, max(0, rint(t)))  round to nearest, ties to even; -Inf -> 0, +Inf -> 65535
+ * gain_dev == NULL means 1.0f, bias_dev == NULL means 0.0f; halfwords outside the n * D of the frames are not touched; an img_dev that is not a multiple of two is
+ * KN_ERR_INVALID.  The same LDS tile at 128 frame positions x 64 images; stores along a frame are a dword per lane where 2 * D and img_dev are multiples of four bytes, halfwords
+ * otherwise.  No workspace; allocates nothing, does not wait for the device.  An added entry point: KN_ABI_VERSION stays (the rule below). */
+int kn_linear_to_u16(const float* x_dev, int64_t ldx, int64_t n, int64_t c, int64_t h, int64_t w, int layout,
+                     const float* gain_dev, const float* bias_dev, uint16_t* img_dev, void* stream);
+
 /* keynet.torch.linear_to_affine (keynet/torch.py:71-77): y_dev [d+1, n] feature-major -> out_dev [n, d] row-major;
  * *maxdev_dev (device float, may be NULL) receives max_b |y[d, b] - 1| so the host can raise ValueError when > 1e-3. */
 int kn_linear_to_affine(const float* y_dev, int64_t ldy, int64_t n, int64_t d, float* out_dev, float* maxdev_dev, void* stream);

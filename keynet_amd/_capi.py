@@ -43,7 +43,7 @@ KN_ABI_VERSION = 5
 # every symbol include/keynet_hip.h declares (tests/test_capi.py checks the header against this list)
 SYMBOLS = ['kn_abi_version', 'kn_last_error', 'kn_device_info', 'kn_csr_create', 'kn_csr_create_f64', 'kn_dtype_bits', 'kn_export_csr_f64', 'kn_spmm_f64', 'kn_tiled_create', 'kn_conv2dtiled_create',
            'kn_convtaps_create', 'kn_convtaps_drop_zero_entries', 'kn_dense_create', 'kn_chain_create', 'kn_destroy', 'kn_nnz', 'kn_nnz_expanded', 'kn_shape', 'kn_export_csr', 'kn_spmm', 'kn_spmm_planes', 'kn_spmm_screen', 'kn_absmax', 'kn_reserve_workspace', 'kn_reserve_workspace_flags', 'kn_wino_status', 'kn_release_side_tables', 'kn_spmm_plan', 'kn_relu',
-           'kn_affine_to_linear', 'kn_u8_to_linear', 'kn_column_range', 'kn_linear_to_u8', 'kn_linear_to_affine', 'kn_planes_to_columns', 'kn_columns_to_planes']
+           'kn_affine_to_linear', 'kn_u8_to_linear', 'kn_column_range', 'kn_linear_to_u8', 'kn_frames_to_linear', 'kn_linear_to_u16', 'kn_linear_to_affine', 'kn_planes_to_columns', 'kn_columns_to_planes']
 
 
 class KeynetHipError(RuntimeError):
@@ -104,6 +104,8 @@ def lib():
         L.kn_u8_to_linear.argtypes = [p, i64, i64, i64, i64, ci, p, i64, i64, p]
         L.kn_column_range.argtypes = [p, i64, i64, i64, p, p, p]
         L.kn_linear_to_u8.argtypes = [p, i64, i64, i64, i64, i64, ci, p, p, p, p]
+        L.kn_frames_to_linear.argtypes = [p, ci, i64, i64, i64, i64, ci, p, p, p, i64, i64, p]
+        L.kn_linear_to_u16.argtypes = [p, i64, i64, i64, i64, i64, ci, p, p, p, p]
         L.kn_linear_to_affine.argtypes = [p, i64, i64, i64, p, p, p]
         L.kn_planes_to_columns.argtypes = [p, i64, i64, i64, i64, i64, p, i64, p]
         L.kn_columns_to_planes.argtypes = [p, i64, i64, i64, i64, p, i64, i64, p]
@@ -334,6 +336,17 @@ def linear_to_u8(x_ptr, ldx, n, c, h, w, layout, gain_ptr, bias_ptr, img_ptr, st
     """kn_linear_to_u8: the first n columns of the feature-major block at ldx -> n uint8 frames (layout 0: NCHW, 1: NHWC), img = saturate(rint(gain[b] * x + bias[b]));
     gain_ptr / bias_ptr None: 1.0 / 0.0."""
     check(lib().kn_linear_to_u8(x_ptr, int(ldx), int(n), int(c), int(h), int(w), int(layout), gain_ptr, bias_ptr, img_ptr, stream))
+
+
+def frames_to_linear(img_ptr, depth, n, c, h, w, layout, scale_ptr, offset_ptr, out_ptr, ldo, n_cols, stream):
+    """kn_frames_to_linear: n frames of `depth` = 8 | 16 bits (layout 0: NCHW, 1: NHWC) -> the feature-major [c * h * w + 1, n_cols] block at ldo,
+    out = offset[b] + scale[b] * img (a multiply, then an add; scale_ptr / offset_ptr None: that statement is left out), ones row appended, columns n .. n_cols - 1 zero images."""
+    check(lib().kn_frames_to_linear(img_ptr, int(depth), int(n), int(c), int(h), int(w), int(layout), scale_ptr, offset_ptr, out_ptr, int(ldo), int(n_cols), stream))
+
+
+def linear_to_u16(x_ptr, ldx, n, c, h, w, layout, gain_ptr, bias_ptr, img_ptr, stream):
+    """kn_linear_to_u16: linear_to_u8 into n uint16 frames, saturating at 65535."""
+    check(lib().kn_linear_to_u16(x_ptr, int(ldx), int(n), int(c), int(h), int(w), int(layout), gain_ptr, bias_ptr, img_ptr, stream))
 
 
 def linear_to_affine(y_ptr, ldy, n, d, out_ptr, maxdev_ptr, stream):

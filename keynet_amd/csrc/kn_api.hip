@@ -1253,6 +1253,35 @@ int kn_linear_to_u8(const float* x_dev, int64_t ldx, int64_t n, int64_t c, int64
     });
 }
 
+int kn_frames_to_linear(const void* img_dev, int depth, int64_t n, int64_t c, int64_t h, int64_t w, int layout, const float* scale_dev, const float* offset_dev,
+                        float* out_dev, int64_t ldo, int64_t n_cols, void* stream) {
+    return guarded([&]() -> int {
+    KN_HOST_ONLY_GUARD();
+    KN_REQUIRE(n >= 1 && n <= n_cols && n_cols <= ldo, KN_ERR_SHAPE, "1 <= n <= n_cols <= ldo");
+    KN_REQUIRE(c >= 1 && h >= 1 && w >= 1, KN_ERR_SHAPE, "empty frame");
+    KN_REQUIRE(c <= INT32_MAX && h <= INT32_MAX && w <= INT32_MAX && h * w <= INT64_MAX / c, KN_ERR_INVALID, "frame size out of range");
+    KN_REQUIRE(layout == 0 || layout == 1, KN_ERR_INVALID, "layout is 0 (NCHW) or 1 (NHWC)");
+    KN_REQUIRE(depth == 8 || depth == 16, KN_ERR_UNSUPPORTED, "depth is 8 or 16 bits");
+    KN_REQUIRE(img_dev && out_dev, KN_ERR_INVALID, "NULL pointer");
+    KN_REQUIRE(depth == 8 || ((uintptr_t)img_dev) % 2 == 0, KN_ERR_INVALID, "16-bit frames at an odd address");
+    return frames_to_linear(img_dev, depth, n, c, h, w, layout, scale_dev, offset_dev, out_dev, ldo, n_cols, reinterpret_cast<hipStream_t>(stream));
+    });
+}
+
+int kn_linear_to_u16(const float* x_dev, int64_t ldx, int64_t n, int64_t c, int64_t h, int64_t w, int layout, const float* gain_dev, const float* bias_dev, uint16_t* img_dev,
+                     void* stream) {
+    return guarded([&]() -> int {
+    KN_HOST_ONLY_GUARD();
+    KN_REQUIRE(n >= 1 && n <= ldx, KN_ERR_SHAPE, "1 <= n <= ldx");
+    KN_REQUIRE(c >= 1 && h >= 1 && w >= 1, KN_ERR_SHAPE, "empty frame");
+    KN_REQUIRE(c <= INT32_MAX && h <= INT32_MAX && w <= INT32_MAX && h * w <= INT64_MAX / c, KN_ERR_INVALID, "frame size out of range");
+    KN_REQUIRE(layout == 0 || layout == 1, KN_ERR_INVALID, "layout is 0 (NCHW) or 1 (NHWC)");
+    KN_REQUIRE(x_dev && img_dev, KN_ERR_INVALID, "NULL pointer");
+    KN_REQUIRE(((uintptr_t)img_dev) % 2 == 0, KN_ERR_INVALID, "16-bit frames at an odd address");
+    return linear_to_u16(x_dev, ldx, n, c, h, w, layout, gain_dev, bias_dev, img_dev, reinterpret_cast<hipStream_t>(stream));
+    });
+}
+
 int kn_linear_to_affine(const float* y_dev, int64_t ldy, int64_t n, int64_t d, float* out_dev, float* maxdev_dev, void* stream) {
     return guarded([&]() -> int {
     KN_HOST_ONLY_GUARD();

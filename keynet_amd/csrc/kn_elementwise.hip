@@ -4,6 +4,8 @@
 //   linear_to_affine    keynet/torch.py:71-77: [d+1, n] -> [n, d], plus max |last row - 1| for the host-side ValueError
 //   u8_to_linear        the sensor's ingest of raw frames (keynet/system.py:183-201 + keynet/torch.py:65-68): n uint8 frames, NCHW or NHWC -> [d+1, n_cols] feature-major, padded
 //   linear_to_u8        the sensor's egress (keynet/system.py:173-181, 223-228 + keynet/torch.py:71-77): n columns of a [d+1, ldx] block -> n uint8 frames, NCHW or NHWC, saturate(rint(gain * x + bias))
+//   frames_to_linear    the dequantising ingest of ENCRYPTED frames (no reference counterpart: the wire between keynet/system.py:173-181 on the sensor and the key-net): n uint8 or uint16 frames -> [d+1, n_cols], offset + scale * (float)img per image
+//   linear_to_u16       linear_to_u8 at 16 bits: saturate(rint(gain * x + bias)) into uint16 frames
 //   column_range        the per-image minimum and maximum mat2gray takes (keynet/sparse.py:27), NaN skipped
 //   planes_to_columns / columns_to_planes   the two layout changes around the spatial CSR of the narrow split route (no reference counterpart)
 // Transposes go through a padded 64x65 LDS tile so both the global read and the global write are coalesced.
@@ -218,6 +220,128 @@ int u8_to_linear(const uint8_t* img, int64_t n, int64_t c, int64_t h, int64_t w,
     return KN_OK;
 }
 
+// kn_frames_to_linear: the dequantising ingest -- kn_u8_to_linear for frames of T = uint8_t or uint16_t with a per-image affine on the way out,
+// out = offset[b] + scale[b] * (float)img (a separate multiply and add; either pointer NULL: that statement is left out).  The structure is u8_to_linear_kernel's, with
+// the tile kept as stored integers: FR_POS<T> = 256 / sizeof(T) frame positions x U8_COLS = 64 images, so an image's row is again 256 + 4 bytes = 65 dwords and the bank
+// argument above carries over: image i starts in bank i (mod 32), the dword stores of a wavefront fall on consecutive banks, and on the way out the four q of one g read one
+// dword (bytes) or two neighbouring dwords (halfwords) of 8 distinct rows -- 8 or 16 distinct banks per instruction.
+//   in    a wavefront reads 256 contiguous bytes of one frame per instruction: a dword per lane (four bytes or two halfwords) where the frame size in bytes and the base
+//         are multiples of four, one element per lane otherwise (at 16 bits the 256 threads then cover two images per step).
+//   out   lane (g, q) owns images 4g .. 4g + 3; it loads their four scale / offset pairs once, before the pass loop, converts (exact at both depths), multiplies, adds and
+//         stores one float4 along the batch.  A pad column (n <= b < n_cols) is +0.0f whatever the offset: a zero image, not a black one.
+template <typename T>
+constexpr int FR_POS = U8_POS / (int)sizeof(T);
+
+template <typename T, bool NHWC, bool L4, bool V4>
+__global__ __launch_bounds__(256) void frames_to_linear_kernel(const T* __restrict__ img, int64_t n, int64_t D, int c, int64_t hw, const float* __restrict__ scale,
+                                                               const float* __restrict__ offset, float* __restrict__ out, int64_t ldo, int64_t n_cols) {
+    constexpr int POS = FR_POS<T>, EPD = 4 / (int)sizeof(T);                        // positions of a tile, elements per dword
+    __shared__ __attribute__((aligned(16))) uint8_t tile[U8_COLS * U8_STRIDE];
+    const int64_t p0 = (int64_t)blockIdx.x * POS;
+    const int64_t b0 = (int64_t)blockIdx.y * U8_COLS;
+    const int lane = (int)threadIdx.x & 63, wave = (int)threadIdx.x >> 6;
+    const int cols = (n_cols - b0 < U8_COLS) ? (int)(n_cols - b0) : U8_COLS;        // columns of this tile that exist: >= 1
+    // in: images beyond n (the pad columns) are zero elements
+    if (L4) {
+        const int64_t p = p0 + EPD * lane;
+        for (int i = wave; i < cols; i += 4) {
+            uint32_t v = 0;
+            if (b0 + i < n && p < D) v = *reinterpret_cast<const uint32_t*>(img + (b0 + i) * D + p);      // D % EPD == 0: a dword is inside the frame or outside it
+            *reinterpret_cast<uint32_t*>(tile + i * U8_STRIDE + 4 * lane) = v;
+        }
+    } else {
+        const int pl = (int)threadIdx.x % POS;
+        const int64_t p = p0 + pl;
+        for (int i = (int)threadIdx.x / POS; i < cols; i += 256 / POS) {
+            T v = 0;
+            if (b0 + i < n && p < D) v = img[(b0 + i) * D + p];
+            *reinterpret_cast<T*>(tile + i * U8_STRIDE + pl * (int)sizeof(T)) = v;
+        }
+    }
+    __syncthreads();
+    // out
+    const int g = lane >> 2, q = lane & 3;
+    const int64_t b = b0 + 4 * g;
+    if (4 * g < cols) {
+        const bool mul = scale != nullptr, add = offset != nullptr;
+        bool live[4];
+        float sc[4], of[4];
+#pragma unroll
+        for (int k = 0; k < 4; k++) {
+            live[k] = b + k < n;
+            sc[k] = (mul && live[k]) ? scale[b + k] : 1.0f;
+            of[k] = (add && live[k]) ? offset[b + k] : 0.0f;
+        }
+        for (int pass = 0; pass < POS / 16; pass++) {
+            const int pl = pass * 16 + wave * 4 + q;
+            const int64_t p = p0 + pl;
+            if (p >= D) break;                              // positions ascend with the pass
+            int64_t r = p;
+            if (NHWC) {
+                const int64_t pix = p / c;
+                r = (p - pix * c) * hw + pix;
+            }
+            const uint8_t* t = tile + (4 * g) * U8_STRIDE + pl * (int)sizeof(T);
+            float v[4];
+#pragma unroll
+            for (int k = 0; k < 4; k++) {
+                float x = 0.0f;
+                if (live[k]) {
+                    x = (float)*reinterpret_cast<const T*>(t + k * U8_STRIDE);
+                    if (mul) x = __fmul_rn(sc[k], x);
+                    if (add) x = __fadd_rn(x, of[k]);
+                }
+                v[k] = x;
+            }
+            u8_store_quad<V4>(out + r * ldo, b, n_cols, make_float4(v[0], v[1], v[2], v[3]));
+        }
+    }
+    if (blockIdx.x == 0 && (int)threadIdx.x < 16 && 4 * (int)threadIdx.x < cols) {       // the ones row: 1.0 under an image, 0.0 under a pad column
+        const int64_t bq = b0 + 4 * (int)threadIdx.x;
+        float4 v;
+        v.x = (bq < n) ? 1.0f : 0.0f;
+        v.y = (bq + 1 < n) ? 1.0f : 0.0f;
+        v.z = (bq + 2 < n) ? 1.0f : 0.0f;
+        v.w = (bq + 3 < n) ? 1.0f : 0.0f;
+        u8_store_quad<V4>(out + D * ldo, bq, n_cols, v);
+    }
+}
+
+template <typename T>
+static int frames_to_linear_t(const T* img, int64_t n, int64_t c, int64_t h, int64_t w, int layout, const float* scale, const float* offset, float* out, int64_t ldo,
+                              int64_t n_cols, hipStream_t s) {
+    const int64_t D = c * h * w;
+    const int64_t ptiles = (D + FR_POS<T> - 1) / FR_POS<T>, ctiles = (n_cols + U8_COLS - 1) / U8_COLS;
+    if (ptiles > INT32_MAX || ctiles > 65535) return fail(KN_ERR_UNSUPPORTED, "kn_frames_to_linear: more tiles than one launch grid holds");
+    const bool nhwc = layout == 1 && c > 1;                // one channel: the two layouts are the same elements
+    const bool l4 = (D * (int64_t)sizeof(T)) % 4 == 0 && ((uintptr_t)img) % 4 == 0;
+    const bool v4 = ldo % 4 == 0 && ((uintptr_t)out) % 16 == 0;
+    const dim3 grid((unsigned)ptiles, (unsigned)ctiles);
+    const char* name = sizeof(T) == 1 ? "frames_to_linear_kernel<u8>" : "frames_to_linear_kernel<u16>";
+#define KN_FR_LAUNCH(NHWC, L4, V4) \
+    KN_LAUNCH(name, (frames_to_linear_kernel<T, NHWC, L4, V4>), grid, dim3(256), 0, s, img, n, D, (int)c, h * w, scale, offset, out, ldo, n_cols)
+    if (nhwc) {
+        if (l4 && v4) KN_FR_LAUNCH(true, true, true);
+        else if (l4) KN_FR_LAUNCH(true, true, false);
+        else if (v4) KN_FR_LAUNCH(true, false, true);
+        else KN_FR_LAUNCH(true, false, false);
+    } else {
+        if (l4 && v4) KN_FR_LAUNCH(false, true, true);
+        else if (l4) KN_FR_LAUNCH(false, true, false);
+        else if (v4) KN_FR_LAUNCH(false, false, true);
+        else KN_FR_LAUNCH(false, false, false);
+    }
+#undef KN_FR_LAUNCH
+    KN_HIP(hipGetLastError());
+    return KN_OK;
+}
+
+int frames_to_linear(const void* img, int depth, int64_t n, int64_t c, int64_t h, int64_t w, int layout, const float* scale, const float* offset, float* out, int64_t ldo,
+                     int64_t n_cols, hipStream_t s) {
+    if (depth == 8) return frames_to_linear_t(static_cast<const uint8_t*>(img), n, c, h, w, layout, scale, offset, out, ldo, n_cols, s);
+    return frames_to_linear_t(static_cast<const uint16_t*>(img), n, c, h, w, layout, scale, offset, out, ldo, n_cols, s);
+}
+
 // kn_linear_to_u8: kn_u8_to_linear run backwards -- the first n columns of a feature-major block [D (+ the ones row, not read), ldx] -> n uint8 frames of D bytes,
 // img = saturate(rint(gain[b] * x + bias[b])).  The same tile: U8_POS = 256 OUTPUT byte positions x U8_COLS = 64 images, parked in LDS as BYTES, tile[image][position],
 // an image's row 260 bytes = 65 dwords.
@@ -335,6 +459,129 @@ int linear_to_u8(const float* x, int64_t ldx, int64_t n, int64_t c, int64_t h, i
         else KN_L8_LAUNCH(false, false, false);
     }
 #undef KN_L8_LAUNCH
+    KN_HIP(hipGetLastError());
+    return KN_OK;
+}
+
+// kn_linear_to_u16: kn_linear_to_u8 at 16 bits, statement for statement, saturating at 65535.  The same LDS tile at U16_POS = 128 output positions x 64 images: an image's
+// row is 128 halfwords + 4 bytes = 65 dwords.
+//   in    as linear_to_u8_kernel: lane (g, q) owns images 4g .. 4g + 3 at the four positions of quad j = 16 * pass + 4 * wave + q (two passes), one float4 along the batch
+//         per position; multiply, add (separate roundings), rint, saturate.  The four positions of an image are packed into TWO dwords, 2j and 2j + 1 of the image's row:
+//         dword (4g + k) * 65 + 2j (+ 1) is in bank 4g + k + 2j (+ 1), and over a half-wave 4g + 2q takes the 16 even residues twice -- a 2-way conflict on each of
+//         the eight store instructions of a pass, against twenty float4 loads and stores of global memory per lane: the kernel stays at the rate of its HBM traffic.
+//   out   a wavefront writes 256 contiguous bytes of one frame: a dword (two halfwords) per lane where 2 * D and the base are multiples of four, one halfword per lane
+//         otherwise (the 256 threads then cover two images per step).
+// No workspace; every address is formed in 64 bits; halfwords outside the n * D are not touched.
+constexpr int U16_POS = U8_POS / 2;
+
+__device__ __forceinline__ uint32_t u16_saturate(float t) {
+    const float r = rintf(t);                               // v_rndne_f32: ties to even
+    return (t != t) ? 0u : (uint32_t)(int)fminf(65535.0f, fmaxf(0.0f, r));
+}
+
+template <bool NHWC, bool V4, bool S4>
+__global__ __launch_bounds__(256) void linear_to_u16_kernel(const float* __restrict__ x, int64_t ldx, int64_t n, int64_t D, int c, int64_t hw, const float* __restrict__ gain,
+                                                            const float* __restrict__ bias, uint16_t* __restrict__ img) {
+    __shared__ __attribute__((aligned(16))) uint8_t tile[U8_COLS * U8_STRIDE];
+    const int64_t p0 = (int64_t)blockIdx.x * U16_POS;
+    const int64_t b0 = (int64_t)blockIdx.y * U8_COLS;
+    const int lane = (int)threadIdx.x & 63, wave = (int)threadIdx.x >> 6;
+    const int cols = (n - b0 < U8_COLS) ? (int)(n - b0) : U8_COLS;                  // images of this tile: >= 1
+    // in
+    const int g = lane >> 2, q = lane & 3;
+    const int64_t b = b0 + 4 * g;
+    if (4 * g < cols) {
+        float gn[4], bs[4];
+#pragma unroll
+        for (int k = 0; k < 4; k++) {
+            gn[k] = (gain && b + k < n) ? gain[b + k] : 1.0f;
+            bs[k] = (bias && b + k < n) ? bias[b + k] : 0.0f;
+        }
+        for (int pass = 0; pass < U16_POS / 64; pass++) {
+            const int j = pass * 16 + wave * 4 + q;
+            const int64_t p = p0 + 4 * j;
+            if (p >= D) break;                              // positions ascend with the pass
+            int64_t pix = 0;
+            int ch = 0;
+            if (NHWC) {
+                if (D <= (int64_t)INT32_MAX) {
+                    const uint32_t px = (uint32_t)p / (uint32_t)c;
+                    pix = px;
+                    ch = (int)((uint32_t)p - px * (uint32_t)c);
+                } else {
+                    pix = p / c;
+                    ch = (int)(p - pix * c);
+                }
+            }
+            uint32_t word[4][2] = {{0u, 0u}, {0u, 0u}, {0u, 0u}, {0u, 0u}};
+#pragma unroll
+            for (int i = 0; i < 4; i++) {
+                float4 v = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
+                if (p + i < D) {
+                    const int64_t r = NHWC ? (int64_t)ch * hw + pix : p + i;
+                    const float* row = x + r * ldx;
+                    if (V4 && b + 4 <= n) {
+                        v = *reinterpret_cast<const float4*>(row + b);
+                    } else {
+                        v.x = row[b];                                               // b < n: 4g < cols
+                        if (b + 1 < n) v.y = row[b + 1];
+                        if (b + 2 < n) v.z = row[b + 2];
+                        if (b + 3 < n) v.w = row[b + 3];
+                    }
+                }
+                word[0][i >> 1] |= u16_saturate(__fadd_rn(__fmul_rn(gn[0], v.x), bs[0])) << (16 * (i & 1));
+                word[1][i >> 1] |= u16_saturate(__fadd_rn(__fmul_rn(gn[1], v.y), bs[1])) << (16 * (i & 1));
+                word[2][i >> 1] |= u16_saturate(__fadd_rn(__fmul_rn(gn[2], v.z), bs[2])) << (16 * (i & 1));
+                word[3][i >> 1] |= u16_saturate(__fadd_rn(__fmul_rn(gn[3], v.w), bs[3])) << (16 * (i & 1));
+                if (NHWC && ++ch == c) {
+                    ch = 0;
+                    pix++;
+                }
+            }
+#pragma unroll
+            for (int k = 0; k < 4; k++) {                                           // images cols .. 4g + 3: rows of the tile nothing reads
+                uint32_t* t = reinterpret_cast<uint32_t*>(tile + (4 * g + k) * U8_STRIDE + 8 * j);
+                t[0] = word[k][0];
+                t[1] = word[k][1];
+            }
+        }
+    }
+    __syncthreads();
+    // out
+    if (S4) {
+        const int64_t p = p0 + 2 * lane;
+        if (p < D)
+            for (int i = wave; i < cols; i += 4) *reinterpret_cast<uint32_t*>(img + (b0 + i) * D + p) = *reinterpret_cast<const uint32_t*>(tile + i * U8_STRIDE + 4 * lane);
+    } else {
+        const int pl = (int)threadIdx.x & (U16_POS - 1);
+        const int64_t p = p0 + pl;
+        if (p < D)
+            for (int i = (int)threadIdx.x / U16_POS; i < cols; i += 256 / U16_POS) img[(b0 + i) * D + p] = *reinterpret_cast<const uint16_t*>(tile + i * U8_STRIDE + 2 * pl);
+    }
+}
+
+int linear_to_u16(const float* x, int64_t ldx, int64_t n, int64_t c, int64_t h, int64_t w, int layout, const float* gain, const float* bias, uint16_t* img, hipStream_t s) {
+    const int64_t D = c * h * w;
+    const int64_t ptiles = (D + U16_POS - 1) / U16_POS, ctiles = (n + U8_COLS - 1) / U8_COLS;
+    if (ptiles > INT32_MAX || ctiles > 65535) return fail(KN_ERR_UNSUPPORTED, "kn_linear_to_u16: more tiles than one launch grid holds");
+    const bool nhwc = layout == 1 && c > 1;                // one channel: the two layouts are the same elements
+    const bool v4 = ldx % 4 == 0 && ((uintptr_t)x) % 16 == 0;
+    const bool s4 = D % 2 == 0 && ((uintptr_t)img) % 4 == 0;
+    const dim3 grid((unsigned)ptiles, (unsigned)ctiles);
+#define KN_L16_LAUNCH(NHWC, V4, S4) \
+    KN_LAUNCH("linear_to_u16_kernel<" #NHWC "," #V4 "," #S4 ">", (linear_to_u16_kernel<NHWC, V4, S4>), grid, dim3(256), 0, s, x, ldx, n, D, (int)c, h * w, gain, bias, img)
+    if (nhwc) {
+        if (v4 && s4) KN_L16_LAUNCH(true, true, true);
+        else if (v4) KN_L16_LAUNCH(true, true, false);
+        else if (s4) KN_L16_LAUNCH(true, false, true);
+        else KN_L16_LAUNCH(true, false, false);
+    } else {
+        if (v4 && s4) KN_L16_LAUNCH(false, true, true);
+        else if (v4) KN_L16_LAUNCH(false, true, false);
+        else if (s4) KN_L16_LAUNCH(false, false, true);
+        else KN_L16_LAUNCH(false, false, false);
+    }
+#undef KN_L16_LAUNCH
     KN_HIP(hipGetLastError());
     return KN_OK;
 }

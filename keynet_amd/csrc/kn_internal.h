@@ -636,6 +636,9 @@ int dense_reduce(const float* z, int64_t ldz, int64_t outs, int64_t splits, cons
 int affine_to_linear(const float* x, int64_t n, int64_t d, float* out, int64_t ldo, hipStream_t s);
 int u8_to_linear(const uint8_t* img, int64_t n, int64_t c, int64_t h, int64_t w, int layout, float* out, int64_t ldo, int64_t n_cols, hipStream_t s);
 int linear_to_u8(const float* x, int64_t ldx, int64_t n, int64_t c, int64_t h, int64_t w, int layout, const float* gain, const float* bias, uint8_t* img, hipStream_t s);
+int frames_to_linear(const void* img, int depth, int64_t n, int64_t c, int64_t h, int64_t w, int layout, const float* scale, const float* offset, float* out, int64_t ldo,
+                     int64_t n_cols, hipStream_t s);
+int linear_to_u16(const float* x, int64_t ldx, int64_t n, int64_t c, int64_t h, int64_t w, int layout, const float* gain, const float* bias, uint16_t* img, hipStream_t s);
 int column_range(const float* x, int64_t rows, int64_t ld, int64_t n_vecs, float* lo, float* hi, hipStream_t s);
 int linear_to_affine(const float* y, int64_t ldy, int64_t n, int64_t d, float* out, float* maxdev, hipStream_t s);
 int planes_to_columns(const float* in, int64_t plane_stride, int64_t ld, int64_t planes, int64_t rows, int64_t n_vecs, float* out, int64_t ld_out, hipStream_t s);

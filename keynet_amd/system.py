@@ -288,6 +288,41 @@ class KeyedModel(object):
         """The normalised `narrow64` of a batch of n images, as NarrowForm.keywords() hands it on: 'mfma' beyond NARROW32_MAX images only (at fewer, narrow64='mfma' is exactly narrow64=True, i.e. narrow32), else a bool."""
         return 'mfma' if (narrow64 == 'mfma' and n > ksp.NARROW32_MAX) else bool(narrow64)
 
+    def frame_shape(self):
+        """(C, H, W) of the images this key-net takes: the input shape of its first keyed layer."""
+        keyed = self._keyed()
+        shape = tuple(int(v) for v in keyed[0]._inshape)[-3:] if keyed and keyed[0]._inshape is not None else ()
+        if len(shape) != 3:
+            raise ValueError('this key-net does not record the shape of its input images')
+        return shape
+
+    def frames_pad_to(self, narrow=False):
+        """What an ingest pads a batch to so that _prepare takes the block in place: whole BATCH_TILE tiles on the wide path of a tiled-conv key-net, otherwise nothing."""
+        wide_tiled = not narrow and any(isinstance(c.W, ksp.Conv2dTiledMatrix) for c in self._keyed())
+        return int(self.BATCH_TILE) if wide_tiled else 1
+
+    def check_cipher_frames(self, cipher_frames, lo, hi, layout='NHWC'):
+        """n of a batch of quantised encrypted frames (uint8 | uint16, this key-net's image shape) with their ranges lo, hi: float32 [n] on the frames' device.
+        ValueError otherwise.  No GPU call."""
+        (n, chw) = ktorch.frame_shape(cipher_frames, layout, ktorch.FRAME_DTYPES)
+        if chw != self.frame_shape():
+            raise ValueError('frames of shape (C, H, W) = %s do not fit the key-net\'s input %s' % (str(chw), str(self.frame_shape())))
+        ktorch.check_range(cipher_frames, lo, hi, n)
+        return n
+
+    def forward_frames(self, cipher_frames, lo, hi, layout='NHWC', **keywords):
+        """Quantised ENCRYPTED frames on the device (what KeyedSensor.encrypt_to_frames returns: uint8 | uint16 [n, H, W, C], or [n, C, H, W] with layout='NCHW', and
+        their ranges lo, hi: float32 [n]) -> [n, classes+1]: the server's call.  It needs no sensor and no image key: the ranges are those of the encrypted images.
+        ktorch.gray_inverse (levels from the frames' dtype), the dequantising ingest ktorch.frames_to_linear (padded to whole BATCH_TILE tiles on the wide path of a
+        tiled-conv key-net, as StreamedForward's), then forward_linear with `keywords`.  ValueError for a wrong dtype, rank, layout or shape, or for lo / hi that are not
+        float32 [n] on the frames' device, before any GPU call."""
+        n = self.check_cipher_frames(cipher_frames, lo, hi, layout)
+        if not cipher_frames.is_cuda:
+            raise ValueError('forward_frames takes frames that are on the device (StreamedForward brings host frames there)')
+        (scale, offset) = ktorch.cipher_range(cipher_frames, lo, hi, n)
+        x = ktorch.frames_to_linear(cipher_frames, layout=layout, pad_to=self.frames_pad_to(bool(keywords.get('narrow'))), scale=scale, offset=offset)
+        return self.forward_linear(x, **keywords)[:n]
+
     def _prepare64(self, x):
         """(x, windows) of a narrow64='mfma' forward of 33 .. 64 images: one feature-major float32 device block of NARROW64_MAX columns, the images beyond the batch zero
         (the straight-line loaders of the 64-column tile take whole aligned tiles, and the stores are wide).  _prepare is not involved."""
@@ -867,6 +902,43 @@ class KeyedSensor(klayer.KeyedLayer):
         images.  Stateless: the loaded tensor of this sensor is neither read nor changed.  ValueError for frames that are not the sensor's shape, before any GPU call."""
         self.check_frames(frames, layout)
         return self.forward(ktorch.frames_to_linear(frames, layout=layout, pad_to=pad_to))
+
+    def encrypt_to_frames(self, frames, layout='NHWC', depth=8, range=None):
+        """Plaintext uint8 frames on the device -> (cipher_frames, lo, hi), all on the device: the ENCRYPTED images as quantised frames of `depth` = 8 | 16 bits
+        (torch.uint8 | torch.uint16, the layout of `frames`) and the float32 [n] ranges they were quantised over -- the wire format between this sensor and a server that
+        holds only the keyed model (KeyedModel.forward_frames, StreamedForward(frames='cipher8' | 'cipher16')); the batch form of save()'s picture
+        (keynet/system.py:173-181) without a private image key.  encrypt_frames, then the range: range=None takes every encrypted image's own minimum and maximum
+        (kn_column_range); range=(lo, hi) is ONE fixed range for every image -- a real converter has one, and it leaks nothing per image; values outside it saturate.
+        Then ktorch.gray_affine(levels = 2^depth - 1) and ktorch.linear_to_frames(depth).  Under a permutation image key range=(0, 255) stores the encrypted block's own
+        bytes.  Stateless, like encrypt_frames.  ValueError for frames that are not the sensor's shape, another depth or a range that is not two finite numbers lo < hi,
+        before any GPU call."""
+        n = self.check_frames(frames, layout)
+        if depth not in ktorch.GRAY_LEVELS:
+            raise ValueError('invalid depth %s: 8 or 16 bits' % str(depth))
+        if range is not None:
+            try:
+                (rlo, rhi) = (float(range[0]), float(range[1]))
+                fixed = len(range) == 2 and np.isfinite(rlo) and np.isfinite(rhi) and rlo < rhi
+            except (TypeError, ValueError, IndexError):
+                fixed = False
+            if not fixed:
+                raise ValueError('range must be None or two finite numbers (lo, hi) with lo < hi, not %s' % str(range))
+        x = self.encrypt_frames(frames, layout=layout)
+        if range is None:
+            (lo, hi) = ktorch.column_range(x)
+        else:
+            (lo, hi) = (torch.full((n,), rlo, dtype=torch.float32, device=x.device), torch.full((n,), rhi, dtype=torch.float32, device=x.device))
+        (gain, bias) = ktorch.gray_affine(lo, hi, ktorch.GRAY_LEVELS[depth])
+        return (ktorch.linear_to_frames(x, tuple(self._inshape[1:]), layout=layout, gain=gain, bias=bias, depth=depth), lo, hi)
+
+    def decrypt_from_frames(self, cipher_frames, lo, hi, layout='NHWC'):
+        """What encrypt_to_frames returns -> plaintext uint8 frames on the device: the dequantising ingest (ktorch.gray_inverse, ktorch.frames_to_linear; the depth is
+        the frames' dtype), then decrypt_frames.  Under a permutation image key and range=(0, 255) the round trip is exact; otherwise to within the quantisation of the
+        encrypted range, seen through the decrypt key.  ValueError for frames that are not the sensor's shape or ranges that are not float32 [n] on the frames' device,
+        before any GPU call."""
+        n = self.check_frames(cipher_frames, layout, ktorch.FRAME_DTYPES)
+        (scale, offset) = ktorch.cipher_range(cipher_frames, lo, hi, n)
+        return self.decrypt_frames(ktorch.frames_to_linear(cipher_frames, layout=layout, scale=scale, offset=offset), layout=layout)
 
     def decrypt(self):
         assert self.isloaded(), 'Load image first'

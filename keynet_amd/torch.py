@@ -34,15 +34,21 @@ def affine_to_linear(x):
 LAYOUTS = ('NCHW', 'NHWC')      # the `layout` strings of frames_to_linear, in the order of kn_u8_to_linear's codes
 
 
+FRAME_DTYPES = (torch.uint8, torch.uint16)      # the stored integers of a quantised frame; their depth in bits is 8 * itemsize
+GRAY_LEVELS = {8: 255, 16: 65535}               # the top gray level of a depth
+
+
 def frame_shape(frames, layout='NHWC', dtype=torch.uint8):
-    """(n, (C, H, W)) of a batch of frames [n, H, W, C] (layout 'NHWC') or [n, C, H, W] ('NCHW'); ValueError for another layout string, rank or dtype, or an empty batch.
+    """(n, (C, H, W)) of a batch of frames [n, H, W, C] (layout 'NHWC') or [n, C, H, W] ('NCHW'); ValueError for another layout string, rank or dtype (one, or a tuple of
+    admissible ones), or an empty batch.
     Touches no GPU (what frames_to_linear, KeyedSensor.encrypt_frames and StreamedForward check their arguments with)."""
     if layout not in LAYOUTS:
         raise ValueError('invalid layout "%s": one of %s' % (str(layout), ', '.join(LAYOUTS)))
     if not isinstance(frames, torch.Tensor):
         raise ValueError('frames must be a torch tensor, not %s' % type(frames).__name__)
-    if frames.dtype != dtype:
-        raise ValueError('frames must be %s, not %s' % (dtype, frames.dtype))
+    dtypes = dtype if isinstance(dtype, tuple) else (dtype,)
+    if frames.dtype not in dtypes:
+        raise ValueError('frames must be %s, not %s' % (' or '.join(str(d) for d in dtypes), frames.dtype))
     if frames.dim() != 4:
         raise ValueError('frames must be [n, %s], not a tensor of rank %d' % ('H, W, C' if layout == 'NHWC' else 'C, H, W', frames.dim()))
     if min(frames.shape) < 1:
@@ -51,22 +57,29 @@ def frame_shape(frames, layout='NHWC', dtype=torch.uint8):
     return (n, (c, a, b) if layout == 'NHWC' else (a, b, c))
 
 
-def frames_to_linear(frames, layout='NHWC', pad_to=1):
-    """uint8 frames on the device, [n, H, W, C] (layout 'NHWC': a camera's order) or [n, C, H, W] ('NCHW') -> [n_cols, C*H*W+1] float32 with a trailing ones
+def frames_to_linear(frames, layout='NHWC', pad_to=1, scale=None, offset=None):
+    """uint8 or uint16 frames on the device, [n, H, W, C] (layout 'NHWC': a camera's order) or [n, C, H, W] ('NCHW') -> [n_cols, C*H*W+1] float32 with a trailing ones
     column, n_cols = n rounded up to a multiple of `pad_to`; the rows beyond n are zero images (all zero, the ones column included: what KeyedModel._prepare
     pads a batch with).  Like the device branch of affine_to_linear the result is the transposed VIEW of a fresh feature-major [D+1, n_cols] block; its first n
-    rows are bit-equal to affine_to_linear(frames.permute(0, 3, 1, 2).float()).  One launch of kn_u8_to_linear on the current stream.  ValueError for a wrong
-    dtype, rank or layout string, before any GPU call."""
-    (n, (C, H, W)) = frame_shape(frames, layout)
+    rows are bit-equal to affine_to_linear(frames.permute(0, 3, 1, 2).float()).  `scale`, `offset`: None or device float32 tensors [n], one pair per image
+    (gray_inverse's): the dequantising ingest, feature = scale[b] * frame + offset[b] -- an f32 multiply, then an f32 add; a None leaves its statement out; the zero
+    images stay zero.  One launch on the current stream: kn_u8_to_linear for uint8 frames without `scale` / `offset`, kn_frames_to_linear for everything else.
+    ValueError for a wrong dtype, rank or layout string, before any GPU call."""
+    (n, (C, H, W)) = frame_shape(frames, layout, FRAME_DTYPES)
     if int(pad_to) < 1:
         raise ValueError('pad_to must be a positive number of images, not %s' % str(pad_to))
     if not frames.is_cuda:
         raise ValueError('frames_to_linear takes frames that are on the device (StreamedForward brings host frames there)')
+    (scale, offset) = (_per_image(scale, n, frames.device, 'scale'), _per_image(offset, n, frames.device, 'offset'))
     n_cols = -(-n // int(pad_to)) * int(pad_to)
     fc = frames.contiguous()
     out = torch.empty((C * H * W + 1, n_cols), dtype=torch.float32, device=frames.device)
     with torch.cuda.device(frames.device):
-        _capi.u8_to_linear(fc.data_ptr(), n, C, H, W, LAYOUTS.index(layout), out.data_ptr(), n_cols, n_cols, _stream_ptr())
+        if frames.dtype == torch.uint8 and scale is None and offset is None:
+            _capi.u8_to_linear(fc.data_ptr(), n, C, H, W, LAYOUTS.index(layout), out.data_ptr(), n_cols, n_cols, _stream_ptr())
+        else:
+            _capi.frames_to_linear(fc.data_ptr(), 8 * fc.element_size(), n, C, H, W, LAYOUTS.index(layout), None if scale is None else scale.data_ptr(),
+                                   None if offset is None else offset.data_ptr(), out.data_ptr(), n_cols, n_cols, _stream_ptr())
     return out.t()
 
 
@@ -111,19 +124,43 @@ def column_range(x_linear):
     return (lo, hi)
 
 
-def gray_affine(lo, hi):
-    """(gain, bias) of the gray mapping of images whose ranges are [lo, hi] onto [0, 255]: gain = 255 / (hi - lo), bias = -lo * gain, element-wise on the tensors' own
-    device without a host read (keynet/sparse.py:25-33 with the 255 of the 8-bit image folded in).  Where hi == lo or the range is not finite (an infinite feature, or the
-    (+Inf, -Inf) of an image with no feature to compare) gain = 0 and bias = 0: such an image becomes black.  The reference divides by zero there: its constant image is
-    all NaN."""
+def gray_affine(lo, hi, levels=255):
+    """(gain, bias) of the gray mapping of images whose ranges are [lo, hi] onto [0, levels]: gain = levels / (hi - lo), bias = -lo * gain, element-wise on the tensors' own
+    device without a host read (keynet/sparse.py:25-33 with the 255 of the 8-bit image folded in; levels=65535: a 16-bit image).  Where hi == lo or the range is not finite
+    (an infinite feature, or the (+Inf, -Inf) of an image with no feature to compare) gain = 0 and bias = 0: such an image becomes black.  The reference divides by zero
+    there: its constant image is all NaN."""
     (lo, hi) = (lo.float(), hi.float())
     span = hi - lo
     ok = torch.isfinite(lo) & torch.isfinite(hi) & torch.isfinite(span) & (span > 0)
     (zero, one) = (torch.zeros_like(span), torch.ones_like(span))
-    gain = 255.0 / torch.where(ok, span, one)
+    gain = float(levels) / torch.where(ok, span, one)
     bias = -torch.where(ok, lo, zero) * gain
-    ok = ok & torch.isfinite(gain) & torch.isfinite(bias)                # (a span so small that 255 / span overflows: not a finite range to map either)
+    ok = ok & torch.isfinite(gain) & torch.isfinite(bias)                # (a span so small that levels / span overflows: not a finite range to map either)
     return (torch.where(ok, gain, zero), torch.where(ok, bias, zero))
+
+
+def gray_inverse(lo, hi, levels=255):
+    """(scale, offset) = ((hi - lo) / levels, lo) of the inverse of gray_affine(lo, hi, levels): gray level q of an image whose range is [lo, hi] stands for the feature
+    scale * q + offset.  Element-wise on the tensors' own device without a host read.  A constant image (hi == lo: gray_affine stored it as black) gives (0, lo), so it is
+    restored exactly; a range that is not finite, or empty (hi < lo), gives (0, 0).  Public numbers: the range of an ENCRYPTED image, or one fixed range of the converter."""
+    (lo, hi) = (lo.float(), hi.float())
+    span = hi - lo
+    ok = torch.isfinite(lo) & torch.isfinite(hi) & torch.isfinite(span) & (span >= 0)
+    zero = torch.zeros_like(span)
+    return (torch.where(ok, span, zero) / float(levels), torch.where(ok, lo, zero))
+
+
+def check_range(cipher_frames, lo, hi, n):
+    """ValueError for ranges lo / hi that are not float32 tensors [n] on the device of the n quantised frames they came with.  No GPU call."""
+    for (v, name) in ((lo, 'lo'), (hi, 'hi')):
+        if not isinstance(v, torch.Tensor) or v.dtype != torch.float32 or tuple(v.shape) != (n,) or v.device != cipher_frames.device:
+            raise ValueError('%s must be a float32 tensor of shape [%d] on the device of the frames' % (name, n))
+
+
+def cipher_range(cipher_frames, lo, hi, n):
+    """gray_inverse of the ranges that came with n quantised frames, the levels read from the frames' dtype (check_range first)."""
+    check_range(cipher_frames, lo, hi, n)
+    return gray_inverse(lo, hi, GRAY_LEVELS[8 * cipher_frames.element_size()])
 
 
 def _per_image(v, n, device, name):
@@ -136,12 +173,15 @@ def _per_image(v, n, device, name):
     return v.detach().contiguous()
 
 
-def linear_to_frames(x_linear, inshape, layout='NHWC', gain=None, bias=None):
+def linear_to_frames(x_linear, inshape, layout='NHWC', gain=None, bias=None, depth=8):
     """[n, C*H*W+1] float32 on the device (`inshape` = (C, H, W)) -> uint8 frames on the device, [n, H, W, C] (layout 'NHWC': a viewer's or an encoder's order) or
     [n, C, H, W] ('NCHW'): frame = min(255, max(0, rint(gain[b] * x + bias[b]))), NaN -> 0 -- an f32 multiply, an f32 add, round to nearest even.  `gain`, `bias`: None (1 and
     0: the block's own values) or device float32 tensors [n], one pair per image (gray_affine's).  The inverse of frames_to_linear: linear_to_frames(frames_to_linear(f)) == f.
     The homogeneous column is not read (linear_to_affine is the call that checks it).  One launch of kn_linear_to_u8 on the current stream; the transposed view of a
-    feature-major block is read in place.  ValueError for a wrong layout string, rank, dtype or feature count, or a host tensor, before any GPU call."""
+    feature-major block is read in place.  depth=16: torch.uint16 frames through kn_linear_to_u16, the same rule saturating at 65535.  ValueError for a wrong layout
+    string, depth, rank, dtype or feature count, or a host tensor, before any GPU call."""
+    if depth not in GRAY_LEVELS:
+        raise ValueError('invalid depth %s: 8 or 16 bits' % str(depth))
     if layout not in LAYOUTS:
         raise ValueError('invalid layout "%s": one of %s' % (str(layout), ', '.join(LAYOUTS)))
     if len(tuple(inshape)) != 3 or min(int(v) for v in inshape) < 1:
@@ -150,9 +190,9 @@ def linear_to_frames(x_linear, inshape, layout='NHWC', gain=None, bias=None):
     (n, D) = _check_linear(x_linear, 'linear_to_frames', C * H * W)
     (gain, bias) = (_per_image(gain, n, x_linear.device, 'gain'), _per_image(bias, n, x_linear.device, 'bias'))
     xt = _feature_major(x_linear)
-    out = torch.empty((n, H, W, C) if layout == 'NHWC' else (n, C, H, W), dtype=torch.uint8, device=xt.device)
+    out = torch.empty((n, H, W, C) if layout == 'NHWC' else (n, C, H, W), dtype=torch.uint8 if depth == 8 else torch.uint16, device=xt.device)
     with torch.cuda.device(xt.device):
-        _capi.linear_to_u8(xt.data_ptr(), n, n, C, H, W, LAYOUTS.index(layout), None if gain is None else gain.data_ptr(), None if bias is None else bias.data_ptr(),
+        (_capi.linear_to_u8 if depth == 8 else _capi.linear_to_u16)(xt.data_ptr(), n, n, C, H, W, LAYOUTS.index(layout), None if gain is None else gain.data_ptr(), None if bias is None else bias.data_ptr(),
                            out.data_ptr(), _stream_ptr())
     return out
 
